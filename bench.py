@@ -569,8 +569,9 @@ def hbm_kernel_report(arch, dyn, tag, B, NL, NK, counts, rec_nf):
             'note': 'algorithmic bytes per launch (live sizes) / rocprofv3 AverageNs of the committed statistics of the same command'}
 
 
-def run_sampling(args, workload, device, rank, world, dist, B, n_rec, n_lig, ragged, gemm='f32'):
-    """Steps/s of one sampling workload + the roofline of its dominant kernel.  Returns the result dict (rank 0) ."""
+def run_sampling(args, workload, device, rank, world, dist, B, n_rec, n_lig, ragged, gemm='f32', dump=None):
+    """Steps/s of one sampling workload + the roofline of its dominant kernel.  Returns the result dict (rank 0) .
+    `dump` (a directory): rank 0 writes the outputs of the last timed step there (dump_outputs)."""
     import torch
     from keypoint_diffusion_amd import graph as G
     w = WORKLOADS[workload]
@@ -592,6 +593,10 @@ def run_sampling(args, workload, device, rank, world, dist, B, n_rec, n_lig, rag
     if args.graph:
         with torch.no_grad():
             step_graph = model.capture_step(g, bidx)
+    # dump: what the last timed step hands its caller (the updated ligand coordinates / features and keypoint coordinates),
+    # copied before the t = T state is restored
+    last_timed = args.steps * args.repeats - 1 if dump else None
+    timing, outputs = [False], {}
 
     def step(i):
         si = T - 1 - (i % T)
@@ -599,6 +604,8 @@ def run_sampling(args, workload, device, rank, world, dist, B, n_rec, n_lig, rag
             step_graph.step(si / T, (si + 1) / T)
         else:
             model.sample_p_zs_given_zt(ones * (si / T), ones * ((si + 1) / T), g, bidx)
+        if timing[0] and i == last_timed:
+            outputs.update(lig_x=lig['x_0'].clone(), lig_h=lig['h_0'].clone(), kp_x=kp['x_0'].clone())
         lig['x_0'].copy_(init[0]), lig['h_0'].copy_(init[1]), kp['x_0'].copy_(init[2])
 
     def tail():
@@ -612,12 +619,16 @@ def run_sampling(args, workload, device, rank, world, dist, B, n_rec, n_lig, rag
         torch.cuda.synchronize()
         eng.profile(True)
         rank_info = {}
+        timing[0] = True
         regions = timed_regions(step, 0, args.steps, args.repeats, dist, tail, info=rank_info)
+        timing[0] = False
         kern_ms, launches = eng.profile_read()
         eng.profile(False)
         counts = eng.last_counts()
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(dump, outputs)
     med = statistics.median(regions)
     steps_per_s = world * args.steps / med
     # the event-timed dominant kernel must fit inside the wall time it is part of
@@ -842,6 +853,36 @@ def compact_line(out, full_path=None):
     return line
 
 
+# ---------------------------------------------------------------------------------------------------
+# --dump-outputs DIR: what the timed path computed in its last step, for comparing two builds output by output
+# ---------------------------------------------------------------------------------------------------
+DUMP_LIMIT = 64 << 20          # bytes of array data over all files of one dump
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """Write `arrays` (name -> tensor or ndarray) as `path/<name>.npy`: float64 stays float64, everything else becomes float32.
+    When the arrays together exceed `limit` bytes, every array keeps the same fraction of its elements, chosen by a generator
+    seeded with 0 (flat indices, ascending): the same shapes give the same sample in every run.  Returns the files written."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = np.asarray(a.detach().cpu() if hasattr(a, 'detach') else a)
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(path, exist_ok=True)
+    files = []
+    for name, a in host.items():
+        if total > limit:
+            keep = a.size * limit // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        f = os.path.join(path, f'{name}.npy')
+        np.save(f, a)
+        files.append(f)
+    print(f'bench.py: outputs of the last timed step -> {", ".join(files)}' + (f' (sampled to {limit} bytes of {total})' if total > limit else ''),
+          file=sys.stderr, flush=True)
+    return files
+
+
 def emit(out):
     """Write the full record to the side file (best effort: a read-only tree must not lose the line) and print the compact line."""
     path = None
@@ -924,7 +965,7 @@ def run_train(args, device, rank, world, dist):
             allreduce_gradients(list(model.parameters()))
         clip_grads(model.parameters(), 1.0)
         opt.step()
-        last[0] = losses['l2']
+        last[0] = losses
 
     rank_info = {}
     for i in range(args.warmup):
@@ -935,6 +976,10 @@ def run_train(args, device, rank, world, dist):
     if egnn_prof:
         trainer.profile(True)
     regions = timed_regions(step, 0, args.steps, args.repeats, dist, info=rank_info)
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step hands its caller: the loss terms of KeypointDiffusion.forward and the parameters after the Adam update
+        losses = {f'loss_{k}': v for k, v in last[0].items() if v is not None}
+        dump_outputs(args.dump_outputs, dict(losses, parameters=torch.cat([p.detach().reshape(-1) for p in model.parameters()])))
     if rank == 0:
         med = statistics.median(regions)
         n_steps_total = args.steps * args.repeats
@@ -949,7 +994,7 @@ def run_train(args, device, rank, world, dist):
                                        f'torch.optim.Adam{"(fused=True)" if args.fused_optimizer else ""} + torch.nn.utils.clip_grad_value_'},
                'repeats': {'n': args.repeats, 'ms_per_step': [1e3 * r / args.steps for r in regions], 'statistic': 'median',
                            'spread_pct': 100.0 * (max(regions) - min(regions)) / med},
-               'complex_steps_per_s': world * args.steps / med * B, 'final_l2': float(last[0].detach()),
+               'complex_steps_per_s': world * args.steps / med * B, 'final_l2': float(last[0]['l2'].detach()),
                'ranks_seen': rank_info.get('ranks_seen'), 'per_rank_ms_per_step': rank_info.get('per_rank_ms_per_step')}
         # ---- roofline of the step: executed FLOPs of the denoiser's forward (the same accounting as the sampling lines: first Linears per
         # node) x 3 (backward = one product for the input gradient and one for the weight gradient per forward product) over the step time,
@@ -1021,6 +1066,10 @@ def main():
     ap.add_argument('--ragged', action='store_true', help='pockets 150-600 atoms, ligands 15-35 atoms (configs[4] shape)')
     ap.add_argument('--tools', action='store_true', help='diagnostic run (profiles/tools): KPD_* switches and the TOOLS build of the library are '
                                                          'allowed; the line then carries "attested": false and is not a contract line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
+                         'at most 64 MB; rank 0): ligand coordinates and features and keypoint coordinates of a sampling workload, '
+                         'the loss terms and updated parameters of a training workload')
     args = ap.parse_args()
     training = args.workload.endswith('_train')
     if args.steps is None:
@@ -1080,7 +1129,8 @@ def main():
     n_rec, n_lig = args.n_rec, args.n_lig
     if args.ragged:
         n_rec, n_lig = ragged_sizes(args.batch, rank)
-    out = run_sampling(args, args.workload, device, rank, world, dist, args.batch, n_rec, n_lig, args.ragged, gemm=args.gemm)
+    out = run_sampling(args, args.workload, device, rank, world, dist, args.batch, n_rec, n_lig, args.ragged, gemm=args.gemm,
+                       dump=args.dump_outputs)
     if rank == 0:
         default_line = args.workload == 'egnn_all_atom' and not args.ragged and not args.graph and args.gemm == 'f32'
         if world == 1 and not args.no_cpu_baseline:

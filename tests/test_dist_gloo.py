@@ -41,6 +41,11 @@ def _torchify(o):
     return o
 
 
+# The rank processes below end with dist.monitored_barrier(), gloo's own barrier on CPU tensors: dist.barrier() asks torch for
+# the machine's accelerator first (torch._C._get_accelerator), which opens the GPU in every rank where one is present, and these
+# CPU ranks must not count against the GPU processes a machine admits.
+
+
 def _free_port():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
@@ -62,7 +67,7 @@ def _worker(rank, world, port, q):
         off += N_LIG[i]
     pos, feat = all_gather_ligands(g)
     q.put(_plain((rank, [p.clone() for p in pos], [f.clone() for f in feat])))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -107,7 +112,7 @@ def _grad_worker(rank, world, port, q):
         p.grad = None if i == 3 else torch.randn(p.shape, generator=gen)      # one frozen parameter
     n_buckets = allreduce_gradients(params, bucket_bytes=300 * 1024)          # forces two buckets
     q.put(_plain((rank, n_buckets, [None if p.grad is None else p.grad.clone() for p in params])))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -154,7 +159,7 @@ def _map_worker(rank, world, port, q):
     pos, feat = sharded_map(costs, fn)
     torch.manual_seed(1000 + rank)      # ranks disagree on their generators; the common seed is rank 0's draw
     q.put(_plain((rank, seen, [p.clone() for p in pos], [f.clone() for f in feat], common_seed())))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -255,7 +260,7 @@ def _s8_proc(rank, world, port, q):
     torch.set_num_threads(1)
     dist.init_process_group('gloo', rank=rank, world_size=world)
     q.put(_plain((rank, _s8_rank_body(rank))))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 

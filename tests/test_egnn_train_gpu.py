@@ -205,7 +205,7 @@ def test_training_step_is_bitwise_reproducible():
     assert not diff, diff[:10]
 
 
-def test_recompute_mode_gives_the_same_gradients():
+def test_recompute_mode_gives_the_same_gradients(tmp_path):
     """KPD_TRAIN_STORE=0 (recompute the edge activations in the backward pass instead of keeping them: the low-memory mode) must
     be bit-identical to the default.  The switch is read once per process, so the other mode runs in a child process."""
     import os
@@ -220,14 +220,14 @@ def test_recompute_mode_gives_the_same_gradients():
             'torch.save([p.grad.cpu() for p in model.parameters()], sys.argv[1])\n' % root)
     outs = []
     for mode in ('1', '0'):
-        path = os.path.join(root, 'gpurun_out', f'_grads_store{mode}.pt') if os.path.isdir(os.path.join(root, 'gpurun_out')) else f'/tmp/_grads_store{mode}.pt'
+        path = str(tmp_path / f'_grads_store{mode}.pt')
         subprocess.run([sys.executable, '-c', code, path], check=True, env=dict(os.environ, KPD_TRAIN_STORE=mode), timeout=600)
         outs.append(torch.load(path))
         os.remove(path)
     assert all(torch.equal(a, b) for a, b in zip(*outs))
 
 
-def test_layer_edge_kernels_on_poisoned_workspaces():
+def test_layer_edge_kernels_on_poisoned_workspaces(tmp_path):
     """The forward / backward edge passes of a layer run as one kernel each (k_egnn_edge_train, k_egnn_edge_bwd); their gradients are checked
     against the oracle's autograd above.  Here: a child process runs the same step on NaN-poisoned workspaces (KPD_POISON=1, read once per
     process) and must reproduce the default run's bits -- a read of memory this step has not written would surface as a NaN or as different
@@ -244,8 +244,7 @@ def test_layer_edge_kernels_on_poisoned_workspaces():
             'torch.save([p.grad.cpu() for p in model.parameters()], sys.argv[1])\n' % root)
     outs = []
     for tag, env in (('default', {}), ('poison', {'KPD_POISON': '1'})):
-        base = os.path.join(root, 'gpurun_out') if os.path.isdir(os.path.join(root, 'gpurun_out')) else '/tmp'
-        path = os.path.join(base, f'_grads_{tag}.pt')
+        path = str(tmp_path / f'_grads_{tag}.pt')
         subprocess.run([sys.executable, '-c', code, path], check=True, env=dict(os.environ, **env), timeout=600)
         outs.append(torch.load(path))
         os.remove(path)

@@ -212,7 +212,7 @@ def test_training_step_is_bitwise_reproducible(tag, over, sizes):
     assert all(torch.equal(a, b) for a, b in zip(*runs))
 
 
-def test_chained_kernels_on_poisoned_workspaces():
+def test_chained_kernels_on_poisoned_workspaces(tmp_path):
     """The chained message / node kernels and the batched weight gradients keep their activations, message pieces and gradient staging in
     buffers of the trainer's own.  A child process runs a training step with all of them (and the LDS of every CU) NaN-filled first
     (KPD_POISON=1) and must reproduce the default run's bits: a read of memory this step has not written would surface as a NaN or as
@@ -232,8 +232,7 @@ def test_chained_kernels_on_poisoned_workspaces():
             'torch.save([eh.detach().cpu(), ex.detach().cpu()] + [p.grad.cpu() for p in model.parameters() if p.grad is not None], sys.argv[1])\n' % root)
     outs = []
     for tag, env in (('default', {}), ('poison', {'KPD_POISON': '1'})):
-        base = os.path.join(root, 'gpurun_out') if os.path.isdir(os.path.join(root, 'gpurun_out')) else '/tmp'
-        path = os.path.join(base, f'_gvp_grads_{tag}.pt')
+        path = str(tmp_path / f'_gvp_grads_{tag}.pt')
         subprocess.run([sys.executable, '-c', code, path], check=True, env=dict(os.environ, **env), timeout=600)
         outs.append(torch.load(path))
         os.remove(path)
