@@ -464,6 +464,21 @@ kpd_status kpd_adam_step(const kpd_adam_param *params_dev, int32_t n_params, int
                          double eps, double weight_decay, int64_t step, double clip_value, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Receptor-ligand distance hinge of the training loss.  Replaces the per-complex loop of KeypointDiffusion.forward
+ * (models/ligand_diffuser.py:149-154: dgl.unbatch, then DistanceHingeLoss = torch.cdist + max(thr - d, 0) + sum per complex,
+ * losses/dist_hinge_loss.py) with one segmented launch (csrc/dist_hinge.hip).
+ *   a [n_a,3], a_ptr [S+1]; b [n_b,3], b_ptr [S+1] (all device; segment s = rows [ptr[s], ptr[s+1]) of each side);
+ *   b_ptr == NULL: self mode (B = A, pairs i < j, upstream's DistanceHingeLoss(pos_a) without pos_b; b and grad_b must be NULL).
+ *   Pointers of empty arrays may be NULL (a side with no rows, seg_loss when S == 0).
+ *   Out (device): seg_loss [S] = sum over the segment's pairs of max(threshold - ||a_i - b_j||, 0), total [1] = their sum;
+ *   grad_a [n_a,3] / grad_b [n_b,3] (optional, NULL = not computed) = d total / d a, d total / d b, with torch's subgradients
+ *   (weight 1/2 at d == threshold, 0 at d == 0).  Rows outside every segment are not written.  Fixed-order reductions, no atomics:
+ *   a segment's loss and gradient rows are bitwise independent of the other segments.  No host synchronisation.
+ * ------------------------------------------------------------------------------------- */
+kpd_status kpd_dist_hinge(const float *a, const int32_t *a_ptr, int32_t n_a, const float *b, const int32_t *b_ptr, int32_t n_b, int32_t S,
+                          float threshold, float *seg_loss, float *total, float *grad_a, float *grad_b, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Reverse-diffusion update around the denoiser.  Replaces the elementwise part of
  * KeypointDiffusion.sample_p_zs_given_zt (models/ligand_diffuser.py:515-536):
  *   z_s = z_t / alpha_ts - var_terms * eps + sigma * noise, then ligand-COM removal from

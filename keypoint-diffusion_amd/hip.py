@@ -194,6 +194,7 @@ def lib():
     L.kpd_xyz_scratch_bytes.restype = C.c_int64
     L.kpd_xyz_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kpd_dist_hinge.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5
     _lib = L
     return L
 
@@ -220,6 +221,7 @@ EXPORTS = [
     'kpd_recenc_trainer_reserve', 'kpd_recenc_trainer_forward', 'kpd_recenc_trainer_backward',
     'kpd_recegnn_trainer_create', 'kpd_recegnn_trainer_destroy', 'kpd_recegnn_trainer_bind', 'kpd_recegnn_trainer_reserve',
     'kpd_recegnn_trainer_forward', 'kpd_recegnn_trainer_backward', 'kpd_ot_emd_uniform', 'kpd_sgemm',
+    'kpd_dist_hinge',
 ]
 
 
@@ -944,6 +946,44 @@ def complex_noise(pb: PreparedBatch, width: int, complex_ids: torch.Tensor, seed
     check(lib().kpd_complex_noise(pb.B, _ptr(pb.lig_ptr), int(width), _ptr(complex_ids.contiguous()), int(seed) & (2 ** 64 - 1),
                                   int(step), int(tag), _ptr(out), _stream()))
     return out
+
+
+def dist_hinge(a: torch.Tensor, a_ptr: torch.Tensor, b: Optional[torch.Tensor], b_ptr: Optional[torch.Tensor], threshold: float,
+               grad_a: bool = False, grad_b: bool = False):
+    """Segmented distance hinge (kpd_dist_hinge): a [n_a,3] and b [n_b,3] fp32 GPU tensors split into S segments by the int32 GPU
+    offsets a_ptr / b_ptr [S+1]; b = None is self mode (pairs i < j of each A segment).  Returns (seg_loss [S], total [1],
+    grad_a [n_a,3] or None, grad_b [n_b,3] or None): the unscaled gradients of the total, zero on rows outside every segment."""
+    def pos(t, name):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise KpdError(f'dist_hinge: {name} must be a GPU tensor (the hinge has no CPU implementation)')
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
+            raise KpdError(f'dist_hinge: {name} must be fp32 [n, 3] (got {t.dtype} {tuple(t.shape)})')
+        return t.contiguous()
+
+    def offsets(p, name, dev):
+        if not (isinstance(p, torch.Tensor) and p.device == dev and p.dtype == torch.int32 and p.dim() == 1 and p.numel() >= 1):
+            raise KpdError(f'dist_hinge: {name} must be a 1-D int32 tensor [S+1] on {dev}')
+        return p.contiguous()
+
+    a = pos(a, 'a')
+    a_ptr = offsets(a_ptr, 'a_ptr', a.device)
+    S = a_ptr.numel() - 1
+    if b is not None:
+        b = pos(b, 'b')
+        if b.device != a.device:
+            raise KpdError('dist_hinge: a and b must be on the same device')
+        b_ptr = offsets(b_ptr, 'b_ptr', a.device)
+        if b_ptr.numel() != S + 1:
+            raise KpdError(f'dist_hinge: a_ptr and b_ptr must have the same length (got {S + 1} and {b_ptr.numel()})')
+    elif b_ptr is not None or grad_b:
+        raise KpdError('dist_hinge: self mode (b = None) takes no b_ptr and no grad_b')
+    seg = torch.empty(S, device=a.device, dtype=torch.float32)
+    total = torch.empty(1, device=a.device, dtype=torch.float32)
+    ga = torch.zeros_like(a) if grad_a else None
+    gb = torch.zeros_like(b) if grad_b else None
+    check(lib().kpd_dist_hinge(_ptr(a), _ptr(a_ptr), int(a.shape[0]), _ptr(b), _ptr(b_ptr), int(b.shape[0]) if b is not None else 0, S,
+                               float(threshold), _ptr(seg), _ptr(total), _ptr(ga), _ptr(gb), _stream()))
+    return seg, total, ga, gb
 
 
 def build_rec_graph(rec_x: torch.Tensor, rec_ptr: torch.Tensor, max_rec: int, r: float, res_idx: Optional[torch.Tensor] = None,

@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from . import graph as G
 from . import hip
 from .dynamics import LigRecDynamics
+from .dist_hinge_loss import segmented_dist_hinge
 from .dynamics_gvp import LigRecDynamicsGVP
 from .receptor_encoder_fixed import FixedReceptorEncoder
 from .receptor_encoder import ReceptorEncoder
@@ -180,7 +181,9 @@ class KeypointDiffusion(nn.Module):
 
     # ---- training entry point ----------------------------------------------------------
     def forward(self, complex_graphs, interface_points):
-        """Losses of one batch (ligand_diffuser.py:89-175): {'l2', 'pos', 'feat', 'rec_encoder'}.
+        """Losses of one batch (ligand_diffuser.py:89-175): {'l2', 'pos', 'feat', 'rec_encoder'}, and 'rl_hinge' when
+        rl_dist_threshold > 0 (the receptor-ligand clash penalty of :137-156, `_rl_hinge`; a training loop adds it with its
+        weight, train.py:340-341).
 
         Trainable end to end in all eight shipped configurations and dev_config: the noise prediction is differentiated by the HIP
         backward passes of the denoisers (kpd_egnn_trainer_* / kpd_gvp_trainer_*, with respect to the keypoint positions, features
@@ -188,8 +191,6 @@ class KeypointDiffusion(nn.Module):
         gvp_40kp, kpd_recegnn_trainer_* for egnn_20kp / egnn_40kp), and the optimal-transport encoder loss (rec_encoder_loss.py)
         adds its gradient at the keypoint positions.  With a fixed encoder there are no encoder parameters and that loss is the
         constant 0 (:85-87)."""
-        if self.rl_dist_threshold > 0:
-            raise NotImplementedError('the receptor-ligand hinge loss (rl_dist_threshold > 0) is unused by every shipped config')
         losses = {}
         g = self.normalize(complex_graphs)
         batch_size, device = g.batch_size, g.device
@@ -197,6 +198,9 @@ class KeypointDiffusion(nn.Module):
         g = self.rec_encoder(g, batch_idxs)
         if self.rec_encoder_type == 'fixed':
             batch_idxs = G.get_batch_idxs(g)                  # :106-107: keypoints = receptor atoms now
+        apply_rl_hinge = self.rl_dist_threshold > 0
+        if apply_rl_hinge:
+            init_kp_com = self._kp_mean(g, batch_idxs['kp'])  # :111-112, before any COM removal
         # :115; the exact transport plans are solved on host threads while the denoiser's forward is launched below
         losses['rec_encoder'] = None
         pending = self.rec_encoder_loss_fn.begin(g, interface_points=interface_points)
@@ -212,6 +216,8 @@ class KeypointDiffusion(nn.Module):
             pending.abandon()                # the denoiser raised: do not leave the solver thread running behind the exception
             raise
         losses['rec_encoder'] = pending.finish()
+        if apply_rl_hinge:
+            losses['rl_hinge'] = self._rl_hinge(g, batch_idxs, eps_x_pred, gamma_t, init_kp_com)
         x_loss = (eps['x'] - eps_x_pred).square().sum()
         n_x_loss_terms = eps['x'].numel()
         h_loss = (eps['h'] - eps_h_pred).square().sum()
@@ -227,6 +233,33 @@ class KeypointDiffusion(nn.Module):
         g.nodes['lig'].data['x_0'] = alpha_t * g.nodes['lig'].data['x_0'] + sigma_t * eps['x']
         g.nodes['lig'].data['h_0'] = alpha_t * g.nodes['lig'].data['h_0'] + sigma_t * eps['h']
         return self.remove_com(g, lig_batch_idx, kp_batch_idx, com='ligand')
+
+    def _kp_mean(self, g, kp_batch_idx):
+        """Per-complex mean keypoint position [B,3] (dgl.readout_nodes(..., 'kp', 'mean') without reading the counts back to the host).
+        Detached: the hinge term's keypoint dependence cancels exactly (see `_rl_hinge`)."""
+        x = g.nodes['kp'].data['x_0'].detach()
+        s = torch.zeros(g.batch_size, 3, dtype=x.dtype, device=x.device).index_add_(0, kp_batch_idx, x)
+        return s / g.batch_num_nodes('kp').clamp(min=1).to(x.dtype)[:, None]
+
+    def _rl_hinge(self, g, batch_idxs, eps_x_pred, gamma_t, init_kp_com):
+        """sum_b sum_{i,j} max(thr - ||x_hat_i - r_j||, 0) over the ligand atoms i and receptor atoms j of every complex
+        (ligand_diffuser.py:137-156), as one segmented kernel launch (kpd_dist_hinge) instead of a loop over dgl.unbatch.
+        x_hat = (z - sigma_t eps_x_pred) / alpha_t is the denoised ligand (denoised_representation, :221-230), moved back into the
+        receptor's frame the way upstream does it: minus the current keypoint mean, plus the keypoint mean before COM removal.  Both
+        means are shifts by the ligand COMs removed before and after noising, so the term reaches the parameters only through
+        eps_x_pred; the keypoint means are detached (their autograd contributions cancel exactly upstream too).  The graph is not
+        modified.  With a fixed encoder the receptor nodes are gone (receptor_encoder_fixed.py) and the term is a differentiable 0."""
+        lig_b, kp_b = batch_idxs['lig'], batch_idxs['kp']
+        alpha_t = self.alpha(gamma_t)[lig_b][:, None]
+        sigma_t = self.sigma(gamma_t)[lig_b][:, None]
+        x_hat = (g.nodes['lig'].data['x_0'] - sigma_t * eps_x_pred) / alpha_t
+        x_hat = x_hat - self._kp_mean(g, kp_b)[lig_b] + init_kp_com[lig_b]
+        rec_x = g.nodes['rec'].data.get('x_0')
+        if rec_x is None:
+            rec_x = torch.zeros(0, 3, device=x_hat.device)
+        total, _ = segmented_dist_hinge(x_hat.float().contiguous(), g.node_ptr('lig').int(), rec_x.detach().float().contiguous(),
+                                        g.node_ptr('rec').int(), self.rl_dist_threshold)
+        return total
 
     def denoised_representation(self, g, lig_batch_idx, kp_batch_idx, eps_x_pred, eps_h_pred, gamma_t):
         """ligand_diffuser.py:221-230."""
