@@ -103,78 +103,61 @@ struct kpd_egnn {
 
 static kpd_status build_weight_arena(kpd_egnn *m) {
     const kpd_egnn_config &c = m->cfg;
-    const size_t wpB = (size_t)WP_FLOATS * 4 + 256, vB = (size_t)HS * 4 + 256;
-    const int n_gemm_layer = m->n_et * 2 + 16 + m->n_upd * 3;
-    size_t bytes = (size_t)c.n_layers * (n_gemm_layer * (wpB + vB) + (m->n_et * 6 + 16 + m->n_upd * 4) * vB);
-    bytes += (size_t)(64 * c.atom_nf + 64 + 64 * 256 + 256 + 2 * c.rec_nf * c.rec_nf + 2 * c.rec_nf +
-                      2 * c.rec_nf * 256 + 256 + 2 * c.atom_nf * 256 + 2 * c.atom_nf + 2 * c.atom_nf * c.atom_nf +
-                      c.atom_nf) * 4 + 64 * 256;
-    bytes += (size_t)c.n_layers * m->n_et * 4 * (16 * 4096 + HS + 64) * 4;
-    bytes += (size_t)c.n_layers * m->n_et * 2 * ((size_t)WH_HALVES * 2 + 256);
-    bytes += (size_t)c.n_layers * m->n_et * 4 * ((size_t)CHH_HALVES * 2 + 256);
-    bytes += (size_t)c.n_layers * m->n_upd * 3 * ((size_t)WH_HALVES * 2 + 256);
-    bytes += 1 << 20;
-    kpd_status st = m->warena.reserve(bytes);
-    if (st != KPD_OK) return st;
     m->warena.poison_at = 2;          // packed weights: poisoned only at KPD_POISON >= 2 (engine.h)
-    Arena &A = m->warena;
     m->L.assign(c.n_layers, LayerW());
-    auto wp = [&]() { return A.take<float>(WP_FLOATS); };
-    auto vec = [&]() { return A.take<float>(HS); };
-    for (int i = 0; i < c.n_layers; ++i) {
-        LayerW &w = m->L[i];
-        memset(&w, 0, sizeof(w));
-        const std::string pre = "egnn.conv_layers." + std::to_string(i) + ".";
-        for (int et = 0; et < m->n_et; ++et) {
-            w.wp_e[et] = wp(); w.wx_e[et] = vec(); w.b_e[et] = vec(); w.wr_e[et] = vec(); w.watt[et] = vec();
-            w.wp_c[et] = wp(); w.wx_c[et] = vec(); w.b_c[et] = vec(); w.wr_c[et] = vec(); w.w3[et] = vec();
-            w.wh_e[et] = A.take<unsigned short>(WH_HALVES); w.wh_c[et] = A.take<unsigned short>(WH_HALVES);
-            for (int var = 0; var < 2; ++var) {
-                const int ss = kSrcSlot[et] + var, ds = kDstSlot[et] + var;
-                w.wp_p[kSrcNt[et]][ss] = wp(); w.wx_p[kSrcNt[et]][ss] = vec();
-                w.wp_p[kDstNt[et]][ds] = wp(); w.wx_p[kDstNt[et]][ds] = vec(); w.b_p[kDstNt[et]][ds] = vec();
-                w.ch_p[kSrcNt[et]][ss] = A.take<float>(16 * 4096); w.wcol_p[kSrcNt[et]][ss] = vec();
-                w.ch_p[kDstNt[et]][ds] = A.take<float>(16 * 4096); w.wcol_p[kDstNt[et]][ds] = vec();
-                w.chh_p[kSrcNt[et]][ss] = A.take<unsigned short>(CHH_HALVES);
-                w.chh_p[kDstNt[et]][ds] = A.take<unsigned short>(CHH_HALVES);
+    return carve(m->warena, ARENA_TAIL, [&](Carve &A) {
+        for (int i = 0; i < c.n_layers; ++i) {
+            LayerW &w = m->L[i];
+            const std::string pre = "egnn.conv_layers." + std::to_string(i) + ".";
+            for (int et = 0; et < m->n_et; ++et) {
+                A(w.wp_e[et], WP_FLOATS); A(w.wx_e[et], HS); A(w.b_e[et], HS); A(w.wr_e[et], HS); A(w.watt[et], HS);
+                A(w.wp_c[et], WP_FLOATS); A(w.wx_c[et], HS); A(w.b_c[et], HS); A(w.wr_c[et], HS); A(w.w3[et], HS);
+                A.as<unsigned short>(w.wh_e[et], WH_HALVES); A.as<unsigned short>(w.wh_c[et], WH_HALVES);
+                for (int var = 0; var < 2; ++var) {
+                    const int ss = kSrcSlot[et] + var, ds = kDstSlot[et] + var;
+                    A(w.wp_p[kSrcNt[et]][ss], WP_FLOATS); A(w.wx_p[kSrcNt[et]][ss], HS);
+                    A(w.wp_p[kDstNt[et]][ds], WP_FLOATS); A(w.wx_p[kDstNt[et]][ds], HS); A(w.b_p[kDstNt[et]][ds], HS);
+                    A(w.ch_p[kSrcNt[et]][ss], 16 * 4096); A(w.wcol_p[kSrcNt[et]][ss], HS);
+                    A(w.ch_p[kDstNt[et]][ds], 16 * 4096); A(w.wcol_p[kDstNt[et]][ds], HS);
+                    A.as<unsigned short>(w.chh_p[kSrcNt[et]][ss], CHH_HALVES);
+                    A.as<unsigned short>(w.chh_p[kDstNt[et]][ds], CHH_HALVES);
+                }
+                const std::string e = kEtName[et];
+                for (const char *blk : {"edge_mlp.", "coord_mlp."})
+                    for (const char *s : {".0.weight", ".0.bias", ".2.weight", ".2.bias"}) m->expected.insert(pre + blk + e + s);
+                m->expected.insert(pre + "coord_mlp." + e + ".4.weight");
+                m->expected.insert(pre + "soft_attention." + e + ".0.weight");
+                m->expected.insert(pre + "soft_attention." + e + ".0.bias");
             }
-            const std::string e = kEtName[et];
-            for (const char *blk : {"edge_mlp.", "coord_mlp."})
-                for (const char *s : {".0.weight", ".0.bias", ".2.weight", ".2.bias"}) m->expected.insert(pre + blk + e + s);
-            m->expected.insert(pre + "coord_mlp." + e + ".4.weight");
-            m->expected.insert(pre + "soft_attention." + e + ".0.weight");
-            m->expected.insert(pre + "soft_attention." + e + ".0.bias");
-        }
-        for (int nt = 0; nt < m->n_upd; ++nt) {
-            w.wp_a[nt] = wp(); w.wx_a[nt] = vec(); w.wp_b[nt] = wp(); w.wx_b[nt] = vec(); w.b0[nt] = vec();
-            w.wp_2[nt] = wp(); w.wx_2[nt] = vec(); w.b2[nt] = vec(); w.ln_w[nt] = vec(); w.ln_b[nt] = vec();
-            w.wh_a[nt] = A.take<unsigned short>(WH_HALVES); w.wh_b[nt] = A.take<unsigned short>(WH_HALVES);
-            w.wh_2[nt] = A.take<unsigned short>(WH_HALVES);
-            const std::string n = kNtName[nt];
-            for (const char *s : {".0.weight", ".0.bias", ".2.weight", ".2.bias"}) m->expected.insert(pre + "node_mlp." + n + s);
-            if (c.norm) {
-                m->expected.insert(pre + "layer_norm." + n + ".weight");
-                m->expected.insert(pre + "layer_norm." + n + ".bias");
+            for (int nt = 0; nt < m->n_upd; ++nt) {
+                A(w.wp_a[nt], WP_FLOATS); A(w.wx_a[nt], HS); A(w.wp_b[nt], WP_FLOATS); A(w.wx_b[nt], HS); A(w.b0[nt], HS);
+                A(w.wp_2[nt], WP_FLOATS); A(w.wx_2[nt], HS); A(w.b2[nt], HS); A(w.ln_w[nt], HS); A(w.ln_b[nt], HS);
+                A.as<unsigned short>(w.wh_a[nt], WH_HALVES); A.as<unsigned short>(w.wh_b[nt], WH_HALVES);
+                A.as<unsigned short>(w.wh_2[nt], WH_HALVES);
+                const std::string n = kNtName[nt];
+                for (const char *s : {".0.weight", ".0.bias", ".2.weight", ".2.bias"}) m->expected.insert(pre + "node_mlp." + n + s);
+                if (c.norm) {
+                    m->expected.insert(pre + "layer_norm." + n + ".weight");
+                    m->expected.insert(pre + "layer_norm." + n + ".bias");
+                }
             }
         }
-    }
-    m->le_W0 = A.take<float>(64 * c.atom_nf); m->le_b0 = A.take<float>(64);
-    m->le_W1t = A.take<float>(64 * 256); m->le_b1 = A.take<float>(256);
-    for (const char *s : {"lig_encoder.0.weight", "lig_encoder.0.bias", "lig_encoder.2.weight", "lig_encoder.2.bias",
-                          "lig_decoder.0.weight", "lig_decoder.0.bias", "lig_decoder.2.weight", "lig_decoder.2.bias"})
-        m->expected.insert(s);
-    if (!m->rec_identity) {
-        m->re_W0 = A.take<float>(2 * c.rec_nf * c.rec_nf); m->re_b0 = A.take<float>(2 * c.rec_nf);
-        m->re_W1t = A.take<float>(2 * c.rec_nf * 256); m->re_b1 = A.take<float>(256);
-        for (const char *s : {"rec_encoder.0.weight", "rec_encoder.0.bias", "rec_encoder.2.weight", "rec_encoder.2.bias"})
+        A(m->le_W0, 64 * c.atom_nf); A(m->le_b0, 64);
+        A(m->le_W1t, 64 * 256); A(m->le_b1, 256);
+        for (const char *s : {"lig_encoder.0.weight", "lig_encoder.0.bias", "lig_encoder.2.weight", "lig_encoder.2.bias",
+                              "lig_decoder.0.weight", "lig_decoder.0.bias", "lig_decoder.2.weight", "lig_decoder.2.bias"})
             m->expected.insert(s);
-    } else {
-        m->re_W0 = m->re_b0 = m->re_W1t = m->re_b1 = nullptr;
-    }
-    m->de_W0 = A.take<float>(2 * c.atom_nf * 256); m->de_b0 = A.take<float>(2 * c.atom_nf);
-    m->de_W1 = A.take<float>(2 * c.atom_nf * c.atom_nf); m->de_b1 = A.take<float>(c.atom_nf);
-    KPD_REQUIRE(m->de_b1 != nullptr, KPD_ERR_HIP, "weight arena too small (internal sizing error)");
-    return KPD_OK;
+        if (!m->rec_identity) {
+            A(m->re_W0, 2 * c.rec_nf * c.rec_nf); A(m->re_b0, 2 * c.rec_nf);
+            A(m->re_W1t, 2 * c.rec_nf * 256); A(m->re_b1, 256);
+            for (const char *s : {"rec_encoder.0.weight", "rec_encoder.0.bias", "rec_encoder.2.weight", "rec_encoder.2.bias"})
+                m->expected.insert(s);
+        } else {
+            m->re_W0 = m->re_b0 = m->re_W1t = m->re_b1 = nullptr;
+        }
+        A(m->de_W0, 2 * c.atom_nf * 256); A(m->de_b0, 2 * c.atom_nf);
+        A(m->de_W1, 2 * c.atom_nf * c.atom_nf); A(m->de_b1, c.atom_nf);
+    });
 }
 
 extern "C" kpd_status kpd_egnn_create(const kpd_egnn_config *cfg, kpd_egnn **out) {
@@ -504,14 +487,13 @@ extern "C" kpd_status kpd_egnn_reserve(kpd_egnn *m, int32_t max_B, int32_t max_n
         return KPD_OK;
     max_B = std::max(max_B, m->cap_B); max_n_lig = std::max(max_n_lig, m->cap_lig); max_n_kp = std::max(max_n_kp, m->cap_kp);
     max_n_kk = std::max(max_n_kk, m->cap_kk); max_lig_pg = std::max(max_lig_pg, m->cap_maxlig); max_kp_pg = std::max(max_kp_pg, m->cap_maxkp);
-    const long cap_ll_l = (long)max_n_lig * std::min(max_lig_pg - 1, m->cfg.ll_k > 0 ? m->cfg.ll_k : 200);
-    const long cap_kl_l = (long)max_n_kp * (m->cfg.kl_k > 0 ? m->cfg.kl_k : std::min(max_lig_pg, 100));
-    KPD_REQUIRE(cap_ll_l < (1l << 30) && cap_kl_l < (1l << 30), KPD_ERR_CAPACITY, "edge capacity overflows int32");
+    kpd_lig_graph &g = m->lg;
+    KPD_TRY(lig_graph_caps(m->cfg.ll_k, m->cfg.kl_k, max_n_lig, max_n_kp, max_lig_pg, g));
     // the edge kernels address a node's row of P by a 32-bit byte offset (node * NSLOT * HS * 4)
     KPD_REQUIRE(((long)std::max(max_n_lig, max_n_kp) + TM) * NSLOT * HS * 4 < (1l << 32), KPD_ERR_CAPACITY,
                 "batch of %d / %d nodes exceeds the 4 GB addressable per node type by the edge kernel's 32-bit row offsets (split the batch)",
                 max_n_lig, max_n_kp);
-    const int cap_ll = std::max<long>(cap_ll_l, 1), cap_kl = std::max<long>(cap_kl_l, 1);
+    const int cap_ll = g.cap_ll, cap_kl = g.cap_kl;
     const int E_cap[4] = {cap_ll, cap_kl, cap_kl, std::max(max_n_kk, 1)};
     int tiles[4], tile_cap = 0;
     for (int et = 0; et < 4; ++et) {
@@ -519,49 +501,24 @@ extern "C" kpd_status kpd_egnn_reserve(kpd_egnn *m, int32_t max_B, int32_t max_n
         tile_cap += tiles[et];
     }
     const int n[2] = {max_n_lig, max_n_kp};
-    size_t bytes = 1 << 20;
-    auto add = [&](size_t cnt, size_t sz) { bytes += ((cnt * sz + 255) & ~size_t(255)); };
-    for (int nt = 0; nt < 2; ++nt) {
-        add((size_t)(n[nt] + TM) * HS, 4); add((size_t)n[nt] * 3, 4); add((size_t)(n[nt] + TM) * NSLOT * HS, 4);
-        add(n[nt], 4); add(max_B, 4);
-    }
-    for (int et = 0; et < 4; ++et) {
-        add((size_t)n[kDstNt[et]] * HS, 4); add((size_t)tiles[et] * HS, 4);
-        add((size_t)n[kDstNt[et]] * 4, 4); add((size_t)tiles[et] * 4, 4);
-    }
-    add(32, 4); add(max_n_lig, 4); add(max_B + 1, 4); add(max_B + 1, 4); add(max_B + 2, 4);
-    add(cap_ll, 4); add(cap_ll, 4); add(max_n_lig + 1, 4);
-    for (int i = 0; i < 4; ++i) add(cap_kl, 4);
-    add(max_n_lig + 1, 4); add(max_n_kp + 1, 4); add(max_B, 4); add(8, 4);
-    KPD_TRY(m->ws.reserve(bytes));
-    Arena &W = m->ws;
-    for (int nt = 0; nt < 2; ++nt) {
-        m->h[nt] = W.take<float>((size_t)(n[nt] + TM) * HS);          // + one tile: kernels touch whole tiles
-        m->x[nt] = W.take<float>((size_t)n[nt] * 3);
-        m->P[nt] = W.take_rows((size_t)(n[nt] + TM) * NSLOT, HS, HW);
-        m->bidx[nt] = W.take<int>(n[nt]);
-        m->z[nt] = W.take<float>(max_B);
-    }
-    for (int et = 0; et < 4; ++et) {
-        m->hn_main[et] = W.take_rows(n[kDstNt[et]], HS, HW);
-        m->hn_cont[et] = W.take_rows(tiles[et], HS, HW);
-        m->xn_main[et] = W.take<float>((size_t)n[kDstNt[et]] * 4);
-        m->xn_cont[et] = W.take<float>((size_t)tiles[et] * 4);
-        m->tiles_et_cap[et] = tiles[et];
-    }
-    m->meta = W.take<int>(32);                 // [0..8] all active edge types, [16..24] the final layer's subset
-    m->ll_deg = W.take<int>(max_n_lig);
-    m->ll_off = W.take<int>(max_B + 1);
-    m->kl_off = W.take<int>(max_B + 1);
-    m->kl_pg = W.take<int>(max_B + 2);
-    kpd_lig_graph &g = m->lg;
-    g.cap_ll = cap_ll; g.cap_kl = cap_kl;
-    g.ll_src = W.take<int>(cap_ll); g.ll_dst = W.take<int>(cap_ll); g.ll_rowptr = W.take<int>(max_n_lig + 1);
-    g.kl_src = W.take<int>(cap_kl); g.kl_dst = W.take<int>(cap_kl); g.kl_rowptr = W.take<int>(max_n_lig + 1);
-    g.lk_src = W.take<int>(cap_kl); g.lk_dst = W.take<int>(cap_kl); g.lk_rowptr = W.take<int>(max_n_kp + 1);
-    g.ll_per_graph = W.take<int>(max_B);
-    g.counts = W.take<int>(8);
-    KPD_REQUIRE(g.counts != nullptr, KPD_ERR_HIP, "workspace arena too small (internal sizing error)");
+    KPD_TRY(carve(m->ws, ARENA_TAIL, [&](Carve &W) {
+        for (int nt = 0; nt < 2; ++nt) {
+            W(m->h[nt], (size_t)(n[nt] + TM) * HS);          // + one tile: kernels touch whole tiles
+            W(m->x[nt], (size_t)n[nt] * 3);
+            W.rows(m->P[nt], (size_t)(n[nt] + TM) * NSLOT, HS, HW);
+            W(m->bidx[nt], n[nt]);
+            W(m->z[nt], max_B);
+        }
+        for (int et = 0; et < 4; ++et) {
+            W.rows(m->hn_main[et], n[kDstNt[et]], HS, HW);
+            W.rows(m->hn_cont[et], tiles[et], HS, HW);
+            W(m->xn_main[et], (size_t)n[kDstNt[et]] * 4);
+            W(m->xn_cont[et], (size_t)tiles[et] * 4);
+        }
+        // meta: [0..8] all active edge types, [16..24] the final layer's subset
+        carve_lig_graph(W, m->meta, m->ll_deg, m->ll_off, m->kl_off, m->kl_pg, g, max_B, max_n_lig, max_n_kp);
+    }));
+    for (int et = 0; et < 4; ++et) m->tiles_et_cap[et] = tiles[et];
     m->cap_B = max_B; m->cap_lig = max_n_lig; m->cap_kp = max_n_kp; m->cap_kk = max_n_kk;
     m->cap_ll = cap_ll; m->cap_kl = cap_kl; m->cap_maxlig = max_lig_pg; m->cap_maxkp = max_kp_pg;
     m->tile_cap = tile_cap;

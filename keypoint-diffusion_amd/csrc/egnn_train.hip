@@ -835,8 +835,9 @@ extern "C" kpd_status kpd_egnn_trainer_reserve(kpd_egnn_trainer *T, int32_t max_
     const kpd_egnn_config &c = T->cfg;
     max_B = std::max(max_B, T->cap_B); max_n_lig = std::max(max_n_lig, T->cap_lig); max_n_kp = std::max(max_n_kp, T->cap_kp);
     max_n_kk = std::max(max_n_kk, T->cap_kk); max_lig_pg = std::max(max_lig_pg, T->cap_maxlig); max_kp_pg = std::max(max_kp_pg, T->cap_maxkp);
-    const int cap_ll = std::max<long>((long)max_n_lig * std::min(max_lig_pg - 1, c.ll_k > 0 ? c.ll_k : 200), 1);
-    const int cap_kl = std::max<long>((long)max_n_kp * (c.kl_k > 0 ? c.kl_k : std::min(max_lig_pg, 100)), 1);
+    kpd_lig_graph &g = T->lg;
+    KPD_TRY(lig_graph_caps(c.ll_k, c.kl_k, max_n_lig, max_n_kp, max_lig_pg, g));
+    const int cap_ll = g.cap_ll, cap_kl = g.cap_kl;
     const int cap_E = std::max(std::max(cap_ll, cap_kl), std::max<int>(max_n_kk, 1));
     const int cap_N = std::max(max_n_lig, max_n_kp);
     KPD_REQUIRE(((long)cap_N + TM) * NSLOT * HS * 4 < (1l << 32), KPD_ERR_CAPACITY,
@@ -844,173 +845,111 @@ extern "C" kpd_status kpd_egnn_trainer_reserve(kpd_egnn_trainer *T, int32_t max_
                 max_n_lig, max_n_kp);
     const int L = c.n_layers;
     const int nn[2] = {max_n_lig, max_n_kp};
-    size_t bytes = 0;
-    auto add = [&](size_t count, size_t sz) { bytes += (count * sz + 255) & ~size_t(255); };
-    for (int nt = 0; nt < 2; ++nt) {
-        for (int l = 0; l <= L; ++l) { add((size_t)nn[nt] * LD, 4); add((size_t)nn[nt] * 3, 4); }
-        for (int l = 0; l < L; ++l) { add((size_t)nn[nt] * LD, 4); add((size_t)nn[nt] * 3, 4); }
-        add(nn[nt], 4); add(max_B, 4); add(nn[nt], 4);
-        for (int k = 0; k < 2; ++k) { add((size_t)nn[nt] * LD, 4); add((size_t)nn[nt] * 3, 4); }
-        add((size_t)nn[nt] * ENC_LD, 4); add((size_t)nn[nt] * ENC_LD, 4);
-    }
-    add((size_t)max_n_lig * ENC_LD, 4); add((size_t)max_n_lig * ENC_LD, 4);
-    for (int k = 0; k < 6; ++k) add((size_t)cap_E * LD, 4);
-    for (int k = 0; k < 7 + 6; ++k) add((size_t)cap_N * LD, 4);          // nb[7] + nbw[2][3]
-    add((size_t)cap_N * ENC_LD, 4);
-    for (int nt = 0; nt < 2; ++nt) {
-        for (int k = 0; k < 3; ++k) add((size_t)nn[nt] * CAT_LD, 4);              // ucat, ducat, dvwcat
-        add((size_t)NSLOT * LD * LD, 4); add((size_t)NSLOT * LD * LD, 4);          // wcat, dwcat
-        add((size_t)NSLOT * LD, 4); add((size_t)NSLOT * LD, 4); add((size_t)NSLOT * LD, 4);   // dbcat, dwr, bcat
-    }
-    add(EPACK_FLOATS, 4);
-    {
-        int tl = 0;
-        for (int et = 0; et < 4; ++et) {
-            const int cap = et == 0 ? cap_ll : et == 3 ? std::max<int>(max_n_kk, 1) : cap_kl;
-            tl += cdiv(cap, TM) + 1;
-            for (int k = 0; k < 4; ++k) { add((size_t)nn[kD[et]] * LD, 4); add((size_t)(cdiv(cap, TM) + 1) * LD, 4); }
-        }
-        add((size_t)tl * 2 * COLSUM_LD, 4); add((size_t)tl * 2 * COLSUM_LD, 4);
-    }
-    for (int et = 0; et < 4; ++et) {
-        const int cap = et == 0 ? cap_ll : et == 3 ? std::max<int>(max_n_kk, 1) : cap_kl;
-        add((size_t)nn[kD[et]] * LD, 4); add((size_t)(cdiv(cap, TM) + 1) * LD, 4); add((size_t)nn[kD[et]] * 4, 4); add((size_t)(cdiv(cap, TM) + 1) * 4, 4);
-    }
-    add(GRAD_PART_FLOATS, 4);
-    add(std::max(cap_E, cap_N), 4);                               // ones
-    add(32, 4); add(max_n_lig, 4); add(max_B + 1, 4); add(max_B + 1, 4); add(max_B + 2, 4);
-    add(cap_ll, 4); add(cap_ll, 4); add(max_n_lig + 1, 4);
-    for (int i = 0; i < 4; ++i) add(cap_kl, 4);
-    add(max_n_lig + 1, 4); add(max_n_kp + 1, 4); add(max_B, 4); add(8, 4);
     const int cap_et[4] = {cap_ll, cap_kl, cap_kl, std::max<int>(max_n_kk, 1)};
-    for (int et = 0; et < 4; ++et) { add(cap_et[et], 4); add(nn[kS[et]] + 1, 4); }
-    add(cap_N, 4);
-    add(colpart_floats(std::max(cap_E, cap_N)), 4);
-    add((size_t)ws_gemm_pack_floats(), 4);
-    T->ws.release();
-    KPD_TRY(T->ws.reserve(bytes + 4096));
-    Arena &W = T->ws;
+    int tl = 0;
+    for (int et = 0; et < 4; ++et) tl += cdiv(cap_et[et], TM) + 1;
+    const int n_ones = std::max(cap_E, cap_N);
     for (int nt = 0; nt < 2; ++nt) {
         T->hs[nt].assign(L + 1, nullptr); T->xs[nt].assign(L + 1, nullptr);
         T->hns[nt].assign(L, nullptr); T->xns[nt].assign(L, nullptr);
-        for (int l = 0; l <= L; ++l) { T->hs[nt][l] = W.take<float>((size_t)nn[nt] * LD); T->xs[nt][l] = W.take<float>((size_t)nn[nt] * 3); }
-        for (int l = 0; l < L; ++l) { T->hns[nt][l] = W.take<float>((size_t)nn[nt] * LD); T->xns[nt][l] = W.take<float>((size_t)nn[nt] * 3); }
-        T->bidx[nt] = W.take<int>(nn[nt]);
-        T->z[nt] = W.take<float>(max_B);
-        T->zinv[nt] = W.take<float>(nn[nt]);
-        for (int k = 0; k < 2; ++k) { T->dh[k][nt] = W.take<float>((size_t)nn[nt] * LD); T->dx[k][nt] = W.take<float>((size_t)nn[nt] * 3); }
-        T->enc1[nt] = W.take<float>((size_t)nn[nt] * ENC_LD);
-        T->enc2[nt] = W.take<float>((size_t)nn[nt] * ENC_LD);
     }
-    T->dec1 = W.take<float>((size_t)max_n_lig * ENC_LD);
-    T->dec2 = W.take<float>((size_t)max_n_lig * ENC_LD);
-    for (int k = 0; k < 7; ++k) T->nb[k] = W.take<float>((size_t)cap_N * LD);
-    for (int nt = 0; nt < 2; ++nt)
-        for (int k = 0; k < 3; ++k) T->nbw[nt][k] = W.take<float>((size_t)cap_N * LD);
-    T->dact = W.take<float>((size_t)cap_N * ENC_LD);
+    T->ws.release();
+    KPD_TRY(carve(T->ws, TRAIN_ARENA_TAIL, [&](Carve &W) {
+        for (int nt = 0; nt < 2; ++nt) {
+            for (int l = 0; l <= L; ++l) { W(T->hs[nt][l], (size_t)nn[nt] * LD); W(T->xs[nt][l], (size_t)nn[nt] * 3); }
+            for (int l = 0; l < L; ++l) { W(T->hns[nt][l], (size_t)nn[nt] * LD); W(T->xns[nt][l], (size_t)nn[nt] * 3); }
+            W(T->bidx[nt], nn[nt]);
+            W(T->z[nt], max_B);
+            W(T->zinv[nt], nn[nt]);
+            for (int k = 0; k < 2; ++k) { W(T->dh[k][nt], (size_t)nn[nt] * LD); W(T->dx[k][nt], (size_t)nn[nt] * 3); }
+            W(T->enc1[nt], (size_t)nn[nt] * ENC_LD);
+            W(T->enc2[nt], (size_t)nn[nt] * ENC_LD);
+        }
+        W(T->dec1, (size_t)max_n_lig * ENC_LD);
+        W(T->dec2, (size_t)max_n_lig * ENC_LD);
+        for (int k = 0; k < 7; ++k) W(T->nb[k], (size_t)cap_N * LD);
+        for (int nt = 0; nt < 2; ++nt)
+            for (int k = 0; k < 3; ++k) W(T->nbw[nt][k], (size_t)cap_N * LD);
+        W(T->dact, (size_t)cap_N * ENC_LD);
+        for (int nt = 0; nt < 2; ++nt) {
+            W(T->ucat[nt], (size_t)nn[nt] * CAT_LD);
+            W(T->ducat[nt], (size_t)nn[nt] * CAT_LD);
+            W(T->dvwcat[nt], (size_t)nn[nt] * CAT_LD);
+            W(T->wcat[nt], (size_t)NSLOT * LD * LD);
+            W(T->dwcat[nt], (size_t)NSLOT * LD * LD);
+            W(T->dbcat[nt], (size_t)NSLOT * LD);
+            W(T->dwr[nt], (size_t)NSLOT * LD);
+            W(T->bcat[nt], (size_t)NSLOT * LD);
+        }
+        W(T->epack, EPACK_FLOATS);
+        for (int et = 0; et < 4; ++et)
+            for (int br = 0; br < 2; ++br) {
+                W(T->dv_main[et][br], (size_t)nn[kD[et]] * LD); W(T->dv_cont[et][br], (size_t)(cdiv(cap_et[et], TM) + 1) * LD);
+                W(T->dvw_main[et][br], (size_t)nn[kD[et]] * LD); W(T->dvw_cont[et][br], (size_t)(cdiv(cap_et[et], TM) + 1) * LD);
+            }
+        W(T->bpart[0], (size_t)tl * 2 * COLSUM_LD); W(T->bpart[1], (size_t)tl * 2 * COLSUM_LD);
+        for (int et = 0; et < 4; ++et) {
+            W(T->hn_main[et], (size_t)nn[kD[et]] * LD); W(T->hn_cont[et], (size_t)(cdiv(cap_et[et], TM) + 1) * LD);
+            W(T->xn_main[et], (size_t)nn[kD[et]] * 4); W(T->xn_cont[et], (size_t)(cdiv(cap_et[et], TM) + 1) * 4);
+        }
+        W(T->part, GRAD_PART_FLOATS);
+        W(T->ones, n_ones);
+        carve_lig_graph(W, T->meta, T->ll_deg, T->ll_off, T->kl_off, T->kl_pg, g, max_B, max_n_lig, max_n_kp);
+        for (int et = 0; et < 4; ++et) { W(T->scsr[et].perm, cap_et[et]); W(T->scsr[et].rowptr, nn[kS[et]] + 1); }
+        W(T->cursor, cap_N);
+        W(T->colpart, colpart_floats(std::max(cap_E, cap_N)));
+        W(T->wsg_pack, (size_t)ws_gemm_pack_floats());
+    }));
+    // (the padding columns 257 .. 263 of every slot are never written by the segmented sums and are read by the products: zeros)
     for (int nt = 0; nt < 2; ++nt) {
-        T->ucat[nt] = W.take<float>((size_t)nn[nt] * CAT_LD);
-        T->ducat[nt] = W.take<float>((size_t)nn[nt] * CAT_LD);
-        T->dvwcat[nt] = W.take<float>((size_t)nn[nt] * CAT_LD);
-        T->wcat[nt] = W.take<float>((size_t)NSLOT * LD * LD);
-        T->dwcat[nt] = W.take<float>((size_t)NSLOT * LD * LD);
-        T->dbcat[nt] = W.take<float>((size_t)NSLOT * LD);
-        T->dwr[nt] = W.take<float>((size_t)NSLOT * LD);
-        T->bcat[nt] = W.take<float>((size_t)NSLOT * LD);
-        // (the padding columns 257 .. 263 of every slot are never written by the segmented sums and are read by the products: zeros)
         KPD_HIP(hipMemset(T->ducat[nt], 0, (size_t)nn[nt] * CAT_LD * 4));
         KPD_HIP(hipMemset(T->dvwcat[nt], 0, (size_t)nn[nt] * CAT_LD * 4));
     }
-    T->epack = W.take<float>(EPACK_FLOATS);
-    {
-        int tl = 0;
-        for (int et = 0; et < 4; ++et) {
-            const int cap = et == 0 ? cap_ll : et == 3 ? std::max<int>(max_n_kk, 1) : cap_kl;
-            tl += cdiv(cap, TM) + 1;
-            for (int br = 0; br < 2; ++br) {
-                T->dv_main[et][br] = W.take<float>((size_t)nn[kD[et]] * LD); T->dv_cont[et][br] = W.take<float>((size_t)(cdiv(cap, TM) + 1) * LD);
-                T->dvw_main[et][br] = W.take<float>((size_t)nn[kD[et]] * LD); T->dvw_cont[et][br] = W.take<float>((size_t)(cdiv(cap, TM) + 1) * LD);
-            }
-        }
-        T->bpart_tiles = tl;
-        T->bpart[0] = W.take<float>((size_t)tl * 2 * COLSUM_LD); T->bpart[1] = W.take<float>((size_t)tl * 2 * COLSUM_LD);
-    }
-    for (int et = 0; et < 4; ++et) {
-        const int cap = et == 0 ? cap_ll : et == 3 ? std::max<int>(max_n_kk, 1) : cap_kl;
-        T->hn_main[et] = W.take<float>((size_t)nn[kD[et]] * LD); T->hn_cont[et] = W.take<float>((size_t)(cdiv(cap, TM) + 1) * LD);
-        T->xn_main[et] = W.take<float>((size_t)nn[kD[et]] * 4); T->xn_cont[et] = W.take<float>((size_t)(cdiv(cap, TM) + 1) * 4);
-    }
+    T->bpart_tiles = tl;
     T->part_floats = GRAD_PART_FLOATS;
-    T->part = W.take<float>(T->part_floats);
-    const int n_ones = std::max(cap_E, cap_N);
-    T->ones = W.take<float>(n_ones);
-    T->meta = W.take<int>(32);
-    T->ll_deg = W.take<int>(max_n_lig);
-    T->ll_off = W.take<int>(max_B + 1);
-    T->kl_off = W.take<int>(max_B + 1);
-    T->kl_pg = W.take<int>(max_B + 2);
-    kpd_lig_graph &g = T->lg;
-    g.cap_ll = cap_ll; g.cap_kl = cap_kl;
-    g.ll_src = W.take<int>(cap_ll); g.ll_dst = W.take<int>(cap_ll); g.ll_rowptr = W.take<int>(max_n_lig + 1);
-    g.kl_src = W.take<int>(cap_kl); g.kl_dst = W.take<int>(cap_kl); g.kl_rowptr = W.take<int>(max_n_lig + 1);
-    g.lk_src = W.take<int>(cap_kl); g.lk_dst = W.take<int>(cap_kl); g.lk_rowptr = W.take<int>(max_n_kp + 1);
-    g.ll_per_graph = W.take<int>(max_B);
-    g.counts = W.take<int>(8);
-    for (int et = 0; et < 4; ++et) { T->scsr[et].perm = W.take<int>(cap_et[et]); T->scsr[et].rowptr = W.take<int>(nn[kS[et]] + 1); }
-    T->cursor = W.take<int>(cap_N);
     T->colpart_blocks = cdiv(std::max(cap_E, cap_N), HEAD_ROWS);
-    T->colpart = W.take<float>(colpart_floats(std::max(cap_E, cap_N)));
-    T->wsg_pack = W.take<float>((size_t)ws_gemm_pack_floats());
-    KPD_REQUIRE(T->colpart != nullptr && T->wsg_pack != nullptr, KPD_ERR_HIP, "workspace arena too small (internal sizing error)");
     {
         if (T->store_base) (void)hipFree(T->store_base);
         T->store_base = nullptr;
         T->store = false;
         static const bool want = !(getenv("KPD_TRAIN_STORE") && atoi(getenv("KPD_TRAIN_STORE")) == 0);
-        auto al = [](size_t floats) { return (floats * 4 + 255) & ~size_t(255); };
-        size_t per_layer = 0;
-        // (a2 = SiLU(pre2) is never read from memory -- the backward edge kernel recomputes it from the pre2 rows it streams: three kept
-        // arrays per branch, pre1 / a1 / pre2)
-        const int n_keep = 6;
-        for (int et = 0; et < T->n_et; ++et) per_layer += n_keep * al((size_t)cap_et[et] * LD) + 3 * al(cap_et[et]) + 3 * al((size_t)cap_et[et] * 3);
-        for (int nt = 0; nt < T->n_upd; ++nt) per_layer += 3 * al((size_t)nn[nt] * LD);
-        // all layers (activations kept: backward recomputes nothing), else one layer's edge slots (the forward edge kernel fills a whole layer
-        // at a time; backward recomputes layer by layer).  Less than one layer's slots (3 GB at C2, B = 64) is an out-of-memory error.
-        size_t edge_layer = 0;
-        for (int et = 0; et < T->n_et; ++et) edge_layer += n_keep * al((size_t)cap_et[et] * LD) + 3 * al(cap_et[et]) + 3 * al((size_t)cap_et[et] * 3);
-        int keep_layers = 0;
-        if (want && hipMalloc(reinterpret_cast<void **>(&T->store_base), per_layer * L) == hipSuccess) keep_layers = L;
-        else {
-            (void)hipGetLastError();              // a failed allocation is not an error: recompute instead
-            T->store_base = nullptr;
-            if (hipMalloc(reinterpret_cast<void **>(&T->store_base), edge_layer) == hipSuccess) keep_layers = 1;
-            else { (void)hipGetLastError(); T->store_base = nullptr; }
-        }
-        KPD_REQUIRE(keep_layers >= 1, KPD_ERR_HIP, "out of device memory: the edge activations of one layer (%zu MB) do not fit", edge_layer >> 20);
-        if (T->store_base && poison_level() >= 1) poison_floats(T->store_base, keep_layers == L ? per_layer * L : edge_layer);       // (debug: KPD_POISON)
-        T->store = keep_layers == L && want;
+        T->slots.assign((size_t)L * 4, kpd_egnn_trainer::Slot());
         for (int nt = 0; nt < 2; ++nt)
             for (int k = 0; k < 3; ++k) T->nq[nt][k].assign(L, nullptr);
-        {
-            T->slots.assign((size_t)L * 4, kpd_egnn_trainer::Slot());
-            char *p = T->store_base;
-            auto take = [&](size_t floats) { float *r = reinterpret_cast<float *>(p); p += al(floats); return r; };
-            for (int l = 0; l < (T->store ? L : 1); ++l)
+        // all layers (activations kept: backward recomputes nothing), else one layer's edge slots (the forward edge kernel fills a whole layer
+        // at a time; backward recomputes layer by layer).  Less than one layer's slots (3 GB at C2, B = 64) is an out-of-memory error.
+        // (a2 = SiLU(pre2) is never read from memory -- the backward edge kernel recomputes it from the pre2 rows it streams: three kept
+        // arrays per branch, pre1 / a1 / pre2)
+        bool all = true;
+        auto kept = [&](Carve &K) {
+            for (int l = 0; l < (all ? L : 1); ++l)
                 for (int et = 0; et < T->n_et; ++et) {
                     kpd_egnn_trainer::Slot &sl = T->slots[(size_t)l * 4 + et];
                     for (int br = 0; br < 2; ++br)
-                        for (int k = 0; k < 4; ++k) sl.e[br][k] = k == 3 ? nullptr : take((size_t)cap_et[et] * LD);
-                    sl.att = take(cap_et[et]); sl.dij = take(cap_et[et]); sl.sc = take(cap_et[et]);
-                    sl.xdiff = take((size_t)cap_et[et] * 3); sl.nvec = take((size_t)cap_et[et] * 3); sl.msgx = take((size_t)cap_et[et] * 3);
+                        for (int k = 0; k < 3; ++k) K(sl.e[br][k], (size_t)cap_et[et] * LD);
+                    K(sl.att, cap_et[et]); K(sl.dij, cap_et[et]); K(sl.sc, cap_et[et]);
+                    K(sl.xdiff, (size_t)cap_et[et] * 3); K(sl.nvec, (size_t)cap_et[et] * 3); K(sl.msgx, (size_t)cap_et[et] * 3);
                 }
-            if (!T->store)
-                for (int l = 1; l < L; ++l)
-                    for (int et = 0; et < 4; ++et) T->slots[(size_t)l * 4 + et] = T->slots[et];         // every layer uses the one set
-            if (T->store)
+            if (all)
                 for (int nt = 0; nt < T->n_upd; ++nt)
                     for (int k = 0; k < 3; ++k)
-                        for (int l = 0; l < L; ++l) T->nq[nt][k][l] = take((size_t)nn[nt] * LD);
+                        for (int l = 0; l < L; ++l) K(T->nq[nt][k][l], (size_t)nn[nt] * LD);
+        };
+        size_t bytes = carve_bytes(kept);
+        if (!want || hipMalloc(reinterpret_cast<void **>(&T->store_base), bytes) != hipSuccess) {
+            (void)hipGetLastError();              // a failed allocation is not an error: recompute instead
+            T->store_base = nullptr;
+            all = false;
+            bytes = carve_bytes(kept);
+            if (hipMalloc(reinterpret_cast<void **>(&T->store_base), bytes) != hipSuccess) { (void)hipGetLastError(); T->store_base = nullptr; }
         }
+        KPD_REQUIRE(T->store_base, KPD_ERR_HIP, "out of device memory: the edge activations of one layer (%zu MB) do not fit", bytes >> 20);
+        if (poison_level() >= 1) poison_floats(T->store_base, bytes);       // (debug: KPD_POISON)
+        carve_raw(T->store_base, kept);
+        T->store = all;
+        if (!T->store)
+            for (int l = 1; l < L; ++l)
+                for (int et = 0; et < 4; ++et) T->slots[(size_t)l * 4 + et] = T->slots[et];         // every layer uses the one set
     }
     hipLaunchKernelGGL(k_fill, grid1(n_ones), dim3(256), 0, nullptr, T->ones, 1.0f, (long long)n_ones);
     KPD_LAUNCH_CHECK();

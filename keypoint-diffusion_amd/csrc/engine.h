@@ -29,12 +29,17 @@ kpd_status launch_radius_bipartite(const float *x, const int *x_ptr, int n_x, in
 //         written -- stale arena contents, pads assumed zero, LDS left by an earlier workgroup -- surfaces as a NaN in the output
 //         instead of as a value that happens to equal the previous forward's;
 //   >= 2  the packed-weight arenas are poisoned too (shows which pads of the packed blocks rely on the arena's zero fill).
-// Integer buffers keep the zero fill (a poisoned index would fault).  tests/test_poison_gpu.py runs the denoisers this way.
+// Integer buffers keep the zero fill (a poisoned index would fault).  Run this way: test_egnn_train_gpu.py::
+// test_layer_edge_kernels_on_poisoned_workspaces, test_gvp_train_gpu.py::test_chained_kernels_on_poisoned_workspaces and
+// test_cold_start_gpu.py.
 int poison_level();
 bool poison_selected();      // KPD_POISON_ONLY=<i>: poison only the i-th float buffer carved in this process (bisecting a NaN to its buffer)
 void poison_floats(void *p, size_t bytes);
 void zero_pad_columns(float *p, size_t rows, int stride, int valid);
 kpd_status poison_lds(hipStream_t st);
+
+// bytes a carved buffer of `bytes` occupies (256-B alignment)
+inline size_t carve_round(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
 // Grow-only device arena: one hipMalloc, carved with 256-B alignment, zero-filled.
 struct Arena {
@@ -46,7 +51,7 @@ struct Arena {
     void reset() { used = 0; }
     template <typename T>
     T *take(size_t count) {
-        size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);
+        size_t bytes = carve_round(count * sizeof(T));
         if (used + bytes > cap) return nullptr;
         T *p = reinterpret_cast<T *>(base + used);
         used += bytes;
@@ -61,6 +66,80 @@ struct Arena {
         return p;
     }
 };
+
+// Padding behind the last buffer of an arena (a kernel may read a little past its buffer's end): inference engines and weight
+// arenas, trainers.
+constexpr size_t ARENA_TAIL = size_t(1) << 20, TRAIN_ARENA_TAIL = 4096;
+
+// The buffers of an arena are listed once, in a function of a Carve, and walked twice: a sizing pass (neither `arena` nor `raw`
+// set) sums their bytes, a carving pass assigns them in the same order -- taken from an Arena (zero fill, KPD_POISON), or laid
+// out in a raw region of the sizing pass's bytes (no fill).  The sizing pass writes no pointer.
+struct Carve {
+    Arena *arena = nullptr;
+    char *raw = nullptr;
+    size_t bytes = 0;           // sizing pass: the list's total; raw carving pass: bytes laid out so far
+    template <typename T>
+    void operator()(T *&p, size_t count) {
+        if (arena) {
+            p = arena->take<T>(count);
+            return;
+        }
+        if (raw) p = reinterpret_cast<T *>(raw + bytes);
+        bytes += carve_round(count * sizeof(T));
+    }
+    // `count` T held by a void * (the f16 planes)
+    template <typename T>
+    void as(void *&p, size_t count) {
+        T *q = nullptr;
+        (*this)(q, count);
+        if (q) p = q;
+    }
+    // Arena::take_rows
+    void rows(float *&p, size_t rows, int stride, int valid) {
+        if (arena) p = arena->take_rows(rows, stride, valid);
+        else (*this)(p, rows * stride);
+    }
+};
+
+template <typename Fn>
+size_t carve_bytes(Fn &&list) {
+    Carve c;
+    list(c);
+    return c.bytes;
+}
+
+// sizes the list, reserves that plus `tail` bytes, carves the list out of the arena
+template <typename Fn>
+kpd_status carve(Arena &A, size_t tail, Fn &&list) {
+    const size_t bytes = carve_bytes(list);
+    KPD_TRY(A.reserve(bytes + tail));
+    Carve c;
+    c.arena = &A;
+    list(c);
+    KPD_REQUIRE(A.used == bytes, KPD_ERR_HIP, "internal: arena carve took %zu bytes of the %zu sized", A.used, bytes);
+    return KPD_OK;
+}
+
+// lays the list out in `base`, a region of carve_bytes(list) bytes
+template <typename Fn>
+void carve_raw(char *base, Fn &&list) {
+    Carve c;
+    c.raw = base;
+    list(c);
+}
+
+// The ligand-graph workspace of the four denoiser engines (EGNN / GVP, inference / trainer).
+// Edge capacities of kpd_build_lig_graph (include/kpd.h) into g.cap_ll / g.cap_kl; KPD_ERR_CAPACITY beyond 2^30.
+kpd_status lig_graph_caps(int ll_k, int kl_k, int max_n_lig, int max_n_kp, int max_lig_pg, kpd_lig_graph &g);
+// launch_lig_graph's scratch (meta: [32]) and the arrays of g, sized by g's capacities
+inline void carve_lig_graph(Carve &c, int *&meta, int *&ll_deg, int *&ll_off, int *&kl_off, int *&kl_pg, kpd_lig_graph &g, int max_B,
+                            int max_n_lig, int max_n_kp) {
+    c(meta, 32); c(ll_deg, max_n_lig); c(ll_off, max_B + 1); c(kl_off, max_B + 1); c(kl_pg, max_B + 2);
+    c(g.ll_src, g.cap_ll); c(g.ll_dst, g.cap_ll); c(g.ll_rowptr, max_n_lig + 1);
+    c(g.kl_src, g.cap_kl); c(g.kl_dst, g.cap_kl); c(g.kl_rowptr, max_n_lig + 1);
+    c(g.lk_src, g.cap_kl); c(g.lk_dst, g.cap_kl); c(g.lk_rowptr, max_n_kp + 1);
+    c(g.ll_per_graph, max_B); c(g.counts, 8);
+}
 
 // Weight repacking helpers (pack.hip).
 // src: torch Linear weight [n_out, ld] row-major on device; uses columns [col0, col0 + K).

@@ -503,6 +503,15 @@ kpd_status launch_lig_graph(const kpd_batch *bt, float ll_cutoff, int ll_k, floa
     return launch_radius_graph(bt->lig_x, bt->lig_ptr, bt->B, bt->n_lig, bt->max_lig, ll_cutoff, 200, g->cap_ll, g->ll_src,
                                g->ll_dst, g->ll_rowptr, g->ll_per_graph, ll_deg_tmp, ll_off_tmp, kl_off_tmp, g->counts, st);
 }
+
+kpd_status lig_graph_caps(int ll_k, int kl_k, int max_n_lig, int max_n_kp, int max_lig_pg, kpd_lig_graph &g) {
+    const long cap_ll = (long)max_n_lig * std::min(max_lig_pg - 1, ll_k > 0 ? ll_k : 200);
+    const long cap_kl = (long)max_n_kp * (kl_k > 0 ? kl_k : std::min(max_lig_pg, 100));
+    KPD_REQUIRE(cap_ll < (1l << 30) && cap_kl < (1l << 30), KPD_ERR_CAPACITY, "edge capacity overflows int32");
+    g.cap_ll = (int)std::max(cap_ll, 1l);
+    g.cap_kl = (int)std::max(cap_kl, 1l);
+    return KPD_OK;
+}
 }  // namespace kpd
 
 extern "C" int64_t kpd_rec_graph_scratch_bytes(int32_t n_rec, int32_t B) {

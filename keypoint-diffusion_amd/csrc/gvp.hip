@@ -89,73 +89,67 @@ extern "C" kpd_status kpd_gvp_create(const kpd_gvp_config *cfg, kpd_gvp **out) {
     m->Vt = cfg->vector_size;
     if (const char *e = getenv("KPD_GEMM")) m->gemm_mode = (!strcmp(e, "f16x2") && m->S == 256) ? 1 : 0;
     const int S = m->S, C = cfg->n_convs;
-    size_t per_gvp = gvp_arena_bytes(S);
-    size_t bytes = per_gvp * ((size_t)C * (4 * cfg->n_message_gvps + 2 * cfg->n_update_gvps) + cfg->n_noise_gvps) +
-                   (size_t)C * 2 * 4 * (S * 4 + 256) + (size_t)2 * (S * 260 + 3 * S) * 4 + 64 * 64 * 4 + (1 << 20);
-    kpd_status st = m->warena.reserve(bytes);
-    if (st != KPD_OK) {
-        delete m;
-        return st;
-    }
     m->warena.poison_at = 2;          // packed weights: poisoned only at KPD_POISON >= 2 (engine.h)
-    Arena &A = m->warena;
     m->msg.resize(C); m->upd.resize(C); m->ln1w.resize(C); m->ln1b.resize(C); m->ln2w.resize(C); m->ln2b.resize(C);
     for (int i = 0; i < C; ++i) {
-        const std::string pre = "noise_predictor.conv_layers." + std::to_string(i) + ".";
-        const int net = m->n_et(i), nnt = net == 4 ? 2 : 1;
         m->msg[i].resize(4); m->upd[i].resize(2);
         m->ln1w[i].assign(2, nullptr); m->ln1b[i].assign(2, nullptr); m->ln2w[i].assign(2, nullptr); m->ln2b[i].assign(2, nullptr);
-        for (int et = 0; et < net; ++et) {
-            m->msg[i][et].resize(cfg->n_message_gvps);
-            for (int j = 0; j < cfg->n_message_gvps; ++j) {
-                HostGvp &g = m->msg[i][et][j];
-                g.vin = j == 0 ? GV + 1 : GV; g.vout = GV;
-                g.s_in = j == 0 ? S + 16 : S; g.sout = S;
-                g.split = j == 0 ? SPLIT_SRC : SPLIT_NONE; g.S = S; g.cut = S - m->St; g.vcut = GV - m->Vt;
-                g.chain_pos = j;
-                alloc_gvp(A, g, m->expected, pre + "edge_message_fns." + kCanon[et] + "." + std::to_string(j));
-            }
-        }
-        for (int nt = 0; nt < nnt; ++nt) {
-            m->upd[i][nt].resize(cfg->n_update_gvps);
-            for (int j = 0; j < cfg->n_update_gvps; ++j) {
-                HostGvp &g = m->upd[i][nt][j];
-                g.vin = GV; g.vout = GV; g.s_in = S; g.sout = S; g.S = S; g.cut = S - m->St; g.vcut = GV - m->Vt;
-                g.chain_pos = 1;            // register-chained node kernel: same form as a non-head message GVP
-                alloc_gvp(A, g, m->expected, pre + "node_update_fns." + kNtNameG[nt] + "." + std::to_string(j));
-            }
-            m->ln1w[i][nt] = A.take<float>(S); m->ln1b[i][nt] = A.take<float>(S);
-            m->ln2w[i][nt] = A.take<float>(S); m->ln2b[i][nt] = A.take<float>(S);
-            for (const char *s : {".feat_norm.weight", ".feat_norm.bias"}) {
-                m->expected.insert(pre + "message_layer_norms." + kNtNameG[nt] + s);
-                m->expected.insert(pre + "update_layer_norms." + kNtNameG[nt] + s);
-            }
-        }
     }
     m->noise.resize(cfg->n_noise_gvps);
-    for (int j = 0; j < cfg->n_noise_gvps; ++j) {
-        HostGvp &g = m->noise[j];
-        const bool last = j == cfg->n_noise_gvps - 1;
-        g.vin = GV; g.vout = last ? 1 : GV; g.s_in = S; g.sout = last ? 64 : S; g.S = S; g.cut = S - m->St; g.vcut = GV - m->Vt;
-        g.vec_sigmoid = last ? 0 : 1;
-        g.chain_pos = 1;                // register-chained noise head (gvp_chain.hip)
-        alloc_gvp(A, g, m->expected, "noise_predictor.noise_predictor.gvps." + std::to_string(j));
-    }
-    const int fin[2] = {cfg->n_lig_scalars + 1, cfg->n_kp_scalars + 1};
-    for (int nt = 0; nt < 2; ++nt) {
-        m->enc_W[nt] = A.take<float>((size_t)S * fin[nt]); m->enc_b[nt] = A.take<float>(S);
-        m->enc_lw[nt] = A.take<float>(S); m->enc_lb[nt] = A.take<float>(S);
-        const std::string e = std::string(kNtNameG[nt]) + "_encoder.";
-        for (const char *s : {"0.weight", "0.bias", "2.weight", "2.bias"}) m->expected.insert(e + s);
-    }
-    m->out_W = A.take<float>((size_t)cfg->n_lig_scalars * 64);
-    m->out_b = A.take<float>(cfg->n_lig_scalars);
-    m->expected.insert("noise_predictor.noise_predictor.to_scalar_output.weight");
-    m->expected.insert("noise_predictor.noise_predictor.to_scalar_output.bias");
-    if (!m->out_b) {
-        set_error("gvp weight arena too small (internal sizing error)");
+    const kpd_status st = carve(m->warena, ARENA_TAIL, [&](Carve &A) {
+        for (int i = 0; i < C; ++i) {
+            const std::string pre = "noise_predictor.conv_layers." + std::to_string(i) + ".";
+            const int net = m->n_et(i), nnt = net == 4 ? 2 : 1;
+            for (int et = 0; et < net; ++et) {
+                m->msg[i][et].resize(cfg->n_message_gvps);
+                for (int j = 0; j < cfg->n_message_gvps; ++j) {
+                    HostGvp &g = m->msg[i][et][j];
+                    g.vin = j == 0 ? GV + 1 : GV; g.vout = GV;
+                    g.s_in = j == 0 ? S + 16 : S; g.sout = S;
+                    g.split = j == 0 ? SPLIT_SRC : SPLIT_NONE; g.S = S; g.cut = S - m->St; g.vcut = GV - m->Vt;
+                    g.chain_pos = j;
+                    alloc_gvp(A, g, m->expected, pre + "edge_message_fns." + kCanon[et] + "." + std::to_string(j));
+                }
+            }
+            for (int nt = 0; nt < nnt; ++nt) {
+                m->upd[i][nt].resize(cfg->n_update_gvps);
+                for (int j = 0; j < cfg->n_update_gvps; ++j) {
+                    HostGvp &g = m->upd[i][nt][j];
+                    g.vin = GV; g.vout = GV; g.s_in = S; g.sout = S; g.S = S; g.cut = S - m->St; g.vcut = GV - m->Vt;
+                    g.chain_pos = 1;            // register-chained node kernel: same form as a non-head message GVP
+                    alloc_gvp(A, g, m->expected, pre + "node_update_fns." + kNtNameG[nt] + "." + std::to_string(j));
+                }
+                A(m->ln1w[i][nt], S); A(m->ln1b[i][nt], S);
+                A(m->ln2w[i][nt], S); A(m->ln2b[i][nt], S);
+                for (const char *s : {".feat_norm.weight", ".feat_norm.bias"}) {
+                    m->expected.insert(pre + "message_layer_norms." + kNtNameG[nt] + s);
+                    m->expected.insert(pre + "update_layer_norms." + kNtNameG[nt] + s);
+                }
+            }
+        }
+        for (int j = 0; j < cfg->n_noise_gvps; ++j) {
+            HostGvp &g = m->noise[j];
+            const bool last = j == cfg->n_noise_gvps - 1;
+            g.vin = GV; g.vout = last ? 1 : GV; g.s_in = S; g.sout = last ? 64 : S; g.S = S; g.cut = S - m->St; g.vcut = GV - m->Vt;
+            g.vec_sigmoid = last ? 0 : 1;
+            g.chain_pos = 1;                // register-chained noise head (gvp_chain.hip)
+            alloc_gvp(A, g, m->expected, "noise_predictor.noise_predictor.gvps." + std::to_string(j));
+        }
+        const int fin[2] = {cfg->n_lig_scalars + 1, cfg->n_kp_scalars + 1};
+        for (int nt = 0; nt < 2; ++nt) {
+            A(m->enc_W[nt], (size_t)S * fin[nt]); A(m->enc_b[nt], S);
+            A(m->enc_lw[nt], S); A(m->enc_lb[nt], S);
+            const std::string e = std::string(kNtNameG[nt]) + "_encoder.";
+            for (const char *s : {"0.weight", "0.bias", "2.weight", "2.bias"}) m->expected.insert(e + s);
+        }
+        A(m->out_W, (size_t)cfg->n_lig_scalars * 64);
+        A(m->out_b, cfg->n_lig_scalars);
+        m->expected.insert("noise_predictor.noise_predictor.to_scalar_output.weight");
+        m->expected.insert("noise_predictor.noise_predictor.to_scalar_output.bias");
+    });
+    if (st != KPD_OK) {
         kpd_gvp_destroy(m);
-        return KPD_ERR_HIP;
+        return st;
     }
     *out = m;
     return KPD_OK;
@@ -271,48 +265,25 @@ extern "C" kpd_status kpd_gvp_reserve(kpd_gvp *m, int32_t max_B, int32_t max_n_l
         return KPD_OK;
     max_B = std::max(max_B, m->cap_B); max_n_lig = std::max(max_n_lig, m->cap_lig); max_n_kp = std::max(max_n_kp, m->cap_kp);
     max_n_kk = std::max(max_n_kk, m->cap_kk); max_lig_pg = std::max(max_lig_pg, m->cap_maxlig); max_kp_pg = std::max(max_kp_pg, m->cap_maxkp);
-    const long cap_ll_l = (long)max_n_lig * std::min(max_lig_pg - 1, m->cfg.ll_k > 0 ? m->cfg.ll_k : 200);
-    const long cap_kl_l = (long)max_n_kp * (m->cfg.kl_k > 0 ? m->cfg.kl_k : std::min(max_lig_pg, 100));
-    KPD_REQUIRE(cap_ll_l < (1l << 30) && cap_kl_l < (1l << 30), KPD_ERR_CAPACITY, "edge capacity overflows int32");
-    const int cap_ll = std::max<long>(cap_ll_l, 1), cap_kl = std::max<long>(cap_kl_l, 1);
-    const int E_cap[4] = {cap_ll, cap_kl, cap_kl, std::max(max_n_kk, 1)};
-    const int S = m->S, n[2] = {max_n_lig, max_n_kp};
-    int tiles[4];
-    size_t bytes = 1 << 20;
-    auto add = [&](size_t cnt) { bytes += ((cnt * 4 + 255) & ~size_t(255)); };
-    for (int nt = 0; nt < 2; ++nt) { add((size_t)n[nt] * S); add((size_t)n[nt] * S); add((size_t)n[nt] * 48); add(n[nt]); add(max_B); }
-    for (int et = 0; et < 4; ++et) {
-        tiles[et] = cdiv(E_cap[et], TM) + 1;
-        add((size_t)n[kSrcNtG[et]] * S);
-        add((size_t)n[kDstNtG[et]] * S); add((size_t)tiles[et] * S); add((size_t)n[kDstNtG[et]] * 48); add((size_t)tiles[et] * 48);
-    }
-    add(32); add(16); add(max_n_lig); add(max_B + 1); add(max_B + 1); add(max_B + 2);
-    add(cap_ll); add(cap_ll); add(max_n_lig + 1);
-    for (int i = 0; i < 4; ++i) add(cap_kl);
-    add(max_n_lig + 1); add(max_n_kp + 1); add(max_B); add(8);
-    KPD_TRY(m->ws.reserve(bytes));
-    Arena &W = m->ws;
-    for (int nt = 0; nt < 2; ++nt) {
-        m->s[nt] = W.take<float>((size_t)n[nt] * S); m->s_tmp[nt] = W.take<float>((size_t)n[nt] * S);
-        m->v[nt] = W.take<float>((size_t)n[nt] * 48);
-        m->bidx[nt] = W.take<int>(n[nt]); m->z[nt] = W.take<float>(max_B);
-    }
-    for (int et = 0; et < 4; ++et) {
-        m->Psrc[et] = W.take<float>((size_t)n[kSrcNtG[et]] * S);
-        m->ms_main[et] = W.take<float>((size_t)n[kDstNtG[et]] * S); m->ms_cont[et] = W.take<float>((size_t)tiles[et] * S);
-        m->mv_main[et] = W.take<float>((size_t)n[kDstNtG[et]] * 48); m->mv_cont[et] = W.take<float>((size_t)tiles[et] * 48);
-    }
-    m->meta4 = W.take<int>(32); m->meta2 = m->meta4 + 16;    // one k_egnn_meta launch fills both tables
-    m->ll_deg = W.take<int>(max_n_lig); m->ll_off = W.take<int>(max_B + 1); m->kl_off = W.take<int>(max_B + 1);
-    m->kl_pg = W.take<int>(max_B + 2);
     kpd_lig_graph &g = m->lg;
-    g.cap_ll = cap_ll; g.cap_kl = cap_kl;
-    g.ll_src = W.take<int>(cap_ll); g.ll_dst = W.take<int>(cap_ll); g.ll_rowptr = W.take<int>(max_n_lig + 1);
-    g.kl_src = W.take<int>(cap_kl); g.kl_dst = W.take<int>(cap_kl); g.kl_rowptr = W.take<int>(max_n_lig + 1);
-    g.lk_src = W.take<int>(cap_kl); g.lk_dst = W.take<int>(cap_kl); g.lk_rowptr = W.take<int>(max_n_kp + 1);
-    g.ll_per_graph = W.take<int>(max_B);
-    g.counts = W.take<int>(8);
-    KPD_REQUIRE(g.counts != nullptr, KPD_ERR_HIP, "gvp workspace arena too small (internal sizing error)");
+    KPD_TRY(lig_graph_caps(m->cfg.ll_k, m->cfg.kl_k, max_n_lig, max_n_kp, max_lig_pg, g));
+    const int E_cap[4] = {g.cap_ll, g.cap_kl, g.cap_kl, std::max(max_n_kk, 1)};
+    const int S = m->S, n[2] = {max_n_lig, max_n_kp};
+    KPD_TRY(carve(m->ws, ARENA_TAIL, [&](Carve &W) {
+        for (int nt = 0; nt < 2; ++nt) {
+            W(m->s[nt], (size_t)n[nt] * S); W(m->s_tmp[nt], (size_t)n[nt] * S);
+            W(m->v[nt], (size_t)n[nt] * 48);
+            W(m->bidx[nt], n[nt]); W(m->z[nt], max_B);
+        }
+        for (int et = 0; et < 4; ++et) {
+            const int tiles = cdiv(E_cap[et], TM) + 1;
+            W(m->Psrc[et], (size_t)n[kSrcNtG[et]] * S);
+            W(m->ms_main[et], (size_t)n[kDstNtG[et]] * S); W(m->ms_cont[et], (size_t)tiles * S);
+            W(m->mv_main[et], (size_t)n[kDstNtG[et]] * 48); W(m->mv_cont[et], (size_t)tiles * 48);
+        }
+        carve_lig_graph(W, m->meta4, m->ll_deg, m->ll_off, m->kl_off, m->kl_pg, g, max_B, max_n_lig, max_n_kp);
+    }));
+    m->meta2 = m->meta4 + 16;    // one k_egnn_meta launch fills both tables
     m->cap_B = max_B; m->cap_lig = max_n_lig; m->cap_kp = max_n_kp; m->cap_kk = max_n_kk;
     m->cap_maxlig = max_lig_pg; m->cap_maxkp = max_kp_pg;
     return KPD_OK;

@@ -46,11 +46,9 @@ struct HostGvp {
 };
 
 std::vector<std::string> split_dots(const std::string &s);
-void alloc_gvp(Arena &A, HostGvp &g, std::set<std::string> &expected, const std::string &prefix);
+void alloc_gvp(Carve &A, HostGvp &g, std::set<std::string> &expected, const std::string &prefix);
 kpd_status want_shape(const char *name, const int64_t *shape, int ndim, std::initializer_list<int64_t> want);
 kpd_status load_gvp_tensor(HostGvp &g, const std::string &param, const char *name, const float *w, const int64_t *shape,
                            int ndim, hipStream_t st);
-// bytes one HostGvp can take from the arena (upper bound)
-size_t gvp_arena_bytes(int S);
 
 }  // namespace kpd

@@ -15,29 +15,25 @@ std::vector<std::string> split_dots(const std::string &s) {
     return out;
 }
 
-size_t gvp_arena_bytes(int S) {
-    return (256 + 16 + 4 * (size_t)(S / 8) * 2048 + 256 + 2 * (size_t)(S / 16 + 2) * (S / 16) * 256 + 12 * 256) * 4 + 16384;
-}
-
-void alloc_gvp(Arena &A, HostGvp &g, std::set<std::string> &expected, const std::string &prefix) {
+void alloc_gvp(Carve &A, HostGvp &g, std::set<std::string> &expected, const std::string &prefix) {
     g.h = std::max(g.vin, g.vout);
-    g.b = A.take<float>(256);
-    g.bg = A.take<float>(16);
+    A(g.b, 256);
+    A(g.bg, 16);
     if (g.split != SPLIT_NONE) {
-        g.wproj = A.take<float>((size_t)(g.S / 8) * 2048);
-        g.bproj = A.take<float>(256);
-        if (g.S == 256) g.wproj_h = A.take<float>((size_t)(g.S / 8) * 2048);
+        A(g.wproj, (size_t)(g.S / 8) * 2048);
+        A(g.bproj, 256);
+        if (g.S == 256) A(g.wproj_h, (size_t)(g.S / 8) * 2048);
     }
     if (g.split == SPLIT_SRC_DST) {
-        g.wproj_dst = A.take<float>((size_t)(g.S / 8) * 2048);
-        if (g.S == 256) g.wproj_dst_h = A.take<float>((size_t)(g.S / 8) * 2048);
+        A(g.wproj_dst, (size_t)(g.S / 8) * 2048);
+        if (g.S == 256) A(g.wproj_dst_h, (size_t)(g.S / 8) * 2048);
     }
     // a split first Linear exists only at the head of an edge-message chain
     if ((g.split != SPLIT_NONE) != (g.chain_pos == 0)) set_error("internal: GVP split/chain position mismatch");
-    g.chain = A.take<float>((size_t)g.chain_chunks() * (g.sout / 16) * 256);
-    if (g.has_h()) g.chain_h = A.take<float>((size_t)g.chain_chunks() * (g.sout / 16) * 256);
-    g.whp = A.take<float>(g.chain_pos == 0 ? 9 * 256 : 256);
-    g.wup = A.take<float>((size_t)g.n_ht() * 256);
+    A(g.chain, (size_t)g.chain_chunks() * (g.sout / 16) * 256);
+    if (g.has_h()) A(g.chain_h, (size_t)g.chain_chunks() * (g.sout / 16) * 256);
+    A(g.whp, g.chain_pos == 0 ? 9 * 256 : 256);
+    A(g.wup, (size_t)g.n_ht() * 256);
     for (const char *s : {".Wh", ".Wu", ".to_feats_out.0.weight", ".to_feats_out.0.bias", ".scalar_to_vector_gates.weight",
                           ".scalar_to_vector_gates.bias"})
         expected.insert(prefix + s);

@@ -947,8 +947,10 @@ extern "C" kpd_status kpd_gvp_trainer_reserve(kpd_gvp_trainer *T, int32_t max_B,
     const kpd_gvp_config &c = T->cfg;
     max_B = std::max(max_B, T->cap_B); max_n_lig = std::max(max_n_lig, T->cap_lig); max_n_kp = std::max(max_n_kp, T->cap_kp);
     max_n_kk = std::max(max_n_kk, T->cap_kk); max_lig_pg = std::max(max_lig_pg, T->cap_maxlig); max_kp_pg = std::max(max_kp_pg, T->cap_maxkp);
-    const int cap_ll = std::max<long>((long)max_n_lig * std::min(max_lig_pg - 1, c.ll_k > 0 ? c.ll_k : 200), 1);
-    const int cap_kl = std::max<long>((long)max_n_kp * (c.kl_k > 0 ? c.kl_k : std::min(max_lig_pg, 100)), 1);
+    kpd_lig_graph &g = T->lg;
+    KPD_TRY(lig_graph_caps(c.ll_k, c.kl_k, max_n_lig, max_n_kp, max_lig_pg, g));
+    const int cap_ll = g.cap_ll, cap_kl = g.cap_kl;
+    const int cap_et[4] = {cap_ll, cap_kl, cap_kl, std::max<int>(max_n_kk, 1)};
     const int R = std::max(std::max(std::max(cap_ll, cap_kl), std::max<int>(max_n_kk, 1)), std::max(max_n_lig, max_n_kp));
     const int L = c.n_convs, S = T->S;
     const int nn[2] = {max_n_lig, max_n_kp};
@@ -957,54 +959,35 @@ extern "C" kpd_status kpd_gvp_trainer_reserve(kpd_gvp_trainer *T, int32_t max_B,
         T->sa[nt].assign(L, nullptr); T->va[nt].assign(L, nullptr);
     }
     T->ws.release();
-    // two passes over the same list: size, then carve
-    for (int pass = 0; pass < 2; ++pass) {
-        size_t bytes = 0;
-        auto F = [&](float *&p, size_t count) {
-            if (pass == 0) bytes += (count * 4 + 255) & ~size_t(255);
-            else p = T->ws.take<float>(count);
-        };
-        auto I = [&](int *&p, size_t count) {
-            if (pass == 0) bytes += (count * 4 + 255) & ~size_t(255);
-            else p = T->ws.take<int>(count);
-        };
+    KPD_TRY(carve(T->ws, TRAIN_ARENA_TAIL, [&](Carve &W) {
         for (int nt = 0; nt < 2; ++nt) {
-            for (int l = 0; l <= L; ++l) { F(T->ss[nt][l], (size_t)nn[nt] * S); F(T->vs[nt][l], (size_t)nn[nt] * 3 * VC); }
-            for (int l = 0; l < L; ++l) { F(T->sa[nt][l], (size_t)nn[nt] * S); F(T->va[nt][l], (size_t)nn[nt] * 3 * VC); }
-            F(T->enc_in[nt], (size_t)nn[nt] * 256); F(T->enc_pre[nt], (size_t)nn[nt] * S); F(T->enc_act[nt], (size_t)nn[nt] * S);
-            I(T->bidx[nt], nn[nt]); F(T->z[nt], max_B);
-            for (int k = 0; k < 2; ++k) { F(T->gs[k][nt], (size_t)nn[nt] * S); F(T->gv[k][nt], (size_t)nn[nt] * 3 * VC); }
+            for (int l = 0; l <= L; ++l) { W(T->ss[nt][l], (size_t)nn[nt] * S); W(T->vs[nt][l], (size_t)nn[nt] * 3 * VC); }
+            for (int l = 0; l < L; ++l) { W(T->sa[nt][l], (size_t)nn[nt] * S); W(T->va[nt][l], (size_t)nn[nt] * 3 * VC); }
+            W(T->enc_in[nt], (size_t)nn[nt] * 256); W(T->enc_pre[nt], (size_t)nn[nt] * S); W(T->enc_act[nt], (size_t)nn[nt] * S);
+            W(T->bidx[nt], nn[nt]); W(T->z[nt], max_B);
+            for (int k = 0; k < 2; ++k) { W(T->gs[k][nt], (size_t)nn[nt] * S); W(T->gv[k][nt], (size_t)nn[nt] * 3 * VC); }
         }
         for (int k = 0; k < 4; ++k) {
             GvpBuf &b = T->gb[k];
-            F(b.Vh, (size_t)R * 3 * VH); F(b.Vu, (size_t)R * 3 * VC); F(b.sh, (size_t)R * VH); F(b.pre, (size_t)R * S); F(b.s, (size_t)R * S);
-            F(b.gate, (size_t)R * VC); F(b.V, (size_t)R * 3 * VC);
+            W(b.Vh, (size_t)R * 3 * VH); W(b.Vu, (size_t)R * 3 * VC); W(b.sh, (size_t)R * VH); W(b.pre, (size_t)R * S); W(b.s, (size_t)R * S);
+            W(b.gate, (size_t)R * VC); W(b.V, (size_t)R * 3 * VC);
         }
-        for (int k = 0; k < 2; ++k) { F(T->ds[k], (size_t)R * (S + RBF)); F(T->dV[k], (size_t)R * 3 * VH); }
-        F(T->dVh, (size_t)R * 3 * VH); F(T->dsh, (size_t)R * VH); F(T->dgate, (size_t)R * VC);
-        F(T->unit, (size_t)R * 3); F(T->rbf, (size_t)R * RBF); F(T->vin, (size_t)R * 3 * VH);
-        F(T->dxe, (size_t)R * 3); F(T->gx[0], (size_t)max_n_lig * 3); F(T->gx[1], (size_t)max_n_kp * 3);
+        for (int k = 0; k < 2; ++k) { W(T->ds[k], (size_t)R * (S + RBF)); W(T->dV[k], (size_t)R * 3 * VH); }
+        W(T->dVh, (size_t)R * 3 * VH); W(T->dsh, (size_t)R * VH); W(T->dgate, (size_t)R * VC);
+        W(T->unit, (size_t)R * 3); W(T->rbf, (size_t)R * RBF); W(T->vin, (size_t)R * 3 * VH);
+        W(T->dxe, (size_t)R * 3); W(T->gx[0], (size_t)max_n_lig * 3); W(T->gx[1], (size_t)max_n_kp * 3);
         const size_t N = std::max(max_n_lig, max_n_kp);
-        F(T->U, N * S); F(T->scale, N); F(T->tmp_s, N * S); F(T->tmp_v, N * 3 * VC); F(T->s1, N * S); F(T->v1, N * 3 * VC);
-        F(T->sb, N * std::max(S, 256)); F(T->vb, N * 3 * VC);
-        F(T->part, GVP_PART_FLOATS);
-        F(T->wsg_pack, (size_t)ws_gemm_pack_floats());
-        F(T->ones, 8);
-        const int cap_et[4] = {cap_ll, cap_kl, cap_kl, std::max<int>(max_n_kk, 1)};
-        for (int et = 0; et < 4; ++et) { I(T->scsr[et].perm, cap_et[et]); I(T->scsr[et].rowptr, nn[kSrc[et]] + 1); }
-        I(T->cursor, std::max(max_n_lig, max_n_kp));
-        F(T->colpart, colpart_floats(R));
-        I(T->meta, 32); I(T->ll_deg, max_n_lig); I(T->ll_off, max_B + 1); I(T->kl_off, max_B + 1); I(T->kl_pg, max_B + 2);
-        kpd_lig_graph &g = T->lg;
-        I(g.ll_src, cap_ll); I(g.ll_dst, cap_ll); I(g.ll_rowptr, max_n_lig + 1);
-        I(g.kl_src, cap_kl); I(g.kl_dst, cap_kl); I(g.kl_rowptr, max_n_lig + 1);
-        I(g.lk_src, cap_kl); I(g.lk_dst, cap_kl); I(g.lk_rowptr, max_n_kp + 1);
-        I(g.ll_per_graph, max_B); I(g.counts, 8);
-        if (pass == 0) KPD_TRY(T->ws.reserve(bytes + 4096));
-    }
-    KPD_REQUIRE(T->lg.counts != nullptr, KPD_ERR_HIP, "workspace arena too small (internal sizing error)");
+        W(T->U, N * S); W(T->scale, N); W(T->tmp_s, N * S); W(T->tmp_v, N * 3 * VC); W(T->s1, N * S); W(T->v1, N * 3 * VC);
+        W(T->sb, N * std::max(S, 256)); W(T->vb, N * 3 * VC);
+        W(T->part, GVP_PART_FLOATS);
+        W(T->wsg_pack, (size_t)ws_gemm_pack_floats());
+        W(T->ones, 8);
+        for (int et = 0; et < 4; ++et) { W(T->scsr[et].perm, cap_et[et]); W(T->scsr[et].rowptr, nn[kSrc[et]] + 1); }
+        W(T->cursor, std::max(max_n_lig, max_n_kp));
+        W(T->colpart, colpart_floats(R));
+        carve_lig_graph(W, T->meta, T->ll_deg, T->ll_off, T->kl_off, T->kl_pg, g, max_B, max_n_lig, max_n_kp);
+    }));
     T->part_floats = GVP_PART_FLOATS;
-    T->lg.cap_ll = cap_ll; T->lg.cap_kl = cap_kl;
     T->colpart_blocks = cdiv(R, HEAD_ROWS);
     T->scratch.unit = T->unit; T->scratch.rbf = T->rbf; T->scratch.vin = T->vin;
     for (int j = 0; j < 4; ++j) T->scratch.gb[j] = T->gb[j];
@@ -1013,35 +996,26 @@ extern "C" kpd_status kpd_gvp_trainer_reserve(kpd_gvp_trainer *T, int32_t max_B,
         T->store_base = nullptr;
         T->store = false;
         static const bool want = !(getenv("KPD_TRAIN_STORE") && atoi(getenv("KPD_TRAIN_STORE")) == 0);
-        const int cap_et[4] = {cap_ll, cap_kl, cap_kl, std::max<int>(max_n_kk, 1)};
         const int nm = c.n_message_gvps;
-        auto al = [](size_t floats) { return (floats * 4 + 255) & ~size_t(255); };
-        auto slot_bytes = [&](size_t E) {
-            size_t b = al(E * 3) + al(E * RBF) + al(E * 3 * VH);
-            for (int j = 0; j < nm; ++j) b += al(E * 3 * VH) + al(E * 3 * VC) + al(E * VH) + 2 * al(E * S) + al(E * VC) + al(E * 3 * VC);
-            return b;
-        };
-        size_t total = 0;
-        for (int conv = 0; conv < L; ++conv)
-            for (int et = 0; et < 4; ++et)
-                if (conv_uses(T, conv, et)) total += slot_bytes(cap_et[et]);
-        if (want && nm <= 4 && hipMalloc(reinterpret_cast<void **>(&T->store_base), std::max<size_t>(total, 256)) == hipSuccess) {
-            T->store = true;
-            T->slots.assign((size_t)L * 4, kpd_gvp_trainer::MsgSlot());
-            char *p = T->store_base;
-            auto take = [&](size_t floats) { float *r = reinterpret_cast<float *>(p); p += al(floats); return r; };
+        T->slots.assign((size_t)L * 4, kpd_gvp_trainer::MsgSlot());
+        auto kept = [&](Carve &K) {
             for (int conv = 0; conv < L; ++conv)
                 for (int et = 0; et < 4; ++et) {
                     if (!conv_uses(T, conv, et)) continue;
                     const size_t E = cap_et[et];
                     kpd_gvp_trainer::MsgSlot &sl = T->slots[(size_t)conv * 4 + et];
-                    sl.unit = take(E * 3); sl.rbf = take(E * RBF); sl.vin = take(E * 3 * VH);
+                    K(sl.unit, E * 3); K(sl.rbf, E * RBF); K(sl.vin, E * 3 * VH);
                     for (int j = 0; j < nm; ++j) {
                         GvpBuf &b = sl.gb[j];
-                        b.Vh = take(E * 3 * VH); b.Vu = take(E * 3 * VC); b.sh = take(E * VH); b.pre = take(E * S); b.s = take(E * S);
-                        b.gate = take(E * VC); b.V = take(E * 3 * VC);
+                        K(b.Vh, E * 3 * VH); K(b.Vu, E * 3 * VC); K(b.sh, E * VH); K(b.pre, E * S); K(b.s, E * S);
+                        K(b.gate, E * VC); K(b.V, E * 3 * VC);
                     }
                 }
+        };
+        const size_t total = want && nm <= 4 ? carve_bytes(kept) : 0;          // (MsgSlot holds up to 4 GVPs)
+        if (want && nm <= 4 && hipMalloc(reinterpret_cast<void **>(&T->store_base), std::max<size_t>(total, 256)) == hipSuccess) {
+            T->store = true;
+            carve_raw(T->store_base, kept);
         } else {
             (void)hipGetLastError();
             T->store_base = nullptr;

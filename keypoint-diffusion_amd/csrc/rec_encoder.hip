@@ -264,7 +264,7 @@ struct kpd_recenc {
     int *bidx[2], *kp_ptr, *meta, *off_tmp, *deg_tmp, *rad_tmp, *xm_src, *xm_dst, *xm_rowptr, *rk_rowptr, *kk_rowptr, *kk_off;
 };
 
-static void alloc_conv(kpd_recenc *m, Arena &A, std::vector<HostGvp> &msg, std::vector<HostGvp> &upd, bool use_dst,
+static void alloc_conv(kpd_recenc *m, Carve &A, std::vector<HostGvp> &msg, std::vector<HostGvp> &upd, bool use_dst,
                        const std::string &pre, float **ln) {
     const kpd_recenc_config &c = m->cfg;
     const int S = m->S;
@@ -289,7 +289,7 @@ static void alloc_conv(kpd_recenc *m, Arena &A, std::vector<HostGvp> &msg, std::
         g.vcut = GV - c.vector_size;
         alloc_gvp(A, g, m->expected, pre + "node_update." + std::to_string(j));
     }
-    for (int i = 0; i < 4; ++i) ln[i] = A.take<float>(S);
+    for (int i = 0; i < 4; ++i) A(ln[i], S);
     for (const char *s : {".feat_norm.weight", ".feat_norm.bias"}) {
         m->expected.insert(pre + "message_layer_norm" + s);
         m->expected.insert(pre + "update_layer_norm" + s);
@@ -316,36 +316,33 @@ extern "C" kpd_status kpd_recenc_create(const kpd_recenc_config *cfg, kpd_recenc
     kpd_recenc *m = new kpd_recenc();
     m->cfg = *cfg;
     const int S = m->S = cfg->out_scalar_size, K = cfg->n_keypoints, F = cfg->in_scalar_size;
-    size_t bytes = gvp_arena_bytes(S) * (size_t)(cfg->n_rr_convs + cfg->n_rk_convs) * (cfg->n_message_gvps + cfg->n_update_gvps) +
-                   (size_t)(cfg->n_rr_convs + cfg->n_rk_convs) * 4 * (S * 4 + 256) +
-                   ((size_t)S * F + 2 * S * S + (size_t)S * K * S + 3 * (size_t)S * K + 8 * S) * 4 + (1 << 20);
-    kpd_status st = m->warena.reserve(bytes);
-    if (st != KPD_OK) {
-        delete m;
-        return st;
-    }
     m->warena.poison_at = 2;          // packed weights: poisoned only at KPD_POISON >= 2 (engine.h)
-    Arena &A = m->warena;
     m->rr_msg.resize(cfg->n_rr_convs); m->rr_upd.resize(cfg->n_rr_convs);
     m->rk_msg.resize(cfg->n_rk_convs); m->rk_upd.resize(cfg->n_rk_convs);
     m->rr_ln1w.resize(cfg->n_rr_convs); m->rr_ln1b.resize(cfg->n_rr_convs); m->rr_ln2w.resize(cfg->n_rr_convs); m->rr_ln2b.resize(cfg->n_rr_convs);
     m->rk_ln1w.resize(cfg->n_rk_convs); m->rk_ln1b.resize(cfg->n_rk_convs); m->rk_ln2w.resize(cfg->n_rk_convs); m->rk_ln2b.resize(cfg->n_rk_convs);
-    for (int i = 0; i < cfg->n_rr_convs; ++i) {
-        float *ln[4];
-        alloc_conv(m, A, m->rr_msg[i], m->rr_upd[i], false, "rr_conv_layers." + std::to_string(i) + ".", ln);
-        m->rr_ln1w[i] = ln[0]; m->rr_ln1b[i] = ln[1]; m->rr_ln2w[i] = ln[2]; m->rr_ln2b[i] = ln[3];
+    const kpd_status st = carve(m->warena, ARENA_TAIL, [&](Carve &A) {
+        for (int i = 0; i < cfg->n_rr_convs; ++i) {
+            float *ln[4] = {};
+            alloc_conv(m, A, m->rr_msg[i], m->rr_upd[i], false, "rr_conv_layers." + std::to_string(i) + ".", ln);
+            m->rr_ln1w[i] = ln[0]; m->rr_ln1b[i] = ln[1]; m->rr_ln2w[i] = ln[2]; m->rr_ln2b[i] = ln[3];
+        }
+        for (int i = 0; i < cfg->n_rk_convs; ++i) {
+            float *ln[4] = {};
+            alloc_conv(m, A, m->rk_msg[i], m->rk_upd[i], i != 0, "rk_conv_layers." + std::to_string(i) + ".", ln);   // :194-197
+            m->rk_ln1w[i] = ln[0]; m->rk_ln1b[i] = ln[1]; m->rk_ln2w[i] = ln[2]; m->rk_ln2b[i] = ln[3];
+        }
+        A(m->emb_W0, (size_t)S * F); A(m->emb_b0, S);
+        A(m->emb_W1t, (size_t)S * S); A(m->emb_b1, S);
+        A(m->emb_lw, S); A(m->emb_lb, S);
+        A(m->kpe_W, (size_t)S * K * S); A(m->kpe_b, (size_t)S * K);
+        A(m->kpe_lw, (size_t)S * K); A(m->kpe_lb, (size_t)S * K);
+        A(m->src_Wt, (size_t)S * S); A(m->dst_Wt, (size_t)S * S);
+    });
+    if (st != KPD_OK) {
+        kpd_recenc_destroy(m);
+        return st;
     }
-    for (int i = 0; i < cfg->n_rk_convs; ++i) {
-        float *ln[4];
-        alloc_conv(m, A, m->rk_msg[i], m->rk_upd[i], i != 0, "rk_conv_layers." + std::to_string(i) + ".", ln);   // :194-197
-        m->rk_ln1w[i] = ln[0]; m->rk_ln1b[i] = ln[1]; m->rk_ln2w[i] = ln[2]; m->rk_ln2b[i] = ln[3];
-    }
-    m->emb_W0 = A.take<float>((size_t)S * F); m->emb_b0 = A.take<float>(S);
-    m->emb_W1t = A.take<float>((size_t)S * S); m->emb_b1 = A.take<float>(S);
-    m->emb_lw = A.take<float>(S); m->emb_lb = A.take<float>(S);
-    m->kpe_W = A.take<float>((size_t)S * K * S); m->kpe_b = A.take<float>((size_t)S * K);
-    m->kpe_lw = A.take<float>((size_t)S * K); m->kpe_lb = A.take<float>((size_t)S * K);
-    m->src_Wt = A.take<float>((size_t)S * S); m->dst_Wt = A.take<float>((size_t)S * S);
     for (const char *s : {"scalar_embed.0.weight", "scalar_embed.0.bias", "scalar_embed.2.weight", "scalar_embed.2.bias",
                           "scalar_norm.weight", "scalar_norm.bias", "keypoint_initializer.src_net.weight",
                           "keypoint_initializer.dst_net.weight", "keypoint_initializer.keypoint_embedding.0.weight",
@@ -355,11 +352,6 @@ extern "C" kpd_status kpd_recenc_create(const kpd_recenc_config *cfg, kpd_recenc
     // present in the state dict, unused by forward (receptor_encoder_gvp.py:37)
     m->ignored.insert("keypoint_initializer.norm.weight");
     m->ignored.insert("keypoint_initializer.norm.bias");
-    if (!m->dst_Wt) {
-        set_error("recenc weight arena too small (internal sizing error)");
-        kpd_recenc_destroy(m);
-        return KPD_ERR_HIP;
-    }
     *out = m;
     return KPD_OK;
 }
@@ -459,28 +451,21 @@ extern "C" kpd_status kpd_recenc_reserve(kpd_recenc *m, int32_t max_B, int32_t m
     const int e_max = std::max(std::max(max_n_rr, cap_rk), 1);
     const int n_max = std::max(max_n_rec, n_kp);
     const int tiles = cdiv(e_max, TM) + 1;
-    size_t bytes = 1 << 20;
-    auto add = [&](size_t cnt) { bytes += ((cnt * 4 + 255) & ~size_t(255)); };
-    for (int nt = 0; nt < 2; ++nt) { add((size_t)n[nt] * S); add((size_t)n[nt] * S); add((size_t)n[nt] * 48); add(n[nt]); }
-    add((size_t)n_max * S); add((size_t)n_max * S); add((size_t)n_max * S); add((size_t)tiles * S); add((size_t)n_max * 48); add((size_t)tiles * 48);
-    add((size_t)max_B * S); add((size_t)n_kp * S); add((size_t)max_n_rec * S); add((size_t)n_kp * S); add(max_B);
-    add(max_B + 1); add(16); add(max_B + 1); add(n_max); add(max_B + 8); add(cap_rk); add(cap_rk); add(max_n_rec + 1); add(n_kp + 1); add(n_kp + 1); add(max_B + 1);
-    KPD_TRY(m->ws.reserve(bytes));
-    Arena &W = m->ws;
-    for (int nt = 0; nt < 2; ++nt) {
-        m->s[nt] = W.take<float>((size_t)n[nt] * S); m->s_tmp[nt] = W.take<float>((size_t)n[nt] * S);
-        m->v[nt] = W.take<float>((size_t)n[nt] * 48); m->bidx[nt] = W.take<int>(n[nt]);
-    }
-    m->Psrc = W.take<float>((size_t)n_max * S); m->Pdst = W.take<float>((size_t)n_max * S);
-    m->ms_main = W.take<float>((size_t)n_max * S); m->ms_cont = W.take<float>((size_t)tiles * S);
-    m->mv_main = W.take<float>((size_t)n_max * 48); m->mv_cont = W.take<float>((size_t)tiles * 48);
-    m->gmean = W.take<float>((size_t)max_B * S); m->kp_emb = W.take<float>((size_t)n_kp * S);
-    m->ft_src = W.take<float>((size_t)max_n_rec * S); m->ft_dst = W.take<float>((size_t)n_kp * S); m->z = W.take<float>(max_B);
-    m->kp_ptr = W.take<int>(max_B + 1); m->meta = W.take<int>(16); m->off_tmp = W.take<int>(max_B + 1); m->deg_tmp = W.take<int>(n_max);
-    m->rad_tmp = W.take<int>(max_B + 8);
-    m->xm_src = W.take<int>(cap_rk); m->xm_dst = W.take<int>(cap_rk); m->xm_rowptr = W.take<int>(max_n_rec + 1);
-    m->rk_rowptr = W.take<int>(n_kp + 1); m->kk_rowptr = W.take<int>(n_kp + 1); m->kk_off = W.take<int>(max_B + 1);
-    KPD_REQUIRE(m->kk_off != nullptr, KPD_ERR_HIP, "recenc workspace arena too small (internal sizing error)");
+    KPD_TRY(carve(m->ws, ARENA_TAIL, [&](Carve &W) {
+        for (int nt = 0; nt < 2; ++nt) {
+            W(m->s[nt], (size_t)n[nt] * S); W(m->s_tmp[nt], (size_t)n[nt] * S);
+            W(m->v[nt], (size_t)n[nt] * 48); W(m->bidx[nt], n[nt]);
+        }
+        W(m->Psrc, (size_t)n_max * S); W(m->Pdst, (size_t)n_max * S);
+        W(m->ms_main, (size_t)n_max * S); W(m->ms_cont, (size_t)tiles * S);
+        W(m->mv_main, (size_t)n_max * 48); W(m->mv_cont, (size_t)tiles * 48);
+        W(m->gmean, (size_t)max_B * S); W(m->kp_emb, (size_t)n_kp * S);
+        W(m->ft_src, (size_t)max_n_rec * S); W(m->ft_dst, (size_t)n_kp * S); W(m->z, max_B);
+        W(m->kp_ptr, max_B + 1); W(m->meta, 16); W(m->off_tmp, max_B + 1); W(m->deg_tmp, n_max);
+        W(m->rad_tmp, max_B + 8);
+        W(m->xm_src, cap_rk); W(m->xm_dst, cap_rk); W(m->xm_rowptr, max_n_rec + 1);
+        W(m->rk_rowptr, n_kp + 1); W(m->kk_rowptr, n_kp + 1); W(m->kk_off, max_B + 1);
+    }));
     m->cap_B = max_B; m->cap_rec = max_n_rec; m->cap_rr = max_n_rr; m->cap_maxrec = max_rec_pg;
     return KPD_OK;
 }

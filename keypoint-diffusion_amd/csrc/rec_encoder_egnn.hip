@@ -307,55 +307,47 @@ extern "C" kpd_status kpd_recegnn_create(const kpd_recegnn_config *cfg, kpd_rece
     KPD_REQUIRE(cfg->message_norm >= 0.0f, KPD_ERR_INVALID, "message_norm=%f", cfg->message_norm);
     kpd_recegnn *m = new kpd_recegnn();
     m->cfg = *cfg;
-    const int ef = cfg->use_sameres_feat ? 1 : 0, f1 = 2 * RW + 2;
-    size_t bytes = (size_t)cfg->n_convs * ((size_t)2 * f1 * RW + 3 * RW * RW + (size_t)2 * RW * RW + 16 * RW) * 4 +
-                   ((size_t)D * K * D + (size_t)D * K + (size_t)D * D + (size_t)(D + 32) * D + 4 * RW) * 4 + (1 << 20);
-    kpd_status st = m->warena.reserve(bytes);
-    if (st != KPD_OK) {
-        delete m;
-        return st;
-    }
+    const int ef = cfg->use_sameres_feat ? 1 : 0;
     m->warena.poison_at = 2;          // packed weights: poisoned only at KPD_POISON >= 2 (engine.h)
-    Arena &A = m->warena;
     m->conv.resize(cfg->n_convs);
-    for (int i = 0; i < cfg->n_convs; ++i) {
-        ConvW &c = m->conv[i];
-        c.in = i == 0 ? in : hid;                                   // receptor_encoder.py:431-449
-        c.out = i == cfg->n_convs - 1 ? D : hid;
-        const int e_in = 2 * c.in + 1 + ef;
-        c.We_t = A.take<float>((size_t)e_in * hid); c.be = A.take<float>(hid);
-        c.W2_t = A.take<float>((size_t)hid * hid); c.b2 = A.take<float>(hid);
-        c.watt = A.take<float>(hid); c.batt = A.take<float>(1);
-        c.Wn1_t = A.take<float>((size_t)(c.in + hid) * hid); c.bn1 = A.take<float>(hid);
-        c.Wn2_t = A.take<float>((size_t)hid * c.out); c.bn2 = A.take<float>(c.out);
-        const std::string p = "rec_convs." + std::to_string(i) + ".";
-        for (const char *s : {"edge_mlp.0.weight", "edge_mlp.0.bias", "edge_mlp.2.weight", "edge_mlp.2.bias", "soft_attention.0.weight",
-                              "soft_attention.0.bias", "node_mlp.0.weight", "node_mlp.0.bias", "node_mlp.2.weight", "node_mlp.2.bias"})
-            m->expected.insert(p + s);
-        if (!cfg->fix_pos) {
-            c.Wc_t = A.take<float>((size_t)e_in * hid); c.bc = A.take<float>(hid); c.w3 = A.take<float>(hid);
-            for (const char *s : {"coord_mlp.0.weight", "coord_mlp.0.bias", "coord_mlp.2.weight"}) m->expected.insert(p + s);
+    const kpd_status st = carve(m->warena, ARENA_TAIL, [&](Carve &A) {
+        for (int i = 0; i < cfg->n_convs; ++i) {
+            ConvW &c = m->conv[i];
+            c.in = i == 0 ? in : hid;                                   // receptor_encoder.py:431-449
+            c.out = i == cfg->n_convs - 1 ? D : hid;
+            const int e_in = 2 * c.in + 1 + ef;
+            A(c.We_t, (size_t)e_in * hid); A(c.be, hid);
+            A(c.W2_t, (size_t)hid * hid); A(c.b2, hid);
+            A(c.watt, hid); A(c.batt, 1);
+            A(c.Wn1_t, (size_t)(c.in + hid) * hid); A(c.bn1, hid);
+            A(c.Wn2_t, (size_t)hid * c.out); A(c.bn2, c.out);
+            const std::string p = "rec_convs." + std::to_string(i) + ".";
+            for (const char *s : {"edge_mlp.0.weight", "edge_mlp.0.bias", "edge_mlp.2.weight", "edge_mlp.2.bias", "soft_attention.0.weight",
+                                  "soft_attention.0.bias", "node_mlp.0.weight", "node_mlp.0.bias", "node_mlp.2.weight", "node_mlp.2.bias"})
+                m->expected.insert(p + s);
+            if (!cfg->fix_pos) {
+                A(c.Wc_t, (size_t)e_in * hid); A(c.bc, hid); A(c.w3, hid);
+                for (const char *s : {"coord_mlp.0.weight", "coord_mlp.0.bias", "coord_mlp.2.weight"}) m->expected.insert(p + s);
+            }
+            if (cfg->norm) {
+                A(c.ln_w, c.out); A(c.ln_b, c.out);
+                m->expected.insert(p + "layer_norm.weight"); m->expected.insert(p + "layer_norm.bias");
+            }
         }
+        A(m->kpe_W, (size_t)D * K * D); A(m->kpe_b, (size_t)D * K);
+        A(m->fc_src_t, (size_t)D * D);
+        A(m->kpf_W_t, (size_t)(D + cfg->k_closest) * D); A(m->kpf_b, D);
+        for (const char *s : {"keypoint_embedding.0.weight", "keypoint_embedding.0.bias", "rec_kp_conv.fc_src.weight",
+                              "rec_kp_conv.kp_feature_mlp.0.weight", "rec_kp_conv.kp_feature_mlp.0.bias"})
+            m->expected.insert(s);
         if (cfg->norm) {
-            c.ln_w = A.take<float>(c.out); c.ln_b = A.take<float>(c.out);
-            m->expected.insert(p + "layer_norm.weight"); m->expected.insert(p + "layer_norm.bias");
+            A(m->kp_lw, D); A(m->kp_lb, D);
+            m->expected.insert("rec_kp_conv.layer_norm.weight"); m->expected.insert("rec_kp_conv.layer_norm.bias");
         }
-    }
-    m->kpe_W = A.take<float>((size_t)D * K * D); m->kpe_b = A.take<float>((size_t)D * K);
-    m->fc_src_t = A.take<float>((size_t)D * D);
-    m->kpf_W_t = A.take<float>((size_t)(D + cfg->k_closest) * D); m->kpf_b = A.take<float>(D);
-    for (const char *s : {"keypoint_embedding.0.weight", "keypoint_embedding.0.bias", "rec_kp_conv.fc_src.weight",
-                          "rec_kp_conv.kp_feature_mlp.0.weight", "rec_kp_conv.kp_feature_mlp.0.bias"})
-        m->expected.insert(s);
-    if (cfg->norm) {
-        m->kp_lw = A.take<float>(D); m->kp_lb = A.take<float>(D);
-        m->expected.insert("rec_kp_conv.layer_norm.weight"); m->expected.insert("rec_kp_conv.layer_norm.bias");
-    }
-    if (!m->kpf_b || (cfg->norm && !m->kp_lb)) {
-        set_error("recegnn weight arena too small (internal sizing error)");
-        m->warena.release();
-        delete m;
-        return KPD_ERR_HIP;
+    });
+    if (st != KPD_OK) {
+        kpd_recegnn_destroy(m);
+        return st;
     }
     *out = m;
     return KPD_OK;
@@ -456,24 +448,17 @@ extern "C" kpd_status kpd_recegnn_reserve(kpd_recegnn *m, int32_t max_B, int32_t
     const int K = c.n_keypoints, D = c.out_n_node_feat, n_kp = max_B * K;
     const int cap_rk = n_kp * (c.k_closest > 0 ? c.k_closest : std::min(100, max_rec_pg));      // radius: at most 100 per keypoint (:246)
     const int n_max = std::max(max_n_rec, n_kp);
-    size_t bytes = 1 << 20;
-    auto add = [&](size_t cnt) { bytes += ((cnt * 4 + 255) & ~size_t(255)); };
-    add((size_t)max_n_rec * RW); add((size_t)max_n_rec * RW); add((size_t)max_n_rec * 3); add((size_t)max_n_rec * 3);
-    add((size_t)max_n_rec * 4 * RW); add(max_B); add((size_t)max_B * D); add((size_t)n_kp * D); add((size_t)max_n_rec * D); add((size_t)n_kp * D);
-    add(max_n_rec); add(max_B + 1); add(max_B + 1); add(n_max); add(max_B + 8); add(cap_rk); add(cap_rk); add(max_n_rec + 1); add(n_kp + 1); add(n_kp + 1);
-    add(max_B + 1);
-    KPD_TRY(m->ws.reserve(bytes));
-    Arena &W = m->ws;
-    for (int i = 0; i < 2; ++i) m->h[i] = W.take<float>((size_t)max_n_rec * RW);
-    for (int i = 0; i < 2; ++i) m->x[i] = W.take<float>((size_t)max_n_rec * 3);
-    m->P = W.take<float>((size_t)max_n_rec * 4 * RW); m->z = W.take<float>(max_B);
-    m->gmean = W.take<float>((size_t)max_B * D); m->kp_h0 = W.take<float>((size_t)n_kp * D);
-    m->ft_src = W.take<float>((size_t)max_n_rec * D); m->ft_dst = W.take<float>((size_t)n_kp * D);
-    m->bidx = W.take<int>(max_n_rec); m->kp_ptr = W.take<int>(max_B + 1); m->off_tmp = W.take<int>(max_B + 1); m->deg_tmp = W.take<int>(n_max);
-    m->rad_tmp = W.take<int>(max_B + 8);
-    m->xm_src = W.take<int>(cap_rk); m->xm_dst = W.take<int>(cap_rk); m->xm_rowptr = W.take<int>(max_n_rec + 1);
-    m->rk_rowptr = W.take<int>(n_kp + 1); m->kk_rowptr = W.take<int>(n_kp + 1); m->kk_off = W.take<int>(max_B + 1);
-    KPD_REQUIRE(m->kk_off != nullptr, KPD_ERR_HIP, "recegnn workspace arena too small (internal sizing error)");
+    KPD_TRY(carve(m->ws, ARENA_TAIL, [&](Carve &W) {
+        for (int i = 0; i < 2; ++i) W(m->h[i], (size_t)max_n_rec * RW);
+        for (int i = 0; i < 2; ++i) W(m->x[i], (size_t)max_n_rec * 3);
+        W(m->P, (size_t)max_n_rec * 4 * RW); W(m->z, max_B);
+        W(m->gmean, (size_t)max_B * D); W(m->kp_h0, (size_t)n_kp * D);
+        W(m->ft_src, (size_t)max_n_rec * D); W(m->ft_dst, (size_t)n_kp * D);
+        W(m->bidx, max_n_rec); W(m->kp_ptr, max_B + 1); W(m->off_tmp, max_B + 1); W(m->deg_tmp, n_max);
+        W(m->rad_tmp, max_B + 8);
+        W(m->xm_src, cap_rk); W(m->xm_dst, cap_rk); W(m->xm_rowptr, max_n_rec + 1);
+        W(m->rk_rowptr, n_kp + 1); W(m->kk_rowptr, n_kp + 1); W(m->kk_off, max_B + 1);
+    }));
     m->cap_B = max_B; m->cap_rec = max_n_rec; m->cap_rr = max_n_rr; m->cap_maxrec = max_rec_pg;
     return KPD_OK;
 }

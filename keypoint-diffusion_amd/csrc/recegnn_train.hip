@@ -551,37 +551,26 @@ extern "C" kpd_status kpd_recegnn_trainer_reserve(kpd_recegnn_trainer *T, int32_
     const int cap_rk = std::max(n_kp * (c.k_closest > 0 ? c.k_closest : std::min(max_rec_pg, 100)), 1), E = std::max<int>(max_n_rr, 1), FW = 2 * Dm + 2;
     T->hs.assign(L + 1, nullptr); T->xs.assign(L + 1, nullptr); T->hneigh.assign(L, nullptr); T->npre.assign(L, nullptr); T->hn.assign(L, nullptr);
     T->ws.release();
-    for (int pass = 0; pass < 2; ++pass) {
-        size_t bytes = 0;
-        auto F = [&](float *&p, size_t count) {
-            if (pass == 0) bytes += (count * 4 + 255) & ~size_t(255);
-            else p = T->ws.take<float>(count);
-        };
-        auto I = [&](int *&p, size_t count) {
-            if (pass == 0) bytes += (count * 4 + 255) & ~size_t(255);
-            else p = T->ws.take<int>(count);
-        };
+    KPD_TRY(carve(T->ws, TRAIN_ARENA_TAIL, [&](Carve &A) {
         const size_t nr = max_n_rec, nk = n_kp, W = (size_t)std::max(Dm + H, D + 16);
-        for (int i = 0; i <= L; ++i) { F(T->hs[i], nr * Dm); F(T->xs[i], nr * 3); }
-        for (int i = 0; i < L; ++i) { F(T->hneigh[i], nr * H); F(T->npre[i], nr * H); F(T->hn[i], nr * Dm); }
-        F(T->gmean, (size_t)max_B * D); F(T->kpe_pre, nk * D); F(T->kp_h0, nk * D); F(T->big, nk * D); F(T->ft_src, nr * D); F(T->ft_dst, nk * D);
-        F(T->att, nr * K); F(T->kp_x, nk * 3); F(T->fin, nk * (D + 16)); F(T->fpre, nk * D); F(T->fact, nk * D);
-        F(T->r, E); F(T->xd, (size_t)E * 3); F(T->f, (size_t)E * FW); F(T->pre1, (size_t)E * H); F(T->a1, (size_t)E * H); F(T->pre2, (size_t)E * H);
-        F(T->m, (size_t)E * H); F(T->s, E); F(T->msg, (size_t)E * H); F(T->cpre, (size_t)E * H); F(T->ca, (size_t)E * H); F(T->c, E);
-        F(T->msgx, (size_t)E * 3); F(T->df, (size_t)E * FW); F(T->dE, (size_t)E * H); F(T->dE2, (size_t)E * H); F(T->dc, E); F(T->dxd, (size_t)E * 3);
-        F(T->dxe, (size_t)E * 3); F(T->ds, E);
-        F(T->cat, nr * W); F(T->na, nr * H); F(T->gcat, nr * W); F(T->gn1, nr * std::max(Dm, H)); F(T->gn2, nr * std::max(Dm, H));
-        for (int k = 0; k < 2; ++k) { F(T->gh[k], nr * Dm); F(T->gx[k], nr * 3); }
-        F(T->gkx, nk * 3); F(T->gk1, nk * (D + 16)); F(T->gk2, nk * (D + 16));
-        F(T->z, (size_t)max_B + 8); F(T->scale, nr);
-        F(T->part, GRAD_PART_FLOATS); F(T->ones, 8); F(T->colpart, colpart_floats(std::max<int>(E, (int)std::max(nr, nk))));
-        I(T->bidx, nr); I(T->kp_ptr, max_B + 1); I(T->rk_src, cap_rk); I(T->rk_dst, cap_rk); I(T->rk_rowptr, nk + 1);
-        I(T->off_tmp, max_B + 2); I(T->xm_src, cap_rk); I(T->xm_dst, cap_rk); I(T->xm_rowptr, nr + 1); I(T->cursor, std::max(nr, nk));
-        I(T->scsr_rr.perm, E); I(T->scsr_rr.rowptr, nr + 1); I(T->scsr_rk.perm, cap_rk); I(T->scsr_rk.rowptr, nr + 1);
-        I(T->kk_rowptr, nk + 1); I(T->deg_tmp, nk); I(T->kk_off, max_B + 1); I(T->rad_tmp, 2 * (size_t)max_B + 16); I(T->rk_off, max_B + 2);
-        if (pass == 0) KPD_TRY(T->ws.reserve(bytes + 4096));
-    }
-    KPD_REQUIRE(T->kk_off != nullptr, KPD_ERR_HIP, "workspace arena too small (internal sizing error)");
+        for (int i = 0; i <= L; ++i) { A(T->hs[i], nr * Dm); A(T->xs[i], nr * 3); }
+        for (int i = 0; i < L; ++i) { A(T->hneigh[i], nr * H); A(T->npre[i], nr * H); A(T->hn[i], nr * Dm); }
+        A(T->gmean, (size_t)max_B * D); A(T->kpe_pre, nk * D); A(T->kp_h0, nk * D); A(T->big, nk * D); A(T->ft_src, nr * D); A(T->ft_dst, nk * D);
+        A(T->att, nr * K); A(T->kp_x, nk * 3); A(T->fin, nk * (D + 16)); A(T->fpre, nk * D); A(T->fact, nk * D);
+        A(T->r, E); A(T->xd, (size_t)E * 3); A(T->f, (size_t)E * FW); A(T->pre1, (size_t)E * H); A(T->a1, (size_t)E * H); A(T->pre2, (size_t)E * H);
+        A(T->m, (size_t)E * H); A(T->s, E); A(T->msg, (size_t)E * H); A(T->cpre, (size_t)E * H); A(T->ca, (size_t)E * H); A(T->c, E);
+        A(T->msgx, (size_t)E * 3); A(T->df, (size_t)E * FW); A(T->dE, (size_t)E * H); A(T->dE2, (size_t)E * H); A(T->dc, E); A(T->dxd, (size_t)E * 3);
+        A(T->dxe, (size_t)E * 3); A(T->ds, E);
+        A(T->cat, nr * W); A(T->na, nr * H); A(T->gcat, nr * W); A(T->gn1, nr * std::max(Dm, H)); A(T->gn2, nr * std::max(Dm, H));
+        for (int k = 0; k < 2; ++k) { A(T->gh[k], nr * Dm); A(T->gx[k], nr * 3); }
+        A(T->gkx, nk * 3); A(T->gk1, nk * (D + 16)); A(T->gk2, nk * (D + 16));
+        A(T->z, (size_t)max_B + 8); A(T->scale, nr);
+        A(T->part, GRAD_PART_FLOATS); A(T->ones, 8); A(T->colpart, colpart_floats(std::max<int>(E, (int)std::max(nr, nk))));
+        A(T->bidx, nr); A(T->kp_ptr, max_B + 1); A(T->rk_src, cap_rk); A(T->rk_dst, cap_rk); A(T->rk_rowptr, nk + 1);
+        A(T->off_tmp, max_B + 2); A(T->xm_src, cap_rk); A(T->xm_dst, cap_rk); A(T->xm_rowptr, nr + 1); A(T->cursor, std::max(nr, nk));
+        A(T->scsr_rr.perm, E); A(T->scsr_rr.rowptr, nr + 1); A(T->scsr_rk.perm, cap_rk); A(T->scsr_rk.rowptr, nr + 1);
+        A(T->kk_rowptr, nk + 1); A(T->deg_tmp, nk); A(T->kk_off, max_B + 1); A(T->rad_tmp, 2 * (size_t)max_B + 16); A(T->rk_off, max_B + 2);
+    }));
     T->part_floats = GRAD_PART_FLOATS;
     T->colpart_blocks = cdiv(std::max<int>(E, std::max(max_n_rec, n_kp)), HEAD_ROWS);
     T->cap_B = max_B; T->cap_rec = max_n_rec; T->cap_rr = max_n_rr; T->cap_maxrec = max_rec_pg; T->cap_rk = cap_rk;

@@ -480,49 +480,38 @@ extern "C" kpd_status kpd_recenc_trainer_reserve(kpd_recenc_trainer *T, int32_t 
     T->rs.assign(Rr + 1, nullptr); T->rv.assign(Rr + 1, nullptr); T->rsa.assign(Rr, nullptr); T->rva.assign(Rr, nullptr);
     T->ks.assign(Rk + 1, nullptr); T->kv.assign(Rk + 1, nullptr); T->ksa.assign(Rk, nullptr); T->kva.assign(Rk, nullptr);
     T->ws.release();
-    for (int pass = 0; pass < 2; ++pass) {
-        size_t bytes = 0;
-        auto F = [&](float *&p, size_t count) {
-            if (pass == 0) bytes += (count * 4 + 255) & ~size_t(255);
-            else p = T->ws.take<float>(count);
-        };
-        auto I = [&](int *&p, size_t count) {
-            if (pass == 0) bytes += (count * 4 + 255) & ~size_t(255);
-            else p = T->ws.take<int>(count);
-        };
+    KPD_TRY(carve(T->ws, TRAIN_ARENA_TAIL, [&](Carve &W) {
         const size_t nr = max_n_rec, nk = n_kp, N = std::max(nr, nk);
-        F(T->e_pre0, nr * S); F(T->e_a0, nr * S); F(T->e_pre1, nr * S); F(T->e_a1, nr * S);
-        for (int i = 0; i <= Rr; ++i) { F(T->rs[i], nr * S); F(T->rv[i], nr * 3 * VC); }
-        for (int i = 0; i < Rr; ++i) { F(T->rsa[i], nr * S); F(T->rva[i], nr * 3 * VC); }
-        for (int j = 0; j <= Rk; ++j) { F(T->ks[j], nk * S); F(T->kv[j], nk * 3 * VC); }
-        for (int j = 0; j < Rk; ++j) { F(T->ksa[j], nk * S); F(T->kva[j], nk * 3 * VC); }
-        F(T->gmean, (size_t)max_B * S); F(T->kpe_pre, nk * S); F(T->kpe_act, nk * S); F(T->kp_emb, nk * S); F(T->big, nk * S);
-        F(T->ft_src, nr * S); F(T->ft_dst, nk * S); F(T->att, nr * K); F(T->kp_x, nk * 3);
+        W(T->e_pre0, nr * S); W(T->e_a0, nr * S); W(T->e_pre1, nr * S); W(T->e_a1, nr * S);
+        for (int i = 0; i <= Rr; ++i) { W(T->rs[i], nr * S); W(T->rv[i], nr * 3 * VC); }
+        for (int i = 0; i < Rr; ++i) { W(T->rsa[i], nr * S); W(T->rva[i], nr * 3 * VC); }
+        for (int j = 0; j <= Rk; ++j) { W(T->ks[j], nk * S); W(T->kv[j], nk * 3 * VC); }
+        for (int j = 0; j < Rk; ++j) { W(T->ksa[j], nk * S); W(T->kva[j], nk * 3 * VC); }
+        W(T->gmean, (size_t)max_B * S); W(T->kpe_pre, nk * S); W(T->kpe_act, nk * S); W(T->kp_emb, nk * S); W(T->big, nk * S);
+        W(T->ft_src, nr * S); W(T->ft_dst, nk * S); W(T->att, nr * K); W(T->kp_x, nk * 3);
         for (int k = 0; k < 4; ++k) {
             GvpBuf &b = T->gb[k];
-            F(b.Vh, (size_t)R * 3 * VHE); F(b.Vu, (size_t)R * 3 * VC); F(b.sh, (size_t)R * VHE); F(b.pre, (size_t)R * S); F(b.s, (size_t)R * S);
-            F(b.gate, (size_t)R * VC); F(b.V, (size_t)R * 3 * VC);
+            W(b.Vh, (size_t)R * 3 * VHE); W(b.Vu, (size_t)R * 3 * VC); W(b.sh, (size_t)R * VHE); W(b.pre, (size_t)R * S); W(b.s, (size_t)R * S);
+            W(b.gate, (size_t)R * VC); W(b.V, (size_t)R * 3 * VC);
         }
-        for (int k = 0; k < 2; ++k) { F(T->ds[k], (size_t)R * SI); F(T->dV[k], (size_t)R * 3 * VHE); }
-        F(T->dVh, (size_t)R * 3 * VHE); F(T->dsh, (size_t)R * VHE); F(T->dgate, (size_t)R * VC);
-        F(T->unit, (size_t)R * 3); F(T->rbf, (size_t)R * RBF); F(T->sin, (size_t)R * SI); F(T->vin, (size_t)R * 3 * VHE); F(T->dxe, (size_t)R * 3);
-        F(T->U, N * S); F(T->scale, N); F(T->tmp_s, N * S); F(T->tmp_v, N * 3 * VC); F(T->s1, N * S); F(T->v1, N * 3 * VC);
-        F(T->sb, N * S); F(T->vb, N * 3 * VC); F(T->gn_s, N * S); F(T->gn_v, N * 3 * VC);
-        F(T->grs, nr * S); F(T->grv, nr * 3 * VC); F(T->gro_s, nr * S); F(T->gro_v, nr * 3 * VC);
-        for (int k = 0; k < 2; ++k) { F(T->gks[k], nk * S); F(T->gkv[k], nk * 3 * VC); }
-        F(T->gkx, nk * 3); F(T->z, max_B);
-        F(T->part, GRAD_PART_FLOATS); F(T->wsg_pack, (size_t)ws_gemm_pack_floats()); F(T->ones, 8);
-        F(T->colpart, colpart_floats(R));
-        I(T->bidx[0], nr); I(T->bidx[1], nk); I(T->kp_ptr, max_B + 1);
-        I(T->rk_src, cap_rk); I(T->rk_dst, cap_rk); I(T->rk_rowptr, nk + 1);
-        I(T->off_tmp, max_B + 2); I(T->xm_src, cap_rk); I(T->xm_dst, cap_rk); I(T->xm_rowptr, nr + 1); I(T->rad_tmp, 2 * max_B + 4);
-        I(T->cursor, N);
-        I(T->scsr_rr.perm, std::max<int>(max_n_rr, 1)); I(T->scsr_rr.rowptr, nr + 1);
-        I(T->scsr_rk.perm, cap_rk); I(T->scsr_rk.rowptr, nr + 1);
-        I(T->kk_rowptr, nk + 1); I(T->deg_tmp, nk); I(T->kk_off, max_B + 1);
-        if (pass == 0) KPD_TRY(T->ws.reserve(bytes + 4096));
-    }
-    KPD_REQUIRE(T->kk_off != nullptr, KPD_ERR_HIP, "workspace arena too small (internal sizing error)");
+        for (int k = 0; k < 2; ++k) { W(T->ds[k], (size_t)R * SI); W(T->dV[k], (size_t)R * 3 * VHE); }
+        W(T->dVh, (size_t)R * 3 * VHE); W(T->dsh, (size_t)R * VHE); W(T->dgate, (size_t)R * VC);
+        W(T->unit, (size_t)R * 3); W(T->rbf, (size_t)R * RBF); W(T->sin, (size_t)R * SI); W(T->vin, (size_t)R * 3 * VHE); W(T->dxe, (size_t)R * 3);
+        W(T->U, N * S); W(T->scale, N); W(T->tmp_s, N * S); W(T->tmp_v, N * 3 * VC); W(T->s1, N * S); W(T->v1, N * 3 * VC);
+        W(T->sb, N * S); W(T->vb, N * 3 * VC); W(T->gn_s, N * S); W(T->gn_v, N * 3 * VC);
+        W(T->grs, nr * S); W(T->grv, nr * 3 * VC); W(T->gro_s, nr * S); W(T->gro_v, nr * 3 * VC);
+        for (int k = 0; k < 2; ++k) { W(T->gks[k], nk * S); W(T->gkv[k], nk * 3 * VC); }
+        W(T->gkx, nk * 3); W(T->z, max_B);
+        W(T->part, GRAD_PART_FLOATS); W(T->wsg_pack, (size_t)ws_gemm_pack_floats()); W(T->ones, 8);
+        W(T->colpart, colpart_floats(R));
+        W(T->bidx[0], nr); W(T->bidx[1], nk); W(T->kp_ptr, max_B + 1);
+        W(T->rk_src, cap_rk); W(T->rk_dst, cap_rk); W(T->rk_rowptr, nk + 1);
+        W(T->off_tmp, max_B + 2); W(T->xm_src, cap_rk); W(T->xm_dst, cap_rk); W(T->xm_rowptr, nr + 1); W(T->rad_tmp, 2 * max_B + 4);
+        W(T->cursor, N);
+        W(T->scsr_rr.perm, std::max<int>(max_n_rr, 1)); W(T->scsr_rr.rowptr, nr + 1);
+        W(T->scsr_rk.perm, cap_rk); W(T->scsr_rk.rowptr, nr + 1);
+        W(T->kk_rowptr, nk + 1); W(T->deg_tmp, nk); W(T->kk_off, max_B + 1);
+    }));
     T->part_floats = GRAD_PART_FLOATS;
     T->colpart_blocks = cdiv(R, HEAD_ROWS);
     T->cap_B = max_B; T->cap_rec = max_n_rec; T->cap_rr = max_n_rr; T->cap_maxrec = max_rec_pg; T->cap_rk = cap_rk; T->cap_R = R;
