@@ -99,7 +99,9 @@ kpd_status kpd_build_lig_graph(const kpd_batch *batch, float ll_cutoff, int32_t 
 typedef struct kpd_egnn_config {
     int32_t atom_nf, rec_nf;
     int32_t n_layers, hidden_nf;       /* hidden_nf 1 .. 256 (the kernels are 256 + 1 wide; narrower models run zero padded: the reference's
-                                          default ctor is 255); > 256 is refused (INTEGRATION.md section 1 lists the limits) */
+                                          default ctor is 255); 257 .. 1024 for inference on the composed wide path (csrc/egnn_wide.hip:
+                                          fp32 only, debug taps layers= / prune= only, no kpd_egnn_profile); the trainer takes <= 256;
+                                          > 1024 is refused (INTEGRATION.md section 1 lists the limits) */
     int32_t use_tanh, norm, update_kp_feat;
     float message_norm;                /* 0 => per-graph average in-degree + 1           */
     int32_t ll_k, kl_k;                /* 0 = radius graph (the cutoffs below), else kNN, <= 16 */

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "egnn_kernels.h"
+#include "egnn_wide.h"
 #include "mfma_core.h"
 
 using namespace kpd;
@@ -99,6 +100,7 @@ struct kpd_egnn {
     float *z[2];
     int *meta, *ll_deg, *ll_off, *kl_off, *kl_pg;
     kpd_lig_graph lg;
+    EgnnWide *wide = nullptr;                  // hidden_nf > 256: the composed wide path (egnn_wide.hip) serves every entry point
 };
 
 static kpd_status build_weight_arena(kpd_egnn *m) {
@@ -165,8 +167,10 @@ extern "C" kpd_status kpd_egnn_create(const kpd_egnn_config *cfg, kpd_egnn **out
     // hidden_nf < 256 runs on the same kernels: features live in columns 0 .. hidden_nf - 1 of the 256-wide layout, the timestep
     // stays in column 256, the columns between hold zeros (zero weight rows / columns, kpd_egnn_load_weight), LayerNorm takes its
     // width at run time
-    KPD_REQUIRE(cfg->hidden_nf >= 1 && cfg->hidden_nf <= HID, KPD_ERR_INVALID, "hidden_nf=%d: the HIP path covers 1 .. 256", cfg->hidden_nf);
-    KPD_REQUIRE(cfg->hidden_nf == HID || cfg->rec_nf != cfg->hidden_nf, KPD_ERR_INVALID,
+    // hidden_nf 257 .. 1024 (inference only): the wide path of egnn_wide.hip behind the same handle
+    KPD_REQUIRE(cfg->hidden_nf >= 1 && cfg->hidden_nf <= WIDE_MAX_HID, KPD_ERR_INVALID, "hidden_nf=%d: the HIP path covers 1 .. %d",
+                cfg->hidden_nf, WIDE_MAX_HID);
+    KPD_REQUIRE(cfg->hidden_nf >= HID || cfg->rec_nf != cfg->hidden_nf, KPD_ERR_INVALID,
                 "rec_nf == hidden_nf = %d (identity keypoint encoder, dynamics.py:326-334) is implemented for hidden_nf = 256 only", cfg->hidden_nf);
     KPD_REQUIRE(cfg->ll_k >= 0 && cfg->ll_k <= KL_KMAX, KPD_ERR_INVALID, "ll_k=%d outside 0..%d (0 = radius graph)", cfg->ll_k, KL_KMAX);
     KPD_REQUIRE(cfg->kl_k >= 0 && cfg->kl_k <= KL_KMAX, KPD_ERR_INVALID, "kl_k=%d outside 0..%d (0 = radius graph)", cfg->kl_k, KL_KMAX);
@@ -180,6 +184,15 @@ extern "C" kpd_status kpd_egnn_create(const kpd_egnn_config *cfg, kpd_egnn **out
     if (st != KPD_OK) return st;
     kpd_egnn *m = new kpd_egnn();
     m->cfg = *cfg;
+    if (cfg->hidden_nf > HID) {
+        st = wide_create(*cfg, &m->wide);
+        if (st != KPD_OK) {
+            delete m;
+            return st;
+        }
+        *out = m;
+        return KPD_OK;
+    }
     if (const char *e = getenv("KPD_GEMM")) m->gemm_mode = !strcmp(e, "f16x2") ? 1 : 0;
     m->h_parts = tool_env_int("KPD_H_PARTS", m->h_parts);      // (TOOLS build only)
     m->n_et = cfg->update_kp_feat ? 4 : 2;
@@ -205,6 +218,7 @@ extern "C" kpd_status kpd_egnn_create(const kpd_egnn_config *cfg, kpd_egnn **out
 
 extern "C" void kpd_egnn_destroy(kpd_egnn *m) {
     if (!m) return;
+    wide_destroy(m->wide);
     for (hipEvent_t e : m->prof_ev) (void)hipEventDestroy(e);
     if (m->edge_dbg) (void)hipFree(m->edge_dbg);
     if (m->stamps) (void)hipFree(m->stamps);
@@ -291,6 +305,7 @@ extern "C" kpd_status kpd_egnn_load_weight(kpd_egnn *m, const char *name, const 
                                            int32_t ndim, void *stream) {
     KPD_REQUIRE(m && name && w && shape, KPD_ERR_INVALID, "null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m->wide) return wide_load_weight(m->wide, name, w, shape, ndim, st);
     const kpd_egnn_config &c = m->cfg;
     const std::string nm(name);
     if (!m->expected.count(nm)) {
@@ -443,6 +458,7 @@ extern "C" kpd_status kpd_egnn_load_weight(kpd_egnn *m, const char *name, const 
 
 extern "C" kpd_status kpd_egnn_commit(kpd_egnn *m) {
     KPD_REQUIRE(m, KPD_ERR_INVALID, "null handle");
+    if (m->wide) return wide_commit(m->wide);
     for (const std::string &n : m->expected)
         if (!m->loaded.count(n)) {
             set_error("weight '%s' was never loaded (%zu of %zu loaded)", n.c_str(), m->loaded.size(), m->expected.size());
@@ -482,6 +498,7 @@ extern "C" kpd_status kpd_egnn_reserve(kpd_egnn *m, int32_t max_B, int32_t max_n
     KPD_REQUIRE(m, KPD_ERR_INVALID, "null handle");
     KPD_REQUIRE(max_B >= 1 && max_n_lig >= 1 && max_n_kp >= 1 && max_n_kk >= 0 && max_lig_pg >= 1 && max_kp_pg >= 1,
                 KPD_ERR_INVALID, "reserve: non-positive size");
+    if (m->wide) return wide_reserve(m->wide, max_B, max_n_lig, max_n_kp, max_n_kk, max_lig_pg, max_kp_pg);
     if (max_B <= m->cap_B && max_n_lig <= m->cap_lig && max_n_kp <= m->cap_kp && max_n_kk <= m->cap_kk &&
         max_lig_pg <= m->cap_maxlig && max_kp_pg <= m->cap_maxkp)
         return KPD_OK;
@@ -528,15 +545,16 @@ extern "C" kpd_status kpd_egnn_reserve(kpd_egnn *m, int32_t max_B, int32_t max_n
 extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const float *t_dev, float *eps_h, float *eps_x,
                                        void *stream) {
     KPD_REQUIRE(m && bt && t_dev && eps_h && eps_x, KPD_ERR_INVALID, "null argument");
-    KPD_REQUIRE(m->committed, KPD_ERR_STATE, "kpd_egnn_forward before kpd_egnn_commit");
+    KPD_REQUIRE(m->wide || m->committed, KPD_ERR_STATE, "kpd_egnn_forward before kpd_egnn_commit");
     KPD_REQUIRE(bt->B >= 1 && bt->n_lig >= 1 && bt->n_kp >= 1, KPD_ERR_INVALID, "empty batch (B=%d n_lig=%d n_kp=%d)", bt->B, bt->n_lig, bt->n_kp);
+    KPD_REQUIRE(!m->cfg.update_kp_feat || bt->n_kk == 0 || (bt->kk_src && bt->kk_dst), KPD_ERR_INVALID, "kk edges missing");
+    KPD_REQUIRE(bt->kk_rowptr, KPD_ERR_INVALID, "kk_rowptr missing");
+    if (m->wide) return wide_forward(m->wide, bt, t_dev, eps_h, eps_x, static_cast<hipStream_t>(stream));
     KPD_REQUIRE(bt->B <= m->cap_B && bt->n_lig <= m->cap_lig && bt->n_kp <= m->cap_kp && bt->n_kk <= m->cap_kk &&
                     bt->max_lig <= m->cap_maxlig && bt->max_kp <= m->cap_maxkp,
                 KPD_ERR_CAPACITY, "batch (B=%d lig=%d kp=%d kk=%d maxlig=%d maxkp=%d) exceeds reserved workspace (%d %d %d %d %d %d)",
                 bt->B, bt->n_lig, bt->n_kp, bt->n_kk, bt->max_lig, bt->max_kp, m->cap_B, m->cap_lig, m->cap_kp, m->cap_kk,
                 m->cap_maxlig, m->cap_maxkp);
-    KPD_REQUIRE(!m->cfg.update_kp_feat || bt->n_kk == 0 || (bt->kk_src && bt->kk_dst), KPD_ERR_INVALID, "kk edges missing");
-    KPD_REQUIRE(bt->kk_rowptr, KPD_ERR_INVALID, "kk_rowptr missing");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const kpd_egnn_config &c = m->cfg;
 
@@ -684,6 +702,7 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
 extern "C" kpd_status kpd_egnn_debug_state(kpd_egnn *m, const char *what, float *out, int64_t n_floats, void *stream) {
     KPD_REQUIRE(m && what && out, KPD_ERR_INVALID, "null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m->wide) return wide_debug_state(m->wide, what, out, n_floats, st);
     const std::string w(what);
     const float *src = nullptr;
     if (w == "h_lig") src = m->h[0];
@@ -736,6 +755,8 @@ extern "C" kpd_status kpd_egnn_debug_state(kpd_egnn *m, const char *what, float 
 
 extern "C" kpd_status kpd_egnn_profile(kpd_egnn *m, int32_t enable) {
     KPD_REQUIRE(m, KPD_ERR_INVALID, "null handle");
+    KPD_REQUIRE(!m->wide, KPD_ERR_INVALID, "kpd_egnn_profile times the fused edge kernel of hidden_nf <= 256; hidden_nf = %d has none",
+                m->cfg.hidden_nf);
     if (enable && m->prof_ev.empty()) {
         m->prof_ev.resize(2 * 8192);
         for (hipEvent_t &e : m->prof_ev) KPD_HIP(hipEventCreate(&e));
@@ -747,6 +768,7 @@ extern "C" kpd_status kpd_egnn_profile(kpd_egnn *m, int32_t enable) {
 
 extern "C" kpd_status kpd_egnn_profile_read(kpd_egnn *m, double *total_ms, int32_t *launches) {
     KPD_REQUIRE(m && total_ms && launches, KPD_ERR_INVALID, "null argument");
+    KPD_REQUIRE(!m->wide, KPD_ERR_INVALID, "kpd_egnn_profile_read: no fused edge kernel at hidden_nf = %d", m->cfg.hidden_nf);
     double tot = 0.0;
     for (size_t i = 0; i + 1 < m->prof_used; i += 2) {
         KPD_HIP(hipEventSynchronize(m->prof_ev[i + 1]));
@@ -761,6 +783,7 @@ extern "C" kpd_status kpd_egnn_profile_read(kpd_egnn *m, double *total_ms, int32
 
 extern "C" kpd_status kpd_egnn_last_counts(kpd_egnn *m, int32_t out[8], void *stream) {
     KPD_REQUIRE(m && out, KPD_ERR_INVALID, "null argument");
+    if (m->wide) return wide_last_counts(m->wide, out, static_cast<hipStream_t>(stream));
     for (int i = 0; i < 7; ++i) out[i] = 0;
     out[7] = m->gemm_mode;                                           // GEMM mode the next forward runs in: 0 exact fp32, 1 f16x2
     if (!m->ws.base) return KPD_OK;                                  // no forward yet: only the mode is meaningful

@@ -709,7 +709,9 @@ constexpr int ENC_LD = 512;       // row stride of the encoder / decoder hidden 
 
 extern "C" kpd_status kpd_egnn_trainer_create(const kpd_egnn_config *cfg, kpd_egnn_trainer **out) {
     KPD_REQUIRE(cfg && out, KPD_ERR_INVALID, "null argument");
-    KPD_REQUIRE(cfg->hidden_nf >= 1 && cfg->hidden_nf <= HID, KPD_ERR_INVALID, "hidden_nf=%d outside 1 .. %d", cfg->hidden_nf, HID);
+    KPD_REQUIRE(cfg->hidden_nf >= 1 && cfg->hidden_nf <= HID, KPD_ERR_INVALID,
+                "hidden_nf=%d outside 1 .. %d: training above %d is not implemented (inference covers hidden_nf up to 1024)", cfg->hidden_nf,
+                HID, HID);
     KPD_REQUIRE(cfg->atom_nf >= 1 && cfg->atom_nf <= 256 && cfg->rec_nf >= 1 && cfg->rec_nf <= 256 && cfg->n_layers >= 1 &&
                     cfg->n_layers <= 64,
                 KPD_ERR_INVALID, "atom_nf=%d rec_nf=%d n_layers=%d", cfg->atom_nf, cfg->rec_nf, cfg->n_layers);

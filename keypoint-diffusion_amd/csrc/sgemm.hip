@@ -53,6 +53,7 @@ struct SgemmArgs {
     // of a 257-wide product -- are computed as riders (xr / xc = -1: none), so that they do not cost a row / column of tiles of their own
     int xr, xc;
     float *x_part;          // split-K: per slice [M column-fringe values | N row-fringe values | corner | column sum of the fringe row]
+    const int *m_live;      // k_sgemm<.., LIVE = true> only: device count of the live rows (<= M); workgroups wholly past it exit
 };
 
 // x or +0.0 by a bit mask: the value is consumed on both outcomes, so the load stays unconditional (a select lets the compiler sink the
@@ -151,9 +152,10 @@ struct TileLoader {
     }
 };
 
-template <int WM, int WN, bool TA, bool TB>
+template <int WM, int WN, bool TA, bool TB, bool LIVE = false>
 __global__ __launch_bounds__(256, 2) void k_sgemm(SgemmArgs a) {
     constexpr int BM = 128 * WM, BN = 32 * WN;
+    if (LIVE && (int)blockIdx.x * BM >= *a.m_live) return;       // (uniform over the workgroup, before any barrier)
     constexpr int STAGE = (BM + BN) * SG_BK;                     // floats of one LDS stage: A tile, then B tile
     extern __shared__ __attribute__((aligned(16))) float smem[];  // a.stages stages
     typedef TileLoader<BM, !TA> LA;                               // op(A)[m][k]: contiguous along k unless transposed
@@ -424,7 +426,16 @@ kpd_status launch_one(dim3 grid, hipStream_t st, const SgemmArgs &a) {
 }
 
 template <int WM, int WN>
+kpd_status launch_live(dim3 grid, hipStream_t st, const SgemmArgs &a) {
+    constexpr int stage_bytes = (128 * WM + 32 * WN) * SG_BK * 4;
+    KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_sgemm<WM, WN, false, true, true>), SG_MAX_STAGES * stage_bytes));
+    hipLaunchKernelGGL((k_sgemm<WM, WN, false, true, true>), grid, dim3(256), a.stages * stage_bytes, st, a);
+    return KPD_OK;
+}
+
+template <int WM, int WN>
 kpd_status launch_shape(bool tA, bool tB, dim3 grid, hipStream_t st, const SgemmArgs &a) {
+    if (a.m_live) return launch_live<WM, WN>(grid, st, a);
     if (!tA && tB) return launch_one<WM, WN, false, true>(grid, st, a);
     if (!tA && !tB) return launch_one<WM, WN, false, false>(grid, st, a);
     if (tA && !tB) return launch_one<WM, WN, true, false>(grid, st, a);
@@ -963,13 +974,14 @@ static kpd_status launch_reduce(const RedArgs &r, hipStream_t st) {
 
 kpd_status sgemm(bool tA, bool tB, int M, int N, int K, float alpha, const float *A, int lda, const float *B, int ldb, float beta,
                  float *C, int ldc, hipStream_t st, float *part, size_t part_floats, float *colsum, const float *silu_pre, const float *bias,
-                 float *act_out) {
+                 float *act_out, const int *m_live) {
     if (M <= 0 || N <= 0) return KPD_OK;
     KPD_REQUIRE(A && B && C && K > 0, KPD_ERR_INVALID, "sgemm: null operand or empty K (M=%d N=%d K=%d)", M, N, K);
+    KPD_REQUIRE(!m_live || (!tA && tB && !part), KPD_ERR_INVALID, "sgemm: a live row count goes with unsplit A B^T products only");
     KPD_REQUIRE(!colsum || (tA && !tB), KPD_ERR_INVALID, "sgemm: column sums ride along with A^T B products only");
     SgemmArgs a;
     a.colsum = colsum; a.cs_part = nullptr; a.silu_pre = silu_pre; a.bias = bias; a.act_out = act_out;
-    a.xr = a.xc = -1; a.x_part = nullptr;
+    a.xr = a.xc = -1; a.x_part = nullptr; a.m_live = m_live;
     if (silu_pre || bias || act_out) part = nullptr;          // these epilogues live in the product kernel: no split along K
     a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.alpha = alpha; a.beta = beta;
     a.vecA = ((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 3) == 0) ? 1 : 0;

@@ -109,6 +109,9 @@ class LigRecDynamics(nn.Module):
         super().__init__()
         if act_fn is not nn.SiLU:
             raise NotImplementedError('only SiLU activations are implemented (every shipped config)')
+        if not 1 <= int(hidden_nf) <= 1024:
+            # the HIP engine covers 1 .. 256 (inference and training) and 257 .. 1024 (inference only)
+            raise ValueError(f'hidden_nf={hidden_nf}: the EGNN denoiser covers hidden_nf 1 .. 1024 (training up to 256)')
         self.atom_nf, self.rec_nf, self.n_layers, self.hidden_nf = atom_nf, rec_nf, n_layers, hidden_nf
         self.use_tanh, self.message_norm, self.norm = use_tanh, message_norm, norm
         self.no_cg, self.n_keypoints, self.graph_cutoffs = no_cg, n_keypoints, graph_cutoffs
@@ -185,7 +188,7 @@ class LigRecDynamics(nn.Module):
             self._engine.set_gemm_mode(self.gemm_mode)            # (one library call per engine and choice, not per forward)
             if self._engine.gemm_mode() != self.gemm_mode:        # an explicit choice is never dropped silently
                 raise hip.KpdError(f'gemm_mode={self.gemm_mode!r} was requested but the engine runs {self._engine.gemm_mode()!r} '
-                                   f'(the f16x2 mode of the GVP denoiser needs n_hidden_scalars = 256)')
+                                   f'(the f16x2 mode needs hidden_nf <= 256 for the EGNN denoiser, n_hidden_scalars = 256 for the GVP one)')
             self._engine._mode_applied = self.gemm_mode
         return self._engine
 

@@ -307,7 +307,7 @@ class EgnnEngine:
         self.cfg = KpdEgnnConfig(int(atom_nf), int(rec_nf), int(n_layers), int(hidden_nf), int(bool(use_tanh)),
                                  int(bool(norm)), int(bool(update_kp_feat)), float(message_norm), int(ll_k), int(kl_k),
                                  float(ll_cutoff), float(kl_cutoff), float(coords_range))
-        self.atom_nf = int(atom_nf)
+        self.atom_nf, self.rec_nf = int(atom_nf), int(rec_nf)
         self._h = C.c_void_p()
         check(lib().kpd_egnn_create(C.byref(self.cfg), C.byref(self._h)))
         self._reserved = None
@@ -341,6 +341,11 @@ class EgnnEngine:
         self.reserve(pb)
         lig_x, lig_h = _dev_f32(lig_x, 'lig x_0'), _dev_f32(lig_h, 'lig h_0')
         kp_x, kp_h = _dev_f32(kp_x, 'kp x_0'), _dev_f32(kp_h, 'kp h_0')
+        # the kernels read atom_nf / rec_nf columns per row: a narrower feature tensor would be read past its end
+        # (upstream's encoder Linears raise on the same mismatch)
+        if tuple(lig_h.shape) != (pb.n_lig, self.atom_nf) or tuple(kp_h.shape) != (pb.n_kp, self.rec_nf):
+            raise KpdError(f'feature shapes lig {tuple(lig_h.shape)} / kp {tuple(kp_h.shape)} do not match the denoiser '
+                           f'(expected ({pb.n_lig}, atom_nf={self.atom_nf}) / ({pb.n_kp}, rec_nf={self.rec_nf}))')
         t = _dev_f32(t, 'timestep')
         eps_h = torch.empty(pb.n_lig, self.atom_nf, device=lig_x.device)
         eps_x = torch.empty(pb.n_lig, 3, device=lig_x.device)
