@@ -39,11 +39,8 @@ typedef enum kpd_status {
 
 const char *kpd_last_error(void);
 int kpd_version(void);
-/* 0 = the product build.  Bit 0 set = the TOOLS build (`make tools`, -DKPD_TOOLS): the only build in which the A/B, ablation and
- * LDS-padding switches of profiles/tools are read from the environment (KPD_EDGE_ABLATE, KPD_EDGE_SPLIT, KPD_*_LDS_PAD,
- * KPD_SGEMM_*, KPD_TRAIN_EPI / _WS / _VEC_FUSED, ...).  bench.py refuses to print a contract line from a library whose flags are not 0.
- * (No reference counterpart: the reference has no build variants; the check exists because a timing library must be able to attest
- * that its kernels cannot be told to skip work.) */
+/* Always 0: the library has one build, and no environment switch of it can make a kernel skip work.  bench.py refuses to print a
+ * contract line from a library whose flags are not 0.  (No reference counterpart: the reference has no build variants.) */
 int kpd_build_flags(void);
 
 /* ---------------------------------------------------------------------------------------
@@ -126,8 +123,7 @@ kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *batch, const float *t_
                             float *eps_h_dev, float *eps_x_dev, void *stream);
 /* Debug/test taps and switches.  Taps copy engine state to out_dev: "h_lig" / "h_kp" (node state, row stride 264), "x_lig" /
  * "x_kp", "z_lig" / "z_kp", "xnm<et>" / "xnc<et>" / "hnm<et>" / "hnc<et>" (segment-sum pieces of edge type et as the last layer
- * left them), "stamps".  Switches (n_floats = 0, out_dev ignored but non-null): "layers=N" (run only the first N layers),
- * "prune=0|1", "stamps=1", and
+ * left them).  Switches (n_floats = 0, out_dev ignored but non-null): "layers=N" (run only the first N layers), "prune=0|1", and
  *   "gemm=f32"   exact fp32 MFMA in every GEMM -- the default and the contract path;
  *   "gemm=f16x2" EXPERIMENTAL, opt-in, never the default and never part of the benchmark's `value`: every fp32 product of the
  *                edge / projection / node-update GEMMs as three f16 MFMA products of hi / lo operand planes with fp32
@@ -164,8 +160,7 @@ kpd_status kpd_egnn_last_counts(kpd_egnn *m, int32_t out[8], void *stream);
  *             d_kp_x [n_kp, 3] may be NULL (written, not accumulated, when given).  Consumes the forward.
  * Memory: reserve() tries to keep the edge activations of every layer (13.5 GB at B = 64 x (300-atom pocket, 25-atom ligand)); if that
  * allocation fails it keeps one layer's worth and recomputes layer by layer in backward (same results, bit for bit).
- * Environment: KPD_TRAIN_STORE=0 (read once per process) selects the recompute mode.  The A/B switches of profiles/tools
- * (KPD_TRAIN_FUSED_*, KPD_SGEMM_*, KPD_TRAIN_WS*, KPD_TRAIN_VEC_FUSED) exist only in the TOOLS build of the library (kpd_build_flags).
+ * Environment: KPD_TRAIN_STORE=0 (read once per process) selects the recompute mode.
  * profile / profile_read: HIP-event time of the two per-layer edge kernels of a training step on their launch stream, as
  * kpd_egnn_profile does for the inference kernel: index 0 = forward (k_egnn_edge_train), 1 = backward (k_egnn_edge_bwd); `edges` =
  * edges those launches processed (for a FLOP count).  No reference counterpart (bench.py's roofline of the training lines).

@@ -81,12 +81,8 @@ struct kpd_egnn {
     int *widen_map = nullptr;
     size_t widen_floats = 0, widen_ints = 0;
     int gemm_mode = 0;                         // 0 exact fp32 MFMA; 1 f16x2 split products in the EGNN GEMMs (KPD_GEMM=f16x2, "gemm=f16x2")
-    int h_parts = 7;                           // diagnostics: which kernels take the f16x2 form (1 edge, 2 projections, 4 node update)
     int prune_last = 1;                        // final layer: only what feeds (h_lig, x_lig) is computed ("prune=0" restores all)
     // optional HIP-event timing of the dominant kernel (k_egnn_edge), for bench.py's roofline
-    unsigned long long *stamps = nullptr;      // device [16], diagnostics (kpd_egnn_debug_state "stamps=1")
-    float *edge_dbg = nullptr;                 // per-row taps of the f16x2 edge kernel's coordinate branch ("edge_dbg=1", -DKPD_EDGE_DBG builds)
-    size_t edge_dbg_floats = 0;
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
     size_t prof_used = 0;
@@ -194,7 +190,6 @@ extern "C" kpd_status kpd_egnn_create(const kpd_egnn_config *cfg, kpd_egnn **out
         return KPD_OK;
     }
     if (const char *e = getenv("KPD_GEMM")) m->gemm_mode = !strcmp(e, "f16x2") ? 1 : 0;
-    m->h_parts = tool_env_int("KPD_H_PARTS", m->h_parts);      // (TOOLS build only)
     m->n_et = cfg->update_kp_feat ? 4 : 2;
     m->n_upd = cfg->update_kp_feat ? 2 : 1;
     m->rec_identity = cfg->rec_nf == cfg->hidden_nf;   // dynamics.py:326-334
@@ -220,8 +215,6 @@ extern "C" void kpd_egnn_destroy(kpd_egnn *m) {
     if (!m) return;
     wide_destroy(m->wide);
     for (hipEvent_t e : m->prof_ev) (void)hipEventDestroy(e);
-    if (m->edge_dbg) (void)hipFree(m->edge_dbg);
-    if (m->stamps) (void)hipFree(m->stamps);
     if (m->widen_buf) (void)hipFree(m->widen_buf);
     if (m->widen_map) (void)hipFree(m->widen_map);
     m->warena.release();
@@ -626,7 +619,7 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
                     pp.n_slots[nt] = k;
                 }
                 pp.tiles0 = cdiv(n[0], TM);
-                pp.gemm_mode = (m->h_parts & 2) ? m->gemm_mode : 0;
+                pp.gemm_mode = m->gemm_mode;
                 KPD_TRY(launch_proj_chain(pp, st));
             }
         }
@@ -636,10 +629,8 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
         ea.meta = last ? m->meta + 16 : m->meta;
         ea.x[0] = m->x[0]; ea.x[1] = m->x[1]; ea.P[0] = m->P[0]; ea.P[1] = m->P[1];
         ea.use_tanh = c.use_tanh; ea.coords_range = c.coords_range;
-        ea.stamps = m->stamps;
-        ea.dbg = m->edge_dbg;
         ea.tile_rows = tr;
-        ea.gemm_mode = (tr == TM && (m->h_parts & 1)) ? m->gemm_mode : 0;
+        ea.gemm_mode = tr == TM ? m->gemm_mode : 0;
         for (int et = 0; et < 4; ++et) {
             ea.src[et] = esrc[et]; ea.dst[et] = edst[et];
             ea.src_nt[et] = kSrcNt[et]; ea.dst_nt[et] = kDstNt[et]; ea.src_slot[et] = kSrcSlot[et]; ea.dst_slot[et] = kDstSlot[et];
@@ -689,8 +680,7 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
                 if (!na.do_update && !na.do_proj) na.u.n = 0;          // nothing to do for this node type
             }
             lp.tiles0 = cdiv(lp.nt[0].u.n, TN);
-            lp.stamps = m->stamps ? m->stamps + 16 : nullptr;
-            lp.gemm_mode = (m->h_parts & 4) ? m->gemm_mode : 0;
+            lp.gemm_mode = m->gemm_mode;
             KPD_TRY(launch_node_layer(lp, st));
         }
     }
@@ -727,25 +717,6 @@ extern "C" kpd_status kpd_egnn_debug_state(kpd_egnn *m, const char *what, float 
         KPD_REQUIRE(v == "f32" || v == "f16x2", KPD_ERR_INVALID, "gemm mode must be f32 or f16x2");
         KPD_REQUIRE(v == "f32" || !m->committed || m->f16_ok, KPD_ERR_WEIGHTS, "%s", F16_RANGE_ERROR);
         m->gemm_mode = v == "f16x2" ? 1 : 0;
-        return KPD_OK;
-    } else if (w == "edge_dbg=1") {          // allocate the per-row tap buffer for the current workspace ([tile_cap][64][4] floats)
-        KPD_REQUIRE(m->tile_cap > 0, KPD_ERR_STATE, "edge_dbg=1 needs a reserved workspace");
-        if (m->edge_dbg) (void)hipFree(m->edge_dbg);
-        m->edge_dbg_floats = (size_t)m->tile_cap * (TM * 4 + 3 * 4 * 64 * 12);      // per-row taps, then per-tile operand taps of rows 0..2 of every wave
-        KPD_HIP(hipMalloc(reinterpret_cast<void **>(&m->edge_dbg), m->edge_dbg_floats * 4));
-        KPD_HIP(hipMemsetAsync(m->edge_dbg, 0, m->edge_dbg_floats * 4, st));
-        return KPD_OK;
-    } else if (w == "edge_dbg") {
-        KPD_REQUIRE(m->edge_dbg && (size_t)n_floats <= m->edge_dbg_floats, KPD_ERR_INVALID, "edge_dbg not enabled or request too large");
-        KPD_HIP(hipMemcpyAsync(out, m->edge_dbg, (size_t)n_floats * 4, hipMemcpyDeviceToDevice, st));
-        return KPD_OK;
-    } else if (w == "stamps=1") {            // start accumulating per-phase cycle sums of the edge kernel
-        if (!m->stamps) KPD_HIP(hipMalloc(reinterpret_cast<void **>(&m->stamps), 32 * sizeof(unsigned long long)));
-        KPD_HIP(hipMemsetAsync(m->stamps, 0, 32 * sizeof(unsigned long long), st));
-        return KPD_OK;
-    } else if (w == "stamps") {              // read them back (as 32 floats: lo/hi 24-bit split is avoided by copying raw)
-        KPD_REQUIRE(m->stamps && n_floats >= 64, KPD_ERR_INVALID, "stamps not enabled or buffer < 64 floats");
-        KPD_HIP(hipMemcpyAsync(out, m->stamps, 32 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
         return KPD_OK;
     }
     KPD_REQUIRE(src, KPD_ERR_INVALID, "unknown debug tap '%s'", what);

@@ -52,13 +52,10 @@ struct EdgeArgs {
     float *xn_main[4], *xn_cont[4];
     int use_tanh;
     float coords_range;
-    unsigned long long *stamps;     // [16] phase-cycle sums, diagnostics only (null in production)
     const void *wh_e[4], *wh_c[4];  // f16x2 mode: W2 of edge_mlp / coord_mlp as f16 hi / lo planes (pack_f16_split)
     int gemm_mode;                  // 0: exact fp32 MFMA (contract path), 1: f16x2 split products (opt-in)
     int tile_rows;                  // edges per tile: 64 (TM)
-    int ablate;                     // timing experiments only (KPD_EDGE_ABLATE), 0 in production
     int split_slots;                // workgroup slots per XCD (set by the launcher): the tiles of an XCD's last round run one branch per work item; 0: off
-    float *dbg;                     // [tiles][64][4] per-row taps of the coordinate branch (builds with -DKPD_EDGE_DBG only; "edge_dbg=1")
 };
 
 // Forward edge kernel of the EGNN trainer (k_egnn_edge_train): the inference kernel's program on the current weights, keeping what the
@@ -78,8 +75,6 @@ struct EdgeTrainArgs {
     float coords_range;
     float *keep[4][2][4];           // [et][branch][pre1, a1, pre2, a2], each [E][HS]
     float *att[4], *sc[4], *dij[4], *xdiff[4], *nvec[4];
-    unsigned long long *stamps;     // [64] phase-cycle sums of both training edge kernels (TOOLS build, KPD_TRAIN_STAMPS; null in production)
-    int skip;                       // TOOLS build (KPD_TR_SKIP): bit 0 / 1 / 2 = leave out the pre1 + a1 / pre2 / geometry stores (timing experiments; results are wrong)
 };
 
 struct EdgePackEntry {
@@ -112,8 +107,6 @@ struct EdgeBwdArgs {
     int part_ld;
     int use_tanh;
     float coords_range;
-    unsigned long long *stamps;     // as EdgeTrainArgs (slots 32 ..)
-    int skip;                       // TOOLS build (KPD_TR_SKIP): bit 3 / 4 = leave out the dpre2 / dpre1 stores
 };
 
 struct NodeArgs {
@@ -148,8 +141,6 @@ struct NodeLayerArgs {
 struct NodeLayerPair {
     NodeLayerArgs nt[2];
     int tiles0;                     // 32-node tiles of nt[0]
-    unsigned long long *stamps;     // [16] phase-cycle sums (diagnostics only, null in production)
-    int dbg;                        // ablation switches for timing experiments (KPD_NODE_ABLATE), 0 in production
     int gemm_mode;                  // 0: exact fp32 MFMA, 1: f16x2 split (k_node_update8_h)
 };
 

@@ -250,7 +250,7 @@ __device__ __forceinline__ void edge_gather_finish(const EdgeGather<NW> &g, cons
     constexpr int RPW = TM / NW;
     const f32x4 w0 = reinterpret_cast<const f32x4 *>(wr)[lane];
     // the wave's RPW distances in RPW / 4 broadcast reads up front instead of a read + wait per row: -1.0 % on the kernel, same-call A/B
-    // (0.877 vs 0.886 ms).  The f16x2 kernel keeps the per-row form (edge_gather_finish_h, KPD_H_BATCH_D): there the batched read came
+    // (0.877 vs 0.886 ms).  The f16x2 kernel keeps the per-row form (edge_gather_finish_h): there the batched read came
     // with a first-forward deviation; every detector of that (profiles/tools/repro_*.py, cold_*_check.py, tests/test_cold_start_gpu.py)
     // is clean for this kernel.
     f32x4 dv[(RPW + 3) / 4];
@@ -311,22 +311,12 @@ __device__ __forceinline__ void store_T_silu_w(float *T, const f32x16 (&acc)[2][
     if ((tid % TPR) == 0) T[(tid / TPR) * SA + 256] = PRE ? silu_pre(ex) : silu(ex + b[256]);
 }
 
-// Phase stamps (diagnostic builds of the timeline only; a.stamps is null in production): wave 0 of
-// every workgroup adds the s_memtime delta of each phase to a.stamps[phase].
-#define KPD_STAMP(idx)                                                                     \
-    if (a.stamps && tid == 0) {                                                            \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                      \
-        atomicAdd(&a.stamps[idx], (unsigned long long)(now_ - t_prev_));                   \
-        t_prev_ = now_;                                                                    \
-    }
-
 template <int NW>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge(EdgeArgs a) {
     constexpr int TPR = NW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EdgeSmem s = edge_smem(smem);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    unsigned long long t_prev_ = a.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
     // tile decode (XCD-aware: consecutive tiles -- neighbouring edges of one complex, which
     // share P rows -- go to the same XCD / L2)
     const int T = a.meta[8];
@@ -406,7 +396,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge(EdgeArgs
     [[maybe_unused]] BPrefetch bpre;
     if constexpr (NW == 4) gemm_b_prefetch(bpre, (bsel & 1) ? a.wp_e[et] : a.wp_c[et], wave, lane);     // lands during the gather / A-build
     lds_barrier();
-    KPD_STAMP(0)
 
     const int first_is_cont = s.misc[0];
     const unsigned long long endmask =
@@ -416,124 +405,99 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge(EdgeArgs
     EdgeGather<NW == 4 ? 4 : TM> gc;      // (one row per wave, unused, in the 8-wave build)
 
     // ---- feature messages: m = edge_mlp(f); msg_h = m * sigmoid(att(m)) (dynamics.py:111-112)
-    // timing experiments of the TOOLS build only (KPD_EDGE_ABLATE: 1 no GEMM, 2 no A-build, 4 no epilogues); the constant 0 in the product
-    const int abl = KPD_TOOL_SWITCH(a.ablate, 0);
     if (bsel & 1) {
-    if (!(abl & 2)) edge_gather_finish<NW>(ge, s, a.wr_e[et], wave, lane);
+    edge_gather_finish<NW>(ge, s, a.wr_e[et], wave, lane);
     lds_barrier();
-    KPD_STAMP(1)
     acc_zero_w<NW>(acc);
-    ex = (abl & 4) ? 0.0f : row_dot_chunks<TPR>(s.A, s.wv + 2 * HS, KP / 4, tid);
-    if (!(abl & 1)) {
-        if constexpr (NW == 4) gemm_rows64_pre<NG, SA>(s.A, a.wp_e[et], acc, wave, lane, bpre);
-        else gemm_rows64_w<NW, NG, SA>(s.A, a.wp_e[et], acc, wave, lane);
-    }
+    ex = row_dot_chunks<TPR>(s.A, s.wv + 2 * HS, KP / 4, tid);
+    if constexpr (NW == 4) gemm_rows64_pre<NG, SA>(s.A, a.wp_e[et], acc, wave, lane, bpre);
+    else gemm_rows64_w<NW, NG, SA>(s.A, a.wp_e[et], acc, wave, lane);
     if constexpr (NW == 4) gemm_b_prefetch(bpre, a.wp_c[et], wave, lane);     // for the coordinate GEMM, four phases away
     lds_barrier();
-    KPD_STAMP(2)
-    if (!(abl & 4)) store_T_silu_w<NW, true>(s.A, acc, ex, a.b_e[et], tid, wave, lane);
-    else if (acc[0][0][0] == 12345.0f) s.A[tid] = acc[1][NW == 4 ? 1 : 0][3] + acc[0][NW == 4 ? 1 : 0][5] + acc[1][0][7];
+    store_T_silu_w<NW, true>(s.A, acc, ex, a.b_e[et], tid, wave, lane);
     if constexpr (NW == 4) {  // the coordinate branch's P rows start travelling now; consumed after the segmented sum below
-        if (!(abl & 2) && (bsel & 2)) {
-        edge_gather_issue<NW>(gc, s, Ps + HS, Pd + HS, wave, lane);
-        __builtin_amdgcn_sched_barrier(0);
+        if (bsel & 2) {
+            edge_gather_issue<NW>(gc, s, Ps + HS, Pd + HS, wave, lane);
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
     lds_barrier();
-    KPD_STAMP(3)
-    if (!(abl & 4)) {
-        float dot = row_dot_chunks<TPR>(s.A, s.wv, 64, tid);
-        const int row = tid / TPR;
-        if ((tid % TPR) == 0) {
-            dot = fmaf(s.A[row * SA + 256], s.wv[256], dot);
-            // T holds c * m, w_att carries 1 / c; the returned weight carries 1 / c so that T * att = m * sigmoid(.)
-            s.att[row] = row < ne ? sigmoidf_(dot + s.wv[ATT_BIAS_AT]) * (1.0f / SILU_C) : 0.0f;
-        }
+    float dot = row_dot_chunks<TPR>(s.A, s.wv, 64, tid);
+    const int row = tid / TPR;
+    if ((tid % TPR) == 0) {
+        dot = fmaf(s.A[row * SA + 256], s.wv[256], dot);
+        // T holds c * m, w_att carries 1 / c; the returned weight carries 1 / c so that T * att = m * sigmoid(.)
+        s.att[row] = row < ne ? sigmoidf_(dot + s.wv[ATT_BIAS_AT]) * (1.0f / SILU_C) : 0.0f;
     }
     lds_barrier();
-    KPD_STAMP(4)
-    if (!(abl & 4)) {
-        // segmented sum over dst (dynamics.py:182-185): thread = column, rows in order; the run
-        // boundaries are wave-uniform (endmask), LDS reads are issued 16 rows at a time
-        float *hmain = a.hn_main[et], *hcont = a.hn_cont[et] + (size_t)tile_in_et * HS;
-        if (tid < 256) {
-            float run = 0.0f;
-            int piece = 0;
+    // segmented sum over dst (dynamics.py:182-185): thread = column, rows in order; the run
+    // boundaries are wave-uniform (endmask), LDS reads are issued 16 rows at a time
+    float *hmain = a.hn_main[et], *hcont = a.hn_cont[et] + (size_t)tile_in_et * HS;
+    if (tid < 256) {
+        float run = 0.0f;
+        int piece = 0;
 #pragma unroll 1
-            for (int r0 = 0; r0 < TM; r0 += 16) {
-                if (r0 >= ne) break;
-                float v[16], w[16];
-                int dvv[16];
-                {
-                    typedef int i32x4 __attribute__((ext_vector_type(4)));
+        for (int r0 = 0; r0 < TM; r0 += 16) {
+            if (r0 >= ne) break;
+            float v[16], w[16];
+            int dvv[16];
+            {
+                typedef int i32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const i32x4 t = *reinterpret_cast<const i32x4 *>(s.dst + r0 + 4 * j);
-                        dvv[4 * j] = t[0]; dvv[4 * j + 1] = t[1]; dvv[4 * j + 2] = t[2]; dvv[4 * j + 3] = t[3];
-                    }
+                for (int j = 0; j < 4; ++j) {
+                    const i32x4 t = *reinterpret_cast<const i32x4 *>(s.dst + r0 + 4 * j);
+                    dvv[4 * j] = t[0]; dvv[4 * j + 1] = t[1]; dvv[4 * j + 2] = t[2]; dvv[4 * j + 3] = t[3];
                 }
+            }
 #pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    w[i] = s.att[r0 + i];
-                    v[i] = s.A[(r0 + i) * SA + tid];
-                }
+            for (int i = 0; i < 16; ++i) {
+                w[i] = s.att[r0 + i];
+                v[i] = s.A[(r0 + i) * SA + tid];
+            }
 #pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    run = fmaf(v[i], w[i], run);
-                    if ((endmask >> (r0 + i)) & 1ull) {
-                        float *out = (piece == 0 && first_is_cont) ? hcont : hmain + ((unsigned)dvv[i] / (unsigned)(NSLOT * 4));
-                        out[tid] = run;
-                        run = 0.0f;
-                        ++piece;
-                    }
+            for (int i = 0; i < 16; ++i) {
+                run = fmaf(v[i], w[i], run);
+                if ((endmask >> (r0 + i)) & 1ull) {
+                    float *out = (piece == 0 && first_is_cont) ? hcont : hmain + ((unsigned)dvv[i] / (unsigned)(NSLOT * 4));
+                    out[tid] = run;
+                    run = 0.0f;
+                    ++piece;
                 }
             }
         }
-        // column 256: the weighted values wait in LDS for the scan at the end of the kernel (with the coordinate messages)
-        if (wave == NW - 1) reinterpret_cast<float *>(s.misc + 8)[lane] = s.A[lane * SA + 256] * s.att[lane];
     }
+    // column 256: the weighted values wait in LDS for the scan at the end of the kernel (with the coordinate messages)
+    if (wave == NW - 1) reinterpret_cast<float *>(s.misc + 8)[lane] = s.A[lane * SA + 256] * s.att[lane];
     lds_barrier();
-    KPD_STAMP(5)
     }
 
     // ---- coordinate messages: msg_x = tanh(coord_mlp(f)) * x_diff * range (dynamics.py:113-120)
     if (bsel & 2) {
-    if (!(abl & 2)) {
     if constexpr (NW == 4) {
         if (!(bsel & 1)) edge_gather_issue<NW>(gc, s, Ps + HS, Pd + HS, wave, lane);        // (a coordinate-only work item of the tail)
         edge_gather_finish<NW>(gc, s, a.wr_c[et], wave, lane);
     } else build_edge_A<NW>(s, Ps + HS, Pd + HS, a.wr_c[et], wave, lane);
-    }
     lds_barrier();
-    KPD_STAMP(6)
     acc_zero_w<NW>(acc);
-    ex = (abl & 4) ? 0.0f : row_dot_chunks<TPR>(s.A, s.wv + 3 * HS, KP / 4, tid);
-    if (!(abl & 1)) {
-        if constexpr (NW == 4) gemm_rows64_pre<NG, SA>(s.A, a.wp_c[et], acc, wave, lane, bpre);
-        else gemm_rows64_w<NW, NG, SA>(s.A, a.wp_c[et], acc, wave, lane);
+    ex = row_dot_chunks<TPR>(s.A, s.wv + 3 * HS, KP / 4, tid);
+    if constexpr (NW == 4) gemm_rows64_pre<NG, SA>(s.A, a.wp_c[et], acc, wave, lane, bpre);
+    else gemm_rows64_w<NW, NG, SA>(s.A, a.wp_c[et], acc, wave, lane);
+    lds_barrier();
+    store_T_silu_w<NW, true>(s.A, acc, ex, a.b_c[et], tid, wave, lane);
+    lds_barrier();
+    float dot = row_dot_chunks<TPR>(s.A, s.wv + HS, 64, tid);
+    const int row = tid / TPR;
+    if ((tid % TPR) == 0) {
+        dot = fmaf(s.A[row * SA + 256], s.wv[HS + 256], dot);
+        float c = a.use_tanh ? tanhf(dot) * a.coords_range : dot;
+        if (row >= ne) c = 0.0f;
+        s.mx[3 * row] = c * s.xd[3 * row];
+        s.mx[3 * row + 1] = c * s.xd[3 * row + 1];
+        s.mx[3 * row + 2] = c * s.xd[3 * row + 2];
     }
     lds_barrier();
-    KPD_STAMP(7)
-    if (!(abl & 4)) store_T_silu_w<NW, true>(s.A, acc, ex, a.b_c[et], tid, wave, lane);
-    else if (acc[0][0][0] == 12345.0f) s.A[tid] = acc[1][NW == 4 ? 1 : 0][3] + acc[0][NW == 4 ? 1 : 0][5] + acc[1][0][7];
-    lds_barrier();
-    KPD_STAMP(8)
-    if (!(abl & 4)) {
-        float dot = row_dot_chunks<TPR>(s.A, s.wv + HS, 64, tid);
-        const int row = tid / TPR;
-        if ((tid % TPR) == 0) {
-            dot = fmaf(s.A[row * SA + 256], s.wv[HS + 256], dot);
-            float c = a.use_tanh ? tanhf(dot) * a.coords_range : dot;
-            if (row >= ne) c = 0.0f;
-            s.mx[3 * row] = c * s.xd[3 * row];
-            s.mx[3 * row + 1] = c * s.xd[3 * row + 1];
-            s.mx[3 * row + 2] = c * s.xd[3 * row + 2];
-        }
     }
-    lds_barrier();
-    KPD_STAMP(9)
-    }
-    if (wave == 0 && !(abl & 4)) {
+    if (wave == 0) {
         // segmented inclusive scan across lanes (lane = row), then the last lane of every run writes
         const unsigned long long heads =
             ((unsigned long long)(unsigned)s.misc[5] << 32) | (unsigned long long)(unsigned)s.misc[4];
@@ -567,7 +531,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge(EdgeArgs
             if (bsel & 1) oh[256] = vh;
         }
     }
-    KPD_STAMP(10)
 }
 
 
@@ -578,13 +541,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge(EdgeArgs
 // registers, one 1-KiB row segment per wave store), pre2, a2 (from the accumulators: 32 consecutive columns of two rows per store), the
 // attention weight, the coordinate scalar and the geometry.  It replaces k_edge_pre1 + k_ws_gemm<0> + the head and segmented-sum
 // kernels of the forward pass (three passes over E x 257 matrices less per branch).
-// phase-cycle sums of the training edge kernels (a.stamps is null in production: profiles/tools/train_stamps.sh)
-#define TRAIN_STAMP(idx)                                                                   \
-    if (a.stamps && tid == 0) {                                                            \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                      \
-        atomicAdd(&a.stamps[idx], (unsigned long long)(now_ - t_prev_));                   \
-        t_prev_ = now_;                                                                    \
-    }
 
 struct EdgeKeep {
     float *pre1, *a1, *pre2;               // rows e0 .. of the branch's kept arrays [E][HS]
@@ -674,7 +630,6 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_train(EdgeTrainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EdgeSmem s = edge_smem(smem);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    unsigned long long t_prev_ = a.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
     const int T = a.meta[8];
     const int chunk = (T + 7) >> 3;
     const int bi = blockIdx.x >> 3;
@@ -689,7 +644,6 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_train(EdgeTrainArgs a) {
     const int e0 = tile_in_et * TM;
     const int ne = min(TM, a.meta[et] - e0);
     const int snt = a.src_nt[et], dnt = a.dst_nt[et];
-    const int ne1 = (a.skip & 1) ? 0 : ne, ne2 = (a.skip & 2) ? 0 : ne;      // rows whose kept values are stored (a.skip = 0 outside timing experiments)
     const int *__restrict__ esrc = a.src[et];
     const int *__restrict__ edst = a.dst[et];
     const float *Ps_e = a.P[snt] + (size_t)a.slot[et][0][0] * HS, *Pd_e = a.P[dnt] + (size_t)a.slot[et][0][1] * HS;
@@ -717,7 +671,7 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_train(EdgeTrainArgs a) {
         s.xd[3 * tid] = dx * inv;
         s.xd[3 * tid + 1] = dy * inv;
         s.xd[3 * tid + 2] = dz * inv;
-        if (tid < ne && !(a.skip & 4)) {
+        if (tid < ne) {
             a.dij[et][e] = d;
             float *xo = a.xdiff[et] + (size_t)e * 3, *no = a.nvec[et] + (size_t)e * 3;
             xo[0] = dx; xo[1] = dy; xo[2] = dz;
@@ -744,7 +698,6 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_train(EdgeTrainArgs a) {
     BPrefetch bpre;
     gemm_b_prefetch(bpre, a.wp[et][0], wave, lane);
     lds_barrier();
-    TRAIN_STAMP(0)
 
     // (the run structure is wave-uniform: as scalars -- three vector registers less in a kernel that sat at 256 with 6 spilled)
     const int first_is_cont = __builtin_amdgcn_readfirstlane(s.misc[0]);
@@ -754,18 +707,15 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_train(EdgeTrainArgs a) {
     float ex;
 
     // ---- feature messages (dynamics.py:103-112)
-    edge_gather_finish_train(ge, s, a.wr[et][0], wave, lane, ke, ne1);
+    edge_gather_finish_train(ge, s, a.wr[et][0], wave, lane, ke, ne);
     lds_barrier();
-    TRAIN_STAMP(1)
     acc_zero_w<NW>(acc);
     ex = row_dot_chunks<TPR>(s.A, s.wv + 2 * HS, KP / 4, tid);
     gemm_rows64_pre<NG, SA>(s.A, a.wp[et][0], acc, wave, lane, bpre);
     gemm_b_prefetch(bpre, a.wp[et][1], wave, lane);
     lds_barrier();
-    TRAIN_STAMP(2)
-    store_T_train(s.A, acc, ex, tid, wave, lane, ke, ne2);
+    store_T_train(s.A, acc, ex, tid, wave, lane, ke, ne);
     lds_barrier();
-    TRAIN_STAMP(3)
     {
         float dot = row_dot_chunks<TPR>(s.A, s.wv, 64, tid);
         const int row = tid / TPR;
@@ -777,7 +727,6 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_train(EdgeTrainArgs a) {
         }
     }
     lds_barrier();
-    TRAIN_STAMP(4)
     EdgeGather<NW> gc;
     edge_gather_issue<NW>(gc, s, Ps_c, Pd_c, wave, lane);      // the coordinate branch's rows travel during the segmented sum
     __builtin_amdgcn_sched_barrier(0);
@@ -820,7 +769,6 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_train(EdgeTrainArgs a) {
         if (wave == NW - 1) reinterpret_cast<float *>(s.misc + 8)[lane] = s.A[lane * SA + 256] * s.att[lane];
     }
     lds_barrier();
-    TRAIN_STAMP(5)
 
     // ---- coordinate messages (dynamics.py:113-120)
     // (the second branch takes the thread index through an opaque copy: with the plain one the compiler keeps LDS addresses of the first
@@ -828,17 +776,14 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_train(EdgeTrainArgs a) {
     int tid_c = tid;
     asm volatile("" : "+v"(tid_c));
     const int lane_c = tid_c & 63;
-    edge_gather_finish_train(gc, s, a.wr[et][1], wave, lane_c, kc, ne1);
+    edge_gather_finish_train(gc, s, a.wr[et][1], wave, lane_c, kc, ne);
     lds_barrier();
-    TRAIN_STAMP(6)
     acc_zero_w<NW>(acc);
     ex = row_dot_chunks<TPR>(s.A, s.wv + 3 * HS, KP / 4, tid_c);
     gemm_rows64_pre<NG, SA>(s.A, a.wp[et][1], acc, wave, lane_c, bpre);
     lds_barrier();
-    TRAIN_STAMP(7)
-    store_T_train(s.A, acc, ex, tid_c, wave, lane_c, kc, ne2);
+    store_T_train(s.A, acc, ex, tid_c, wave, lane_c, kc, ne);
     lds_barrier();
-    TRAIN_STAMP(8)
     {
         float dot = row_dot_chunks<TPR>(s.A, s.wv + HS, 64, tid_c);
         const int row = tid_c / TPR;
@@ -880,8 +825,6 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_train(EdgeTrainArgs a) {
             oh[256] = vh;
         }
     }
-    TRAIN_STAMP(9)
-    if (a.stamps && tid == 0) atomicAdd(&a.stamps[15], 1ull);
 }
 
 // ---- backward form (egnn_train.hip, backward pass of the edge MLPs of a layer) ---------------------------------------------------
@@ -1008,7 +951,7 @@ __device__ __forceinline__ void edge_head_bwd_rows(const EdgeBwdSmem &s, const E
                 if (lane == 0) t[0] = gt;
                 *reinterpret_cast<f32x4 *>(s.A + r * SA + 256 + 4 * lane) = t;
             }
-            if (on && !(a.skip & 8)) {
+            if (on) {
                 *reinterpret_cast<f32x4 *>(pre2 + (size_t)(e0 + r) * HS + 4 * lane) = g;
                 if (lane == 0) {
                     pre2[(size_t)(e0 + r) * HS + 256] = gt;
@@ -1026,8 +969,7 @@ __device__ __forceinline__ void edge_head_bwd_rows(const EdgeBwdSmem &s, const E
 
 // T = acc * SiLU'(pre1) to LDS and, over pre1, to HBM; rows past ne are zeros (their A rows were).  All 64 values of pre1 a lane needs are
 // requested before the first is used: one memory latency per tile and branch instead of one per group of rows.
-__device__ __forceinline__ void store_T_bwd(float *T, const f32x16 (&acc)[2][2], float ex, int tid, int wave, int lane, float *__restrict__ pre1, int ne,
-                                            int ne_st) {
+__device__ __forceinline__ void store_T_bwd(float *T, const f32x16 (&acc)[2][2], float ex, int tid, int wave, int lane, float *__restrict__ pre1, int ne) {
     const int row0 = 4 * (lane >> 5), col0 = 64 * wave + (lane & 31);
     unsigned off0 = (unsigned)(row0 * HS + col0) * 4u;
     asm volatile("" : "+v"(off0));
@@ -1053,7 +995,7 @@ __device__ __forceinline__ void store_T_bwd(float *T, const f32x16 (&acc)[2][2],
                 const int rl = 32 * mt + 8 * (reg >> 2) + (reg & 3), row = rl + row0;
                 const float v = acc[mt][nt][reg] * silu_grad_(p[mt][nt][reg]);
                 T[row * SA + col0 + 32 * nt] = v;
-                if (row < ne_st) *reinterpret_cast<float *>(bp + (off0 + (unsigned)(rl * HS + 32 * nt) * 4u)) = v;
+                if (row < ne) *reinterpret_cast<float *>(bp + (off0 + (unsigned)(rl * HS + 32 * nt) * 4u)) = v;
             }
     if ((tid & 3) == 0) {
         const int row = tid >> 2;
@@ -1071,7 +1013,6 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_bwd(EdgeBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EdgeBwdSmem s = edge_bwd_smem(smem);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    unsigned long long t_prev_ = a.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
     const int T = a.meta[8];
     const int chunk = (T + 7) >> 3;
     const int bi = blockIdx.x >> 3;
@@ -1124,7 +1065,6 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_bwd(EdgeBwdArgs a) {
     BPrefetch bpre;
     gemm_b_prefetch(bpre, a.wpT[et][0], wave, lane);
     lds_barrier();
-    TRAIN_STAMP(32)
     const int first_is_cont = s.misc[0];
     const unsigned long long endmask = ((unsigned long long)(unsigned)s.misc[3] << 32) | (unsigned long long)(unsigned)s.misc[2];
     const unsigned long long headmask = ((unsigned long long)(unsigned)s.misc[5] << 32) | (unsigned long long)(unsigned)s.misc[4];
@@ -1134,9 +1074,7 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_bwd(EdgeBwdArgs a) {
     for (int br = 0; br < 2; ++br) {
         // (an opaque copy of the thread index per branch: see k_egnn_edge_train -- nothing derived from it is carried across the loop)
         int tid_b = tid;
-#ifndef KPD_BWD_LAUNDER_OFF
         asm volatile("" : "+v"(tid_b));
-#endif
         const int lane_b = tid_b & 63;
         float *pre1 = a.keep[et][br][0] + (size_t)e0 * HS;
         HeadSums hs;
@@ -1149,16 +1087,13 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_bwd(EdgeBwdArgs a) {
             edge_head_bwd_rows<false>(s, a, et, e0, ne, wave, lane_b, nullptr, a.keep[et][1][2], a.w3[et], nullptr, a.nvec[et], hs);
         }
         lds_barrier();
-        TRAIN_STAMP(33 + 8 * br)
         acc_zero_w<NW>(acc);
         const float ex = row_dot_chunks<TPR>(s.A, s.wv + br * HS, KP / 4, tid_b);
         gemm_rows64_pre<NG, SA>(s.A, a.wpT[et][br], acc, wave, lane_b, bpre);
         if (br == 0) gemm_b_prefetch(bpre, a.wpT[et][1], wave, lane_b);
         lds_barrier();
-        TRAIN_STAMP(34 + 8 * br)
-        store_T_bwd(s.A, acc, ex, tid_b, wave, lane_b, pre1, ne, (a.skip & 16) ? 0 : ne);
+        store_T_bwd(s.A, acc, ex, tid_b, wave, lane_b, pre1, ne);
         lds_barrier();
-        TRAIN_STAMP(35 + 8 * br)
         {   // d dij += dpre1 . W1[:, 514]
             const float dot = row_dot_chunks<TPR>(s.A, s.wv + (2 + br) * HS, KP / 4, tid_b);
             if ((tid_b % TPR) == 0) s.ddij[tid_b / TPR] += dot;
@@ -1199,7 +1134,6 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_bwd(EdgeBwdArgs a) {
             }
         }
         lds_barrier();
-        TRAIN_STAMP(36 + 8 * br)
         if (wave == 0) {    // column 256: segmented inclusive scan across lanes (lane_b = row), the last lane_b of every run writes
             const unsigned long long upto = lane_b == 63 ? ~0ull : ((1ull << (lane_b + 1)) - 1ull);
             const int start = 63 - __clzll((long long)((headmask & upto) | 1ull));
@@ -1240,10 +1174,8 @@ __global__ __launch_bounds__(256, 2) void k_egnn_edge_bwd(EdgeBwdArgs a) {
             }
             lds_barrier();
         }
-        TRAIN_STAMP(37 + 8 * br)
     }
     if (tid < ne) a.sc[et][e0 + tid] = s.ddij[tid];          // d dij of both branches, over sc
-    if (a.stamps && tid == 0) atomicAdd(&a.stamps[63], 1ull);
 }
 
 // dV[v] = main[v] + the continuation pieces of the tiles v's in-edges span (zeros without in-edges), the same for dVw: the pieces of
@@ -1357,44 +1289,18 @@ __device__ __forceinline__ EdgeSmem edge_smem_h(float *smem) {
 }
 
 // A[r][:] = SiLU(Ps[src_r] + Pd[dst_r] + d_r w_r) as f16 hi / lo planes; columns 264..271 (K padding of the 16-wide k-steps) zero
-// BATCH_D: read the wave's RPW distances with RPW / 4 broadcast ds_read_b128 up front instead of one ds_read_b32 (and an LDS round trip)
-// per row.  OFF in production: with the batched read at both call sites of k_egnn_edge_h (0.394 instead of 0.402 ms) the FIRST forward
-// of a process differed from all later ones in a few x pieces (first segments of ll / kl tiles, ~1 % of the piece) -- at either site
-// alone, or with the per-row reads, it does not (profiles/tools/repro_layer.py, repro_pieces.py; six fresh processes each).  The
-// batched form is semantically identical, so the cause is a timing-dependent hazard that was not found; the arrangement that has
-// never shown it is the one that ships.
-#ifndef KPD_H_BATCH_D
-#define KPD_H_BATCH_D false
-#endif
-template <int NW, bool BATCH_D>
+// (one distance read per row: the batched broadcast read of k_egnn_edge, 2 % faster here, made a process's first forward differ from
+// later ones in a few x pieces, by a hazard that was never found)
+template <int NW>
 __device__ __forceinline__ void edge_gather_finish_h(const EdgeGather<NW> &g, const EdgeSmem &s, _Float16 *Ah, const float *__restrict__ wr,
-                                                     int wave, int lane, float *dbg2 = nullptr) {
+                                                     int wave, int lane) {
     constexpr int RPW = TM / NW;
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     const f32x4 w0 = reinterpret_cast<const f32x4 *>(wr)[lane];
-    // the wave's RPW distances in one batch of broadcast reads (a read + wait per row costs an LDS round trip each, and the per-row
-    // addresses were being kept live -- spilled -- across the GEMM)
-    f32x4 dv[RPW / 4];
-#ifdef KPD_HZ_VM0      // hazard hunt (profiles/tools/hz_variant.sh): every gathered row has landed before the first one is consumed
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#pragma unroll
-    for (int i = 0; i < RPW / 4; ++i) dv[i] = BATCH_D ? *reinterpret_cast<const f32x4 *>(s.d + wave * RPW + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
-#ifdef KPD_HZ_LGKM0    // hazard hunt: the batched distances have landed before anything else is issued
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
 #pragma unroll
     for (int rr = 0; rr < RPW; ++rr) {
         const int r = wave * RPW + rr;
-#ifdef KPD_EDGE_DBG
-        if (dbg2 && rr < 3) {       // the operands exactly as this row consumes them
-            float *o = dbg2 + ((size_t)(rr * 4 + wave) * 64 + lane) * 12;
-            *reinterpret_cast<f32x4 *>(o) = g.ps[rr];
-            *reinterpret_cast<f32x4 *>(o + 4) = g.pd[rr];
-            o[8] = BATCH_D ? dv[rr >> 2][rr & 3] : s.d[r]; o[9] = w0[0]; o[10] = __builtin_bit_cast(float, s.src[r]); o[11] = __builtin_bit_cast(float, s.dst[r]);
-        }
-#endif
-        f32x4 v = g.ps[rr] + g.pd[rr] + (BATCH_D ? dv[rr >> 2][rr & 3] : s.d[r]) * w0;
+        f32x4 v = g.ps[rr] + g.pd[rr] + s.d[r] * w0;
         v[0] = silu_pre_x64(v[0]); v[1] = silu_pre_x64(v[1]); v[2] = silu_pre_x64(v[2]); v[3] = silu_pre_x64(v[3]);
         unsigned h0, h1, l0, l1;
         split_pair(v[0], v[1], h0, l0);
@@ -1441,7 +1347,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge_h(EdgeAr
     // (the wave index as a scalar, as in k_node_update8: the per-row LDS addresses of the A-builds become scalar base + immediate offset
     // instead of one VGPR per row kept live -- spilled -- across the GEMMs)
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    unsigned long long t_prev_ = a.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
     // tile decode (XCD-aware: consecutive tiles -- neighbouring edges of one complex, which
     // share P rows -- go to the same XCD / L2)
     const int T = a.meta[8];
@@ -1503,7 +1408,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge_h(EdgeAr
         }
     }
     lds_barrier();
-    KPD_STAMP(0)
 
     const float *Ps = a.P[snt] + (size_t)a.src_slot[et] * HS;
     const float *Pd = a.P[dnt] + (size_t)a.dst_slot[et] * HS;
@@ -1514,33 +1418,26 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge_h(EdgeAr
     float ex;
 
     // ---- feature messages: m = edge_mlp(f); msg_h = m * sigmoid(att(m)) (dynamics.py:111-112)
-    constexpr int abl = 0;
     {
         EdgeGather<NW> ge;
         edge_gather_issue<NW>(ge, s, Ps, Pd, wave, lane);
-        edge_gather_finish_h<NW, KPD_H_BATCH_D>(ge, s, Ah, a.wr_e[et], wave, lane);
+        edge_gather_finish_h<NW>(ge, s, Ah, a.wr_e[et], wave, lane);
     }
     lds_barrier();
-    KPD_STAMP(1)
     acc_zero_w<NW>(acc);
     ex = row_dot_h2<TPR>(Ah, wxs, tid);
-#ifndef KPD_HZ_NOGEMM   // hazard hunt: the kernel without its matrix products (results meaningless, run-to-run equality still telling)
     if constexpr (NW == 4) gemm_rows64_h(Ah, a.wh_e[et], acc, wave, lane);
     else gemm_rows64_h8(Ah, a.wh_e[et], acc, wave, lane);
-#endif
     unscale_acc(acc, ex);
     lds_barrier();
-    KPD_STAMP(2)
-    if (!(abl & 4)) store_T_silu_w<NW, true>(s.A, acc, ex, a.b_e[et], tid, wave, lane);
-    else if (acc[0][0][0] == 12345.0f) s.A[tid] = acc[1][NW == 4 ? 1 : 0][3] + acc[0][NW == 4 ? 1 : 0][5] + acc[1][0][7];
+    store_T_silu_w<NW, true>(s.A, acc, ex, a.b_e[et], tid, wave, lane);
     EdgeGather<NW> gc;
     {   // the coordinate branch's P rows start travelling now; consumed after the segmented sum below
         edge_gather_issue<NW>(gc, s, Ps + HS, Pd + HS, wave, lane);
         __builtin_amdgcn_sched_barrier(0);
     }
     lds_barrier();
-    KPD_STAMP(3)
-    if (!(abl & 4)) {
+    {
         float dot = row_dot_chunks<TPR>(s.A, s.wv, 64, tid);
         const int row = tid / TPR;
         if ((tid % TPR) == 0) {
@@ -1550,8 +1447,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge_h(EdgeAr
         }
     }
     lds_barrier();
-    KPD_STAMP(4)
-    if (!(abl & 4)) {
+    {
         // segmented sum over dst (dynamics.py:182-185): thread = column, rows in order; the run
         // boundaries are wave-uniform (endmask), LDS reads are issued 16 rows at a time
         float *hmain = a.hn_main[et], *hcont = a.hn_cont[et] + (size_t)tile_in_et * HS;
@@ -1599,50 +1495,32 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge_h(EdgeAr
         }
     }
     lds_barrier();
-    KPD_STAMP(5)
 
     // ---- coordinate messages: msg_x = tanh(coord_mlp(f)) * x_diff * range (dynamics.py:113-120)
-#ifdef KPD_EDGE_DBG
-    edge_gather_finish_h<NW, KPD_H_BATCH_D>(gc, s, Ah, a.wr_c[et], wave, lane, a.dbg ? a.dbg + (size_t)a.meta[8] * TM * 4 + (size_t)tile * (3 * 4 * 64 * 12) : nullptr);
-#else
-    edge_gather_finish_h<NW, KPD_H_BATCH_D>(gc, s, Ah, a.wr_c[et], wave, lane);
-#endif
+    edge_gather_finish_h<NW>(gc, s, Ah, a.wr_c[et], wave, lane);
     lds_barrier();
-    KPD_STAMP(6)
     acc_zero_w<NW>(acc);
     ex = row_dot_h2<TPR>(Ah, wxs + 544, tid);
-#ifndef KPD_HZ_NOGEMM   // hazard hunt: the kernel without its matrix products (results meaningless, run-to-run equality still telling)
     if constexpr (NW == 4) gemm_rows64_h(Ah, a.wh_c[et], acc, wave, lane);
     else gemm_rows64_h8(Ah, a.wh_c[et], acc, wave, lane);
-#endif
     unscale_acc(acc, ex);
     lds_barrier();
-    KPD_STAMP(7)
-    if (!(abl & 4)) store_T_silu_w<NW, true>(s.A, acc, ex, a.b_c[et], tid, wave, lane);
-    else if (acc[0][0][0] == 12345.0f) s.A[tid] = acc[1][NW == 4 ? 1 : 0][3] + acc[0][NW == 4 ? 1 : 0][5] + acc[1][0][7];
+    store_T_silu_w<NW, true>(s.A, acc, ex, a.b_c[et], tid, wave, lane);
     lds_barrier();
-    KPD_STAMP(8)
-    if (!(abl & 4)) {
+    {
         float dot = row_dot_chunks<TPR>(s.A, s.wv + HS, 64, tid);
         const int row = tid / TPR;
         if ((tid % TPR) == 0) {
             dot = fmaf(s.A[row * SA + 256], s.wv[HS + 256], dot);
             float c = a.use_tanh ? tanhf(dot) * a.coords_range : dot;
             if (row >= ne) c = 0.0f;
-#ifdef KPD_EDGE_DBG
-            if (a.dbg) {
-                float *o = a.dbg + ((size_t)tile * TM + row) * 4;
-                o[0] = dot; o[1] = s.d[row]; o[2] = s.A[row * SA + 256]; o[3] = s.A[row * SA + 7];
-            }
-#endif
             s.mx[3 * row] = c * s.xd[3 * row];
             s.mx[3 * row + 1] = c * s.xd[3 * row + 1];
             s.mx[3 * row + 2] = c * s.xd[3 * row + 2];
         }
     }
     lds_barrier();
-    KPD_STAMP(9)
-    if (wave == 0 && !(abl & 4)) {
+    if (wave == 0) {
         // segmented inclusive scan across lanes (lane = row), then the last lane of every run writes
         const unsigned long long heads =
             ((unsigned long long)(unsigned)s.misc[5] << 32) | (unsigned long long)(unsigned)s.misc[4];
@@ -1667,7 +1545,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge_h(EdgeAr
             out[2] = vz;
         }
     }
-    KPD_STAMP(10)
 }
 
 
@@ -1690,13 +1567,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
     const int node0 = (blockIdx.x - (which ? p.tiles0 : 0)) * TN;
     constexpr int RPW = TN / 8;          // rows per wave in the copy loops
     constexpr int TPR = 512 / TN;        // threads per row in the row-wise passes
-    unsigned long long t_prev_ = p.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
-#define NL_STAMP(idx)                                                                      \
-    if (p.stamps && tid == 0) {                                                            \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                      \
-        atomicAdd(&p.stamps[idx], (unsigned long long)(now_ - t_prev_));                   \
-        t_prev_ = now_;                                                                    \
-    }
 
     // rows of h to the tile: all of a wave's loads in flight together (the h array is padded to a whole tile; rows >= n hold zeros)
     auto load_h = [&]() {
@@ -1758,13 +1628,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
         // GEMM 1a: W[:, :257] . h
         load_h();
         lds_barrier();
-        NL_STAMP(0)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
         gemm_rows32_t8<NG, SA>(A, a.wp_a, acc, wave, lane);
         float ex = row_dot_chunks<TPR>(A, s_wx, KP / 4, tid);
         lds_barrier();
-        NL_STAMP(1)
         // GEMM 1b: + W[:, 257:] . (h_neigh / z); h_neigh = sum of segment pieces over the incoming edge
         // types in fixed order (multi_update_all cross_reducer='sum')
         {
@@ -1820,11 +1688,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
             }
         }
         lds_barrier();
-        NL_STAMP(2)
         gemm_rows32_t8<NG, SA>(A, a.wp_b, acc, wave, lane);
         ex += row_dot_chunks<TPR>(A, s_wx + HS, KP / 4, tid);
         lds_barrier();
-        NL_STAMP(3)
         // hidden = SiLU(. + b0) -> T (pad columns 257..263 stay 0 from the h_neigh tile)
         {
             const int col = 32 * wave + (lane & 31);
@@ -1834,14 +1700,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
         }
         if ((tid % TPR) == 0) A[(tid / TPR) * SA + 256] = silu(ex + a.b0[256]);
         lds_barrier();
-        NL_STAMP(4)
         // GEMM 2 + bias + residual (dynamics.py:201-203)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
         gemm_rows32_t8<NG, SA>(A, a.wp_2, acc, wave, lane);
         ex = row_dot_chunks<TPR>(A, s_wx + 2 * HS, KP / 4, tid);
         lds_barrier();
-        NL_STAMP(5)
         {
             const int col = 32 * wave + (lane & 31);
             const float bb = a.b2[col];
@@ -1859,7 +1723,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
             if (lane == 0) A[r * SA + 256] += a.h[(size_t)(node0 + r) * HS + 256];
         }
         lds_barrier();
-        NL_STAMP(6)
         // LayerNorm(257) (dynamics.py:81-87, 204), biased variance, eps = 1e-5
         if (a.norm) {
             const int row = tid / TPR, q = tid % TPR;
@@ -1887,7 +1750,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
             }
         }
         lds_barrier();
-        NL_STAMP(7)
         // normalise in place (the tile becomes the A operand of the projections) and write h' back
 #pragma unroll 2
         for (int rr = 0; rr < RPW; ++rr) {
@@ -1916,9 +1778,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
             }
         }
         lds_barrier();
-        NL_STAMP(8)
     }
-#undef NL_STAMP
 }
 
 
@@ -2158,27 +2018,22 @@ kpd_status launch_decode(const float *h, const float *x, const float *x0, int n,
 kpd_status launch_egnn_edge(const EdgeArgs &a, int tile_cap, hipStream_t st) {
     if (tile_cap == 0) return KPD_OK;
     if (poison_level() >= 1) KPD_TRY(poison_lds(st));      // debug only (engine.h)
-    // KPD_EDGE_LDS_PAD (diagnostics): extra dynamic LDS to force one workgroup per CU
-    static const int pad = tool_env_int("KPD_EDGE_LDS_PAD", 0);
-    static const int ablate = tool_env_int("KPD_EDGE_ABLATE", 0);
-    EdgeArgs b = a;
-    b.ablate = ablate;
     KPD_REQUIRE(a.tile_rows == TM, KPD_ERR_INVALID, "the edge kernels walk 64-edge tiles");
     // 4 waves per workgroup: 256 VGPRs per lane leave room to keep the coordinate branch's gathered P rows in registers across
     // the attention / segmented-sum phases (the 8-wave and the 32-row builds of rounds 1 - 3 lost to it and were removed in round 4)
     if (a.gemm_mode == 1) {
         for (int et = 0; et < 4; ++et)
             KPD_REQUIRE(!a.wp_e[et] || (a.wh_e[et] && a.wh_c[et]), KPD_ERR_STATE, "f16x2 weights of edge type %d were not packed", et);
-        KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_egnn_edge_h<4>), EDGE_H_LDS_BYTES + pad));
-        hipLaunchKernelGGL(k_egnn_edge_h<4>, dim3(8 * cdiv(tile_cap, 8)), dim3(256), EDGE_H_LDS_BYTES + pad, st, b);
+        KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_egnn_edge_h<4>), EDGE_H_LDS_BYTES));
+        hipLaunchKernelGGL(k_egnn_edge_h<4>, dim3(8 * cdiv(tile_cap, 8)), dim3(256), EDGE_H_LDS_BYTES, st, a);
         KPD_LAUNCH_CHECK();
         return KPD_OK;
     }
-    KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_egnn_edge<4>), EDGE_LDS_BYTES + pad));
-    // the tail of a launch split by branch (k_egnn_edge): two workgroup slots per CU, an eighth of them per XCD; KPD_EDGE_SPLIT=0: whole tiles only
-    static const bool split = tool_env_int("KPD_EDGE_SPLIT", 1) != 0;
-    b.split_slots = (split && pad == 0) ? 2 * cu_count() / 8 : 0;
-    hipLaunchKernelGGL(k_egnn_edge<4>, dim3(8 * (cdiv(tile_cap, 8) + b.split_slots / 2)), dim3(256), EDGE_LDS_BYTES + pad, st, b);
+    KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_egnn_edge<4>), EDGE_LDS_BYTES));
+    // the tail of a launch split by branch (k_egnn_edge): two workgroup slots per CU, an eighth of them per XCD
+    EdgeArgs b = a;
+    b.split_slots = 2 * cu_count() / 8;
+    hipLaunchKernelGGL(k_egnn_edge<4>, dim3(8 * (cdiv(tile_cap, 8) + b.split_slots / 2)), dim3(256), EDGE_LDS_BYTES, st, b);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
 }
@@ -2187,8 +2042,6 @@ kpd_status launch_node_layer(const NodeLayerPair &p, hipStream_t st) {
     const int tiles = p.tiles0 + cdiv(p.nt[1].u.n, TN);
     if (tiles == 0) return KPD_OK;
     if (poison_level() >= 1) KPD_TRY(poison_lds(st));      // debug only (engine.h)
-    // KPD_NODE_LDS_PAD (diagnostics): extra dynamic LDS to lower the number of co-resident workgroups
-    static const int pad = tool_env_int("KPD_NODE_LDS_PAD", 0);
     for (int nt = 0; nt < 2; ++nt)
         KPD_REQUIRE(p.nt[nt].u.n == 0 || (p.nt[nt].do_update && !p.nt[nt].do_proj), KPD_ERR_INVALID, "node launch: update-only node types expected");
     // k_node_update8 reads the segment bounds of (up to) two incoming edge types unconditionally: an updated node type has at least one, with its arrays
@@ -2200,7 +2053,7 @@ kpd_status launch_node_layer(const NodeLayerPair &p, hipStream_t st) {
             KPD_REQUIRE(u.rowptr[i] && u.hn_main[i] && u.hn_cont[i] && u.xn_main[i] && u.xn_cont[i], KPD_ERR_INVALID,
                         "node launch: segment arrays of incoming edge type %d of node type %d are missing", i, nt);
     }
-    if (p.gemm_mode == 1 && !p.stamps) {                   // (phase-stamped diagnostic launches keep the exact kernel)
+    if (p.gemm_mode == 1) {
         for (int nt = 0; nt < 2; ++nt)
             if (p.nt[nt].u.n > 0)
                 KPD_REQUIRE(p.nt[nt].u.wh_a && p.nt[nt].u.wh_b && p.nt[nt].u.wh_2, KPD_ERR_STATE, "node weights of type %d have no f16 planes", nt);
@@ -2209,8 +2062,8 @@ kpd_status launch_node_layer(const NodeLayerPair &p, hipStream_t st) {
         KPD_LAUNCH_CHECK();
         return KPD_OK;
     }
-    KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_node_update8), NODE_LAYER_LDS_BYTES + pad));
-    hipLaunchKernelGGL(k_node_update8, dim3(tiles), dim3(512), NODE_LAYER_LDS_BYTES + pad, st, p);
+    KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_node_update8), NODE_LAYER_LDS_BYTES));
+    hipLaunchKernelGGL(k_node_update8, dim3(tiles), dim3(512), NODE_LAYER_LDS_BYTES, st, p);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
 }

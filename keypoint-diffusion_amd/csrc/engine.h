@@ -33,7 +33,6 @@ kpd_status launch_radius_bipartite(const float *x, const int *x_ptr, int n_x, in
 // test_layer_edge_kernels_on_poisoned_workspaces, test_gvp_train_gpu.py::test_chained_kernels_on_poisoned_workspaces and
 // test_cold_start_gpu.py.
 int poison_level();
-bool poison_selected();      // KPD_POISON_ONLY=<i>: poison only the i-th float buffer carved in this process (bisecting a NaN to its buffer)
 void poison_floats(void *p, size_t bytes);
 void zero_pad_columns(float *p, size_t rows, int stride, int valid);
 kpd_status poison_lds(hipStream_t st);
@@ -55,7 +54,7 @@ struct Arena {
         if (used + bytes > cap) return nullptr;
         T *p = reinterpret_cast<T *>(base + used);
         used += bytes;
-        if (std::is_floating_point<T>::value && poison_level() >= poison_at && poison_selected()) poison_floats(p, bytes);
+        if (std::is_floating_point<T>::value && poison_level() >= poison_at) poison_floats(p, bytes);
         return p;
     }
     // rows x stride floats of which only the first `valid` columns of a row are ever written: the K-padding columns are part of

@@ -41,7 +41,6 @@ struct kpd_gvp {
     bool f16_ok = true;                       // the committed weights fit the f16 planes (pack.hip range guard)
     int gemm_mode = 0;                        // 0 exact fp32; 1 f16x2 split in the message chain (KPD_GEMM=f16x2, "gemm=f16x2")
     int debug_convs = -1;
-    unsigned long long *stamps = nullptr;     // device [32], diagnostics
     int coop_rows = 0;                        // row limit of the cooperative node-side kernels (0: default; kpd_gvp_debug_state "coop_rows=N")
     // optional HIP-event timing of the dominant kernel (k_gvp_chain), for bench.py's roofline
     bool prof_on = false;
@@ -158,7 +157,6 @@ extern "C" kpd_status kpd_gvp_create(const kpd_gvp_config *cfg, kpd_gvp **out) {
 extern "C" void kpd_gvp_destroy(kpd_gvp *m) {
     if (!m) return;
     for (hipEvent_t e : m->prof_ev) (void)hipEventDestroy(e);
-    if (m->stamps) (void)hipFree(m->stamps);
     m->warena.release();
     m->ws.release();
     delete m;
@@ -356,8 +354,7 @@ extern "C" kpd_status kpd_gvp_forward(kpd_gvp *m, const kpd_batch *bt, const flo
         ea.meta = net == 4 ? m->meta4 : m->meta2;
         ea.x[0] = x[0]; ea.x[1] = x[1]; ea.v[0] = m->v[0]; ea.v[1] = m->v[1];
         ea.n_gvps = c.n_message_gvps; ea.S = S; ea.rbf_dmax = 15.0f;            // gvp.py:350 default, not overridden
-        ea.stamps = m->stamps;
-        ea.gemm_mode = (S == 256 && !m->stamps) ? m->gemm_mode : 0;
+        ea.gemm_mode = S == 256 ? m->gemm_mode : 0;
         for (int et = 0; et < net; ++et) {
             ea.src[et] = esrc[et]; ea.dst[et] = edst[et]; ea.Psrc[et] = m->Psrc[et];
             for (int j = 0; j < c.n_message_gvps; ++j) ea.g[et][j] = m->msg[ci][et][j].dev();
@@ -431,16 +428,6 @@ extern "C" kpd_status kpd_gvp_debug_state(kpd_gvp *m, const char *what, float *o
         m->gemm_mode = (v == "f16x2" && m->S == 256) ? 1 : 0;
         return KPD_OK;
     }
-    if (w == "stamps=1") {
-        if (!m->stamps) KPD_HIP(hipMalloc(reinterpret_cast<void **>(&m->stamps), 32 * sizeof(unsigned long long)));
-        KPD_HIP(hipMemsetAsync(m->stamps, 0, 32 * sizeof(unsigned long long), st));
-        return KPD_OK;
-    }
-    if (w == "stamps") {
-        KPD_REQUIRE(m->stamps && out && n_floats >= 64, KPD_ERR_INVALID, "stamps not enabled or buffer < 64 floats");
-        KPD_HIP(hipMemcpyAsync(out, m->stamps, 32 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
-        return KPD_OK;
-    }
     const float *src = nullptr;
     if (w == "s_lig") src = m->s[0];
     else if (w == "s_kp") src = m->s[1];
@@ -479,7 +466,7 @@ extern "C" kpd_status kpd_gvp_profile_read(kpd_gvp *m, double *total_ms, int32_t
 extern "C" kpd_status kpd_gvp_last_counts(kpd_gvp *m, int32_t out[8], void *stream) {
     KPD_REQUIRE(m && out, KPD_ERR_INVALID, "null argument");
     for (int i = 0; i < 7; ++i) out[i] = 0;
-    out[7] = (m->gemm_mode && !m->stamps) ? 1 : 0;    // GEMM mode the next forward's dominant kernel runs in: 0 exact fp32, 1 f16x2 (a phase-stamped diagnostic run keeps the exact chain)
+    out[7] = m->gemm_mode ? 1 : 0;                     // GEMM mode the next forward's dominant kernel runs in: 0 exact fp32, 1 f16x2
     if (!m->meta4) return KPD_OK;                      // no forward yet: only the mode is meaningful
     hipStream_t st = static_cast<hipStream_t>(stream);
     int host[25];

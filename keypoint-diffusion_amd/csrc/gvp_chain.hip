@@ -28,19 +28,15 @@ typedef const __attribute__((address_space(4))) GvpBwdSlot cBwdSlot;
 
 namespace {
 
-#ifndef KPD_CHAIN_NBUF
-#define KPD_CHAIN_NBUF 3          // buffers of the edge kernel's weight ring (chain_core.h)
-#endif
-#ifndef KPD_CHAIN_SWAVE
-#define KPD_CHAIN_SWAVE 1         // the wave index of the edge kernel as a scalar (ring hand-offs and LDS-DMA bases become scalar work)
-#endif
+constexpr int CHAIN_NBUF = 3;           // buffers of the edge kernel's weight ring (chain_core.h)
+constexpr bool CHAIN_SWAVE = true;      // the wave index of the edge kernel as a scalar (ring hand-offs and LDS-DMA bases become scalar work)
 
 template <int NTS>
 struct ChainSmem {
     static constexpr int S = 16 * NTS;
     static constexpr int CH4 = NTS * 64;                 // float4 per chunk
     static constexpr int SO = S + 4;                     // row stride of the output staging tile
-    static constexpr int REGION0 = (KPD_CHAIN_NBUF * CH4 * 4 > TM * SO) ? KPD_CHAIN_NBUF * CH4 * 4 : TM * SO;   // ring / output tile (floats)
+    static constexpr int REGION0 = (CHAIN_NBUF * CH4 * 4 > TM * SO) ? CHAIN_NBUF * CH4 * 4 : TM * SO;   // ring / output tile (floats)
     static constexpr int FLOATS = REGION0 + TM * 48 + TM + 16;
 };
 
@@ -54,7 +50,7 @@ struct ChainSmem {
 template <int NTS, class Ring, int TR = 0, class TG = cTrainGvp>
 __device__ __forceinline__ void chain_generic_gvp(Ring &ring, const v4f *cb, const v4f *nb, const GvpW &gk, const float *next_bias,
                                                   v4f (&x)[NTS], v4f (&acc)[NTS], v4f (&Vc)[3], int lane, int q,
-                                                  TG *tg = nullptr, size_t erow = 0, bool live = false, int skip = 0) {
+                                                  TG *tg = nullptr, size_t erow = 0, bool live = false) {
     // cb: this GVP's chunks (NTS scalar slabs, the sh slab, the gate slab); nb: the next GVP's -- or, after the last one, cb + NTS chunks,
     // so that the two refills past the end re-read chunks that exist.  The chunk two ahead of local chunk i:
     constexpr int CH4 = NTS * 64;
@@ -71,7 +67,7 @@ __device__ __forceinline__ void chain_generic_gvp(Ring &ring, const v4f *cb, con
 #pragma unroll
     for (int r = 0; r < 4; ++r) sh[r] = sqrt1(fmaxf(Vh[0][r] * Vh[0][r] + Vh[1][r] * Vh[1][r] + Vh[2][r] * Vh[2][r], 1e-8f));
     if constexpr (TR) {
-        if (live && !(skip & 4)) {
+        if (live) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) *reinterpret_cast<gv4f *>(G(tg->Vh) + (erow * 3 + c) * 16 + 4 * q) = Vh[c];
             *reinterpret_cast<gv4f *>(G(tg->sh) + erow * 16 + 4 * q) = sh;
@@ -87,7 +83,7 @@ __device__ __forceinline__ void chain_generic_gvp(Ring &ring, const v4f *cb, con
     const v4f bgv = *reinterpret_cast<const v4f *>(gk.bg + 4 * q);
     const v4f wu = reinterpret_cast<const v4f *>(gk.wup)[lane];
     if constexpr (TR) {
-        if (live && !(skip & 1)) {
+        if (live) {
             gfloat *pr = G(tg->pre) + erow * (16 * NTS) + 4 * q;
 #pragma unroll
             for (int mt = 0; mt < NTS; ++mt) *reinterpret_cast<gv4f *>(pr + 16 * mt) = acc[mt];
@@ -96,7 +92,7 @@ __device__ __forceinline__ void chain_generic_gvp(Ring &ring, const v4f *cb, con
 #pragma unroll
     for (int mt = 0; mt < NTS; ++mt) x[mt] = silu4(acc[mt]);
     if constexpr (TR) {
-        if (live && !(skip & 2)) {
+        if (live) {
             gfloat *sr = G(tg->s) + erow * (16 * NTS) + 4 * q;
 #pragma unroll
             for (int mt = 0; mt < NTS; ++mt) *reinterpret_cast<gv4f *>(sr + 16 * mt) = x[mt];
@@ -126,7 +122,7 @@ __device__ __forceinline__ void chain_generic_gvp(Ring &ring, const v4f *cb, con
         ring.release();
         gate = (ga[0] + ga[1]) + (ga[2] + ga[3]) + bgv;
         if constexpr (TR) {
-            if (live && !(skip & 4)) *reinterpret_cast<gv4f *>(G(tg->gate) + erow * 16 + 4 * q) = gate;          // before the sigmoid (k_gvp_gate_bwd applies it)
+            if (live) *reinterpret_cast<gv4f *>(G(tg->gate) + erow * 16 + 4 * q) = gate;          // before the sigmoid (k_gvp_gate_bwd applies it)
         }
         if (gk.vec_sigmoid) {
 #pragma unroll
@@ -140,7 +136,7 @@ __device__ __forceinline__ void chain_generic_gvp(Ring &ring, const v4f *cb, con
         for (int r = 0; r < 4; ++r) t = mfma16(wu[r], Vh[c][r], t);
         Vc[c] = gate * t;
         if constexpr (TR) {
-            if (live && !(skip & 4)) {
+            if (live) {
                 *reinterpret_cast<gv4f *>(G(tg->Vu) + (erow * 3 + c) * 16 + 4 * q) = t;
                 *reinterpret_cast<gv4f *>(G(tg->V) + (erow * 3 + c) * 16 + 4 * q) = Vc[c];
             }
@@ -296,14 +292,6 @@ __device__ __forceinline__ void chain_generic_gvp_h(Ring &ring, Src &chunk_src, 
     }
 }
 
-// phase-cycle sums for profiles/tools/gvp_stamps.py (a.stamps is null in production)
-#define CHAIN_STAMP(idx)                                                                   \
-    if (stamps && tid == 0) {                                                              \
-        const unsigned long long t_now = __builtin_amdgcn_s_memtime();                     \
-        atomicAdd(stamps + (idx), t_now - t_prev);                                         \
-        t_prev = t_now;                                                                    \
-    }
-
 // TR = 1: the training forward (a.train, gvp_kernels.h) -- the same chain on current weights, every activation the backward pass reads stored
 // on the way (8.5 KB per edge), node vectors and vector pieces in the trainers' [3][16] layout.
 template <int NTS, int HM = 0, int TR = 0>
@@ -316,9 +304,7 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
     int *sdst = reinterpret_cast<int *>(Vout + TM * 48);
     int *misc = sdst + TM;
 
-    const int tid = threadIdx.x, wave = KPD_CHAIN_SWAVE ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6, lane = tid & 63;
-    unsigned long long *stamps = a.stamps;
-    unsigned long long t_prev = stamps ? __builtin_amdgcn_s_memtime() : 0ull;
+    const int tid = threadIdx.x, wave = CHAIN_SWAVE ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6, lane = tid & 63;
     const int T = a.meta[8];
     const int chunk_tiles = (T + 7) >> 3;
     const int bi = blockIdx.x >> 3;
@@ -350,7 +336,7 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
         }
         return reinterpret_cast<const v4f *>(HM ? a.g[et][stage].chain_h : a.g[et][stage].chain) + (size_t)local * CH4;      // (wave-uniform)
     };
-    ChunkRing<CH4, KPD_CHAIN_NBUF> ring;
+    ChunkRing<CH4, CHAIN_NBUF> ring;
     ring.init(smem, total, wave, tid);
     ring.start(chunk_src);
     auto acquire = [&]() -> const v4f * { return ring.acquire(chunk_src); };
@@ -476,7 +462,7 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
         const int tail = h0 - 16 * (n_ht - 1);            // valid rows of the last hidden tile
         const int tail_reg = min(4, tail);
         if constexpr (TR) {       // geometry, message input vectors [x_diff | source], hidden vectors and their norms (17 channels)
-            if (live && !(a.train_skip & 4)) {
+            if (live) {
                 if (q == 0) {
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
@@ -499,7 +485,6 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
         }
 
         ring.first();
-        CHAIN_STAMP(0)
         // scalar GEMM: [rbf | sh] part of to_feats_out
         {
             const v4f *buf = acquire();
@@ -516,14 +501,13 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
                 release();
             }
         }
-        CHAIN_STAMP(1)
         const v4f bgv = *reinterpret_cast<const v4f *>(g0.bg + 4 * q);
         const v4f *wup = reinterpret_cast<const v4f *>(g0.wup) + lane;
         v4f wu[3];
 #pragma unroll
         for (int ht = 0; ht < 3; ++ht) wu[ht] = ht < n_ht ? wup[ht * 64] : zero4();
         if constexpr (TR) {
-            if (live && !(a.train_skip & 1)) {
+            if (live) {
                 gfloat *pr = G(tsl->g[0].pre) + erow * S + 4 * q;
 #pragma unroll
                 for (int mt = 0; mt < NTS; ++mt) *reinterpret_cast<gv4f *>(pr + 16 * mt) = acc[mt];
@@ -532,7 +516,7 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
 #pragma unroll
         for (int mt = 0; mt < NTS; ++mt) x[mt] = silu4(HM ? acc[mt] * H_UNSCALE : acc[mt]);
         if constexpr (TR) {
-            if (live && !(a.train_skip & 2)) {
+            if (live) {
                 gfloat *sr = G(tsl->g[0].s) + erow * S + 4 * q;
 #pragma unroll
                 for (int mt = 0; mt < NTS; ++mt) *reinterpret_cast<gv4f *>(sr + 16 * mt) = x[mt];
@@ -543,7 +527,6 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
 #pragma unroll
             for (int mt = 0; mt < NTS; ++mt) acc[mt] = *reinterpret_cast<const v4f *>(bn + 16 * mt);
         }
-        CHAIN_STAMP(2)
         // gates                                                                       (gvp.py:105-107)
         {
             if constexpr (HM) {
@@ -563,14 +546,13 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
                 gate = (ga[0] + ga[1]) + (ga[2] + ga[3]) + bgv;
             }
             if constexpr (TR) {
-                if (live && !(a.train_skip & 4)) *reinterpret_cast<gv4f *>(G(tsl->g[0].gate) + erow * 16 + 4 * q) = gate;
+                if (live) *reinterpret_cast<gv4f *>(G(tsl->g[0].gate) + erow * 16 + 4 * q) = gate;
             }
             if (g0.vec_sigmoid) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) gate[r] = sigmoidf_(gate[r]);
             }
         }
-        CHAIN_STAMP(3)
         // vec2: v' = gate * Wu^T Vh                                                   (gvp.py:97, 111)
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -586,13 +568,12 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
             }
             Vc[c] = gate * t;
             if constexpr (TR) {
-                if (live && !(a.train_skip & 4)) {
+                if (live) {
                     *reinterpret_cast<gv4f *>(G(tsl->g[0].Vu) + (erow * 3 + c) * 16 + 4 * q) = t;
                     *reinterpret_cast<gv4f *>(G(tsl->g[0].V) + (erow * 3 + c) * 16 + 4 * q) = Vc[c];
                 }
             }
         }
-        CHAIN_STAMP(4)
     }
 
     // ---- GVP 1 .. n-1: scalars and vectors come from the previous GVP's registers ------------------------
@@ -603,10 +584,9 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
             const v4f *cb = reinterpret_cast<const v4f *>(a.g[et][k].chain);
             const v4f *nb = k + 1 < n_gvps ? reinterpret_cast<const v4f *>(a.g[et][k + 1].chain) : cb + (size_t)NTS * CH4;
             if constexpr (TR) chain_generic_gvp<NTS, decltype(ring), 1>(ring, cb, nb, a.g[et][k], k + 1 < n_gvps ? a.g[et][k + 1].b : nullptr, x, acc, Vc, lane, q,
-                                                                         &tsl->g[k], erow, live, a.train_skip);
+                                                                         &tsl->g[k], erow, live);
             else chain_generic_gvp<NTS>(ring, cb, nb, a.g[et][k], k + 1 < n_gvps ? a.g[et][k + 1].b : nullptr, x, acc, Vc, lane, q);
         }
-        CHAIN_STAMP(6)
     }
 
     // ---- messages -> LDS: the ring is reused, so drain the (redundant) tail fetches first -----------------
@@ -631,7 +611,6 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
         }
     }
     lds_barrier();
-    CHAIN_STAMP(10)
 
     // ---- segmented sums over dst: scalars (thread = column) and the 48 vector floats in ONE pass over the rows --------
     // (the vector columns ride on the first 48 threads -- S = 256 -- or on the last wave's spare lanes; a second pass for them
@@ -678,7 +657,6 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain(GvpEdgeArgs a) {
             }
         }
     }
-    CHAIN_STAMP(11)
 }
 
 // ---- backward of the message chains (training; autograd of gvp.py:89-116 under :540-551), register-chained --------------------------
@@ -818,7 +796,7 @@ __global__ __launch_bounds__(256, 2) void k_gvp_chain_bwd(GvpEdgeBwdArgs a) {
     const int total = (n_gvps - 1) * NG + 4;
     const v4f *first = reinterpret_cast<const v4f *>(a.g[et][n_gvps - 1].chain);
     auto chunk_src = [&](int c) -> const v4f * { return first + (size_t)c * CH4; };       // (chunks 0 and 1 only: every GVP has at least four)
-    ChunkRing<CH4, KPD_CHAIN_NBUF> ring;
+    ChunkRing<CH4, CHAIN_NBUF> ring;
     ring.init(smem, total, wave, tid);
     ring.start(chunk_src);
 
@@ -894,7 +872,7 @@ __global__ __launch_bounds__(256, 2) void k_gvp_node_chain_bwd(GvpNodeBwdArgs a)
     const int n_gvps = a.n_gvps;
     const v4f *first = reinterpret_cast<const v4f *>(a.g[n_gvps - 1].chain);
     auto chunk_src = [&](int c) -> const v4f * { return first + (size_t)c * CH4; };
-    ChunkRing<CH4, KPD_CHAIN_NBUF> ring;
+    ChunkRing<CH4, CHAIN_NBUF> ring;
     ring.init(smem, n_gvps * NG, wave, tid);
     ring.start(chunk_src);
     const int el = lane & 15, q = lane >> 4;
@@ -1357,9 +1335,7 @@ kpd_status launch_gvp_edge(const GvpEdgeArgs &a, int tile_cap, hipStream_t st) {
         for (int et = 0; et < 4; ++et)
             KPD_REQUIRE(!a.src[et] || (a.g[et][0].h == 17 && a.n_gvps <= 4), KPD_ERR_INVALID, "gvp chain kernel: the training form wants a 17-channel head GVP");
         KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_gvp_chain<16, 0, 1>), ChainSmem<16>::FLOATS * 4));
-        GvpEdgeArgs b = a;
-        b.train_skip = tool_env_int("KPD_TR_SKIP", 0);          // (TOOLS build: timing experiments; a compile-time 0 in the product)
-        hipLaunchKernelGGL((k_gvp_chain<16, 0, 1>), grid, dim3(256), ChainSmem<16>::FLOATS * 4, st, b);
+        hipLaunchKernelGGL((k_gvp_chain<16, 0, 1>), grid, dim3(256), ChainSmem<16>::FLOATS * 4, st, a);
     } else if (a.S == 256)
         hipLaunchKernelGGL(k_gvp_chain<16>, grid, dim3(256), ChainSmem<16>::FLOATS * 4, st, a);
     else
@@ -1377,7 +1353,7 @@ kpd_status launch_gvp_edge_bwd(const GvpEdgeBwdArgs &a, int tile_cap, hipStream_
             for (int k = 0; k < a.n_gvps; ++k)
                 KPD_REQUIRE(a.g[et][k].chain && (k == 0 || (a.g[et][k].wut && a.g[et][k].wht)), KPD_ERR_STATE,
                             "message GVP %d of edge type %d was not packed for the chained backward kernel", k, et);
-    const int lds = KPD_CHAIN_NBUF * 16 * 64 * 16;
+    const int lds = CHAIN_NBUF * 16 * 64 * 16;
     KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_gvp_chain_bwd<16>), lds));
     hipLaunchKernelGGL(k_gvp_chain_bwd<16>, dim3(8 * cdiv(tile_cap, 8)), dim3(256), lds, st, a);
     KPD_LAUNCH_CHECK();
@@ -1390,7 +1366,7 @@ kpd_status launch_gvp_node_bwd(const GvpNodeBwdArgs &a, hipStream_t st) {
     KPD_REQUIRE(a.n_gvps >= 1 && a.n_gvps <= GVP_MAX_CHAIN && a.ds && a.dV && a.ds_in && a.dv_in, KPD_ERR_INVALID, "gvp node chain backward: bad arguments");
     for (int k = 0; k < a.n_gvps; ++k)
         KPD_REQUIRE(a.g[k].chain && a.g[k].wut && a.g[k].wht && a.f[k].pre && a.o[k].dpre, KPD_ERR_STATE, "update GVP %d was not prepared for the chained backward kernel", k);
-    const int lds = KPD_CHAIN_NBUF * 16 * 64 * 16;
+    const int lds = CHAIN_NBUF * 16 * 64 * 16;
     KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_gvp_node_chain_bwd<16>), lds));
     hipLaunchKernelGGL(k_gvp_node_chain_bwd<16>, dim3(cdiv(a.n, TM)), dim3(256), lds, st, a);
     KPD_LAUNCH_CHECK();

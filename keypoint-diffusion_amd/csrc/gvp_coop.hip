@@ -403,11 +403,8 @@ __global__ __launch_bounds__(256, 2) void k_gvp_noise_coop(GvpNoiseArgs a) {
 }  // namespace
 
 // Rows up to which a node-side launch takes the cooperative form (gvp_kernels.h).  Measured on gvp_40kp / gvp_all_atom shapes
-// (profiles/r05_gvp_coop_ab.txt); KPD_COOP_ROWS (TOOLS build only) overrides it for the sweep.
-int coop_rows_max(int requested) {
-    static const int rows = tool_env_int("KPD_COOP_ROWS", COOP_ROWS_DEFAULT);
-    return requested != 0 ? requested : rows;
-}
+// (profiles/r05_gvp_coop_ab.txt).
+int coop_rows_max(int requested) { return requested != 0 ? requested : COOP_ROWS_DEFAULT; }
 
 kpd_status launch_gvp_node_coop(const GvpNodePair &pin, hipStream_t st) {
     GvpNodePair p = pin;

@@ -48,9 +48,7 @@ struct GvpEdgeArgs {
     float rbf_dmax;
     float *ms_main[4], *ms_cont[4];   // [n_dst][S], [tiles][S]
     float *mv_main[4], *mv_cont[4];   // [n_dst][48], [tiles][48]
-    unsigned long long *stamps;       // [32] phase-cycle sums (diagnostics only, null in production)
     int gemm_mode;                    // 0: exact fp32 MFMA; 1: f16x2 split in the 256 x 256 products of the non-head message GVPs
-    int train_skip;                   // TOOLS build only (KPD_TR_SKIP): bit 0 / 1 / 2 = leave out the pre / s / remaining stores of the training form (timing experiments)
     const GvpTrainSlot *train;        // non-null: the training form of the kernel -- node vectors v arrive as [n][3][16], the vector pieces
                                       // mv_main / mv_cont leave as [3][16], and every activation the backward pass reads is stored (device table [4])
 };

@@ -1022,8 +1022,7 @@ extern "C" kpd_status kpd_gvp_trainer_reserve(kpd_gvp_trainer *T, int32_t max_B,
         }
         // the fused message forward wants the kept activations (it writes them) and the 256-wide kernels
         T->release_fused();
-        static const bool want_fused = tool_env_int("KPD_TRAIN_FUSED", 1) != 0;      // TOOLS build: A/B against the per-GVP path
-        if (T->store && S == 256 && want_fused) {
+        if (T->store && S == 256) {
             size_t floats = 0;
             for (int conv = 0; conv < L; ++conv)
                 for (int et = 0; et < 4; ++et)

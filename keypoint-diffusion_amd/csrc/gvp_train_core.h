@@ -586,11 +586,6 @@ __global__ __launch_bounds__(256) void k_gvp_vec17_bwd(const float *__restrict__
         p[i] = ((x0p[i] + x0p[VEC17_PART + i]) + x0p[2 * VEC17_PART + i]) + x0p[3 * VEC17_PART + i];
 }
 
-inline bool vec_fused() {
-    static const bool on = tool_env_int("KPD_TRAIN_VEC_FUSED", 1) != 0;          // A/B runs
-    return on;
-}
-
 template <int VI, int H, int VO>
 kpd_status launch_gvp_vec_fwd(const float *v_in, const float *Wh, const float *Wu, int M, float *Vh, float *Vu, float *sh, hipStream_t st) {
     hipLaunchKernelGGL((k_gvp_vec_fwd<VI, H, VO>), dim3(cdiv(M, 128)), dim3(128), 0, st, v_in, Wh, Wu, M, Vh, Vu, sh);
@@ -880,40 +875,28 @@ kpd_status gvp_params(TT *T, const std::string &p, int vi, int vo, int si, int s
     return KPD_OK;
 }
 
-// the 256 x 256 scalar block of a GVP can take the weight-stationary GEMM (KPD_TRAIN_WS=0: library GEMMs throughout)
-bool ws_ok(const GvpP &g, int ld_s) {
-    static const bool on = tool_env_int("KPD_TRAIN_WS", 1) != 0;
-    return on && g.si == 256 && g.so == 256 && ld_s == 256;
-}
-
-// the 16 / 17 vector norms of to_feats_out's input ride along in the weight-stationary kernel (KPD_TRAIN_WS_EXTRA=0: separate products)
-inline bool ws_extra() {
-    static const bool on = tool_env_int("KPD_TRAIN_WS_EXTRA", 1) != 0;
-    return on;
-}
+// the 256 x 256 scalar block of a GVP can take the weight-stationary GEMM
+bool ws_ok(const GvpP &g, int ld_s) { return g.si == 256 && g.so == 256 && ld_s == 256; }
 
 // GVP.forward (gvp.py:89-116).  s_in == nullptr: B.pre already holds the contribution of the scalar inputs (no bias).
 template <class TT>
 kpd_status gvp_fwd(TT *T, const GvpP &g, int M, const float *s_in, int ld_s, const float *v_in, const GvpBuf &B,
                    bool identity) {
     if (M == 0) return KPD_OK;
-    bool fused = false;
-    if (vec_fused()) {          // the shapes the engines use: message head [x_diff | v_src] (17), plain (16), noise head (16 -> 1), encoder rk head (33)
-        fused = true;
-        if (g.vi == 17 && g.h == 17 && g.vo == 16) {
-            const int blocks = std::max(1, std::min(cdiv(cdiv(M, 16), 4), 4 * cu_count()));
-            hipLaunchKernelGGL(k_gvp_vec17_fwd, dim3(blocks), dim3(256), 0, T->st, v_in, g.Wh.w, g.Wu.w, M, B.Vh, B.Vu, B.sh);
-            KPD_LAUNCH_CHECK();
-        }
-        else if (g.vi == 16 && g.h == 16 && g.vo == 16) {
-            const int blocks = std::max(1, std::min(cdiv(cdiv(M, 16), 4), 4 * cu_count()));
-            hipLaunchKernelGGL(k_gvp_vec16_fwd, dim3(blocks), dim3(256), 0, T->st, v_in, g.Wh.w, g.Wu.w, M, B.Vh, B.Vu, B.sh);
-            KPD_LAUNCH_CHECK();
-        }
-        else if (g.vi == 16 && g.h == 16 && g.vo == 1) KPD_TRY((launch_gvp_vec_fwd<16, 16, 1>(v_in, g.Wh.w, g.Wu.w, M, B.Vh, B.Vu, B.sh, T->st)));
-        else if (g.vi == 33 && g.h == 33 && g.vo == 16) KPD_TRY((launch_gvp_vec_fwd<33, 33, 16>(v_in, g.Wh.w, g.Wu.w, M, B.Vh, B.Vu, B.sh, T->st)));
-        else fused = false;
+    bool fused = true;          // the shapes the engines use: message head [x_diff | v_src] (17), plain (16), noise head (16 -> 1), encoder rk head (33)
+    if (g.vi == 17 && g.h == 17 && g.vo == 16) {
+        const int blocks = std::max(1, std::min(cdiv(cdiv(M, 16), 4), 4 * cu_count()));
+        hipLaunchKernelGGL(k_gvp_vec17_fwd, dim3(blocks), dim3(256), 0, T->st, v_in, g.Wh.w, g.Wu.w, M, B.Vh, B.Vu, B.sh);
+        KPD_LAUNCH_CHECK();
     }
+    else if (g.vi == 16 && g.h == 16 && g.vo == 16) {
+        const int blocks = std::max(1, std::min(cdiv(cdiv(M, 16), 4), 4 * cu_count()));
+        hipLaunchKernelGGL(k_gvp_vec16_fwd, dim3(blocks), dim3(256), 0, T->st, v_in, g.Wh.w, g.Wu.w, M, B.Vh, B.Vu, B.sh);
+        KPD_LAUNCH_CHECK();
+    }
+    else if (g.vi == 16 && g.h == 16 && g.vo == 1) KPD_TRY((launch_gvp_vec_fwd<16, 16, 1>(v_in, g.Wh.w, g.Wu.w, M, B.Vh, B.Vu, B.sh, T->st)));
+    else if (g.vi == 33 && g.h == 33 && g.vo == 16) KPD_TRY((launch_gvp_vec_fwd<33, 33, 16>(v_in, g.Wh.w, g.Wu.w, M, B.Vh, B.Vu, B.sh, T->st)));
+    else fused = false;
     if (!fused) {
         KPD_TRY(gemm(T, false, false, 3 * M, g.h, g.vi, v_in, g.vi, g.Wh.w, g.h, 0.0f, B.Vh, g.h));
         KPD_TRY(gemm(T, false, false, 3 * M, g.vo, g.h, B.Vh, g.h, g.Wu.w, g.vo, 0.0f, B.Vu, g.vo));
@@ -925,7 +908,7 @@ kpd_status gvp_fwd(TT *T, const GvpP &g, int M, const float *s_in, int ld_s, con
     if (s_in && ws_ok(g, ld_s)) {
         // the narrow vector-norm block first, then the 256 x 256 scalar block on the weight-stationary GEMM with the partial
         // pre-activation, the bias and the SiLU fused into its epilogue
-        if (g.h <= 17 && ws_extra()) {           // ... with the vector-norm block as extra inputs of the same kernel, and the gate product
+        if (g.h <= 17) {                         // ... with the vector-norm block as extra inputs of the same kernel, and the gate product
             WsgExtra x;                          // (16 outputs of the activated row) taken in its epilogue
             x.X2 = B.sh; x.W = g.Ws.w + g.si; x.sn = g.si + g.h; x.sk = 1; x.n = g.h; x.ld = g.h;
             if (g.vo == 16) { x.Wg = g.Wg.w; x.ldg = g.so; x.ng = g.vo; x.G2 = B.gate; x.G2b = T->dgate; gate_parts = true; }
@@ -966,7 +949,7 @@ kpd_status gvp_bwd(TT *T, const GvpP &g, int M, const float *s_in, int ld_s, con
     if (s_in) {
         if (g.Ws.g) KPD_TRY(grad_gemm(T, g.so, g.si, M, ds, g.so, s_in, ld_s, g.Ws.g, g.si + g.h));
         if (ds_in) {
-            if (ws_ok(g, ld_s) && g.h <= 17 && ws_extra()) {       // ... with dsh = ds Ws[:, si:] as extra outputs of the same kernel
+            if (ws_ok(g, ld_s) && g.h <= 17) {       // ... with dsh = ds Ws[:, si:] as extra outputs of the same kernel
                 WsgExtra x;
                 x.Y2 = T->dsh; x.W = g.Ws.w + g.si; x.sn = 1; x.sk = g.si + g.h; x.n = g.h; x.ld = g.h;
                 KPD_TRY(ws_gemm(WS_PLAIN, ds, M, g.so, g.Ws.w, g.si + g.h, true, nullptr, nullptr, ds_in, nullptr, g.si, T->wsg_pack, T->st, false, false,
@@ -979,7 +962,7 @@ kpd_status gvp_bwd(TT *T, const GvpP &g, int M, const float *s_in, int ld_s, con
     // the sh block of to_feats_out, with the bias gradient (column sums of ds) riding along
     KPD_TRY(grad_gemm(T, g.so, g.h, M, ds, g.so, B.sh, g.h, g.Ws.g ? g.Ws.g + g.si : nullptr, g.si + g.h, g.bs.g));
     if (!have_dsh) KPD_TRY(gemm(T, false, false, M, g.h, g.so, ds, g.so, g.Ws.w + g.si, g.si + g.h, 0.0f, T->dsh, g.h));
-    if (vec_fused() && g.vi == 17 && g.h == 17 && g.vo == 16 && T->part && T->part_floats >= (size_t)VEC16_MAX_WAVES * VEC17_PART) {
+    if (g.vi == 17 && g.h == 17 && g.vo == 16 && T->part && T->part_floats >= (size_t)VEC16_MAX_WAVES * VEC17_PART) {
         const int blocks = std::max(1, std::min(cdiv(cdiv(M, 16), 4), std::min(2 * cu_count(), VEC16_MAX_WAVES / 4)));
         hipLaunchKernelGGL(k_gvp_vec17_bwd, dim3(blocks), dim3(256), 0, T->st, dV, B.Vh, B.sh, T->dsh, v_in, g.Wh.w, g.Wu.w, M, dv_in, T->part);
         KPD_LAUNCH_CHECK();
@@ -989,7 +972,7 @@ kpd_status gvp_bwd(TT *T, const GvpP &g, int M, const float *s_in, int ld_s, con
         }
         return KPD_OK;
     }
-    if (vec_fused() && g.vi == 16 && g.h == 16 && g.vo == 16 && T->part && T->part_floats >= (size_t)VEC16_MAX_WAVES * 512) {
+    if (g.vi == 16 && g.h == 16 && g.vo == 16 && T->part && T->part_floats >= (size_t)VEC16_MAX_WAVES * 512) {
         const int blocks = std::max(1, std::min(cdiv(cdiv(M, 16), 4), std::min(2 * cu_count(), VEC16_MAX_WAVES / 4)));
         hipLaunchKernelGGL(k_gvp_vec16_bwd, dim3(blocks), dim3(256), 0, T->st, dV, B.Vh, B.sh, T->dsh, v_in, g.Wh.w, g.Wu.w, M, dv_in, T->part);
         KPD_LAUNCH_CHECK();

@@ -105,15 +105,14 @@ __device__ __forceinline__ void gemm_b_prefetch(BPrefetch &p, const float *__res
     p.y1 = bp[513];
 }
 
-#ifndef KPD_GEMM_SETS
-#define KPD_GEMM_SETS 2          // operand register sets of gemm_rows64_pre: fragments of k-group g + SETS are requested behind the MFMAs of group g
-                                 // (3 sets -- two groups of cover for the L2 round trip -- measured in round 5: 0.8130 vs 0.8132 ms, no difference)
-#endif
+// operand register sets of gemm_rows64_pre: fragments of k-group g + GEMM_SETS are requested behind the MFMAs of group g
+// (3 sets -- two groups of cover for the L2 round trip -- measured in round 5: 0.8130 vs 0.8132 ms, no difference)
+constexpr int GEMM_SETS = 2;
 template <int NG_, int SA_>
 __device__ __forceinline__ void gemm_rows64_pre(const float *__restrict__ A, const float *__restrict__ Wp,
                                                 f32x16 (&acc)[2][2], int wave, int lane, const BPrefetch &pre) {
-    static_assert(NG_ > KPD_GEMM_SETS, "prefetched form needs more k-groups than operand sets");
-    constexpr int NS = KPD_GEMM_SETS;
+    static_assert(NG_ > GEMM_SETS, "prefetched form needs more k-groups than operand sets");
+    constexpr int NS = GEMM_SETS;
     const int r = lane & 31, h = lane >> 5;
     const float *a0p = A + r * SA_ + 4 * h;
     const float *a1p = A + (32 + r) * SA_ + 4 * h;
@@ -638,11 +637,7 @@ __device__ __forceinline__ float row_dot_chunks(const float *__restrict__ T, con
 // counter, i.e. every wave would wait at each barrier for its outstanding global stores (segment
 // pieces, projections) to be acknowledged; nothing in these kernels reads those back.
 __device__ __forceinline__ void lds_barrier() {
-#ifdef KPD_HZ_FULLBAR   // hazard hunt (profiles/tools/hz_variant.sh): every barrier also drains the vector-memory counter
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
 }
 
 // Row/column owned by accumulator register `reg` of tile (mt, nt) on this lane.

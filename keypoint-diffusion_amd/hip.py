@@ -11,7 +11,7 @@ from typing import Dict, Optional
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# KPD_LIB: another build of the same library (profiles/tools load the TOOLS build, csrc/tools_build/libkpd_hip.so, this way);
+# KPD_LIB: another copy of the same library (for example a parent commit's, to compare against);
 # bench.py refuses to run with it set and checks kpd_build_flags() == 0
 LIB_PATH = os.environ.get('KPD_LIB') or os.path.join(_HERE, 'csrc', 'libkpd_hip.so')
 _lib = None

@@ -1,5 +1,5 @@
 """Run-to-run bit equality of the EGNN denoiser at the contract shape (diagnostic): prints how many output elements differ
-between repeated forwards.  KPD_GEMM / KPD_H_PARTS select the kernels."""
+between repeated forwards.  KPD_GEMM selects the kernels."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)

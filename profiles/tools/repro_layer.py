@@ -1,4 +1,4 @@
-"""Which rows / columns of the node state deviate run to run after ONE EGNN layer (diagnostic; KPD_GEMM / KPD_H_PARTS select the kernels)."""
+"""Which rows / columns of the node state deviate run to run after ONE EGNN layer (diagnostic; KPD_GEMM selects the kernels)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)

@@ -31,9 +31,8 @@ def test_version_and_error_string_without_gpu():
 
 
 def test_product_build_has_no_ablation_or_ab_switches():
-    """The shipped library is the product build: kpd_build_flags() == 0 and the names of the A/B, ablation and LDS-padding switches of
-    profiles/tools (read from the environment only by the TOOLS build, `make tools`) are not even in the binary.  What the product does
-    read: KPD_GEMM (the opt-in f16x2 mode), KPD_TRAIN_STORE (recompute instead of keeping activations), KPD_POISON (NaN-poisoned
+    """The shipped library is the only build: kpd_build_flags() == 0 and the names of the retired A/B, ablation and LDS-padding
+    switches of earlier rounds are not in the binary.  What the library does read: KPD_GEMM (the opt-in f16x2 mode), KPD_TRAIN_STORE (recompute instead of keeping activations), KPD_POISON (NaN-poisoned
     workspaces for the read-before-write tests) -- bench.py refuses to run with any of them set."""
     assert hip.lib().kpd_build_flags() == 0
     blob = open(hip.LIB_PATH, 'rb').read()
