@@ -6,7 +6,7 @@ denoiser forward + z_s update + COM removal) over one batch of B synthetic compl
 is already resident in HBM.  Contract workload = BASELINE.json configs[1]:
 egnn_all_atom dynamics, B = 64 synthetic 300-atom pockets / 25-atom ligands, T = 500.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks (torch.distributed.run: RANK /
 WORLD_SIZE / MASTER_* in the environment) or -- when WORLD_SIZE is absent -- this script starts N fresh
@@ -17,10 +17,13 @@ step).  W warm-up steps, then `--repeats` regions of EXACTLY K steps, each brack
 synchronize on both sides and reduced with MAX over ranks; `value` is the MEDIAN region, the spread is
 reported beside it.  Rank 0 prints ONE JSON line.
 
-At N = 1 the default run also measures (and nests under `secondary`) BASELINE.json configs[2]
-(gvp_40kp, B = 64) and the configs[4] shape (gvp_all_atom, ragged 150-600 / 15-35 atoms), each with its
-own roofline and CPU baseline, and one full sampling run end to end (`end_to_end`: receptor encoding +
-T reverse steps + host copy -> measured ligands/min).
+A plain run does only what that line needs: set up, warm up, time the regions, write `--dump-outputs`,
+print.  `--full` (off by default) adds, at N = 1, everything that takes runs of its own: the CPU baseline
+of the oracle with its parity check of the measured path, and for the contract workload BASELINE.json
+configs[0] on the GPU, configs[2] (gvp_40kp, B = 64) and the configs[4] shape (gvp_all_atom, ragged
+150-600 / 15-35 atoms), B = 512 and the f16x2 mode (nested under `secondary`, each with its own roofline
+and CPU baseline), and full sampling runs end to end (`end_to_end`: receptor encoding + T reverse steps +
+host copy -> measured ligands/min).
 """
 import argparse
 import json
@@ -1039,7 +1042,7 @@ def run_train(args, device, rank, world, dist):
             rf['edge_kernels'] = kern
             assert sum(k['ms_per_step'] for k in kern.values()) <= 1e3 * t_step * 1.001
         out['roofline'] = rf
-        if world == 1 and not args.no_cpu_baseline and w['enc'] == 'fixed':
+        if world == 1 and args.full and not args.no_cpu_baseline and w['enc'] == 'fixed':
             out['cpu_baseline'] = train_cpu_baseline(args.workload)
         emit(out)
 
@@ -1053,11 +1056,15 @@ def main():
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--n-rec', type=int, default=300)
     ap.add_argument('--n-lig', type=int, default=25)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='at N = 1, also measure what takes runs of its own: the CPU baseline with its '
+                                                        'parity check and, for the contract workload, the secondary workloads and the '
+                                                        'end-to-end runs (off: only the timed steps of the line)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and its parity check')
     ap.add_argument('--fused-optimizer', action='store_true', help='training workloads: torch.optim.Adam(fused=True)')
     ap.add_argument('--torch-optimizer', action='store_true', help='training workloads: torch.optim.Adam + torch.nn.utils.clip_grad_value_ instead '
                                                                    'of keypoint_diffusion_amd.optim (one launch each)')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the configs[2] / configs[4]-shape / end-to-end measurements')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the configs[0] / configs[2] / configs[4]-shape / end-to-end '
+                                                                'measurements')
     ap.add_argument('--workload', default='egnn_all_atom', choices=list(WORKLOADS),
                     help='egnn_all_atom = BASELINE.json configs[1] (the contract line); the others are secondary')
     ap.add_argument('--gemm', default='f32', choices=['f32', 'f16x2'],
@@ -1133,10 +1140,10 @@ def main():
                        dump=args.dump_outputs)
     if rank == 0:
         default_line = args.workload == 'egnn_all_atom' and not args.ragged and not args.graph and args.gemm == 'f32'
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args.workload, ragged=args.ragged, B_scale=args.batch, with_c1=default_line)
             out['gpu_over_cpu'] = out['value'] / out['cpu_baseline']['value']
-        if world == 1 and default_line and not args.no_secondary:
+        if world == 1 and args.full and default_line and not args.no_secondary:
             # BASELINE.json configs[2] and the configs[4] shape, same method (shorter regions), each with its roofline
             sec_args = argparse.Namespace(**vars(args))
             sec_args.steps, sec_args.warmup = max(20, args.steps // 2), max(5, args.warmup // 2)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the judged evidence for one round on the GPU box (run from the repo root):
 #   bash profiles/tools/collect_round.sh r02
-# 1) the default bench line (contract line + secondary workloads + end-to-end)            -> <tag>/bench.json
+# 1) the --full bench line (contract line + CPU baseline + secondary workloads + end-to-end) -> <tag>/bench.json, its full record -> <tag>/bench_full.json
 # 2) rocprofv3 --kernel-trace --stats of the contract workload, of its opt-in f16x2 mode and of the two GVP workloads -> <tag>/stats_*
 # 3) separate PMC passes per workload: SQ counters, FETCH_SIZE, WRITE_SIZE                  -> <tag>/pmc_*
 # 4) traffic.json: HBM bytes per launch of the dominant kernel of every workload (2 x FETCH_SIZE + WRITE_SIZE)
@@ -11,7 +11,8 @@ tag=${1:-r05}
 root=$(cd "$(dirname "$0")/../.." && pwd); cd /tmp && export TMPDIR=/tmp && cd "$root"
 out=gpurun_out/$tag
 rm -rf $out && mkdir -p $out
-python bench.py > $out/bench.json 2> $out/bench.err && cp gpurun_out/bench_full_record.json $out/bench_full.json
+python bench.py --full > $out/bench.json 2> $out/bench.err
+cp "$(python -c 'import json, sys; print(json.load(sys.stdin)["full_record"])' < $out/bench.json)" $out/bench_full.json
 short="--steps 3 --warmup 1 --repeats 1 --no-cpu-baseline --no-secondary"
 for wl in egnn_all_atom egnn_all_atom_f16x2 gvp_40kp gvp_all_atom_ragged gvp_40kp_f16x2 gvp_all_atom_ragged_f16x2; do
   case $wl in
