@@ -190,7 +190,9 @@ typedef struct kpd_gvp_config {
     int32_t vector_size;               /* 1 .. 16 (kernels are 16 channels wide; fewer are zero padded)           */
     int32_t n_convs, n_hidden_scalars; /* n_hidden_scalars 1 .. 256 (kernels are 128 / 256 wide, likewise); the   */
                                        /* training engine kpd_gvp_trainer_* takes the same ranges (narrower models */
-                                       /* through zero-padded wide parameter copies)                               */
+                                       /* through zero-padded wide parameter copies); 257 .. 1024 for inference on */
+                                       /* the composed wide path (csrc/gvp_wide.hip: fp32 only; debug taps convs=, */
+                                       /* gemm=f32, ws_bytes only; no kpd_gvp_profile); > 1024 is refused          */
     int32_t update_kp;
     int32_t message_norm_mode;         /* 0: constant message_norm, 1: 'mean', 2: message_norm == 0
                                           (per-graph average in-degree + 1, gvp.py:504-507)  */

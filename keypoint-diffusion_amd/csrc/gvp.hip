@@ -11,6 +11,7 @@
 
 #include "egnn_kernels.h"
 #include "gvp_host.h"
+#include "gvp_wide.h"
 
 using namespace kpd;
 
@@ -55,6 +56,7 @@ struct kpd_gvp {
     float *z[2];
     int *meta4, *meta2, *ll_deg, *ll_off, *kl_off, *kl_pg;
     kpd_lig_graph lg;
+    GvpWide *wide = nullptr;                    // n_hidden_scalars > 256: the composed wide path (gvp_wide.hip) serves every entry point
 
     int n_et(int conv) const { return (cfg.update_kp && conv != cfg.n_convs - 1) ? 4 : 2; }
 };
@@ -62,8 +64,9 @@ struct kpd_gvp {
 extern "C" kpd_status kpd_gvp_create(const kpd_gvp_config *cfg, kpd_gvp **out) {
     KPD_REQUIRE(cfg && out, KPD_ERR_INVALID, "null argument");
     KPD_REQUIRE(cfg->vector_size >= 1 && cfg->vector_size <= GV, KPD_ERR_INVALID, "vector_size=%d: supported sizes are 1 .. 16", cfg->vector_size);
-    KPD_REQUIRE(cfg->n_hidden_scalars >= 1 && cfg->n_hidden_scalars <= 256, KPD_ERR_INVALID,
-                "n_hidden_scalars=%d: supported widths are 1 .. 256", cfg->n_hidden_scalars);
+    // n_hidden_scalars 257 .. 1024 (inference only): the wide path of gvp_wide.hip behind the same handle
+    KPD_REQUIRE(cfg->n_hidden_scalars >= 1 && cfg->n_hidden_scalars <= GVP_WIDE_MAX_S, KPD_ERR_INVALID,
+                "n_hidden_scalars=%d: supported widths are 1 .. %d", cfg->n_hidden_scalars, GVP_WIDE_MAX_S);
     KPD_REQUIRE(cfg->ll_k >= 0 && cfg->ll_k <= KL_KMAX, KPD_ERR_INVALID, "ll_k=%d outside 0..%d (0 = radius graph)", cfg->ll_k, KL_KMAX);
     KPD_REQUIRE(cfg->kl_k >= 0 && cfg->kl_k <= KL_KMAX, KPD_ERR_INVALID, "kl_k=%d outside 0..%d (0 = radius graph)", cfg->kl_k, KL_KMAX);
     KPD_REQUIRE(cfg->kl_k > 0 || cfg->kl_cutoff > 0.0f, KPD_ERR_INVALID, "kl_k = 0 needs graph_cutoffs['kl'] > 0");
@@ -80,6 +83,15 @@ extern "C" kpd_status kpd_gvp_create(const kpd_gvp_config *cfg, kpd_gvp **out) {
     KPD_TRY(egnn_kernels_init());
     kpd_gvp *m = new kpd_gvp();
     m->cfg = *cfg;
+    if (cfg->n_hidden_scalars > 256) {
+        const kpd_status st = gvp_wide_create(*cfg, &m->wide);
+        if (st != KPD_OK) {
+            delete m;
+            return st;
+        }
+        *out = m;
+        return KPD_OK;
+    }
     // any n_hidden_scalars up to 256 runs on the 128- or 256-wide kernels: weights are packed with zero rows / columns for the padding
     // features (gvp_host.hip), which therefore stay exactly 0 through SiLU, gates and residuals; the two LayerNorms take the true width
     m->St = cfg->n_hidden_scalars;
@@ -156,6 +168,7 @@ extern "C" kpd_status kpd_gvp_create(const kpd_gvp_config *cfg, kpd_gvp **out) {
 
 extern "C" void kpd_gvp_destroy(kpd_gvp *m) {
     if (!m) return;
+    gvp_wide_destroy(m->wide);
     for (hipEvent_t e : m->prof_ev) (void)hipEventDestroy(e);
     m->warena.release();
     m->ws.release();
@@ -166,6 +179,7 @@ extern "C" kpd_status kpd_gvp_load_weight(kpd_gvp *m, const char *name, const fl
                                           void *stream) {
     KPD_REQUIRE(m && name && w && shape, KPD_ERR_INVALID, "null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m->wide) return gvp_wide_load_weight(m->wide, name, w, shape, ndim, st);
     const std::string nm(name);
     if (!m->expected.count(nm)) {
         set_error("unknown or unused weight name '%s' for this configuration", name);
@@ -225,6 +239,7 @@ extern "C" kpd_status kpd_gvp_load_weight(kpd_gvp *m, const char *name, const fl
 
 extern "C" kpd_status kpd_gvp_commit(kpd_gvp *m) {
     KPD_REQUIRE(m, KPD_ERR_INVALID, "null handle");
+    if (m->wide) return gvp_wide_commit(m->wide);
     for (const std::string &n : m->expected)
         if (!m->loaded.count(n)) {
             set_error("weight '%s' was never loaded (%zu of %zu loaded)", n.c_str(), m->loaded.size(), m->expected.size());
@@ -258,6 +273,7 @@ extern "C" kpd_status kpd_gvp_reserve(kpd_gvp *m, int32_t max_B, int32_t max_n_l
     KPD_REQUIRE(m, KPD_ERR_INVALID, "null handle");
     KPD_REQUIRE(max_B >= 1 && max_n_lig >= 1 && max_n_kp >= 1 && max_n_kk >= 0 && max_lig_pg >= 1 && max_kp_pg >= 1,
                 KPD_ERR_INVALID, "reserve: non-positive size");
+    if (m->wide) return gvp_wide_reserve(m->wide, max_B, max_n_lig, max_n_kp, max_n_kk, max_lig_pg, max_kp_pg);
     if (max_B <= m->cap_B && max_n_lig <= m->cap_lig && max_n_kp <= m->cap_kp && max_n_kk <= m->cap_kk &&
         max_lig_pg <= m->cap_maxlig && max_kp_pg <= m->cap_maxkp)
         return KPD_OK;
@@ -290,13 +306,14 @@ extern "C" kpd_status kpd_gvp_reserve(kpd_gvp *m, int32_t max_B, int32_t max_n_l
 extern "C" kpd_status kpd_gvp_forward(kpd_gvp *m, const kpd_batch *bt, const float *t_dev, float *eps_h, float *eps_x,
                                       void *stream) {
     KPD_REQUIRE(m && bt && t_dev && eps_h && eps_x, KPD_ERR_INVALID, "null argument");
-    KPD_REQUIRE(m->committed, KPD_ERR_STATE, "kpd_gvp_forward before kpd_gvp_commit");
+    KPD_REQUIRE(m->wide || m->committed, KPD_ERR_STATE, "kpd_gvp_forward before kpd_gvp_commit");
     KPD_REQUIRE(bt->B >= 1 && bt->n_lig >= 1 && bt->n_kp >= 1, KPD_ERR_INVALID, "empty batch");
     KPD_REQUIRE(bt->kp_v, KPD_ERR_INVALID, "kp_v (keypoint vector features v_0) missing");
+    KPD_REQUIRE(bt->kk_rowptr && (bt->n_kk == 0 || (bt->kk_src && bt->kk_dst)), KPD_ERR_INVALID, "kk edges missing");
+    if (m->wide) return gvp_wide_forward(m->wide, bt, t_dev, eps_h, eps_x, static_cast<hipStream_t>(stream));
     KPD_REQUIRE(bt->B <= m->cap_B && bt->n_lig <= m->cap_lig && bt->n_kp <= m->cap_kp && bt->n_kk <= m->cap_kk &&
                     bt->max_lig <= m->cap_maxlig && bt->max_kp <= m->cap_maxkp,
                 KPD_ERR_CAPACITY, "batch exceeds reserved workspace (call kpd_gvp_reserve)");
-    KPD_REQUIRE(bt->kk_rowptr && (bt->n_kk == 0 || (bt->kk_src && bt->kk_dst)), KPD_ERR_INVALID, "kk edges missing");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const kpd_gvp_config &c = m->cfg;
     const int S = m->S;
@@ -412,6 +429,7 @@ extern "C" kpd_status kpd_gvp_forward(kpd_gvp *m, const kpd_batch *bt, const flo
 extern "C" kpd_status kpd_gvp_debug_state(kpd_gvp *m, const char *what, float *out, int64_t n_floats, void *stream) {
     KPD_REQUIRE(m && what, KPD_ERR_INVALID, "null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (m->wide) return gvp_wide_debug_state(m->wide, what, out, n_floats, st);
     const std::string w(what);
     if (w.rfind("convs=", 0) == 0) {
         m->debug_convs = atoi(w.c_str() + 6);
@@ -440,6 +458,8 @@ extern "C" kpd_status kpd_gvp_debug_state(kpd_gvp *m, const char *what, float *o
 
 extern "C" kpd_status kpd_gvp_profile(kpd_gvp *m, int32_t enable) {
     KPD_REQUIRE(m, KPD_ERR_INVALID, "null handle");
+    KPD_REQUIRE(!m->wide, KPD_ERR_INVALID, "kpd_gvp_profile times the fused message-chain kernel of n_hidden_scalars <= 256; "
+                "n_hidden_scalars = %d has none", m->cfg.n_hidden_scalars);
     if (enable && m->prof_ev.empty()) {
         m->prof_ev.resize(2 * 8192);
         for (hipEvent_t &e : m->prof_ev) KPD_HIP(hipEventCreate(&e));
@@ -451,6 +471,8 @@ extern "C" kpd_status kpd_gvp_profile(kpd_gvp *m, int32_t enable) {
 
 extern "C" kpd_status kpd_gvp_profile_read(kpd_gvp *m, double *total_ms, int32_t *launches) {
     KPD_REQUIRE(m && total_ms && launches, KPD_ERR_INVALID, "null argument");
+    KPD_REQUIRE(!m->wide, KPD_ERR_INVALID, "kpd_gvp_profile_read: no fused message-chain kernel at n_hidden_scalars = %d",
+                m->cfg.n_hidden_scalars);
     double tot = 0.0;
     for (size_t i = 0; i + 1 < m->prof_used; i += 2) {
         KPD_HIP(hipEventSynchronize(m->prof_ev[i + 1]));
@@ -465,6 +487,7 @@ extern "C" kpd_status kpd_gvp_profile_read(kpd_gvp *m, double *total_ms, int32_t
 
 extern "C" kpd_status kpd_gvp_last_counts(kpd_gvp *m, int32_t out[8], void *stream) {
     KPD_REQUIRE(m && out, KPD_ERR_INVALID, "null argument");
+    if (m->wide) return gvp_wide_last_counts(m->wide, out, static_cast<hipStream_t>(stream));
     for (int i = 0; i < 7; ++i) out[i] = 0;
     out[7] = m->gemm_mode ? 1 : 0;                     // GEMM mode the next forward's dominant kernel runs in: 0 exact fp32, 1 f16x2
     if (!m->meta4) return KPD_OK;                      // no forward yet: only the mode is meaningful

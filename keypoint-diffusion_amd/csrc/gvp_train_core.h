@@ -879,9 +879,11 @@ kpd_status gvp_params(TT *T, const std::string &p, int vi, int vo, int si, int s
 bool ws_ok(const GvpP &g, int ld_s) { return g.si == 256 && g.so == 256 && ld_s == 256; }
 
 // GVP.forward (gvp.py:89-116).  s_in == nullptr: B.pre already holds the contribution of the scalar inputs (no bias).
+// m_live (optional): device count of the live rows of M, passed to the scalar products (train_ops.h gemm); B.pre == B.s is allowed
+// then (the activated output alone).  The trainers pass none.
 template <class TT>
 kpd_status gvp_fwd(TT *T, const GvpP &g, int M, const float *s_in, int ld_s, const float *v_in, const GvpBuf &B,
-                   bool identity) {
+                   bool identity, const int *m_live = nullptr) {
     if (M == 0) return KPD_OK;
     bool fused = true;          // the shapes the engines use: message head [x_diff | v_src] (17), plain (16), noise head (16 -> 1), encoder rk head (33)
     if (g.vi == 17 && g.h == 17 && g.vo == 16) {
@@ -905,7 +907,7 @@ kpd_status gvp_fwd(TT *T, const GvpP &g, int M, const float *s_in, int ld_s, con
     }
     long long tot = (long long)M * g.so;
     bool gate_parts = false;
-    if (s_in && ws_ok(g, ld_s)) {
+    if (s_in && ws_ok(g, ld_s) && !m_live) {
         // the narrow vector-norm block first, then the 256 x 256 scalar block on the weight-stationary GEMM with the partial
         // pre-activation, the bias and the SiLU fused into its epilogue
         if (g.h <= 17) {                         // ... with the vector-norm block as extra inputs of the same kernel, and the gate product
@@ -919,11 +921,11 @@ kpd_status gvp_fwd(TT *T, const GvpP &g, int M, const float *s_in, int ld_s, con
             KPD_TRY(ws_gemm(WS_BIAS_SILU, s_in, M, ld_s, g.Ws.w, g.si + g.h, false, g.bs.w, nullptr, B.pre, B.s, g.so, T->wsg_pack, T->st, false, true));
         }
     } else {
-        if (s_in) KPD_TRY(gemm(T, false, true, M, g.so, g.si, s_in, ld_s, g.Ws.w, g.si + g.h, 0.0f, B.pre, g.so));
+        if (s_in) KPD_TRY(gemm(T, false, true, M, g.so, g.si, s_in, ld_s, g.Ws.w, g.si + g.h, 0.0f, B.pre, g.so, 1.0f, nullptr, nullptr, nullptr, m_live));
         // + the vector-norm block, the bias and the SiLU in the epilogue: B.pre keeps the pre-activation, B.s its activation
-        KPD_TRY(gemm(T, false, true, M, g.so, g.h, B.sh, g.h, g.Ws.w + g.si, g.si + g.h, 1.0f, B.pre, g.so, 1.0f, nullptr, g.bs.w, B.s));
+        KPD_TRY(gemm(T, false, true, M, g.so, g.h, B.sh, g.h, g.Ws.w + g.si, g.si + g.h, 1.0f, B.pre, g.so, 1.0f, nullptr, g.bs.w, B.s, m_live));
     }
-    if (!gate_parts) KPD_TRY(gemm(T, false, true, M, g.vo, g.so, B.s, g.so, g.Wg.w, g.so, 0.0f, B.gate, g.vo, 1.0f, nullptr, g.bg.w));
+    if (!gate_parts) KPD_TRY(gemm(T, false, true, M, g.vo, g.so, B.s, g.so, g.Wg.w, g.so, 0.0f, B.gate, g.vo, 1.0f, nullptr, g.bg.w, nullptr, m_live));
     tot = (long long)M * g.vo;
     const float *p1 = gate_parts ? T->dgate : nullptr;
     if ((g.vo & 3) == 0) hipLaunchKernelGGL(k_gvp_gate<4>, grid1(tot / 4), dim3(256), 0, T->st, B.gate, p1, g.bg.w, B.Vu, M, g.vo / 4, identity ? 1 : 0, B.V);

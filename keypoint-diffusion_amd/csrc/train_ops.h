@@ -461,10 +461,13 @@ inline size_t colpart_floats(int max_rows) { return (size_t)cdiv(std::max(max_ro
 // row-major C[M,N] = alpha op(A) op(B) + beta C
 // silu_pre: C = (.) * SiLU'(silu_pre), element for element (silu_pre laid out like C): replaces a k_silu_bwd pass over C
 // bias / act_out: C = (.) + bias[n], act_out = SiLU(C) (laid out like C): replaces a k_bias_silu / k_bias_add pass over C
+// m_live (A B^T, K > 0): device count of the live rows (sgemm.h); the product goes to the unsplit kernel with its epilogue whatever
+// its size, so a row's bits do not depend on M (the wide GVP denoiser, gvp_wide.hip; the trainers pass none)
 kpd_status gemm(TrainCtx *T, bool tA, bool tB, int M, int N, int K, const float *A, int lda, const float *B, int ldb,
                 float beta, float *C, int ldc, float alpha = 1.0f, const float *silu_pre = nullptr, const float *bias = nullptr,
-                float *act_out = nullptr) {
+                float *act_out = nullptr, const int *m_live = nullptr) {
     if (M == 0 || N == 0) return KPD_OK;
+    if (m_live) return sgemm(tA, tB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, T->st, nullptr, 0, nullptr, silu_pre, bias, act_out, m_live);
     if (K == 0 && (bias || act_out)) {
         KPD_REQUIRE(beta == 1.0f && !silu_pre && bias, KPD_ERR_INVALID, "gemm: empty K with a bias epilogue needs beta = 1 and a bias");
         if (act_out) hipLaunchKernelGGL(k_bias_silu, grid1((long long)M * N), dim3(256), 0, T->st, C, bias, (long long)M * N, N, ldc, act_out);

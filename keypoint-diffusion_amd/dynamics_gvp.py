@@ -101,6 +101,9 @@ class LigRecDynamicsGVP(nn.Module):
             raise NotImplementedError('No CG is not implemented for GVP')
         if act_fn is not nn.SiLU:
             raise NotImplementedError('only SiLU activations are implemented (every shipped config)')
+        if not 1 <= int(n_hidden_scalars) <= 1024:
+            # the HIP engine covers 1 .. 256 (inference and training) and 257 .. 1024 (inference only)
+            raise ValueError(f'n_hidden_scalars={n_hidden_scalars}: the GVP denoiser covers n_hidden_scalars 1 .. 1024 (training up to 256)')
         if not update_kp and n_convs > 1:
             # the reference drops 'kp' from node_data after the first conv and fails (gvp.py:501, 536)
             raise NotImplementedError('update_kp=False with more than one convolution cannot run in the reference')
