@@ -94,7 +94,9 @@ kpd_status kpd_build_lig_graph(const kpd_batch *batch, float ll_cutoff, int32_t 
  * the decoder.  Constructor fields mirror LigRecDynamics.__init__ (:300-340).
  * ------------------------------------------------------------------------------------- */
 typedef struct kpd_egnn_config {
-    int32_t atom_nf, rec_nf;
+    int32_t atom_nf, rec_nf;           /* atom_nf 1 .. 256, rec_nf 1 .. 256 (rec_nf == hidden_nf: identity keypoint encoder, any
+                                          hidden_nf <= 256); the same ranges as the trainer.  atom_nf > 32, rec_nf 129 .. 255 and the
+                                          identity encoder below hidden_nf 256 run exact fp32 only ("gemm=f16x2" is refused) */
     int32_t n_layers, hidden_nf;       /* hidden_nf 1 .. 256 (the kernels are 256 + 1 wide; narrower models run zero padded: the reference's
                                           default ctor is 255); 257 .. 1024 for inference on the composed wide path (csrc/egnn_wide.hip:
                                           fp32 only, debug taps layers= / prune= only, no kpd_egnn_profile); the trainer takes <= 256;
@@ -186,7 +188,8 @@ kpd_status kpd_egnn_trainer_profile_read(kpd_egnn_trainer *t, double total_ms[2]
  * LigRecDynamicsGVP.__init__ (:106-147).  kpd_batch.kp_v carries the keypoint vector features v_0.
  * ------------------------------------------------------------------------------------- */
 typedef struct kpd_gvp_config {
-    int32_t n_lig_scalars, n_kp_scalars;
+    int32_t n_lig_scalars, n_kp_scalars; /* n_lig_scalars 1 .. 255 (> 64: exact fp32 only), n_kp_scalars 1 .. 256 (the */
+                                         /* trainer takes n_kp_scalars 1 .. 255)                                        */
     int32_t vector_size;               /* 1 .. 16 (kernels are 16 channels wide; fewer are zero padded)           */
     int32_t n_convs, n_hidden_scalars; /* n_hidden_scalars 1 .. 256 (kernels are 128 / 256 wide, likewise); the   */
                                        /* training engine kpd_gvp_trainer_* takes the same ranges (narrower models */
@@ -229,7 +232,7 @@ kpd_status kpd_gvp_last_counts(kpd_gvp *m, int32_t out[8], void *stream);
 
 /* Training path of the GVP denoiser: same contract as kpd_egnn_trainer_* above for
  * LigRecDynamicsGVP.forward (models/dynamics_gvp.py:149-199).  Gradients flow to every parameter and to the scalar and
- * vector input features: d_lig_h [n_lig, n_lig_scalars], d_kp_h [n_kp, n_kp_scalars], d_kp_v [n_kp, 16, 3] (each may be
+ * vector input features: d_lig_h [n_lig, n_lig_scalars], d_kp_h [n_kp, n_kp_scalars], d_kp_v [n_kp, vector_size, 3] (each may be
  * NULL); positions receive no gradient (they enter through the unit edge vector and the rbf code only and are data in
  * every training configuration served). */
 typedef struct kpd_gvp_trainer kpd_gvp_trainer;
@@ -271,7 +274,8 @@ kpd_status kpd_gvp_trainer_backward(kpd_gvp_trainer *t, const float *d_eps_h, co
  * ReceptorEncoderGVP.__init__ (:99-114) + graph_cutoffs.
  * ------------------------------------------------------------------------------------- */
 typedef struct kpd_recenc_config {
-    int32_t in_scalar_size, out_scalar_size;   /* out_scalar_size in {128, 256}            */
+    int32_t in_scalar_size, out_scalar_size;   /* each 1 .. 256 (kernels are 128 / 256 wide; narrower models run zero
+                                                  padded, the LayerNorms and the attention scale take the true width) */
     int32_t vector_size;                       /* 1 .. 16 (16-channel kernels, fewer are zero padded); kp_v of kpd_rec_out is [n_kp][vector_size][3] */
     int32_t n_rr_convs, n_rk_convs, n_message_gvps, n_update_gvps;
     int32_t message_norm_mode;                 /* 0 constant, 1 'mean', 2 message_norm == 0 */
@@ -296,8 +300,8 @@ typedef struct kpd_rec_batch {
 
 typedef struct kpd_rec_out {
     float *kp_x;                /* [dev] [B*K,3]    keypoint positions                     */
-    float *kp_h;                /* [dev] [B*K,S]    keypoint scalars                       */
-    float *kp_v;                /* [dev] [B*K,16,3] keypoint vectors                       */
+    float *kp_h;                /* [dev] [B*K,out_scalar_size] keypoint scalars            */
+    float *kp_v;                /* [dev] [B*K][vector_size][3] keypoint vectors            */
     int32_t *rk_src, *rk_dst;   /* [dev] [B*K*k_closest] rec->kp edges, kp-major           */
     int32_t cap_kk;             /* capacity of kk_src / kk_dst (>= B*K*min(K-1,100))       */
     int32_t *kk_src, *kk_dst;   /* [dev] kp-kp radius graph, dst-sorted                    */

@@ -81,6 +81,7 @@ struct kpd_egnn {
     int *widen_map = nullptr;
     size_t widen_floats = 0, widen_ints = 0;
     int gemm_mode = 0;                         // 0 exact fp32 MFMA; 1 f16x2 split products in the EGNN GEMMs (KPD_GEMM=f16x2, "gemm=f16x2")
+    bool f32_only = false;                     // atom_nf > 32, rec_nf 129 .. 255, identity encoder below 256: no f16x2 mode
     int prune_last = 1;                        // final layer: only what feeds (h_lig, x_lig) is computed ("prune=0" restores all)
     // optional HIP-event timing of the dominant kernel (k_egnn_edge), for bench.py's roofline
     bool prof_on = false;
@@ -166,15 +167,15 @@ extern "C" kpd_status kpd_egnn_create(const kpd_egnn_config *cfg, kpd_egnn **out
     // hidden_nf 257 .. 1024 (inference only): the wide path of egnn_wide.hip behind the same handle
     KPD_REQUIRE(cfg->hidden_nf >= 1 && cfg->hidden_nf <= WIDE_MAX_HID, KPD_ERR_INVALID, "hidden_nf=%d: the HIP path covers 1 .. %d",
                 cfg->hidden_nf, WIDE_MAX_HID);
-    KPD_REQUIRE(cfg->hidden_nf >= HID || cfg->rec_nf != cfg->hidden_nf, KPD_ERR_INVALID,
-                "rec_nf == hidden_nf = %d (identity keypoint encoder, dynamics.py:326-334) is implemented for hidden_nf = 256 only", cfg->hidden_nf);
     KPD_REQUIRE(cfg->ll_k >= 0 && cfg->ll_k <= KL_KMAX, KPD_ERR_INVALID, "ll_k=%d outside 0..%d (0 = radius graph)", cfg->ll_k, KL_KMAX);
     KPD_REQUIRE(cfg->kl_k >= 0 && cfg->kl_k <= KL_KMAX, KPD_ERR_INVALID, "kl_k=%d outside 0..%d (0 = radius graph)", cfg->kl_k, KL_KMAX);
     KPD_REQUIRE(cfg->kl_k > 0 || cfg->kl_cutoff > 0.0f, KPD_ERR_INVALID, "kl_k = 0 needs graph_cutoffs['kl'] > 0");
     KPD_REQUIRE(cfg->ll_k > 0 || cfg->ll_cutoff > 0.0f, KPD_ERR_INVALID, "ll_k = 0 needs graph_cutoffs['ll'] > 0");
     KPD_REQUIRE(cfg->n_layers >= 1 && cfg->n_layers <= 64, KPD_ERR_INVALID, "n_layers=%d", cfg->n_layers);
-    KPD_REQUIRE(cfg->atom_nf >= 1 && cfg->atom_nf <= 32, KPD_ERR_INVALID, "atom_nf=%d outside 1..32", cfg->atom_nf);
-    KPD_REQUIRE(cfg->rec_nf >= 1 && (cfg->rec_nf <= 128 || cfg->rec_nf == 256), KPD_ERR_INVALID, "rec_nf=%d", cfg->rec_nf);
+    // atom_nf 33 .. 256, rec_nf 129 .. 255 and the identity keypoint encoder (rec_nf == hidden_nf, dynamics.py:326-334) below
+    // hidden_nf 256 take the wider embed / decode forms (launch_embed, launch_decode) and run exact fp32 only
+    KPD_REQUIRE(cfg->atom_nf >= 1 && cfg->atom_nf <= 256, KPD_ERR_INVALID, "atom_nf=%d outside 1..256", cfg->atom_nf);
+    KPD_REQUIRE(cfg->rec_nf >= 1 && cfg->rec_nf <= 256, KPD_ERR_INVALID, "rec_nf=%d outside 1..256", cfg->rec_nf);
     KPD_REQUIRE(cfg->message_norm >= 0.0f, KPD_ERR_INVALID, "message_norm=%f", cfg->message_norm);
     kpd_status st = egnn_kernels_init();
     if (st != KPD_OK) return st;
@@ -189,10 +190,11 @@ extern "C" kpd_status kpd_egnn_create(const kpd_egnn_config *cfg, kpd_egnn **out
         *out = m;
         return KPD_OK;
     }
-    if (const char *e = getenv("KPD_GEMM")) m->gemm_mode = !strcmp(e, "f16x2") ? 1 : 0;
     m->n_et = cfg->update_kp_feat ? 4 : 2;
     m->n_upd = cfg->update_kp_feat ? 2 : 1;
     m->rec_identity = cfg->rec_nf == cfg->hidden_nf;   // dynamics.py:326-334
+    m->f32_only = cfg->atom_nf > 32 || (m->rec_identity ? cfg->hidden_nf != HID : cfg->rec_nf > 128 && cfg->rec_nf != HID);
+    if (const char *e = getenv("KPD_GEMM")) m->gemm_mode = !strcmp(e, "f16x2") && !m->f32_only ? 1 : 0;
     st = build_weight_arena(m);
     if (st == KPD_OK && cfg->hidden_nf != HID) {
         m->widen_floats = (size_t)HW * (2 * HW + 1);
@@ -715,6 +717,9 @@ extern "C" kpd_status kpd_egnn_debug_state(kpd_egnn *m, const char *what, float 
     } else if (w.rfind("gemm=", 0) == 0) {         // "gemm=f32" (exact fp32 MFMA, the contract path) | "gemm=f16x2" (split f16 products)
         const std::string v = w.substr(5);
         KPD_REQUIRE(v == "f32" || v == "f16x2", KPD_ERR_INVALID, "gemm mode must be f32 or f16x2");
+        KPD_REQUIRE(v == "f32" || !m->f32_only, KPD_ERR_INVALID,
+                    "gemm=f16x2: atom_nf = %d / rec_nf = %d (hidden_nf = %d) run the exact fp32 path only; the f16x2 mode covers atom_nf <= 32 "
+                    "with rec_nf <= 128 or 256, or the identity keypoint encoder at hidden_nf 256", m->cfg.atom_nf, m->cfg.rec_nf, m->cfg.hidden_nf);
         KPD_REQUIRE(v == "f32" || !m->committed || m->f16_ok, KPD_ERR_WEIGHTS, "%s", F16_RANGE_ERROR);
         m->gemm_mode = v == "f16x2" ? 1 : 0;
         return KPD_OK;

@@ -71,15 +71,18 @@ __global__ void k_egnn_meta(const int *__restrict__ counts, int e_kk, int active
 
 // ---- encoders (dynamics.py:313-318, 326-334, 355-363) -------------------------------------
 // out[node][0..255] = SiLU(W1 SiLU(W0 in + b0) + b1), out[node][256] = t[graph], pads 0.
-// W1t is stored transposed [hid][256] so that consecutive threads read consecutive floats.
+// W1t is stored transposed [hid][256] so that consecutive threads read consecutive floats.  HMAX bounds the hidden layer: 256, or
+// 512 for the keypoint encoder of rec_nf 129 .. 255 (rec_nf -> 2 rec_nf -> hidden_nf).  Identity (dynamics.py:326-334): the fin
+// input columns, zeros up to 255.
 constexpr int EMB_NODES = 8;
+template <int HMAX>
 __global__ __launch_bounds__(256) void k_embed(const float *__restrict__ in, int n, int fin,
                                                const float *__restrict__ W0, const float *__restrict__ b0, int hid,
                                                const float *__restrict__ W1t, const float *__restrict__ b1,
                                                const float *__restrict__ t, const int *__restrict__ bidx,
                                                float *__restrict__ out, int identity) {
     __shared__ float s_in[EMB_NODES][256];
-    __shared__ float s_hid[EMB_NODES][256];
+    __shared__ float s_hid[EMB_NODES][HMAX];
     const int node0 = blockIdx.x * EMB_NODES, tid = threadIdx.x;
     for (int i = tid; i < EMB_NODES * fin; i += 256) {
         const int j = i / fin, k = i - j * fin;
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(256) void k_embed(const float *__restrict__ in, int
     } else {
 #pragma unroll
         for (int j = 0; j < EMB_NODES; ++j)
-            if (node0 + j < n) out[(size_t)(node0 + j) * HS + tid] = s_in[j][tid];
+            if (node0 + j < n) out[(size_t)(node0 + j) * HS + tid] = tid < fin ? s_in[j][tid] : 0.0f;
     }
     if (tid < EMB_NODES * 8) {
         const int j = tid >> 3, c = tid & 7;
@@ -123,13 +126,15 @@ __global__ __launch_bounds__(256) void k_embed(const float *__restrict__ in, int
 }
 
 // ---- decoder (dynamics.py:320-324, 376-381) -----------------------------------------------
-// One wave per ligand atom.  eps_h = W1 SiLU(W0 h[:256] + b0) + b1;  eps_x = x - x_0.
+// One wave per ligand atom.  eps_h = W1 SiLU(W0 h[:256] + b0) + b1;  eps_x = x - x_0.  HMAX bounds the hidden layer 2 atom_nf:
+// 64 (atom_nf <= 32, one output per lane), or 512 (atom_nf <= 256, each lane walks the outputs 64 apart).
+template <int HMAX>
 __global__ __launch_bounds__(64) void k_decode(const float *__restrict__ h, const float *__restrict__ x,
                                                const float *__restrict__ x0, int n, int atom_nf, int hid,
                                                const float *__restrict__ W0, const float *__restrict__ b0,
                                                const float *__restrict__ W1, const float *__restrict__ b1,
                                                float *__restrict__ eps_h, float *__restrict__ eps_x) {
-    __shared__ float s_hid[64];
+    __shared__ float s_hid[HMAX];
     const int v = blockIdx.x, lane = threadIdx.x;
     if (v >= n) return;
     const f32x4 hv = *reinterpret_cast<const f32x4 *>(h + (size_t)v * HS + 4 * lane);
@@ -153,10 +158,18 @@ __global__ __launch_bounds__(64) void k_decode(const float *__restrict__ h, cons
             if (lane == 0 && u0 + i < hid) s_hid[u0 + i] = silu(s[i] + b0[u0 + i]);
     }
     __syncthreads();
-    if (lane < atom_nf) {
-        float s = b1[lane];
-        for (int u = 0; u < hid; ++u) s = fmaf(W1[(size_t)lane * hid + u], s_hid[u], s);
-        eps_h[(size_t)v * atom_nf + lane] = s;
+    if constexpr (HMAX <= 64) {
+        if (lane < atom_nf) {
+            float s = b1[lane];
+            for (int u = 0; u < hid; ++u) s = fmaf(W1[(size_t)lane * hid + u], s_hid[u], s);
+            eps_h[(size_t)v * atom_nf + lane] = s;
+        }
+    } else {
+        for (int o = lane; o < atom_nf; o += 64) {
+            float s = b1[o];
+            for (int u = 0; u < hid; ++u) s = fmaf(W1[(size_t)o * hid + u], s_hid[u], s);
+            eps_h[(size_t)v * atom_nf + o] = s;
+        }
     }
     if (lane < 3) eps_x[(size_t)v * 3 + lane] = x[(size_t)v * 3 + lane] - x0[(size_t)v * 3 + lane];
 }
@@ -1997,10 +2010,13 @@ kpd_status launch_egnn_meta(const int *counts, int e_kk, int active_mask, int ac
 kpd_status launch_embed(const float *in, int n, int fin, const float *W0, const float *b0, int hid, const float *W1t,
                         const float *b1, const float *t, const int *bidx, float *out, int identity, hipStream_t st) {
     if (n == 0) return KPD_OK;
-    KPD_REQUIRE(fin <= 256 && hid <= 256, KPD_ERR_INVALID, "embed: fin=%d hid=%d exceed 256", fin, hid);
-    KPD_REQUIRE(!identity || fin == 256, KPD_ERR_INVALID, "identity encoder needs 256 input features");
-    hipLaunchKernelGGL(k_embed, dim3(cdiv(n, EMB_NODES)), dim3(256), 0, st, in, n, fin, W0, b0, hid, W1t, b1, t, bidx,
-                       out, identity);
+    KPD_REQUIRE(fin <= 256 && hid <= 512, KPD_ERR_INVALID, "embed: fin=%d hid=%d exceed 256 / 512", fin, hid);
+    if (hid <= 256 || identity)
+        hipLaunchKernelGGL(k_embed<256>, dim3(cdiv(n, EMB_NODES)), dim3(256), 0, st, in, n, fin, W0, b0, hid, W1t, b1, t, bidx,
+                           out, identity);
+    else
+        hipLaunchKernelGGL(k_embed<512>, dim3(cdiv(n, EMB_NODES)), dim3(256), 0, st, in, n, fin, W0, b0, hid, W1t, b1, t, bidx,
+                           out, identity);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
 }
@@ -2009,8 +2025,11 @@ kpd_status launch_decode(const float *h, const float *x, const float *x0, int n,
                          const float *b0, const float *W1, const float *b1, float *eps_h, float *eps_x,
                          hipStream_t st) {
     if (n == 0) return KPD_OK;
-    KPD_REQUIRE(hid <= 64 && atom_nf <= 64, KPD_ERR_INVALID, "decode: hid=%d atom_nf=%d exceed 64", hid, atom_nf);
-    hipLaunchKernelGGL(k_decode, dim3(n), dim3(64), 0, st, h, x, x0, n, atom_nf, hid, W0, b0, W1, b1, eps_h, eps_x);
+    KPD_REQUIRE(hid <= 512 && atom_nf <= 256, KPD_ERR_INVALID, "decode: hid=%d atom_nf=%d exceed 512 / 256", hid, atom_nf);
+    if (hid <= 64 && atom_nf <= 64)
+        hipLaunchKernelGGL(k_decode<64>, dim3(n), dim3(64), 0, st, h, x, x0, n, atom_nf, hid, W0, b0, W1, b1, eps_h, eps_x);
+    else
+        hipLaunchKernelGGL(k_decode<512>, dim3(n), dim3(64), 0, st, h, x, x0, n, atom_nf, hid, W0, b0, W1, b1, eps_h, eps_x);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
 }

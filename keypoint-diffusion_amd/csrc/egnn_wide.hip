@@ -88,11 +88,13 @@ __global__ __launch_bounds__(256) void k_wide_embed(const float *__restrict__ in
 }
 
 // ---- decoder (dynamics.py:320-324, 376-381): one wave per ligand atom; eps_h = W1 SiLU(W0 h[:H] + b0) + b1, eps_x = x - x_0 ----
+// HMAX bounds the hidden layer 2 atom_nf: 64 (atom_nf <= 32, one output per lane) or 512 (atom_nf <= 256, outputs 64 apart per lane)
+template <int HMAX>
 __global__ __launch_bounds__(64) void k_wide_decode(const float *__restrict__ h, int ldh, int H, const float *__restrict__ x,
                                                     const float *__restrict__ x0, int n, int atom_nf, const float *__restrict__ W0,
                                                     const float *__restrict__ b0, const float *__restrict__ W1,
                                                     const float *__restrict__ b1, float *__restrict__ eps_h, float *__restrict__ eps_x) {
-    __shared__ float s_hid[64];
+    __shared__ float s_hid[HMAX];
     const int v = blockIdx.x, lane = threadIdx.x, hid = 2 * atom_nf;
     if (v >= n) return;
     const float *hr = h + (size_t)v * ldh;
@@ -104,10 +106,18 @@ __global__ __launch_bounds__(64) void k_wide_decode(const float *__restrict__ h,
         if (lane == 0) s_hid[u] = wsilu(s + b0[u]);
     }
     __syncthreads();
-    if (lane < atom_nf) {
-        float s = b1[lane];
-        for (int u = 0; u < hid; ++u) s = fmaf(W1[(size_t)lane * hid + u], s_hid[u], s);
-        eps_h[(size_t)v * atom_nf + lane] = s;
+    if constexpr (HMAX <= 64) {
+        if (lane < atom_nf) {
+            float s = b1[lane];
+            for (int u = 0; u < hid; ++u) s = fmaf(W1[(size_t)lane * hid + u], s_hid[u], s);
+            eps_h[(size_t)v * atom_nf + lane] = s;
+        }
+    } else {
+        for (int o = lane; o < atom_nf; o += 64) {
+            float s = b1[o];
+            for (int u = 0; u < hid; ++u) s = fmaf(W1[(size_t)o * hid + u], s_hid[u], s);
+            eps_h[(size_t)v * atom_nf + o] = s;
+        }
     }
     if (lane < 3) eps_x[(size_t)v * 3 + lane] = x[(size_t)v * 3 + lane] - x0[(size_t)v * 3 + lane];
 }
@@ -302,6 +312,7 @@ kpd_status wide_create(const kpd_egnn_config &c, EgnnWide **out) {
     KPD_REQUIRE(c.rec_nf != c.hidden_nf, KPD_ERR_INVALID,
                 "rec_nf == hidden_nf = %d (identity keypoint encoder, dynamics.py:326-334) is implemented for hidden_nf = 256 only", c.hidden_nf);
     KPD_REQUIRE(c.rec_nf <= 256, KPD_ERR_INVALID, "rec_nf=%d: the wide path's keypoint encoder takes at most 256 inputs", c.rec_nf);
+    KPD_REQUIRE(c.atom_nf >= 1 && c.atom_nf <= 256, KPD_ERR_INVALID, "atom_nf=%d outside 1 .. 256", c.atom_nf);
     EgnnWide *m = new EgnnWide();
     m->cfg = c;
     m->H = c.hidden_nf;
@@ -593,8 +604,12 @@ kpd_status wide_forward(EgnnWide *m, const kpd_batch *bt, const float *t_dev, fl
             KPD_LAUNCH_CHECK();
         }
     }
-    hipLaunchKernelGGL(k_wide_decode, dim3(bt->n_lig), dim3(64), 0, st, m->hA[NT_LIG], ldh, m->H, m->x[NT_LIG], bt->lig_x, bt->n_lig,
-                       c.atom_nf, m->de_W0, m->de_b0, m->de_W1, m->de_b1, eps_h, eps_x);
+    if (c.atom_nf <= 32)
+        hipLaunchKernelGGL(k_wide_decode<64>, dim3(bt->n_lig), dim3(64), 0, st, m->hA[NT_LIG], ldh, m->H, m->x[NT_LIG], bt->lig_x, bt->n_lig,
+                           c.atom_nf, m->de_W0, m->de_b0, m->de_W1, m->de_b1, eps_h, eps_x);
+    else
+        hipLaunchKernelGGL(k_wide_decode<512>, dim3(bt->n_lig), dim3(64), 0, st, m->hA[NT_LIG], ldh, m->H, m->x[NT_LIG], bt->lig_x, bt->n_lig,
+                           c.atom_nf, m->de_W0, m->de_b0, m->de_W1, m->de_b1, eps_h, eps_x);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
 }

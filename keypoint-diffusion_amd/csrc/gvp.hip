@@ -77,8 +77,9 @@ extern "C" kpd_status kpd_gvp_create(const kpd_gvp_config *cfg, kpd_gvp **out) {
     KPD_REQUIRE(cfg->n_message_gvps >= 1 && cfg->n_message_gvps <= GVP_MAX_CHAIN && cfg->n_update_gvps >= 1 &&
                     cfg->n_update_gvps <= GVP_MAX_CHAIN && cfg->n_noise_gvps >= 1 && cfg->n_noise_gvps <= GVP_MAX_CHAIN,
                 KPD_ERR_INVALID, "GVP chain lengths must be within 1..%d", GVP_MAX_CHAIN);
-    KPD_REQUIRE(cfg->n_lig_scalars >= 1 && cfg->n_lig_scalars <= 64 && cfg->n_kp_scalars >= 1 && cfg->n_kp_scalars <= 256,
-                KPD_ERR_INVALID, "feature widths out of range");
+    // n_lig_scalars 65 .. 255 (the encoder input n_lig_scalars + 1 fits its 256 columns) run exact fp32 only
+    KPD_REQUIRE(cfg->n_lig_scalars >= 1 && cfg->n_lig_scalars <= 255 && cfg->n_kp_scalars >= 1 && cfg->n_kp_scalars <= 256,
+                KPD_ERR_INVALID, "n_lig_scalars=%d / n_kp_scalars=%d outside 1 .. 255 / 1 .. 256", cfg->n_lig_scalars, cfg->n_kp_scalars);
     KPD_REQUIRE(cfg->message_norm_mode >= 0 && cfg->message_norm_mode <= 2, KPD_ERR_INVALID, "message_norm_mode");
     KPD_TRY(egnn_kernels_init());
     kpd_gvp *m = new kpd_gvp();
@@ -98,7 +99,7 @@ extern "C" kpd_status kpd_gvp_create(const kpd_gvp_config *cfg, kpd_gvp **out) {
     m->S = m->St <= 128 ? 128 : 256;
     m->V = GV;
     m->Vt = cfg->vector_size;
-    if (const char *e = getenv("KPD_GEMM")) m->gemm_mode = (!strcmp(e, "f16x2") && m->S == 256) ? 1 : 0;
+    if (const char *e = getenv("KPD_GEMM")) m->gemm_mode = (!strcmp(e, "f16x2") && m->S == 256 && cfg->n_lig_scalars <= 64) ? 1 : 0;
     const int S = m->S, C = cfg->n_convs;
     m->warena.poison_at = 2;          // packed weights: poisoned only at KPD_POISON >= 2 (engine.h)
     m->msg.resize(C); m->upd.resize(C); m->ln1w.resize(C); m->ln1b.resize(C); m->ln2w.resize(C); m->ln2b.resize(C);
@@ -442,6 +443,8 @@ extern "C" kpd_status kpd_gvp_debug_state(kpd_gvp *m, const char *what, float *o
     if (w.rfind("gemm=", 0) == 0) {              // "gemm=f32" (exact, the default) | "gemm=f16x2" (split f16 products in the message chain)
         const std::string v = w.substr(5);
         KPD_REQUIRE(v == "f32" || v == "f16x2", KPD_ERR_INVALID, "gemm mode must be f32 or f16x2");
+        KPD_REQUIRE(v == "f32" || m->cfg.n_lig_scalars <= 64, KPD_ERR_INVALID,
+                    "gemm=f16x2: the f16x2 mode covers n_lig_scalars <= 64; n_lig_scalars = %d runs the exact fp32 path only", m->cfg.n_lig_scalars);
         KPD_REQUIRE(v == "f32" || m->S != 256 || !m->committed || m->f16_ok, KPD_ERR_WEIGHTS, "%s", F16_RANGE_ERROR);
         m->gemm_mode = (v == "f16x2" && m->S == 256) ? 1 : 0;
         return KPD_OK;

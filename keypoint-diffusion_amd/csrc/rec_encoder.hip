@@ -17,12 +17,14 @@ namespace kpd {
 
 // ---- small kernels ---------------------------------------------------------------------------------
 // out = LN(SiLU(W1 SiLU(W0 in + b0) + b1))   (receptor_encoder_gvp.py:158-164, 221-222)
+// S: row width of `out` and of the packed weights; St <= S: the model's out_scalar_size (the rest is padding: zero weight rows,
+// written as 0, excluded from the LayerNorm statistics)
 constexpr int REMB_NODES = 4;
 __global__ __launch_bounds__(256) void k_rec_embed(const float *__restrict__ in, int n, int fin, const float *__restrict__ W0,
                                                    const float *__restrict__ b0, const float *__restrict__ W1t,
                                                    const float *__restrict__ b1, const float *__restrict__ lw,
-                                                   const float *__restrict__ lb, int S, float *__restrict__ out) {
-    __shared__ float s_in[REMB_NODES][64];
+                                                   const float *__restrict__ lb, int S, int St, float *__restrict__ out) {
+    __shared__ float s_in[REMB_NODES][256];
     __shared__ float s_hid[REMB_NODES][256];
     __shared__ float s_red[REMB_NODES][2][4];
     const int node0 = blockIdx.x * REMB_NODES, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -31,7 +33,7 @@ __global__ __launch_bounds__(256) void k_rec_embed(const float *__restrict__ in,
         s_in[j][k] = node0 + j < n ? in[(size_t)(node0 + j) * fin + k] : 0.0f;
     }
     __syncthreads();
-    const bool on = tid < S;
+    const bool on = tid < St;
     float y[REMB_NODES];
 #pragma unroll
     for (int j = 0; j < REMB_NODES; ++j) y[j] = on ? b0[tid] : 0.0f;
@@ -47,7 +49,7 @@ __global__ __launch_bounds__(256) void k_rec_embed(const float *__restrict__ in,
 #pragma unroll
     for (int j = 0; j < REMB_NODES; ++j) y[j] = on ? b1[tid] : 0.0f;
     if (on)
-        for (int u = 0; u < S; ++u) {
+        for (int u = 0; u < St; ++u) {
             const float wv = W1t[(size_t)u * S + tid];
 #pragma unroll
             for (int j = 0; j < REMB_NODES; ++j) y[j] = fmaf(wv, s_hid[j][u], y[j]);
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(256) void k_rec_embed(const float *__restrict__ in,
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < REMB_NODES; ++j) {
-        mean[j] = (s_red[j][0][0] + s_red[j][0][1] + s_red[j][0][2] + s_red[j][0][3]) / (float)S;
+        mean[j] = (s_red[j][0][0] + s_red[j][0][1] + s_red[j][0][2] + s_red[j][0][3]) / (float)St;
         const float d = on ? y[j] - mean[j] : 0.0f;
         float v = d * d;
 #pragma unroll
@@ -75,10 +77,19 @@ __global__ __launch_bounds__(256) void k_rec_embed(const float *__restrict__ in,
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < REMB_NODES; ++j) {
-        const float rstd = 1.0f / sqrtf((s_red[j][1][0] + s_red[j][1][1] + s_red[j][1][2] + s_red[j][1][3]) / (float)S + 1e-5f);
+        const float rstd = 1.0f / sqrtf((s_red[j][1][0] + s_red[j][1][1] + s_red[j][1][2] + s_red[j][1][3]) / (float)St + 1e-5f);
         const int v = node0 + j;
-        if (on && v < n) out[(size_t)v * S + tid] = (y[j] - mean[j]) * rstd * lw[tid] + lb[tid];
+        if (tid < S && v < n) out[(size_t)v * S + tid] = on ? (y[j] - mean[j]) * rstd * lw[tid] + lb[tid] : 0.0f;
     }
+}
+
+// dst[R][C] = the [rows][cols] matrix src (or its transpose [cols][rows] when `transpose`) in the top-left corner, zeros elsewhere
+__global__ void k_pad2d(const float *__restrict__ src, int rows, int cols, int transpose, float *__restrict__ dst, int R, int C) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= R * C) return;
+    const int r = i / C, c = i - r * C;
+    const int sr = transpose ? c : r, sc = transpose ? r : c;
+    dst[i] = (sr < rows && sc < cols) ? src[(size_t)sr * cols + sc] : 0.0f;
 }
 
 __global__ void k_iota_scaled(int *out, int n, int scale) {
@@ -116,23 +127,25 @@ __global__ __launch_bounds__(256) void k_graph_mean(const float *__restrict__ s,
     out[(size_t)b * S + c] = acc / (float)(ptr[b + 1] - ptr[b]);
 }
 
-// keypoint embedding: LN_{S*K}(SiLU(W mean + b)) -> [B][K][S]  (receptor_encoder_gvp.py:31-35, 54-55)
+// keypoint embedding: LN_{St*K}(SiLU(W mean + b)) -> [B][K][S]  (receptor_encoder_gvp.py:31-35, 54-55): W is the model's
+// [K St, St]; the LayerNorm runs over the K St live entries of the (k d) layout, entry j lands in column j % St of keypoint j / St,
+// columns St .. S - 1 are written as 0
 constexpr int KPE_MAX = 10240;
 __global__ __launch_bounds__(256) void k_kp_embed(const float *__restrict__ mean, const float *__restrict__ W,
                                                   const float *__restrict__ b, const float *__restrict__ lw,
-                                                  const float *__restrict__ lb, int S, int SK, float *__restrict__ out) {
+                                                  const float *__restrict__ lb, int S, int St, int K, float *__restrict__ out) {
     __shared__ float s_m[256];
     __shared__ float s_buf[KPE_MAX];
     __shared__ float s_red[4];
     __shared__ float s_stat[2];
-    const int g = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int g = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, SK = St * K;
     if (tid < S) s_m[tid] = mean[(size_t)g * S + tid];
     __syncthreads();
     float part = 0.0f;
     for (int j = tid; j < SK; j += 256) {
         float acc = b[j];
-        const float *w = W + (size_t)j * S;
-        for (int k = 0; k < S; ++k) acc = fmaf(w[k], s_m[k], acc);
+        const float *w = W + (size_t)j * St;
+        for (int k = 0; k < St; ++k) acc = fmaf(w[k], s_m[k], acc);
         acc = silu(acc);
         s_buf[j] = acc;
         part += acc;
@@ -157,7 +170,9 @@ __global__ __launch_bounds__(256) void k_kp_embed(const float *__restrict__ mean
     if (tid == 0) s_stat[1] = 1.0f / sqrtf((s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (float)SK + 1e-5f);
     __syncthreads();
     const float rstd = s_stat[1];
-    for (int j = tid; j < SK; j += 256) out[(size_t)g * SK + j] = (s_buf[j] - mu) * rstd * lw[j] + lb[j];
+    for (int j = tid; j < SK; j += 256) out[((size_t)g * K + j / St) * S + j % St] = (s_buf[j] - mu) * rstd * lw[j] + lb[j];
+    const int pad = S - St;
+    for (int i = tid; i < K * pad; i += 256) out[((size_t)g * K + i / pad) * S + St + i % pad] = 0.0f;
 }
 
 // out[node][:] = Wt^T in[node][:]  (bias-free Linear with the weight stored transposed [in][out])
@@ -183,16 +198,17 @@ __global__ __launch_bounds__(256) void k_linear_rows(const float *__restrict__ i
 }
 
 // attention-pooled keypoint positions (receptor_encoder_gvp.py:57-87): one workgroup per keypoint;
-// logits are exponentiated without max-subtraction, exactly as upstream.
+// logits are exponentiated without max-subtraction, exactly as upstream, and scaled by 1 / sqrt(St) of the model's width (the
+// S - St padding columns of both operands are 0).
 __global__ __launch_bounds__(256) void k_kp_attention(const float *__restrict__ ft_src, const float *__restrict__ ft_dst,
                                                       const float *__restrict__ rec_x, const int *__restrict__ rec_ptr, int K,
-                                                      int S, float *__restrict__ kp_x) {
+                                                      int S, int St, float *__restrict__ kp_x) {
     __shared__ float s_q[256];
     __shared__ float s_part[256][4];
     const int kp = blockIdx.x, g = kp / K, tid = threadIdx.x;
     if (tid < S) s_q[tid] = ft_dst[(size_t)kp * S + tid];
     __syncthreads();
-    const float scale = 1.0f / sqrtf((float)S);
+    const float scale = 1.0f / sqrtf((float)St);
     float a_sum = 0.f, ax = 0.f, ay = 0.f, az = 0.f;
     for (int r = rec_ptr[g] + tid; r < rec_ptr[g + 1]; r += 256) {
         const float *f = ft_src + (size_t)r * S;
@@ -239,7 +255,7 @@ kpd_status launch_linear_rows(const float *in, int n, int S, const float *Wt, fl
 kpd_status launch_kp_attention(const float *ft_src, const float *ft_dst, const float *rec_x, const int *rec_ptr, int n_kp, int K,
                                int S, float *kp_x, hipStream_t st) {
     KPD_REQUIRE(S <= 256, KPD_ERR_INVALID, "kp attention: S=%d > 256", S);
-    hipLaunchKernelGGL(k_kp_attention, dim3(n_kp), dim3(256), 0, st, ft_src, ft_dst, rec_x, rec_ptr, K, S, kp_x);
+    hipLaunchKernelGGL(k_kp_attention, dim3(n_kp), dim3(256), 0, st, ft_src, ft_dst, rec_x, rec_ptr, K, S, S, kp_x);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
 }
@@ -249,7 +265,8 @@ kpd_status launch_kp_attention(const float *ft_src, const float *ft_dst, const f
 // ---- engine -----------------------------------------------------------------------------------------
 struct kpd_recenc {
     kpd_recenc_config cfg;
-    int S;
+    int S;                    // kernel width 128 or 256
+    int St;                   // out_scalar_size <= S: the S - St trailing scalars of every row are padding (zero weight rows / columns)
     Arena warena, ws;
     std::vector<std::vector<HostGvp>> rr_msg, rr_upd, rk_msg, rk_upd;   // [conv][j]
     std::vector<float *> rr_ln1w, rr_ln1b, rr_ln2w, rr_ln2b, rk_ln1w, rk_ln1b, rk_ln2w, rk_ln2b;
@@ -278,13 +295,14 @@ static void alloc_conv(kpd_recenc *m, Carve &A, std::vector<HostGvp> &msg, std::
         g.sout = S;
         g.split = j == 0 ? (use_dst ? SPLIT_SRC_DST : SPLIT_SRC) : SPLIT_NONE;
         g.S = S;
+        g.cut = S - m->St;
         g.chain_pos = j;
         g.vcut = GV - c.vector_size;             // narrower models: every 16-channel block carries vector_size channels (gvp_host.hip)
         alloc_gvp(A, g, m->expected, pre + "edge_message." + std::to_string(j));
     }
     for (int j = 0; j < c.n_update_gvps; ++j) {
         HostGvp &g = upd[j];
-        g.vin = GV; g.vout = GV; g.s_in = S; g.sout = S;
+        g.vin = GV; g.vout = GV; g.s_in = S; g.sout = S; g.S = S; g.cut = S - m->St;
         g.chain_pos = 1;
         g.vcut = GV - c.vector_size;
         alloc_gvp(A, g, m->expected, pre + "node_update." + std::to_string(j));
@@ -299,9 +317,12 @@ static void alloc_conv(kpd_recenc *m, Carve &A, std::vector<HostGvp> &msg, std::
 extern "C" kpd_status kpd_recenc_create(const kpd_recenc_config *cfg, kpd_recenc **out) {
     KPD_REQUIRE(cfg && out, KPD_ERR_INVALID, "null argument");
     KPD_REQUIRE(cfg->vector_size >= 1 && cfg->vector_size <= GV, KPD_ERR_INVALID, "vector_size=%d outside 1 .. %d", cfg->vector_size, GV);
-    KPD_REQUIRE(cfg->out_scalar_size == 128 || cfg->out_scalar_size == 256, KPD_ERR_INVALID, "out_scalar_size=%d: supported 128, 256",
+    // any out_scalar_size up to 256 runs on the 128- or 256-wide kernels, as in the GVP denoiser (gvp.hip): weights packed with zero
+    // rows / columns for the padding scalars, which stay exactly 0; the LayerNorms and the attention scale take the true width
+    KPD_REQUIRE(cfg->out_scalar_size >= 1 && cfg->out_scalar_size <= 256, KPD_ERR_INVALID, "out_scalar_size=%d outside 1 .. 256",
                 cfg->out_scalar_size);
-    KPD_REQUIRE(cfg->in_scalar_size >= 1 && cfg->in_scalar_size <= 64, KPD_ERR_INVALID, "in_scalar_size=%d", cfg->in_scalar_size);
+    KPD_REQUIRE(cfg->in_scalar_size >= 1 && cfg->in_scalar_size <= 256, KPD_ERR_INVALID, "in_scalar_size=%d outside 1 .. 256",
+                cfg->in_scalar_size);
     KPD_REQUIRE((cfg->k_closest >= 1 && cfg->k_closest <= KL_KMAX && cfg->kp_rad == 0.0f) || (cfg->k_closest == 0 && cfg->kp_rad > 0.0f),
                 KPD_ERR_INVALID, "rec->kp graph: either 1 <= k_closest <= %d with kp_rad = 0, or k_closest = 0 with kp_rad > 0 (got %d, %f)",
                 KL_KMAX, cfg->k_closest, cfg->kp_rad);
@@ -315,7 +336,7 @@ extern "C" kpd_status kpd_recenc_create(const kpd_recenc_config *cfg, kpd_recenc
     KPD_TRY(egnn_kernels_init());
     kpd_recenc *m = new kpd_recenc();
     m->cfg = *cfg;
-    const int S = m->S = cfg->out_scalar_size, K = cfg->n_keypoints, F = cfg->in_scalar_size;
+    const int St = m->St = cfg->out_scalar_size, S = m->S = St <= 128 ? 128 : 256, K = cfg->n_keypoints, F = cfg->in_scalar_size;
     m->warena.poison_at = 2;          // packed weights: poisoned only at KPD_POISON >= 2 (engine.h)
     m->rr_msg.resize(cfg->n_rr_convs); m->rr_upd.resize(cfg->n_rr_convs);
     m->rk_msg.resize(cfg->n_rk_convs); m->rk_upd.resize(cfg->n_rk_convs);
@@ -335,8 +356,8 @@ extern "C" kpd_status kpd_recenc_create(const kpd_recenc_config *cfg, kpd_recenc
         A(m->emb_W0, (size_t)S * F); A(m->emb_b0, S);
         A(m->emb_W1t, (size_t)S * S); A(m->emb_b1, S);
         A(m->emb_lw, S); A(m->emb_lb, S);
-        A(m->kpe_W, (size_t)S * K * S); A(m->kpe_b, (size_t)S * K);
-        A(m->kpe_lw, (size_t)S * K); A(m->kpe_lb, (size_t)S * K);
+        A(m->kpe_W, (size_t)St * K * St); A(m->kpe_b, (size_t)St * K);
+        A(m->kpe_lw, (size_t)St * K); A(m->kpe_lb, (size_t)St * K);
         A(m->src_Wt, (size_t)S * S); A(m->dst_Wt, (size_t)S * S);
     });
     if (st != KPD_OK) {
@@ -373,36 +394,42 @@ extern "C" kpd_status kpd_recenc_load_weight(kpd_recenc *m, const char *name, co
         set_error("unknown or unused weight name '%s' for this configuration", name);
         return KPD_ERR_WEIGHTS;
     }
-    const int S = m->S, K = m->cfg.n_keypoints, F = m->cfg.in_scalar_size;
+    const int S = m->S, St = m->St, K = m->cfg.n_keypoints, F = m->cfg.in_scalar_size;
     const std::vector<std::string> tk = split_dots(nm);
     auto tail_from = [&](size_t i) {
         std::string t;
         for (size_t k = i; k < tk.size(); ++k) t += (k > i ? "." : "") + tk[k];
         return t;
     };
+    // [rows][cols] (transposed: [cols][rows]) into the top-left corner of an R x C block, zeros elsewhere
+    auto pad2d = [&](int rows, int cols, bool transpose, float *dst, int R, int C) -> kpd_status {
+        hipLaunchKernelGGL(k_pad2d, dim3(cdiv(R * C, 256)), dim3(256), 0, st, w, rows, cols, transpose ? 1 : 0, dst, R, C);
+        KPD_LAUNCH_CHECK();
+        return KPD_OK;
+    };
     const bool is_w = tk.back() == "weight";
-    if (tk[0] == "scalar_embed") {
+    if (tk[0] == "scalar_embed") {        // rows (and columns) St .. S - 1 stay zero
         if (tk[1] == "0") {
-            if (is_w) { KPD_TRY(want_shape(name, shape, ndim, {S, F})); KPD_TRY(copy_pad(w, S * F, m->emb_W0, S * F, st)); }
-            else { KPD_TRY(want_shape(name, shape, ndim, {S})); KPD_TRY(copy_pad(w, S, m->emb_b0, S, st)); }
+            if (is_w) { KPD_TRY(want_shape(name, shape, ndim, {St, F})); KPD_TRY(pad2d(St, F, false, m->emb_W0, S, F)); }
+            else { KPD_TRY(want_shape(name, shape, ndim, {St})); KPD_TRY(copy_pad(w, St, m->emb_b0, S, st)); }
         } else {
-            if (is_w) { KPD_TRY(want_shape(name, shape, ndim, {S, S})); KPD_TRY(transpose2d(w, S, S, m->emb_W1t, st)); }
-            else { KPD_TRY(want_shape(name, shape, ndim, {S})); KPD_TRY(copy_pad(w, S, m->emb_b1, S, st)); }
+            if (is_w) { KPD_TRY(want_shape(name, shape, ndim, {St, St})); KPD_TRY(pad2d(St, St, true, m->emb_W1t, S, S)); }
+            else { KPD_TRY(want_shape(name, shape, ndim, {St})); KPD_TRY(copy_pad(w, St, m->emb_b1, S, st)); }
         }
     } else if (tk[0] == "scalar_norm") {
-        KPD_TRY(want_shape(name, shape, ndim, {S}));
-        KPD_TRY(copy_pad(w, S, is_w ? m->emb_lw : m->emb_lb, S, st));
+        KPD_TRY(want_shape(name, shape, ndim, {St}));
+        KPD_TRY(copy_pad(w, St, is_w ? m->emb_lw : m->emb_lb, S, st));
     } else if (tk[0] == "keypoint_initializer") {
         if (tk[1] == "src_net" || tk[1] == "dst_net") {
-            KPD_TRY(want_shape(name, shape, ndim, {S, S}));
-            KPD_TRY(transpose2d(w, S, S, tk[1] == "src_net" ? m->src_Wt : m->dst_Wt, st));
-        } else {   // keypoint_embedding.{0,2}.{weight,bias}
+            KPD_TRY(want_shape(name, shape, ndim, {St, St}));
+            KPD_TRY(pad2d(St, St, true, tk[1] == "src_net" ? m->src_Wt : m->dst_Wt, S, S));
+        } else {   // keypoint_embedding.{0,2}.{weight,bias}: the model's own (k d) layout, unpadded
             if (tk[2] == "0") {
-                if (is_w) { KPD_TRY(want_shape(name, shape, ndim, {S * K, S})); KPD_TRY(copy_pad(w, S * K * S, m->kpe_W, S * K * S, st)); }
-                else { KPD_TRY(want_shape(name, shape, ndim, {S * K})); KPD_TRY(copy_pad(w, S * K, m->kpe_b, S * K, st)); }
+                if (is_w) { KPD_TRY(want_shape(name, shape, ndim, {St * K, St})); KPD_TRY(copy_pad(w, St * K * St, m->kpe_W, St * K * St, st)); }
+                else { KPD_TRY(want_shape(name, shape, ndim, {St * K})); KPD_TRY(copy_pad(w, St * K, m->kpe_b, St * K, st)); }
             } else {
-                KPD_TRY(want_shape(name, shape, ndim, {S * K}));
-                KPD_TRY(copy_pad(w, S * K, is_w ? m->kpe_lw : m->kpe_lb, S * K, st));
+                KPD_TRY(want_shape(name, shape, ndim, {St * K}));
+                KPD_TRY(copy_pad(w, St * K, is_w ? m->kpe_lw : m->kpe_lb, St * K, st));
             }
         }
     } else {       // rr_conv_layers.<i>.<block>... | rk_conv_layers.<i>.<block>...
@@ -413,11 +440,11 @@ extern "C" kpd_status kpd_recenc_load_weight(kpd_recenc *m, const char *name, co
             std::vector<HostGvp> &vec = blk == "edge_message" ? (rr ? m->rr_msg[i] : m->rk_msg[i]) : (rr ? m->rr_upd[i] : m->rk_upd[i]);
             KPD_TRY(load_gvp_tensor(vec[atoi(tk[3].c_str())], tail_from(4), name, w, shape, ndim, st));
         } else {   // message_layer_norm.feat_norm.<p> | update_layer_norm.feat_norm.<p>
-            KPD_TRY(want_shape(name, shape, ndim, {S}));
+            KPD_TRY(want_shape(name, shape, ndim, {St}));
             float *dst;
             if (blk == "message_layer_norm") dst = rr ? (is_w ? m->rr_ln1w[i] : m->rr_ln1b[i]) : (is_w ? m->rk_ln1w[i] : m->rk_ln1b[i]);
             else dst = rr ? (is_w ? m->rr_ln2w[i] : m->rr_ln2b[i]) : (is_w ? m->rk_ln2w[i] : m->rk_ln2b[i]);
-            KPD_TRY(copy_pad(w, S, dst, S, st));
+            KPD_TRY(copy_pad(w, St, dst, S, st));
         }
     }
     m->loaded.insert(nm);
@@ -511,7 +538,7 @@ static kpd_status run_conv(kpd_recenc *m, int et, int n_src, int n_dst, int n_ed
     na.ms_main[0] = m->ms_main; na.ms_cont[0] = m->ms_cont; na.mv_main[0] = m->mv_main; na.mv_cont[0] = m->mv_cont;
     na.ln1_w = ln[0]; na.ln1_b = ln[1]; na.ln2_w = ln[2]; na.ln2_b = ln[3];
     na.n_gvps = c.n_update_gvps; na.S = S;
-    na.ln_inv_n = 1.0f / (float)S; na.ln_pad = 0.0f;
+    na.ln_inv_n = 1.0f / (float)m->St; na.ln_pad = (float)(S - m->St);     // scalar half of GVPLayerNorm over the model's width
     na.vn_inv_n = 1.0f / (float)c.vector_size; na.vn_pad = (float)(GV - c.vector_size);      // vector half of GVPLayerNorm over the model's channels
     for (int j = 0; j < c.n_update_gvps; ++j) na.g[j] = upd[j].dev();
     np.tiles0 = dnt == 0 ? cdiv(n_dst, TM) : 0;
@@ -529,7 +556,7 @@ extern "C" kpd_status kpd_recenc_forward(kpd_recenc *m, const kpd_rec_batch *bt,
                     out->kk_per_graph && out->counts, KPD_ERR_INVALID, "output buffers missing");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const kpd_recenc_config &c = m->cfg;
-    const int S = m->S, K = c.n_keypoints, B = bt->B, n_rec = bt->n_rec, n_kp = B * K;
+    const int S = m->S, St = m->St, K = c.n_keypoints, B = bt->B, n_rec = bt->n_rec, n_kp = B * K;
     KPD_REQUIRE(out->cap_kk >= (long)n_kp * std::min(K - 1, 100), KPD_ERR_CAPACITY, "cap_kk=%d too small", out->cap_kk);
 
     KPD_TRY(launch_node_graph_index(bt->rec_ptr, B, n_rec, m->bidx[0], st));
@@ -537,7 +564,7 @@ extern "C" kpd_status kpd_recenc_forward(kpd_recenc *m, const kpd_rec_batch *bt,
     KPD_LAUNCH_CHECK();
     KPD_TRY(launch_node_graph_index(m->kp_ptr, B, n_kp, m->bidx[1], st));
     hipLaunchKernelGGL(k_rec_embed, dim3(cdiv(n_rec, REMB_NODES)), dim3(256), 0, st, bt->rec_h, n_rec, c.in_scalar_size, m->emb_W0,
-                       m->emb_b0, m->emb_W1t, m->emb_b1, m->emb_lw, m->emb_lb, S, m->s[0]);
+                       m->emb_b0, m->emb_W1t, m->emb_b1, m->emb_lw, m->emb_lb, S, St, m->s[0]);
     KPD_LAUNCH_CHECK();
     KPD_HIP(hipMemsetAsync(m->v[0], 0, (size_t)n_rec * 48 * 4, st));                               // :225
 
@@ -557,13 +584,13 @@ extern "C" kpd_status kpd_recenc_forward(kpd_recenc *m, const kpd_rec_batch *bt,
     // keypoint positions (:40-93)
     hipLaunchKernelGGL(k_graph_mean, dim3(B), dim3(256), 0, st, m->s[0], bt->rec_ptr, S, m->gmean);
     KPD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_kp_embed, dim3(B), dim3(256), 0, st, m->gmean, m->kpe_W, m->kpe_b, m->kpe_lw, m->kpe_lb, S, S * K, m->kp_emb);
+    hipLaunchKernelGGL(k_kp_embed, dim3(B), dim3(256), 0, st, m->gmean, m->kpe_W, m->kpe_b, m->kpe_lw, m->kpe_lb, S, St, K, m->kp_emb);
     KPD_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_linear_rows, dim3(cdiv(n_rec, 4)), dim3(256), 0, st, m->s[0], n_rec, S, m->src_Wt, m->ft_src);
     KPD_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_linear_rows, dim3(cdiv(n_kp, 4)), dim3(256), 0, st, m->kp_emb, n_kp, S, m->dst_Wt, m->ft_dst);
     KPD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_kp_attention, dim3(n_kp), dim3(256), 0, st, m->ft_src, m->ft_dst, bt->rec_x, bt->rec_ptr, K, S, out->kp_x);
+    hipLaunchKernelGGL(k_kp_attention, dim3(n_kp), dim3(256), 0, st, m->ft_src, m->ft_dst, bt->rec_x, bt->rec_ptr, K, S, St, out->kp_x);
     KPD_LAUNCH_CHECK();
     KPD_HIP(hipMemsetAsync(m->s[1], 0, (size_t)n_kp * S * 4, st));                                 // :90-91
     KPD_HIP(hipMemsetAsync(m->v[1], 0, (size_t)n_kp * 48 * 4, st));
@@ -588,7 +615,9 @@ extern "C" kpd_status kpd_recenc_forward(kpd_recenc *m, const kpd_rec_batch *bt,
         KPD_TRY(run_conv(m, 2, n_rec, n_kp, n_kp * std::min(rk_per_kp(c), bt->max_rec), out->rk_src, out->rk_dst, m->rk_rowptr, bt->rec_x, out->kp_x,
                          m->rk_msg[i], m->rk_upd[i], ln, i != 0, c.rk_cutoff, st));
     }
-    KPD_HIP(hipMemcpyAsync(out->kp_h, m->s[1], (size_t)n_kp * S * 4, hipMemcpyDeviceToDevice, st));
+    // kp_h [n_kp][St]: the live columns of the S-wide rows
+    if (St == S) KPD_HIP(hipMemcpyAsync(out->kp_h, m->s[1], (size_t)n_kp * S * 4, hipMemcpyDeviceToDevice, st));
+    else KPD_HIP(hipMemcpy2DAsync(out->kp_h, (size_t)St * 4, m->s[1], (size_t)S * 4, (size_t)St * 4, n_kp, hipMemcpyDeviceToDevice, st));
     // kp v_0 [n_kp][vector_size][3]: the leading channels of the 16-channel rows
     if (c.vector_size == GV) KPD_HIP(hipMemcpyAsync(out->kp_v, m->v[1], (size_t)n_kp * 48 * 4, hipMemcpyDeviceToDevice, st));
     else KPD_HIP(hipMemcpy2DAsync(out->kp_v, (size_t)c.vector_size * 12, m->v[1], 48 * 4, (size_t)c.vector_size * 12, n_kp, hipMemcpyDeviceToDevice, st));
