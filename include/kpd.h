@@ -539,6 +539,57 @@ kpd_status kpd_xyz_emit(const float *pos, const float *feat, const int32_t *lig_
                         int32_t F, const uint32_t *symbols, int32_t *elem, uint8_t *text, int64_t capacity,
                         int64_t *text_ptr, int32_t *status, void *scratch, void *stream);
 
+/* Pocket extraction: the array-level part of dataset construction, for a batch of whole receptors + ligands
+ * (csrc/pocket.hip).  Replaces get_pocket_atoms (data_processing/pdbbind_processing.py:85-149, called by
+ * process_crossdocked.py:112-119) and the residue-wise selection of process_bindingmoad.py:124-161 / byop.py:119-157:
+ * ligand bounding box + padding (:92-97, :114-117), atoms closer than pocket_cutoff to a ligand atom (:124-128), expansion to
+ * whole residues (torch.isin, :131-134), compaction (:137-138).  PDB / SDF parsing stays with the caller.
+ *   rec_x [n_rec,3], rec_ptr [B+1] (complex b = rows [rec_ptr[b], rec_ptr[b+1]), at most max_rec each), res_idx [n_rec]
+ *   (per complex in [0, atoms of that complex), as prody's getResindices; need not be contiguous or sorted), probe [n_rec]
+ *   bytes (atoms that count for the distance test), emit [n_rec] bytes (atoms that may appear in the pocket), lig_x [n_lig,3],
+ *   lig_ptr [B+1] (at most 1024 ligand atoms per complex); box_padding < 0: no box; all device pointers.
+ *   A residue is selected if one of its probe atoms lies inside the box and closer than pocket_cutoff to a ligand atom.
+ *   Out (device): in_box [n_rec] bytes (geometric box test of every atom, upstream's >= lower, <= upper on fp32 corners),
+ *   pocket_mask [n_rec] bytes (emit and residue selected: upstream's byres_pocket_atom_mask), rows [cap_rows] (selected atoms,
+ *   global row numbers ascending), pocket_res [cap_rows] (rank of the atom's residue among the selected residues of its complex
+ *   in order of first appearance), pocket_ptr [B+1] (pocket_ptr[B] is the size needed, also when it exceeds cap_rows; the rows of
+ *   a complex that does not fit are not written), status [B]: bit 0 = no pocket atom, bit 1 = cap_rows too small for this
+ *   complex, bit 2 = a res_idx outside its range (that atom is never selected), bit 3 = malformed segment, more than max_rec
+ *   atoms or more than 1024 ligand atoms (complex left out).  Nothing is read or written out of bounds in any of these cases.
+ *   scratch: kpd_pocket_scratch_bytes(n_rec, B) device bytes.  Four kernel launches (and five memsets) whatever B is; no host synchronisation.
+ * Arithmetic: every threshold test compares the squared distance, computed in fp64 from direct differences of the fp32
+ * coordinates (the differences are exact), with the squared threshold; a NaN coordinate is never selected.  Upstream's own
+ * decisions (scipy float64 / torch.cdist's fp32 matmul form) agree with this wherever they are stable.
+ * Deterministic and bitwise independent of batch composition (no float atomics; flags are same-value byte stores).
+ * ------------------------------------------------------------------------------------- */
+int64_t kpd_pocket_scratch_bytes(int32_t n_rec, int32_t B);
+kpd_status kpd_pocket_select(const float *rec_x, const int32_t *rec_ptr, const int32_t *res_idx, const uint8_t *probe,
+                             const uint8_t *emit, int32_t n_rec, int32_t max_rec, const float *lig_x, const int32_t *lig_ptr,
+                             int32_t n_lig, int32_t B, float box_padding, float pocket_cutoff, int32_t cap_rows, uint8_t *in_box,
+                             uint8_t *pocket_mask, int32_t *rows, int32_t *pocket_res, int32_t *pocket_ptr, int32_t *status,
+                             void *scratch, void *stream);
+
+/* Interface points, the targets of the optimal-transport encoder loss (losses/rec_encoder_loss.py:71-82).  Replaces
+ * get_interface_points (data_processing/pdbbind_processing.py:295-325; called at :142-145 with the box atoms and at
+ * process_bindingmoad.py:200 with the pocket atoms): midpoints (lig + rec) / 2 of all pairs closer than dist_thr in
+ * torch.where order (ligand atom ascending, then receptor atom ascending, :306-308), thinned by the sequential greedy rule
+ * (:312-321: the first candidate is kept, a later one if it is >= excl_thr from every point kept so far).
+ *   rec_x, rec_ptr, lig_x, lig_ptr as above; cand_mask [n_rec] bytes = the candidate receptor set (in_box & probe for the
+ *   CrossDocked form, pocket_mask for the BindingMOAD / byop form); cap_cand = candidate capacity per complex, cap_points =
+ *   capacity of points (all complexes together).
+ *   Out (device): points [cap_points,3], ip_ptr [B+1] (ip_ptr[B] is the size needed; the points of a complex that does not fit
+ *   are not written), n_cand [B] (exact, also beyond cap_cand), status [B]: bit 0 = no candidate (upstream raises
+ *   InterfacePointException), bit 1 = more candidates than cap_cand (the points are then those of the first cap_cand
+ *   candidates, a prefix of the full answer), more than 4096 points in one complex, or cap_points too small for this complex,
+ *   bit 3 = malformed segment or more than 1024 ligand atoms.  scratch: kpd_interface_points_scratch_bytes(n_rec, B, cap_cand).
+ *   Three launches whatever B is; no host synchronisation.  Arithmetic and determinism as for kpd_pocket_select; midpoints are
+ *   (a + b) * 0.5f in fp32, bitwise upstream's. */
+int64_t kpd_interface_points_scratch_bytes(int32_t n_rec, int32_t B, int32_t cap_cand);
+kpd_status kpd_interface_points(const float *rec_x, const int32_t *rec_ptr, const uint8_t *cand_mask, int32_t n_rec,
+                                const float *lig_x, const int32_t *lig_ptr, int32_t n_lig, int32_t B, float dist_thr,
+                                float excl_thr, int32_t cap_cand, int32_t cap_points, float *points, int32_t *ip_ptr,
+                                int32_t *n_cand, int32_t *status, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,14 @@ def lib():
     L.kpd_xyz_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.kpd_dist_hinge.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5
+    L.kpd_pocket_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.kpd_pocket_scratch_bytes.restype = C.c_int64
+    L.kpd_pocket_select.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
+                                    C.c_float, C.c_int32] + [C.c_void_p] * 8
+    L.kpd_interface_points_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.kpd_interface_points_scratch_bytes.restype = C.c_int64
+    L.kpd_interface_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_float, C.c_float, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     _lib = L
     return L
 
@@ -222,6 +230,7 @@ EXPORTS = [
     'kpd_recegnn_trainer_create', 'kpd_recegnn_trainer_destroy', 'kpd_recegnn_trainer_bind', 'kpd_recegnn_trainer_reserve',
     'kpd_recegnn_trainer_forward', 'kpd_recegnn_trainer_backward', 'kpd_ot_emd_uniform', 'kpd_sgemm',
     'kpd_dist_hinge',
+    'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
 ]
 
 
@@ -1019,6 +1028,77 @@ def build_rec_graph(rec_x: torch.Tensor, rec_ptr: torch.Tensor, max_rec: int, r:
     if E > cap:
         raise KpdError(f'rr graph: {E} edges exceed the capacity {cap} (internal sizing error)')
     return src[:E], dst[:E], per_graph, (same[:E].bool() if same is not None else None)
+
+
+POCKET_EMPTY, POCKET_CAPACITY, POCKET_BAD_RES, POCKET_BAD_SEGMENT = 1, 2, 4, 8     # status bits of the two pocket entry points
+POCKET_MAX_LIG = 1024
+
+
+def _pocket_args(rec_x, rec_ptr, lig_x, lig_ptr, masks):
+    rec_x, lig_x = _dev_f32(rec_x, 'rec_x'), _dev_f32(lig_x, 'lig_x')
+    for name, t in (('rec_ptr', rec_ptr), ('lig_ptr', lig_ptr)):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.numel() >= 1 and t.is_contiguous()):
+            raise KpdError(f'{name} must be a contiguous int32 GPU tensor of B + 1 offsets')
+    n_rec, B = rec_x.shape[0], rec_ptr.numel() - 1
+    if rec_x.shape != (n_rec, 3) or lig_x.dim() != 2 or lig_x.shape[1] != 3 or lig_ptr.numel() != B + 1:
+        raise KpdError(f'rec_x {tuple(rec_x.shape)}, lig_x {tuple(lig_x.shape)}, {B + 1} / {lig_ptr.numel()} offsets')
+    out = []
+    for name, t in masks:
+        if not (t.is_cuda and t.numel() == n_rec and t.dtype in (torch.bool, torch.uint8)):
+            raise KpdError(f'{name} must be a bool or uint8 GPU tensor with one entry per receptor atom')
+        out.append(t.contiguous().view(torch.uint8) if t.dtype == torch.bool else t.contiguous())
+    return rec_x, lig_x, n_rec, B, out
+
+
+def pocket_select(rec_x: torch.Tensor, rec_ptr: torch.Tensor, res_idx: torch.Tensor, probe: torch.Tensor, emit: torch.Tensor,
+                  lig_x: torch.Tensor, lig_ptr: torch.Tensor, max_rec: int, box_padding: float, pocket_cutoff: float,
+                  cap_rows: Optional[int] = None):
+    """Pocket atoms of a batch of whole receptors on the GPU (kpd_pocket_select; include/kpd.h has the contract).
+    rec_x [n_rec,3], res_idx [n_rec] int32, probe / emit [n_rec] bool or uint8, lig_x [n_lig,3], rec_ptr / lig_ptr [B+1]
+    int32, all on the GPU; box_padding < 0 or None: no box.  Returns a dict: rows (global atom numbers, ascending),
+    pocket_res, pocket_ptr (list of B + 1 offsets; the last is the size needed), status (list of B), in_box, pocket_mask
+    (bool [n_rec]).  One host read (offsets + status together)."""
+    rec_x, lig_x, n_rec, B, (probe, emit) = _pocket_args(rec_x, rec_ptr, lig_x, lig_ptr, (('probe', probe), ('emit', emit)))
+    if not (res_idx.is_cuda and res_idx.dtype == torch.int32 and res_idx.numel() == n_rec):
+        raise KpdError('res_idx must be an int32 GPU tensor with one entry per receptor atom')
+    dev = rec_x.device
+    cap = n_rec if cap_rows is None else int(cap_rows)
+    in_box = torch.empty(n_rec, dtype=torch.uint8, device=dev)
+    mask = torch.empty(n_rec, dtype=torch.uint8, device=dev)
+    rows = torch.empty(cap, dtype=torch.int32, device=dev)
+    pocket_res = torch.empty(cap, dtype=torch.int32, device=dev)
+    meta = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)         # pocket_ptr [B + 1], status [B]
+    scratch = torch.empty(int(lib().kpd_pocket_scratch_bytes(n_rec, B)), dtype=torch.uint8, device=dev)
+    check(lib().kpd_pocket_select(_ptr(rec_x), _ptr(rec_ptr), _ptr(res_idx.contiguous()), _ptr(probe), _ptr(emit), n_rec, int(max_rec),
+                                  _ptr(lig_x), _ptr(lig_ptr), int(lig_x.shape[0]), B, -1.0 if box_padding is None else float(box_padding),
+                                  float(pocket_cutoff), cap, _ptr(in_box), _ptr(mask), _ptr(rows), _ptr(pocket_res), _ptr(meta),
+                                  meta.data_ptr() + 4 * (B + 1), _ptr(scratch), _stream()))
+    host = meta.cpu().tolist()
+    ptr, status = host[:B + 1], host[B + 1:]
+    n = min(ptr[-1], cap)
+    return dict(rows=rows[:n], pocket_res=pocket_res[:n], pocket_ptr=ptr, status=status, in_box=in_box.bool(), pocket_mask=mask.bool())
+
+
+def interface_points(rec_x: torch.Tensor, rec_ptr: torch.Tensor, cand_mask: torch.Tensor, lig_x: torch.Tensor, lig_ptr: torch.Tensor,
+                     dist_thr: float, excl_thr: float, cap_cand: int = 2048, cap_points: Optional[int] = None):
+    """Interface points of a batch on the GPU (kpd_interface_points).  cand_mask [n_rec] bool or uint8: the candidate
+    receptor atoms.  cap_cand: candidate capacity per complex, cap_points: capacity for the points of all complexes
+    (default: B * min(cap_cand, 4096), which cannot overflow).  Returns a dict: points [n,3], ip_ptr (list of B + 1 offsets;
+    the last is the size needed), n_cand (list of B, exact also beyond cap_cand), status (list of B).  One host read."""
+    rec_x, lig_x, n_rec, B, (cand_mask,) = _pocket_args(rec_x, rec_ptr, lig_x, lig_ptr, (('cand_mask', cand_mask),))
+    dev = rec_x.device
+    cap_cand = int(cap_cand)
+    cap_pts = B * min(cap_cand, 4096) if cap_points is None else int(cap_points)
+    points = torch.empty(cap_pts, 3, dtype=torch.float32, device=dev)
+    meta = torch.empty(3 * B + 1, dtype=torch.int32, device=dev)         # ip_ptr [B + 1], n_cand [B], status [B]
+    scratch = torch.empty(int(lib().kpd_interface_points_scratch_bytes(n_rec, B, cap_cand)), dtype=torch.uint8, device=dev)
+    base = meta.data_ptr()
+    check(lib().kpd_interface_points(_ptr(rec_x), _ptr(rec_ptr), _ptr(cand_mask), n_rec, _ptr(lig_x), _ptr(lig_ptr), int(lig_x.shape[0]), B,
+                                     float(dist_thr), float(excl_thr), cap_cand, cap_pts, _ptr(points), base, base + 4 * (B + 1),
+                                     base + 4 * (2 * B + 1), _ptr(scratch), _stream()))
+    host = meta.cpu().tolist()
+    ptr = host[:B + 1]
+    return dict(points=points[:min(ptr[-1], cap_pts)], ip_ptr=ptr, n_cand=host[B + 1:2 * B + 1], status=host[2 * B + 1:])
 
 
 def xyz_emit(pos: torch.Tensor, feat: torch.Tensor, lig_ptr: torch.Tensor, elements):
