@@ -125,7 +125,11 @@ kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *batch, const float *t_
                             float *eps_h_dev, float *eps_x_dev, void *stream);
 /* Debug/test taps and switches.  Taps copy engine state to out_dev: "h_lig" / "h_kp" (node state, row stride 264), "x_lig" /
  * "x_kp", "z_lig" / "z_kp", "xnm<et>" / "xnc<et>" / "hnm<et>" / "hnc<et>" (segment-sum pieces of edge type et as the last layer
- * left them).  Switches (n_floats = 0, out_dev ignored but non-null): "layers=N" (run only the first N layers), "prune=0|1", and
+ * left them), "kp_table_ok" (n_floats = 1: 1.0 when layer 0 of the last forward took its keypoint projections from the per-class
+ * table, 0.0 when it ran per atom).  One-hot kp_h (fixed receptor encoder) is detected on the device at every forward: layer 0 then
+ * embeds and projects the B * rec_nf class rows instead of every keypoint, bit-identical to the per-atom path, which any other kp_h
+ * falls back to inside the same stream ("kp_table=0" forces it; fp32 mode, rec_nf != hidden_nf and B * rec_nf <= n_kp / 2 only).
+ * Switches (n_floats = 0, out_dev ignored but non-null): "layers=N" (run only the first N layers), "prune=0|1", "kp_table=0|1", and
  *   "gemm=f32"   exact fp32 MFMA in every GEMM -- the default and the contract path;
  *   "gemm=f16x2" EXPERIMENTAL, opt-in, never the default and never part of the benchmark's `value`: every fp32 product of the
  *                edge / projection / node-update GEMMs as three f16 MFMA products of hi / lo operand planes with fp32

@@ -97,6 +97,14 @@ struct kpd_egnn {
     float *z[2];
     int *meta, *ll_deg, *ll_off, *kl_off, *kl_pg;
     kpd_lig_graph lg;
+    // layer 0 of one-hot keypoint features (fixed receptor encoder): per-class table of the embedded rows and their projections
+    int kp_table = 1;                          // "kp_table=0" keeps every forward on the per-atom path
+    int tab_rows = 0;                          // rows of the table the workspace holds: min(cap_B * rec_nf, cap_kp / 2); 0: none
+    bool last_table = false;                   // the last forward enqueued the table path
+    int *rowmap = nullptr, *kp_ok = nullptr;   // node -> table row; device flag, the bits of 1.0f while every row of kp_h was one-hot
+    float *tab_in = nullptr;                   // [tab_rows][rec_nf]: row g * rec_nf + c = e_c
+    int *tab_bidx = nullptr;                   // [tab_rows]: its graph g
+    float *hT = nullptr, *PT = nullptr;        // the table's h and P, laid out as h[NT_KP] / P[NT_KP]
     EgnnWide *wide = nullptr;                  // hidden_nf > 256: the composed wide path (egnn_wide.hip) serves every entry point
 };
 
@@ -513,6 +521,9 @@ extern "C" kpd_status kpd_egnn_reserve(kpd_egnn *m, int32_t max_B, int32_t max_n
         tile_cap += tiles[et];
     }
     const int n[2] = {max_n_lig, max_n_kp};
+    // the class table serves batches with B * rec_nf <= n_kp / 2 (kpd_egnn_forward): never more rows than that
+    const int rec_nf = m->cfg.rec_nf;
+    const int tab_rows = m->rec_identity ? 0 : (int)std::min<long>((long)max_B * rec_nf, max_n_kp / 2);
     KPD_TRY(carve(m->ws, ARENA_TAIL, [&](Carve &W) {
         for (int nt = 0; nt < 2; ++nt) {
             W(m->h[nt], (size_t)(n[nt] + TM) * HS);          // + one tile: kernels touch whole tiles
@@ -529,7 +540,27 @@ extern "C" kpd_status kpd_egnn_reserve(kpd_egnn *m, int32_t max_B, int32_t max_n
         }
         // meta: [0..8] all active edge types, [16..24] the final layer's subset
         carve_lig_graph(W, m->meta, m->ll_deg, m->ll_off, m->kl_off, m->kl_pg, g, max_B, max_n_lig, max_n_kp);
+        if (tab_rows > 0) {
+            W(m->rowmap, max_n_kp);
+            W(m->kp_ok, 1);
+            W(m->tab_in, (size_t)tab_rows * rec_nf);
+            W(m->tab_bidx, tab_rows);
+            W(m->hT, (size_t)(tab_rows + TM) * HS);
+            W.rows(m->PT, (size_t)(tab_rows + TM) * NSLOT, HS, HW);
+        }
     }));
+    m->tab_rows = tab_rows;
+    m->last_table = false;
+    if (tab_rows > 0) {          // the table's input never changes: written once per workspace
+        std::vector<float> in((size_t)tab_rows * rec_nf, 0.0f);
+        std::vector<int> gi(tab_rows);
+        for (int r = 0; r < tab_rows; ++r) {
+            in[(size_t)r * rec_nf + r % rec_nf] = 1.0f;
+            gi[r] = r / rec_nf;
+        }
+        KPD_HIP(hipMemcpy(m->tab_in, in.data(), in.size() * 4, hipMemcpyHostToDevice));
+        KPD_HIP(hipMemcpy(m->tab_bidx, gi.data(), gi.size() * 4, hipMemcpyHostToDevice));
+    }
     for (int et = 0; et < 4; ++et) m->tiles_et_cap[et] = tiles[et];
     m->cap_B = max_B; m->cap_lig = max_n_lig; m->cap_kp = max_n_kp; m->cap_kk = max_n_kk;
     m->cap_ll = cap_ll; m->cap_kl = cap_kl; m->cap_maxlig = max_lig_pg; m->cap_maxkp = max_kp_pg;
@@ -573,6 +604,22 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
                          m->bidx[NT_LIG], m->h[NT_LIG], 0, st));
     KPD_TRY(launch_embed(bt->kp_h, bt->n_kp, c.rec_nf, m->re_W0, m->re_b0, 2 * c.rec_nf, m->re_W1t, m->re_b1, t_dev,
                          m->bidx[NT_KP], m->h[NT_KP], m->rec_identity ? 1 : 0, st));
+    // One-hot kp_h (the fixed receptor encoder's element encoding): the layer-0 keypoint state embed(kp_h[v], t[graph(v)]) and its
+    // eight projections take at most rec_nf values per complex.  The same two kernels run on the B * rec_nf class rows, and layer 0's
+    // edge kernel gathers keypoint rows from that table -- row for row the bits the per-atom launch gives.  Whether kp_h IS one-hot
+    // is decided on the device at every forward (k_kp_classify -> kp_ok); the per-atom launch stays in the stream behind it and
+    // returns at once when the flag is set.  Enqueued only where it can pay: fp32 mode, a learned embedding, at most half as many
+    // class rows as keypoints.
+    const int n_tab = bt->B * c.rec_nf;
+    const bool kp_tab = m->kp_table && m->gemm_mode == 0 && m->tab_rows > 0 && (long)bt->B * c.rec_nf <= bt->n_kp / 2;
+    m->last_table = kp_tab;
+    if (kp_tab) {
+        KPD_REQUIRE(n_tab <= m->tab_rows, KPD_ERR_CAPACITY, "internal: %d class rows, table of %d", n_tab, m->tab_rows);
+        KPD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->kp_ok), 0x3f800000, 1, st));
+        KPD_TRY(launch_kp_classify(bt->kp_h, bt->n_kp, c.rec_nf, m->bidx[NT_KP], m->rowmap, m->kp_ok, st));
+        KPD_TRY(launch_embed(m->tab_in, n_tab, c.rec_nf, m->re_W0, m->re_b0, 2 * c.rec_nf, m->re_W1t, m->re_b1, t_dev, m->tab_bidx,
+                             m->hT, 0, st));
+    }
 
     // tile capacity for this batch (host-known upper bound; the kernel exits early past the device-side total)
     const int e_kl_cap = bt->n_kp * (c.kl_k > 0 ? c.kl_k : std::min(bt->max_lig, 100));
@@ -622,7 +669,18 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
                 }
                 pp.tiles0 = cdiv(n[0], TM);
                 pp.gemm_mode = m->gemm_mode;
-                KPD_TRY(launch_proj_chain(pp, st));
+                if (kp_tab && li == 0) {
+                    // keypoints: the class rows beside the ligand rows, then the per-atom rows in a launch that skips itself while kp_ok is set
+                    ProjPair pk = pp;
+                    pk.n_slots[NT_LIG] = 0;
+                    pk.skip_if = m->kp_ok;
+                    ProjArgs &pa = pp.nt[NT_KP];
+                    pa.h = m->hT; pa.n = n_tab; pa.P = m->PT;
+                    KPD_TRY(launch_proj_chain(pp, st));
+                    KPD_TRY(launch_proj_chain(pk, st));
+                } else {
+                    KPD_TRY(launch_proj_chain(pp, st));
+                }
             }
         }
         EdgeArgs ea;
@@ -644,6 +702,7 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
             ea.hn_main[et] = m->hn_main[et]; ea.hn_cont[et] = m->hn_cont[et];
             ea.xn_main[et] = m->xn_main[et]; ea.xn_cont[et] = m->xn_cont[et];
         }
+        if (kp_tab && li == 0) { ea.PT = m->PT; ea.rowmap = m->rowmap; ea.kp_ok = m->kp_ok; }
         const bool prof = m->prof_on && m->prof_used + 2 <= m->prof_ev.size();
         if (prof) KPD_HIP(hipEventRecord(m->prof_ev[m->prof_used], st));
         KPD_TRY(launch_egnn_edge(ea, last ? tile_cap_last : tile_cap, st));
@@ -707,6 +766,17 @@ extern "C" kpd_status kpd_egnn_debug_state(kpd_egnn *m, const char *what, float 
              w[3] >= '0' && w[3] < '4') {          // segment-sum pieces of edge type w[3] as the last layer left them
         const int et = w[3] - '0';
         src = w[0] == 'x' ? (w[2] == 'm' ? m->xn_main[et] : m->xn_cont[et]) : (w[2] == 'm' ? m->hn_main[et] : m->hn_cont[et]);
+    }
+    else if (w == "kp_table_ok") {                 // 1.0 / 0.0: layer 0 of the last forward took its keypoint rows from the class table / per atom
+        KPD_REQUIRE(n_floats == 1, KPD_ERR_INVALID, "kp_table_ok is one value");
+        if (!m->last_table) {
+            KPD_HIP(hipMemsetAsync(out, 0, 4, st));
+            return KPD_OK;
+        }
+        src = reinterpret_cast<const float *>(m->kp_ok);
+    } else if (w.rfind("kp_table=", 0) == 0) {     // A/B switch of the class table (tests: bit-identical eps)
+        m->kp_table = atoi(w.c_str() + 9);
+        return KPD_OK;
     }
     else if (w.rfind("layers=", 0) == 0) {
         m->debug_layers = atoi(w.c_str() + 7);

@@ -44,6 +44,8 @@ __global__ __launch_bounds__(512, 1) void k_proj_ws(ProjWs qa) {
     v4f *W = reinterpret_cast<v4f *>(smem);
     float *s_wcol = smem + WS_W4 * 4, *s_bias = s_wcol + 128, *s_wrow = s_bias + 128;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    // the per-atom launch behind the keypoint class table (egnn.hip): nothing to do when the table serves the layer
+    if (qa.p.skip_if && *qa.p.skip_if) return;                // uniform over the grid
     const int which = (int)blockIdx.x >= qa.blocks0 ? 1 : 0;
     const ProjArgs &a = qa.p.nt[which];
     const int local = blockIdx.x - (which ? qa.blocks0 : 0);
@@ -301,6 +303,7 @@ kpd_status launch_proj_chain(const ProjPair &p, hipStream_t st) {
     }
     q.blocks0 = blocks[0];
     if (p.gemm_mode == 1) {
+        KPD_REQUIRE(!p.skip_if, KPD_ERR_INVALID, "projection launch: skip_if is served by the exact mode only");
         for (int nt = 0; nt < 2; ++nt)
             for (int s = 0; s < p.n_slots[nt]; ++s)
                 KPD_REQUIRE(p.nt[nt].chain_h[s], KPD_ERR_STATE, "projection slot %d has no f16 planes (f16x2 mode)", s);

@@ -12,6 +12,7 @@ constexpr int ET_LL = 0, ET_KL = 1, ET_LK = 2, ET_KK = 3;
 constexpr int NT_LIG = 0, NT_KP = 1;
 
 constexpr int EDGE_LDS_BYTES = TM * SA * 4 + (TM * 2 + TM + 3 * TM + TM + 3 * TM + 4 * HS + 8 + TM) * 4;   // ... misc[8], 64 column-256 values
+constexpr int EDGE_KPT_LDS_BYTES = EDGE_LDS_BYTES + 2 * TM * 4;     // k_egnn_edge_kpt: + the gather offsets of both sides (EdgeSmem::gsrc / gdst)
 // k_egnn_edge_h: two f16 planes of 64 x 280 halves (= the T tile's region), row data, two fp32 head rows, W2 row 256 as 2 x 2 x 272 halves
 constexpr int EDGE_H_LDS_BYTES = 64 * 280 * 2 * 2 + (TM * 2 + TM + 3 * TM + TM + 3 * TM + 2 * HS + 8) * 4 + 2 * 2 * 272 * 2;
 
@@ -34,6 +35,7 @@ struct ProjPair {
     int n_slots[2];
     int slots_per_block;            // consecutive slots one workgroup computes from its resident h registers
     int gemm_mode;                  // 0: exact fp32 MFMA, 1: f16x2 split (k_proj_ws_h)
+    const int *skip_if;             // device flag (or null): every workgroup returns at once when it reads non-zero (exact mode only)
 };
 
 struct EdgeArgs {
@@ -56,6 +58,11 @@ struct EdgeArgs {
     int gemm_mode;                  // 0: exact fp32 MFMA (contract path), 1: f16x2 split products (opt-in)
     int tile_rows;                  // edges per tile: 64 (TM)
     int split_slots;                // workgroup slots per XCD (set by the launcher): the tiles of an XCD's last round run one branch per work item; 0: off
+    // layer 0 with one-hot keypoint features (null otherwise): when *kp_ok is non-zero the keypoint-side rows are gathered from the
+    // per-class table PT [B * rec_nf][NSLOT][HS] at row rowmap[node] instead of P[NT_KP] at row node (k_egnn_edge_kpt)
+    const float *PT;
+    const int *rowmap;
+    const int *kp_ok;
 };
 
 // Forward edge kernel of the EGNN trainer (k_egnn_edge_train): the inference kernel's program on the current weights, keeping what the
@@ -158,6 +165,9 @@ kpd_status launch_egnn_meta(const int *counts, int e_kk, int active_mask, int ac
                             int update_kp, int *meta, float *z_lig, float *z_kp, hipStream_t st, int tile_rows = TM);
 kpd_status launch_embed(const float *in, int n, int fin, const float *W0, const float *b0, int hid, const float *W1t,
                         const float *b1, const float *t, const int *bidx, float *out, int identity, hipStream_t st);
+// one-hot test of the keypoint features: rowmap[v] = bidx[v] * fin + c for a row that is exactly e_c (one element with the bits of
+// 1.0f, all others +0.0f); any other row stores 0 to *ok (set by the caller beforehand, on the stream)
+kpd_status launch_kp_classify(const float *kp_h, int n, int fin, const int *bidx, int *rowmap, int *ok, hipStream_t st);
 kpd_status launch_decode(const float *h, const float *x, const float *x0, int n, int atom_nf, int hid, const float *W0,
                          const float *b0, const float *W1, const float *b1, float *eps_h, float *eps_x, hipStream_t st);
 kpd_status launch_egnn_edge(const EdgeArgs &a, int tile_cap, hipStream_t st);

@@ -34,6 +34,25 @@ __global__ void k_node_graph_index(const int *__restrict__ ptr, int B, int n, in
     bidx[i] = lo;
 }
 
+// Layer 0 of the fixed receptor encoder: kp_h is a one-hot element encoding, so the embedded keypoint rows and their projections take
+// at most fin distinct values per complex.  rowmap[v] = row of node v in the per-class table (graph * fin + class); a row that is not
+// exactly one-hot (compared by bits: one 1.0f, the rest +0.0f, so that the class row e_c is the same input bit for bit) clears *ok and
+// the forward runs the per-atom path (egnn.hip).
+__global__ void k_kp_classify(const float *__restrict__ kp_h, int n, int fin, const int *__restrict__ bidx, int *__restrict__ rowmap,
+                              int *__restrict__ ok) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    const unsigned *row = reinterpret_cast<const unsigned *>(kp_h) + (size_t)v * fin;
+    int ones = 0, other = 0, c = 0;
+    for (int k = 0; k < fin; ++k) {
+        const unsigned u = row[k];
+        if (u == 0x3f800000u) { ++ones; c = k; }
+        else if (u != 0u) other = 1;
+    }
+    rowmap[v] = bidx[v] * fin + c;                       // always inside the table
+    if (ones != 1 || other) *ok = 0;
+}
+
 // meta layout: [0..3] E per etype (ll, kl, lk, kk), [4..8] first tile of each etype (+total); the same nine
 // entries at [16..24] for the final layer's edge-type subset (active_last).
 // z: per-graph message normaliser (dynamics.py:277-285) -- always over ALL active edge types: the pruned
@@ -180,11 +199,13 @@ constexpr unsigned PROW_B = NSLOT * HS * 4;       // bytes of one node's row of 
 struct EdgeSmem {
     float *A;
     int *src, *dst;     // byte offsets of the endpoints' P rows (node * PROW_B)
+    int *gsrc, *gdst;   // byte offsets the gathers read: src / dst themselves, or (k_egnn_edge_kpt) the rows of the keypoint class table
     float *d, *xd, *att, *mx;
     float *wv;          // [4][HS]: soft-attention row (+bias at ATT_BIAS_AT), coordinate head row, W2[256, :] of edge_mlp / coord_mlp
     int *misc;          // [0] first run continues the previous tile, [2..3] segment-end mask, [4..5] head mask
 };
 
+template <bool KPT = false>
 __device__ __forceinline__ EdgeSmem edge_smem(float *smem) {
     EdgeSmem s;
     s.A = smem;
@@ -196,6 +217,8 @@ __device__ __forceinline__ EdgeSmem edge_smem(float *smem) {
     s.mx = s.att + TM;
     s.wv = s.mx + 3 * TM;
     s.misc = reinterpret_cast<int *>(s.wv + 4 * HS);
+    s.gsrc = KPT ? s.misc + 8 + TM : s.src;      // (EDGE_KPT_LDS_BYTES)
+    s.gdst = KPT ? s.gsrc + TM : s.dst;
     return s;
 }
 
@@ -215,32 +238,36 @@ template <int NW>
 __device__ __forceinline__ void edge_gather_issue(EdgeGather<NW> &g, const EdgeSmem &s, const float *__restrict__ Ps,
                                                   const float *__restrict__ Pd, int wave, int lane) {
     constexpr int RPW = TM / NW;
-    // s.src / s.dst hold the P rows' 32-bit byte offsets (node * PROW_B, premultiplied in phase 0; P stays far below 4 GB):
+    // s.gsrc / s.gdst hold the P rows' 32-bit byte offsets (node * PROW_B, premultiplied in phase 0; P stays far below 4 GB):
     // one full-rate add per row and side here instead of a quarter-rate integer multiply-add.  One 1-KiB row segment per
     // wave instruction, all rows in flight.
     const char *ps = reinterpret_cast<const char *>(Ps), *pd = reinterpret_cast<const char *>(Pd);
 #pragma unroll
     for (int rr = 0; rr < RPW; ++rr) {
         const int r = wave * RPW + rr;
-        g.ps[rr] = *reinterpret_cast<const f32x4 *>(ps + ((unsigned)s.src[r] + 16u * lane));
-        g.pd[rr] = *reinterpret_cast<const f32x4 *>(pd + ((unsigned)s.dst[r] + 16u * lane));
+        g.ps[rr] = *reinterpret_cast<const f32x4 *>(ps + ((unsigned)s.gsrc[r] + 16u * lane));
+        g.pd[rr] = *reinterpret_cast<const f32x4 *>(pd + ((unsigned)s.gdst[r] + 16u * lane));
     }
     if (lane < 4 * RPW && (lane & 3) < 2) {
         const int r = wave * RPW + (lane >> 2), c = lane & 3;
-        g.tps = *reinterpret_cast<const f32x4 *>(ps + ((unsigned)s.src[r] + 16u * (64 + c)));
-        g.tpd = *reinterpret_cast<const f32x4 *>(pd + ((unsigned)s.dst[r] + 16u * (64 + c)));
+        g.tps = *reinterpret_cast<const f32x4 *>(ps + ((unsigned)s.gsrc[r] + 16u * (64 + c)));
+        g.tpd = *reinterpret_cast<const f32x4 *>(pd + ((unsigned)s.gdst[r] + 16u * (64 + c)));
     }
 }
 
 // The same gathers issued before the tile's LDS row data exists: lane (l & (RPW - 1)) of every wave loads the endpoints of row
 // wave * RPW + (l & (RPW - 1)) itself, the row's (wave-uniform) offsets are read out of those lanes (v_readlane) and the loads go
 // out while wave 0 is still in its geometry chain -- the gather latency then overlaps phase 0 and its barrier.
+// maps / mapd (k_egnn_edge_kpt; null: the node index itself): node -> row of Ps / Pd.
 template <int NW>
 __device__ __forceinline__ void edge_gather_issue_early(EdgeGather<NW> &g, const int *__restrict__ esrc, const int *__restrict__ edst, int e0,
-                                                        int ne, const float *__restrict__ Ps, const float *__restrict__ Pd, int wave, int lane) {
+                                                        int ne, const float *__restrict__ Ps, const float *__restrict__ Pd, int wave, int lane,
+                                                        const int *__restrict__ maps = nullptr, const int *__restrict__ mapd = nullptr) {
     constexpr int RPW = TM / NW;
     const int rl = min(wave * RPW + (lane & (RPW - 1)), ne - 1);
-    const int iu = esrc[e0 + rl], iv = edst[e0 + rl];
+    int iu = esrc[e0 + rl], iv = edst[e0 + rl];
+    if (maps) iu = maps[iu];                      // (wave-uniform)
+    if (mapd) iv = mapd[iv];
     const char *ps = reinterpret_cast<const char *>(Ps), *pd = reinterpret_cast<const char *>(Pd);
 #pragma unroll
     for (int rr = 0; rr < RPW; ++rr) {
@@ -324,11 +351,12 @@ __device__ __forceinline__ void store_T_silu_w(float *T, const f32x16 (&acc)[2][
     if ((tid % TPR) == 0) T[(tid / TPR) * SA + 256] = PRE ? silu_pre(ex) : silu(ex + b[256]);
 }
 
-template <int NW>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge(EdgeArgs a) {
+// KPT: the layer-0 form behind k_egnn_edge_kpt (keypoint-side rows through the class table when *a.kp_ok says so)
+template <int NW, bool KPT>
+__device__ __forceinline__ void egnn_edge_tile(const EdgeArgs &a) {
     constexpr int TPR = NW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const EdgeSmem s = edge_smem(smem);
+    const EdgeSmem s = edge_smem<KPT>(smem);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     // tile decode (XCD-aware: consecutive tiles -- neighbouring edges of one complex, which
     // share P rows -- go to the same XCD / L2)
@@ -364,10 +392,21 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge(EdgeArgs
 
     const float *Ps = a.P[snt] + (size_t)a.src_slot[et] * HS;
     const float *Pd = a.P[dnt] + (size_t)a.dst_slot[et] * HS;
+    [[maybe_unused]] const int *maps = nullptr, *mapd = nullptr;
+    if constexpr (KPT) {
+        if (*a.kp_ok) {                               // one branch, uniform over the launch: table rows or per-atom rows
+            if (snt == NT_KP) { maps = a.rowmap; Ps = a.PT + (size_t)a.src_slot[et] * HS; }
+            if (dnt == NT_KP) { mapd = a.rowmap; Pd = a.PT + (size_t)a.dst_slot[et] * HS; }
+        }
+    }
     // the feature branch's P rows start travelling before the geometry chain and the first barrier (-1.1 % on the kernel, same-call
     // A/B: 0.859 vs 0.869 ms)
     EdgeGather<NW> ge;
-    if (bsel & 1) edge_gather_issue_early<NW>(ge, esrc, edst, e0, ne, Ps, Pd, wave, lane);
+    if constexpr (KPT) {
+        if (bsel & 1) edge_gather_issue_early<NW>(ge, esrc, edst, e0, ne, Ps, Pd, wave, lane, maps, mapd);
+    } else {
+        if (bsel & 1) edge_gather_issue_early<NW>(ge, esrc, edst, e0, ne, Ps, Pd, wave, lane);
+    }
     __builtin_amdgcn_sched_barrier(0);
     // phase 0: edge endpoints and geometry (dynamics.py:160-169, 209-217); head weights to LDS
     if (tid < TM) {
@@ -375,6 +414,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge(EdgeArgs
         const int u = esrc[e], v = edst[e];
         s.src[tid] = (int)((unsigned)u * PROW_B);        // byte offsets of the nodes' P rows
         s.dst[tid] = (int)((unsigned)v * PROW_B);
+        if constexpr (KPT) {                             // s.dst stays the node: the segmented sums divide it back into the node index
+            s.gsrc[tid] = (int)((unsigned)(maps ? maps[u] : u) * PROW_B);
+            s.gdst[tid] = (int)((unsigned)(mapd ? mapd[v] : v) * PROW_B);
+        }
         const float *xs = a.x[snt] + (size_t)u * 3, *xd = a.x[dnt] + (size_t)v * 3;
         const float dx = xs[0] - xd[0], dy = xs[1] - xd[1], dz = xs[2] - xd[2];
         const float d = sqrtf(dx * dx + dy * dy + dz * dz);
@@ -544,6 +587,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge(EdgeArgs
             if (bsel & 1) oh[256] = vh;
         }
     }
+}
+
+template <int NW>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_egnn_edge(EdgeArgs a) {
+    egnn_edge_tile<NW, false>(a);
+}
+
+// layer 0 when the keypoint projections may come from the per-class table (a.PT / a.rowmap / a.kp_ok set)
+__global__ __launch_bounds__(256, 2) void k_egnn_edge_kpt(EdgeArgs a) {
+    egnn_edge_tile<4, true>(a);
 }
 
 
@@ -1298,6 +1351,8 @@ __device__ __forceinline__ EdgeSmem edge_smem_h(float *smem) {
     s.mx = s.att + TM;
     s.wv = s.mx + 3 * TM;
     s.misc = reinterpret_cast<int *>(s.wv + 2 * HS);
+    s.gsrc = s.src;
+    s.gdst = s.dst;
     return s;
 }
 
@@ -2021,6 +2076,13 @@ kpd_status launch_embed(const float *in, int n, int fin, const float *W0, const 
     return KPD_OK;
 }
 
+kpd_status launch_kp_classify(const float *kp_h, int n, int fin, const int *bidx, int *rowmap, int *ok, hipStream_t st) {
+    if (n == 0) return KPD_OK;
+    hipLaunchKernelGGL(k_kp_classify, dim3(cdiv(n, 256)), dim3(256), 0, st, kp_h, n, fin, bidx, rowmap, ok);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
 kpd_status launch_decode(const float *h, const float *x, const float *x0, int n, int atom_nf, int hid, const float *W0,
                          const float *b0, const float *W1, const float *b1, float *eps_h, float *eps_x,
                          hipStream_t st) {
@@ -2048,10 +2110,17 @@ kpd_status launch_egnn_edge(const EdgeArgs &a, int tile_cap, hipStream_t st) {
         KPD_LAUNCH_CHECK();
         return KPD_OK;
     }
-    KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_egnn_edge<4>), EDGE_LDS_BYTES));
     // the tail of a launch split by branch (k_egnn_edge): two workgroup slots per CU, an eighth of them per XCD
     EdgeArgs b = a;
     b.split_slots = 2 * cu_count() / 8;
+    if (a.kp_ok) {
+        KPD_REQUIRE(a.PT && a.rowmap, KPD_ERR_INVALID, "edge launch: keypoint class table without its rows or row map");
+        KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_egnn_edge_kpt), EDGE_KPT_LDS_BYTES));
+        hipLaunchKernelGGL(k_egnn_edge_kpt, dim3(8 * (cdiv(tile_cap, 8) + b.split_slots / 2)), dim3(256), EDGE_KPT_LDS_BYTES, st, b);
+        KPD_LAUNCH_CHECK();
+        return KPD_OK;
+    }
+    KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_egnn_edge<4>), EDGE_LDS_BYTES));
     hipLaunchKernelGGL(k_egnn_edge<4>, dim3(8 * (cdiv(tile_cap, 8) + b.split_slots / 2)), dim3(256), EDGE_LDS_BYTES, st, b);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
