@@ -506,6 +506,50 @@ kpd_status kpd_sample_update(int32_t B, const int32_t *lig_ptr, const int32_t *k
 kpd_status kpd_step_coefficients(const float *gamma, int32_t n_gamma, const float *s, const float *t,
                                  int32_t B, float *coef, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Inpainting: the reverse step around fixed atoms (RePaint-style replacement conditioning; no upstream counterpart, this
+ * comment is the specification).  Some ligand atoms are given (a scaffold, a hinge binder, a warhead); they are held at
+ * their known positions and features while the other atoms are generated around them.
+ *
+ * The sampler's state lives in a ligand-COM-free frame, and the keypoints translate rigidly with it.  The input (receptor)
+ * frame is therefore recovered at every step from the keypoints alone: with kp_com0 [B,3] = per-complex mean of the keypoint
+ * positions in the input frame and m_b = the mean of complex b's rows of kp_x on entry to the step (lane-strided partial sums
+ * and a butterfly over one wavefront: a fixed order that depends on nothing but that complex), a position X given in the input
+ * frame sits at k0 = (X - kp_com0_b) + m_b in the state frame -- evaluated in that order, the first difference removes the
+ * large input-frame magnitudes.  Nothing is accumulated from step to step, so the frame cannot drift and a captured step replays.
+ *
+ * One step t -> s for complex b (coef6 [B,6] = {alpha_t|s, var, sigma_step, alpha_s, sigma_s, sigma_t|s}):
+ *   1. candidate for every atom, the arithmetic of kpd_sample_update:  u = z_t / alpha_t|s - var eps + sigma_step n   (x and h)
+ *   2. frame: m_b, k0 as above
+ *   3. noised known part:  k = alpha_s k0 + sigma_s n',  kh = alpha_s Hn + sigma_s n'_h   (n', n'_h: a second pair of draws)
+ *   4. merge:  z_s = fixed ? (k, kh) : u
+ *   5. COM removal: the mean of the merged ligand positions (staged in LDS, summed in a fixed order) is subtracted from the
+ *      ligand and from the keypoints, as kpd_sample_update does.
+ * kpd_sample_update, kpd_sample_update_inpaint and kpd_sample_renoise are instances of one device function, so a complex with
+ * no fixed atom leaves kpd_sample_update_inpaint with exactly the bits kpd_sample_update gives, and a complex's result is
+ * bitwise independent of the other complexes in the batch.
+ *   fixed [n_lig] bytes (1 = given); known_x [n_lig,3] input frame, known_h [n_lig,atom_nf] already divided by the feature
+ *   normalisation constant, known_noise_x / known_noise_h like noise_x / noise_h: all four are read on fixed rows only.
+ * One workgroup per complex, max_lig <= 4096 (positions staged in LDS), larger ligands and keypoint sets than the workgroup
+ * are strided over; no atomics, no host synchronisation, counts come from device memory (capturable).
+ *
+ * kpd_sample_renoise moves the state back from s to t between two repetitions of a resampled step:
+ *   z_t = alpha_t|s z_s + sigma_t|s n'' for x and h, then the same COM removal (reads columns 0 and 5 of coef6).
+ * kpd_inpaint_coefficients fills coef6; its first three columns are the bits of kpd_step_coefficients.
+ * ------------------------------------------------------------------------------------- */
+kpd_status kpd_inpaint_coefficients(const float *gamma, int32_t n_gamma, const float *s, const float *t,
+                                    int32_t B, float *coef6, void *stream);
+kpd_status kpd_sample_update_inpaint(int32_t B, const int32_t *lig_ptr, const int32_t *kp_ptr,
+                                     int32_t atom_nf, float *lig_x, float *lig_h, float *kp_x,
+                                     const float *eps_x, const float *eps_h,
+                                     const float *noise_x, const float *noise_h, const float *coef6,
+                                     const uint8_t *fixed, const float *known_x, const float *known_h,
+                                     const float *kp_com0, const float *known_noise_x, const float *known_noise_h,
+                                     int32_t max_lig, void *stream);
+kpd_status kpd_sample_renoise(int32_t B, const int32_t *lig_ptr, const int32_t *kp_ptr, int32_t atom_nf,
+                              float *lig_x, float *lig_h, float *kp_x, const float *noise_x, const float *noise_h,
+                              const float *coef6, int32_t max_lig, void *stream);
+
 /* Sharding-invariant N(0,1) noise for the ligand rows of a batch (opt-in replacement of the global torch.randn draws of
  * ligand_diffuser.py:367, 530-531): out [n_nodes, width] with rows of complex b =
  * [node_ptr[b], node_ptr[b+1]).  Philox4x32-10 keyed by (seed, complex_id[b]), counter (element, step, tag): the values do

@@ -6,26 +6,71 @@
 
 namespace kpd {
 
-// coef[b] = {alpha_t_given_s, var_terms, sigma}
-__global__ __launch_bounds__(256) void k_sample_update(const int *__restrict__ lig_ptr, const int *__restrict__ kp_ptr,
-                                                       int atom_nf, float *__restrict__ lig_x, float *__restrict__ lig_h,
-                                                       float *__restrict__ kp_x, const float *__restrict__ eps_x,
-                                                       const float *__restrict__ eps_h, const float *__restrict__ noise_x,
-                                                       const float *__restrict__ noise_h, const float *__restrict__ coef) {
-    extern __shared__ float sx[];          // [3 * n_lig of this complex]
-    __shared__ float s_com[3];
+// The three state updates of the sampler share this body, so the candidate expression and the COM removal are the same
+// instructions in every one of them (FMA contraction cannot differ) and a complex without fixed atoms leaves the inpainting
+// kernel with the bits of the plain one.  One workgroup per complex; sx [3 * n_lig of this complex] stages the new positions.
+enum { UPD_PLAIN = 0, UPD_INPAINT = 1, UPD_RENOISE = 2 };
+
+struct InpaintArgs {                        // UPD_INPAINT only (include/kpd.h has the algorithm)
+    const unsigned char *fixed;             // [n_lig] 1 = this atom is given
+    const float *known_x, *known_h;         // [n_lig,3] input frame, [n_lig,atom_nf] normalised; read on fixed rows only
+    const float *kp_com0;                   // [B,3] keypoint mean in the input frame
+    const float *known_noise_x, *known_noise_h;
+};
+
+// c = the coefficient row of this complex: {alpha_t|s, var, sigma_step} and, beyond UPD_PLAIN, {alpha_s, sigma_s, sigma_t|s}
+template <int MODE>
+__device__ __forceinline__ void update_and_center(const int *__restrict__ lig_ptr, const int *__restrict__ kp_ptr, int atom_nf,
+                                                  float *__restrict__ lig_x, float *__restrict__ lig_h, float *__restrict__ kp_x,
+                                                  const float *__restrict__ eps_x, const float *__restrict__ eps_h,
+                                                  const float *__restrict__ noise_x, const float *__restrict__ noise_h,
+                                                  const float *__restrict__ c, const InpaintArgs &ia, float *sx, float *s_com,
+                                                  float *s_frame) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const int llo = lig_ptr[b], nl = lig_ptr[b + 1] - llo;
     const int klo = kp_ptr[b], nk = kp_ptr[b + 1] - klo;
-    const float alpha = coef[3 * b], var = coef[3 * b + 1], sigma = coef[3 * b + 2];
+    const float alpha = c[0], var = c[1], sigma = c[2];
+
+    if constexpr (MODE == UPD_INPAINT) {
+        // frame: mean of this complex's keypoint rows as they are on entry.  Wave w < 3 sums component w: lane-strided partial
+        // sums, then a butterfly over the 64 lanes -- a fixed order that depends on nothing but this complex.
+        const int w = tid >> 6, lane = tid & 63;
+        if (w < 3) {
+            float p = 0.0f;
+            for (int j = lane; j < nk; j += 64) p += kp_x[(size_t)(klo + j) * 3 + w];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) p += __shfl_xor(p, off, 64);
+            if (lane == 0) s_frame[w] = p / (float)nk;
+        }
+        __syncthreads();
+    }
 
     for (int i = tid; i < nl * 3; i += blockDim.x) {
         const size_t g = (size_t)llo * 3 + i;
-        sx[i] = lig_x[g] / alpha - var * eps_x[g] + sigma * noise_x[g];
+        if constexpr (MODE == UPD_RENOISE) {
+            sx[i] = alpha * lig_x[g] + c[5] * noise_x[g];
+        } else {
+            float u = lig_x[g] / alpha - var * eps_x[g] + sigma * noise_x[g];
+            if constexpr (MODE == UPD_INPAINT) {
+                if (ia.fixed[llo + i / 3]) {
+                    const float k0 = (ia.known_x[g] - ia.kp_com0[3 * b + i % 3]) + s_frame[i % 3];   // this order: see kpd.h
+                    u = c[3] * k0 + c[4] * ia.known_noise_x[g];
+                }
+            }
+            sx[i] = u;
+        }
     }
     for (int i = tid; i < nl * atom_nf; i += blockDim.x) {
         const size_t g = (size_t)llo * atom_nf + i;
-        lig_h[g] = lig_h[g] / alpha - var * eps_h[g] + sigma * noise_h[g];
+        if constexpr (MODE == UPD_RENOISE) {
+            lig_h[g] = alpha * lig_h[g] + c[5] * noise_h[g];
+        } else {
+            float u = lig_h[g] / alpha - var * eps_h[g] + sigma * noise_h[g];
+            if constexpr (MODE == UPD_INPAINT) {
+                if (ia.fixed[llo + i / atom_nf]) u = c[3] * ia.known_h[g] + c[4] * ia.known_noise_h[g];
+            }
+            lig_h[g] = u;
+        }
     }
     __syncthreads();
     if (tid < 3) {
@@ -38,25 +83,74 @@ __global__ __launch_bounds__(256) void k_sample_update(const int *__restrict__ l
     for (int i = tid; i < nk * 3; i += blockDim.x) kp_x[(size_t)klo * 3 + i] -= s_com[i % 3];
 }
 
+// coef[b] = {alpha_t_given_s, var_terms, sigma}
+__global__ __launch_bounds__(256) void k_sample_update(const int *__restrict__ lig_ptr, const int *__restrict__ kp_ptr,
+                                                       int atom_nf, float *__restrict__ lig_x, float *__restrict__ lig_h,
+                                                       float *__restrict__ kp_x, const float *__restrict__ eps_x,
+                                                       const float *__restrict__ eps_h, const float *__restrict__ noise_x,
+                                                       const float *__restrict__ noise_h, const float *__restrict__ coef) {
+    extern __shared__ float sx[];          // [3 * n_lig of this complex]
+    __shared__ float s_com[3];
+    update_and_center<UPD_PLAIN>(lig_ptr, kp_ptr, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h,
+                                 coef + 3 * blockIdx.x, InpaintArgs{}, sx, s_com, nullptr);
+}
+
+// Replacement conditioning: fixed atoms take the noised known part instead of the candidate.  coef6[b] = {alpha_t|s, var_terms,
+// sigma, alpha_s, sigma_s, sigma_t|s} (k_inpaint_coef).
+__global__ __launch_bounds__(256) void k_sample_update_inpaint(const int *__restrict__ lig_ptr, const int *__restrict__ kp_ptr,
+                                                               int atom_nf, float *__restrict__ lig_x, float *__restrict__ lig_h,
+                                                               float *__restrict__ kp_x, const float *__restrict__ eps_x,
+                                                               const float *__restrict__ eps_h, const float *__restrict__ noise_x,
+                                                               const float *__restrict__ noise_h, const float *__restrict__ coef6,
+                                                               InpaintArgs ia) {
+    extern __shared__ float sx[];
+    __shared__ float s_com[3], s_frame[3];
+    update_and_center<UPD_INPAINT>(lig_ptr, kp_ptr, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h,
+                                   coef6 + 6 * blockIdx.x, ia, sx, s_com, s_frame);
+}
+
+// Back from s to t between two repetitions of a resampled step: z_t = alpha_t|s z_s + sigma_t|s n, then the COM removal.
+__global__ __launch_bounds__(256) void k_sample_renoise(const int *__restrict__ lig_ptr, const int *__restrict__ kp_ptr, int atom_nf,
+                                                        float *__restrict__ lig_x, float *__restrict__ lig_h, float *__restrict__ kp_x,
+                                                        const float *__restrict__ noise_x, const float *__restrict__ noise_h,
+                                                        const float *__restrict__ coef6) {
+    extern __shared__ float sx[];
+    __shared__ float s_com[3];
+    update_and_center<UPD_RENOISE>(lig_ptr, kp_ptr, atom_nf, lig_x, lig_h, kp_x, nullptr, nullptr, noise_x, noise_h,
+                                   coef6 + 6 * blockIdx.x, InpaintArgs{}, sx, s_com, nullptr);
+}
+
 // Per-complex coefficients of one reverse step from the noise-schedule table (ligand_diffuser.py:505-526, 654-690):
 // gamma lookup at round(t T), sigma^2_t|s = -expm1(softplus(g_s) - softplus(g_t)), alpha_t|s = exp((softplus(g_s) -
 // softplus(g_t)) / 2), sigma = sqrt(sigmoid(gamma)).  Replaces ~30 elementwise launches on B-element tensors.
 __device__ __forceinline__ float softplusf_(float x) { return x > 20.0f ? x : log1pf(expf(x)); }   // torch default threshold
 
-__global__ void k_step_coef(const float *__restrict__ gamma, int n_gamma, const float *__restrict__ s,
-                            const float *__restrict__ t, int B, float *__restrict__ coef) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
+// {alpha_t|s, var_terms, sigma_step, alpha_s, sigma_s, sigma_t|s}: one body for both coefficient kernels, so the first three are the same bits
+__device__ __forceinline__ void step_coef_row(const float *__restrict__ gamma, int n_gamma, float s, float t, float (&o)[6]) {
     const float T = (float)(n_gamma - 1);
-    const int is = min(max((int)rintf(s[b] * T), 0), n_gamma - 1), it = min(max((int)rintf(t[b] * T), 0), n_gamma - 1);
+    const int is = min(max((int)rintf(s * T), 0), n_gamma - 1), it = min(max((int)rintf(t * T), 0), n_gamma - 1);
     const float gs = gamma[is], gt = gamma[it];
     const float dsp = softplusf_(gs) - softplusf_(gt);
     const float sigma2_ts = -expm1f(dsp);
     const float alpha_ts = expf(0.5f * dsp);
     const float sig_s = sqrtf(1.0f / (1.0f + expf(-gs))), sig_t = sqrtf(1.0f / (1.0f + expf(-gt)));
-    coef[3 * b] = alpha_ts;
-    coef[3 * b + 1] = sigma2_ts / alpha_ts / sig_t;
-    coef[3 * b + 2] = sqrtf(sigma2_ts) * sig_s / sig_t;
+    o[0] = alpha_ts;
+    o[1] = sigma2_ts / alpha_ts / sig_t;
+    o[2] = sqrtf(sigma2_ts) * sig_s / sig_t;
+    o[3] = sqrtf(1.0f / (1.0f + expf(gs)));            // alpha_s = sqrt(sigmoid(-gamma_s))
+    o[4] = sig_s;
+    o[5] = sqrtf(sigma2_ts);
+}
+
+template <int W>
+__global__ void k_step_coef(const float *__restrict__ gamma, int n_gamma, const float *__restrict__ s,
+                            const float *__restrict__ t, int B, float *__restrict__ coef) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float o[6];
+    step_coef_row(gamma, n_gamma, s[b], t[b], o);
+#pragma unroll
+    for (int i = 0; i < W; ++i) coef[W * b + i] = o[i];
 }
 
 // ---- per-complex counter-based noise ------------------------------------------------------------------------
@@ -111,7 +205,7 @@ extern "C" kpd_status kpd_step_coefficients(const float *gamma, int32_t n_gamma,
                                             float *coef, void *stream) {
     KPD_REQUIRE(gamma && s && t && coef, KPD_ERR_INVALID, "null argument");
     KPD_REQUIRE(n_gamma >= 2 && B >= 1, KPD_ERR_INVALID, "n_gamma=%d B=%d", n_gamma, B);
-    hipLaunchKernelGGL(k_step_coef, dim3(cdiv(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), gamma, n_gamma, s, t, B,
+    hipLaunchKernelGGL(k_step_coef<3>, dim3(cdiv(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), gamma, n_gamma, s, t, B,
                        coef);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
@@ -127,6 +221,47 @@ extern "C" kpd_status kpd_sample_update(int32_t B, const int32_t *lig_ptr, const
     hipLaunchKernelGGL(k_sample_update, dim3(B), dim3(256), (size_t)max_lig * 3 * sizeof(float),
                        static_cast<hipStream_t>(stream), lig_ptr, kp_ptr, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h,
                        noise_x, noise_h, coef);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+extern "C" kpd_status kpd_inpaint_coefficients(const float *gamma, int32_t n_gamma, const float *s, const float *t, int32_t B,
+                                               float *coef, void *stream) {
+    KPD_REQUIRE(gamma && s && t && coef, KPD_ERR_INVALID, "null argument");
+    KPD_REQUIRE(n_gamma >= 2 && B >= 1, KPD_ERR_INVALID, "n_gamma=%d B=%d", n_gamma, B);
+    hipLaunchKernelGGL(k_step_coef<6>, dim3(cdiv(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), gamma, n_gamma, s, t, B,
+                       coef);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+extern "C" kpd_status kpd_sample_update_inpaint(int32_t B, const int32_t *lig_ptr, const int32_t *kp_ptr, int32_t atom_nf,
+                                                float *lig_x, float *lig_h, float *kp_x, const float *eps_x, const float *eps_h,
+                                                const float *noise_x, const float *noise_h, const float *coef6,
+                                                const uint8_t *fixed, const float *known_x, const float *known_h,
+                                                const float *kp_com0, const float *known_noise_x, const float *known_noise_h,
+                                                int32_t max_lig, void *stream) {
+    KPD_REQUIRE(lig_ptr && kp_ptr && lig_x && lig_h && kp_x && eps_x && eps_h && noise_x && noise_h && coef6 && fixed && known_x &&
+                    known_h && kp_com0 && known_noise_x && known_noise_h,
+                KPD_ERR_INVALID, "null argument");
+    KPD_REQUIRE(B >= 1 && atom_nf >= 1 && max_lig >= 1 && max_lig <= 4096, KPD_ERR_INVALID, "B=%d atom_nf=%d max_lig=%d", B, atom_nf,
+                max_lig);
+    const InpaintArgs ia{fixed, known_x, known_h, kp_com0, known_noise_x, known_noise_h};
+    hipLaunchKernelGGL(k_sample_update_inpaint, dim3(B), dim3(256), (size_t)max_lig * 3 * sizeof(float),
+                       static_cast<hipStream_t>(stream), lig_ptr, kp_ptr, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h,
+                       coef6, ia);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+extern "C" kpd_status kpd_sample_renoise(int32_t B, const int32_t *lig_ptr, const int32_t *kp_ptr, int32_t atom_nf, float *lig_x,
+                                         float *lig_h, float *kp_x, const float *noise_x, const float *noise_h, const float *coef6,
+                                         int32_t max_lig, void *stream) {
+    KPD_REQUIRE(lig_ptr && kp_ptr && lig_x && lig_h && kp_x && noise_x && noise_h && coef6, KPD_ERR_INVALID, "null argument");
+    KPD_REQUIRE(B >= 1 && atom_nf >= 1 && max_lig >= 1 && max_lig <= 4096, KPD_ERR_INVALID, "B=%d atom_nf=%d max_lig=%d", B, atom_nf,
+                max_lig);
+    hipLaunchKernelGGL(k_sample_renoise, dim3(B), dim3(256), (size_t)max_lig * 3 * sizeof(float), static_cast<hipStream_t>(stream),
+                       lig_ptr, kp_ptr, atom_nf, lig_x, lig_h, kp_x, noise_x, noise_h, coef6);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
 }

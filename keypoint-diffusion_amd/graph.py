@@ -300,10 +300,37 @@ def unbatch(g: HeteroBatch) -> List[HeteroBatch]:
     return out
 
 
-def readout_nodes(g: HeteroBatch, feat: str, op: str = 'mean', ntype: str = None) -> torch.Tensor:
-    """dgl.readout_nodes: per-complex reduction of a node feature ([B, ...])."""
+def segment_sum_ordered(x: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+    """[B, D] sums of the rows of x [N, D] per segment (`counts` [B] int64), added in a fixed order: every segment is padded with
+    zeros to a power of two and its rows are added pairwise, neighbours first.  index_add_ accumulates floats with atomics, so its
+    bits change from call to call; here they do not, and (x + 0 is exact, a row's place in the tree is its index in the segment)
+    they do not depend on the other segments either.  log2(longest segment) small launches: for set-up code, not for a step."""
+    B, (N, D) = counts.shape[0], x.shape
+    longest = int(counts.max()) if B else 0
+    P = 1 << max(longest - 1, 0).bit_length()
+    seg = torch.arange(B, device=x.device).repeat_interleave(counts)
+    pos = torch.arange(N, device=x.device) - (torch.cumsum(counts, 0) - counts)[seg]
+    pad = x.new_zeros(B, P, D)
+    pad[seg, pos] = x
+    while P > 1:
+        pad = pad[:, 0::2] + pad[:, 1::2]
+        P >>= 1
+    return pad[:, 0]
+
+
+def readout_nodes(g: HeteroBatch, feat: str, op: str = 'mean', ntype: str = None, ordered: bool = False) -> torch.Tensor:
+    """dgl.readout_nodes: per-complex reduction of a node feature ([B, ...]).  `ordered`: sum in a fixed order
+    (`segment_sum_ordered`), for callers that promise the same bits for the same inputs."""
     x = g._ndata[ntype][feat]
     counts = g._bnn[ntype]
+    if ordered:
+        flat = x.flatten(1) if x.dim() > 1 else x[:, None]
+        out = segment_sum_ordered(flat, counts).reshape((g.batch_size,) + tuple(x.shape[1:]))
+        if op == 'sum':
+            return out
+        if op == 'mean':
+            return out / counts.clamp(min=1).to(x.dtype).view((-1,) + (1,) * (x.dim() - 1))
+        raise ValueError(f'unsupported readout op {op!r}')
     bidx = torch.arange(g.batch_size, device=g.device).repeat_interleave(counts)
     out = torch.zeros((g.batch_size,) + tuple(x.shape[1:]), dtype=x.dtype, device=g.device)
     out.index_add_(0, bidx, x)

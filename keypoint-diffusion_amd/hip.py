@@ -145,6 +145,9 @@ def lib():
     L.kpd_complex_noise.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p]
     L.kpd_step_coefficients.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.kpd_inpaint_coefficients.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.kpd_sample_update_inpaint.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 14 + [C.c_int32, C.c_void_p]
+    L.kpd_sample_renoise.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
     L.kpd_egnn_trainer_create.argtypes = [C.POINTER(KpdEgnnConfig), C.POINTER(C.c_void_p)]
     L.kpd_egnn_trainer_destroy.argtypes = [C.c_void_p]
     L.kpd_egnn_trainer_destroy.restype = None
@@ -213,6 +216,7 @@ EXPORTS = [
     'kpd_egnn_create', 'kpd_egnn_destroy', 'kpd_egnn_load_weight', 'kpd_egnn_commit', 'kpd_egnn_reserve',
     'kpd_egnn_forward', 'kpd_egnn_debug_state', 'kpd_egnn_last_counts', 'kpd_egnn_profile',
     'kpd_egnn_profile_read', 'kpd_sample_update', 'kpd_step_coefficients', 'kpd_complex_noise',
+    'kpd_inpaint_coefficients', 'kpd_sample_update_inpaint', 'kpd_sample_renoise',
     'kpd_gvp_create', 'kpd_gvp_destroy', 'kpd_gvp_load_weight', 'kpd_gvp_commit', 'kpd_gvp_reserve',
     'kpd_gvp_forward', 'kpd_gvp_debug_state', 'kpd_gvp_profile', 'kpd_gvp_profile_read', 'kpd_gvp_last_counts',
     'kpd_recenc_create', 'kpd_recenc_destroy', 'kpd_recenc_load_weight', 'kpd_recenc_commit', 'kpd_recenc_reserve',
@@ -951,6 +955,18 @@ def step_coefficients(gamma: torch.Tensor, s: torch.Tensor, t: torch.Tensor) -> 
     return coef
 
 
+def inpaint_coefficients(gamma: torch.Tensor, s: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """[B,6] coefficients of an inpainting step (kpd_inpaint_coefficients): the three of `step_coefficients`, bit for bit, then
+    alpha_s, sigma_s, sigma_t|s."""
+    gamma, s, t = _dev_f32(gamma, 'gamma'), _dev_f32(s, 's'), _dev_f32(t, 't')
+    if s.shape != t.shape or s.dim() != 1:
+        raise KpdError(f'inpaint_coefficients: s {tuple(s.shape)} and t {tuple(t.shape)} must be equal 1-D tensors')
+    coef = torch.empty(s.shape[0], 6, device=s.device)
+    check(lib().kpd_inpaint_coefficients(gamma.data_ptr(), int(gamma.shape[0]), s.data_ptr(), t.data_ptr(), int(s.shape[0]),
+                                         coef.data_ptr(), _stream()))
+    return coef
+
+
 def complex_noise(pb: PreparedBatch, width: int, complex_ids: torch.Tensor, seed: int, step: int, tag: int) -> torch.Tensor:
     """[n_lig, width] N(0,1) noise that depends only on (seed, complex id, step, tag, position in the complex)
     (kpd_complex_noise): a sharded run draws what the single-process run draws."""
@@ -1145,3 +1161,45 @@ def sample_update(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, 
     args = [_dev_f32(a, 'arg') for a in (eps_x, eps_h, noise_x, noise_h, coef)]
     check(lib().kpd_sample_update(pb.B, _ptr(pb.lig_ptr), _ptr(pb.kp_ptr), int(atom_nf), _ptr(lig_x), _ptr(lig_h),
                                   _ptr(kp_x), *[a.data_ptr() for a in args], pb.max_lig, _stream()))
+
+
+def _update_args(name, pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, per_x, per_h, coef, width):
+    """The checks of `sample_update`, and the sizes: the kernels index every per-atom array by the batch's own offsets."""
+    for t in (lig_x, lig_h, kp_x):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
+            raise KpdError(f'{name} state tensors must be contiguous fp32 GPU tensors (updated in place)')
+    F = int(atom_nf)
+    if F < 1 or lig_x.shape != (pb.n_lig, 3) or lig_h.shape != (pb.n_lig, F) or kp_x.shape != (pb.n_kp, 3):
+        raise KpdError(f'{name}: lig_x {tuple(lig_x.shape)}, lig_h {tuple(lig_h.shape)}, kp_x {tuple(kp_x.shape)} do not fit a batch of '
+                       f'{pb.n_lig} ligand atoms x {F} features and {pb.n_kp} keypoints')
+    per_x, per_h, coef = [_dev_f32(a, 'arg') for a in per_x], [_dev_f32(a, 'arg') for a in per_h], _dev_f32(coef, 'coef')
+    if any(a.shape != lig_x.shape for a in per_x) or any(a.shape != lig_h.shape for a in per_h) or coef.shape != (pb.B, width):
+        raise KpdError(f'{name}: every per-atom argument must have the shape of lig_x / lig_h, coef must be [{pb.B}, {width}]')
+    return per_x, per_h, coef
+
+
+def sample_update_inpaint(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h, coef6, fixed, known_x,
+                          known_h, kp_com0, known_noise_x, known_noise_h):
+    """In-place reverse-diffusion update around fixed atoms + ligand-COM removal (kpd_sample_update_inpaint; include/kpd.h
+    states the algorithm).  fixed [n_lig] uint8 / bool, known_x in the input frame, known_h normalised, kp_com0 [B,3]."""
+    (eps_x, noise_x, known_x, known_noise_x), (eps_h, noise_h, known_h, known_noise_h), coef6 = _update_args(
+        'sample_update_inpaint', pb, atom_nf, lig_x, lig_h, kp_x, (eps_x, noise_x, known_x, known_noise_x),
+        (eps_h, noise_h, known_h, known_noise_h), coef6, 6)
+    if not (fixed.is_cuda and fixed.dtype in (torch.bool, torch.uint8) and fixed.shape == (pb.n_lig,)):
+        raise KpdError('fixed must be a bool or uint8 GPU tensor with one entry per ligand atom')
+    fixed = fixed.contiguous().view(torch.uint8) if fixed.dtype == torch.bool else fixed.contiguous()
+    kp_com0 = _dev_f32(kp_com0, 'kp_com0')
+    if kp_com0.shape != (pb.B, 3):
+        raise KpdError(f'kp_com0 must be [{pb.B}, 3] (got {tuple(kp_com0.shape)})')
+    check(lib().kpd_sample_update_inpaint(pb.B, _ptr(pb.lig_ptr), _ptr(pb.kp_ptr), int(atom_nf), _ptr(lig_x), _ptr(lig_h), _ptr(kp_x),
+                                          _ptr(eps_x), _ptr(eps_h), _ptr(noise_x), _ptr(noise_h), _ptr(coef6), _ptr(fixed),
+                                          _ptr(known_x), _ptr(known_h), _ptr(kp_com0), _ptr(known_noise_x), _ptr(known_noise_h),
+                                          pb.max_lig, _stream()))
+
+
+def sample_renoise(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, noise_x, noise_h, coef6):
+    """In-place z_t = alpha_t|s z_s + sigma_t|s noise + ligand-COM removal (kpd_sample_renoise): back from s to t between two
+    repetitions of a resampled inpainting step."""
+    (noise_x,), (noise_h,), coef6 = _update_args('sample_renoise', pb, atom_nf, lig_x, lig_h, kp_x, (noise_x,), (noise_h,), coef6, 6)
+    check(lib().kpd_sample_renoise(pb.B, _ptr(pb.lig_ptr), _ptr(pb.kp_ptr), int(atom_nf), _ptr(lig_x), _ptr(lig_h), _ptr(kp_x),
+                                   _ptr(noise_x), _ptr(noise_h), _ptr(coef6), pb.max_lig, _stream()))

@@ -76,11 +76,27 @@ class PredefinedNoiseSchedule(nn.Module):
         return self.gamma[torch.round(t * self.timesteps).long()]
 
 
+class InpaintContext:
+    """What an inpainting step needs besides the state (include/kpd.h, "Inpainting"): `fixed` [n_lig] bool / uint8 (1 = this atom
+    is given), `x` [n_lig,3] known positions in the input (receptor) frame, `h` [n_lig,atom_nf] known features already divided
+    by `lig_feat_norm_constant` (both read on the fixed rows only), `kp_com0` [B,3] keypoint mean in the input frame."""
+
+    def __init__(self, fixed: torch.Tensor, x: torch.Tensor, h: torch.Tensor, kp_com0: torch.Tensor):
+        if not (isinstance(fixed, torch.Tensor) and fixed.dtype in (torch.bool, torch.uint8) and fixed.dim() == 1):
+            raise ValueError(f'fixed must be a 1-D bool or uint8 tensor with one entry per ligand atom (got '
+                             f'{getattr(fixed, "dtype", type(fixed))} {tuple(getattr(fixed, "shape", ()))})')
+        if x.shape != (fixed.shape[0], 3) or h.dim() != 2 or h.shape[0] != fixed.shape[0] or kp_com0.dim() != 2 or kp_com0.shape[1] != 3:
+            raise ValueError(f'inpaint: x {tuple(x.shape)}, h {tuple(h.shape)}, kp_com0 {tuple(kp_com0.shape)} do not fit '
+                             f'{fixed.shape[0]} ligand atoms')
+        self.fixed = (fixed.view(torch.uint8) if fixed.dtype == torch.bool else fixed).contiguous()
+        self.x, self.h, self.kp_com0 = x.float().contiguous(), h.float().contiguous(), kp_com0.float().contiguous()
+
+
 class StepGraph:
     """A captured reverse step.  `step(s, t)` writes the two scalars into static device buffers and replays the graph;
     the graph holds the denoiser forward (graph build included), the noise draw and the in-place z_s update."""
 
-    def __init__(self, model: 'KeypointDiffusion', g, bidx=None, noise=None):
+    def __init__(self, model: 'KeypointDiffusion', g, bidx=None, noise=None, inpaint=None):
         dev, B = g.device, g.batch_size
         if dev.type != 'cuda':
             raise hip.KpdError('a step graph needs the batch on the GPU')
@@ -93,19 +109,20 @@ class StepGraph:
         saved = [t.clone() for t in state]
         T = model.n_timesteps
         self.s.fill_((T - 1) / T)
+        kw = {} if inpaint is None else {'inpaint': inpaint}          # the plain step is called exactly as before
         # warm-up outside capture (workspace reservation, first-use initialisation), on a side stream as capture requires
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(2):
-                model.sample_p_zs_given_zt(self.s, self.t, g, bidx, noise=noise)
+                model.sample_p_zs_given_zt(self.s, self.t, g, bidx, noise=noise, **kw)
         torch.cuda.current_stream(dev).wait_stream(side)
         for t, c in zip(state, saved):
             t.copy_(c)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            model.sample_p_zs_given_zt(self.s, self.t, g, bidx, noise=noise)
-        self._keep = (g, noise)
+            model.sample_p_zs_given_zt(self.s, self.t, g, bidx, noise=noise, **kw)
+        self._keep = (g, noise, inpaint)
         # The captured kernels hold raw pointers into the engine's workspace arena and packed weights.  Holding the engine
         # object keeps both allocations alive even if the module builds a new engine; the pin records what must not have
         # changed for a replay to mean "one reverse step of this model": the arena (a larger batch re-reserves it, which
@@ -278,12 +295,12 @@ class KeypointDiffusion(nn.Module):
         g.nodes['lig'].data['h_0'] = g.nodes['lig'].data['h_0'] * self.lig_feat_norm_constant
         return g
 
-    def remove_com(self, g, lig_batch_idx, kp_batch_idx, com: str = None):
+    def remove_com(self, g, lig_batch_idx, kp_batch_idx, com: str = None, ordered: bool = False):
         if com is None:
             raise NotImplementedError('removing COM of receptor/ligand complex not implemented')
         if com not in ('ligand', 'receptor'):
             raise ValueError(f'invalid value for com: {com=}')
-        c = G.readout_nodes(g, feat='x_0', ntype='lig' if com == 'ligand' else 'kp', op='mean')
+        c = G.readout_nodes(g, feat='x_0', ntype='lig' if com == 'ligand' else 'kp', op='mean', ordered=ordered)
         g.nodes['lig'].data['x_0'] = g.nodes['lig'].data['x_0'] - c[lig_batch_idx]
         g.nodes['kp'].data['x_0'] = g.nodes['kp'].data['x_0'] - c[kp_batch_idx]
         return g
@@ -314,6 +331,17 @@ class KeypointDiffusion(nn.Module):
         sig_s, sig_t = self.sigma(g_s), self.sigma(g_t)
         return torch.stack([alpha_ts, sigma2_ts / alpha_ts / sig_t, sigma_ts * sig_s / sig_t], dim=1).contiguous()
 
+    def inpaint_coefficients(self, s: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        """[B,6] = the three columns of `step_coefficients`, bit for bit, then (alpha_s, sigma_s, sigma_t|s): what an inpainting
+        step needs to noise the known part to level s and to move the state back from s to t (include/kpd.h).  One kernel on
+        the GPU (kpd_inpaint_coefficients), the torch mirror on host tensors."""
+        if s.is_cuda:
+            return hip.inpaint_coefficients(self.gamma.gamma, s, t)
+        g_s, g_t = self.gamma(s), self.gamma(t)
+        _, sigma_ts, _ = self.sigma_and_alpha_t_given_s(g_t, g_s)
+        return torch.cat([self.step_coefficients(s, t), torch.stack([self.alpha(g_s), self.sigma(g_s), sigma_ts], dim=1)],
+                         dim=1).contiguous()
+
     def use_complex_noise(self, seed):
         """Opt in to sharding-invariant noise: every draw of the sampler becomes a function of (seed, complex id, timestep,
         position in the complex) (kpd_complex_noise), so a run split over ranks reproduces the single-process run.
@@ -326,14 +354,19 @@ class KeypointDiffusion(nn.Module):
             return torch.randn(g.num_nodes('lig'), width, device=g.device)
         return hip.complex_noise(g.prepared(), width, complex_ids, self._noise_seed, step, tag)
 
-    def sample_p_zs_given_zt(self, s, t, g, batch_idxs=None, noise=None, complex_ids=None, step=0):
+    def sample_p_zs_given_zt(self, s, t, g, batch_idxs=None, noise=None, complex_ids=None, step=0, inpaint=None, repetition=0):
         """One reverse step (ligand_diffuser.py:497-538).  `noise` = (pos_noise, feat_noise) may be
         injected for reproducible parity tests; by default it is drawn with torch.randn as upstream
-        (or per complex, `use_complex_noise`, when `complex_ids` [B] int64 and the integer `step` are given)."""
+        (or per complex, `use_complex_noise`, when `complex_ids` [B] int64 and the integer `step` are given).
+        `inpaint` (an `InpaintContext`): the step around fixed atoms (kpd_sample_update_inpaint); `noise` may then be the 4-tuple
+        (pos_noise, feat_noise, known_pos_noise, known_feat_noise), and `repetition` u selects the tags 6u .. 6u + 3 of the
+        per-complex streams.  With `inpaint=None` nothing differs from the plain step."""
         lig, kp = g.nodes['lig'].data, g.nodes['kp'].data
         for d, k in ((lig, 'x_0'), (lig, 'h_0'), (kp, 'x_0')):
             if not (d[k].is_contiguous() and d[k].dtype == torch.float32):
                 d[k] = d[k].contiguous().float()
+        if inpaint is not None:
+            return self._inpaint_step(s, t, g, batch_idxs, noise, complex_ids, step, inpaint, repetition)
         coef = self.step_coefficients(s, t)
         eps_h, eps_x = self.dynamics(g, t, batch_idxs)
         if noise is None:
@@ -342,13 +375,39 @@ class KeypointDiffusion(nn.Module):
                           noise[0], noise[1], coef)
         return g
 
+    def _inpaint_step(self, s, t, g, batch_idxs, noise, complex_ids, step, inpaint, repetition):
+        lig, kp = g.nodes['lig'].data, g.nodes['kp'].data
+        coef = self.inpaint_coefficients(s, t)
+        eps_h, eps_x = self.dynamics(g, t, batch_idxs)
+        noise = tuple(noise) if noise is not None else ()
+        if len(noise) not in (0, 2, 4):
+            raise ValueError('noise must be (pos, feat) or (pos, feat, known_pos, known_feat)')
+        F = lig['h_0'].shape[1]
+        for tag in range(len(noise), 4):             # draw order: step x, step h, known x, known h
+            noise += (self._draw(g, 3 if tag % 2 == 0 else F, complex_ids, step, 6 * repetition + tag),)
+        hip.sample_update_inpaint(g.prepared(), self.n_lig_features, lig['x_0'], lig['h_0'], kp['x_0'], eps_x, eps_h, noise[0],
+                                  noise[1], coef, inpaint.fixed, inpaint.x, inpaint.h, inpaint.kp_com0, noise[2], noise[3])
+        return g
+
+    def renoise_zt_given_zs(self, s, t, g, noise=None, complex_ids=None, step=0, repetition=0):
+        """The forward move between two repetitions of a resampled inpainting step: z_t = alpha_t|s z_s + sigma_t|s n for the
+        ligand positions and features, then ligand-COM removal (kpd_sample_renoise).  Tags 6u + 4, 6u + 5 of the per-complex
+        streams."""
+        lig, kp = g.nodes['lig'].data, g.nodes['kp'].data
+        if noise is None:
+            noise = (self._draw(g, 3, complex_ids, step, 6 * repetition + 4),
+                     self._draw(g, lig['h_0'].shape[1], complex_ids, step, 6 * repetition + 5))
+        hip.sample_renoise(g.prepared(), self.n_lig_features, lig['x_0'], lig['h_0'], kp['x_0'], noise[0], noise[1],
+                           self.inpaint_coefficients(s, t))
+        return g
+
     @torch.no_grad()
-    def capture_step(self, g, bidx=None, noise=None) -> 'StepGraph':
+    def capture_step(self, g, bidx=None, noise=None, inpaint=None) -> 'StepGraph':
         """One reverse step (`sample_p_zs_given_zt`) captured as a HIP graph for this batch: replaying it costs one
         launch instead of ~30.  The step's kernels take shapes from host-known capacities and counts from device memory,
         so the same graph serves every timestep.  Measured gain is small (B = 1: 0.99 -> 0.96 ms/step, B = 64: 8.32 ->
         8.29): the step is bound by its chain of dependent kernels, not by launch overhead."""
-        return StepGraph(self, g, bidx, noise)
+        return StepGraph(self, g, bidx, noise, inpaint)
 
     @torch.no_grad()
     def sample_from_encoded_receptors(self, g, visualize=False, init_lig_pos: torch.Tensor = None, complex_ids=None,
@@ -357,26 +416,70 @@ class KeypointDiffusion(nn.Module):
         (global index of every complex in the job) selects the per-complex noise streams of `use_complex_noise`.
         `use_graph=True`: replay the reverse step as a captured HIP graph (not with the per-complex noise streams, which
         take the timestep as a launch argument); the default is the eager step, the measured difference is ≤ 3 %."""
+        return self._reverse_loop(g, visualize, init_lig_pos, complex_ids, use_graph)
+
+    @torch.no_grad()
+    def inpaint_from_encoded_receptors(self, g, fixed: torch.Tensor, resamplings: int = 1, visualize=False,
+                                       init_lig_pos: torch.Tensor = None, complex_ids=None, use_graph: Optional[bool] = None,
+                                       overwrite_fixed: bool = True):
+        """The reverse loop around fixed atoms (RePaint-style replacement conditioning; include/kpd.h, "Inpainting").  `fixed`
+        [n_lig] bool / uint8 marks the given ligand atoms; their known positions (input frame) and features are the ligand rows
+        of `g`, the other rows are generated.  Every timestep is run `resamplings` times with a forward move back to t in between
+        (r T denoiser forwards in all).  `overwrite_fixed`: return the fixed rows as the caller's values bit for bit; otherwise
+        they come back as the loop leaves them, X + (alpha_0 - 1) k0 + sigma_0 n'.  Without `init_lig_pos` a complex with fixed
+        atoms starts in the frame of the mean of its known positions.  `use_graph=True` is available for `resamplings == 1` with
+        the global noise.  Returns what `sample_from_encoded_receptors` returns."""
+        n_lig = g.num_nodes('lig')
+        if not (isinstance(fixed, torch.Tensor) and fixed.dtype in (torch.bool, torch.uint8)):
+            raise ValueError(f'fixed must be a bool or uint8 tensor (got {getattr(fixed, "dtype", type(fixed).__name__)})')
+        if fixed.dim() != 1 or fixed.shape[0] != n_lig:
+            raise ValueError(f'fixed must have one entry per ligand atom: expected [{n_lig}], got {list(fixed.shape)}')
+        if isinstance(resamplings, bool) or not isinstance(resamplings, int) or resamplings < 1:
+            raise ValueError(f'resamplings must be an integer >= 1 (got {resamplings!r})')
+        width = g.nodes['lig'].data['h_0'].shape[1] if g.nodes['lig'].data['h_0'].dim() == 2 else -1
+        if width != self.n_lig_features:
+            raise ValueError(f"the ligand features of g (h_0) must have atom_nf = {self.n_lig_features} columns (got {width})")
+        if g.device.type != 'cuda':
+            raise hip.KpdError(f'inpaint_from_encoded_receptors: g must live on the GPU (got {g.device}); there is no CPU implementation')
+        return self._reverse_loop(g, visualize, init_lig_pos, complex_ids, use_graph, fixed=fixed.to(g.device),
+                                  resamplings=resamplings, overwrite_fixed=overwrite_fixed)
+
+    def _reverse_loop(self, g, visualize, init_lig_pos, complex_ids, use_graph, fixed=None, resamplings=1, overwrite_fixed=True):
+        """The loop behind `sample_from_encoded_receptors` (fixed is None: the plain sampler, call for call as upstream) and
+        `inpaint_from_encoded_receptors`.  The per-complex means of the set-up and of the frame restoration are summed in a fixed
+        order (`G.segment_sum_ordered`): with the per-complex noise streams a run is then a function of its inputs and the seed,
+        bit for bit, as the step kernels already are."""
         device, B = g.device, g.batch_size
-        init_kp_com = G.readout_nodes(g, feat='x_0', op='mean', ntype='kp')
+        init_kp_com = G.readout_nodes(g, feat='x_0', op='mean', ntype='kp', ordered=True)
         bidx = G.get_batch_idxs(g)
         lig_b, kp_b = bidx['lig'], bidx['kp']
+        ctx = None
+        if fixed is not None:
+            fixed = fixed.bool()
+            known_x, known_h = g.nodes['lig'].data['x_0'].float().clone(), g.nodes['lig'].data['h_0'].float().clone()
+            ctx = InpaintContext(fixed, known_x, known_h / self.lig_feat_norm_constant, init_kp_com)
         if init_lig_pos is not None:
             assert init_lig_pos.shape == (B, 3)
             frame = init_lig_pos
         else:
-            frame = G.readout_nodes(g, feat='x_0', op='mean', ntype='rec')
+            frame = G.readout_nodes(g, feat='x_0', op='mean', ntype='rec', ordered=True)
+            if ctx is not None:          # a complex with fixed atoms starts around them
+                w = fixed.to(known_x.dtype)[:, None]
+                n_lig_atoms = g.batch_num_nodes('lig')
+                n_fixed = G.segment_sum_ordered(w, n_lig_atoms)
+                known_com = G.segment_sum_ordered(known_x * w, n_lig_atoms) / n_fixed.clamp(min=1)
+                frame = torch.where(n_fixed > 0, known_com, frame)
         g.nodes['kp'].data['x_0'] = g.nodes['kp'].data['x_0'] - frame[kp_b]
         if complex_ids is not None:
             complex_ids = complex_ids.to(device).long()
         for tag, feat in enumerate(('x_0', 'h_0')):
             g.nodes['lig'].data[feat] = self._draw(g, g.nodes['lig'].data[feat].shape[1], complex_ids, self.n_timesteps, tag)
-        g = self.remove_com(g, lig_b, kp_b, com='ligand')
+        g = self.remove_com(g, lig_b, kp_b, com='ligand', ordered=True)
 
         def snapshot():
             f = G.copy_graph(g, n_copies=1, batched_graph=True)[0]
             f = self.unnormalize(f)
-            delta = init_kp_com - G.readout_nodes(f, feat='x_0', ntype='kp', op='mean')
+            delta = init_kp_com - G.readout_nodes(f, feat='x_0', ntype='kp', op='mean', ordered=True)
             f.nodes['lig'].data['x_0'] = f.nodes['lig'].data['x_0'] + delta[lig_b]
             parts = G.unbatch(f.to('cpu'))
             return [p.nodes['lig'].data['x_0'] for p in parts], [p.nodes['lig'].data['h_0'] for p in parts]
@@ -389,30 +492,53 @@ class KeypointDiffusion(nn.Module):
         per_complex = getattr(self, '_noise_seed', None) is not None and complex_ids is not None
         if use_graph and per_complex:
             raise ValueError('use_graph=True cannot be combined with per-complex noise streams (the timestep is a launch argument)')
-        step_graph = self.capture_step(g, bidx) if use_graph else None
+        if use_graph and resamplings != 1:
+            raise ValueError('use_graph=True needs resamplings == 1 (the forward move between repetitions is not part of the captured step)')
+        if ctx is None:
+            step_graph = self.capture_step(g, bidx) if use_graph else None
+        else:
+            step_graph = self.capture_step(g, bidx, inpaint=ctx) if use_graph else None
         for s in reversed(range(self.n_timesteps)):
             if step_graph is not None:
                 step_graph.step(s / self.n_timesteps, (s + 1) / self.n_timesteps)
-            else:
+            elif ctx is None:
                 g = self.sample_p_zs_given_zt(ones * (s / self.n_timesteps), ones * ((s + 1) / self.n_timesteps), g, bidx,
                                               complex_ids=complex_ids, step=s)
+            else:
+                s_, t_ = ones * (s / self.n_timesteps), ones * ((s + 1) / self.n_timesteps)
+                for u in range(resamplings):
+                    g = self.sample_p_zs_given_zt(s_, t_, g, bidx, complex_ids=complex_ids, step=s, inpaint=ctx, repetition=u)
+                    if u + 1 < resamplings:
+                        g = self.renoise_zt_given_zs(s_, t_, g, complex_ids=complex_ids, step=s, repetition=u)
             if visualize:
                 fx, fh = snapshot()
                 frames_x.append(fx), frames_h.append(fh)
 
-        g = self.remove_com(g, lig_b, kp_b, com='receptor')
+        g = self.remove_com(g, lig_b, kp_b, com='receptor', ordered=True)
         for nt in ('lig', 'kp'):
             g.nodes[nt].data['x_0'] = g.nodes[nt].data['x_0'] + init_kp_com[bidx[nt]]
         g = self.unnormalize(g)
-        if visualize:
+        if ctx is not None and overwrite_fixed:
+            g.nodes['lig'].data['x_0'] = torch.where(fixed[:, None], known_x, g.nodes['lig'].data['x_0'])
+            g.nodes['lig'].data['h_0'] = torch.where(fixed[:, None], known_h, g.nodes['lig'].data['h_0'])
+        if visualize and not (ctx is not None and overwrite_fixed):
             return list(zip(*frames_x)), list(zip(*frames_h))
         parts = G.unbatch(g.to('cpu'))
-        return [p.nodes['lig'].data['x_0'] for p in parts], [p.nodes['lig'].data['h_0'] for p in parts]
+        pos, feat = [p.nodes['lig'].data['x_0'] for p in parts], [p.nodes['lig'].data['h_0'] for p in parts]
+        if visualize:                                        # the last frame is the result: it carries the overwritten rows
+            frames_x[-1], frames_h[-1] = pos, feat
+            return list(zip(*frames_x)), list(zip(*frames_h))
+        return pos, feat
 
     @torch.no_grad()
     def _sample(self, ref_graphs: List[G.HeteroBatch], n_lig_atoms: List[List[int]], rec_enc_batch_size: int = 32,
-                diff_batch_size: int = 32, visualize=False, use_ref_lig_com: bool = False, group=None):
+                diff_batch_size: int = 32, visualize=False, use_ref_lig_com: bool = False, group=None, known=None,
+                resamplings: int = 1):
         """Several pockets x several ligands per pocket (ligand_diffuser.py:271-340).
+
+        `known` (inpainting): one entry per pocket, None or (pos [m_i,3] in the pocket's frame, feat [m_i,atom_nf]); these atoms
+        are rows 0 .. m_i - 1 of every ligand generated for pocket i and are held fixed, the other rows are generated
+        (`inpaint_from_encoded_receptors`, with `resamplings`).
 
         The flat list of (pocket, replicate) complexes it builds (:292-313) is the unit of multi-GPU work:
         when a `torch.distributed` process group with more than one rank is initialised, every rank calls this with the SAME
@@ -429,6 +555,24 @@ class KeypointDiffusion(nn.Module):
         # the flat complex list: (pocket index, number of ligand atoms), in input order
         flat = [(i, int(n)) for i, sizes in enumerate(n_lig_atoms) for n in sizes]
         device = ref_graphs[0].device
+        if isinstance(resamplings, bool) or not isinstance(resamplings, int) or resamplings < 1:
+            raise ValueError(f'resamplings must be an integer >= 1 (got {resamplings!r})')
+        if known is not None:
+            if len(known) != len(ref_graphs):
+                raise ValueError(f'known must have one entry per pocket ({len(ref_graphs)}), got {len(known)}')
+            known = [None if k is None else (torch.as_tensor(k[0]).float(), torch.as_tensor(k[1]).float()) for k in known]
+            for i, k in enumerate(known):
+                if k is None:
+                    continue
+                if k[0].dim() != 2 or k[0].shape[1] != 3 or k[1].dim() != 2 or k[1].shape[0] != k[0].shape[0]:
+                    raise ValueError(f'known[{i}] must be (pos [m,3], feat [m,atom_nf]); got {tuple(k[0].shape)}, {tuple(k[1].shape)}')
+                if k[1].shape[1] != self.n_lig_features:
+                    raise ValueError(f'known[{i}]: the known features must have atom_nf = {self.n_lig_features} columns '
+                                     f'(got {k[1].shape[1]})')
+                small = [n for n in n_lig_atoms[i] if int(n) < k[0].shape[0]]
+                if small:
+                    raise ValueError(f'n_lig_atoms[{i}] asks for {int(small[0])} atoms, fewer than the {k[0].shape[0]} known atoms '
+                                     f'of known[{i}]')
 
         def run(mine):
             """Ligands of the complexes `mine` (a range into `flat`)."""
@@ -442,12 +586,23 @@ class KeypointDiffusion(nn.Module):
             for c in mine:           # one copy_graph call per (pocket, run of replicates) keeps the reference's copy semantics
                 i, n = flat[c]
                 graphs.extend(G.copy_graph(encoded[i], n_copies=1, lig_atoms_per_copy=torch.tensor([n])))
+                if known is not None:
+                    m = 0 if known[i] is None else known[i][0].shape[0]
+                    d = graphs[-1].nodes['lig'].data
+                    if m:
+                        d['x_0'][:m], d['h_0'][:m] = known[i][0].to(device), known[i][1].to(device)
+                    d['_fixed'] = torch.arange(n, device=device) < m
             pos, feat = [], []
             for lo in range(0, len(graphs), diff_batch_size):
                 bg = G.batch(graphs[lo:lo + diff_batch_size])
                 init = G.readout_nodes(bg, feat='x_0', op='mean', ntype='lig') if use_ref_lig_com else None
                 ids = torch.arange(mine[lo], mine[lo] + bg.batch_size, dtype=torch.long)
-                p, f = self.sample_from_encoded_receptors(bg, visualize=visualize, init_lig_pos=init, complex_ids=ids)
+                if known is None:
+                    p, f = self.sample_from_encoded_receptors(bg, visualize=visualize, init_lig_pos=init, complex_ids=ids)
+                else:
+                    fixed = bg.nodes['lig'].data.pop('_fixed')
+                    p, f = self.inpaint_from_encoded_receptors(bg, fixed, resamplings=resamplings, visualize=visualize,
+                                                               init_lig_pos=init, complex_ids=ids)
                 pos.extend(p), feat.extend(f)
             return pos, feat
 
@@ -474,6 +629,21 @@ class KeypointDiffusion(nn.Module):
                             diff_batch_size: int = 32, visualize=False):
         s = self._sample([rec_graph], n_lig_atoms=[n_lig_atoms.tolist()], rec_enc_batch_size=rec_enc_batch_size,
                          diff_batch_size=diff_batch_size, visualize=visualize)
+        return s[0]['positions'], s[0]['features']
+
+    @torch.no_grad()
+    def inpaint_given_pocket(self, rec_graph, known_pos: torch.Tensor, known_feat: torch.Tensor, n_lig_atoms: torch.Tensor,
+                             rec_enc_batch_size: int = 32, diff_batch_size: int = 32, resamplings: int = 1, visualize=False):
+        """Ligands of the sizes `n_lig_atoms` for one pocket, grown around the known atoms: `known_pos` [m,3] (the pocket's
+        frame) and `known_feat` [m,atom_nf] come back as rows 0 .. m - 1 of every ligand."""
+        known_pos, known_feat = torch.as_tensor(known_pos), torch.as_tensor(known_feat)
+        if known_pos.dim() != 2 or known_pos.shape[1] != 3:
+            raise ValueError(f'known_pos must be [m, 3] (got {tuple(known_pos.shape)})')
+        if known_feat.dim() != 2 or known_feat.shape[0] != known_pos.shape[0] or known_feat.shape[1] != self.n_lig_features:
+            raise ValueError(f'known_feat must be [{known_pos.shape[0]}, atom_nf = {self.n_lig_features}] (got {tuple(known_feat.shape)})')
+        s = self._sample([rec_graph], n_lig_atoms=[torch.as_tensor(n_lig_atoms).tolist()], rec_enc_batch_size=rec_enc_batch_size,
+                         diff_batch_size=diff_batch_size, visualize=visualize, known=[(known_pos, known_feat)],
+                         resamplings=resamplings)
         return s[0]['positions'], s[0]['features']
 
     @torch.no_grad()
