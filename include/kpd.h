@@ -550,6 +550,61 @@ kpd_status kpd_sample_renoise(int32_t B, const int32_t *lig_ptr, const int32_t *
                               float *lig_x, float *lig_h, float *kp_x, const float *noise_x, const float *noise_h,
                               const float *coef6, int32_t max_lig, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Clash guidance: the reverse step that keeps the ligand out of a set of atoms (no upstream counterpart, this comment is the
+ * specification).  Upstream knows steric clashes only as a training loss (rl_dist_threshold, models/ligand_diffuser.py:137-156,
+ * here kpd_dist_hinge); this imposes the same constraint at sampling time, on the same quantity -- the denoised estimate x-hat --
+ * without retraining and without a gradient through the denoiser.
+ *
+ * Inputs per batch beyond those of kpd_sample_update: wall_x [n_wall,3], the atoms to stay away from, in the input (receptor)
+ * frame; wall_ptr [B+1] int32 offsets, complex b owns rows [wall_ptr[b], wall_ptr[b+1]) and may own none; kp_com0 [B,3], the
+ * keypoint mean in the input frame (as in inpainting); threshold > 0 in Angstrom; coef9 [B,9] from kpd_guided_coefficients:
+ *   columns 0-5 = the bits of kpd_inpaint_coefficients (so 0-2 = the bits of kpd_step_coefficients),
+ *   6 = alpha_t = sqrt(sigmoid(-gamma_t)),  7 = sigma_t = sqrt(sigmoid(gamma_t)),
+ *   8 = w = scale alpha_s sigma^2_t|s / sigma_t^2  when round(t T) <= round(t_max T), else 0.
+ * alpha_s sigma^2_t|s / sigma_t^2 is the weight of x_0 in the mean of q(z_s | z_t, x_0); upstream's mu is that mean evaluated at
+ * x-hat, so moving x-hat by D moves mu by exactly this weight times D.  It lies in [0.19, 0.9995] for T = 10 and in
+ * [3.9e-4, 0.36] for T = 1000 (polynomial_2, precision 1e-4 and 1e-5): nothing blows up at t ~ 1, where 1 / alpha_t ~ 300.
+ *
+ * One step t -> s for complex b:
+ *   1. candidate for every atom, the arithmetic of kpd_sample_update:  u = z_t / alpha_t|s - var eps + sigma_step n   (x and h)
+ *   2. denoised positions:  xh_i = (z_t,i - sigma_t eps_x,i) / alpha_t          (denoised_representation, :221-230)
+ *   3. frame, as in inpainting: m_b = ordered mean of this complex's kp_x rows on entry; a wall atom r sits at
+ *      r' = (r - kp_com0_b) + m_b, evaluated in that order
+ *   4. force:  F_i = sum_r max(threshold - d, 0) (xh_i - r') / d,  d = |xh_i - r'|, over the wall atoms of complex b.  A pair with
+ *      d < 1e-6 has no direction and adds nothing.  F_i is minus the gradient of the squared hinge 1/2 sum (threshold - d)+^2; the
+ *      square is deliberate: the gradient of upstream's linear hinge jumps by a unit vector at d = threshold, where a last-bit
+ *      difference would flip a whole contact.  With scale = 1 an atom with one contact has its x-hat moved onto the threshold sphere.
+ *   5. shift:  u_x,i += w F_i.  Features are not guided.
+ *   6. inpainting merge, if a mask is given: fixed rows are replaced as kpd_sample_update_inpaint does.  Fixed atoms are not
+ *      pushed and are not part of the wall.
+ *   7. COM removal, as in every other instance.
+ * The guided step is a fourth instance of the device function behind kpd_sample_update, kpd_sample_update_inpaint and
+ * kpd_sample_renoise, whose bits it does not change.  A neutral complex -- no wall atoms, or w = 0, or no pair under the threshold --
+ * leaves with exactly the bits of kpd_sample_update (with a mask: of kpd_sample_update_inpaint).  An atom's force is summed by one
+ * wavefront, lanes striding the wall atoms, then a butterfly: a fixed order that depends only on its complex, so a complex's result
+ * is bitwise independent of the batch and of the repeat.  No atomics, no host synchronisation, counts come from device memory
+ * (capturable); one workgroup per complex; max_lig <= 4096 (x-hat is staged in LDS beside the new positions, 96 KB at most); wall
+ * atoms are read from global memory, any number per complex.  wall_ptr must be ascending within [0, n_wall]: the kernel reads
+ * what it says.  fixed, known_x, known_h, known_noise_x, known_noise_h: all NULL (no mask) or all given.
+ *
+ * kpd_clash_score is the report to rank or filter finished samples by: out [B,3] = per complex {1/2 sum (threshold - d)+^2, the
+ * number of pairs with d < threshold (exact up to 2^24), the smallest such d or +inf}, ligand and wall in one frame, through the
+ * same pair loop (coincident pairs count here), summed in a fixed order.
+ * ------------------------------------------------------------------------------------- */
+kpd_status kpd_guided_coefficients(const float *gamma, int32_t n_gamma, const float *s, const float *t,
+                                   int32_t B, float scale, float t_max, float *coef9, void *stream);
+kpd_status kpd_sample_update_guided(int32_t B, const int32_t *lig_ptr, const int32_t *kp_ptr,
+                                    int32_t atom_nf, float *lig_x, float *lig_h, float *kp_x,
+                                    const float *eps_x, const float *eps_h,
+                                    const float *noise_x, const float *noise_h, const float *coef9,
+                                    const uint8_t *fixed, const float *known_x, const float *known_h,
+                                    const float *kp_com0, const float *known_noise_x, const float *known_noise_h,
+                                    const int32_t *wall_ptr, const float *wall_x,
+                                    float threshold, int32_t max_lig, void *stream);
+kpd_status kpd_clash_score(int32_t B, const int32_t *lig_ptr, const float *lig_x, const int32_t *wall_ptr,
+                           const float *wall_x, float threshold, float *out, void *stream);
+
 /* Sharding-invariant N(0,1) noise for the ligand rows of a batch (opt-in replacement of the global torch.randn draws of
  * ligand_diffuser.py:367, 530-531): out [n_nodes, width] with rows of complex b =
  * [node_ptr[b], node_ptr[b+1]).  Philox4x32-10 keyed by (seed, complex_id[b]), counter (element, step, tag): the values do

@@ -148,6 +148,11 @@ def lib():
     L.kpd_inpaint_coefficients.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.kpd_sample_update_inpaint.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 14 + [C.c_int32, C.c_void_p]
     L.kpd_sample_renoise.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
+    L.kpd_guided_coefficients.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p,
+                                          C.c_void_p]
+    L.kpd_sample_update_guided.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 16 +
+                                           [C.c_float, C.c_int32, C.c_void_p])
+    L.kpd_clash_score.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_void_p]
     L.kpd_egnn_trainer_create.argtypes = [C.POINTER(KpdEgnnConfig), C.POINTER(C.c_void_p)]
     L.kpd_egnn_trainer_destroy.argtypes = [C.c_void_p]
     L.kpd_egnn_trainer_destroy.restype = None
@@ -217,6 +222,7 @@ EXPORTS = [
     'kpd_egnn_forward', 'kpd_egnn_debug_state', 'kpd_egnn_last_counts', 'kpd_egnn_profile',
     'kpd_egnn_profile_read', 'kpd_sample_update', 'kpd_step_coefficients', 'kpd_complex_noise',
     'kpd_inpaint_coefficients', 'kpd_sample_update_inpaint', 'kpd_sample_renoise',
+    'kpd_guided_coefficients', 'kpd_sample_update_guided', 'kpd_clash_score',
     'kpd_gvp_create', 'kpd_gvp_destroy', 'kpd_gvp_load_weight', 'kpd_gvp_commit', 'kpd_gvp_reserve',
     'kpd_gvp_forward', 'kpd_gvp_debug_state', 'kpd_gvp_profile', 'kpd_gvp_profile_read', 'kpd_gvp_last_counts',
     'kpd_recenc_create', 'kpd_recenc_destroy', 'kpd_recenc_load_weight', 'kpd_recenc_commit', 'kpd_recenc_reserve',
@@ -1203,3 +1209,106 @@ def sample_renoise(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, noise_x, nois
     (noise_x,), (noise_h,), coef6 = _update_args('sample_renoise', pb, atom_nf, lig_x, lig_h, kp_x, (noise_x,), (noise_h,), coef6, 6)
     check(lib().kpd_sample_renoise(pb.B, _ptr(pb.lig_ptr), _ptr(pb.kp_ptr), int(atom_nf), _ptr(lig_x), _ptr(lig_h), _ptr(kp_x),
                                    _ptr(noise_x), _ptr(noise_h), _ptr(coef6), pb.max_lig, _stream()))
+
+
+def guided_coefficients(gamma: torch.Tensor, s: torch.Tensor, t: torch.Tensor, scale: float, t_max: float) -> torch.Tensor:
+    """[B,9] coefficients of a guided step (kpd_guided_coefficients): the six of `inpaint_coefficients`, bit for bit, then alpha_t,
+    sigma_t and the guidance weight w = scale alpha_s sigma^2_t|s / sigma_t^2 (0 above t_max)."""
+    gamma, s, t = _dev_f32(gamma, 'gamma'), _dev_f32(s, 's'), _dev_f32(t, 't')
+    if s.shape != t.shape or s.dim() != 1:
+        raise KpdError(f'guided_coefficients: s {tuple(s.shape)} and t {tuple(t.shape)} must be equal 1-D tensors')
+    if not (float(scale) >= 0.0 and 0.0 < float(t_max) <= 1.0):
+        raise KpdError(f'guided_coefficients: scale must be >= 0 and t_max in (0, 1] (got scale = {scale!r}, t_max = {t_max!r})')
+    coef = torch.empty(s.shape[0], 9, device=s.device)
+    check(lib().kpd_guided_coefficients(gamma.data_ptr(), int(gamma.shape[0]), s.data_ptr(), t.data_ptr(), int(s.shape[0]),
+                                        float(scale), float(t_max), coef.data_ptr(), _stream()))
+    return coef
+
+
+def _wall_args(name, wall_x, wall_ptr, B):
+    """Shape, dtype and device of a wall: wall_x [n_wall,3] fp32, wall_ptr [B+1] int32, both on the GPU.  The VALUES of wall_ptr
+    are not read here (that would synchronise every step, and cannot be done while a graph is captured): `check_wall` does it,
+    once per tensor (`_wall_values_once`)."""
+    if not (isinstance(wall_x, torch.Tensor) and isinstance(wall_ptr, torch.Tensor) and wall_x.is_cuda and wall_ptr.is_cuda):
+        raise KpdError(f'{name}: wall_x and wall_ptr must be GPU tensors (there is no CPU implementation)')
+    if wall_x.dtype != torch.float32 or wall_x.dim() != 2 or wall_x.shape[1] != 3 or not wall_x.is_contiguous():
+        raise KpdError(f'{name}: wall_x must be a contiguous fp32 [n_wall, 3] tensor (got {wall_x.dtype} {tuple(wall_x.shape)})')
+    if wall_ptr.dtype != torch.int32 or wall_ptr.shape != (B + 1,) or not wall_ptr.is_contiguous():
+        raise KpdError(f'{name}: wall_ptr must be a contiguous int32 [{B + 1}] tensor, one offset per complex and the total '
+                       f'(got {wall_ptr.dtype} {tuple(wall_ptr.shape)}): the wall does not fit the batch')
+
+
+def check_wall(wall_x: torch.Tensor, wall_ptr: torch.Tensor, B: int, name: str = 'wall'):
+    """The values of wall_ptr [B+1]: 0 first, ascending, n_wall last -- the kernels read the rows it names.  One host read; call it
+    once per batch (`GuidanceContext` does), not per step."""
+    if not (isinstance(wall_ptr, torch.Tensor) and wall_ptr.dim() == 1 and wall_ptr.shape[0] == B + 1 and
+            not wall_ptr.dtype.is_floating_point):
+        raise KpdError(f'{name}: wall_ptr must be an integer [{B + 1}] tensor (the wall does not fit the batch of {B} complexes)')
+    if not (isinstance(wall_x, torch.Tensor) and wall_x.dim() == 2 and wall_x.shape[1] == 3):
+        raise KpdError(f'{name}: wall_x must be [n_wall, 3] (got {tuple(getattr(wall_x, "shape", ()))})')
+    p = wall_ptr.detach().cpu().long()
+    if int(p[0]) != 0 or int(p[-1]) != wall_x.shape[0] or bool((p[1:] < p[:-1]).any()):
+        raise KpdError(f'{name}: wall_ptr must ascend from 0 to n_wall = {wall_x.shape[0]} (got {p.tolist()[:8]}{"..." if B > 7 else ""})')
+
+
+_walls_seen = {}          # (wall_ptr storage, version, n_wall) -> the tensor (held, so its address cannot be recycled)
+
+
+def _wall_values_once(wall_x, wall_ptr, B, name):
+    """`check_wall` the first time this wall_ptr tensor is seen, nothing afterwards: the values are read on the host once per
+    batch, not per step (a step inside a graph capture never reads them: the capture's warm-up steps did)."""
+    key = (wall_ptr.data_ptr(), wall_ptr._version, int(wall_x.shape[0]), B)
+    if key not in _walls_seen:
+        check_wall(wall_x, wall_ptr, B, name)
+        if len(_walls_seen) >= 16:
+            _walls_seen.pop(next(iter(_walls_seen)))
+        _walls_seen[key] = wall_ptr
+
+
+def sample_update_guided(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h, coef9, wall_x, wall_ptr,
+                         kp_com0, threshold, fixed=None, known_x=None, known_h=None, known_noise_x=None, known_noise_h=None):
+    """In-place guided reverse-diffusion update + ligand-COM removal (kpd_sample_update_guided; include/kpd.h, "Clash guidance",
+    states the algorithm).  wall_x [n_wall,3] in the input frame, wall_ptr [B+1] int32 (its values are checked the first time the tensor is seen),
+    kp_com0 [B,3]; `fixed` and the four known-part tensors: all None, or the inpainting arguments of `sample_update_inpaint`."""
+    masked = fixed is not None
+    inp = (known_x, known_h, known_noise_x, known_noise_h)
+    if any((a is not None) != masked for a in inp):
+        raise KpdError('sample_update_guided: fixed, known_x, known_h, known_noise_x and known_noise_h go together (all or none)')
+    per_x = (eps_x, noise_x) + ((known_x, known_noise_x) if masked else ())
+    per_h = (eps_h, noise_h) + ((known_h, known_noise_h) if masked else ())
+    per_x, per_h, coef9 = _update_args('sample_update_guided', pb, atom_nf, lig_x, lig_h, kp_x, per_x, per_h, coef9, 9)
+    if masked:
+        if not (fixed.is_cuda and fixed.dtype in (torch.bool, torch.uint8) and fixed.shape == (pb.n_lig,)):
+            raise KpdError('fixed must be a bool or uint8 GPU tensor with one entry per ligand atom')
+        fixed = fixed.contiguous().view(torch.uint8) if fixed.dtype == torch.bool else fixed.contiguous()
+    else:
+        per_x, per_h = per_x + [None, None], per_h + [None, None]
+    _wall_args('sample_update_guided', wall_x, wall_ptr, pb.B)
+    _wall_values_once(wall_x, wall_ptr, pb.B, 'sample_update_guided')
+    kp_com0 = _dev_f32(kp_com0, 'kp_com0')
+    if kp_com0.shape != (pb.B, 3):
+        raise KpdError(f'kp_com0 must be [{pb.B}, 3] (got {tuple(kp_com0.shape)})')
+    if not float(threshold) > 0.0:
+        raise KpdError(f'sample_update_guided: threshold must be positive (got {threshold!r})')
+    check(lib().kpd_sample_update_guided(pb.B, _ptr(pb.lig_ptr), _ptr(pb.kp_ptr), int(atom_nf), _ptr(lig_x), _ptr(lig_h), _ptr(kp_x),
+                                         _ptr(per_x[0]), _ptr(per_h[0]), _ptr(per_x[1]), _ptr(per_h[1]), _ptr(coef9), _ptr(fixed),
+                                         _ptr(per_x[2]), _ptr(per_h[2]), _ptr(kp_com0), _ptr(per_x[3]), _ptr(per_h[3]),
+                                         _ptr(wall_ptr), _ptr(wall_x), float(threshold), pb.max_lig, _stream()))
+
+
+def clash_score(lig_x: torch.Tensor, lig_ptr: torch.Tensor, wall_x: torch.Tensor, wall_ptr: torch.Tensor, threshold: float) -> torch.Tensor:
+    """[B,3] = per complex {1/2 sum (threshold - d)+^2, pairs with d < threshold, smallest such d or +inf} between the ligand rows
+    [lig_ptr[b], lig_ptr[b+1]) of lig_x and the wall rows of wall_x, both in one frame (kpd_clash_score): the report to rank or
+    filter samples by.  fp32 GPU positions, int32 GPU offsets [B+1]."""
+    if not (isinstance(lig_ptr, torch.Tensor) and lig_ptr.dim() == 1 and lig_ptr.shape[0] >= 2):
+        raise KpdError('clash_score: lig_ptr must be a 1-D tensor of B + 1 offsets')
+    B = lig_ptr.shape[0] - 1
+    _wall_args('clash_score', wall_x, wall_ptr, B)
+    _wall_args('clash_score (ligand side)', lig_x, lig_ptr, B)
+    check_wall(wall_x, wall_ptr, B, 'clash_score')
+    check_wall(lig_x, lig_ptr, B, 'clash_score (ligand side)')
+    if not float(threshold) > 0.0:
+        raise KpdError(f'clash_score: threshold must be positive (got {threshold!r})')
+    out = torch.empty(B, 3, device=lig_x.device, dtype=torch.float32)
+    check(lib().kpd_clash_score(B, _ptr(lig_ptr), _ptr(lig_x), _ptr(wall_ptr), _ptr(wall_x), float(threshold), _ptr(out), _stream()))
+    return out

@@ -92,11 +92,51 @@ class InpaintContext:
         self.x, self.h, self.kp_com0 = x.float().contiguous(), h.float().contiguous(), kp_com0.float().contiguous()
 
 
+class ClashGuidance:
+    """Clash guidance as the caller asks for it (include/kpd.h, "Clash guidance"): push the denoised ligand positions out of the
+    `threshold` Angstrom spheres around the wall atoms at every reverse step with t <= `t_max`, `scale` = 1 moving a single contact
+    exactly onto its sphere.  `wall`: None, or the atoms to stay away from in the form the entry point documents -- one [m_i,3]
+    tensor per pocket for `_sample` and its callers (None: each pocket's receptor atoms as given), `(wall_x [n_wall,3],
+    wall_ptr [B+1])` for `sample_from_encoded_receptors` / `inpaint_from_encoded_receptors` (None: the `rec` rows of the batch when
+    it has any, else its keypoints).  A C-alpha model sees one atom per residue: hand it the full-atom pocket explicitly."""
+
+    def __init__(self, threshold: float, scale: float = 1.0, t_max: float = 1.0, wall=None):
+        for name, v in (('threshold', threshold), ('scale', scale), ('t_max', t_max)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float('inf'), float('-inf')):
+                raise ValueError(f'{name} must be a finite number (got {v!r})')
+        if not threshold > 0:
+            raise ValueError(f'threshold must be positive, in Angstrom (got {threshold!r})')
+        if not scale >= 0:
+            raise ValueError(f'scale must be >= 0 (got {scale!r})')
+        if not 0 < t_max <= 1:
+            raise ValueError(f't_max must lie in (0, 1] (got {t_max!r})')
+        self.threshold, self.scale, self.t_max, self.wall = float(threshold), float(scale), float(t_max), wall
+
+    def with_wall(self, wall) -> 'ClashGuidance':
+        return ClashGuidance(self.threshold, self.scale, self.t_max, wall)
+
+
+class GuidanceContext:
+    """What a guided step needs besides the state: `wall_x` [n_wall,3] in the input (receptor) frame, `wall_ptr` [B+1] offsets
+    per complex (0 first, ascending, n_wall last: read once here, the kernel trusts it), `kp_com0` [B,3] keypoint mean in the
+    input frame, and the numbers of a `ClashGuidance`."""
+
+    def __init__(self, wall_x: torch.Tensor, wall_ptr: torch.Tensor, kp_com0: torch.Tensor, threshold: float, scale: float = 1.0,
+                 t_max: float = 1.0):
+        c = ClashGuidance(threshold, scale, t_max)
+        self.threshold, self.scale, self.t_max = c.threshold, c.scale, c.t_max
+        if not (isinstance(kp_com0, torch.Tensor) and kp_com0.dim() == 2 and kp_com0.shape[1] == 3):
+            raise ValueError(f'guidance: kp_com0 must be [B, 3] (got {tuple(getattr(kp_com0, "shape", ()))})')
+        hip.check_wall(wall_x, wall_ptr, kp_com0.shape[0], 'guidance')
+        self.wall_x, self.wall_ptr = wall_x.float().contiguous(), wall_ptr.int().contiguous()
+        self.kp_com0 = kp_com0.float().contiguous()
+
+
 class StepGraph:
     """A captured reverse step.  `step(s, t)` writes the two scalars into static device buffers and replays the graph;
     the graph holds the denoiser forward (graph build included), the noise draw and the in-place z_s update."""
 
-    def __init__(self, model: 'KeypointDiffusion', g, bidx=None, noise=None, inpaint=None):
+    def __init__(self, model: 'KeypointDiffusion', g, bidx=None, noise=None, inpaint=None, guidance=None):
         dev, B = g.device, g.batch_size
         if dev.type != 'cuda':
             raise hip.KpdError('a step graph needs the batch on the GPU')
@@ -110,6 +150,8 @@ class StepGraph:
         T = model.n_timesteps
         self.s.fill_((T - 1) / T)
         kw = {} if inpaint is None else {'inpaint': inpaint}          # the plain step is called exactly as before
+        if guidance is not None:
+            kw['guidance'] = guidance
         # warm-up outside capture (workspace reservation, first-use initialisation), on a side stream as capture requires
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -122,7 +164,7 @@ class StepGraph:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             model.sample_p_zs_given_zt(self.s, self.t, g, bidx, noise=noise, **kw)
-        self._keep = (g, noise, inpaint)
+        self._keep = (g, noise, inpaint, guidance)
         # The captured kernels hold raw pointers into the engine's workspace arena and packed weights.  Holding the engine
         # object keeps both allocations alive even if the module builds a new engine; the pin records what must not have
         # changed for a replay to mean "one reverse step of this model": the arena (a larger batch re-reserves it, which
@@ -342,6 +384,20 @@ class KeypointDiffusion(nn.Module):
         return torch.cat([self.step_coefficients(s, t), torch.stack([self.alpha(g_s), self.sigma(g_s), sigma_ts], dim=1)],
                          dim=1).contiguous()
 
+    def guided_coefficients(self, s: torch.Tensor, t: torch.Tensor, scale: float = 1.0, t_max: float = 1.0) -> torch.Tensor:
+        """[B,9] = the six columns of `inpaint_coefficients`, bit for bit, then alpha_t, sigma_t and the guidance weight
+        w = scale alpha_s sigma^2_t|s / sigma_t^2 for round(t T) <= round(t_max T), 0 above (include/kpd.h, "Clash guidance").  One
+        kernel on the GPU (kpd_guided_coefficients), the torch mirror on host tensors."""
+        c = ClashGuidance(1.0, scale, t_max)
+        if s.is_cuda:
+            return hip.guided_coefficients(self.gamma.gamma, s, t, c.scale, c.t_max)
+        g_s, g_t = self.gamma(s), self.gamma(t)
+        sigma2_ts, _, _ = self.sigma_and_alpha_t_given_s(g_t, g_s)
+        T = self.n_timesteps
+        on = torch.round(t * T) <= torch.round(torch.tensor(c.t_max, dtype=t.dtype) * T)
+        w = torch.where(on, c.scale * self.alpha(g_s) * sigma2_ts / torch.sigmoid(g_t), torch.zeros_like(g_t))
+        return torch.cat([self.inpaint_coefficients(s, t), torch.stack([self.alpha(g_t), self.sigma(g_t), w], dim=1)], dim=1).contiguous()
+
     def use_complex_noise(self, seed):
         """Opt in to sharding-invariant noise: every draw of the sampler becomes a function of (seed, complex id, timestep,
         position in the complex) (kpd_complex_noise), so a run split over ranks reproduces the single-process run.
@@ -354,17 +410,22 @@ class KeypointDiffusion(nn.Module):
             return torch.randn(g.num_nodes('lig'), width, device=g.device)
         return hip.complex_noise(g.prepared(), width, complex_ids, self._noise_seed, step, tag)
 
-    def sample_p_zs_given_zt(self, s, t, g, batch_idxs=None, noise=None, complex_ids=None, step=0, inpaint=None, repetition=0):
+    def sample_p_zs_given_zt(self, s, t, g, batch_idxs=None, noise=None, complex_ids=None, step=0, inpaint=None, repetition=0,
+                             guidance=None):
         """One reverse step (ligand_diffuser.py:497-538).  `noise` = (pos_noise, feat_noise) may be
         injected for reproducible parity tests; by default it is drawn with torch.randn as upstream
         (or per complex, `use_complex_noise`, when `complex_ids` [B] int64 and the integer `step` are given).
         `inpaint` (an `InpaintContext`): the step around fixed atoms (kpd_sample_update_inpaint); `noise` may then be the 4-tuple
         (pos_noise, feat_noise, known_pos_noise, known_feat_noise), and `repetition` u selects the tags 6u .. 6u + 3 of the
-        per-complex streams.  With `inpaint=None` nothing differs from the plain step."""
+        per-complex streams.  With `inpaint=None` nothing differs from the plain step.
+        `guidance` (a `GuidanceContext`: the prepared wall and `kp_com0`): the step with the clash shift (kpd_sample_update_guided),
+        alone or together with `inpaint`; it draws what the step without it draws.  With `guidance=None` nothing differs."""
         lig, kp = g.nodes['lig'].data, g.nodes['kp'].data
         for d, k in ((lig, 'x_0'), (lig, 'h_0'), (kp, 'x_0')):
             if not (d[k].is_contiguous() and d[k].dtype == torch.float32):
                 d[k] = d[k].contiguous().float()
+        if guidance is not None:
+            return self._guided_step(s, t, g, batch_idxs, noise, complex_ids, step, inpaint, repetition, guidance)
         if inpaint is not None:
             return self._inpaint_step(s, t, g, batch_idxs, noise, complex_ids, step, inpaint, repetition)
         coef = self.step_coefficients(s, t)
@@ -389,6 +450,80 @@ class KeypointDiffusion(nn.Module):
                                   noise[1], coef, inpaint.fixed, inpaint.x, inpaint.h, inpaint.kp_com0, noise[2], noise[3])
         return g
 
+    def _guided_step(self, s, t, g, batch_idxs, noise, complex_ids, step, inpaint, repetition, guidance):
+        if not isinstance(guidance, GuidanceContext):
+            raise ValueError(f'guidance must be a GuidanceContext (the prepared wall and kp_com0), got {type(guidance).__name__}')
+        if g.device.type != 'cuda':
+            raise hip.KpdError(f'a guided step needs the batch on the GPU (got {g.device}); there is no CPU implementation')
+        lig, kp = g.nodes['lig'].data, g.nodes['kp'].data
+        coef = self.guided_coefficients(s, t, guidance.scale, guidance.t_max)
+        eps_h, eps_x = self.dynamics(g, t, batch_idxs)
+        noise = tuple(noise) if noise is not None else ()
+        F = lig['h_0'].shape[1]
+        if inpaint is None:                          # the draws of the plain step: tags 0 and 1
+            if len(noise) not in (0, 2):
+                raise ValueError('noise must be (pos, feat)')
+            if not noise:
+                noise = (self._draw(g, 3, complex_ids, step, 0), self._draw(g, F, complex_ids, step, 1))
+            known = {}
+        else:                                        # the draws of the inpainting step
+            if len(noise) not in (0, 2, 4):
+                raise ValueError('noise must be (pos, feat) or (pos, feat, known_pos, known_feat)')
+            for tag in range(len(noise), 4):
+                noise += (self._draw(g, 3 if tag % 2 == 0 else F, complex_ids, step, 6 * repetition + tag),)
+            known = dict(fixed=inpaint.fixed, known_x=inpaint.x, known_h=inpaint.h, known_noise_x=noise[2], known_noise_h=noise[3])
+        hip.sample_update_guided(g.prepared(), self.n_lig_features, lig['x_0'], lig['h_0'], kp['x_0'], eps_x, eps_h, noise[0], noise[1],
+                                 coef, guidance.wall_x, guidance.wall_ptr, guidance.kp_com0, guidance.threshold, **known)
+        return g
+
+    def resolve_wall(self, g, wall=None):
+        """(wall_x [n_wall,3] fp32, wall_ptr [B+1] int32) on g's device for a batch of encoded pockets, before the loop moves it.
+        `wall=None`: the `rec` rows of `g` when it has any (for the fixed encoder these are the atoms the keypoints were taken
+        from), else its `kp` rows; otherwise `wall` is `(wall_x, wall_ptr)` in the input frame and is checked against the batch."""
+        B = g.batch_size
+        if wall is None:
+            nt = 'rec' if g.num_nodes('rec') > 0 else 'kp'
+            wall_x, wall_ptr = g.nodes[nt].data['x_0'].float().clone(), g.node_ptr(nt)
+        else:
+            if not (isinstance(wall, (tuple, list)) and len(wall) == 2):
+                raise ValueError('guidance.wall must be None or (wall_x [n_wall,3], wall_ptr [B+1]) for a batch of encoded pockets')
+            wall_x, wall_ptr = torch.as_tensor(wall[0]), torch.as_tensor(wall[1])
+            hip.check_wall(wall_x, wall_ptr, B, 'guidance.wall')
+        return wall_x.float().to(g.device).contiguous(), wall_ptr.to(g.device).int().contiguous()
+
+    def resolve_pocket_walls(self, ref_graphs, wall=None):
+        """One [m_i,3] fp32 tensor per pocket, in that pocket's frame: `wall=None` takes each pocket's receptor atoms as given
+        (`rec` `x_0` of `ref_graphs[i]`, before encoding); otherwise `wall` is one tensor per pocket."""
+        if wall is None:
+            return [r.nodes['rec'].data['x_0'].float() for r in ref_graphs]
+        if not isinstance(wall, (list, tuple)) or len(wall) != len(ref_graphs):
+            raise ValueError(f'guidance.wall must have one [m,3] tensor per pocket ({len(ref_graphs)}), got '
+                             f'{len(wall) if isinstance(wall, (list, tuple)) else type(wall).__name__}')
+        wall = [torch.as_tensor(w).float() for w in wall]
+        for i, w in enumerate(wall):
+            if w.dim() != 2 or w.shape[1] != 3:
+                raise ValueError(f'guidance.wall[{i}] must be [m, 3] (got {tuple(w.shape)})')
+        return wall
+
+    def clash_score(self, positions, wall, threshold: float) -> torch.Tensor:
+        """[n,3] = per ligand {1/2 sum (threshold - d)+^2, pairs with d < threshold, smallest such d or +inf} (kpd_clash_score):
+        `positions` is a list of [n_i,3] tensors as the samplers return them, `wall` one [m,3] tensor for all of them or a list
+        with one per ligand, in the same frame.  Runs on the GPU the model lives on; the result comes back on the host."""
+        positions = [torch.as_tensor(p).float() for p in positions]
+        wall = [torch.as_tensor(wall).float()] * len(positions) if isinstance(wall, torch.Tensor) else [torch.as_tensor(w).float() for w in wall]
+        if len(wall) != len(positions) or not positions:
+            raise ValueError(f'clash_score: {len(positions)} ligands but {len(wall)} walls')
+        for name, ts in (('positions', positions), ('wall', wall)):
+            for i, p in enumerate(ts):
+                if p.dim() != 2 or p.shape[1] != 3:
+                    raise ValueError(f'clash_score: {name}[{i}] must be [n, 3] (got {tuple(p.shape)})')
+        dev = next(self.parameters()).device
+        if dev.type != 'cuda':
+            raise hip.KpdError(f'clash_score runs on the GPU (the model lives on {dev}); there is no CPU implementation')
+        ptr = lambda ts: torch.tensor([0] + [p.shape[0] for p in ts]).cumsum(0).int().to(dev)
+        return hip.clash_score(torch.cat(positions).to(dev).contiguous(), ptr(positions), torch.cat(wall).to(dev).contiguous(), ptr(wall),
+                               ClashGuidance(threshold).threshold).cpu()
+
     def renoise_zt_given_zs(self, s, t, g, noise=None, complex_ids=None, step=0, repetition=0):
         """The forward move between two repetitions of a resampled inpainting step: z_t = alpha_t|s z_s + sigma_t|s n for the
         ligand positions and features, then ligand-COM removal (kpd_sample_renoise).  Tags 6u + 4, 6u + 5 of the per-complex
@@ -402,33 +537,48 @@ class KeypointDiffusion(nn.Module):
         return g
 
     @torch.no_grad()
-    def capture_step(self, g, bidx=None, noise=None, inpaint=None) -> 'StepGraph':
+    def capture_step(self, g, bidx=None, noise=None, inpaint=None, guidance=None) -> 'StepGraph':
         """One reverse step (`sample_p_zs_given_zt`) captured as a HIP graph for this batch: replaying it costs one
         launch instead of ~30.  The step's kernels take shapes from host-known capacities and counts from device memory,
         so the same graph serves every timestep.  Measured gain is small (B = 1: 0.99 -> 0.96 ms/step, B = 64: 8.32 ->
         8.29): the step is bound by its chain of dependent kernels, not by launch overhead."""
-        return StepGraph(self, g, bidx, noise, inpaint)
+        if guidance is None:
+            return StepGraph(self, g, bidx, noise, inpaint)
+        return StepGraph(self, g, bidx, noise, inpaint, guidance)
 
     @torch.no_grad()
     def sample_from_encoded_receptors(self, g, visualize=False, init_lig_pos: torch.Tensor = None, complex_ids=None,
-                                      use_graph: Optional[bool] = None):
+                                      use_graph: Optional[bool] = None, guidance: Optional[ClashGuidance] = None):
         """Full reverse loop for a batch of encoded pockets (ligand_diffuser.py:342-469).  `complex_ids` [B] int64
         (global index of every complex in the job) selects the per-complex noise streams of `use_complex_noise`.
         `use_graph=True`: replay the reverse step as a captured HIP graph (not with the per-complex noise streams, which
-        take the timestep as a launch argument); the default is the eager step, the measured difference is ≤ 3 %."""
-        return self._reverse_loop(g, visualize, init_lig_pos, complex_ids, use_graph)
+        take the timestep as a launch argument); the default is the eager step, the measured difference is ≤ 3 %.
+        `guidance` (a `ClashGuidance`): every step pushes the denoised positions out of the wall atoms (`resolve_wall` says
+        which); GPU batches only.  With `guidance=None` the loop is call for call what it was."""
+        if guidance is None:
+            return self._reverse_loop(g, visualize, init_lig_pos, complex_ids, use_graph)
+        return self._reverse_loop(g, visualize, init_lig_pos, complex_ids, use_graph, guidance=self._checked_guidance(g, guidance))
+
+    @staticmethod
+    def _checked_guidance(g, guidance):
+        if not isinstance(guidance, ClashGuidance):
+            raise ValueError(f'guidance must be a ClashGuidance (got {type(guidance).__name__})')
+        if g.device.type != 'cuda':
+            raise hip.KpdError(f'guided sampling needs the batch on the GPU (got {g.device}); there is no CPU implementation')
+        return guidance
 
     @torch.no_grad()
     def inpaint_from_encoded_receptors(self, g, fixed: torch.Tensor, resamplings: int = 1, visualize=False,
                                        init_lig_pos: torch.Tensor = None, complex_ids=None, use_graph: Optional[bool] = None,
-                                       overwrite_fixed: bool = True):
+                                       overwrite_fixed: bool = True, guidance: Optional[ClashGuidance] = None):
         """The reverse loop around fixed atoms (RePaint-style replacement conditioning; include/kpd.h, "Inpainting").  `fixed`
         [n_lig] bool / uint8 marks the given ligand atoms; their known positions (input frame) and features are the ligand rows
         of `g`, the other rows are generated.  Every timestep is run `resamplings` times with a forward move back to t in between
         (r T denoiser forwards in all).  `overwrite_fixed`: return the fixed rows as the caller's values bit for bit; otherwise
         they come back as the loop leaves them, X + (alpha_0 - 1) k0 + sigma_0 n'.  Without `init_lig_pos` a complex with fixed
         atoms starts in the frame of the mean of its known positions.  `use_graph=True` is available for `resamplings == 1` with
-        the global noise.  Returns what `sample_from_encoded_receptors` returns."""
+        the global noise.  `guidance` (a `ClashGuidance`): the free atoms are also pushed out of the wall atoms; the fixed atoms
+        are neither pushed nor part of the wall.  Returns what `sample_from_encoded_receptors` returns."""
         n_lig = g.num_nodes('lig')
         if not (isinstance(fixed, torch.Tensor) and fixed.dtype in (torch.bool, torch.uint8)):
             raise ValueError(f'fixed must be a bool or uint8 tensor (got {getattr(fixed, "dtype", type(fixed).__name__)})')
@@ -441,10 +591,12 @@ class KeypointDiffusion(nn.Module):
             raise ValueError(f"the ligand features of g (h_0) must have atom_nf = {self.n_lig_features} columns (got {width})")
         if g.device.type != 'cuda':
             raise hip.KpdError(f'inpaint_from_encoded_receptors: g must live on the GPU (got {g.device}); there is no CPU implementation')
+        kw = {} if guidance is None else {'guidance': self._checked_guidance(g, guidance)}
         return self._reverse_loop(g, visualize, init_lig_pos, complex_ids, use_graph, fixed=fixed.to(g.device),
-                                  resamplings=resamplings, overwrite_fixed=overwrite_fixed)
+                                  resamplings=resamplings, overwrite_fixed=overwrite_fixed, **kw)
 
-    def _reverse_loop(self, g, visualize, init_lig_pos, complex_ids, use_graph, fixed=None, resamplings=1, overwrite_fixed=True):
+    def _reverse_loop(self, g, visualize, init_lig_pos, complex_ids, use_graph, fixed=None, resamplings=1, overwrite_fixed=True,
+                      guidance=None):
         """The loop behind `sample_from_encoded_receptors` (fixed is None: the plain sampler, call for call as upstream) and
         `inpaint_from_encoded_receptors`.  The per-complex means of the set-up and of the frame restoration are summed in a fixed
         order (`G.segment_sum_ordered`): with the per-complex noise streams a run is then a function of its inputs and the seed,
@@ -453,7 +605,10 @@ class KeypointDiffusion(nn.Module):
         init_kp_com = G.readout_nodes(g, feat='x_0', op='mean', ntype='kp', ordered=True)
         bidx = G.get_batch_idxs(g)
         lig_b, kp_b = bidx['lig'], bidx['kp']
-        ctx = None
+        ctx, gkw = None, {}
+        if guidance is not None:         # the wall in the input frame, before anything moves; every call below gets it as a keyword
+            gkw = {'guidance': GuidanceContext(*self.resolve_wall(g, guidance.wall), init_kp_com, guidance.threshold, guidance.scale,
+                                               guidance.t_max)}
         if fixed is not None:
             fixed = fixed.bool()
             known_x, known_h = g.nodes['lig'].data['x_0'].float().clone(), g.nodes['lig'].data['h_0'].float().clone()
@@ -495,19 +650,19 @@ class KeypointDiffusion(nn.Module):
         if use_graph and resamplings != 1:
             raise ValueError('use_graph=True needs resamplings == 1 (the forward move between repetitions is not part of the captured step)')
         if ctx is None:
-            step_graph = self.capture_step(g, bidx) if use_graph else None
+            step_graph = self.capture_step(g, bidx, **gkw) if use_graph else None
         else:
-            step_graph = self.capture_step(g, bidx, inpaint=ctx) if use_graph else None
+            step_graph = self.capture_step(g, bidx, inpaint=ctx, **gkw) if use_graph else None
         for s in reversed(range(self.n_timesteps)):
             if step_graph is not None:
                 step_graph.step(s / self.n_timesteps, (s + 1) / self.n_timesteps)
             elif ctx is None:
                 g = self.sample_p_zs_given_zt(ones * (s / self.n_timesteps), ones * ((s + 1) / self.n_timesteps), g, bidx,
-                                              complex_ids=complex_ids, step=s)
+                                              complex_ids=complex_ids, step=s, **gkw)
             else:
                 s_, t_ = ones * (s / self.n_timesteps), ones * ((s + 1) / self.n_timesteps)
                 for u in range(resamplings):
-                    g = self.sample_p_zs_given_zt(s_, t_, g, bidx, complex_ids=complex_ids, step=s, inpaint=ctx, repetition=u)
+                    g = self.sample_p_zs_given_zt(s_, t_, g, bidx, complex_ids=complex_ids, step=s, inpaint=ctx, repetition=u, **gkw)
                     if u + 1 < resamplings:
                         g = self.renoise_zt_given_zs(s_, t_, g, complex_ids=complex_ids, step=s, repetition=u)
             if visualize:
@@ -533,12 +688,16 @@ class KeypointDiffusion(nn.Module):
     @torch.no_grad()
     def _sample(self, ref_graphs: List[G.HeteroBatch], n_lig_atoms: List[List[int]], rec_enc_batch_size: int = 32,
                 diff_batch_size: int = 32, visualize=False, use_ref_lig_com: bool = False, group=None, known=None,
-                resamplings: int = 1):
+                resamplings: int = 1, guidance: Optional[ClashGuidance] = None):
         """Several pockets x several ligands per pocket (ligand_diffuser.py:271-340).
 
         `known` (inpainting): one entry per pocket, None or (pos [m_i,3] in the pocket's frame, feat [m_i,atom_nf]); these atoms
         are rows 0 .. m_i - 1 of every ligand generated for pocket i and are held fixed, the other rows are generated
         (`inpaint_from_encoded_receptors`, with `resamplings`).
+
+        `guidance` (a `ClashGuidance`): clash guidance in every reverse step; its `wall` is None (each pocket's receptor atoms as
+        given in `ref_graphs[i]`, before encoding) or one [m_i,3] tensor per pocket in that pocket's frame.  A C-alpha model
+        should be handed the full-atom pocket here.  Every complex carries its pocket's wall, so sharding changes nothing.
 
         The flat list of (pocket, replicate) complexes it builds (:292-313) is the unit of multi-GPU work:
         when a `torch.distributed` process group with more than one rank is initialised, every rank calls this with the SAME
@@ -557,6 +716,9 @@ class KeypointDiffusion(nn.Module):
         device = ref_graphs[0].device
         if isinstance(resamplings, bool) or not isinstance(resamplings, int) or resamplings < 1:
             raise ValueError(f'resamplings must be an integer >= 1 (got {resamplings!r})')
+        walls = None
+        if guidance is not None:
+            walls = [w.to(device) for w in self.resolve_pocket_walls(ref_graphs, self._checked_guidance(ref_graphs[0], guidance).wall)]
         if known is not None:
             if len(known) != len(ref_graphs):
                 raise ValueError(f'known must have one entry per pocket ({len(ref_graphs)}), got {len(known)}')
@@ -597,12 +759,17 @@ class KeypointDiffusion(nn.Module):
                 bg = G.batch(graphs[lo:lo + diff_batch_size])
                 init = G.readout_nodes(bg, feat='x_0', op='mean', ntype='lig') if use_ref_lig_com else None
                 ids = torch.arange(mine[lo], mine[lo] + bg.batch_size, dtype=torch.long)
+                gkw = {}
+                if walls is not None:
+                    ws = [walls[flat[c][0]] for c in mine[lo:lo + bg.batch_size]]
+                    wptr = torch.tensor([0] + [w.shape[0] for w in ws]).cumsum(0)
+                    gkw = {'guidance': guidance.with_wall((torch.cat(ws), wptr))}
                 if known is None:
-                    p, f = self.sample_from_encoded_receptors(bg, visualize=visualize, init_lig_pos=init, complex_ids=ids)
+                    p, f = self.sample_from_encoded_receptors(bg, visualize=visualize, init_lig_pos=init, complex_ids=ids, **gkw)
                 else:
                     fixed = bg.nodes['lig'].data.pop('_fixed')
                     p, f = self.inpaint_from_encoded_receptors(bg, fixed, resamplings=resamplings, visualize=visualize,
-                                                               init_lig_pos=init, complex_ids=ids)
+                                                               init_lig_pos=init, complex_ids=ids, **gkw)
                 pos.extend(p), feat.extend(f)
             return pos, feat
 
@@ -626,16 +793,19 @@ class KeypointDiffusion(nn.Module):
 
     @torch.no_grad()
     def sample_given_pocket(self, rec_graph, n_lig_atoms: torch.Tensor, rec_enc_batch_size: int = 32,
-                            diff_batch_size: int = 32, visualize=False):
+                            diff_batch_size: int = 32, visualize=False, guidance: Optional[ClashGuidance] = None):
+        """`guidance.wall`: None (the pocket's receptor atoms) or one [m,3] tensor in the pocket's frame."""
+        kw = {} if guidance is None else {'guidance': self._one_pocket(guidance)}
         s = self._sample([rec_graph], n_lig_atoms=[n_lig_atoms.tolist()], rec_enc_batch_size=rec_enc_batch_size,
-                         diff_batch_size=diff_batch_size, visualize=visualize)
+                         diff_batch_size=diff_batch_size, visualize=visualize, **kw)
         return s[0]['positions'], s[0]['features']
 
     @torch.no_grad()
     def inpaint_given_pocket(self, rec_graph, known_pos: torch.Tensor, known_feat: torch.Tensor, n_lig_atoms: torch.Tensor,
-                             rec_enc_batch_size: int = 32, diff_batch_size: int = 32, resamplings: int = 1, visualize=False):
+                             rec_enc_batch_size: int = 32, diff_batch_size: int = 32, resamplings: int = 1, visualize=False,
+                             guidance: Optional[ClashGuidance] = None):
         """Ligands of the sizes `n_lig_atoms` for one pocket, grown around the known atoms: `known_pos` [m,3] (the pocket's
-        frame) and `known_feat` [m,atom_nf] come back as rows 0 .. m - 1 of every ligand."""
+        frame) and `known_feat` [m,atom_nf] come back as rows 0 .. m - 1 of every ligand.  `guidance` as in `sample_given_pocket`."""
         known_pos, known_feat = torch.as_tensor(known_pos), torch.as_tensor(known_feat)
         if known_pos.dim() != 2 or known_pos.shape[1] != 3:
             raise ValueError(f'known_pos must be [m, 3] (got {tuple(known_pos.shape)})')
@@ -643,18 +813,25 @@ class KeypointDiffusion(nn.Module):
             raise ValueError(f'known_feat must be [{known_pos.shape[0]}, atom_nf = {self.n_lig_features}] (got {tuple(known_feat.shape)})')
         s = self._sample([rec_graph], n_lig_atoms=[torch.as_tensor(n_lig_atoms).tolist()], rec_enc_batch_size=rec_enc_batch_size,
                          diff_batch_size=diff_batch_size, visualize=visualize, known=[(known_pos, known_feat)],
-                         resamplings=resamplings)
+                         resamplings=resamplings, **({} if guidance is None else {'guidance': self._one_pocket(guidance)}))
         return s[0]['positions'], s[0]['features']
+
+    @staticmethod
+    def _one_pocket(guidance):
+        """The single-pocket entry points take the wall as one tensor; `_sample` takes one per pocket."""
+        if not isinstance(guidance, ClashGuidance):
+            raise ValueError(f'guidance must be a ClashGuidance (got {type(guidance).__name__})')
+        return guidance if guidance.wall is None else guidance.with_wall([guidance.wall])
 
     @torch.no_grad()
     def sample_random_sizes(self, ref_graphs, n_replicates: int = 10, rec_enc_batch_size: int = 32,
-                            diff_batch_size: int = 32):
+                            diff_batch_size: int = 32, guidance: Optional[ClashGuidance] = None):
         if self.lig_size_dist is None:
             raise ValueError('no processed_dataset_dir was given: the ligand-size prior is unavailable')
         n_rec = torch.tensor([g.num_nodes('rec') for g in ref_graphs])
         n_lig = self.lig_size_dist.sample(n_rec, n_replicates)
         return self._sample(ref_graphs, n_lig_atoms=n_lig.tolist(), rec_enc_batch_size=rec_enc_batch_size,
-                            diff_batch_size=diff_batch_size)
+                            diff_batch_size=diff_batch_size, **({} if guidance is None else {'guidance': guidance}))
 
 
 LigandDiffuser = KeypointDiffusion
