@@ -111,7 +111,7 @@ __global__ void k_meta_single(int et, const int *__restrict__ count_dev, int cou
 }
 
 // message_norm == 0: z[b] = edges into the graph's dst nodes / number of dst nodes  (no +1 here:
-// receptor_encoder_gvp.py:245-246, 268-269)
+// receptor_encoder_gvp.py:245-246, 268-269; receptor_encoder.py:505-509)
 __global__ void k_z_indegree(const int *__restrict__ rowptr, const int *__restrict__ ptr, int B, float *__restrict__ z) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) z[b] = (float)(rowptr[ptr[b + 1]] - rowptr[ptr[b]]) / (float)(ptr[b + 1] - ptr[b]);
@@ -232,6 +232,85 @@ __global__ __launch_bounds__(256) void k_kp_attention(const float *__restrict__ 
     if (tid < 3) kp_x[(size_t)kp * 3 + tid] = s_part[0][1 + tid] / s_part[0][0];
 }
 
+// The training engines' attention pooling with kept weights (KeypointInitializer, receptor_encoder_gvp.py:57-87; RecKeyConv,
+// receptor_encoder.py:188-222): one workgroup per keypoint over the receptor atoms of its graph, their positions in rec_x.
+// Not k_kp_attention: this one multiplies by the reciprocal of the sum and scales by the row width S.
+// w[r * K + k] = exp(<ft_src[r], ft_dst[kp]> / sqrt(S)) / sum over the graph (no max-subtraction, as upstream); kp_x = sum w x_r
+__global__ __launch_bounds__(256) void k_att_fwd(const float *__restrict__ ft_src, const float *__restrict__ ft_dst, const float *__restrict__ rec_x,
+                                                 const int *__restrict__ rec_ptr, int K, int S, float *__restrict__ w, float *__restrict__ kp_x) {
+    __shared__ float s_q[256];
+    __shared__ float s_part[256][4];
+    const int kp = blockIdx.x, g = kp / K, k = kp - g * K, tid = threadIdx.x;
+    if (tid < S) s_q[tid] = ft_dst[(size_t)kp * S + tid];
+    __syncthreads();
+    const float scale = 1.0f / sqrtf((float)S);
+    float a_sum = 0.f, ax = 0.f, ay = 0.f, az = 0.f;
+    for (int r = rec_ptr[g] + tid; r < rec_ptr[g + 1]; r += 256) {
+        const float *f = ft_src + (size_t)r * S;
+        float dot = 0.0f;
+        for (int j = 0; j < S; ++j) dot = fmaf(f[j], s_q[j], dot);
+        const float a = expf(dot * scale);
+        w[(size_t)r * K + k] = a;
+        a_sum += a;
+        ax = fmaf(a, rec_x[(size_t)r * 3], ax);
+        ay = fmaf(a, rec_x[(size_t)r * 3 + 1], ay);
+        az = fmaf(a, rec_x[(size_t)r * 3 + 2], az);
+    }
+    s_part[tid][0] = a_sum; s_part[tid][1] = ax; s_part[tid][2] = ay; s_part[tid][3] = az;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (tid < o)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) s_part[tid][c] += s_part[tid + o][c];
+        __syncthreads();
+    }
+    const float inv = 1.0f / s_part[0][0];
+    for (int r = rec_ptr[g] + tid; r < rec_ptr[g + 1]; r += 256) w[(size_t)r * K + k] *= inv;
+    if (tid < 3) kp_x[(size_t)kp * 3 + tid] = s_part[0][1 + tid] * inv;
+}
+
+// d<ft_src[r], ft_dst[kp]> = w (<dkp_x, x_r> - <dkp_x, kp_x>) / sqrt(S), written over w (softmax backward of kp_x = sum w x)
+__global__ __launch_bounds__(256) void k_att_bwd_logits(float *__restrict__ w, const float *__restrict__ rec_x, const int *__restrict__ rec_ptr,
+                                                        int K, int S, const float *__restrict__ dkp_x, const float *__restrict__ kp_x) {
+    const int kp = blockIdx.x, g = kp / K, k = kp - g * K;
+    const float dx = dkp_x[(size_t)kp * 3], dy = dkp_x[(size_t)kp * 3 + 1], dz = dkp_x[(size_t)kp * 3 + 2];
+    const float base = dx * kp_x[(size_t)kp * 3] + dy * kp_x[(size_t)kp * 3 + 1] + dz * kp_x[(size_t)kp * 3 + 2];
+    const float scale = 1.0f / sqrtf((float)S);
+    for (int r = rec_ptr[g] + threadIdx.x; r < rec_ptr[g + 1]; r += 256) {
+        const float dw = dx * rec_x[(size_t)r * 3] + dy * rec_x[(size_t)r * 3 + 1] + dz * rec_x[(size_t)r * 3 + 2];
+        w[(size_t)r * K + k] *= (dw - base) * scale;
+    }
+}
+
+// dft_dst[kp, s] = sum over the graph's receptor atoms of G[r, k] ft_src[r, s]   (ascending r: deterministic)
+__global__ __launch_bounds__(256) void k_att_bwd_dst(const float *__restrict__ G, const float *__restrict__ ft_src, const int *__restrict__ rec_ptr,
+                                                     int K, int S, float *__restrict__ dft_dst) {
+    const int kp = blockIdx.x, g = kp / K, k = kp - g * K, s = threadIdx.x;
+    if (s >= S) return;
+    float acc = 0.0f;
+    for (int r = rec_ptr[g]; r < rec_ptr[g + 1]; ++r) acc = fmaf(G[(size_t)r * K + k], ft_src[(size_t)r * S + s], acc);
+    dft_dst[(size_t)kp * S + s] = acc;
+}
+
+// dft_src[r, s] = sum over the graph's keypoints of G[r, k] ft_dst[kp_k, s]
+__global__ __launch_bounds__(256) void k_att_bwd_src(const float *__restrict__ G, const float *__restrict__ ft_dst, const int *__restrict__ bidx,
+                                                     int K, int S, float *__restrict__ dft_src) {
+    const int r = blockIdx.x, s = threadIdx.x, g = bidx[r];
+    if (s >= S) return;
+    float acc = 0.0f;
+    for (int k = 0; k < K; ++k) acc = fmaf(G[(size_t)r * K + k], ft_dst[((size_t)g * K + k) * S + s], acc);
+    dft_src[(size_t)r * S + s] = acc;
+}
+
+// g[r, :] += dmean[graph(r), :] / n_graph   (backward of dgl.readout_nodes mean)
+__global__ void k_mean_bwd(const float *__restrict__ dmean, const int *__restrict__ bidx, const int *__restrict__ ptr, long long total, int S,
+                           float *__restrict__ g) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int r = (int)(i / S), c = (int)(i - (long long)r * S), b = bidx[r];
+    g[i] += dmean[(size_t)b * S + c] / (float)(ptr[b + 1] - ptr[b]);
+}
+
 kpd_status launch_iota_scaled(int *out, int n, int scale, hipStream_t st) {
     hipLaunchKernelGGL(k_iota_scaled, dim3(cdiv(n, 256)), dim3(256), 0, st, out, n, scale);
     KPD_LAUNCH_CHECK();
@@ -256,6 +335,50 @@ kpd_status launch_kp_attention(const float *ft_src, const float *ft_dst, const f
                                int S, float *kp_x, hipStream_t st) {
     KPD_REQUIRE(S <= 256, KPD_ERR_INVALID, "kp attention: S=%d > 256", S);
     hipLaunchKernelGGL(k_kp_attention, dim3(n_kp), dim3(256), 0, st, ft_src, ft_dst, rec_x, rec_ptr, K, S, S, kp_x);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+kpd_status launch_indegree_ratio(const int *rowptr, const int *ptr, int B, float *z, hipStream_t st) {
+    hipLaunchKernelGGL(k_z_indegree, dim3(cdiv(B, 256)), dim3(256), 0, st, rowptr, ptr, B, z);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+kpd_status launch_graph_mean_bwd(const float *dmean, const int *bidx, const int *ptr, int n, int S, float *g, hipStream_t st) {
+    const long long total = (long long)n * S;
+    hipLaunchKernelGGL(k_mean_bwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dmean, bidx, ptr, total, S, g);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+kpd_status launch_att_fwd(const float *ft_src, const float *ft_dst, const float *rec_x, const int *rec_ptr, int n_kp, int K, int S,
+                          float *w, float *kp_x, hipStream_t st) {
+    KPD_REQUIRE(S <= 256, KPD_ERR_INVALID, "kp attention: S=%d > 256", S);
+    hipLaunchKernelGGL(k_att_fwd, dim3(n_kp), dim3(256), 0, st, ft_src, ft_dst, rec_x, rec_ptr, K, S, w, kp_x);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+kpd_status launch_att_bwd_logits(float *w, const float *rec_x, const int *rec_ptr, int n_kp, int K, int S, const float *dkp_x,
+                                 const float *kp_x, hipStream_t st) {
+    hipLaunchKernelGGL(k_att_bwd_logits, dim3(n_kp), dim3(256), 0, st, w, rec_x, rec_ptr, K, S, dkp_x, kp_x);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+kpd_status launch_att_bwd_dst(const float *G, const float *ft_src, const int *rec_ptr, int n_kp, int K, int S, float *dft_dst,
+                              hipStream_t st) {
+    KPD_REQUIRE(S <= 256, KPD_ERR_INVALID, "kp attention: S=%d > 256", S);
+    hipLaunchKernelGGL(k_att_bwd_dst, dim3(n_kp), dim3(256), 0, st, G, ft_src, rec_ptr, K, S, dft_dst);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+kpd_status launch_att_bwd_src(const float *G, const float *ft_dst, const int *bidx, int n_rec, int K, int S, float *dft_src,
+                              hipStream_t st) {
+    KPD_REQUIRE(S <= 256, KPD_ERR_INVALID, "kp attention: S=%d > 256", S);
+    hipLaunchKernelGGL(k_att_bwd_src, dim3(n_rec), dim3(256), 0, st, G, ft_dst, bidx, K, S, dft_src);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
 }
@@ -570,8 +693,7 @@ extern "C" kpd_status kpd_recenc_forward(kpd_recenc *m, const kpd_rec_batch *bt,
 
     // rec-rec convolutions (:240-254)
     if (c.message_norm_mode == 2) {
-        hipLaunchKernelGGL(k_z_indegree, dim3(cdiv(B, 256)), dim3(256), 0, st, bt->rr_rowptr, bt->rec_ptr, B, m->z);
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_indegree_ratio(bt->rr_rowptr, bt->rec_ptr, B, m->z, st));
     }
     hipLaunchKernelGGL(k_meta_single, dim3(1), dim3(64), 0, st, 0, static_cast<const int *>(nullptr), bt->n_rr, m->meta);
     KPD_LAUNCH_CHECK();
@@ -605,8 +727,7 @@ extern "C" kpd_status kpd_recenc_forward(kpd_recenc *m, const kpd_rec_batch *bt,
                                         m->rad_tmp, m->rad_tmp + B, m->off_tmp, m->xm_src, m->xm_dst, m->xm_rowptr, out->rk_src,
                                         out->rk_dst, m->rk_rowptr, st));
     if (c.message_norm_mode == 2) {
-        hipLaunchKernelGGL(k_z_indegree, dim3(cdiv(B, 256)), dim3(256), 0, st, m->rk_rowptr, m->kp_ptr, B, m->z);   // :266-269
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_indegree_ratio(m->rk_rowptr, m->kp_ptr, B, m->z, st));                            // :266-269
     }
     hipLaunchKernelGGL(k_meta_single, dim3(1), dim3(64), 0, st, 2, m->off_tmp + B, 0, m->meta);
     KPD_LAUNCH_CHECK();

@@ -190,12 +190,6 @@ __global__ __launch_bounds__(RW) void k_rc_conv(RcConvArgs a) {
     }
 }
 
-// message_norm == 0: z[b] = rr edges of the graph / receptor nodes of the graph (no +1, :505-509)
-__global__ void k_rc_z(const int *__restrict__ rowptr, const int *__restrict__ ptr, int B, float *__restrict__ z) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) z[b] = (float)(rowptr[ptr[b + 1]] - rowptr[ptr[b]]) / (float)(ptr[b + 1] - ptr[b]);
-}
-
 // keypoint_embedding (:529-530): out[b][j] = SiLU(W[j] . mean[b] + bias[j]), j < D K; W row-major [D K][D]
 __global__ __launch_bounds__(RW) void k_rc_kp_embed(const float *__restrict__ mean, const float *__restrict__ W,
                                                     const float *__restrict__ bias, int D, int DK, float *__restrict__ out) {
@@ -482,8 +476,7 @@ extern "C" kpd_status kpd_recegnn_forward(kpd_recegnn *m, const kpd_rec_batch *b
     KPD_TRY(launch_node_graph_index(bt->rec_ptr, B, n_rec, m->bidx, st));
     KPD_TRY(launch_iota_scaled(m->kp_ptr, B + 1, K, st));
     if (c.message_norm == 0.0f) {
-        hipLaunchKernelGGL(k_rc_z, dim3(cdiv(B, 256)), dim3(256), 0, st, bt->rr_rowptr, bt->rec_ptr, B, m->z);
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_indegree_ratio(bt->rr_rowptr, bt->rec_ptr, B, m->z, st));          // rr edges / receptor atoms of the graph (no +1, :505-509)
     }
     // ReceptorConv stack (:512-513); layer i reads (h, x) buffer i & 1 (layer 0: the inputs) and writes the other
     const float *h_in = bt->rec_h, *x_in = bt->rec_x;

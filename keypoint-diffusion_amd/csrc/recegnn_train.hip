@@ -92,11 +92,6 @@ __global__ void k_rc_scale(const float *__restrict__ z, const int *__restrict__ 
     if (v < n) scale[v] = 1.0f / (z ? z[bidx[v]] : norm);
 }
 
-__global__ void k_rc_z(const int *__restrict__ rowptr, const int *__restrict__ ptr, int B, float *__restrict__ z) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) z[b] = (float)(rowptr[ptr[b + 1]] - rowptr[ptr[b]]) / (float)(ptr[b + 1] - ptr[b]);
-}
-
 // backward of the attention gate: dmsg [E, H] in, dm [E, H] out (in place), ds [E]; one wave per edge
 __global__ void k_rc_att_bwd(const float *__restrict__ m, const float *__restrict__ s, const float *__restrict__ w, int E, int H,
                              float *__restrict__ dmsg, float *__restrict__ ds) {
@@ -156,46 +151,6 @@ __global__ void k_rc_geom_bwd(const int *__restrict__ src, const int *__restrict
     for (int k = 0; k < 3; ++k) dxe[3 * e + k] = (dxd ? dxd[3 * e + k] : 0.0f) * inv + q * df3[k];
 }
 
-__global__ void k_rc_mean_bwd(const float *__restrict__ dmean, const int *__restrict__ bidx, const int *__restrict__ ptr, long long total, int D,
-                              float *__restrict__ g) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int r = (int)(i / D), c = (int)(i - (long long)r * D), b = bidx[r];
-    g[i] += dmean[(size_t)b * D + c] / (float)(ptr[b + 1] - ptr[b]);
-}
-
-// RecKeyConv attention (:188-222) with kept weights: w[r * K + k] = softmax over the graph's atoms; kp_x = sum w x_val
-__global__ __launch_bounds__(256) void k_rk_att_fwd(const float *__restrict__ ft_src, const float *__restrict__ ft_dst, const float *__restrict__ xv,
-                                                    const int *__restrict__ rec_ptr, int K, int D, float *__restrict__ w, float *__restrict__ kp_x) {
-    __shared__ float s_q[256];
-    __shared__ float s_part[256][4];
-    const int kp = blockIdx.x, g = kp / K, k = kp - g * K, tid = threadIdx.x;
-    if (tid < D) s_q[tid] = ft_dst[(size_t)kp * D + tid];
-    __syncthreads();
-    const float scale = 1.0f / sqrtf((float)D);
-    float a_sum = 0.f, ax = 0.f, ay = 0.f, az = 0.f;
-    for (int r = rec_ptr[g] + tid; r < rec_ptr[g + 1]; r += 256) {
-        const float *f = ft_src + (size_t)r * D;
-        float dot = 0.0f;
-        for (int j = 0; j < D; ++j) dot = fmaf(f[j], s_q[j], dot);
-        const float a = expf(dot * scale);
-        w[(size_t)r * K + k] = a;
-        a_sum += a;
-        ax = fmaf(a, xv[(size_t)r * 3], ax); ay = fmaf(a, xv[(size_t)r * 3 + 1], ay); az = fmaf(a, xv[(size_t)r * 3 + 2], az);
-    }
-    s_part[tid][0] = a_sum; s_part[tid][1] = ax; s_part[tid][2] = ay; s_part[tid][3] = az;
-    __syncthreads();
-    for (int o = 128; o >= 1; o >>= 1) {
-        if (tid < o)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) s_part[tid][c] += s_part[tid + o][c];
-        __syncthreads();
-    }
-    const float inv = 1.0f / s_part[0][0];
-    for (int r = rec_ptr[g] + tid; r < rec_ptr[g + 1]; r += 256) w[(size_t)r * K + k] *= inv;
-    if (tid < 3) kp_x[(size_t)kp * 3 + tid] = s_part[0][1 + tid] * inv;
-}
-
 // d x_val[r] += sum_k w[r, k] dkp_x[k]  (before w is overwritten by the logit gradients); one thread per atom
 __global__ void k_rk_att_bwd_val(const float *__restrict__ w, const float *__restrict__ dkp_x, const int *__restrict__ bidx, int n, int K,
                                  float *__restrict__ gx) {
@@ -209,36 +164,6 @@ __global__ void k_rk_att_bwd_val(const float *__restrict__ w, const float *__res
         c = fmaf(wk, dkp_x[((size_t)g * K + k) * 3 + 2], c);
     }
     gx[3 * r] += a; gx[3 * r + 1] += b; gx[3 * r + 2] += c;
-}
-
-__global__ __launch_bounds__(256) void k_rk_att_bwd_logits(float *__restrict__ w, const float *__restrict__ xv, const int *__restrict__ rec_ptr, int K,
-                                                           int D, const float *__restrict__ dkp_x, const float *__restrict__ kp_x) {
-    const int kp = blockIdx.x, g = kp / K, k = kp - g * K;
-    const float dx = dkp_x[(size_t)kp * 3], dy = dkp_x[(size_t)kp * 3 + 1], dz = dkp_x[(size_t)kp * 3 + 2];
-    const float base = dx * kp_x[(size_t)kp * 3] + dy * kp_x[(size_t)kp * 3 + 1] + dz * kp_x[(size_t)kp * 3 + 2];
-    const float scale = 1.0f / sqrtf((float)D);
-    for (int r = rec_ptr[g] + threadIdx.x; r < rec_ptr[g + 1]; r += 256) {
-        const float dw = dx * xv[(size_t)r * 3] + dy * xv[(size_t)r * 3 + 1] + dz * xv[(size_t)r * 3 + 2];
-        w[(size_t)r * K + k] *= (dw - base) * scale;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_rk_att_bwd_dst(const float *__restrict__ G, const float *__restrict__ ft_src, const int *__restrict__ rec_ptr,
-                                                        int K, int D, float *__restrict__ dft_dst) {
-    const int kp = blockIdx.x, g = kp / K, k = kp - g * K, s = threadIdx.x;
-    if (s >= D) return;
-    float acc = 0.0f;
-    for (int r = rec_ptr[g]; r < rec_ptr[g + 1]; ++r) acc = fmaf(G[(size_t)r * K + k], ft_src[(size_t)r * D + s], acc);
-    dft_dst[(size_t)kp * D + s] = acc;
-}
-
-__global__ __launch_bounds__(256) void k_rk_att_bwd_src(const float *__restrict__ G, const float *__restrict__ ft_dst, const int *__restrict__ bidx,
-                                                        int K, int D, float *__restrict__ dft_src) {
-    const int r = blockIdx.x, s = threadIdx.x, g = bidx[r];
-    if (s >= D) return;
-    float acc = 0.0f;
-    for (int k = 0; k < K; ++k) acc = fmaf(G[(size_t)r * K + k], ft_dst[((size_t)g * K + k) * D + s], acc);
-    dft_src[(size_t)r * D + s] = acc;
 }
 
 // keypoint feature rows (:284-289): [mean over the k nearest atoms of h | the k distances |x0 - kp_x + 1e-30|]
@@ -599,8 +524,7 @@ extern "C" kpd_status kpd_recegnn_trainer_forward(kpd_recegnn_trainer *T, const 
     KPD_TRY(launch_iota_scaled(T->kp_ptr, B + 1, K, st));
     KPD_TRY(build_src_csr(T, bt->rr_src, bt->n_rr, n_rec, T->cursor, T->scsr_rr));
     if (c.message_norm == 0.0f) {
-        hipLaunchKernelGGL(k_rc_z, grid1(B), dim3(256), 0, st, bt->rr_rowptr, bt->rec_ptr, B, T->z);
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_indegree_ratio(bt->rr_rowptr, bt->rec_ptr, B, T->z, st));
     }
     hipLaunchKernelGGL(k_rc_scale, grid1(n_rec), dim3(256), 0, st, c.message_norm == 0.0f ? T->z : (const float *)nullptr, T->bidx, n_rec,
                        c.message_norm == 0.0f ? 1.0f : c.message_norm, T->scale);
@@ -625,8 +549,7 @@ extern "C" kpd_status kpd_recegnn_trainer_forward(kpd_recegnn_trainer *T, const 
     KPD_TRY(gemm(T, false, true, n_rec, D, D, T->hs[L], D, Wf.w, D, 0.0f, T->ft_src, D));
     KPD_TRY(gemm(T, false, true, n_kp, D, D, T->kp_h0, D, Wf.w, D, 0.0f, T->ft_dst, D));
     const float *xv = c.fix_pos ? bt->rec_x : T->xs[L];
-    hipLaunchKernelGGL(k_rk_att_fwd, dim3(n_kp), dim3(256), 0, st, T->ft_src, T->ft_dst, xv, bt->rec_ptr, K, D, T->att, T->kp_x);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(launch_att_fwd(T->ft_src, T->ft_dst, xv, bt->rec_ptr, n_kp, K, D, T->att, T->kp_x, st));
     int e_rk = 0;
     if (k > 0) {
         // k nearest receptor atoms of every keypoint by the ORIGINAL positions (:262-267); kp-major, nearest first
@@ -715,13 +638,10 @@ extern "C" kpd_status kpd_recegnn_trainer_backward(kpd_recegnn_trainer *T, const
         hipLaunchKernelGGL(k_rk_att_bwd_val, grid1(n_rec), dim3(256), 0, st, T->att, T->gkx, T->bidx, n_rec, K, T->gx[cur]);
         KPD_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_rk_att_bwd_logits, dim3(n_kp), dim3(256), 0, st, T->att, xv, bt.rec_ptr, K, D, T->gkx, T->kp_x);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(launch_att_bwd_logits(T->att, xv, bt.rec_ptr, n_kp, K, D, T->gkx, T->kp_x, st));
     float *dft_dst = T->gk1, *dft_src = T->gn1;
-    hipLaunchKernelGGL(k_rk_att_bwd_dst, dim3(n_kp), dim3(256), 0, st, T->att, T->ft_src, bt.rec_ptr, K, D, dft_dst);
-    KPD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_rk_att_bwd_src, dim3(n_rec), dim3(256), 0, st, T->att, T->ft_dst, T->bidx, K, D, dft_src);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(launch_att_bwd_dst(T->att, T->ft_src, bt.rec_ptr, n_kp, K, D, dft_dst, st));
+    KPD_TRY(launch_att_bwd_src(T->att, T->ft_dst, T->bidx, n_rec, K, D, dft_src, st));
     // ft_src = h_L Wf^T, ft_dst = kp_h0 Wf^T: one weight, two uses
     if (Wf.g) {
         KPD_TRY(grad_gemm(T, D, D, n_rec, dft_src, D, T->hs[L], D, Wf.g, D));
@@ -733,8 +653,7 @@ extern "C" kpd_status kpd_recegnn_trainer_backward(kpd_recegnn_trainer *T, const
         for (int c0 = 0; c0 < D * K; c0 += COLSUM_LD) KPD_TRY(colsum_acc(T, B, std::min(COLSUM_LD, D * K - c0), T->big + c0, D * K, bk.g + c0));
     if (Wk.g) KPD_TRY(gemm(T, true, false, D * K, D, B, T->big, D * K, T->gmean, D, 1.0f, Wk.g, D));
     KPD_TRY(gemm(T, false, false, B, D, D * K, T->big, D * K, Wk.w, D, 0.0f, T->gk2, D));              // d gmean
-    hipLaunchKernelGGL(k_rc_mean_bwd, grid1((long long)n_rec * D), dim3(256), 0, st, T->gk2, T->bidx, bt.rec_ptr, (long long)n_rec * D, D, T->gh[cur]);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(launch_graph_mean_bwd(T->gk2, T->bidx, bt.rec_ptr, n_rec, D, T->gh[cur], st));
 
     // ReceptorConv stack, last to first
     for (int i = L - 1; i >= 0; --i) {

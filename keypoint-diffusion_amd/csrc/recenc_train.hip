@@ -43,89 +43,6 @@ __global__ void k_enc_vin(const float *__restrict__ unit, const float *__restric
     out[i] = ch == 0 ? unit[3 * e + c] : ch <= VC ? v_src[((size_t)src[e] * 3 + c) * VC + ch - 1] : v_dst[((size_t)dst[e] * 3 + c) * VC + ch - 1 - VC];
 }
 
-// message_norm == 0: z[graph] = edges into the graph's destination nodes / destination nodes (receptor_encoder_gvp.py:243-246, :266-269)
-__global__ void k_enc_z(const int *__restrict__ rowptr, const int *__restrict__ ptr, int B, float *__restrict__ z) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) z[b] = (float)(rowptr[ptr[b + 1]] - rowptr[ptr[b]]) / (float)(ptr[b + 1] - ptr[b]);
-}
-
-// g[r, :] += dmean[graph(r), :] / n_graph   (backward of dgl.readout_nodes mean)
-__global__ void k_mean_bwd(const float *__restrict__ dmean, const int *__restrict__ bidx, const int *__restrict__ ptr, long long total, int S,
-                           float *__restrict__ g) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int r = (int)(i / S), c = (int)(i - (long long)r * S), b = bidx[r];
-    g[i] += dmean[(size_t)b * S + c] / (float)(ptr[b + 1] - ptr[b]);
-}
-
-// KeypointInitializer attention (receptor_encoder_gvp.py:57-87): one workgroup per keypoint over the receptor atoms of its graph.
-// w[r * K + k] = exp(<ft_src[r], ft_dst[kp]> / sqrt(S)) / sum over the graph (no max-subtraction, as upstream); kp_x = sum w x_r
-__global__ __launch_bounds__(256) void k_att_fwd(const float *__restrict__ ft_src, const float *__restrict__ ft_dst, const float *__restrict__ rec_x,
-                                                 const int *__restrict__ rec_ptr, int K, int S, float *__restrict__ w, float *__restrict__ kp_x) {
-    __shared__ float s_q[256];
-    __shared__ float s_part[256][4];
-    const int kp = blockIdx.x, g = kp / K, k = kp - g * K, tid = threadIdx.x;
-    if (tid < S) s_q[tid] = ft_dst[(size_t)kp * S + tid];
-    __syncthreads();
-    const float scale = 1.0f / sqrtf((float)S);
-    float a_sum = 0.f, ax = 0.f, ay = 0.f, az = 0.f;
-    for (int r = rec_ptr[g] + tid; r < rec_ptr[g + 1]; r += 256) {
-        const float *f = ft_src + (size_t)r * S;
-        float dot = 0.0f;
-        for (int j = 0; j < S; ++j) dot = fmaf(f[j], s_q[j], dot);
-        const float a = expf(dot * scale);
-        w[(size_t)r * K + k] = a;
-        a_sum += a;
-        ax = fmaf(a, rec_x[(size_t)r * 3], ax);
-        ay = fmaf(a, rec_x[(size_t)r * 3 + 1], ay);
-        az = fmaf(a, rec_x[(size_t)r * 3 + 2], az);
-    }
-    s_part[tid][0] = a_sum; s_part[tid][1] = ax; s_part[tid][2] = ay; s_part[tid][3] = az;
-    __syncthreads();
-    for (int o = 128; o >= 1; o >>= 1) {
-        if (tid < o)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) s_part[tid][c] += s_part[tid + o][c];
-        __syncthreads();
-    }
-    const float inv = 1.0f / s_part[0][0];
-    for (int r = rec_ptr[g] + tid; r < rec_ptr[g + 1]; r += 256) w[(size_t)r * K + k] *= inv;
-    if (tid < 3) kp_x[(size_t)kp * 3 + tid] = s_part[0][1 + tid] * inv;
-}
-
-// d<ft_src[r], ft_dst[kp]> = w (<dkp_x, x_r> - <dkp_x, kp_x>) / sqrt(S), written over w (softmax backward of kp_x = sum w x)
-__global__ __launch_bounds__(256) void k_att_bwd_logits(float *__restrict__ w, const float *__restrict__ rec_x, const int *__restrict__ rec_ptr,
-                                                        int K, int S, const float *__restrict__ dkp_x, const float *__restrict__ kp_x) {
-    const int kp = blockIdx.x, g = kp / K, k = kp - g * K;
-    const float dx = dkp_x[(size_t)kp * 3], dy = dkp_x[(size_t)kp * 3 + 1], dz = dkp_x[(size_t)kp * 3 + 2];
-    const float base = dx * kp_x[(size_t)kp * 3] + dy * kp_x[(size_t)kp * 3 + 1] + dz * kp_x[(size_t)kp * 3 + 2];
-    const float scale = 1.0f / sqrtf((float)S);
-    for (int r = rec_ptr[g] + threadIdx.x; r < rec_ptr[g + 1]; r += 256) {
-        const float dw = dx * rec_x[(size_t)r * 3] + dy * rec_x[(size_t)r * 3 + 1] + dz * rec_x[(size_t)r * 3 + 2];
-        w[(size_t)r * K + k] *= (dw - base) * scale;
-    }
-}
-
-// dft_dst[kp, s] = sum over the graph's receptor atoms of G[r, k] ft_src[r, s]   (ascending r: deterministic)
-__global__ __launch_bounds__(256) void k_att_bwd_dst(const float *__restrict__ G, const float *__restrict__ ft_src, const int *__restrict__ rec_ptr,
-                                                     int K, int S, float *__restrict__ dft_dst) {
-    const int kp = blockIdx.x, g = kp / K, k = kp - g * K, s = threadIdx.x;
-    if (s >= S) return;
-    float acc = 0.0f;
-    for (int r = rec_ptr[g]; r < rec_ptr[g + 1]; ++r) acc = fmaf(G[(size_t)r * K + k], ft_src[(size_t)r * S + s], acc);
-    dft_dst[(size_t)kp * S + s] = acc;
-}
-
-// dft_src[r, s] = sum over the graph's keypoints of G[r, k] ft_dst[kp_k, s]
-__global__ __launch_bounds__(256) void k_att_bwd_src(const float *__restrict__ G, const float *__restrict__ ft_dst, const int *__restrict__ bidx,
-                                                     int K, int S, float *__restrict__ dft_src) {
-    const int r = blockIdx.x, s = threadIdx.x, g = bidx[r];
-    if (s >= S) return;
-    float acc = 0.0f;
-    for (int k = 0; k < K; ++k) acc = fmaf(G[(size_t)r * K + k], ft_dst[((size_t)g * K + k) * S + s], acc);
-    dft_src[(size_t)r * S + s] = acc;
-}
-
 }  // namespace
 }  // namespace kpd
 
@@ -553,8 +470,7 @@ extern "C" kpd_status kpd_recenc_trainer_forward(kpd_recenc_trainer *T, const kp
         KPD_HIP(hipMemsetAsync(T->rv[0], 0, (size_t)n_rec * 3 * VC * 4, st));
     }
     if (c.message_norm_mode == 2) {
-        hipLaunchKernelGGL(k_enc_z, grid1(B), dim3(256), 0, st, bt->rr_rowptr, bt->rec_ptr, B, T->z);
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_indegree_ratio(bt->rr_rowptr, bt->rec_ptr, B, T->z, st));
     }
     for (int i = 0; i < Rr; ++i) KPD_TRY(conv_fwd(T, rr_conv(T, i)));
 
@@ -574,8 +490,7 @@ extern "C" kpd_status kpd_recenc_trainer_forward(kpd_recenc_trainer *T, const kp
         KPD_LAUNCH_CHECK();
         KPD_TRY(gemm(T, false, true, n_rec, S, S, T->rs[Rr], S, Ws.w, S, 0.0f, T->ft_src, S));
         KPD_TRY(gemm(T, false, true, n_kp, S, S, T->kp_emb, S, Wd.w, S, 0.0f, T->ft_dst, S));
-        hipLaunchKernelGGL(k_att_fwd, dim3(n_kp), dim3(256), 0, st, T->ft_src, T->ft_dst, bt->rec_x, bt->rec_ptr, K, S, T->att, T->kp_x);
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_att_fwd(T->ft_src, T->ft_dst, bt->rec_x, bt->rec_ptr, n_kp, K, S, T->att, T->kp_x, st));
         KPD_HIP(hipMemsetAsync(T->ks[0], 0, (size_t)n_kp * S * 4, st));                                 // :90-91
         KPD_HIP(hipMemsetAsync(T->kv[0], 0, (size_t)n_kp * 3 * VC * 4, st));
     }
@@ -593,8 +508,7 @@ extern "C" kpd_status kpd_recenc_trainer_forward(kpd_recenc_trainer *T, const kp
     T->E_rk = e_rk;
     KPD_TRY(build_src_csr(T, T->rk_src, e_rk, n_rec, T->cursor, T->scsr_rk));
     if (c.message_norm_mode == 2) {
-        hipLaunchKernelGGL(k_enc_z, grid1(B), dim3(256), 0, st, T->rk_rowptr, T->kp_ptr, B, T->z);          // :266-269
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_indegree_ratio(T->rk_rowptr, T->kp_ptr, B, T->z, st));          // :266-269
     }
     for (int j = 0; j < Rk; ++j) KPD_TRY(conv_fwd(T, rk_conv(T, j)));
 
@@ -637,8 +551,7 @@ extern "C" kpd_status kpd_recenc_trainer_backward(kpd_recenc_trainer *T, const f
     // rec -> kp convolutions, last to first: the keypoint-state gradient moves from gks[cur] to gks[nxt]; the receptor-state and
     // keypoint-position gradients accumulate
     if (c.message_norm_mode == 2) {
-        hipLaunchKernelGGL(k_enc_z, grid1(B), dim3(256), 0, st, T->rk_rowptr, T->kp_ptr, B, T->z);
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_indegree_ratio(T->rk_rowptr, T->kp_ptr, B, T->z, st));
     }
     for (int j = Rk - 1; j >= 0; --j) {
         KPD_HIP(hipMemsetAsync(T->gks[nxt], 0, (size_t)n_kp * S * 4, st));
@@ -657,13 +570,10 @@ extern "C" kpd_status kpd_recenc_trainer_backward(kpd_recenc_trainer *T, const f
         KPD_TRY(param(T, "keypoint_initializer.keypoint_embedding.2.bias", S * K, 1, &lb));
         KPD_TRY(param(T, "keypoint_initializer.src_net.weight", S, S, &Ws));
         KPD_TRY(param(T, "keypoint_initializer.dst_net.weight", S, S, &Wd));
-        hipLaunchKernelGGL(k_att_bwd_logits, dim3(n_kp), dim3(256), 0, st, T->att, bt.rec_x, bt.rec_ptr, K, S, T->gkx, T->kp_x);
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_att_bwd_logits(T->att, bt.rec_x, bt.rec_ptr, n_kp, K, S, T->gkx, T->kp_x, st));
         float *dft_dst = T->gks[nxt], *dft_src = T->U;                        // free node-sized buffers
-        hipLaunchKernelGGL(k_att_bwd_dst, dim3(n_kp), dim3(256), 0, st, T->att, T->ft_src, bt.rec_ptr, K, S, dft_dst);
-        KPD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_att_bwd_src, dim3(n_rec), dim3(256), 0, st, T->att, T->ft_dst, T->bidx[0], K, S, dft_src);
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_att_bwd_dst(T->att, T->ft_src, bt.rec_ptr, n_kp, K, S, dft_dst, st));
+        KPD_TRY(launch_att_bwd_src(T->att, T->ft_dst, T->bidx[0], n_rec, K, S, dft_src, st));
         // ft_src = s_R Ws^T, ft_dst = kp_emb Wd^T
         if (Ws.g) KPD_TRY(grad_gemm(T, S, S, n_rec, dft_src, S, T->rs[Rr], S, Ws.g, S));
         KPD_TRY(gemm(T, false, false, n_rec, S, S, dft_src, S, Ws.w, S, 1.0f, T->grs, S));
@@ -679,16 +589,13 @@ extern "C" kpd_status kpd_recenc_trainer_backward(kpd_recenc_trainer *T, const f
         KPD_TRY(colsum_wide(T, B, S * K, T->kp_emb, b.g));
         if (W.g) KPD_TRY(gemm(T, true, false, S * K, S, B, T->kp_emb, S * K, T->gmean, S, 1.0f, W.g, S));
         KPD_TRY(gemm(T, false, false, B, S, S * K, T->kp_emb, S * K, W.w, S, 0.0f, T->ft_dst, S));      // d gmean [B, S]
-        hipLaunchKernelGGL(k_mean_bwd, grid1((long long)n_rec * S), dim3(256), 0, st, T->ft_dst, T->bidx[0], bt.rec_ptr, (long long)n_rec * S, S,
-                           T->grs);
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_graph_mean_bwd(T->ft_dst, T->bidx[0], bt.rec_ptr, n_rec, S, T->grs, st));
     }
 
     // rec-rec convolutions, last to first: grs / grv hold the gradient of the state LEAVING conv i and receive the gradient of the
     // state entering it (source and destination are the same nodes: residual, source-side and destination-side terms all add up)
     if (c.message_norm_mode == 2) {
-        hipLaunchKernelGGL(k_enc_z, grid1(B), dim3(256), 0, st, bt.rr_rowptr, bt.rec_ptr, B, T->z);
-        KPD_LAUNCH_CHECK();
+        KPD_TRY(launch_indegree_ratio(bt.rr_rowptr, bt.rec_ptr, B, T->z, st));
     }
     for (int i = Rr - 1; i >= 0; --i) {
         KPD_HIP(hipMemcpyAsync(T->gro_s, T->grs, (size_t)n_rec * S * 4, hipMemcpyDeviceToDevice, st));

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
+from .engine_owner import EngineOwner, train_backward, train_forward
 from .graph import HeteroBatch
 
 
@@ -30,32 +31,19 @@ class _EgnnTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, pb, timestep, lig_x, lig_h, kp_x, kp_h, *params):
-        trainer, names = module._trainer()
-        ctx.trainer, ctx.names = trainer, names
+        trainer = train_forward(ctx, module, params)
         # the C side keeps raw pointers into the batch structure (per-complex offsets, the kk edge list) and reads them again in the
         # backward pass: the prepared batch must outlive the graph object the caller may drop right after the forward call
         ctx.pb = pb
         ctx.inputs = (lig_x, lig_h, kp_x, kp_h, timestep)          # kept alive until backward (the C side holds pointers)
-        # The trainer keeps the saved layer states of ONE forward.  Every forward takes a new generation number; backward
-        # refuses to run on a workspace a later forward has overwritten.  The parameters go through save_for_backward, so
-        # autograd's version check catches an in-place update between forward and backward (the C side reads them in place).
-        trainer.generation = getattr(trainer, 'generation', 0) + 1
-        ctx.generation = trainer.generation
-        ctx.save_for_backward(*params)
-        trainer.bind(names, params, [None] * len(params))
         eps_h, eps_x = trainer.forward(pb, lig_x, lig_h, kp_x, kp_h, timestep)
         return eps_h, eps_x
 
     @staticmethod
     def backward(ctx, d_eps_h, d_eps_x):
-        if ctx.generation != ctx.trainer.generation:
-            raise hip.KpdError('backward of a LigRecDynamics forward whose saved layer states were overwritten by a later grad-enabled '
-                               'forward of the same module (one forward/backward pair at a time per module)')
-        params = ctx.saved_tensors
+        grads = train_backward(ctx, 7, 'LigRecDynamics', 'layer states')
         lig_x, lig_h, kp_x, kp_h, _ = ctx.inputs
         need = ctx.needs_input_grad[3:7]
-        grads = hip.zero_grads_like(params, [ctx.needs_input_grad[7 + i] for i in range(len(params))])
-        ctx.trainer.bind(ctx.names, params, grads)
         d_in = [torch.empty_like(t) if n else None for t, n in zip((lig_x, lig_h, kp_x, kp_h), need)]
         ctx.trainer.backward(d_eps_h.contiguous().float(), d_eps_x.contiguous().float(), d_in[1], d_in[0], d_in[3], d_in[2])
         return (None, None, None, *d_in, *grads)
@@ -101,7 +89,8 @@ class LigRecEGNN(nn.Module):
             for _ in range(n_layers)])
 
 
-class LigRecDynamics(nn.Module):
+class LigRecDynamics(EngineOwner, nn.Module):
+    _gemm_mode_hint = '(the f16x2 mode needs hidden_nf <= 256 for the EGNN denoiser, n_hidden_scalars = 256 for the GVP one)'
 
     def __init__(self, atom_nf, rec_nf, n_layers=4, hidden_nf=255, act_fn=nn.SiLU, use_tanh=False, message_norm=1,
                  no_cg: bool = False, n_keypoints: int = 20, graph_cutoffs: dict = {}, update_kp_feat: bool = False,
@@ -124,73 +113,24 @@ class LigRecDynamics(nn.Module):
         self.egnn = LigRecEGNN(n_layers=n_layers, in_size=hidden_nf + 1, hidden_size=hidden_nf + 1,
                                out_size=hidden_nf + 1, use_tanh=use_tanh, message_norm=message_norm,
                                update_kp_feat=update_kp_feat, norm=norm)
-        self._engine = None
-        self._engine_key = None
         # GEMM mode of the inference engine: None = the library default (exact fp32 MFMA, or what KPD_GEMM names when the engine
         # is created); 'f32' | 'f16x2' = an explicit choice that is re-applied to EVERY engine this module builds (weights
         # replaced, optimizer step, .to()), so a model cannot silently fall back to another mode.
         self.gemm_mode = None
-        self._train = None
 
-    def _trainer(self):
-        """The training engine and the parameter names in `self.parameters()` order (reference state-dict names)."""
-        if self._train is None:
-            if isinstance(self.message_norm, (dict, str)):
-                raise ValueError(f'message_norm must be a number for the EGNN denoiser, got {self.message_norm!r}')
-            cfg = hip.KpdEgnnConfig(int(self.atom_nf), int(self.rec_nf), int(self.n_layers), int(self.hidden_nf),
-                                    int(bool(self.use_tanh)), int(bool(self.norm)), int(bool(self.update_kp_feat)),
-                                    float(self.message_norm), int(self.ll_k), int(self.kl_k),
-                                    float(self.graph_cutoffs.get('ll', 0.0)), float(self.graph_cutoffs.get('kl', 0.0)), 10.0)
-            self._train = (hip.EgnnTrainer(cfg, self.atom_nf, self.rec_nf), [n for n, _ in self.named_parameters()])
-        return self._train
+    def _config(self) -> 'hip.KpdEgnnConfig':
+        if isinstance(self.message_norm, (dict, str)):
+            raise ValueError(f'message_norm must be a number for the EGNN denoiser, got {self.message_norm!r}')
+        return hip.KpdEgnnConfig(int(self.atom_nf), int(self.rec_nf), int(self.n_layers), int(self.hidden_nf),
+                                 int(bool(self.use_tanh)), int(bool(self.norm)), int(bool(self.update_kp_feat)),
+                                 float(self.message_norm), int(self.ll_k), int(self.kl_k),
+                                 float(self.graph_cutoffs.get('ll', 0.0)), float(self.graph_cutoffs.get('kl', 0.0)), 10.0)
 
-    # ---- HIP engine management ---------------------------------------------------------
-    def _weights_key(self):
-        """(storage pointer, version counter) of every parameter: changes when weights are replaced or modified in place.
-        Walking the module tree costs ~0.7 ms of host time (hundreds of tensors), more than a B = 1 reverse step takes on the GPU,
-        so the list of Parameter objects is cached.  It is rebuilt after `.to()` / `load_state_dict` and whenever ANY module of the
-        process registered a parameter since it was built (`hip.param_generation`: `module.weight = nn.Parameter(...)`, parametrize
-        and pruning all go through `register_parameter`), so a Parameter object swapped in deep inside the module is seen by the
-        next forward.  Unsupported as an immediate trigger: writes into `module._parameters` that bypass `register_parameter` (seen by
-        the periodic re-walk below)."""
-        gen = hip.param_generation()
-        ps = self.__dict__.get('_param_list')
-        # every 256th call walks the tree again whatever the hook said: mutations that bypass `register_parameter` (a direct
-        # `module._parameters[name] = p`, `__setstate__` / deepcopy swaps) are then seen after at most 256 forwards instead of never
-        n = self.__dict__['_param_calls'] = self.__dict__.get('_param_calls', 0) + 1
-        if ps is None or self.__dict__.get('_param_gen') != gen or (n & 255) == 0:
-            ps = self.__dict__['_param_list'] = list(self.parameters())
-            self.__dict__['_param_gen'] = gen
-        return tuple([(p.data_ptr(), p._version) for p in ps])
+    def _build_engine(self):
+        return hip.EgnnEngine(self._config())
 
-    def _apply(self, fn, *a, **kw):
-        self.__dict__.pop('_param_list', None)
-        return super()._apply(fn, *a, **kw)
-
-    def load_state_dict(self, *a, **kw):
-        self.__dict__.pop('_param_list', None)
-        return super().load_state_dict(*a, **kw)
-
-    def engine(self) -> 'hip.EgnnEngine':
-        """(Re)build the device engine when weights were replaced or modified in place."""
-        key = self._weights_key()
-        if self._engine is None or key != self._engine_key:
-            if isinstance(self.message_norm, (dict, str)):
-                raise ValueError(f'message_norm must be a number for the EGNN denoiser, got {self.message_norm!r}')
-            eng = hip.EgnnEngine(self.atom_nf, self.rec_nf, self.n_layers, self.hidden_nf, self.use_tanh, self.norm,
-                                 self.update_kp_feat, self.message_norm, self.ll_k, self.kl_k,
-                                 self.graph_cutoffs.get('ll', 0.0), self.graph_cutoffs.get('kl', 0.0))
-            eng.load_state_dict(self.state_dict())
-            self._engine, self._engine_key = eng, key
-        if self.gemm_mode is not None and getattr(self._engine, '_mode_applied', None) != self.gemm_mode:
-            if self.gemm_mode not in ('f32', 'f16x2'):
-                raise ValueError(f"gemm_mode must be None, 'f32' or 'f16x2', got {self.gemm_mode!r}")
-            self._engine.set_gemm_mode(self.gemm_mode)            # (one library call per engine and choice, not per forward)
-            if self._engine.gemm_mode() != self.gemm_mode:        # an explicit choice is never dropped silently
-                raise hip.KpdError(f'gemm_mode={self.gemm_mode!r} was requested but the engine runs {self._engine.gemm_mode()!r} '
-                                   f'(the f16x2 mode needs hidden_nf <= 256 for the EGNN denoiser, n_hidden_scalars = 256 for the GVP one)')
-            self._engine._mode_applied = self.gemm_mode
-        return self._engine
+    def _build_trainer(self):
+        return hip.EgnnTrainer(self._config())
 
     def forward(self, g: HeteroBatch, timestep: torch.Tensor, batch_idxs: Dict[str, torch.Tensor] = None):
         """Predicted noise (eps_h [N_lig, atom_nf], eps_x [N_lig, 3]); `batch_idxs` is accepted for

@@ -102,41 +102,30 @@ def lib():
     L.kpd_build_flags.restype = C.c_int
     for name in EXPORTS:
         getattr(L, name)          # AttributeError if a declared symbol is not exported
-    L.kpd_egnn_create.argtypes = [C.POINTER(KpdEgnnConfig), C.POINTER(C.c_void_p)]
-    L.kpd_egnn_destroy.argtypes = [C.c_void_p]
-    L.kpd_egnn_destroy.restype = None
-    L.kpd_egnn_load_weight.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
-    L.kpd_egnn_commit.argtypes = [C.c_void_p]
-    L.kpd_egnn_reserve.argtypes = [C.c_void_p] + [C.c_int32] * 6
+    # the handle functions every family has: identical up to the config struct and the number of sizes `reserve` takes
+    for family, cfg, n_sizes in (('egnn', KpdEgnnConfig, 6), ('gvp', KpdGvpConfig, 6), ('recenc', KpdRecencConfig, 4),
+                                 ('recegnn', KpdRecegnnConfig, 4)):
+        for prefix in (family, family + '_trainer'):
+            fn = lambda name: getattr(L, f'kpd_{prefix}_{name}')
+            fn('create').argtypes = [C.POINTER(cfg), C.POINTER(C.c_void_p)]
+            fn('destroy').argtypes = [C.c_void_p]
+            fn('destroy').restype = None
+            fn('reserve').argtypes = [C.c_void_p] + [C.c_int32] * n_sizes
+        fn = lambda name: getattr(L, f'kpd_{family}_{name}')
+        fn('load_weight').argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
+        fn('commit').argtypes = [C.c_void_p]
+        fn('trainer_bind').argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
     L.kpd_egnn_forward.argtypes = [C.c_void_p, C.POINTER(KpdBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.kpd_egnn_debug_state.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.kpd_egnn_last_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
     L.kpd_egnn_profile.argtypes = [C.c_void_p, C.c_int32]
     L.kpd_egnn_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-    L.kpd_gvp_create.argtypes = [C.POINTER(KpdGvpConfig), C.POINTER(C.c_void_p)]
-    L.kpd_gvp_destroy.argtypes = [C.c_void_p]
-    L.kpd_gvp_destroy.restype = None
-    L.kpd_gvp_load_weight.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
-    L.kpd_gvp_commit.argtypes = [C.c_void_p]
-    L.kpd_gvp_reserve.argtypes = [C.c_void_p] + [C.c_int32] * 6
     L.kpd_gvp_forward.argtypes = [C.c_void_p, C.POINTER(KpdBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.kpd_gvp_debug_state.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.kpd_gvp_last_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
     L.kpd_gvp_profile.argtypes = [C.c_void_p, C.c_int32]
     L.kpd_gvp_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-    L.kpd_recenc_create.argtypes = [C.POINTER(KpdRecencConfig), C.POINTER(C.c_void_p)]
-    L.kpd_recenc_destroy.argtypes = [C.c_void_p]
-    L.kpd_recenc_destroy.restype = None
-    L.kpd_recenc_load_weight.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
-    L.kpd_recenc_commit.argtypes = [C.c_void_p]
-    L.kpd_recenc_reserve.argtypes = [C.c_void_p] + [C.c_int32] * 4
     L.kpd_recenc_forward.argtypes = [C.c_void_p, C.POINTER(KpdRecBatch), C.POINTER(KpdRecOut), C.c_void_p]
-    L.kpd_recegnn_create.argtypes = [C.POINTER(KpdRecegnnConfig), C.POINTER(C.c_void_p)]
-    L.kpd_recegnn_destroy.argtypes = [C.c_void_p]
-    L.kpd_recegnn_destroy.restype = None
-    L.kpd_recegnn_load_weight.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
-    L.kpd_recegnn_commit.argtypes = [C.c_void_p]
-    L.kpd_recegnn_reserve.argtypes = [C.c_void_p] + [C.c_int32] * 4
     L.kpd_recegnn_forward.argtypes = [C.c_void_p, C.POINTER(KpdRecBatch), C.c_void_p, C.POINTER(KpdRecOut), C.c_void_p, C.c_void_p,
                                       C.c_void_p]
     L.kpd_build_lig_graph.argtypes = [C.POINTER(KpdBatch), C.c_float, C.c_int32, C.c_float, C.c_int32, C.POINTER(KpdLigGraph),
@@ -153,20 +142,10 @@ def lib():
     L.kpd_sample_update_guided.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 16 +
                                            [C.c_float, C.c_int32, C.c_void_p])
     L.kpd_clash_score.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_void_p]
-    L.kpd_egnn_trainer_create.argtypes = [C.POINTER(KpdEgnnConfig), C.POINTER(C.c_void_p)]
-    L.kpd_egnn_trainer_destroy.argtypes = [C.c_void_p]
-    L.kpd_egnn_trainer_destroy.restype = None
-    L.kpd_egnn_trainer_bind.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
-    L.kpd_egnn_trainer_reserve.argtypes = [C.c_void_p] + [C.c_int32] * 6
     L.kpd_egnn_trainer_forward.argtypes = [C.c_void_p, C.POINTER(KpdBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.kpd_egnn_trainer_backward.argtypes = [C.c_void_p] + [C.c_void_p] * 7
     L.kpd_egnn_trainer_profile.argtypes = [C.c_void_p, C.c_int32]
     L.kpd_egnn_trainer_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-    L.kpd_gvp_trainer_create.argtypes = [C.POINTER(KpdGvpConfig), C.POINTER(C.c_void_p)]
-    L.kpd_gvp_trainer_destroy.argtypes = [C.c_void_p]
-    L.kpd_gvp_trainer_destroy.restype = None
-    L.kpd_gvp_trainer_bind.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
-    L.kpd_gvp_trainer_reserve.argtypes = [C.c_void_p] + [C.c_int32] * 6
     L.kpd_gvp_trainer_forward.argtypes = [C.c_void_p, C.POINTER(KpdBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.kpd_gvp_trainer_backward.argtypes = [C.c_void_p] + [C.c_void_p] * 8
     L.kpd_gvp_trainer_set_dropout.argtypes = [C.c_void_p, C.c_float, C.c_uint64]
@@ -175,19 +154,9 @@ def lib():
     L.kpd_adam_step.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                 C.c_double, C.c_void_p]
     L.kpd_dropout_mask.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
-    L.kpd_recenc_trainer_create.argtypes = [C.POINTER(KpdRecencConfig), C.POINTER(C.c_void_p)]
-    L.kpd_recenc_trainer_destroy.argtypes = [C.c_void_p]
-    L.kpd_recenc_trainer_destroy.restype = None
-    L.kpd_recenc_trainer_bind.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
     L.kpd_recenc_trainer_set_dropout.argtypes = [C.c_void_p, C.c_float, C.c_uint64]
-    L.kpd_recenc_trainer_reserve.argtypes = [C.c_void_p] + [C.c_int32] * 4
     L.kpd_recenc_trainer_forward.argtypes = [C.c_void_p, C.POINTER(KpdRecBatch), C.POINTER(KpdRecOut), C.c_void_p]
     L.kpd_recenc_trainer_backward.argtypes = [C.c_void_p] + [C.c_void_p] * 4
-    L.kpd_recegnn_trainer_create.argtypes = [C.POINTER(KpdRecegnnConfig), C.POINTER(C.c_void_p)]
-    L.kpd_recegnn_trainer_destroy.argtypes = [C.c_void_p]
-    L.kpd_recegnn_trainer_destroy.restype = None
-    L.kpd_recegnn_trainer_bind.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
-    L.kpd_recegnn_trainer_reserve.argtypes = [C.c_void_p] + [C.c_int32] * 4
     L.kpd_recegnn_trainer_forward.argtypes = [C.c_void_p, C.POINTER(KpdRecBatch), C.c_void_p, C.POINTER(KpdRecOut), C.c_void_p, C.c_void_p,
                                               C.c_void_p]
     L.kpd_recegnn_trainer_backward.argtypes = [C.c_void_p] + [C.c_void_p] * 3
@@ -318,43 +287,108 @@ def build_lig_graph(pb: PreparedBatch, lig_x: torch.Tensor, kp_x: torch.Tensor, 
     return out
 
 
-class EgnnEngine:
-    """Owns one kpd_egnn handle: packed weights + workspace for LigRecDynamics.forward."""
+class _Handle:
+    """Owns one kpd_<prefix>_* handle of the library (`prefix`: 'egnn', 'gvp_trainer', ...), created from its ctypes config."""
 
-    def __init__(self, atom_nf, rec_nf, n_layers, hidden_nf, use_tanh, norm, update_kp_feat, message_norm, ll_k, kl_k,
-                 ll_cutoff, kl_cutoff, coords_range=10.0):
-        self.cfg = KpdEgnnConfig(int(atom_nf), int(rec_nf), int(n_layers), int(hidden_nf), int(bool(use_tanh)),
-                                 int(bool(norm)), int(bool(update_kp_feat)), float(message_norm), int(ll_k), int(kl_k),
-                                 float(ll_cutoff), float(kl_cutoff), float(coords_range))
-        self.atom_nf, self.rec_nf = int(atom_nf), int(rec_nf)
+    def __init__(self, prefix: str, cfg):
+        self._prefix, self.cfg = prefix, cfg
         self._h = C.c_void_p()
-        check(lib().kpd_egnn_create(C.byref(self.cfg), C.byref(self._h)))
-        self._reserved = None
+        check(self._fn('create')(C.byref(self.cfg), C.byref(self._h)))
+
+    def _fn(self, name: str):
+        return getattr(lib(), f'kpd_{self._prefix}_{name}')
 
     def __del__(self):
         if getattr(self, '_h', None) and _lib is not None:
-            _lib.kpd_egnn_destroy(self._h)
+            getattr(_lib, f'kpd_{self._prefix}_destroy')(self._h)
             self._h = None
 
+
+class _Engine(_Handle):
+    """An inference handle: weights are packed once from a state dict."""
+
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
-        L = lib()
-        st = _stream()
-        keep = []
+        load, st = self._fn('load_weight'), _stream()
+        keep = []                                  # the converted copies live until the packing kernels have read them
         for name, t in sd.items():
+            if t.numel() == 0:                     # dropout.vector_dropout.dummy_param
+                continue
             t = _dev_f32(t.detach(), name)
             keep.append(t)
             shape = (C.c_int64 * t.dim())(*t.shape)
-            check(L.kpd_egnn_load_weight(self._h, name.encode(), t.data_ptr(), shape, t.dim(), st))
+            check(load(self._h, name.encode(), t.data_ptr(), shape, t.dim(), st))
         torch.cuda.current_stream().synchronize()     # packing kernels read the source tensors
-        check(L.kpd_egnn_commit(self._h))
+        check(self._fn('commit')(self._h))
+
+
+class _Trainer(_Handle):
+    """A training handle: parameters are bound by reference name to their live storage (read in place every step); gradients
+    are written into the buffers bound for the backward call."""
+
+    def bind(self, names, weights, grads):
+        bind = self._fn('bind')
+        for name, w, g in zip(names, weights, grads):
+            if w.numel() == 0:                     # dropout.vector_dropout.dummy_param
+                continue
+            if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()):
+                raise KpdError(f'parameter {name} must be a contiguous fp32 GPU tensor')
+            shape = (C.c_int64 * w.dim())(*w.shape)
+            check(bind(self._h, name.encode(), w.data_ptr(), None if g is None else g.data_ptr(), shape, w.dim()))
+
+
+class _Denoiser:
+    """What the denoiser handles (engines and trainers) share: the grow-only workspace and the edge counts of the last forward."""
+    _reserved = None
 
     def reserve(self, pb: PreparedBatch):
         key = (pb.B, pb.n_lig, pb.n_kp, pb.n_kk, pb.max_lig, pb.max_kp)
         if self._reserved is not None and all(a <= b for a, b in zip(key, self._reserved)):
             return
-        torch.cuda.synchronize()
-        check(lib().kpd_egnn_reserve(self._h, *key))
+        torch.cuda.synchronize()                   # not stream-ordered: it frees the workspace kernels in flight may still use
+        check(self._fn('reserve')(self._h, *key))
         self._reserved = key if self._reserved is None else tuple(max(a, b) for a, b in zip(key, self._reserved))
+
+    def _counts(self):
+        arr = (C.c_int32 * 8)()
+        check(self._fn('last_counts')(self._h, arr, _stream()))
+        return arr
+
+    def last_counts(self):
+        return dict(zip(('E_ll', 'E_kl', 'E_lk', 'E_kk', 'tiles', 'tiles_last', 'E_last'), self._counts()))
+
+
+class _DenoiserEngine(_Denoiser, _Engine):
+    """The diagnostics of the two inference denoisers."""
+
+    def debug(self, what: str, n_floats: int = 0, device=None) -> Optional[torch.Tensor]:
+        out = torch.empty(max(n_floats, 1), device=device or 'cuda')
+        check(self._fn('debug_state')(self._h, what.encode(), out.data_ptr(), n_floats, _stream()))
+        return out if n_floats else None
+
+    def profile(self, enable: bool):
+        check(self._fn('profile')(self._h, int(enable)))
+
+    def profile_read(self):
+        """(total ms, launches) of the fused edge kernel (EGNN) / the message-chain kernel (GVP) since profile(True)."""
+        ms, n = C.c_double(), C.c_int32()
+        check(self._fn('profile_read')(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def gemm_mode(self) -> str:
+        """The GEMM mode the engine runs in, as the library reports it ('f32' = exact fp32 MFMA, 'f16x2' = split f16 products;
+        the GVP denoiser has 'f16x2' at 256 hidden scalars only)."""
+        return 'f16x2' if self._counts()[7] else 'f32'
+
+    def set_gemm_mode(self, mode: str):
+        self.debug(f'gemm={mode}')
+
+
+class EgnnEngine(_DenoiserEngine):
+    """Owns one kpd_egnn handle: packed weights + workspace for LigRecDynamics.forward."""
+
+    def __init__(self, cfg: KpdEgnnConfig):
+        super().__init__('egnn', cfg)
+        self.atom_nf, self.rec_nf = int(cfg.atom_nf), int(cfg.rec_nf)
 
     def forward(self, pb: PreparedBatch, lig_x, lig_h, kp_x, kp_h, t):
         self.reserve(pb)
@@ -372,34 +406,6 @@ class EgnnEngine:
         check(lib().kpd_egnn_forward(self._h, C.byref(bt), t.data_ptr(), eps_h.data_ptr(), eps_x.data_ptr(), _stream()))
         return eps_h, eps_x
 
-    def debug(self, what: str, n_floats: int = 0, device=None) -> Optional[torch.Tensor]:
-        out = torch.empty(max(n_floats, 1), device=device or 'cuda')
-        check(lib().kpd_egnn_debug_state(self._h, what.encode(), out.data_ptr(), n_floats, _stream()))
-        return out if n_floats else None
-
-    def profile(self, enable: bool):
-        check(lib().kpd_egnn_profile(self._h, int(enable)))
-
-    def profile_read(self):
-        """(total ms, launches) of the fused edge kernel since profile(True)."""
-        ms, n = C.c_double(), C.c_int32()
-        check(lib().kpd_egnn_profile_read(self._h, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-    def last_counts(self):
-        arr = (C.c_int32 * 8)()
-        check(lib().kpd_egnn_last_counts(self._h, arr, _stream()))
-        return dict(E_ll=arr[0], E_kl=arr[1], E_lk=arr[2], E_kk=arr[3], tiles=arr[4], tiles_last=arr[5], E_last=arr[6])
-
-    def gemm_mode(self) -> str:
-        """The GEMM mode the engine runs in, as the library reports it ('f32' = exact fp32 MFMA, 'f16x2' = split f16 products)."""
-        arr = (C.c_int32 * 8)()
-        check(lib().kpd_egnn_last_counts(self._h, arr, _stream()))
-        return 'f16x2' if arr[7] else 'f32'
-
-    def set_gemm_mode(self, mode: str):
-        self.debug(f'gemm={mode}')
-
 
 _PARAM_GEN = [0]
 
@@ -413,41 +419,17 @@ torch.nn.modules.module.register_module_parameter_registration_hook(_on_register
 
 def param_generation() -> int:
     """Counts `register_parameter` calls of every module in the process (a global torch hook): the cached parameter lists of the
-    denoiser modules are rebuilt when it moves, so a swapped Parameter object is never read through a stale list."""
+    engine-owning modules are rebuilt when it moves, so a swapped Parameter object is never read through a stale list."""
     return _PARAM_GEN[0]
 
 
-class EgnnTrainer:
+class EgnnTrainer(_Denoiser, _Trainer):
     """Owns one kpd_egnn_trainer handle: forward with saved layer states + backward of LigRecDynamics.forward.
-    Parameters are bound by reference name to their live storage (read in place every step); gradients are written
-    into fresh zero tensors per backward call and handed to autograd."""
+    Gradients are written into fresh zero tensors per backward call and handed to autograd."""
 
-    def __init__(self, cfg: 'KpdEgnnConfig', atom_nf: int, rec_nf: int):
-        self.cfg, self.atom_nf, self.rec_nf = cfg, int(atom_nf), int(rec_nf)
-        self._h = C.c_void_p()
-        check(lib().kpd_egnn_trainer_create(C.byref(self.cfg), C.byref(self._h)))
-        self._reserved = None
-
-    def __del__(self):
-        if getattr(self, '_h', None) and _lib is not None:
-            _lib.kpd_egnn_trainer_destroy(self._h)
-            self._h = None
-
-    def bind(self, names, weights, grads):
-        L = lib()
-        for name, w, g in zip(names, weights, grads):
-            if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()):
-                raise KpdError(f'parameter {name} must be a contiguous fp32 GPU tensor')
-            shape = (C.c_int64 * w.dim())(*w.shape)
-            check(L.kpd_egnn_trainer_bind(self._h, name.encode(), w.data_ptr(), None if g is None else g.data_ptr(), shape, w.dim()))
-
-    def reserve(self, pb: PreparedBatch):
-        key = (pb.B, pb.n_lig, pb.n_kp, pb.n_kk, pb.max_lig, pb.max_kp)
-        if self._reserved is not None and all(a <= b for a, b in zip(key, self._reserved)):
-            return
-        torch.cuda.synchronize()
-        check(lib().kpd_egnn_trainer_reserve(self._h, *key))
-        self._reserved = key if self._reserved is None else tuple(max(a, b) for a, b in zip(key, self._reserved))
+    def __init__(self, cfg: KpdEgnnConfig):
+        super().__init__('egnn_trainer', cfg)
+        self.atom_nf, self.rec_nf = int(cfg.atom_nf), int(cfg.rec_nf)
 
     def forward(self, pb: PreparedBatch, lig_x, lig_h, kp_x, kp_h, t):
         self.reserve(pb)
@@ -471,52 +453,12 @@ class EgnnTrainer:
         return {'fwd': (ms[0], n[0], e[0]), 'bwd': (ms[1], n[1], e[1])}
 
 
-class GvpEngine:
+class GvpEngine(_DenoiserEngine):
     """Owns one kpd_gvp handle: packed weights + workspace for LigRecDynamicsGVP.forward."""
 
-    def __init__(self, n_lig_scalars, n_kp_scalars, vector_size, n_convs, n_hidden_scalars, update_kp, message_norm,
-                 ll_k, kl_k, ll_cutoff, kl_cutoff, n_message_gvps, n_update_gvps, n_noise_gvps):
-        if message_norm == 'mean':
-            mode, val = 1, 1.0
-        elif message_norm == 0:
-            mode, val = 2, 0.0
-        else:
-            mode, val = 0, float(message_norm)
-        self.cfg = KpdGvpConfig(int(n_lig_scalars), int(n_kp_scalars), int(vector_size), int(n_convs),
-                                int(n_hidden_scalars), int(bool(update_kp)), mode, val, int(ll_k), int(kl_k),
-                                float(ll_cutoff), float(kl_cutoff), int(n_message_gvps), int(n_update_gvps),
-                                int(n_noise_gvps))
-        self.n_lig_scalars = int(n_lig_scalars)
-        self._h = C.c_void_p()
-        check(lib().kpd_gvp_create(C.byref(self.cfg), C.byref(self._h)))
-        self._reserved = None
-
-    def __del__(self):
-        if getattr(self, '_h', None) and _lib is not None:
-            _lib.kpd_gvp_destroy(self._h)
-            self._h = None
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]):
-        L = lib()
-        st = _stream()
-        keep = []
-        for name, t in sd.items():
-            if t.numel() == 0:                     # dropout.vector_dropout.dummy_param
-                continue
-            t = _dev_f32(t.detach(), name)
-            keep.append(t)
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            check(L.kpd_gvp_load_weight(self._h, name.encode(), t.data_ptr(), shape, t.dim(), st))
-        torch.cuda.current_stream().synchronize()
-        check(L.kpd_gvp_commit(self._h))
-
-    def reserve(self, pb: PreparedBatch):
-        key = (pb.B, pb.n_lig, pb.n_kp, pb.n_kk, pb.max_lig, pb.max_kp)
-        if self._reserved is not None and all(a <= b for a, b in zip(key, self._reserved)):
-            return
-        torch.cuda.synchronize()
-        check(lib().kpd_gvp_reserve(self._h, *key))
-        self._reserved = key if self._reserved is None else tuple(max(a, b) for a, b in zip(key, self._reserved))
+    def __init__(self, cfg: KpdGvpConfig):
+        super().__init__('gvp', cfg)
+        self.n_lig_scalars = int(cfg.n_lig_scalars)
 
     def forward(self, pb: PreparedBatch, lig_x, lig_h, kp_x, kp_h, kp_v, t):
         self.reserve(pb)
@@ -531,66 +473,12 @@ class GvpEngine:
         check(lib().kpd_gvp_forward(self._h, C.byref(bt), t.data_ptr(), eps_h.data_ptr(), eps_x.data_ptr(), _stream()))
         return eps_h, eps_x
 
-    def debug(self, what: str, n_floats: int = 0, device=None) -> Optional[torch.Tensor]:
-        out = torch.empty(max(n_floats, 1), device=device or 'cuda')
-        check(lib().kpd_gvp_debug_state(self._h, what.encode(), out.data_ptr(), n_floats, _stream()))
-        return out if n_floats else None
 
-    def profile(self, enable: bool):
-        check(lib().kpd_gvp_profile(self._h, int(enable)))
-
-    def profile_read(self):
-        """(total ms, launches) of the message-chain kernel since profile(True)."""
-        ms, n = C.c_double(), C.c_int32()
-        check(lib().kpd_gvp_profile_read(self._h, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-    def last_counts(self):
-        arr = (C.c_int32 * 8)()
-        check(lib().kpd_gvp_last_counts(self._h, arr, _stream()))
-        return dict(E_ll=arr[0], E_kl=arr[1], E_lk=arr[2], E_kk=arr[3], tiles=arr[4], tiles_last=arr[5], E_last=arr[6])
-
-    def gemm_mode(self) -> str:
-        """The GEMM mode the engine runs in, as the library reports it ('f16x2' needs 256 hidden scalars; otherwise 'f32')."""
-        arr = (C.c_int32 * 8)()
-        check(lib().kpd_gvp_last_counts(self._h, arr, _stream()))
-        return 'f16x2' if arr[7] else 'f32'
-
-    def set_gemm_mode(self, mode: str):
-        self.debug(f'gemm={mode}')
-
-
-class GvpTrainer:
+class GvpTrainer(_Denoiser, _Trainer):
     """Owns one kpd_gvp_trainer handle: forward with saved conv states + backward of LigRecDynamicsGVP.forward."""
 
-    def __init__(self, cfg: 'KpdGvpConfig'):
-        self.cfg = cfg
-        self._h = C.c_void_p()
-        check(lib().kpd_gvp_trainer_create(C.byref(self.cfg), C.byref(self._h)))
-        self._reserved = None
-
-    def __del__(self):
-        if getattr(self, '_h', None) and _lib is not None:
-            _lib.kpd_gvp_trainer_destroy(self._h)
-            self._h = None
-
-    def bind(self, names, weights, grads):
-        L = lib()
-        for name, w, g in zip(names, weights, grads):
-            if w.numel() == 0:                     # dropout.vector_dropout.dummy_param
-                continue
-            if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()):
-                raise KpdError(f'parameter {name} must be a contiguous fp32 GPU tensor')
-            shape = (C.c_int64 * w.dim())(*w.shape)
-            check(L.kpd_gvp_trainer_bind(self._h, name.encode(), w.data_ptr(), None if g is None else g.data_ptr(), shape, w.dim()))
-
-    def reserve(self, pb: PreparedBatch):
-        key = (pb.B, pb.n_lig, pb.n_kp, pb.n_kk, pb.max_lig, pb.max_kp)
-        if self._reserved is not None and all(a <= b for a, b in zip(key, self._reserved)):
-            return
-        torch.cuda.synchronize()
-        check(lib().kpd_gvp_trainer_reserve(self._h, *key))
-        self._reserved = key if self._reserved is None else tuple(max(a, b) for a, b in zip(key, self._reserved))
+    def __init__(self, cfg: KpdGvpConfig):
+        super().__init__('gvp_trainer', cfg)
 
     def set_dropout(self, rate: float, seed: int):
         check(lib().kpd_gvp_trainer_set_dropout(self._h, float(rate), int(seed) & (2 ** 64 - 1)))
@@ -607,10 +495,10 @@ class GvpTrainer:
         check(lib().kpd_gvp_trainer_backward(self._h, d_eps_h.data_ptr(), d_eps_x.data_ptr(), _ptr(d_lig_h), _ptr(d_kp_h), _ptr(d_kp_v),
                                              _ptr(d_lig_x), _ptr(d_kp_x), _stream()))
 
-    def last_counts(self):
-        arr = (C.c_int32 * 4)()
+    def _counts(self):
+        arr = (C.c_int32 * 4)()                    # the four edge counts only: `last_counts` has four entries here
         check(lib().kpd_gvp_trainer_last_counts(self._h, arr))
-        return dict(E_ll=arr[0], E_kl=arr[1], E_lk=arr[2], E_kk=arr[3])
+        return arr
 
     def message_path(self) -> int:
         """1: the convs' edge messages run through the register-chained kernels (hidden width 256), 0: one GVP at a time."""
@@ -648,165 +536,90 @@ def sorted_csr(src: torch.Tensor, dst: torch.Tensor, n_dst: int, device, return_
     return out + (order,) if return_order else out
 
 
-class RecEncEngine:
-    """Owns one kpd_recenc handle: packed weights + workspace for ReceptorEncoderGVP.forward."""
-
-    def __init__(self, in_scalar_size, out_scalar_size, vector_size, n_rr_convs, n_rk_convs, n_message_gvps, n_update_gvps,
-                 message_norm, k_closest, n_keypoints, rr_cutoff, rk_cutoff, kk_cutoff, kp_rad=0.0):
-        mode, val = _norm_mode(message_norm)
-        self.cfg = KpdRecencConfig(int(in_scalar_size), int(out_scalar_size), int(vector_size), int(n_rr_convs),
-                                   int(n_rk_convs), int(n_message_gvps), int(n_update_gvps), mode, val, int(k_closest),
-                                   int(n_keypoints), float(rr_cutoff), float(rk_cutoff), float(kk_cutoff), float(kp_rad))
-        # rk edges per keypoint: k of the kNN graph, or at most 10 of the radius graph (receptor_encoder_gvp.py:306)
-        self.S, self.K, self.k = int(out_scalar_size), int(n_keypoints), int(k_closest) if k_closest else 10
-        self._h = C.c_void_p()
-        check(lib().kpd_recenc_create(C.byref(self.cfg), C.byref(self._h)))
-
-    def __del__(self):
-        if getattr(self, '_h', None) and _lib is not None:
-            _lib.kpd_recenc_destroy(self._h)
-            self._h = None
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]):
-        L = lib()
-        st = _stream()
-        keep = []
-        for name, t in sd.items():
-            if t.numel() == 0:
-                continue
-            t = _dev_f32(t.detach(), name)
-            keep.append(t)
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            check(L.kpd_recenc_load_weight(self._h, name.encode(), t.data_ptr(), shape, t.dim(), st))
-        torch.cuda.current_stream().synchronize()
-        check(L.kpd_recenc_commit(self._h))
-
-    def forward(self, rec_counts: torch.Tensor, rec_x, rec_h, rr_src, rr_dst):
-        return _recenc_call(self, lib().kpd_recenc_reserve, lib().kpd_recenc_forward, rec_counts, rec_x, rec_h, rr_src, rr_dst)
-
-
-def _recenc_call(eng, reserve_fn, forward_fn, rec_counts, rec_x, rec_h, rr_src, rr_dst):
-    """Shared by RecEncEngine.forward and RecEncTrainer.forward: batch structs, output buffers, one library call."""
+def _rec_batch(eng, rec_counts, rec_x, rec_h, rr_src, rr_dst):
+    """The head the two encoder calls share: sizes and offsets of the batch, the dst-sorted rr graph with its permutation (for edge
+    data), the workspace of `eng` reserved for them, and the batch struct."""
     dev = rec_x.device
     rec_counts = rec_counts.cpu().long()
     B, n_rec, max_rec = int(rec_counts.numel()), int(rec_counts.sum()), int(rec_counts.max())
-    if int(rec_counts.min()) < 1:
-        raise KpdError('every pocket needs at least one receptor atom')
     rec_ptr = torch.cat([torch.zeros(1, dtype=torch.long), rec_counts.cumsum(0)]).int().to(dev)
     rec_x, rec_h = _dev_f32(rec_x, 'rec x_0'), _dev_f32(rec_h, 'rec h_0')
-    s, d, rowptr = sorted_csr(rr_src, rr_dst, n_rec, dev)
-    torch.cuda.synchronize()
-    check(reserve_fn(eng._h, B, n_rec, int(s.numel()), max_rec))
+    s, d, rowptr, order = sorted_csr(rr_src, rr_dst, n_rec, dev, return_order=True)
+    torch.cuda.synchronize()                       # as in _Denoiser.reserve
+    check(eng._fn('reserve')(eng._h, B, n_rec, int(s.numel()), max_rec))
+    bt = KpdRecBatch(B, n_rec, max_rec, _ptr(rec_ptr), _ptr(rec_x), _ptr(rec_h), int(s.numel()), _ptr(s), _ptr(d), _ptr(rowptr))
+    return B, n_rec, max_rec, rec_ptr, rec_x, rec_h, s, d, rowptr, order, bt
+
+
+def _trim_edges(out):
+    """The tail the two encoder calls share: cut the kk / rk edge lists to the counts the library wrote."""
+    e_kk, e_rk = out['counts'].tolist()            # once per pocket: a host sync here is fine
+    out['kk_src'], out['kk_dst'] = out['kk_src'][:e_kk], out['kk_dst'][:e_kk]
+    out['rk_src'], out['rk_dst'] = out['rk_src'][:e_rk], out['rk_dst'][:e_rk]
+
+
+def _recenc_call(eng, rec_counts, rec_x, rec_h, rr_src, rr_dst):
+    """RecEncEngine.forward and RecEncTrainer.forward: batch structs, output buffers, one library call."""
+    dev = rec_x.device
+    if int(rec_counts.min()) < 1:
+        raise KpdError('every pocket needs at least one receptor atom')
+    B, n_rec, max_rec, rec_ptr, rec_x, rec_h, s, d, rowptr, _, bt = _rec_batch(eng, rec_counts, rec_x, rec_h, rr_src, rr_dst)
     n_kp = B * eng.K
     cap_kk = max(n_kp * min(eng.K - 1, 100), 1)
     f32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
     i32 = lambda n: torch.zeros(n, device=dev, dtype=torch.int32)
     out = dict(kp_x=f32(n_kp, 3), kp_h=f32(n_kp, eng.S), kp_v=f32(n_kp, int(eng.cfg.vector_size), 3), rk_src=i32(n_kp * eng.k),
                rk_dst=i32(n_kp * eng.k), kk_src=i32(cap_kk), kk_dst=i32(cap_kk), kk_per_graph=i32(B), counts=i32(2))
-    bt = KpdRecBatch(B, n_rec, max_rec, _ptr(rec_ptr), _ptr(rec_x), _ptr(rec_h), int(s.numel()), _ptr(s), _ptr(d),
-                     _ptr(rowptr))
     ro = KpdRecOut(_ptr(out['kp_x']), _ptr(out['kp_h']), _ptr(out['kp_v']), _ptr(out['rk_src']), _ptr(out['rk_dst']),
                    cap_kk, _ptr(out['kk_src']), _ptr(out['kk_dst']), _ptr(out['kk_per_graph']), _ptr(out['counts']))
-    check(forward_fn(eng._h, C.byref(bt), C.byref(ro), _stream()))
-    e_kk, e_rk = out['counts'].tolist()            # once per pocket: a host sync here is fine
-    out['kk_src'], out['kk_dst'] = out['kk_src'][:e_kk], out['kk_dst'][:e_kk]
-    out['rk_src'], out['rk_dst'] = out['rk_src'][:e_rk], out['rk_dst'][:e_rk]
+    check(eng._fn('forward')(eng._h, C.byref(bt), C.byref(ro), _stream()))
+    _trim_edges(out)
     out['_keep'] = (rec_ptr, rec_x, rec_h, s, d, rowptr)      # the training engine reads these again in its backward pass
     return out
 
 
-class RecEncTrainer:
-    """Owns one kpd_recenc_trainer handle: ReceptorEncoderGVP.forward with saved node states + its backward pass.  Parameters
-    are bound by reference name to live storage; gradients are accumulated into the buffers bound for the backward call."""
+class _RecEnc:
+    """What RecEncEngine and RecEncTrainer share: the sizes read from the config, and forward."""
 
-    def __init__(self, cfg: 'KpdRecencConfig'):
-        self.cfg = cfg
-        self.S, self.K = int(cfg.out_scalar_size), int(cfg.n_keypoints)
-        self.k = int(cfg.k_closest) if cfg.k_closest else 10
-        self._h = C.c_void_p()
-        check(lib().kpd_recenc_trainer_create(C.byref(self.cfg), C.byref(self._h)))
+    def __init__(self, prefix: str, cfg: KpdRecencConfig):
+        super().__init__(prefix, cfg)
+        # rk edges per keypoint: k of the kNN graph, or at most 10 of the radius graph (receptor_encoder_gvp.py:306)
+        self.S, self.K, self.k = int(cfg.out_scalar_size), int(cfg.n_keypoints), int(cfg.k_closest) if cfg.k_closest else 10
 
-    def __del__(self):
-        if getattr(self, '_h', None) and _lib is not None:
-            _lib.kpd_recenc_trainer_destroy(self._h)
-            self._h = None
+    def forward(self, rec_counts: torch.Tensor, rec_x, rec_h, rr_src, rr_dst):
+        return _recenc_call(self, rec_counts, rec_x, rec_h, rr_src, rr_dst)
 
-    def bind(self, names, weights, grads):
-        L = lib()
-        for name, w, g in zip(names, weights, grads):
-            if w.numel() == 0:                     # dropout.vector_dropout.dummy_param
-                continue
-            if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()):
-                raise KpdError(f'parameter {name} must be a contiguous fp32 GPU tensor')
-            shape = (C.c_int64 * w.dim())(*w.shape)
-            check(L.kpd_recenc_trainer_bind(self._h, name.encode(), w.data_ptr(), None if g is None else g.data_ptr(), shape, w.dim()))
+
+class RecEncEngine(_RecEnc, _Engine):
+    """Owns one kpd_recenc handle: packed weights + workspace for ReceptorEncoderGVP.forward."""
+
+    def __init__(self, cfg: KpdRecencConfig):
+        super().__init__('recenc', cfg)
+
+
+class RecEncTrainer(_RecEnc, _Trainer):
+    """Owns one kpd_recenc_trainer handle: ReceptorEncoderGVP.forward with saved node states + its backward pass."""
+
+    def __init__(self, cfg: KpdRecencConfig):
+        super().__init__('recenc_trainer', cfg)
 
     def set_dropout(self, rate: float, seed: int):
         check(lib().kpd_recenc_trainer_set_dropout(self._h, float(rate), int(seed) & (2 ** 64 - 1)))
-
-    def forward(self, rec_counts, rec_x, rec_h, rr_src, rr_dst):
-        return _recenc_call(self, lib().kpd_recenc_trainer_reserve, lib().kpd_recenc_trainer_forward, rec_counts, rec_x, rec_h,
-                            rr_src, rr_dst)
 
     def backward(self, d_kp_x, d_kp_h, d_kp_v):
         check(lib().kpd_recenc_trainer_backward(self._h, _ptr(d_kp_x), _ptr(d_kp_h), _ptr(d_kp_v), _stream()))
 
 
-class RecEgnnEngine:
-    """Owns one kpd_recegnn handle: weights + workspace for ReceptorEncoder.forward (models/receptor_encoder.py)."""
-
-    def __init__(self, n_convs, n_keypoints, in_n_node_feat, hidden_n_node_feat, out_n_node_feat, use_sameres_feat, use_tanh,
-                 coords_range, message_norm, k_closest, norm, fix_pos, kk_cutoff, kp_rad=0.0):
-        self.cfg = KpdRecegnnConfig(int(n_convs), int(n_keypoints), int(in_n_node_feat), int(hidden_n_node_feat),
-                                    int(out_n_node_feat), int(bool(use_sameres_feat)), int(bool(use_tanh)), int(bool(norm)),
-                                    int(bool(fix_pos)), float(coords_range), float(message_norm), int(k_closest), float(kk_cutoff),
-                                    float(kp_rad))
-        self.D, self.K, self.k, self.ef = int(out_n_node_feat), int(n_keypoints), int(k_closest), bool(use_sameres_feat)
-        self.rk_cap = int(k_closest) if k_closest else 100       # rk edges per keypoint: k, or at most 100 within kp_rad (:246)
-        self._h = C.c_void_p()
-        check(lib().kpd_recegnn_create(C.byref(self.cfg), C.byref(self._h)))
-
-    def __del__(self):
-        if getattr(self, '_h', None) and _lib is not None:
-            _lib.kpd_recegnn_destroy(self._h)
-            self._h = None
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]):
-        L = lib()
-        st = _stream()
-        keep = []
-        for name, t in sd.items():
-            if t.numel() == 0:
-                continue
-            t = _dev_f32(t.detach(), name)
-            keep.append(t)
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            check(L.kpd_recegnn_load_weight(self._h, name.encode(), t.data_ptr(), shape, t.dim(), st))
-        torch.cuda.current_stream().synchronize()
-        check(L.kpd_recegnn_commit(self._h))
-
-    def forward(self, rec_counts: torch.Tensor, rec_x, rec_h, rr_src, rr_dst, same_res=None):
-        return _recegnn_call(self, lib().kpd_recegnn_reserve, lib().kpd_recegnn_forward, rec_counts, rec_x, rec_h, rr_src, rr_dst, same_res)
-
-
-def _recegnn_call(eng, reserve_fn, forward_fn, rec_counts, rec_x, rec_h, rr_src, rr_dst, same_res):
-    """Shared by RecEgnnEngine.forward and RecEgnnTrainer.forward."""
+def _recegnn_call(eng, rec_counts, rec_x, rec_h, rr_src, rr_dst, same_res):
+    """RecEgnnEngine.forward and RecEgnnTrainer.forward."""
     dev = rec_x.device
-    rec_counts = rec_counts.cpu().long()
-    B, n_rec, max_rec = int(rec_counts.numel()), int(rec_counts.sum()), int(rec_counts.max())
     if int(rec_counts.min()) < eng.k:
         raise KpdError(f'every pocket needs at least k_closest={eng.k} receptor atoms (the reference stacks exactly k '
                        f'neighbour distances per keypoint)')
-    rec_ptr = torch.cat([torch.zeros(1, dtype=torch.long), rec_counts.cumsum(0)]).int().to(dev)
-    rec_x, rec_h = _dev_f32(rec_x, 'rec x_0'), _dev_f32(rec_h, 'rec h_0')
-    s, d, rowptr, order = sorted_csr(rr_src, rr_dst, n_rec, dev, return_order=True)
-    a = None
-    if eng.ef:
-        if same_res is None:
-            raise KpdError("use_sameres_feat needs g.edges['rr'].data['same_res']")
-        a = same_res.to(dev).reshape(-1)[order].float().contiguous()
-    torch.cuda.synchronize()
-    check(reserve_fn(eng._h, B, n_rec, int(s.numel()), max_rec))
+    if eng.ef and same_res is None:
+        raise KpdError("use_sameres_feat needs g.edges['rr'].data['same_res']")
+    B, n_rec, max_rec, rec_ptr, rec_x, rec_h, s, d, rowptr, order, bt = _rec_batch(eng, rec_counts, rec_x, rec_h, rr_src, rr_dst)
+    a = same_res.to(dev).reshape(-1)[order].float().contiguous() if eng.ef else None
     n_kp = B * eng.K
     cap_kk = max(n_kp * min(eng.K - 1, 100), 1)
     f32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
@@ -815,46 +628,38 @@ def _recegnn_call(eng, reserve_fn, forward_fn, rec_counts, rec_x, rec_h, rr_src,
     out = dict(kp_x=f32(n_kp, 3), kp_h=f32(n_kp, eng.D), rk_src=i32(cap_rk), rk_dst=i32(cap_rk),
                kk_src=i32(cap_kk), kk_dst=i32(cap_kk), kk_per_graph=i32(B), counts=i32(2), rec_h=f32(n_rec, eng.D),
                rec_x=f32(n_rec, 3))
-    bt = KpdRecBatch(B, n_rec, max_rec, _ptr(rec_ptr), _ptr(rec_x), _ptr(rec_h), int(s.numel()), _ptr(s), _ptr(d), _ptr(rowptr))
     ro = KpdRecOut(_ptr(out['kp_x']), _ptr(out['kp_h']), None, _ptr(out['rk_src']), _ptr(out['rk_dst']), cap_kk,
                    _ptr(out['kk_src']), _ptr(out['kk_dst']), _ptr(out['kk_per_graph']), _ptr(out['counts']))
-    check(forward_fn(eng._h, C.byref(bt), _ptr(a) if a is not None else None, C.byref(ro), _ptr(out['rec_h']),
-                     _ptr(out['rec_x']), _stream()))
-    e_kk, e_rk = out['counts'].tolist()            # once per pocket: a host sync here is fine
-    out['kk_src'], out['kk_dst'] = out['kk_src'][:e_kk], out['kk_dst'][:e_kk]
-    out['rk_src'], out['rk_dst'] = out['rk_src'][:e_rk], out['rk_dst'][:e_rk]
+    check(eng._fn('forward')(eng._h, C.byref(bt), _ptr(a), C.byref(ro), _ptr(out['rec_h']), _ptr(out['rec_x']), _stream()))
+    _trim_edges(out)
     out['_keep'] = (rec_ptr, rec_x, rec_h, s, d, rowptr, a)      # the training engine reads these again in its backward pass
     return out
 
 
-class RecEgnnTrainer:
+class _RecEgnn:
+    """What RecEgnnEngine and RecEgnnTrainer share: the sizes read from the config, and forward."""
+
+    def __init__(self, prefix: str, cfg: KpdRecegnnConfig):
+        super().__init__(prefix, cfg)
+        self.D, self.K, self.k, self.ef = int(cfg.out_n_node_feat), int(cfg.n_keypoints), int(cfg.k_closest), bool(cfg.use_sameres_feat)
+        self.rk_cap = self.k if self.k else 100    # rk edges per keypoint: k, or at most 100 within kp_rad (:246)
+
+    def forward(self, rec_counts: torch.Tensor, rec_x, rec_h, rr_src, rr_dst, same_res=None):
+        return _recegnn_call(self, rec_counts, rec_x, rec_h, rr_src, rr_dst, same_res)
+
+
+class RecEgnnEngine(_RecEgnn, _Engine):
+    """Owns one kpd_recegnn handle: weights + workspace for ReceptorEncoder.forward (models/receptor_encoder.py)."""
+
+    def __init__(self, cfg: KpdRecegnnConfig):
+        super().__init__('recegnn', cfg)
+
+
+class RecEgnnTrainer(_RecEgnn, _Trainer):
     """Owns one kpd_recegnn_trainer handle: ReceptorEncoder.forward with saved layer states + its backward pass."""
 
-    def __init__(self, cfg: 'KpdRecegnnConfig'):
-        self.cfg = cfg
-        self.D, self.K, self.k, self.ef = int(cfg.out_n_node_feat), int(cfg.n_keypoints), int(cfg.k_closest), bool(cfg.use_sameres_feat)
-        self.rk_cap = self.k if self.k else 100                   # rk edges per keypoint: k, or at most 100 within kp_rad
-        self._h = C.c_void_p()
-        check(lib().kpd_recegnn_trainer_create(C.byref(self.cfg), C.byref(self._h)))
-
-    def __del__(self):
-        if getattr(self, '_h', None) and _lib is not None:
-            _lib.kpd_recegnn_trainer_destroy(self._h)
-            self._h = None
-
-    def bind(self, names, weights, grads):
-        L = lib()
-        for name, w, g in zip(names, weights, grads):
-            if w.numel() == 0:
-                continue
-            if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()):
-                raise KpdError(f'parameter {name} must be a contiguous fp32 GPU tensor')
-            shape = (C.c_int64 * w.dim())(*w.shape)
-            check(L.kpd_recegnn_trainer_bind(self._h, name.encode(), w.data_ptr(), None if g is None else g.data_ptr(), shape, w.dim()))
-
-    def forward(self, rec_counts, rec_x, rec_h, rr_src, rr_dst, same_res=None):
-        return _recegnn_call(self, lib().kpd_recegnn_trainer_reserve, lib().kpd_recegnn_trainer_forward, rec_counts, rec_x, rec_h,
-                             rr_src, rr_dst, same_res)
+    def __init__(self, cfg: KpdRecegnnConfig):
+        super().__init__('recegnn_trainer', cfg)
 
     def backward(self, d_kp_x, d_kp_h):
         check(lib().kpd_recegnn_trainer_backward(self._h, _ptr(d_kp_x), _ptr(d_kp_h), _stream()))

@@ -6,6 +6,8 @@ from typing import Dict
 import torch
 import torch.nn as nn
 
+from . import hip
+from .engine_owner import EngineOwner, train_backward, train_forward
 from .graph import HeteroBatch, get_batch_info
 
 
@@ -15,12 +17,7 @@ class _RecEgnnTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, rec_counts, rec_x, rec_h, rr_src, rr_dst, same_res, holder, *params):
-        trainer, names = module._trainer()
-        ctx.trainer, ctx.names = trainer, names
-        trainer.generation = getattr(trainer, 'generation', 0) + 1
-        ctx.generation = trainer.generation
-        ctx.save_for_backward(*params)
-        trainer.bind(names, params, [None] * len(params))
+        trainer = train_forward(ctx, module, params)
         out = trainer.forward(rec_counts, rec_x, rec_h, rr_src, rr_dst, same_res)
         ctx.keep = out.pop('_keep')                                 # device copies the C side reads again in backward
         holder.update(out)
@@ -28,13 +25,7 @@ class _RecEgnnTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_x, d_h):
-        from . import hip
-        if ctx.generation != ctx.trainer.generation:
-            raise hip.KpdError('backward of a ReceptorEncoder forward whose saved states were overwritten by a later grad-enabled '
-                               'forward of the same module (one forward/backward pair at a time per module)')
-        params = ctx.saved_tensors
-        grads = hip.zero_grads_like(params, [ctx.needs_input_grad[8 + i] for i in range(len(params))])
-        ctx.trainer.bind(ctx.names, params, grads)
+        grads = train_backward(ctx, 8, 'ReceptorEncoder', 'states')
         c = lambda t: None if t is None else t.contiguous().float()
         ctx.trainer.backward(c(d_x), c(d_h))
         return (None,) * 8 + tuple(grads)
@@ -75,7 +66,7 @@ class RecKeyConv(nn.Module):
         self.layer_norm = nn.LayerNorm(out_feats) if norm else nn.Identity()
 
 
-class ReceptorEncoder(nn.Module):
+class ReceptorEncoder(EngineOwner, nn.Module):
 
     def __init__(self, n_convs: int = 6, n_keypoints: int = 10, graph_cutoffs: dict = {}, in_n_node_feat: int = 13,
                  use_sameres_feat: bool = False, hidden_n_node_feat: int = 256, out_n_node_feat: int = 256, use_tanh=True,
@@ -107,31 +98,18 @@ class ReceptorEncoder(nn.Module):
         self.keypoint_embedding = nn.Sequential(nn.Linear(out_n_node_feat, out_n_node_feat * n_keypoints), nn.SiLU())
         self.rec_kp_conv = RecKeyConv(in_feats=out_n_node_feat, out_feats=out_n_node_feat, n_keypoints=n_keypoints, fix_pos=fix_pos,
                                       num_heads=1, k_closest=k_closest, kp_rad=kp_rad, norm=norm)
-        self._engine = None
-        self._engine_key = None
-        self._train = None
 
-    def _trainer(self):
-        """The training engine and the parameter names in `self.parameters()` order (reference state-dict names)."""
-        from . import hip
-        if self._train is None:
-            cfg = hip.KpdRecegnnConfig(int(self.n_convs), int(self.n_keypoints), int(self.in_n_node_feat), int(self.hidden_n_node_feat),
-                                       int(self.out_n_node_feat), int(bool(self.use_sameres_feat)), int(bool(self.use_tanh)),
-                                       int(bool(self.norm)), int(bool(self.fix_pos)), float(self.coords_range), float(self.message_norm),
-                                       int(self.k_closest), float(self.graph_cutoffs['kk']), float(self.kp_rad))
-            self._train = (hip.RecEgnnTrainer(cfg), [n for n, _ in self.named_parameters()])
-        return self._train
+    def _config(self) -> 'hip.KpdRecegnnConfig':
+        return hip.KpdRecegnnConfig(int(self.n_convs), int(self.n_keypoints), int(self.in_n_node_feat), int(self.hidden_n_node_feat),
+                                    int(self.out_n_node_feat), int(bool(self.use_sameres_feat)), int(bool(self.use_tanh)),
+                                    int(bool(self.norm)), int(bool(self.fix_pos)), float(self.coords_range), float(self.message_norm),
+                                    int(self.k_closest), float(self.graph_cutoffs['kk']), float(self.kp_rad))
 
-    def engine(self):
-        from . import hip
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._engine is None or key != self._engine_key:
-            eng = hip.RecEgnnEngine(self.n_convs, self.n_keypoints, self.in_n_node_feat, self.hidden_n_node_feat, self.out_n_node_feat,
-                                    self.use_sameres_feat, self.use_tanh, self.coords_range, self.message_norm, self.k_closest,
-                                    self.norm, self.fix_pos, self.graph_cutoffs['kk'], kp_rad=self.kp_rad)
-            eng.load_state_dict(self.state_dict())
-            self._engine, self._engine_key = eng, key
-        return self._engine
+    def _build_engine(self):
+        return hip.RecEgnnEngine(self._config())
+
+    def _build_trainer(self):
+        return hip.RecEgnnTrainer(self._config())
 
     def forward(self, g: HeteroBatch, batch_idxs: Dict[str, torch.Tensor] = None) -> HeteroBatch:
         """Writes keypoint x_0 / h_0, replaces the rk edges by the kNN edges and adds the kk radius graph

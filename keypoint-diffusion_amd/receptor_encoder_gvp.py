@@ -7,6 +7,8 @@ from typing import Dict, Union
 import torch
 import torch.nn as nn
 
+from . import hip
+from .engine_owner import EngineOwner, train_backward, train_forward
 from .graph import HeteroBatch, get_batch_info
 from .gvp import GVPEdgeConv
 
@@ -17,12 +19,7 @@ class _RecEncTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, rec_counts, rec_x, rec_h, rr_src, rr_dst, holder, *params):
-        trainer, names = module._trainer()
-        ctx.trainer, ctx.names = trainer, names
-        trainer.generation = getattr(trainer, 'generation', 0) + 1
-        ctx.generation = trainer.generation
-        ctx.save_for_backward(*params)
-        trainer.bind(names, params, [None] * len(params))
+        trainer = train_forward(ctx, module, params)
         rate = module.dropout_rate if module.training else 0.0
         module.last_dropout_seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if rate > 0 else 0
         trainer.set_dropout(rate, module.last_dropout_seed)
@@ -33,13 +30,7 @@ class _RecEncTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_x, d_h, d_v):
-        from . import hip
-        if ctx.generation != ctx.trainer.generation:
-            raise hip.KpdError('backward of a ReceptorEncoderGVP forward whose saved states were overwritten by a later grad-enabled '
-                               'forward of the same module (one forward/backward pair at a time per module)')
-        params = ctx.saved_tensors
-        grads = hip.zero_grads_like(params, [ctx.needs_input_grad[7 + i] for i in range(len(params))])
-        ctx.trainer.bind(ctx.names, params, grads)
+        grads = train_backward(ctx, 7, 'ReceptorEncoderGVP', 'states')
         c = lambda t: None if t is None else t.contiguous().float()
         ctx.trainer.backward(c(d_x), c(d_h), c(d_v))
         return (None,) * 7 + tuple(grads)
@@ -58,7 +49,7 @@ class KeypointInitializer(nn.Module):
         self.norm = nn.LayerNorm(scalar_size)
 
 
-class ReceptorEncoderGVP(nn.Module):
+class ReceptorEncoderGVP(EngineOwner, nn.Module):
 
     def __init__(self, in_scalar_size: int, out_scalar_size: int = 128, n_message_gvps: int = 1, n_update_gvps: int = 1,
                  vector_size: int = 16, n_rr_convs: int = 3, n_rk_convs: int = 2, message_norm: Union[float, str] = 10,
@@ -96,41 +87,27 @@ class ReceptorEncoderGVP(nn.Module):
              for i in range(n_rk_convs)])
 
         self.dropout_rate = dropout
-        self._engine = None
-        self._engine_key = None
-        self._train = None
 
-    def _trainer(self):
-        """The training engine and the parameter names in `self.parameters()` order (reference state-dict names)."""
-        from . import hip
-        if self._train is None:
-            if self.use_sameres_feat:
-                raise NotImplementedError('use_sameres_feat=True cannot run in the reference GVP encoder; every shipped config sets it to False')
-            mode, val = hip._norm_mode(self.message_norm)
-            cfg = hip.KpdRecencConfig(int(self.in_scalar_size), int(self.out_scalar_size), int(self.vector_size), int(self.n_rr_convs),
-                                      int(self.n_rk_convs), int(self.n_message_gvps), int(self.n_update_gvps), mode, val,
-                                      int(self.k_closest), int(self.n_keypoints), float(self.graph_cutoffs['rr']),
-                                      float(self.graph_cutoffs['rk']), float(self.graph_cutoffs['kk']), float(self.kp_rad))
-            self._train = (hip.RecEncTrainer(cfg), [n for n, _ in self.named_parameters()])
-        return self._train
+    def _config(self) -> 'hip.KpdRecencConfig':
+        mode, val = hip._norm_mode(self.message_norm)
+        return hip.KpdRecencConfig(int(self.in_scalar_size), int(self.out_scalar_size), int(self.vector_size), int(self.n_rr_convs),
+                                   int(self.n_rk_convs), int(self.n_message_gvps), int(self.n_update_gvps), mode, val,
+                                   int(self.k_closest), int(self.n_keypoints), float(self.graph_cutoffs['rr']),
+                                   float(self.graph_cutoffs['rk']), float(self.graph_cutoffs['kk']), float(self.kp_rad))
 
-    def engine(self):
-        from . import hip
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._engine is None or key != self._engine_key:
-            if self.use_sameres_feat:
-                # upstream this switch cannot run: forward reads g.edges['rr'].data['a'] (receptor_encoder_gvp.py:230), a key no
-                # dataset writes (pdbbind_processing.py:272 stores 'same_res'), and the rk convolutions are built with
-                # edge_feat_size = 1 but called without edge features (:176-208, :279-281)
-                raise NotImplementedError('use_sameres_feat=True cannot run in the reference GVP encoder (it reads an edge feature "a" '
-                                          'that no dataset provides); every shipped config sets it to False')
-            eng = hip.RecEncEngine(self.in_scalar_size, self.out_scalar_size, self.vector_size, self.n_rr_convs,
-                                   self.n_rk_convs, self.n_message_gvps, self.n_update_gvps, self.message_norm,
-                                   self.k_closest, self.n_keypoints, self.graph_cutoffs['rr'], self.graph_cutoffs['rk'],
-                                   self.graph_cutoffs['kk'], kp_rad=self.kp_rad)
-            eng.load_state_dict(self.state_dict())
-            self._engine, self._engine_key = eng, key
-        return self._engine
+    def _build_engine(self):
+        if self.use_sameres_feat:
+            # upstream this switch cannot run: forward reads g.edges['rr'].data['a'] (receptor_encoder_gvp.py:230), a key no
+            # dataset writes (pdbbind_processing.py:272 stores 'same_res'), and the rk convolutions are built with
+            # edge_feat_size = 1 but called without edge features (:176-208, :279-281)
+            raise NotImplementedError('use_sameres_feat=True cannot run in the reference GVP encoder (it reads an edge feature "a" '
+                                      'that no dataset provides); every shipped config sets it to False')
+        return hip.RecEncEngine(self._config())
+
+    def _build_trainer(self):
+        if self.use_sameres_feat:
+            raise NotImplementedError('use_sameres_feat=True cannot run in the reference GVP encoder; every shipped config sets it to False')
+        return hip.RecEncTrainer(self._config())
 
     def forward(self, g: HeteroBatch, batch_idxs: Dict[str, torch.Tensor] = None) -> HeteroBatch:
         """Writes keypoint x_0 / h_0 / v_0, replaces the rk edges by the kNN edges and adds the kk radius

@@ -28,7 +28,9 @@ def _batch(cfg, n_rec, seed=19):
 @pytest.mark.parametrize('name,n_rec,over', [
     ('recegnn_20kp', [33, 21], {}), ('recegnn_small', [33, 21, 40], {}), ('recegnn_fixpos', [50, 5, 27], {}),
     # keypoint features from the receptor atoms within kp_rad (RecKeyConv.kp_rad_feats, receptor_encoder.py:238-264; configs/dev_config.yml:46)
-    ('recegnn_small', [33, 21, 40], dict(k_closest=0, kp_rad=5.0)), ('recegnn_20kp', [33, 21], dict(k_closest=0, kp_rad=9.0))])
+    ('recegnn_small', [33, 21, 40], dict(k_closest=0, kp_rad=5.0)), ('recegnn_20kp', [33, 21], dict(k_closest=0, kp_rad=9.0)),
+    # a pocket above 256 atoms: the attention kernels stride a graph's atoms 256 at a time
+    ('recegnn_small', [300, 21], {})])
 def test_encoder_gradients_match_oracle_autograd(cuda, name, n_rec, over):
     cfg = dict(RECEGNN_CFGS[name], **over)
     kw = dict(cfg, graph_cutoffs=CUT)

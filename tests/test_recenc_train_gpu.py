@@ -27,7 +27,9 @@ def _weights(n_kp, S, seed, V=16):
                                        (RECENC_NORM0, [50, 3, 27]), (RECENC_40KP, [150, 90]), (RECENC_RAD, [120, 45]),
                                        # vector_size < 16 (round 4: trained through zero-padded wide copies, csrc/train_ops.h WideSet)
                                        (dict(RECENC_CFGS['recenc_norm10'], vector_size=8), [33, 21]),
-                                       (dict(RECENC_CFGS['recenc_mean'], vector_size=5), [33, 21])])
+                                       (dict(RECENC_CFGS['recenc_mean'], vector_size=5), [33, 21]),
+                                       # a pocket above 256 atoms: the attention kernels stride a graph's atoms 256 at a time
+                                       (RECENC_CFGS['recenc_norm10'], [300, 21])])
 def test_encoder_gradients_match_oracle_autograd(cuda, cfg, n_rec):
     cfg = dict(cfg, dropout=0.0)
     kw = dict(cfg, graph_cutoffs=CUT)
