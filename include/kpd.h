@@ -630,8 +630,8 @@ kpd_status kpd_build_rec_graph(const float *rec_x, const int32_t *rec_ptr, int32
 /* Output side of sampling: element decode and XYZ text for a batch of sampled ligands.
  * Replaces the tensor -> text part of write_sampled_ligands (sample.py:66-90: torch.argmax over the feature columns,
  * dataset.lig_atom_idx_to_element) and write_xyz_file (utils.py:11-21: "<n>\n\n" + "<el> <x:.3f> <y:.3f> <z:.3f>\n"
- * per atom), as analysis/molecule_builder.py:47-48 calls it per ligand; bond perception (openbabel / rdkit) stays with
- * the caller.  The bytes equal Python's: "%.3f" of the exact fp32 value, round-half-even, '-0.000', 'nan', 'inf'.
+ * per atom), as analysis/molecule_builder.py:47-48 calls it per ligand; bonds, fragments and SDF text: kpd_mol_perceive and
+ * kpd_sdf_emit below.  The bytes equal Python's: "%.3f" of the exact fp32 value, round-half-even, '-0.000', 'nan', 'inf'.
  *   pos [n_atoms,3], feat [n_atoms,F], lig_ptr [B+1] (device); symbols [F] device, each element symbol as up to four
  *   NUL-padded bytes packed little-endian; elem [n_atoms] out (argmax, first maximum); text [capacity] out; text_ptr
  *   [B+1] int64 out (ligand b's block = text[text_ptr[b] : text_ptr[b+1]]; text_ptr[B] is the size needed, also when it
@@ -692,6 +692,74 @@ kpd_status kpd_interface_points(const float *rec_x, const int32_t *rec_ptr, cons
                                 const float *lig_x, const int32_t *lig_ptr, int32_t n_lig, int32_t B, float dist_thr,
                                 float excl_thr, int32_t cap_cand, int32_t cap_points, float *points, int32_t *ip_ptr,
                                 int32_t *n_cand, int32_t *status, void *scratch, void *stream);
+
+/* Molecules from sampled ligands (csrc/molecule.hip): atoms -> bond graph -> valences, fragments, validity counts, SDF text.
+ * Replaces, for the array-level part, make_mol_openbabel (analysis/molecule_builder.py:38-60, a per-ligand XYZ string round trip
+ * through openbabel), check_atom_valency and compute_avg_frag_size (analysis/metrics.py:156-206) and the SDF writing of
+ * sample.py.  openbabel's rules cannot be restated here, so THIS COMMENT IS THE DEFINITION: the lookup-table builder of the
+ * EDM / DiffSBDD lineage that upstream's molecule_builder.py was adapted from.  Connectivity comes from covalent radii, bond
+ * orders from length classes, both under valence caps.  SMILES, sanitisation, force fields and docking stay with the caller.
+ *
+ * Ligands carry heavy atoms only; no hydrogens are added.  Everything below is per ligand (at most 256 atoms).
+ * Element table, by atomic number (radii after Pyykko & Atsumi 2009 in integer picometres, single / double / triple, 0 = no
+ * bond of that order; cap = chemical valence cap):
+ *     H  1:  32   0   0  1      B  5:  85  78   0  3      C  6:  75  67  60  4      N  7:  71  60  54  3      O  8:  63  57   0  2
+ *     F  9:  64   0   0  1      Si 14: 116  0   0  4      P 15: 111 102   0  5      S 16: 103  94   0  6      Cl 17: 99   0   0  1
+ *     As 33: 121  0   0  3      Br 35: 114  0   0  1      I 53: 133   0   0  1
+ *   Any other atomic number is "unknown": such an atom is never bonded and sets status bit 2.
+ * Arithmetic (as kpd_pocket_select): d2(i,j) = fp64 sum of squares of the differences of the fp32 coordinates (differences
+ *   exact, each product and sum rounded once, (dx^2 + dy^2) + dz^2).  The test of order k with margin m is
+ *   d2 <= (double)(T * T) * 1e-4 with the integer T = r_k(i) + r_k(j) + m (pm); false if either radius is 0.  A NaN or Inf
+ *   coordinate makes every test false: such an atom is never bonded and sets status bit 2.
+ * Steps:
+ *   1. candidates: i < j bonded if d2 > 0.16 (0.4 A) and the order-1 test holds with m = 45;
+ *   2. degree pruning: atoms i in ascending order; while degree(i) > cap(i), remove i's bond with the largest d2 (tie: the
+ *      larger partner index).  A removal lowers the partner's degree too, which is why the order of the atoms matters;
+ *   3. order by length: a surviving bond gets order 3 if the order-3 test holds with m = 3, else 2 if the order-2 test holds
+ *      with m = 5, else 1;
+ *   4. valence repair: atoms i in ascending order; while the sum of i's orders > cap(i), lower by one the order of i's bond
+ *      with the highest order (among equals: the largest d2, then the larger partner index).  Terminates: degree <= cap;
+ *   5. fragments: frag[a] = rank of a's connected component in order of first atom (0, 1, ...); the largest fragment has the
+ *      most atoms, the lowest rank on a tie;
+ *   6. validity (upstream's check_atom_valency): an atom is invalid if valence == 0, valence > allowed[class], or its element
+ *      is unknown.  `allowed` comes from the caller (upstream's allowed_bonds maxima) and is deliberately another table than
+ *      `cap`: a sulfone S (valence 6 > 4) counts as invalid, as it would upstream.
+ * Limits: the orders are LENGTH CLASSES.  No aromaticity or Kekule perception (an ideal benzene, 1.397 A, gets six single
+ *   bonds), no formal charges (nitro groups are demoted to single bonds).  Connectivity, fragments and the counts of step 5 do
+ *   not depend on the orders.
+ *
+ * kpd_mol_perceive: pos [n_atoms,3], feat [n_atoms,F], lig_ptr [B+1], z [F] (atomic number of every feature class), allowed
+ *   [F]; all device pointers.  Out (device): elem [n_atoms] (argmax of the feature row, first maximum, the routine of
+ *   kpd_xyz_emit), valence [n_atoms], frag [n_atoms] (all three -1 for the atoms of a ligand that is left out), bond_ij
+ *   [cap_bonds,2] (global row numbers, i < j; per ligand sorted by i, then j), bond_order [cap_bonds], bond_ptr [B+1]
+ *   (bond_ptr[B] is the size needed, also when it exceeds cap_bonds; the bonds of a ligand that does not fit are not written;
+ *   cap_bonds = 3 n_atoms always suffices, degree <= 6), summary [B,4] = {n_bonds, n_frags, largest_frag_atoms,
+ *   n_invalid_atoms}, status [B]: bit 0 = empty ligand, bit 1 = cap_bonds too small for this ligand, bit 2 = a non-finite
+ *   coordinate or an unknown element, bit 3 = malformed segment or more than 256 atoms (ligand left out: summary 0, no bonds;
+ *   nothing is read or written out of bounds).  scratch: kpd_mol_scratch_bytes(n_atoms, B) device bytes.
+ *   One wave per ligand; three launches (and three memsets) whatever B is; no host synchronisation, no float atomics;
+ *   deterministic and bitwise independent of batch composition.
+ *
+ * kpd_sdf_emit: MOL V2000 blocks from those outputs.  symbols [F] as for kpd_xyz_emit (at most three bytes are printed).
+ *   Block: an empty title line, "  kpd_hip " + 10 blanks + "3D", an empty comment line, the counts line
+ *   "%3d%3d  0  0  0  0  0  0  0  0999 V2000", atom lines "%10.4f%10.4f%10.4f %-3s 0  0  0  0  0  0  0  0  0  0  0  0", bond
+ *   lines "%3d%3d%3d  0" (1-based numbers local to the block), "M  END", "$$$$"; every line ends in '\n'.  Coordinates are
+ *   Python's "%10.4f" of the exact fp32 value (round-half-even on the binary value, "-0.0000").  largest_only != 0: only the
+ *   atoms and bonds of the largest fragment, renumbered in atom order (upstream's largest_frag).
+ *   text [capacity], text_ptr [B+1] int64 as for kpd_xyz_emit (text_ptr[B] = size needed); status [B]: bit 0 = a non-finite
+ *   coordinate, bit 1 = a coordinate whose text is wider than 10 characters, bit 2 = no molecule (mol_status bits 1 or 3, or
+ *   inconsistent inputs), bit 3 = capacity too small for this ligand (nothing written for it).  With bits 0-2 the block is
+ *   empty.  scratch: kpd_sdf_scratch_bytes(n_atoms, B).  Three launches whatever B is; no host synchronisation. */
+int64_t kpd_mol_scratch_bytes(int32_t n_atoms, int32_t B);
+kpd_status kpd_mol_perceive(const float *pos, const float *feat, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, int32_t F,
+                            const int32_t *z, const int32_t *allowed, int32_t cap_bonds, int32_t *elem, int32_t *valence,
+                            int32_t *frag, int32_t *bond_ij, int32_t *bond_order, int32_t *bond_ptr, int32_t *summary,
+                            int32_t *status, void *scratch, void *stream);
+int64_t kpd_sdf_scratch_bytes(int32_t n_atoms, int32_t B);
+kpd_status kpd_sdf_emit(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, const int32_t *elem, int32_t F,
+                        const uint32_t *symbols, const int32_t *frag, const int32_t *bond_ij, const int32_t *bond_order,
+                        const int32_t *bond_ptr, int32_t cap_bonds, const int32_t *mol_status, int32_t largest_only,
+                        uint8_t *text, int64_t capacity, int64_t *text_ptr, int32_t *status, void *scratch, void *stream);
 
 #ifdef __cplusplus
 }

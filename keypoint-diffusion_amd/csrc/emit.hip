@@ -5,59 +5,11 @@
 // half-to-even on the exact binary value (integer arithmetic below, no floating-point rounding involved).
 // Byte work, HBM-bound and tiny: three launches per batch (lines, ligand offsets, compaction).
 #include "common.h"
+#include "emit_core.h"
 
 namespace kpd {
 
 constexpr int LINE_SLOT = 80;       // 2 symbol bytes + 3 x (space, sign, <= 16 integer digits, '.', 3 digits) + '\n' <= 72
-
-// "%.3f" of an fp32 value into buf; returns the length, or -1 if |v| >= 2^53 (not printable with 64-bit integers here)
-__device__ __forceinline__ int format_f3(float v, char *buf) {
-    const unsigned bits = __float_as_uint(v);
-    const bool neg = bits >> 31;
-    const int e8 = (bits >> 23) & 0xff;
-    const unsigned frac = bits & 0x7fffffu;
-    int n = 0;
-    if (e8 == 255) {                // Python: 'nan' without sign, 'inf' / '-inf'
-        if (frac) {
-            buf[0] = 'n'; buf[1] = 'a'; buf[2] = 'n';
-            return 3;
-        }
-        if (neg) buf[n++] = '-';
-        buf[n++] = 'i'; buf[n++] = 'n'; buf[n++] = 'f';
-        return n;
-    }
-    const unsigned long long m = e8 ? (frac | 0x800000u) : frac;
-    const int e = (e8 ? e8 : 1) - 150;              // value = m * 2^e
-    const unsigned long long M = m * 1000ull;       // < 2^34
-    unsigned long long N;                           // round_half_even(|v| * 1000)
-    if (e >= 0) {
-        if (e > 29) return -1;
-        N = M << e;
-    } else {
-        const int s = -e;
-        if (s >= 64) {
-            N = 0;
-        } else {
-            const unsigned long long q = M >> s, r = M & ((1ull << s) - 1ull), half = 1ull << (s - 1);
-            N = q + ((r > half || (r == half && (q & 1ull))) ? 1ull : 0ull);
-        }
-    }
-    if (neg) buf[n++] = '-';                        // the sign survives rounding to zero ('-0.000'), as in Python
-    unsigned long long ip = N / 1000ull;
-    const unsigned fp = (unsigned)(N % 1000ull);
-    char tmp[20];
-    int nd = 0;
-    do {
-        tmp[nd++] = (char)('0' + (int)(ip % 10ull));
-        ip /= 10ull;
-    } while (ip);
-    while (nd) buf[n++] = tmp[--nd];
-    buf[n++] = '.';
-    buf[n++] = (char)('0' + fp / 100);
-    buf[n++] = (char)('0' + (fp / 10) % 10);
-    buf[n++] = (char)('0' + fp % 10);
-    return n;
-}
 
 // one thread per atom: argmax of the feature row (first maximum, torch.argmax on CPU), the atom's line into its slot
 __global__ void k_emit_lines(const float *__restrict__ pos, const float *__restrict__ feat, int N, int F,
@@ -65,20 +17,7 @@ __global__ void k_emit_lines(const float *__restrict__ pos, const float *__restr
                              int *__restrict__ len, int *__restrict__ status) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const float *f = feat + (size_t)i * F;
-    int best = 0;
-    float bv = f[0];
-    bool has_nan = bv != bv;
-    for (int k = 1; k < F && !has_nan; ++k) {       // torch.argmax: first maximum; a NaN is a maximum
-        const float x = f[k];
-        if (x != x) {
-            best = k;
-            has_nan = true;
-        } else if (x > bv) {
-            bv = x;
-            best = k;
-        }
-    }
+    const int best = argmax_first(feat + (size_t)i * F, F);
     elem[i] = best;
     char line[LINE_SLOT];
     int n = 0;
@@ -90,7 +29,7 @@ __global__ void k_emit_lines(const float *__restrict__ pos, const float *__restr
     }
     for (int c = 0; c < 3; ++c) {
         line[n++] = ' ';
-        const int w = format_f3(pos[(size_t)i * 3 + c], line + n);
+        const int w = format_fixed<3>(pos[(size_t)i * 3 + c], line + n);
         if (w < 0) {
             atomicOr(status, 1);
             line[n++] = '?';

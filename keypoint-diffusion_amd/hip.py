@@ -180,6 +180,12 @@ def lib():
     L.kpd_interface_points_scratch_bytes.restype = C.c_int64
     L.kpd_interface_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_float, C.c_float, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    for name in ('kpd_mol_scratch_bytes', 'kpd_sdf_scratch_bytes'):
+        getattr(L, name).argtypes = [C.c_int32, C.c_int32]
+        getattr(L, name).restype = C.c_int64
+    L.kpd_mol_perceive.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 10
+    L.kpd_sdf_emit.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 +
+                               [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4)
     _lib = L
     return L
 
@@ -210,6 +216,7 @@ EXPORTS = [
     'kpd_recegnn_trainer_forward', 'kpd_recegnn_trainer_backward', 'kpd_ot_emd_uniform', 'kpd_sgemm',
     'kpd_dist_hinge',
     'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
+    'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
 ]
 
 
@@ -928,6 +935,17 @@ def interface_points(rec_x: torch.Tensor, rec_ptr: torch.Tensor, cand_mask: torc
     return dict(points=points[:min(ptr[-1], cap_pts)], ip_ptr=ptr, n_cand=host[B + 1:2 * B + 1], status=host[2 * B + 1:])
 
 
+def _packed_symbols(elements, device, longest: int = 4) -> torch.Tensor:
+    """Element symbols as NUL-padded little-endian words, the form kpd_xyz_emit and kpd_sdf_emit read."""
+    packed = []
+    for el in elements:
+        b = el.encode('ascii')
+        if not 1 <= len(b) <= longest:
+            raise KpdError(f'element symbol {el!r} must be 1-{longest} ASCII characters')
+        packed.append(int.from_bytes(b.ljust(4, b'\0'), 'little'))
+    return torch.tensor(packed, dtype=torch.int32, device=device)        # ASCII: the top bit is never set
+
+
 def xyz_emit(pos: torch.Tensor, feat: torch.Tensor, lig_ptr: torch.Tensor, elements):
     """Element decode + XYZ text of a batch of ligands on the GPU (kpd_xyz_emit).
     pos [N,3], feat [N,F] fp32 GPU tensors, lig_ptr [B+1] int32 GPU tensor, elements: F symbols.
@@ -939,14 +957,8 @@ def xyz_emit(pos: torch.Tensor, feat: torch.Tensor, lig_ptr: torch.Tensor, eleme
     N, B, F = pos.shape[0], lig_ptr.numel() - 1, feat.shape[1] if feat.dim() == 2 else -1
     if pos.shape != (N, 3) or feat.shape[0] != N or F != len(elements):
         raise KpdError(f'xyz_emit: pos {tuple(pos.shape)}, feat {tuple(feat.shape)}, {len(elements)} element symbols')
-    packed = []
-    for el in elements:
-        b = el.encode('ascii')
-        if not 1 <= len(b) <= 4:
-            raise KpdError(f'element symbol {el!r} must be 1-4 ASCII characters')
-        packed.append(int.from_bytes(b.ljust(4, b'\0'), 'little'))
     dev = pos.device
-    symbols = torch.tensor(packed, dtype=torch.int32, device=dev)        # ASCII: the top bit is never set
+    symbols = _packed_symbols(elements, dev)
     elem = torch.empty(N, dtype=torch.int32, device=dev)
     capacity = 72 * N + 16 * B + 16         # a line is at most 71 bytes, a header at most 12
     text = torch.empty(capacity, dtype=torch.uint8, device=dev)
@@ -962,6 +974,71 @@ def xyz_emit(pos: torch.Tensor, feat: torch.Tensor, lig_ptr: torch.Tensor, eleme
     if st & 1:
         raise KpdError('xyz_emit: a coordinate with |x| >= 2^53 cannot be printed (diverged sample?)')
     return elem, bytes(text[:ptr[-1]].cpu().numpy()), ptr
+
+
+MOL_EMPTY, MOL_CAPACITY, MOL_BAD_ATOM, MOL_BAD_SEGMENT = 1, 2, 4, 8          # status bits of kpd_mol_perceive
+SDF_NONFINITE, SDF_WIDE, SDF_NO_MOLECULE, SDF_CAPACITY = 1, 2, 4, 8         # status bits of kpd_sdf_emit
+MOL_MAX_ATOMS = 256
+
+
+def _mol_ptr(lig_ptr: torch.Tensor) -> int:
+    if not (lig_ptr.is_cuda and lig_ptr.dtype == torch.int32 and lig_ptr.dim() == 1 and lig_ptr.numel() >= 1 and lig_ptr.is_contiguous()):
+        raise KpdError('lig_ptr must be a contiguous int32 GPU tensor of B + 1 offsets')
+    return lig_ptr.numel() - 1
+
+
+def mol_perceive(pos: torch.Tensor, feat: torch.Tensor, lig_ptr: torch.Tensor, z, allowed, cap_bonds: Optional[int] = None):
+    """Bond graph, valences, fragments and validity counts of a batch of ligands on the GPU (kpd_mol_perceive; include/kpd.h
+    states the rule).  pos [N,3], feat [N,F] fp32 GPU tensors, lig_ptr [B+1] int32 GPU tensor, z / allowed: the atomic number
+    and the largest allowed valence of every feature class (F integers each).  cap_bonds: capacity of the bond list (default
+    3 N, which cannot overflow).  Returns a dict of device tensors: elem, valence, frag [N], bonds [cap_bonds,2], order
+    [cap_bonds], bond_ptr [B+1], summary [B,4], status [B].  No host synchronisation."""
+    pos, feat = _dev_f32(pos, 'pos'), _dev_f32(feat, 'feat')
+    B = _mol_ptr(lig_ptr)
+    N, F = pos.shape[0], feat.shape[1] if feat.dim() == 2 else -1
+    if pos.shape != (N, 3) or feat.shape[0] != N or F < 1 or len(z) != F or len(allowed) != F:
+        raise KpdError(f'mol_perceive: pos {tuple(pos.shape)}, feat {tuple(feat.shape)}, {len(z)} atomic numbers, {len(allowed)} valences')
+    dev = pos.device
+    cap = 3 * N if cap_bonds is None else int(cap_bonds)
+    table = torch.tensor([list(map(int, z)), list(map(int, allowed))], dtype=torch.int32, device=dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = dict(elem=i32(N), valence=i32(N), frag=i32(N), bonds=i32(cap, 2), order=i32(cap), bond_ptr=i32(B + 1), summary=i32(B, 4),
+               status=i32(B))
+    scratch = torch.empty(int(lib().kpd_mol_scratch_bytes(N, B)), dtype=torch.uint8, device=dev)
+    check(lib().kpd_mol_perceive(_ptr(pos), _ptr(feat), _ptr(lig_ptr), N, B, F, _ptr(table[0]), _ptr(table[1]), cap, _ptr(out['elem']),
+                                 _ptr(out['valence']), _ptr(out['frag']), _ptr(out['bonds']), _ptr(out['order']), _ptr(out['bond_ptr']),
+                                 _ptr(out['summary']), _ptr(out['status']), _ptr(scratch), _stream()))
+    return out
+
+
+def sdf_emit(pos: torch.Tensor, lig_ptr: torch.Tensor, elements, mol: dict, largest_only: bool = False, capacity: Optional[int] = None):
+    """MOL V2000 / SDF text of a batch of ligands on the GPU (kpd_sdf_emit) from what `mol_perceive` returned.
+    elements: F symbols of at most three characters.  Returns (text bytes, text_ptr list of B + 1 offsets, status list of B);
+    ligand b's block is text[text_ptr[b]:text_ptr[b + 1]], empty when its status is not 0.  The only host synchronisation is
+    the copy of the finished text."""
+    pos = _dev_f32(pos, 'pos')
+    B = _mol_ptr(lig_ptr)
+    N, F = pos.shape[0], len(elements)
+    for name in ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'):
+        t = mol[name]
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise KpdError(f'sdf_emit: {name} must be a contiguous int32 GPU tensor')
+    cap_bonds = mol['order'].numel()
+    if (pos.shape != (N, 3) or F < 1 or mol['elem'].numel() != N or mol['frag'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or
+            mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B):
+        raise KpdError(f'sdf_emit: pos {tuple(pos.shape)}, {B} ligands, {F} element symbols do not match the perceived molecules')
+    dev = pos.device
+    symbols = _packed_symbols(elements, dev, 3)
+    cap = 70 * N + 13 * cap_bonds + 77 * B if capacity is None else int(capacity)      # fixed-width lines: the exact upper bound
+    text = torch.empty(cap, dtype=torch.uint8, device=dev)
+    text_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib().kpd_sdf_scratch_bytes(N, B)), dtype=torch.uint8, device=dev)
+    check(lib().kpd_sdf_emit(_ptr(pos), _ptr(lig_ptr), N, B, _ptr(mol['elem']), F, _ptr(symbols), _ptr(mol['frag']), _ptr(mol['bonds']),
+                             _ptr(mol['order']), _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']), int(bool(largest_only)), _ptr(text),
+                             cap, _ptr(text_ptr), _ptr(status), _ptr(scratch), _stream()))
+    ptr = text_ptr.cpu().tolist()
+    return bytes(text[:min(ptr[-1], cap)].cpu().numpy()), ptr, status.cpu().tolist()
 
 
 def sample_update(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h, coef):

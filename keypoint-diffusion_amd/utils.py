@@ -1,9 +1,10 @@
 """Output side of sampling: sampled ligands -> element symbols and XYZ text, computed on the GPU.
 
 Mirrors the tensor -> text part of the reference's `write_sampled_ligands` (sample.py:66-90) and `write_xyz_file`
-(utils.py:11-21; called per ligand from analysis/molecule_builder.py:47-48).  Bond perception and SDF writing
-(openbabel, rdkit) are the caller's: they take the XYZ blocks returned here.  There is no CPU implementation —
-tensors must live on the GPU and the HIP library must be present.
+(utils.py:11-21; called per ligand from analysis/molecule_builder.py:47-48), and writes SDF: bond perception runs on the
+GPU as well (`molecule.build_molecules`, the rule stated in include/kpd.h), so `sampled_ligands_sdf` / `write_sdf_file` need
+neither openbabel nor rdkit.  There is no CPU implementation — tensors must live on the GPU and the HIP library must be
+present.
 """
 from pathlib import Path
 from typing import List, Optional, Sequence, Tuple
@@ -51,3 +52,19 @@ def write_xyz_file(coords: torch.Tensor, atom_types: Sequence[str], filename: Op
         return out
     with open(filename, 'w') as f:
         f.write(out)
+
+
+def sampled_ligands_sdf(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig_elements: Sequence[str],
+                        largest_frag: bool = False) -> List[str]:
+    """For every sampled ligand its MOL V2000 block, closed by `$$$$` (bonds perceived on the GPU, `molecule.build_molecules`);
+    `largest_frag`: only the largest fragment of every ligand, as upstream's `process_molecule(largest_frag=True)`."""
+    from .molecule import build_molecules
+    return build_molecules(lig_pos, lig_feat, lig_elements).sdf(largest_frag=largest_frag)
+
+
+def write_sdf_file(filename, lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig_elements: Sequence[str],
+                   largest_frag: bool = False) -> None:
+    """Write the blocks of `sampled_ligands_sdf`, concatenated, as one SDF file."""
+    blocks = sampled_ligands_sdf(lig_pos, lig_feat, lig_elements, largest_frag=largest_frag)
+    with open(filename, 'w') as f:
+        f.write(''.join(blocks))
