@@ -698,7 +698,8 @@ kpd_status kpd_interface_points(const float *rec_x, const int32_t *rec_ptr, cons
  * through openbabel), check_atom_valency and compute_avg_frag_size (analysis/metrics.py:156-206) and the SDF writing of
  * sample.py.  openbabel's rules cannot be restated here, so THIS COMMENT IS THE DEFINITION: the lookup-table builder of the
  * EDM / DiffSBDD lineage that upstream's molecule_builder.py was adapted from.  Connectivity comes from covalent radii, bond
- * orders from length classes, both under valence caps.  SMILES, sanitisation, force fields and docking stay with the caller.
+ * orders from length classes, both under valence caps.  Sanitisation, force fields and docking stay with the caller; what
+ * upstream compares SMILES for (uniqueness, novelty) is kpd_mol_keys below.
  *
  * Ligands carry heavy atoms only; no hydrogens are added.  Everything below is per ligand (at most 256 atoms).
  * Element table, by atomic number (radii after Pyykko & Atsumi 2009 in integer picometres, single / double / triple, 0 = no
@@ -760,6 +761,56 @@ kpd_status kpd_sdf_emit(const float *pos, const int32_t *lig_ptr, int32_t n_atom
                         const uint32_t *symbols, const int32_t *frag, const int32_t *bond_ij, const int32_t *bond_order,
                         const int32_t *bond_ptr, int32_t cap_bonds, const int32_t *mol_status, int32_t largest_only,
                         uint8_t *text, int64_t capacity, int64_t *text_ptr, int32_t *status, void *scratch, void *stream);
+
+/* Properties of the SET of sampled ligands (csrc/molset.hip): uniqueness and novelty (analysis/metrics.py:135-147) and the
+ * Tanimoto diversity of a pocket's samples (MoleculeProperties.calculate_diversity, analysis/metrics.py:263-277).  Upstream
+ * compares canonical SMILES and RDKit path fingerprints, which cannot be restated here, so THIS COMMENT IS THE DEFINITION:
+ * a key that is equal for isomorphic bond graphs, and a bit vector of the substructures around every atom, both read off the
+ * bond graph kpd_mol_perceive left on the device.  All arithmetic is on unsigned 64-bit integers, modulo 2^64, except the
+ * final Tanimoto ratio.
+ *   mix(x):  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31  (splitmix64's finaliser)
+ *   K1 = 0x9E3779B97F4A7C15, K2 = 0xC2B2AE3D27D4EB4F, K3 = 0x165667B19E3779F9.
+ * Scope S of a ligand: with largest_only its largest fragment (frag of kpd_mol_perceive: most atoms, the lowest rank on a
+ *   tie), else all of its atoms.  Only bonds with both ends in S count.  n, m = atoms and bonds in S; deg(a) = degree of a in
+ *   S; d(a,b) = length in bonds of the shortest path inside S, 65535 if there is none; Z(a) = z[elem[a]], the atomic number
+ *   of a's class (as a two's-complement integer); l = bond_order with with_orders, else 1.
+ * Key:  inv_0[a] = mix(Z(a) + deg(a) K3 + K1 * sum over b in S, b != a, of mix(Z(b) K2 + d(a,b)));
+ *       inv_r[a] = mix(K1 inv_{r-1}[a] + sum over the bonds (a,b) of mix(inv_{r-1}[b] + l K2)),   r = 1 .. n;
+ *       key      = mix(n + m K3 + K1 * sum over a in S of mix(inv_n[a])).
+ *   Every sum is commutative: neither the order of the atoms nor that of the bonds matters.  The distance term of inv_0 is
+ *   what tells ring sizes apart (plain neighbourhood refinement gives decalin and bicyclopentyl one key).
+ * Fingerprint: f_0[a] = mix(Z(a) + deg(a) K3), f_r from f_{r-1} by the step of inv_r; for r = 0 .. radius every atom a of S
+ *   sets bit (f_r[a] mod nbits) of the ligand's row: bit k is bit (k & 31) of word (k >> 5).  The seeds are local on purpose:
+ *   molecules that share a substructure share its bits.
+ * Limits: a key describes the CONSTITUTION only: no stereo (enantiomers and E/Z isomers share a key), no hydrogens, no
+ *   charges.  With with_orders it inherits the length-class bond orders of kpd_mol_perceive (no aromaticity: two Kekule-like
+ *   geometries of one ring can differ); with_orders = 0 makes it independent of them.  It is a hash: equal keys of
+ *   non-isomorphic graphs are possible in principle (none among the 1 136 pairs of equal size, composition and bond count,
+ *   27 of them isomorphic, of the 700 seeded random molecule-like graphs of tests/test_molset_config.py: there key equality
+ *   and labelled-graph isomorphism coincide).
+ *
+ * kpd_mol_keys: lig_ptr [B+1], elem / frag [n_atoms], bond_ij [cap_bonds,2], bond_order [cap_bonds], bond_ptr [B+1],
+ *   mol_status [B] as kpd_mol_perceive wrote them, z [F]; radius 0 .. 4, nbits a power of two in 64 .. 4096.  Out (device):
+ *   key [B] (the uint64 bit pattern), fp [B, nbits / 32], atom_inv [n_atoms] (inv_n of every atom of S, 0 elsewhere; may be
+ *   NULL), status [B]: bit 0 = no molecule (mol_status bits 0, 1 or 3, an empty S, or inputs that are no output of
+ *   kpd_mol_perceive: an element or fragment out of range, a bond outside the ligand, twice, of an order outside 1 .. 3, or a
+ *   seventh neighbour); such a ligand gets key 0 and an all-zero row, and nothing is read or written out of bounds.
+ *   One wave per ligand, one launch (and a memset for atom_inv) whatever B is; no scratch, no host synchronisation, no float
+ *   arithmetic; a ligand's results are bitwise independent of the rest of the batch.
+ *
+ * kpd_fp_diversity: fp [B, W] (W >= 1 words per row), use [B] (0 = leave the ligand out), group_ptr [G+1]: group g is the
+ *   ligands group_ptr[g] .. group_ptr[g+1] - 1 (a pocket's samples).  For every pair i < j of used ligands of a group:
+ *   c = popcount(a & b), u = popcount(a | b), T = (double)c / (double)u, T = 1 if u == 0.  Out (device): div_sum [G] =
+ *   sum of (1 - T) in fp64, n_pairs [G] int64, status [G]: bit 0 = malformed segment (not 0 <= group_ptr[g] <=
+ *   group_ptr[g+1] <= B: div_sum 0, n_pairs 0, nothing read).  One workgroup per group, one launch; the partial sums of its
+ *   256 threads meet in a fixed tree: no float atomics, deterministic, and bitwise the same whether a group is alone or in a
+ *   batch.  The mean Tanimoto distance upstream reports is div_sum / n_pairs (0 for fewer than two ligands). */
+kpd_status kpd_mol_keys(const int32_t *lig_ptr, int32_t n_atoms, int32_t B, const int32_t *elem, int32_t F, const int32_t *z,
+                        const int32_t *frag, const int32_t *bond_ij, const int32_t *bond_order, const int32_t *bond_ptr,
+                        int32_t cap_bonds, const int32_t *mol_status, int32_t largest_only, int32_t with_orders, int32_t radius,
+                        int32_t nbits, int64_t *key, uint32_t *fp, int64_t *atom_inv, int32_t *status, void *stream);
+kpd_status kpd_fp_diversity(const uint32_t *fp, const uint8_t *use, int32_t B, int32_t W, const int32_t *group_ptr, int32_t G,
+                            double *div_sum, int64_t *n_pairs, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -10,14 +10,10 @@
 // Small latency-bound kernels; nothing is shared between ligands, no float atomics, bitwise independent of batch composition.
 #include "common.h"
 #include "emit_core.h"
+#include "molecule_core.h"
 
 namespace kpd {
 
-constexpr int MOL_MAX = 256;            // atoms of one ligand
-constexpr int MOL_W = MOL_MAX / 32;     // words of one row of a bit matrix
-constexpr int MOL_K = MOL_MAX / 64;     // atoms per lane
-
-enum : int { MOL_EMPTY = 1, MOL_CAPACITY = 2, MOL_BAD_ATOM = 4, MOL_BAD_SEGMENT = 8 };
 enum : int { SDF_NONFINITE = 1, SDF_WIDE = 2, SDF_NO_MOLECULE = 4, SDF_CAPACITY = 8 };
 
 // the element table: r1 | r2 << 8 | r3 << 16 | cap << 24 (covalent radii after Pyykko & Atsumi 2009 in pm, 0 = no bond of that
@@ -43,12 +39,6 @@ __device__ __forceinline__ unsigned element_row(int z) {
 #undef KPD_EL
 }
 
-__device__ __forceinline__ bool mol_segment(const int *__restrict__ ptr, int b, int n, int &a0, int &a1) {
-    a0 = ptr[b];
-    a1 = ptr[b + 1];
-    return a0 >= 0 && a1 >= a0 && a1 <= n;
-}
-
 // fp64 sum of squares of the exact differences; every product and sum is rounded on its own (no fused multiply-add)
 __device__ __forceinline__ double mol_d2(const float *p, int i, int j) {
     const double dx = (double)p[i * 3] - (double)p[j * 3], dy = (double)p[i * 3 + 1] - (double)p[j * 3 + 1],
@@ -61,12 +51,6 @@ __device__ __forceinline__ bool within(double d2, unsigned ri, unsigned rj, int 
     if (!ri || !rj) return false;
     const int T = (int)ri + (int)rj + margin;
     return d2 <= (double)(T * T) * 1e-4;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 __device__ __forceinline__ int wave_exclusive(int v, int lane, int &total) {

@@ -186,6 +186,9 @@ def lib():
     L.kpd_mol_perceive.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 10
     L.kpd_sdf_emit.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 +
                                [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4)
+    L.kpd_mol_keys.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p] +
+                               [C.c_int32] * 4 + [C.c_void_p] * 5)
+    L.kpd_fp_diversity.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
     _lib = L
     return L
 
@@ -217,6 +220,7 @@ EXPORTS = [
     'kpd_dist_hinge',
     'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
     'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
+    'kpd_mol_keys', 'kpd_fp_diversity',
 ]
 
 
@@ -1039,6 +1043,61 @@ def sdf_emit(pos: torch.Tensor, lig_ptr: torch.Tensor, elements, mol: dict, larg
                              cap, _ptr(text_ptr), _ptr(status), _ptr(scratch), _stream()))
     ptr = text_ptr.cpu().tolist()
     return bytes(text[:min(ptr[-1], cap)].cpu().numpy()), ptr, status.cpu().tolist()
+
+
+KEY_NO_MOLECULE = 1         # status bit of kpd_mol_keys
+DIV_BAD_SEGMENT = 1         # status bit of kpd_fp_diversity
+
+
+def mol_keys(lig_ptr: torch.Tensor, z, mol: dict, largest_only: bool = True, with_orders: bool = True, radius: int = 2, nbits: int = 2048,
+             atom_inv: bool = False):
+    """Isomorphism keys and substructure fingerprints of a batch of perceived molecules on the GPU (kpd_mol_keys; include/kpd.h
+    states the rule).  `mol`: what `mol_perceive` returned, z: the atomic number of every feature class.  Returns a dict of
+    device tensors: key [B] int64 (the uint64 bit pattern), fp [B, nbits/32] int32 (the uint32 bit pattern), status [B] (bit 0:
+    no molecule, key 0 and an all-zero row) and, on request, atom_inv [N] int64.  No host synchronisation."""
+    B = _mol_ptr(lig_ptr)
+    for name in ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'):
+        t = mol.get(name)
+        if t is None or not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise KpdError(f'mol_keys: {name} must be a contiguous int32 GPU tensor')
+    N, F, cap_bonds = mol['elem'].numel(), len(z), mol['order'].numel()
+    if (F < 1 or mol['frag'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or mol['bond_ptr'].numel() != B + 1 or
+            mol['status'].numel() != B):
+        raise KpdError(f'mol_keys: {B} ligands, {F} atomic numbers do not match the perceived molecules')
+    nbits, radius = int(nbits), int(radius)
+    if not (0 <= radius <= 4 and 64 <= nbits <= 4096 and nbits & (nbits - 1) == 0):
+        raise KpdError(f'mol_keys: radius {radius} must be 0 .. 4 and nbits {nbits} a power of two in 64 .. 4096')
+    dev = lig_ptr.device
+    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
+    out = dict(key=torch.empty(B, dtype=torch.int64, device=dev), fp=torch.empty(B, nbits // 32, dtype=torch.int32, device=dev),
+               status=torch.empty(B, dtype=torch.int32, device=dev))
+    if atom_inv:
+        out['atom_inv'] = torch.empty(N, dtype=torch.int64, device=dev)
+    check(lib().kpd_mol_keys(_ptr(lig_ptr), N, B, _ptr(mol['elem']), F, _ptr(zt), _ptr(mol['frag']), _ptr(mol['bonds']), _ptr(mol['order']),
+                             _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']), int(bool(largest_only)), int(bool(with_orders)), radius,
+                             nbits, _ptr(out['key']), _ptr(out['fp']), _ptr(out.get('atom_inv')), _ptr(out['status']), _stream()))
+    return out
+
+
+def fp_diversity(fp: torch.Tensor, use: torch.Tensor, group_ptr: torch.Tensor):
+    """Sum of the Tanimoto distances over the pairs of used ligands of every group on the GPU (kpd_fp_diversity).
+    fp [B,W] int32 GPU tensor (fingerprint rows), use [B] bool / uint8, group_ptr [G+1] int32 GPU tensor.  Returns device
+    tensors (div_sum [G] float64, n_pairs [G] int64, status [G]: bit 0 = malformed segment).  No host synchronisation."""
+    if not (fp.is_cuda and fp.dtype == torch.int32 and fp.dim() == 2 and fp.shape[1] >= 1 and fp.is_contiguous()):
+        raise KpdError('fp_diversity: fp must be a contiguous int32 GPU tensor [B, W]')
+    if not (group_ptr.is_cuda and group_ptr.dtype == torch.int32 and group_ptr.dim() == 1 and group_ptr.numel() >= 1 and group_ptr.is_contiguous()):
+        raise KpdError('fp_diversity: group_ptr must be a contiguous int32 GPU tensor of G + 1 offsets')
+    G = group_ptr.numel() - 1
+    B, W = fp.shape
+    if not (use.is_cuda and use.dtype in (torch.bool, torch.uint8) and use.shape == (B,)):
+        raise KpdError(f'fp_diversity: use must be a bool or uint8 GPU tensor of {B} entries')
+    use = use.contiguous().view(torch.uint8)
+    dev = fp.device
+    div_sum = torch.empty(G, dtype=torch.float64, device=dev)
+    n_pairs = torch.empty(G, dtype=torch.int64, device=dev)
+    status = torch.empty(G, dtype=torch.int32, device=dev)
+    check(lib().kpd_fp_diversity(_ptr(fp), _ptr(use), B, W, _ptr(group_ptr), G, _ptr(div_sum), _ptr(n_pairs), _ptr(status), _stream()))
+    return div_sum, n_pairs, status
 
 
 def sample_update(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h, coef):

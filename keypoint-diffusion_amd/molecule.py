@@ -6,11 +6,19 @@ a per-ligand XYZ string round trip through openbabel), `check_atom_valency` and 
 :225-236) and the SDF writing of sample.py / test.py.  Here it is one batched call for all ligands (`kpd_mol_perceive`,
 `kpd_sdf_emit`, csrc/molecule.hip), and the metrics are torch reductions over the device tensors it returns.
 
+The numbers about the SET of samples are here too: `uniqueness` and `novelty` (analysis/metrics.py:135-147) and the Tanimoto
+`diversity` of a pocket's samples (`MoleculeProperties.calculate_diversity`, :263-277).  Upstream compares canonical SMILES
+and RDKit fingerprints; here a key that is equal for isomorphic bond graphs and a substructure bit vector are computed from
+the bond graph on the device (`kpd_mol_keys`, `kpd_fp_diversity`, csrc/molset.hip; include/kpd.h is their definition), and
+the set operations are torch calls.  A key describes the constitution only (no stereo) and, unless `with_orders=False`,
+inherits the length-class bond orders.
+
 openbabel's perception rules are not restated: include/kpd.h defines the rule used here, the lookup-table builder of the
 EDM / DiffSBDD lineage (covalent radii for connectivity, length classes for the bond orders, valence caps).  The bond orders
-are length classes, not a Kekule structure; connectivity, fragments and the metrics below do not depend on them.  What needs
-SMILES or a force field (`validity`, `uniqueness`, `novelty`, QED / SA, UFF relaxation) stays with the caller, who can read
-the SDF blocks with rdkit.  There is no CPU implementation: tensors must live on the GPU and the HIP library must be present.
+are length classes, not a Kekule structure; connectivity, fragments and `metrics` do not depend on them.  What needs
+sanitisation, a force field or a docking program (`validity`, QED / SA, UFF relaxation, docking) stays with the caller, who
+can read the SDF blocks with rdkit.  There is no CPU implementation: tensors must live on the GPU and the HIP library must be
+present.
 """
 from typing import Dict, List, Optional, Sequence
 
@@ -101,6 +109,65 @@ class Molecules:
             out['atom_type_kldiv'] = float(-torch.sum(p * torch.log(q / (p + EPS) + EPS)))
         return out
 
+    def _keys(self, largest_frag: bool, with_orders: bool, radius: int = 2, nbits: int = 2048) -> Dict[str, torch.Tensor]:
+        if self.lig_elements is None or self.bonds is None:
+            raise hip.KpdError('these Molecules carry no bond graph: build them with build_molecules')
+        if len(self) == 0:
+            dev = self.lig_ptr.device
+            return dict(key=torch.zeros(0, dtype=torch.int64, device=dev), fp=torch.zeros(0, int(nbits) // 32, dtype=torch.int32, device=dev),
+                        status=torch.zeros(0, dtype=torch.int32, device=dev))
+        mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
+        z = [ATOMIC_NUMBERS.get(el, 0) for el in self.lig_elements]
+        return hip.mol_keys(self.lig_ptr, z, mol, largest_only=largest_frag, with_orders=with_orders, radius=radius, nbits=nbits)
+
+    def keys(self, largest_frag: bool = True, with_orders: bool = True) -> torch.Tensor:
+        """One int64 per ligand that is equal for isomorphic bond graphs and different otherwise (the key of include/kpd.h,
+        computed on the GPU): what upstream uses canonical SMILES for.  `largest_frag`: of the largest fragment, as upstream
+        takes the SMILES of (`compute_connectivity`); `with_orders=False`: of the connectivity alone, independent of the
+        length-class bond orders.  Constitution only: no stereo.  A ligand without a molecule (empty, left out) has key 0."""
+        return self._keys(largest_frag, with_orders)['key']
+
+    def fingerprints(self, radius: int = 2, nbits: int = 2048, largest_frag: bool = True, with_orders: bool = True) -> torch.Tensor:
+        """Substructure bit vectors [B, nbits/32] int32 (the fingerprint of include/kpd.h): one bit per atom and per
+        neighbourhood radius 0 .. `radius`; all zero for a ligand without a molecule."""
+        return self._keys(largest_frag, with_orders, radius, nbits)['fp']
+
+    def set_metrics(self, group_ptr: Optional[torch.Tensor] = None, train_keys: Optional[torch.Tensor] = None,
+                    connectivity_thresh: float = 0.5, radius: int = 2, nbits: int = 2048, largest_frag: bool = True,
+                    with_orders: bool = True) -> Dict[str, object]:
+        """Upstream's numbers about the set of samples, from keys and fingerprints instead of SMILES and RDKit fingerprints:
+        uniqueness = distinct keys / connected ligands (`compute_uniqueness`, analysis/metrics.py:135-140; "connected": has a
+        molecule and largest fragment atoms / atoms >= `connectivity_thresh`, `compute_connectivity` without the sanitisation
+        step before it, as in `metrics`), novelty = share of those distinct keys that are not in `train_keys`
+        (`compute_novelty`; only when `train_keys`, e.g. from `training_keys`, is given), and with `group_ptr` [G+1] (int32
+        offsets: consecutive ligands of a pocket form a group) diversity_per_group [G] (float64 device tensor: the mean
+        Tanimoto distance over the pairs of a group's ligands that have a molecule, 0.0 for fewer than two,
+        `MoleculeProperties.calculate_diversity`), diversity (its mean) and diversity_std (`np.std`, as upstream prints).
+        An empty set gives upstream's 0.0."""
+        r = self._keys(largest_frag, with_orders, radius, nbits)
+        has = (r['status'] & hip.KEY_NO_MOLECULE) == 0
+        n = (self.lig_ptr[1:] - self.lig_ptr[:-1]).double()
+        connected = has & (self.summary[:, 2].double() / n >= connectivity_thresh)
+        keys = r['key'][connected]
+        distinct = torch.unique(keys)
+        out: Dict[str, object] = dict(uniqueness=distinct.numel() / keys.numel() if keys.numel() else 0.0)
+        if train_keys is not None:
+            known = torch.isin(distinct, torch.as_tensor(train_keys, dtype=torch.int64).to(distinct.device))
+            out['novelty'] = float((~known).double().mean()) if distinct.numel() else 0.0
+        if group_ptr is not None:
+            group_ptr = torch.as_tensor(group_ptr, dtype=torch.int32).to(self.lig_ptr.device).contiguous()
+            if group_ptr.numel() < 2 or len(self) == 0:           # no groups, or no ligands in them
+                per_group = torch.zeros(max(group_ptr.numel() - 1, 0), dtype=torch.float64, device=group_ptr.device)
+            else:
+                div_sum, n_pairs, status = hip.fp_diversity(r['fp'], has, group_ptr)
+                if bool(status.any()):
+                    raise hip.KpdError(f'set_metrics: group_ptr must be ascending offsets into the {len(self)} ligands')
+                per_group = torch.where(n_pairs > 0, div_sum / n_pairs.clamp(min=1).double(), torch.zeros_like(div_sum))
+            out['diversity_per_group'] = per_group
+            out['diversity'] = float(per_group.mean()) if per_group.numel() else 0.0
+            out['diversity_std'] = float(per_group.std(unbiased=False)) if per_group.numel() else 0.0
+        return out
+
 
 def _class_tables(lig_elements: Sequence[str], allowed_bonds: Optional[Dict[str, object]]):
     allowed_bonds = ALLOWED_BONDS if allowed_bonds is None else allowed_bonds
@@ -138,10 +205,24 @@ def build_molecules(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], l
                      hip._dev_f32(pos, 'pos'), lig_elements)
 
 
+def training_keys(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig_elements: Sequence[str], largest_frag: bool = True,
+                  with_orders: bool = True) -> torch.Tensor:
+    """The keys of the training ligands as a sorted int64 tensor without repeats, for `set_metrics(train_keys=...)`.
+    `lig_pos` / `lig_feat`: the processed dataset's ligand coordinates and one-hot features (GPU tensors, as for
+    `build_molecules`).  The ligands are perceived by the same rule as the samples, so novelty compares like with like; pass
+    the `largest_frag` / `with_orders` the samples' keys will be computed with.  Ligands without a molecule are left out."""
+    mols = build_molecules(lig_pos, lig_feat, lig_elements)
+    r = mols._keys(largest_frag, with_orders)
+    return torch.unique(r['key'][(r['status'] & hip.KEY_NO_MOLECULE) == 0])
+
+
 def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_counts: Optional[torch.Tensor] = None,
-                    allowed_bonds: Optional[Dict[str, object]] = None, connectivity_thresh: float = 0.5, device=None) -> Dict[str, float]:
+                    allowed_bonds: Optional[Dict[str, object]] = None, connectivity_thresh: float = 0.5, device=None,
+                    train_keys: Optional[torch.Tensor] = None, set_metrics: bool = False) -> Dict[str, float]:
     """The part of `ModelAnalyzer.sample_and_analyze` (analysis/metrics.py:60-100) that needs no rdkit: `samples` is the list
-    of {'positions', 'features'} dicts `_sample` returns, one per pocket; the result is `Molecules.metrics` over all of them.
+    of {'positions', 'features'} dicts `_sample` returns, one per pocket; the result is `Molecules.metrics` over all of them
+    and, with `set_metrics=True`, `Molecules.set_metrics` as well (uniqueness, novelty against `train_keys` if given, and the
+    diversity of every pocket's ligands).
     `_sample` hands its ligands back on the host: name the GPU to work on as `device` and they are copied there (one copy of
     the concatenated batch would do as well: `build_molecules` takes GPU tensors only and never computes on the host)."""
     lig_pos, lig_feat = [], []
@@ -150,4 +231,9 @@ def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_count
         lig_feat.extend(rec['features'])
     if device is not None:
         lig_pos, lig_feat = [p.to(device) for p in lig_pos], [f.to(device) for f in lig_feat]
-    return build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds).metrics(type_counts, connectivity_thresh)
+    mols = build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds)
+    out = mols.metrics(type_counts, connectivity_thresh)
+    if set_metrics:
+        group_ptr = torch.tensor([0] + [len(rec['positions']) for rec in samples], dtype=torch.int64).cumsum(0).to(torch.int32)
+        out.update(mols.set_metrics(group_ptr, train_keys, connectivity_thresh))
+    return out
