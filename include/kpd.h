@@ -698,8 +698,9 @@ kpd_status kpd_interface_points(const float *rec_x, const int32_t *rec_ptr, cons
  * through openbabel), check_atom_valency and compute_avg_frag_size (analysis/metrics.py:156-206) and the SDF writing of
  * sample.py.  openbabel's rules cannot be restated here, so THIS COMMENT IS THE DEFINITION: the lookup-table builder of the
  * EDM / DiffSBDD lineage that upstream's molecule_builder.py was adapted from.  Connectivity comes from covalent radii, bond
- * orders from length classes, both under valence caps.  Sanitisation, force fields and docking stay with the caller; what
- * upstream compares SMILES for (uniqueness, novelty) is kpd_mol_keys below.
+ * orders from length classes, both under valence caps.  Sanitisation, RDKit's force fields and docking stay with the caller;
+ * what upstream compares SMILES for (uniqueness, novelty) is kpd_mol_keys below, and the relaxation of the samples inside their
+ * pockets (by a force field of this library's own, not UFF) is kpd_relax at the end of this file.
  *
  * Ligands carry heavy atoms only; no hydrogens are added.  Everything below is per ligand (at most 256 atoms).
  * Element table, by atomic number (radii after Pyykko & Atsumi 2009 in integer picometres, single / double / triple, 0 = no
@@ -811,6 +812,76 @@ kpd_status kpd_mol_keys(const int32_t *lig_ptr, int32_t n_atoms, int32_t B, cons
                         int32_t nbits, int64_t *key, uint32_t *fp, int64_t *atom_inv, int32_t *status, void *stream);
 kpd_status kpd_fp_diversity(const uint32_t *fp, const uint8_t *use, int32_t B, int32_t W, const int32_t *group_ptr, int32_t G,
                             double *div_sum, int64_t *n_pairs, int32_t *status, void *stream);
+
+/* Relaxation of sampled ligands inside their rigid pockets (csrc/relax.hip).  Stands where upstream runs
+ * analysis/pocket_minimization.py: RDKit's UFF on ligand + receptor with every receptor atom fixed, maxIts = 400, then the plain
+ * (unaligned) CalcRMS and the energies before and after.  RDKit's UFF cannot be restated here -- it needs hydrogens, atom typing,
+ * torsions and inversions -- so THIS COMMENT IS THE DEFINITION of the force field and of the minimiser.  IT IS NOT UFF: heavy
+ * atoms only, no torsions or inversions, no electrostatics, a rigid pocket.  Its energies are comparable between samples relaxed
+ * by this function and with nothing else, RDKit's numbers least of all.
+ *
+ * Ligand and pocket are in one frame, as for kpd_clash_score.  All arithmetic is fp64 on values read from the fp32 inputs;
+ * energies in kcal/mol, lengths in Angstrom.  Only the connectivity of kpd_mol_perceive is used, not bond_order (the length
+ * classes know no aromaticity): rest values are the ideal values nearest to the sampled geometry, so a benzene ring stays one.
+ * Bond (i,j):  E = 1/2 k_b (d - r0)^2.  Candidates for r0 from the radii table above, in half picometres: L1 = 2 (r1(i) + r1(j)),
+ *   L2 and L3 the same sums of the double and triple radii where both are non-zero, L15 = (L1 + L2) / 2 where L2 exists;
+ *   r0 = 0.005 L of the candidate nearest to the sampled length, the longer one on a tie.  d < 1e-6: energy, no force.
+ * Angle (i,j,k) at centre j, for i < k among j's neighbours:  E = 1/2 k_a (cos t - cos t0)^2, with c the sampled cosine:
+ *   c > cos 100 deg (-0.1736481776669303): t0 = the sampled angle (small rings are not reshaped); else a centre with four or more
+ *   neighbours: 109.47122 deg (cos t0 = -0.3333333228927115); else c <= cos 150 deg (-0.8660254037844387): 180 deg (cos t0 = -1);
+ *   else c <= cos 114.7356 deg (-0.4184314830435483): 120 deg (-1/2); else 109.47122 deg.  cos = (u.v) * (1 / sqrt(|u|^2 |v|^2));
+ *   an angle with an arm shorter than 1e-6 adds nothing, and one that cannot be measured in the sample keeps "the sampled angle".
+ * Non-bonded pair:  Lennard-Jones in UFF's form, e(d) = D_ij [(x_ij / d)^12 - 2 (x_ij / d)^6], x_ij = sqrt(x_i) sqrt(x_j),
+ *   D_ij = sqrt(D_i) sqrt(D_j) (fp64 roots of the fp32 parameters).  The pair energy is e(d) - e(r_c) for d < r_c and 0 beyond.
+ *   Soft core: for d < s x_ij it is the tangent line of e at s x_ij (minus e(r_c)), which keeps the energy and the force of a
+ *   clashing sample finite and well scaled.  d < 1e-6: energy, no force.  It applies, with weight w_intra, to the pairs of ligand
+ *   atoms whose shortest path has three or more bonds or that are not connected, and, with weight 1, to every ligand atom x every
+ *   atom of its pocket.  The vdW parameters {x, D} come from the caller: lig_vdw [F,2] per ligand class, pocket_vdw [n_pocket,2].
+ * E = ((bond + angle) + intra) + pocket.  gmax = the largest norm of an atom's gradient.
+ *
+ * Minimiser: L-BFGS on the 3n ligand coordinates, 8 stored pairs (s, y), two-loop recursion with the initial scaling
+ *   gamma = s.y / y.y of the newest pair; a pair with s.y <= 1e-10 y.y, or with y.y <= 1e-20 g'.g' (g' the gradient at the new
+ *   point: where the energy is linear in the step, as inside the soft core, y is rounding noise), is not stored.  One iteration, while gmax > gtol and fewer
+ *   than max_iters were run: p = -H g; if not g.p < 0, drop the pairs and take p = -g.  First trial step
+ *   alpha = min(1, max_step / max_i |p_i|) (no atom moves more than max_step in a trial: none tunnels through another); accept if
+ *   E' is finite and E' <= E + 1e-4 alpha g.p, else halve alpha, at most 20 times.  If no step is accepted and pairs are stored,
+ *   drop them (the iteration is spent); if none are stored, stop with status bit 3.  Every dot product and every energy and
+ *   gradient sum is reduced in a fixed order that depends on the ligand and its pocket only.
+ *   The report describes the rows written: after at least one iteration the positions are rounded to fp32 and the energy, its
+ *   parts and gmax are evaluated once more there (that evaluation is counted).  Should the rounding alone turn a gain into a rise
+ *   (E > E_before), the ligand keeps its input rows and the numbers of the first evaluation.  Hence E_after <= E_before always.
+ *
+ * kpd_relax: pos [n_atoms,3], lig_ptr [B+1], elem [n_atoms], bond_ij [cap_bonds,2], bond_ptr [B+1], mol_status [B] as
+ *   kpd_mol_perceive wrote them, z [F], lig_vdw [F,2]; pocket_x [n_pocket,3], pocket_vdw [n_pocket,2], pocket_ptr [P+1] (pocket q
+ *   = rows [pocket_ptr[q], pocket_ptr[q+1]), any number of atoms), pocket_of [B] (the pocket of every ligand, -1 = none; many
+ *   ligands share one pocket without copies of it); all device pointers.  max_atoms (1 .. 256) and max_pocket are host-known
+ *   upper bounds that size the workgroup's LDS: a ligand with more than max_atoms atoms is left out (bit 0); of a pocket, the
+ *   first atoms are staged in LDS, as many as max_pocket asks for and fit, and the rest is read from global memory with the
+ *   same result to the bit.  params: NULL for kpd_relax_defaults (k_b 700, k_a 200, r_c 10, s 0.6, w_intra 1, gtol 1e-3, max_step
+ *   0.2, max_iters 400).
+ *   Out (device): pos_out [n_atoms,3] fp32 (may be pos itself); report [B,12] fp64 = {E_before, E_after, rmsd (plain RMSD of
+ *   the rows written against the input rows, in atom order, no alignment, no symmetry), gmax_after, iterations, energy
+ *   evaluations, bond / angle / intra / pocket part of E_after, pocket part of E_before, gmax_before}; status [B]:
+ *   bit 0 = no molecule (mol_status bits 0, 1 or 3, more than max_atoms atoms, or inputs that are no output of kpd_mol_perceive:
+ *   an element out of range, a bond outside the ligand, twice, between elements the bond rule never bonds, or a seventh
+ *   neighbour), bit 1 = a non-finite coordinate in the ligand or its pocket, a vdW parameter that is not finite, x <= 0 or D < 0,
+ *   a pocket_of outside [-1, P) or a malformed pocket segment, bit 2 = gmax_after > gtol without bit 3: max_iters came first, or the fp32
+ *   rounding of pos_out alone lifts the gradient over gtol (k_b times half an ulp of a coordinate of 10 A is 3e-4; informational), bit 3 = the
+ *   line search could not lower the energy further (informational; the result stands).  With bit 0 or 1 the ligand's rows of
+ *   pos_out are its input rows and its report is zeros; nothing is read or written out of bounds.
+ *   One workgroup per ligand, one launch (and one copy pos -> pos_out) for the whole minimisation of every ligand whatever B is;
+ *   no scratch, no host synchronisation, no atomics on floats; a ligand's result is bitwise independent of the rest of the batch,
+ *   of max_atoms / max_pocket, and of the repeat. */
+typedef struct kpd_relax_params {
+    double k_b, k_a, r_c, s, w_intra, gtol, max_step;
+    int32_t max_iters;
+} kpd_relax_params;
+void kpd_relax_defaults(kpd_relax_params *params);
+kpd_status kpd_relax(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, int32_t max_atoms, const int32_t *elem,
+                     int32_t F, const int32_t *z, const float *lig_vdw, const int32_t *bond_ij, const int32_t *bond_ptr,
+                     int32_t cap_bonds, const int32_t *mol_status, const float *pocket_x, const float *pocket_vdw,
+                     const int32_t *pocket_ptr, int32_t n_pocket, int32_t P, int32_t max_pocket, const int32_t *pocket_of,
+                     const kpd_relax_params *params, float *pos_out, double *report, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -16,29 +16,6 @@ namespace kpd {
 
 enum : int { SDF_NONFINITE = 1, SDF_WIDE = 2, SDF_NO_MOLECULE = 4, SDF_CAPACITY = 8 };
 
-// the element table: r1 | r2 << 8 | r3 << 16 | cap << 24 (covalent radii after Pyykko & Atsumi 2009 in pm, 0 = no bond of that
-// order; cap = chemical valence cap); 0 for every other atomic number
-__device__ __forceinline__ unsigned element_row(int z) {
-#define KPD_EL(r1, r2, r3, cap) ((unsigned)(r1) | (unsigned)(r2) << 8 | (unsigned)(r3) << 16 | (unsigned)(cap) << 24)
-    switch (z) {
-    case 1: return KPD_EL(32, 0, 0, 1);         // H
-    case 5: return KPD_EL(85, 78, 0, 3);        // B
-    case 6: return KPD_EL(75, 67, 60, 4);       // C
-    case 7: return KPD_EL(71, 60, 54, 3);       // N
-    case 8: return KPD_EL(63, 57, 0, 2);        // O
-    case 9: return KPD_EL(64, 0, 0, 1);         // F
-    case 14: return KPD_EL(116, 0, 0, 4);       // Si
-    case 15: return KPD_EL(111, 102, 0, 5);     // P
-    case 16: return KPD_EL(103, 94, 0, 6);      // S
-    case 17: return KPD_EL(99, 0, 0, 1);        // Cl
-    case 33: return KPD_EL(121, 0, 0, 3);       // As
-    case 35: return KPD_EL(114, 0, 0, 1);       // Br
-    case 53: return KPD_EL(133, 0, 0, 1);       // I
-    default: return 0u;
-    }
-#undef KPD_EL
-}
-
 // fp64 sum of squares of the exact differences; every product and sum is rounded on its own (no fused multiply-add)
 __device__ __forceinline__ double mol_d2(const float *p, int i, int j) {
     const double dx = (double)p[i * 3] - (double)p[j * 3], dy = (double)p[i * 3 + 1] - (double)p[j * 3 + 1],

@@ -1,5 +1,6 @@
 // What the molecule kernels share (molecule.hip: perception and SDF text; molset.hip: keys, fingerprints, diversity): the size
-// limits of one ligand, the status bits of kpd_mol_perceive and the segment check.
+// limits of one ligand, the element table, the status bits of kpd_mol_perceive and the segment check.
+// relax.hip reads the same table for its rest lengths.
 #pragma once
 #include "common.h"
 
@@ -10,6 +11,29 @@ constexpr int MOL_W = MOL_MAX / 32;     // words of one row of a bit matrix
 constexpr int MOL_K = MOL_MAX / 64;     // atoms per lane
 
 enum : int { MOL_EMPTY = 1, MOL_CAPACITY = 2, MOL_BAD_ATOM = 4, MOL_BAD_SEGMENT = 8 };
+
+// the element table: r1 | r2 << 8 | r3 << 16 | cap << 24 (covalent radii after Pyykko & Atsumi 2009 in pm, 0 = no bond of that
+// order; cap = chemical valence cap); 0 for every other atomic number
+__device__ __forceinline__ unsigned element_row(int z) {
+#define KPD_EL(r1, r2, r3, cap) ((unsigned)(r1) | (unsigned)(r2) << 8 | (unsigned)(r3) << 16 | (unsigned)(cap) << 24)
+    switch (z) {
+    case 1: return KPD_EL(32, 0, 0, 1);         // H
+    case 5: return KPD_EL(85, 78, 0, 3);        // B
+    case 6: return KPD_EL(75, 67, 60, 4);       // C
+    case 7: return KPD_EL(71, 60, 54, 3);       // N
+    case 8: return KPD_EL(63, 57, 0, 2);        // O
+    case 9: return KPD_EL(64, 0, 0, 1);         // F
+    case 14: return KPD_EL(116, 0, 0, 4);       // Si
+    case 15: return KPD_EL(111, 102, 0, 5);     // P
+    case 16: return KPD_EL(103, 94, 0, 6);      // S
+    case 17: return KPD_EL(99, 0, 0, 1);        // Cl
+    case 33: return KPD_EL(121, 0, 0, 3);       // As
+    case 35: return KPD_EL(114, 0, 0, 1);       // Br
+    case 53: return KPD_EL(133, 0, 0, 1);       // I
+    default: return 0u;
+    }
+#undef KPD_EL
+}
 
 __device__ __forceinline__ bool mol_segment(const int *__restrict__ ptr, int b, int n, int &a0, int &a1) {
     a0 = ptr[b];

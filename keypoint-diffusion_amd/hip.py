@@ -84,6 +84,11 @@ class KpdRecOut(C.Structure):
                 ('kk_per_graph', C.c_void_p), ('counts', C.c_void_p)]
 
 
+class KpdRelaxParams(C.Structure):
+    _fields_ = [('k_b', C.c_double), ('k_a', C.c_double), ('r_c', C.c_double), ('s', C.c_double), ('w_intra', C.c_double),
+                ('gtol', C.c_double), ('max_step', C.c_double), ('max_iters', C.c_int32)]
+
+
 class KpdError(RuntimeError):
     pass
 
@@ -189,6 +194,10 @@ def lib():
     L.kpd_mol_keys.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p] +
                                [C.c_int32] * 4 + [C.c_void_p] * 5)
     L.kpd_fp_diversity.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
+    L.kpd_relax_defaults.argtypes = [C.POINTER(KpdRelaxParams)]
+    L.kpd_relax_defaults.restype = None
+    L.kpd_relax.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
+                            [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p, C.POINTER(KpdRelaxParams)] + [C.c_void_p] * 4)
     _lib = L
     return L
 
@@ -220,7 +229,7 @@ EXPORTS = [
     'kpd_dist_hinge',
     'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
     'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
-    'kpd_mol_keys', 'kpd_fp_diversity',
+    'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_relax_defaults', 'kpd_relax',
 ]
 
 
@@ -1098,6 +1107,68 @@ def fp_diversity(fp: torch.Tensor, use: torch.Tensor, group_ptr: torch.Tensor):
     status = torch.empty(G, dtype=torch.int32, device=dev)
     check(lib().kpd_fp_diversity(_ptr(fp), _ptr(use), B, W, _ptr(group_ptr), G, _ptr(div_sum), _ptr(n_pairs), _ptr(status), _stream()))
     return div_sum, n_pairs, status
+
+
+RELAX_NO_MOLECULE, RELAX_BAD_INPUT, RELAX_ITER_CAP, RELAX_LINE_SEARCH = 1, 2, 4, 8      # status bits of kpd_relax
+RELAX_REPORT = ('E_before', 'E_after', 'rmsd', 'gmax_after', 'iterations', 'evaluations', 'E_bond', 'E_angle', 'E_intra', 'E_pocket',
+                'E_pocket_before', 'gmax_before')
+
+
+def relax_params(**params) -> KpdRelaxParams:
+    """The parameters of kpd_relax: the library's defaults (kpd_relax_defaults) with the given fields replaced."""
+    p = KpdRelaxParams()
+    lib().kpd_relax_defaults(C.byref(p))
+    names = {f[0] for f in KpdRelaxParams._fields_}
+    for k, v in params.items():
+        if k not in names:
+            raise KpdError(f'relax: unknown parameter {k!r} (known: {sorted(names)})')
+        setattr(p, k, int(v) if k == 'max_iters' else float(v))
+    if not (p.k_b >= 0 and p.k_a >= 0 and p.r_c > 0 and 0 < p.s < 1 and p.w_intra >= 0 and p.gtol >= 0 and p.max_step > 0 and
+            p.max_iters >= 0):
+        raise KpdError(f'relax: k_b {p.k_b}, k_a {p.k_a}, w_intra {p.w_intra}, gtol {p.gtol} must be >= 0, r_c {p.r_c} and max_step '
+                       f'{p.max_step} > 0, s {p.s} in (0, 1), max_iters {p.max_iters} >= 0')
+    return p
+
+
+def relax(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_vdw: torch.Tensor, mol: dict, pocket_x: torch.Tensor, pocket_vdw: torch.Tensor,
+          pocket_ptr: torch.Tensor, pocket_of: torch.Tensor, max_atoms: int = MOL_MAX_ATOMS, max_pocket: Optional[int] = None, **params):
+    """Relax a batch of perceived ligands inside their rigid pockets on the GPU (kpd_relax; include/kpd.h states the force field
+    and the minimiser: this library's own, NOT UFF).  pos [N,3] fp32, lig_ptr [B+1] int32, z: the atomic number of every feature
+    class, lig_vdw [F,2] fp32 {x, D} per class, `mol`: what `mol_perceive` returned, pocket_x [M,3], pocket_vdw [M,2] fp32,
+    pocket_ptr [P+1] and pocket_of [B] int32 (-1: no pocket); all GPU tensors.  max_atoms / max_pocket: host-known upper bounds
+    that size the kernel's LDS (a larger ligand is left out, a larger pocket is merely read from global memory).  Returns
+    (pos_out [N,3] fp32, report [B,12] float64 with the columns RELAX_REPORT, status [B] int32).  No host synchronisation."""
+    pos = _dev_f32(pos, 'pos')
+    B = _mol_ptr(lig_ptr)
+    for name in ('elem', 'bonds', 'bond_ptr', 'status'):
+        t = mol.get(name)
+        if t is None or not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise KpdError(f'relax: {name} must be a contiguous int32 GPU tensor')
+    for name, t in (('pocket_ptr', pocket_ptr), ('pocket_of', pocket_of)):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()):
+            raise KpdError(f'relax: {name} must be a contiguous 1-D int32 GPU tensor')
+    lig_vdw, pocket_x, pocket_vdw = _dev_f32(lig_vdw, 'lig_vdw'), _dev_f32(pocket_x, 'pocket_x'), _dev_f32(pocket_vdw, 'pocket_vdw')
+    N, F, M, P = pos.shape[0], len(z), pocket_x.shape[0], pocket_ptr.numel() - 1
+    cap_bonds = mol['bonds'].numel() // 2
+    if (pos.shape != (N, 3) or F < 1 or lig_vdw.shape != (F, 2) or mol['elem'].numel() != N or mol['bond_ptr'].numel() != B + 1 or
+            mol['status'].numel() != B or pocket_x.shape != (M, 3) or pocket_vdw.shape != (M, 2) or P < 0 or pocket_of.numel() != B):
+        raise KpdError(f'relax: pos {tuple(pos.shape)}, {B} ligands, {F} classes, lig_vdw {tuple(lig_vdw.shape)}, pocket_x '
+                       f'{tuple(pocket_x.shape)}, pocket_vdw {tuple(pocket_vdw.shape)}, {P} pockets, pocket_of {tuple(pocket_of.shape)} '
+                       f'do not match each other or the perceived molecules')
+    max_atoms = int(max_atoms)
+    if not 1 <= max_atoms <= MOL_MAX_ATOMS:
+        raise KpdError(f'relax: max_atoms {max_atoms} must be 1 .. {MOL_MAX_ATOMS}')
+    p = relax_params(**params)
+    dev = pos.device
+    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
+    pos_out = torch.empty_like(pos)
+    report = torch.empty(B, 12, dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib().kpd_relax(_ptr(pos), _ptr(lig_ptr), N, B, max_atoms, _ptr(mol['elem']), F, _ptr(zt), _ptr(lig_vdw), _ptr(mol['bonds']),
+                          _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']), _ptr(pocket_x), _ptr(pocket_vdw), _ptr(pocket_ptr), M, P,
+                          M if max_pocket is None else int(max_pocket), _ptr(pocket_of), C.byref(p), _ptr(pos_out), _ptr(report),
+                          _ptr(status), _stream()))
+    return pos_out, report, status
 
 
 def sample_update(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h, coef):

@@ -16,9 +16,16 @@ inherits the length-class bond orders.
 openbabel's perception rules are not restated: include/kpd.h defines the rule used here, the lookup-table builder of the
 EDM / DiffSBDD lineage (covalent radii for connectivity, length classes for the bond orders, valence caps).  The bond orders
 are length classes, not a Kekule structure; connectivity, fragments and `metrics` do not depend on them.  What needs
-sanitisation, a force field or a docking program (`validity`, QED / SA, UFF relaxation, docking) stays with the caller, who
-can read the SDF blocks with rdkit.  There is no CPU implementation: tensors must live on the GPU and the HIP library must be
-present.
+sanitisation or a docking program (`validity`, QED / SA, docking) stays with the caller, who can read the SDF blocks with rdkit.
+
+Where upstream minimises every sample inside its pocket with RDKit's UFF (analysis/pocket_minimization.py), `Molecules.relax` /
+`relax_samples` relax the whole batch in one kernel launch (`kpd_relax`, csrc/relax.hip) with a force field of this library's
+own, defined in include/kpd.h: harmonic bonds and angles around the ideal values nearest to the sampled geometry, soft-core
+Lennard-Jones inside the ligand and against the pocket, L-BFGS.  It is NOT UFF: heavy atoms only, no torsions or inversions,
+no electrostatics, a rigid pocket.  Its energies rank samples relaxed here against each other; they are not comparable with
+RDKit's, and whoever needs UFF itself still runs RDKit on the SDF blocks.
+
+There is no CPU implementation: tensors must live on the GPU and the HIP library must be present.
 """
 from typing import Dict, List, Optional, Sequence
 
@@ -42,6 +49,29 @@ ALLOWED_BONDS: Dict[str, int] = {'H': 1, 'C': 4, 'N': 3, 'O': 2, 'F': 1, 'B': 3,
 
 EPS = 1e-10         # LigandTypeDistribution.EPS
 
+# van der Waals parameters for `Molecules.relax`, element -> (x in Angstrom, D in kcal/mol), in the form of the UFF table of Rappe
+# et al. 1992.  RECALLED, NOT CHECKED AGAINST THE PAPER: nothing may rely on these being UFF's values; pass `vdw=` to override.
+VDW_PARAMS: Dict[str, tuple] = {
+    'H': (2.886, 0.044), 'B': (4.083, 0.180), 'C': (3.851, 0.105), 'N': (3.660, 0.069), 'O': (3.500, 0.060), 'F': (3.364, 0.050),
+    'Na': (2.983, 0.030), 'Mg': (3.021, 0.111), 'Si': (4.295, 0.402), 'P': (4.147, 0.305), 'S': (4.035, 0.274), 'Cl': (3.947, 0.227),
+    'K': (3.812, 0.035), 'Ca': (3.399, 0.238), 'Mn': (2.961, 0.013), 'Fe': (2.912, 0.013), 'Co': (2.872, 0.014), 'Ni': (2.834, 0.015),
+    'Cu': (3.495, 0.005), 'Zn': (2.763, 0.124), 'As': (4.230, 0.309), 'Se': (4.205, 0.291), 'Br': (4.189, 0.251), 'I': (4.500, 0.339),
+}
+
+
+def vdw_table(elements: Sequence[str], vdw: Optional[Dict[str, tuple]] = None) -> List[List[float]]:
+    """[{x, D}] for the element symbols, from `vdw` first and VDW_PARAMS second; an element in neither raises."""
+    rows = []
+    for el in elements:
+        row = (vdw or {}).get(el, VDW_PARAMS.get(el))
+        if row is None:
+            raise hip.KpdError(f'relax: no van der Waals parameters for element {el!r}; pass vdw={{{el!r}: (x, D)}}')
+        x, d = float(row[0]), float(row[1])
+        if not (0 < x < float('inf') and 0 <= d < float('inf')):
+            raise hip.KpdError(f'relax: van der Waals parameters of {el!r} must be x > 0 and D >= 0 (got {row!r})')
+        rows.append([x, d])
+    return rows
+
 
 class Molecules:
     """The perceived molecules of a batch of ligands, as device tensors:
@@ -55,10 +85,12 @@ class Molecules:
     def __init__(self, lig_ptr: torch.Tensor, summary: torch.Tensor, status: torch.Tensor, elem: Optional[torch.Tensor] = None,
                  valence: Optional[torch.Tensor] = None, frag: Optional[torch.Tensor] = None, bonds: Optional[torch.Tensor] = None,
                  order: Optional[torch.Tensor] = None, bond_ptr: Optional[torch.Tensor] = None, pos: Optional[torch.Tensor] = None,
-                 lig_elements: Optional[Sequence[str]] = None):
+                 lig_elements: Optional[Sequence[str]] = None, max_atoms: Optional[int] = None, sizes: Optional[List[int]] = None):
         self.lig_ptr, self.summary, self.status = lig_ptr, summary, status
         self.elem, self.valence, self.frag, self.bonds, self.order, self.bond_ptr = elem, valence, frag, bonds, order, bond_ptr
         self.pos, self.lig_elements = pos, None if lig_elements is None else list(lig_elements)
+        self._sizes = None if sizes is None else list(sizes)           # host-known atoms per ligand, if the builder knew them
+        self._max_atoms = max_atoms if max_atoms is not None or not self._sizes else max(self._sizes)
 
     def __len__(self) -> int:
         return int(self.lig_ptr.numel()) - 1
@@ -169,6 +201,78 @@ class Molecules:
         return out
 
 
+    def relax(self, pocket_pos: List[torch.Tensor], pocket_elements: List[Sequence[str]], pocket_of=None,
+              vdw: Optional[Dict[str, tuple]] = None, **params) -> 'Relaxed':
+        """Relax every ligand inside its rigid pocket on the GPU, all in one launch (`kpd_relax`): what upstream does per ligand
+        in analysis/pocket_minimization.py, with the force field and the L-BFGS minimiser include/kpd.h defines instead of
+        RDKit's UFF.  NOT UFF: heavy atoms only, no torsions or inversions, no electrostatics, a rigid pocket; the energies
+        are comparable between samples relaxed by this function only.
+        `pocket_pos`: a list of [m_p,3] GPU tensors in the ligands' frame, `pocket_elements`: a list of symbol lists, one per
+        pocket; `pocket_of`: the pocket of every ligand (-1: none), all zeros by default when one pocket is given; `vdw`:
+        element -> (x, D), consulted before VDW_PARAMS (an element in neither raises); `params`: k_b, k_a, r_c, s, w_intra,
+        gtol, max_step, max_iters."""
+        if self.pos is None or self.lig_elements is None or self.bonds is None:
+            raise hip.KpdError('these Molecules carry no coordinates: build them with build_molecules')
+        if len(pocket_pos) != len(pocket_elements):
+            raise ValueError('pocket_pos and pocket_elements must have one entry per pocket')
+        if not self.pos.is_cuda or any(not p.is_cuda for p in pocket_pos):
+            raise hip.KpdError('relax: ligands and pockets must live on the GPU; relaxation has no CPU implementation')
+        B, dev = len(self), self.pos.device
+        for q, (p, els) in enumerate(zip(pocket_pos, pocket_elements)):
+            if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] != len(els):
+                raise hip.KpdError(f'relax: pocket {q} has positions {tuple(p.shape)} and {len(els)} element symbols')
+        if pocket_of is None:
+            if len(pocket_pos) != 1:
+                raise ValueError(f'pocket_of is needed to tell which of the {len(pocket_pos)} pockets every ligand sits in')
+            pocket_of = torch.zeros(B, dtype=torch.int32, device=dev)
+        else:
+            host = torch.as_tensor(pocket_of).cpu().flatten()
+            if host.numel() != B or (host.numel() and (int(host.min()) < -1 or int(host.max()) >= len(pocket_pos))):
+                raise ValueError(f'pocket_of must name one of the {len(pocket_pos)} pockets (or -1) for each of the {B} ligands')
+            pocket_of = host.to(torch.int32).to(dev)
+        lig_vdw = torch.tensor(vdw_table(self.lig_elements, vdw), dtype=torch.float32, device=dev).reshape(-1, 2)
+        rows = [r for els in pocket_elements for r in vdw_table(els, vdw)]
+        pocket_vdw = torch.tensor(rows, dtype=torch.float32, device=dev).reshape(-1, 2)
+        sizes = [int(p.shape[0]) for p in pocket_pos]
+        pocket_x = torch.cat([p.reshape(-1, 3).float() for p in pocket_pos]) if sizes else torch.zeros(0, 3, device=dev)
+        pocket_ptr = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0).to(torch.int32).to(dev)
+        z = [ATOMIC_NUMBERS.get(el, 0) for el in self.lig_elements]
+        mol = dict(elem=self.elem, bonds=self.bonds, bond_ptr=self.bond_ptr, status=self.status)
+        if B == 0:
+            return Relaxed(self, self.pos, torch.zeros(0, 12, dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev))
+        n_max = self._max_atoms if self._max_atoms is not None else hip.MOL_MAX_ATOMS
+        pos, report, status = hip.relax(self.pos, self.lig_ptr, z, lig_vdw, mol, pocket_x, pocket_vdw, pocket_ptr, pocket_of,
+                                        max_atoms=max(1, min(n_max, hip.MOL_MAX_ATOMS)), max_pocket=max(sizes, default=0), **params)
+        return Relaxed(self, pos, report, status)
+
+
+class Relaxed:
+    """What `Molecules.relax` returns: `.molecules` (a `Molecules` with the same bond graph at the relaxed positions, so `.sdf()`,
+    `.metrics()` and `.keys()` work unchanged: its SDF blocks are upstream's pocket_minimized_ligands.sdf), `.pos` (a list of
+    per-ligand [n_i,3] tensors), `.report` [B,12] float64 (columns hip.RELAX_REPORT) and `.status` [B] (bits: 1 no molecule,
+    2 bad input, 4 max_iters reached before gtol, 8 line search exhausted; with 1 or 2 the ligand is unchanged), device tensors."""
+
+    def __init__(self, mols: Molecules, pos: torch.Tensor, report: torch.Tensor, status: torch.Tensor):
+        self.molecules = Molecules(mols.lig_ptr, mols.summary, mols.status, mols.elem, mols.valence, mols.frag, mols.bonds, mols.order,
+                                   mols.bond_ptr, pos, mols.lig_elements, mols._max_atoms)
+        self.report, self.status, self._sizes = report, status, mols._sizes
+
+    @property
+    def pos(self) -> List[torch.Tensor]:
+        sizes = self._sizes if self._sizes is not None else (self.molecules.lig_ptr[1:] - self.molecules.lig_ptr[:-1]).tolist()
+        return list(torch.split(self.molecules.pos, sizes))
+
+    def table(self) -> Dict[str, list]:
+        """Upstream's CSV columns (pocket_minimization.py: lig_idx, rmsd, energy_before, energy_after) plus pocket_energy (the
+        ligand-pocket part of energy_after), as lists; ligands that were left out (status bit 0 or 1) have no row, as upstream
+        skips a ligand it could not minimise.  Energies in the units of include/kpd.h's force field, not UFF's."""
+        st = self.status.cpu()
+        rep = self.report.cpu()
+        keep = ((st & (hip.RELAX_NO_MOLECULE | hip.RELAX_BAD_INPUT)) == 0).nonzero().flatten().tolist()
+        return dict(lig_idx=keep, rmsd=rep[keep, 2].tolist(), energy_before=rep[keep, 0].tolist(), energy_after=rep[keep, 1].tolist(),
+                    pocket_energy=rep[keep, 9].tolist())
+
+
 def _class_tables(lig_elements: Sequence[str], allowed_bonds: Optional[Dict[str, object]]):
     allowed_bonds = ALLOWED_BONDS if allowed_bonds is None else allowed_bonds
     z, allowed = [], []
@@ -202,7 +306,7 @@ def build_molecules(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], l
         raise hip.KpdError(f'features {tuple(feat.shape)} do not match the {len(lig_elements)} element symbols')
     m = hip.mol_perceive(pos, feat, ptr, z, allowed)
     return Molecules(ptr, m['summary'], m['status'], m['elem'], m['valence'], m['frag'], m['bonds'], m['order'], m['bond_ptr'],
-                     hip._dev_f32(pos, 'pos'), lig_elements)
+                     hip._dev_f32(pos, 'pos'), lig_elements, sizes=sizes)
 
 
 def training_keys(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig_elements: Sequence[str], largest_frag: bool = True,
@@ -237,3 +341,25 @@ def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_count
         group_ptr = torch.tensor([0] + [len(rec['positions']) for rec in samples], dtype=torch.int64).cumsum(0).to(torch.int32)
         out.update(mols.set_metrics(group_ptr, train_keys, connectivity_thresh))
     return out
+
+
+def relax_samples(samples: List[dict], pockets: List[dict], lig_elements: Sequence[str], device=None,
+                  allowed_bonds: Optional[Dict[str, object]] = None, vdw: Optional[Dict[str, tuple]] = None, **params) -> Relaxed:
+    """The counterpart of `analyze_samples` for upstream's analysis/pocket_minimization.py: `samples` is the list of
+    {'positions', 'features'} dicts `_sample` returns, one per pocket, and `pockets` one {'positions': [m,3] tensor, 'elements':
+    m symbols} dict per entry, in the frame of its ligands.  All ligands are perceived and relaxed inside their own pocket in
+    one batch (`Molecules.relax`, whose limits apply: the force field of include/kpd.h, NOT UFF); ligand k of the result is
+    the k-th ligand in the order of `samples`.  `device`: the GPU to copy host tensors to, as for `analyze_samples`."""
+    if len(samples) != len(pockets):
+        raise ValueError('samples and pockets must have one entry per pocket')
+    lig_pos, lig_feat, pocket_of = [], [], []
+    for q, rec in enumerate(samples):
+        lig_pos.extend(rec['positions'])
+        lig_feat.extend(rec['features'])
+        pocket_of.extend([q] * len(rec['positions']))
+    pocket_pos = [torch.as_tensor(p['positions']) for p in pockets]
+    if device is not None:
+        lig_pos, lig_feat = [p.to(device) for p in lig_pos], [f.to(device) for f in lig_feat]
+        pocket_pos = [p.to(device) for p in pocket_pos]
+    mols = build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds)
+    return mols.relax(pocket_pos, [list(p['elements']) for p in pockets], pocket_of=pocket_of, vdw=vdw, **params)
