@@ -152,17 +152,20 @@ __global__ void k_kl_build(const float *__restrict__ lig_x, const int *__restric
             // as "farthest" and fill free slots in index order, so every emitted index is a real atom of this complex
             d = d < 3.0e38f ? d : 3.0e38f;
             int id = l;
-            // insertion into the sorted best-list (strict < keeps the lower index on ties)
+            // insertion into the sorted best-list: strict < puts the new atom behind every entry of equal distance (all of a lower
+            // index); from there on every entry moves down one slot, whatever its distance, so equal entries keep their order
+            bool shift = false;
 #pragma unroll
             for (int j = 0; j < KL_KMAX; ++j) {
                 if (j >= kk) break;                       // (uniform: kk is the same for the whole workgroup)
-                if (d < bd[j] || bi[j] < 0) {
+                if (shift || d < bd[j] || bi[j] < 0) {
                     const float td = bd[j];
                     const int ti = bi[j];
                     bd[j] = d;
                     bi[j] = id;
                     d = td;
                     id = ti;
+                    shift = true;
                 }
             }
         }
@@ -256,15 +259,17 @@ __global__ void k_ll_knn_fill(const float *__restrict__ x, const int *__restrict
             float d = dx * dx + dy * dy + dz * dz;
             d = d < 3.0e38f ? d : 3.0e38f;               // non-finite: farthest, fills free slots in index order (see k_kl_build)
             int id = l;
+            bool shift = false;                          // as in k_kl_build: behind equal distances, then move the rest down
 #pragma unroll
             for (int j = 0; j < KL_KMAX; ++j) {
-                if (j < kk && (d < bd[j] || bi[j] < 0)) {
+                if (j < kk && (shift || d < bd[j] || bi[j] < 0)) {
                     const float td = bd[j];
                     const int ti = bi[j];
                     bd[j] = d;
                     bi[j] = id;
                     d = td;
                     id = ti;
+                    shift = true;
                 }
             }
         }
@@ -428,12 +433,12 @@ kpd_status launch_knn_bipartite(const float *x, const int *x_ptr, int n_x, int m
                                 int max_y, int B, int k, int *off_tmp, int *xm_src, int *xm_dst, int *xm_rowptr, int *ym_src,
                                 int *ym_dst, int *ym_rowptr, hipStream_t st) {
     KPD_REQUIRE(k >= 1 && k <= KL_KMAX, KPD_ERR_INVALID, "knn k=%d outside 1..%d", k, KL_KMAX);
-    hipLaunchKernelGGL(k_kl_offsets, dim3(1), dim3(64), 0, st, x_ptr, y_ptr, B, k, off_tmp);
-    KPD_LAUNCH_CHECK();
     const int words = cdiv(max_y, 32);
     const size_t lds = (size_t)max_x * (3 * sizeof(float) + (size_t)words * sizeof(unsigned) + sizeof(int)) + 16;
     KPD_REQUIRE(lds <= 150 * 1024, KPD_ERR_INVALID, "knn needs %zu B of LDS (max_x=%d, max_y=%d)", lds, max_x, max_y);
     KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_kl_build), 150 * 1024));
+    hipLaunchKernelGGL(k_kl_offsets, dim3(1), dim3(64), 0, st, x_ptr, y_ptr, B, k, off_tmp);
+    KPD_LAUNCH_CHECK();
     // one thread per keypoint in phase 1: 320 threads take the 300 keypoints of an all-atom pocket in ONE pass (256 needed a second pass
     // with 44 active threads: 43.6 -> see profiles/r04_kl_build.txt)
     const int threads = max_y > 256 ? (max_y > 320 ? 512 : 320) : 256;

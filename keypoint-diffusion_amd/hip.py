@@ -848,11 +848,12 @@ def dist_hinge(a: torch.Tensor, a_ptr: torch.Tensor, b: Optional[torch.Tensor], 
 
 
 def build_rec_graph(rec_x: torch.Tensor, rec_ptr: torch.Tensor, max_rec: int, r: float, res_idx: Optional[torch.Tensor] = None,
-                    max_nn: int = 100):
+                    max_nn: int = 100, return_rowptr: bool = False):
     """rr radius graph (+ same-residue flags) of a batch of pockets on the GPU (kpd_build_rec_graph).
     rec_x [n_rec,3] fp32, rec_ptr [B+1] int32, res_idx [n_rec] int32 or None, all on the GPU.
     Returns (src, dst, per_graph [B], same_res bool [E] or None), dst-major with global row numbers.  One host sync
-    (the edge count) — this is input-pipeline work, once per batch, not step-path work."""
+    (the edge count) — this is input-pipeline work, once per batch, not step-path work.  return_rowptr appends the CSR row
+    pointers [n_rec + 1] of the list to the tuple."""
     rec_x = _dev_f32(rec_x, 'rec_x')
     if not (rec_ptr.is_cuda and rec_ptr.dtype == torch.int32):
         raise KpdError('rec_ptr must be an int32 GPU tensor')
@@ -874,7 +875,8 @@ def build_rec_graph(rec_x: torch.Tensor, rec_ptr: torch.Tensor, max_rec: int, r:
     E = int(counts[0].item())
     if E > cap:
         raise KpdError(f'rr graph: {E} edges exceed the capacity {cap} (internal sizing error)')
-    return src[:E], dst[:E], per_graph, (same[:E].bool() if same is not None else None)
+    out = (src[:E], dst[:E], per_graph, (same[:E].bool() if same is not None else None))
+    return out + (rowptr,) if return_rowptr else out
 
 
 POCKET_EMPTY, POCKET_CAPACITY, POCKET_BAD_RES, POCKET_BAD_SEGMENT = 1, 2, 4, 8     # status bits of the two pocket entry points
