@@ -6,6 +6,8 @@
 // Byte work, HBM-bound and tiny: three launches per batch (lines, ligand offsets, compaction).
 #include "common.h"
 #include "emit_core.h"
+#include "engine.h"
+#include "scan_core.h"
 
 namespace kpd {
 
@@ -60,38 +62,11 @@ __global__ void k_emit_ligand_len(const int *__restrict__ lig_ptr, int B, const 
     if (lane == 0) lig_len[b] = s + header_len(a1 - a0);
 }
 
-// single workgroup: exclusive scan of the ligand lengths -> text_ptr [B + 1]
-__global__ void k_emit_scan(const long long *__restrict__ lig_len, int B, long long *__restrict__ text_ptr) {
-    __shared__ long long part[256];
-    __shared__ long long carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < B; base += 256) {
-        const int i = base + tid;
-        const long long v = i < B ? lig_len[i] : 0;
-        part[tid] = v;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const long long t = tid >= off ? part[tid - off] : 0;
-            __syncthreads();
-            part[tid] += t;
-            __syncthreads();
-        }
-        if (i < B) text_ptr[i] = carry + part[tid] - v;
-        __syncthreads();
-        if (tid == 255) carry += part[255];
-        __syncthreads();
-    }
-    if (tid == 0) text_ptr[B] = carry;
-}
-
 // one workgroup per ligand: header, then every line at its offset (in-block scan of the line lengths)
 __global__ void k_emit_compact(const int *__restrict__ lig_ptr, const int *__restrict__ len, const char *__restrict__ slots,
                                const long long *__restrict__ text_ptr, long long capacity, char *__restrict__ text,
                                int *__restrict__ status) {
-    __shared__ int part[256];
-    __shared__ int carry;
+    __shared__ int part[256 / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int a0 = lig_ptr[b], a1 = lig_ptr[b + 1], n = a1 - a0;
     const long long t0 = text_ptr[b];
@@ -108,28 +83,19 @@ __global__ void k_emit_compact(const int *__restrict__ lig_ptr, const int *__res
         }
         text[t0 + hl - 2] = '\n';
         text[t0 + hl - 1] = '\n';
-        carry = hl;
     }
-    __syncthreads();
+    int carry = hl;
     for (int base = 0; base < n; base += 256) {
         const int i = base + tid;
         const int v = i < n ? len[a0 + i] : 0;
-        part[tid] = v;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const int t = tid >= off ? part[tid - off] : 0;
-            __syncthreads();
-            part[tid] += t;
-            __syncthreads();
-        }
+        int total;
+        const int at = carry + block_exclusive<256>(v, part, total);
         if (i < n) {
-            char *dst = text + t0 + carry + part[tid] - v;
+            char *dst = text + t0 + at;
             const char *src = slots + (size_t)(a0 + i) * LINE_SLOT;
             for (int k = 0; k < v; ++k) dst[k] = src[k];
         }
-        __syncthreads();
-        if (tid == 255) carry += part[255];
-        __syncthreads();
+        carry += total;
     }
 }
 
@@ -137,11 +103,19 @@ __global__ void k_emit_compact(const int *__restrict__ lig_ptr, const int *__res
 
 using namespace kpd;
 
-static size_t emit_len_bytes(int n_atoms) { return ((size_t)n_atoms * 4 + 255) & ~(size_t)255; }
+// a line slot and its length for every atom, the bytes of every ligand's block
+struct XyzScratch {
+    int n_atoms, B;
+    char *slots = nullptr;
+    int *len = nullptr;
+    long long *lig_len = nullptr;
+    void operator()(Carve &c) { c(slots, (size_t)n_atoms * LINE_SLOT); c(len, n_atoms); c(lig_len, B); }
+};
 
 extern "C" int64_t kpd_xyz_scratch_bytes(int32_t n_atoms, int32_t B) {
     if (n_atoms < 0 || B < 0) return -1;
-    return (int64_t)((size_t)n_atoms * LINE_SLOT + emit_len_bytes(n_atoms) + (size_t)B * 8 + 8);
+    XyzScratch s{n_atoms, B};
+    return scratch_bytes(s);
 }
 
 extern "C" kpd_status kpd_xyz_emit(const float *pos, const float *feat, const int32_t *lig_ptr, int32_t n_atoms, int32_t B,
@@ -154,9 +128,11 @@ extern "C" kpd_status kpd_xyz_emit(const float *pos, const float *feat, const in
     KPD_REQUIRE(!capacity || text, KPD_ERR_INVALID, "null text buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     KPD_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));
-    char *slots = static_cast<char *>(scratch);
-    int *len = reinterpret_cast<int *>(slots + (size_t)n_atoms * LINE_SLOT);
-    long long *lig_len = reinterpret_cast<long long *>(reinterpret_cast<char *>(len) + emit_len_bytes(n_atoms));
+    XyzScratch s{n_atoms, B};
+    carve_raw(static_cast<char *>(scratch), s);
+    char *slots = s.slots;
+    int *len = s.len;
+    long long *lig_len = s.lig_len;
     if (n_atoms) {
         hipLaunchKernelGGL(k_emit_lines, dim3(cdiv(n_atoms, 256)), dim3(256), 0, st, pos, feat, n_atoms, F, symbols, elem, slots, len,
                            status);
@@ -166,8 +142,7 @@ extern "C" kpd_status kpd_xyz_emit(const float *pos, const float *feat, const in
         hipLaunchKernelGGL(k_emit_ligand_len, dim3(cdiv(B, 4)), dim3(256), 0, st, lig_ptr, B, len, lig_len);
         KPD_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_emit_scan, dim3(1), dim3(256), 0, st, lig_len, B, reinterpret_cast<long long *>(text_ptr));
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(exclusive_scan(st, lig_len, B, reinterpret_cast<long long *>(text_ptr)));
     if (B) {
         hipLaunchKernelGGL(k_emit_compact, dim3(B), dim3(256), 0, st, lig_ptr, len, slots,
                            reinterpret_cast<const long long *>(text_ptr), (long long)capacity, reinterpret_cast<char *>(text), status);

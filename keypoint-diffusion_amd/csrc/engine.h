@@ -107,6 +107,13 @@ size_t carve_bytes(Fn &&list) {
     return c.bytes;
 }
 
+// what a *_scratch_bytes entry point answers for its list: never 0, so that an empty batch still has a region to pass
+template <typename Fn>
+int64_t scratch_bytes(Fn &&list) {
+    const size_t bytes = carve_bytes(list);
+    return (int64_t)(bytes ? bytes : 256);
+}
+
 // sizes the list, reserves that plus `tail` bytes, carves the list out of the arena
 template <typename Fn>
 kpd_status carve(Arena &A, size_t tail, Fn &&list) {
@@ -119,7 +126,8 @@ kpd_status carve(Arena &A, size_t tail, Fn &&list) {
     return KPD_OK;
 }
 
-// lays the list out in `base`, a region of carve_bytes(list) bytes
+// lays the list out in `base`, a region of carve_bytes(list) bytes (caller-supplied scratch: of scratch_bytes(list), which is
+// that, or 256 for an empty list)
 template <typename Fn>
 void carve_raw(char *base, Fn &&list) {
     Carve c;

@@ -8,6 +8,8 @@
 #include <algorithm>
 
 #include "common.h"
+#include "engine.h"
+#include "scan_core.h"
 
 namespace kpd {
 
@@ -41,36 +43,17 @@ __global__ void k_ll_count(const float *__restrict__ x, const int *__restrict__ 
     if (threadIdx.x == 0) per_graph[b] = s_tot;
 }
 
-// Pass 2 (single workgroup): exclusive scan of the per-complex ll counts; totals.
+// Pass 2 is the single-workgroup exclusive scan of the per-complex counts (scan_core.h), which ends with the totals:
 // counts[0] = E_ll, counts[1] = E_kl (= kl_off[B], data independent).
-__global__ void k_scan_graph_counts(const int *__restrict__ per_graph, int B, int *__restrict__ off,
-                                    const int *__restrict__ kl_off, int *__restrict__ counts) {
-    __shared__ int s_part[1024];
-    __shared__ int s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < B; base += blockDim.x) {
-        const int i = base + threadIdx.x;
-        const int v = i < B ? per_graph[i] : 0;
-        s_part[threadIdx.x] = v;
-        __syncthreads();
-        for (int s = 1; s < blockDim.x; s <<= 1) {          // Hillis-Steele inclusive scan
-            int t = threadIdx.x >= s ? s_part[threadIdx.x - s] : 0;
-            __syncthreads();
-            s_part[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < B) off[i] = s_carry + s_part[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == blockDim.x - 1) s_carry += s_part[threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        off[B] = s_carry;
-        counts[0] = s_carry;
+struct GraphCounts {
+    const int *kl_off;
+    int B;
+    int *counts;
+    __device__ void operator()(int total) const {
+        counts[0] = total;
         counts[1] = kl_off ? kl_off[B] : 0;
     }
-}
+};
 
 // Pass 3: fill.  Edge order: dst (centre) major, src ascending.
 __global__ void k_ll_fill(const float *__restrict__ x, const int *__restrict__ ptr, float r2, int max_nn,
@@ -418,8 +401,7 @@ kpd_status launch_radius_graph(const float *x, const int *ptr, int B, int n_tota
     size_t lds = (size_t)max_per_graph * 3 * sizeof(float);
     hipLaunchKernelGGL(k_ll_count, dim3(B), dim3(threads), lds, st, x, ptr, r2, max_nn, deg_tmp, per_graph);
     KPD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_scan_graph_counts, dim3(1), dim3(1024), 0, st, per_graph, B, off_tmp, kl_off_for_counts, counts);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(exclusive_scan(st, per_graph, B, off_tmp, (int *)nullptr, GraphCounts{kl_off_for_counts, B, counts}));
     lds = (size_t)max_per_graph * (3 * sizeof(float) + sizeof(int));
     hipLaunchKernelGGL(k_ll_fill, dim3(B), dim3(threads), lds, st, x, ptr, r2, max_nn, deg_tmp, off_tmp, n_total, cap, src, dst,
                        rowptr);
@@ -454,8 +436,7 @@ kpd_status launch_knn_graph(const float *x, const int *ptr, int B, int n_total, 
     KPD_REQUIRE(k >= 1 && k <= KL_KMAX, KPD_ERR_INVALID, "ll_k=%d outside 1..%d", k, KL_KMAX);
     hipLaunchKernelGGL(k_ll_knn_counts, dim3(cdiv(B, 256)), dim3(256), 0, st, ptr, B, k, per_graph);
     KPD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_scan_graph_counts, dim3(1), dim3(1024), 0, st, per_graph, B, off_tmp, kl_off_for_counts, counts);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(exclusive_scan(st, per_graph, B, off_tmp, (int *)nullptr, GraphCounts{kl_off_for_counts, B, counts}));
     const int threads = std::min(256, std::max(64, (max_per_graph + 63) / 64 * 64));
     hipLaunchKernelGGL(k_ll_knn_fill, dim3(B), dim3(threads), (size_t)max_per_graph * 3 * sizeof(float), st, x, ptr, k, off_tmp, n_total,
                        cap, src, dst, rowptr);
@@ -475,9 +456,7 @@ kpd_status launch_radius_bipartite(const float *x, const int *x_ptr, int n_x, in
     hipLaunchKernelGGL(k_klr_count, dim3(B), dim3(256), (size_t)max_x * 3 * sizeof(float), st, x, x_ptr, y, y_ptr, r * r, max_nn,
                        per_graph_tmp);
     KPD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_scan_graph_counts, dim3(1), dim3(1024), 0, st, per_graph_tmp, B, off_tmp, static_cast<const int *>(nullptr),
-                       scratch2);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(exclusive_scan(st, per_graph_tmp, B, off_tmp, (int *)nullptr, GraphCounts{nullptr, B, scratch2}));
     hipLaunchKernelGGL(k_klr_fill, dim3(B), dim3(256), lds, st, x, x_ptr, y, y_ptr, off_tmp, r * r, max_nn, words, n_x, n_y, xm_src,
                        xm_dst, xm_rowptr, ym_src, ym_dst, ym_rowptr);
     KPD_LAUNCH_CHECK();
@@ -519,9 +498,17 @@ kpd_status lig_graph_caps(int ll_k, int kl_k, int max_n_lig, int max_n_kp, int m
 }
 }  // namespace kpd
 
+// launch_radius_graph's scratch: the in-degree of every atom, the edge offset of every complex
+struct RecGraphScratch {
+    int n_rec, B;
+    int *deg_tmp = nullptr, *off_tmp = nullptr;
+    void operator()(Carve &c) { c(deg_tmp, n_rec); c(off_tmp, (size_t)B + 1); }
+};
+
 extern "C" int64_t kpd_rec_graph_scratch_bytes(int32_t n_rec, int32_t B) {
     if (n_rec < 0 || B < 0) return -1;
-    return (int64_t)((size_t)n_rec + (size_t)B + 4) * (int64_t)sizeof(int);
+    RecGraphScratch s{n_rec, B};
+    return scratch_bytes(s);
 }
 
 extern "C" kpd_status kpd_build_rec_graph(const float *rec_x, const int32_t *rec_ptr, int32_t B, int32_t n_rec, int32_t max_rec,
@@ -533,8 +520,9 @@ extern "C" kpd_status kpd_build_rec_graph(const float *rec_x, const int32_t *rec
                 n_rec, max_nn, cap, (double)r);
     KPD_REQUIRE((res_idx == nullptr) == (same_res == nullptr), KPD_ERR_INVALID, "res_idx and same_res go together");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int *deg_tmp = static_cast<int *>(scratch), *off_tmp = deg_tmp + n_rec;
-    KPD_TRY(launch_radius_graph(rec_x, rec_ptr, B, n_rec, max_rec, r, max_nn, cap, src, dst, rowptr, per_graph, deg_tmp, off_tmp,
+    RecGraphScratch s{n_rec, B};
+    carve_raw(static_cast<char *>(scratch), s);
+    KPD_TRY(launch_radius_graph(rec_x, rec_ptr, B, n_rec, max_rec, r, max_nn, cap, src, dst, rowptr, per_graph, s.deg_tmp, s.off_tmp,
                                 nullptr, counts, st));
     if (same_res && cap) {
         hipLaunchKernelGGL(k_same_res, dim3(cdiv(cap, 256)), dim3(256), 0, st, src, dst, counts, cap, res_idx, same_res);

@@ -10,7 +10,9 @@
 // Small latency-bound kernels; nothing is shared between ligands, no float atomics, bitwise independent of batch composition.
 #include "common.h"
 #include "emit_core.h"
+#include "engine.h"
 #include "molecule_core.h"
+#include "scan_core.h"
 
 namespace kpd {
 
@@ -337,33 +339,6 @@ k_mol_perceive(const float *__restrict__ pos, const float *__restrict__ feat, co
     }
 }
 
-// single workgroup: exclusive scan of per-ligand counts -> ptr [B + 1]
-template <typename T_in, typename T_out>
-__global__ void k_mol_scan(const T_in *__restrict__ count, int B, T_out *__restrict__ ptr) {
-    __shared__ T_out part[256];
-    __shared__ T_out carry;
-    const int tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < B; base += 256) {
-        const int i = base + tid;
-        const T_out v = i < B ? (T_out)count[i] : 0;
-        part[tid] = v;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const T_out t = tid >= off ? part[tid - off] : 0;
-            __syncthreads();
-            part[tid] += t;
-            __syncthreads();
-        }
-        if (i < B) ptr[i] = carry + part[tid] - v;
-        __syncthreads();
-        if (tid == 255) carry += part[255];
-        __syncthreads();
-    }
-    if (tid == 0) ptr[B] = carry;
-}
-
 // one wave per ligand: its bonds from the scratch list to bond_ptr
 __global__ void __launch_bounds__(64)
 k_mol_gather(const int *__restrict__ lig_ptr, const int *__restrict__ tmp_ij, const int *__restrict__ tmp_order,
@@ -585,12 +560,17 @@ k_sdf_write(const float *__restrict__ pos, const int *__restrict__ lig_ptr, cons
 
 using namespace kpd;
 
-static size_t mol_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the bond list before compaction (3 n rows of (i, j) and of the order), bonds per ligand
+struct MolScratch {
+    int n_atoms, B;
+    int *tmp_ij = nullptr, *tmp_order = nullptr, *n_bonds = nullptr;
+    void operator()(Carve &c) { c(tmp_ij, (size_t)n_atoms * 6); c(tmp_order, (size_t)n_atoms * 3); c(n_bonds, B); }
+};
 
 extern "C" int64_t kpd_mol_scratch_bytes(int32_t n_atoms, int32_t B) {
     if (n_atoms < 0 || B < 0) return -1;
-    // the bond list before compaction (3 n rows of (i, j) and of the order), bonds per ligand
-    return (int64_t)(mol_up256((size_t)n_atoms * 24) + mol_up256((size_t)n_atoms * 12) + mol_up256((size_t)B * 4) + 256);
+    MolScratch s{n_atoms, B};
+    return scratch_bytes(s);
 }
 
 extern "C" kpd_status kpd_mol_perceive(const float *pos, const float *feat, const int32_t *lig_ptr, int32_t n_atoms, int32_t B,
@@ -604,10 +584,9 @@ extern "C" kpd_status kpd_mol_perceive(const float *pos, const float *feat, cons
     KPD_REQUIRE(!B || (summary && status), KPD_ERR_INVALID, "null argument");
     KPD_REQUIRE(!cap_bonds || (bond_ij && bond_order), KPD_ERR_INVALID, "null bond buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char *s = static_cast<char *>(scratch);
-    int *tmp_ij = reinterpret_cast<int *>(s);
-    int *tmp_order = reinterpret_cast<int *>(s + mol_up256((size_t)n_atoms * 24));
-    int *n_bonds = reinterpret_cast<int *>(s + mol_up256((size_t)n_atoms * 24) + mol_up256((size_t)n_atoms * 12));
+    MolScratch s{n_atoms, B};
+    carve_raw(static_cast<char *>(scratch), s);
+    int *tmp_ij = s.tmp_ij, *tmp_order = s.tmp_order, *n_bonds = s.n_bonds;
     if (n_atoms) {                                  // atoms of a ligand that is left out (and of none) read -1
         KPD_HIP(hipMemsetAsync(elem, 0xff, (size_t)n_atoms * 4, st));
         KPD_HIP(hipMemsetAsync(valence, 0xff, (size_t)n_atoms * 4, st));
@@ -618,8 +597,7 @@ extern "C" kpd_status kpd_mol_perceive(const float *pos, const float *feat, cons
                            tmp_order, n_bonds, summary, status);
         KPD_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((k_mol_scan<int, int>), dim3(1), dim3(256), 0, st, n_bonds, B, bond_ptr);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(exclusive_scan(st, n_bonds, B, bond_ptr));
     if (B) {
         hipLaunchKernelGGL(k_mol_gather, dim3(B), dim3(64), 0, st, lig_ptr, tmp_ij, tmp_order, bond_ptr, cap_bonds, bond_ij, bond_order,
                            status);
@@ -628,9 +606,18 @@ extern "C" kpd_status kpd_mol_perceive(const float *pos, const float *feat, cons
     return KPD_OK;
 }
 
+// {flags, atoms, bonds, rank} and the bytes of every ligand's block
+struct SdfScratch {
+    int B;
+    int *info = nullptr;
+    long long *lig_len = nullptr;
+    void operator()(Carve &c) { c(info, (size_t)B * 4); c(lig_len, B); }
+};
+
 extern "C" int64_t kpd_sdf_scratch_bytes(int32_t n_atoms, int32_t B) {
     if (n_atoms < 0 || B < 0) return -1;
-    return (int64_t)(mol_up256((size_t)B * 16) + mol_up256((size_t)B * 8) + 256);
+    SdfScratch s{B};
+    return scratch_bytes(s);
 }
 
 extern "C" kpd_status kpd_sdf_emit(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, const int32_t *elem,
@@ -646,16 +633,16 @@ extern "C" kpd_status kpd_sdf_emit(const float *pos, const int32_t *lig_ptr, int
     KPD_REQUIRE(!cap_bonds || (bond_ij && bond_order), KPD_ERR_INVALID, "null bond buffer");
     KPD_REQUIRE(!capacity || text, KPD_ERR_INVALID, "null text buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char *s = static_cast<char *>(scratch);
-    int *info = reinterpret_cast<int *>(s);
-    long long *lig_len = reinterpret_cast<long long *>(s + mol_up256((size_t)B * 16));
+    SdfScratch s{B};
+    carve_raw(static_cast<char *>(scratch), s);
+    int *info = s.info;
+    long long *lig_len = s.lig_len;
     if (B) {
         hipLaunchKernelGGL(k_sdf_size, dim3(B), dim3(256), 0, st, pos, lig_ptr, n_atoms, elem, F, frag, bond_ij, bond_ptr, cap_bonds,
                            mol_status, largest_only, info, lig_len);
         KPD_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((k_mol_scan<long long, long long>), dim3(1), dim3(256), 0, st, lig_len, B, reinterpret_cast<long long *>(text_ptr));
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(exclusive_scan(st, lig_len, B, reinterpret_cast<long long *>(text_ptr)));
     if (B) {
         hipLaunchKernelGGL(k_sdf_write, dim3(B), dim3(256), 0, st, pos, lig_ptr, elem, symbols, frag, bond_ij, bond_order, bond_ptr, info,
                            reinterpret_cast<const long long *>(text_ptr), (long long)capacity, reinterpret_cast<char *>(text), status);

@@ -6,6 +6,8 @@
 // Small latency-bound kernels: a complex is one workgroup (or one row of tiles in k_pocket_mark); nothing is shared between
 // complexes, there are no float atomics, and results are bitwise independent of batch composition.
 #include "common.h"
+#include "engine.h"
+#include "scan_core.h"
 
 namespace kpd {
 
@@ -21,29 +23,6 @@ __device__ __forceinline__ bool segment(const int *__restrict__ ptr, int b, int 
     a0 = ptr[b];
     a1 = ptr[b + 1];
     return a0 >= 0 && a1 >= a0 && a1 <= n;
-}
-
-// exclusive prefix of v over the workgroup, in thread order; total = sum over the workgroup.  part: 4 ints of LDS.
-__device__ __forceinline__ int block_exclusive(int v, int *part, int &total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int s = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(s, off);
-        if (lane >= off) s += t;
-    }
-    __syncthreads();                    // part may still be read from the previous call
-    if (lane == 63) part[w] = s;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < PK_THREADS / 64; ++k) {
-        const int p = part[k];
-        if (k < w) base += p;
-        total += p;
-    }
-    return base + s - v;
 }
 
 // ligand of the complex into LDS; returns its size, or -1 if it does not fit
@@ -172,26 +151,11 @@ k_pocket_count(const int *__restrict__ rec_ptr, int n_rec, const int *__restrict
         }
     }
     int total;
-    block_exclusive(mine, part, total);
+    block_exclusive<PK_THREADS>(mine, part, total);
     if (tid == 0) {
         cnt[b] = total;
         if (!total) atomicOr(status + b, PK_EMPTY);
     }
-}
-
-// single workgroup: exclusive scan of per-complex counts -> ptr [B + 1]
-__global__ void __launch_bounds__(PK_THREADS) k_pocket_scan(const int *__restrict__ cnt, int B, int *__restrict__ ptr) {
-    __shared__ int part[PK_THREADS / 64];
-    int carry = 0;
-    for (int base = 0; base < B; base += PK_THREADS) {
-        const int i = base + threadIdx.x;
-        const int v = i < B ? cnt[i] : 0;
-        int total;
-        const int ex = block_exclusive(v, part, total);
-        if (i < B) ptr[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) ptr[B] = carry;
 }
 
 // ---- 2b. compact: rows in ascending order, residue labels in order of first appearance ---------------------------
@@ -215,7 +179,7 @@ k_pocket_compact(const int *__restrict__ rec_ptr, int n_rec, const int *__restri
         const bool e = i < a1 && emitted(i, a0, a1, res_idx, emit, res_flag);
         const bool first = e && first_atom[a0 + res_idx[i]] == i;
         int total;
-        const int packed = block_exclusive((int)e | ((int)first << 16), part, total);     // both counts are <= 256 per step
+        const int packed = block_exclusive<PK_THREADS>((int)e | ((int)first << 16), part, total);     // both counts are <= 256 per step
         if (e) rows[p0 + n_out + (packed & 0xffff)] = i;
         if (first) res_rank[a0 + res_idx[i]] = n_res + (packed >> 16);
         n_out += total & 0xffff;
@@ -257,7 +221,7 @@ k_ip_select(const float *__restrict__ rec_x, const int *__restrict__ rec_ptr, in
         const int i = base + tid;
         const bool c = i < a1 && cand_mask[i];
         int total;
-        const int ex = block_exclusive(c, part, total);
+        const int ex = block_exclusive<PK_THREADS>((int)c, part, total);
         if (c) clist[a0 + nc + ex] = i;
         nc += total;
     }
@@ -287,7 +251,7 @@ k_ip_select(const float *__restrict__ rec_x, const int *__restrict__ rec_ptr, in
             }
         }
         int total;
-        long long slot = found + block_exclusive(k, part, total);
+        long long slot = found + block_exclusive<PK_THREADS>(k, part, total);
 #pragma unroll
         for (int it = 0; it < IP_ITEMS; ++it) {
             if (!hit[it]) continue;
@@ -374,12 +338,18 @@ k_ip_gather(const float *__restrict__ cand, int cap_cand, const int *__restrict_
 
 using namespace kpd;
 
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// residue flags, first emitted atom and rank of every residue, atoms emitted per complex
+struct PocketScratch {
+    int n_rec, B;
+    uint8_t *res_flag = nullptr;
+    int *first_atom = nullptr, *res_rank = nullptr, *cnt = nullptr;
+    void operator()(Carve &c) { c(res_flag, n_rec); c(first_atom, n_rec); c(res_rank, n_rec); c(cnt, B); }
+};
 
 extern "C" int64_t kpd_pocket_scratch_bytes(int32_t n_rec, int32_t B) {
     if (n_rec < 0 || B < 0) return -1;
-    // residue flags (bytes), first emitted atom and rank of every residue (ints), atoms emitted per complex
-    return (int64_t)(up256((size_t)n_rec) + 2 * up256((size_t)n_rec * 4) + up256((size_t)B * 4) + 256);
+    PocketScratch s{n_rec, B};
+    return scratch_bytes(s);
 }
 
 extern "C" kpd_status kpd_pocket_select(const float *rec_x, const int32_t *rec_ptr, const int32_t *res_idx, const uint8_t *probe,
@@ -395,14 +365,10 @@ extern "C" kpd_status kpd_pocket_select(const float *rec_x, const int32_t *rec_p
     KPD_REQUIRE(!cap_rows || (rows && pocket_res), KPD_ERR_INVALID, "null output");
     KPD_REQUIRE(pocket_cutoff == pocket_cutoff && box_padding == box_padding, KPD_ERR_INVALID, "NaN threshold");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char *p = static_cast<char *>(scratch);
-    uint8_t *res_flag = reinterpret_cast<uint8_t *>(p);
-    p += up256((size_t)n_rec);
-    int *first_atom = reinterpret_cast<int *>(p);
-    p += up256((size_t)n_rec * 4);
-    int *res_rank = reinterpret_cast<int *>(p);
-    p += up256((size_t)n_rec * 4);
-    int *cnt = reinterpret_cast<int *>(p);
+    PocketScratch s{n_rec, B};
+    carve_raw(static_cast<char *>(scratch), s);
+    uint8_t *res_flag = s.res_flag;
+    int *first_atom = s.first_atom, *res_rank = s.res_rank, *cnt = s.cnt;
     if (n_rec) {
         KPD_HIP(hipMemsetAsync(res_flag, 0, (size_t)n_rec, st));
         KPD_HIP(hipMemsetAsync(first_atom, 0x7f, (size_t)n_rec * 4, st));
@@ -420,8 +386,7 @@ extern "C" kpd_status kpd_pocket_select(const float *rec_x, const int32_t *rec_p
                            first_atom, cnt, status);
         KPD_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_pocket_scan, dim3(1), dim3(PK_THREADS), 0, st, cnt, B, pocket_ptr);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(exclusive_scan(st, cnt, B, pocket_ptr));
     if (B) {
         hipLaunchKernelGGL(k_pocket_compact, dim3(B), dim3(PK_THREADS), 0, st, rec_ptr, n_rec, res_idx, emit, res_flag, first_atom,
                            res_rank, pocket_ptr, cap_rows, rows, pocket_res, status);
@@ -430,10 +395,18 @@ extern "C" kpd_status kpd_pocket_select(const float *rec_x, const int32_t *rec_p
     return KPD_OK;
 }
 
+// candidate receptor atoms, candidate midpoints of every complex, points kept per complex
+struct InterfaceScratch {
+    int n_rec, B, cap_cand;
+    int *clist = nullptr, *n_pts = nullptr;
+    float *cand = nullptr;
+    void operator()(Carve &c) { c(clist, n_rec); c(cand, (size_t)B * cap_cand * 3); c(n_pts, B); }
+};
+
 extern "C" int64_t kpd_interface_points_scratch_bytes(int32_t n_rec, int32_t B, int32_t cap_cand) {
     if (n_rec < 0 || B < 0 || cap_cand < 0) return -1;
-    // candidate receptor atoms (ints), candidate midpoints of every complex, points kept per complex
-    return (int64_t)(up256((size_t)n_rec * 4) + up256((size_t)B * cap_cand * 12) + up256((size_t)B * 4) + 256);
+    InterfaceScratch s{n_rec, B, cap_cand};
+    return scratch_bytes(s);
 }
 
 extern "C" kpd_status kpd_interface_points(const float *rec_x, const int32_t *rec_ptr, const uint8_t *cand_mask, int32_t n_rec,
@@ -450,19 +423,16 @@ extern "C" kpd_status kpd_interface_points(const float *rec_x, const int32_t *re
     KPD_REQUIRE(!cap_points || points, KPD_ERR_INVALID, "null output");
     KPD_REQUIRE(dist_thr == dist_thr && excl_thr == excl_thr, KPD_ERR_INVALID, "NaN threshold");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char *p = static_cast<char *>(scratch);
-    int *clist = reinterpret_cast<int *>(p);
-    p += up256((size_t)n_rec * 4);
-    float *cand = reinterpret_cast<float *>(p);
-    p += up256((size_t)B * cap_cand * 12);
-    int *n_pts = reinterpret_cast<int *>(p);
+    InterfaceScratch s{n_rec, B, cap_cand};
+    carve_raw(static_cast<char *>(scratch), s);
+    int *clist = s.clist, *n_pts = s.n_pts;
+    float *cand = s.cand;
     if (B) {
         hipLaunchKernelGGL(k_ip_select, dim3(B), dim3(PK_THREADS), 0, st, rec_x, rec_ptr, n_rec, cand_mask, lig_x, lig_ptr, n_lig, dist_thr,
                            excl_thr, cap_cand, clist, cand, n_cand, n_pts, status);
         KPD_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_pocket_scan, dim3(1), dim3(PK_THREADS), 0, st, n_pts, B, ip_ptr);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(exclusive_scan(st, n_pts, B, ip_ptr));
     if (B) {
         hipLaunchKernelGGL(k_ip_gather, dim3(B), dim3(PK_THREADS), 0, st, cand, cap_cand, ip_ptr, cap_points, points, status);
         KPD_LAUNCH_CHECK();

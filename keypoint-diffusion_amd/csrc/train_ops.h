@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.h"
+#include "scan_core.h"
 #include "sgemm.h"
 
 namespace kpd {
@@ -204,33 +205,6 @@ struct SrcCsr {
 __global__ void k_idx_count(const int *__restrict__ idx, int E, int *__restrict__ cnt) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < E) atomicAdd(&cnt[idx[e]], 1);
-}
-
-__global__ void k_idx_scan(const int *cnt, int n, int *__restrict__ rowptr, int *cursor) {      // cnt may alias cursor
-    __shared__ int s_part[1024];
-    __shared__ int s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += blockDim.x) {
-        const int i = base + threadIdx.x;
-        const int v = i < n ? cnt[i] : 0;
-        s_part[threadIdx.x] = v;
-        __syncthreads();
-        for (int st = 1; st < (int)blockDim.x; st <<= 1) {
-            const int t = (int)threadIdx.x >= st ? s_part[threadIdx.x - st] : 0;
-            __syncthreads();
-            s_part[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n) {
-            rowptr[i] = s_carry + s_part[threadIdx.x] - v;
-            cursor[i] = rowptr[i];
-        }
-        __syncthreads();
-        if (threadIdx.x == blockDim.x - 1) s_carry += s_part[threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) rowptr[n] = s_carry;
 }
 
 __global__ void k_idx_fill(const int *__restrict__ idx, int E, int *__restrict__ cursor, int *__restrict__ perm) {
@@ -539,8 +513,7 @@ kpd_status build_src_csr(TrainCtx *T, const int *src, int E, int n_src, int *cur
         hipLaunchKernelGGL(k_idx_count, grid1(E), dim3(256), 0, T->st, src, E, cursor);
         KPD_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_idx_scan, dim3(1), dim3(1024), 0, T->st, cursor, n_src, out.rowptr, cursor);
-    KPD_LAUNCH_CHECK();
+    KPD_TRY(exclusive_scan(T->st, cursor, n_src, out.rowptr, cursor));          // the counts become each node's write cursor in place
     if (E > 0) {
         hipLaunchKernelGGL(k_idx_fill, grid1(E), dim3(256), 0, T->st, src, E, cursor, out.perm);
         KPD_LAUNCH_CHECK();

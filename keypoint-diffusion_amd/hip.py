@@ -252,6 +252,30 @@ def _dev_f32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.contiguous().float()
 
 
+def _offsets(t, name: str, count: str = 'B') -> int:
+    """`t` must be a contiguous 1-D int32 GPU tensor of `count` + 1 offsets; returns that count."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.numel() >= 1 and t.is_contiguous()):
+        raise KpdError(f'{name} must be a contiguous int32 GPU tensor of {count} + 1 offsets')
+    return t.numel() - 1
+
+
+def _per_entry(t, name: str, n: int, what: str, contiguous: bool = False) -> torch.Tensor:
+    """`t` must be a 1-D int32 GPU tensor with one entry per `what` (n of them); returns it contiguous.  `contiguous`: a strided
+    tensor is refused, not copied (the sites that always refused one)."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n and
+            (t.is_contiguous() or not contiguous)):
+        raise KpdError(f'{name} must be a {"contiguous " if contiguous else ""}1-D int32 GPU tensor with one entry per {what}')
+    return t.contiguous()
+
+
+def _mol_fields(where: str, mol: dict, names) -> None:
+    """The named entries of what `mol_perceive` returned must be contiguous int32 GPU tensors."""
+    for name in names:
+        t = mol.get(name)
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise KpdError(f'{where}: {name} must be a contiguous int32 GPU tensor')
+
+
 class PreparedBatch:
     """Device-side, int32, dst-sorted view of the static part of a batch (built once per batch)."""
 
@@ -855,11 +879,9 @@ def build_rec_graph(rec_x: torch.Tensor, rec_ptr: torch.Tensor, max_rec: int, r:
     (the edge count) — this is input-pipeline work, once per batch, not step-path work.  return_rowptr appends the CSR row
     pointers [n_rec + 1] of the list to the tuple."""
     rec_x = _dev_f32(rec_x, 'rec_x')
-    if not (rec_ptr.is_cuda and rec_ptr.dtype == torch.int32):
-        raise KpdError('rec_ptr must be an int32 GPU tensor')
-    n_rec, B = rec_x.shape[0], rec_ptr.numel() - 1
-    if res_idx is not None and not (res_idx.is_cuda and res_idx.dtype == torch.int32 and res_idx.numel() == n_rec):
-        raise KpdError('res_idx must be an int32 GPU tensor with one entry per receptor atom')
+    n_rec, B = rec_x.shape[0], _offsets(rec_ptr, 'rec_ptr')
+    if res_idx is not None:
+        res_idx = _per_entry(res_idx, 'res_idx', n_rec, 'receptor atom')
     dev = rec_x.device
     cap = n_rec * max(1, min(int(max_nn), int(max_rec) - 1))
     src = torch.empty(cap, dtype=torch.int32, device=dev)
@@ -869,9 +891,8 @@ def build_rec_graph(rec_x: torch.Tensor, rec_ptr: torch.Tensor, max_rec: int, r:
     counts = torch.empty(2, dtype=torch.int32, device=dev)
     same = torch.empty(cap, dtype=torch.uint8, device=dev) if res_idx is not None else None
     scratch = torch.empty(int(lib().kpd_rec_graph_scratch_bytes(n_rec, B)), dtype=torch.uint8, device=dev)
-    check(lib().kpd_build_rec_graph(_ptr(rec_x), _ptr(rec_ptr), B, n_rec, int(max_rec), float(r), int(max_nn),
-                                    _ptr(res_idx.contiguous()) if res_idx is not None else None, cap, _ptr(src), _ptr(dst),
-                                    _ptr(rowptr), _ptr(per_graph), _ptr(same), _ptr(counts), _ptr(scratch), _stream()))
+    check(lib().kpd_build_rec_graph(_ptr(rec_x), _ptr(rec_ptr), B, n_rec, int(max_rec), float(r), int(max_nn), _ptr(res_idx),
+                                    cap, _ptr(src), _ptr(dst), _ptr(rowptr), _ptr(per_graph), _ptr(same), _ptr(counts), _ptr(scratch), _stream()))
     E = int(counts[0].item())
     if E > cap:
         raise KpdError(f'rr graph: {E} edges exceed the capacity {cap} (internal sizing error)')
@@ -885,11 +906,8 @@ POCKET_MAX_LIG = 1024
 
 def _pocket_args(rec_x, rec_ptr, lig_x, lig_ptr, masks):
     rec_x, lig_x = _dev_f32(rec_x, 'rec_x'), _dev_f32(lig_x, 'lig_x')
-    for name, t in (('rec_ptr', rec_ptr), ('lig_ptr', lig_ptr)):
-        if not (t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.numel() >= 1 and t.is_contiguous()):
-            raise KpdError(f'{name} must be a contiguous int32 GPU tensor of B + 1 offsets')
-    n_rec, B = rec_x.shape[0], rec_ptr.numel() - 1
-    if rec_x.shape != (n_rec, 3) or lig_x.dim() != 2 or lig_x.shape[1] != 3 or lig_ptr.numel() != B + 1:
+    n_rec, B = rec_x.shape[0], _offsets(rec_ptr, 'rec_ptr')
+    if rec_x.shape != (n_rec, 3) or lig_x.dim() != 2 or lig_x.shape[1] != 3 or _offsets(lig_ptr, 'lig_ptr') != B:
         raise KpdError(f'rec_x {tuple(rec_x.shape)}, lig_x {tuple(lig_x.shape)}, {B + 1} / {lig_ptr.numel()} offsets')
     out = []
     for name, t in masks:
@@ -908,8 +926,7 @@ def pocket_select(rec_x: torch.Tensor, rec_ptr: torch.Tensor, res_idx: torch.Ten
     pocket_res, pocket_ptr (list of B + 1 offsets; the last is the size needed), status (list of B), in_box, pocket_mask
     (bool [n_rec]).  One host read (offsets + status together)."""
     rec_x, lig_x, n_rec, B, (probe, emit) = _pocket_args(rec_x, rec_ptr, lig_x, lig_ptr, (('probe', probe), ('emit', emit)))
-    if not (res_idx.is_cuda and res_idx.dtype == torch.int32 and res_idx.numel() == n_rec):
-        raise KpdError('res_idx must be an int32 GPU tensor with one entry per receptor atom')
+    res_idx = _per_entry(res_idx, 'res_idx', n_rec, 'receptor atom')
     dev = rec_x.device
     cap = n_rec if cap_rows is None else int(cap_rows)
     in_box = torch.empty(n_rec, dtype=torch.uint8, device=dev)
@@ -918,7 +935,7 @@ def pocket_select(rec_x: torch.Tensor, rec_ptr: torch.Tensor, res_idx: torch.Ten
     pocket_res = torch.empty(cap, dtype=torch.int32, device=dev)
     meta = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)         # pocket_ptr [B + 1], status [B]
     scratch = torch.empty(int(lib().kpd_pocket_scratch_bytes(n_rec, B)), dtype=torch.uint8, device=dev)
-    check(lib().kpd_pocket_select(_ptr(rec_x), _ptr(rec_ptr), _ptr(res_idx.contiguous()), _ptr(probe), _ptr(emit), n_rec, int(max_rec),
+    check(lib().kpd_pocket_select(_ptr(rec_x), _ptr(rec_ptr), _ptr(res_idx), _ptr(probe), _ptr(emit), n_rec, int(max_rec),
                                   _ptr(lig_x), _ptr(lig_ptr), int(lig_x.shape[0]), B, -1.0 if box_padding is None else float(box_padding),
                                   float(pocket_cutoff), cap, _ptr(in_box), _ptr(mask), _ptr(rows), _ptr(pocket_res), _ptr(meta),
                                   meta.data_ptr() + 4 * (B + 1), _ptr(scratch), _stream()))
@@ -967,9 +984,7 @@ def xyz_emit(pos: torch.Tensor, feat: torch.Tensor, lig_ptr: torch.Tensor, eleme
     Returns (element index per atom [N] int32 GPU tensor, text bytes, text_ptr list of B+1 offsets); the only host
     synchronisation is the copy of the finished text."""
     pos, feat = _dev_f32(pos, 'pos'), _dev_f32(feat, 'feat')
-    if not (lig_ptr.is_cuda and lig_ptr.dtype == torch.int32 and lig_ptr.dim() == 1 and lig_ptr.numel() >= 1):
-        raise KpdError('lig_ptr must be an int32 GPU tensor of B + 1 offsets')
-    N, B, F = pos.shape[0], lig_ptr.numel() - 1, feat.shape[1] if feat.dim() == 2 else -1
+    N, B, F = pos.shape[0], _offsets(lig_ptr, 'lig_ptr'), feat.shape[1] if feat.dim() == 2 else -1
     if pos.shape != (N, 3) or feat.shape[0] != N or F != len(elements):
         raise KpdError(f'xyz_emit: pos {tuple(pos.shape)}, feat {tuple(feat.shape)}, {len(elements)} element symbols')
     dev = pos.device
@@ -996,12 +1011,6 @@ SDF_NONFINITE, SDF_WIDE, SDF_NO_MOLECULE, SDF_CAPACITY = 1, 2, 4, 8         # st
 MOL_MAX_ATOMS = 256
 
 
-def _mol_ptr(lig_ptr: torch.Tensor) -> int:
-    if not (lig_ptr.is_cuda and lig_ptr.dtype == torch.int32 and lig_ptr.dim() == 1 and lig_ptr.numel() >= 1 and lig_ptr.is_contiguous()):
-        raise KpdError('lig_ptr must be a contiguous int32 GPU tensor of B + 1 offsets')
-    return lig_ptr.numel() - 1
-
-
 def mol_perceive(pos: torch.Tensor, feat: torch.Tensor, lig_ptr: torch.Tensor, z, allowed, cap_bonds: Optional[int] = None):
     """Bond graph, valences, fragments and validity counts of a batch of ligands on the GPU (kpd_mol_perceive; include/kpd.h
     states the rule).  pos [N,3], feat [N,F] fp32 GPU tensors, lig_ptr [B+1] int32 GPU tensor, z / allowed: the atomic number
@@ -1009,7 +1018,7 @@ def mol_perceive(pos: torch.Tensor, feat: torch.Tensor, lig_ptr: torch.Tensor, z
     3 N, which cannot overflow).  Returns a dict of device tensors: elem, valence, frag [N], bonds [cap_bonds,2], order
     [cap_bonds], bond_ptr [B+1], summary [B,4], status [B].  No host synchronisation."""
     pos, feat = _dev_f32(pos, 'pos'), _dev_f32(feat, 'feat')
-    B = _mol_ptr(lig_ptr)
+    B = _offsets(lig_ptr, 'lig_ptr')
     N, F = pos.shape[0], feat.shape[1] if feat.dim() == 2 else -1
     if pos.shape != (N, 3) or feat.shape[0] != N or F < 1 or len(z) != F or len(allowed) != F:
         raise KpdError(f'mol_perceive: pos {tuple(pos.shape)}, feat {tuple(feat.shape)}, {len(z)} atomic numbers, {len(allowed)} valences')
@@ -1032,12 +1041,9 @@ def sdf_emit(pos: torch.Tensor, lig_ptr: torch.Tensor, elements, mol: dict, larg
     ligand b's block is text[text_ptr[b]:text_ptr[b + 1]], empty when its status is not 0.  The only host synchronisation is
     the copy of the finished text."""
     pos = _dev_f32(pos, 'pos')
-    B = _mol_ptr(lig_ptr)
+    B = _offsets(lig_ptr, 'lig_ptr')
     N, F = pos.shape[0], len(elements)
-    for name in ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'):
-        t = mol[name]
-        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
-            raise KpdError(f'sdf_emit: {name} must be a contiguous int32 GPU tensor')
+    _mol_fields('sdf_emit', mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'))
     cap_bonds = mol['order'].numel()
     if (pos.shape != (N, 3) or F < 1 or mol['elem'].numel() != N or mol['frag'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or
             mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B):
@@ -1066,11 +1072,8 @@ def mol_keys(lig_ptr: torch.Tensor, z, mol: dict, largest_only: bool = True, wit
     states the rule).  `mol`: what `mol_perceive` returned, z: the atomic number of every feature class.  Returns a dict of
     device tensors: key [B] int64 (the uint64 bit pattern), fp [B, nbits/32] int32 (the uint32 bit pattern), status [B] (bit 0:
     no molecule, key 0 and an all-zero row) and, on request, atom_inv [N] int64.  No host synchronisation."""
-    B = _mol_ptr(lig_ptr)
-    for name in ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'):
-        t = mol.get(name)
-        if t is None or not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
-            raise KpdError(f'mol_keys: {name} must be a contiguous int32 GPU tensor')
+    B = _offsets(lig_ptr, 'lig_ptr')
+    _mol_fields('mol_keys', mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'))
     N, F, cap_bonds = mol['elem'].numel(), len(z), mol['order'].numel()
     if (F < 1 or mol['frag'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or mol['bond_ptr'].numel() != B + 1 or
             mol['status'].numel() != B):
@@ -1096,9 +1099,7 @@ def fp_diversity(fp: torch.Tensor, use: torch.Tensor, group_ptr: torch.Tensor):
     tensors (div_sum [G] float64, n_pairs [G] int64, status [G]: bit 0 = malformed segment).  No host synchronisation."""
     if not (fp.is_cuda and fp.dtype == torch.int32 and fp.dim() == 2 and fp.shape[1] >= 1 and fp.is_contiguous()):
         raise KpdError('fp_diversity: fp must be a contiguous int32 GPU tensor [B, W]')
-    if not (group_ptr.is_cuda and group_ptr.dtype == torch.int32 and group_ptr.dim() == 1 and group_ptr.numel() >= 1 and group_ptr.is_contiguous()):
-        raise KpdError('fp_diversity: group_ptr must be a contiguous int32 GPU tensor of G + 1 offsets')
-    G = group_ptr.numel() - 1
+    G = _offsets(group_ptr, 'fp_diversity: group_ptr', 'G')
     B, W = fp.shape
     if not (use.is_cuda and use.dtype in (torch.bool, torch.uint8) and use.shape == (B,)):
         raise KpdError(f'fp_diversity: use must be a bool or uint8 GPU tensor of {B} entries')
@@ -1141,19 +1142,15 @@ def relax(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_vdw: torch.Tensor, mo
     that size the kernel's LDS (a larger ligand is left out, a larger pocket is merely read from global memory).  Returns
     (pos_out [N,3] fp32, report [B,12] float64 with the columns RELAX_REPORT, status [B] int32).  No host synchronisation."""
     pos = _dev_f32(pos, 'pos')
-    B = _mol_ptr(lig_ptr)
-    for name in ('elem', 'bonds', 'bond_ptr', 'status'):
-        t = mol.get(name)
-        if t is None or not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
-            raise KpdError(f'relax: {name} must be a contiguous int32 GPU tensor')
-    for name, t in (('pocket_ptr', pocket_ptr), ('pocket_of', pocket_of)):
-        if not (t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()):
-            raise KpdError(f'relax: {name} must be a contiguous 1-D int32 GPU tensor')
+    B = _offsets(lig_ptr, 'lig_ptr')
+    _mol_fields('relax', mol, ('elem', 'bonds', 'bond_ptr', 'status'))
+    P = _offsets(pocket_ptr, 'relax: pocket_ptr', 'P')
+    pocket_of = _per_entry(pocket_of, 'relax: pocket_of', B, 'ligand', contiguous=True)
     lig_vdw, pocket_x, pocket_vdw = _dev_f32(lig_vdw, 'lig_vdw'), _dev_f32(pocket_x, 'pocket_x'), _dev_f32(pocket_vdw, 'pocket_vdw')
-    N, F, M, P = pos.shape[0], len(z), pocket_x.shape[0], pocket_ptr.numel() - 1
+    N, F, M = pos.shape[0], len(z), pocket_x.shape[0]
     cap_bonds = mol['bonds'].numel() // 2
     if (pos.shape != (N, 3) or F < 1 or lig_vdw.shape != (F, 2) or mol['elem'].numel() != N or mol['bond_ptr'].numel() != B + 1 or
-            mol['status'].numel() != B or pocket_x.shape != (M, 3) or pocket_vdw.shape != (M, 2) or P < 0 or pocket_of.numel() != B):
+            mol['status'].numel() != B or pocket_x.shape != (M, 3) or pocket_vdw.shape != (M, 2)):
         raise KpdError(f'relax: pos {tuple(pos.shape)}, {B} ligands, {F} classes, lig_vdw {tuple(lig_vdw.shape)}, pocket_x '
                        f'{tuple(pocket_x.shape)}, pocket_vdw {tuple(pocket_vdw.shape)}, {P} pockets, pocket_of {tuple(pocket_of.shape)} '
                        f'do not match each other or the perceived molecules')

@@ -77,3 +77,37 @@ def test_write_xyz_file_mirror_and_errors(tmp_path):
         kutils.sampled_ligands_xyz([coords], [torch.zeros(2, 10)], ELEMENTS)
     with pytest.raises(hip.KpdError):          # beyond the printable range
         kutils.sampled_ligands_xyz([torch.full((1, 3), 1e17).cuda()], [torch.zeros(1, 10).cuda()], ELEMENTS)
+
+
+@pytest.mark.gpu
+def test_xyz_emit_scratch_guard_bands_and_empty_batch():
+    """kpd_xyz_emit through the C ABI with guard bands on both sides of exactly kpd_xyz_scratch_bytes; no ligands at all."""
+    from keypoint_diffusion_amd import hip
+    from .util import guarded, intact
+    dev = torch.device('cuda')
+    g = torch.Generator().manual_seed(9)
+    sizes = [7, 1, 300, 12]
+    lig_pos, lig_feat = [torch.randn(n, 3, generator=g) * 25.0 for n in sizes], [torch.randn(n, 10, generator=g) for n in sizes]
+    ref = oemit.sampled_ligands_xyz(lig_pos, lig_feat, ELEMENTS)
+    pos, feat = torch.cat(lig_pos).to(dev), torch.cat(lig_feat).to(dev)
+    lig_ptr = torch.tensor([0] + list(np.cumsum(sizes)), dtype=torch.int32, device=dev)
+    N, B = sum(sizes), len(sizes)
+    L = hip.lib()
+    symbols = hip._packed_symbols(ELEMENTS, dev)
+    elem = torch.empty(N, dtype=torch.int32, device=dev)
+    cap = 72 * N + 16 * B + 16
+    text, p_text = guarded(cap, torch.uint8, dev, 0x5a)
+    text_ptr, status = torch.empty(B + 1, dtype=torch.int64, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    nb = int(L.kpd_xyz_scratch_bytes(N, B))
+    scratch, p_scr = guarded(nb, torch.uint8, dev, 0x5a)
+    hip.check(L.kpd_xyz_emit(pos.data_ptr(), feat.data_ptr(), lig_ptr.data_ptr(), N, B, 10, symbols.data_ptr(), elem.data_ptr(), p_text, cap,
+                             text_ptr.data_ptr(), status.data_ptr(), p_scr, None))
+    torch.cuda.synchronize()
+    assert intact(scratch, nb, 0x5a) and intact(text, cap, 0x5a) and int(status.item()) == 0
+    ptr = text_ptr.cpu().tolist()
+    raw = bytes(text[64:64 + ptr[-1]].cpu().numpy()).decode()
+    assert [raw[ptr[b]:ptr[b + 1]] for b in range(B)] == [t for _, t in ref]
+    assert elem.cpu().tolist() == [i for idxs, _ in ref for i in idxs]
+    # B = 0: the scan still runs and writes the one offset
+    _, text0, ptr0 = hip.xyz_emit(pos[:0], feat[:0], lig_ptr[:1], ELEMENTS)
+    assert text0 == b'' and ptr0 == [0]

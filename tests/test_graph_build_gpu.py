@@ -118,6 +118,31 @@ def test_rec_graph(cuda, name):
     assert len(hip.build_rec_graph(x, ptr, int(counts.max()), gc.REC_R, res, max_nn=gc.REC_CASES[name].max_nn)) == 4     # default return
 
 
+def test_rec_graph_scratch_guard_bands(cuda):
+    """kpd_build_rec_graph through the C ABI with guard bands on both sides of exactly kpd_rec_graph_scratch_bytes."""
+    from .util import guarded, intact
+    name = 'rec_sizes'                                   # pockets of 1, 2 and 2048 atoms
+    x, ptr, res = _rec_on_device(name, cuda)
+    _, counts, _ = gc.rec_case(name)
+    ref = gc.rec_reference(name)
+    n_rec, B, E = int(counts.sum()), counts.numel(), ref['src'].numel()
+    L = hip.lib()
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=cuda)
+    src, dst, rowptr, per_graph, cnt = i32(E), i32(E), i32(n_rec + 1), i32(B), i32(2)
+    same = torch.empty(E, dtype=torch.uint8, device=cuda)
+    nb = int(L.kpd_rec_graph_scratch_bytes(n_rec, B))
+    scratch, p_scr = guarded(nb, torch.uint8, cuda, 0x5a)
+    hip.check(L.kpd_build_rec_graph(x.data_ptr(), ptr.data_ptr(), B, n_rec, int(counts.max()), gc.REC_R, gc.REC_CASES[name].max_nn,
+                                    res.data_ptr(), E, src.data_ptr(), dst.data_ptr(), rowptr.data_ptr(), per_graph.data_ptr(),
+                                    same.data_ptr(), cnt.data_ptr(), p_scr, None))
+    torch.cuda.synchronize()
+    assert intact(scratch, nb, 0x5a), f'{name}: wrote outside the {nb} bytes of scratch'
+    assert cnt.tolist() == [E, 0]
+    _same_list(name, 'rr', (src.long().cpu(), dst.long().cpu()), (ref['src'], ref['dst']), og.counts_to_batch_idx(counts)[ref['dst']])
+    assert torch.equal(rowptr.long().cpu(), ref['rowptr']) and torch.equal(per_graph.long().cpu(), ref['per_graph'])
+    assert torch.equal(same.bool().cpu(), ref['same_res'])
+
+
 def test_rec_graph_refuses_past_the_limit(cuda):
     x, counts, _ = gc.rec_over_limit()
     with pytest.raises(hip.KpdError, match=r'radius graph: 2049 nodes per graph \(max 2048\)'):

@@ -9,6 +9,7 @@ import torch
 from keypoint_diffusion_amd import hip, molecule, utils
 from . import molecule_ref as R
 from .molecule_cases import ALLOWED, ELEMENTS, TEXTBOOK, TWO_ETHANOLS_CL, Z, one_hot
+from .util import guarded, intact
 
 pytestmark = pytest.mark.gpu
 PAD, CANARY = 64, 0x5A
@@ -48,13 +49,15 @@ def perceive_gpu(dev, pos, feat, ptr, z=Z, allowed=ALLOWED, cap_bonds=None):
     o = dict(elem=g.new(N), valence=g.new(N), frag=g.new(N), bonds=g.new(2 * cap), order=g.new(cap), bond_ptr=g.new(B + 1),
              summary=g.new(4 * B), status=g.new(B))
     L = hip.lib()
-    scratch = g.new(int(L.kpd_mol_scratch_bytes(N, B)), torch.uint8)
+    nb = int(L.kpd_mol_scratch_bytes(N, B))
+    scratch, p_scr = guarded(nb, torch.uint8, dev, CANARY)                 # the scratch has a band on either side
     zt, at = torch.tensor(z, dtype=torch.int32, device=dev), torch.tensor(allowed, dtype=torch.int32, device=dev)
     hip.check(L.kpd_mol_perceive(pos_d.data_ptr(), feat_d.data_ptr(), ptr_d.data_ptr(), N, B, F, zt.data_ptr(), at.data_ptr(), cap,
                                  *[o[k].data_ptr() for k in ('elem', 'valence', 'frag', 'bonds', 'order', 'bond_ptr', 'summary', 'status')],
-                                 scratch.data_ptr(), torch.cuda.current_stream().cuda_stream))
+                                 p_scr, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     g.check()
+    assert intact(scratch, nb, CANARY), f'kpd_mol_perceive wrote outside its {nb} bytes of scratch'
     sizes = dict(elem=N, valence=N, frag=N, bonds=2 * cap, order=cap, bond_ptr=B + 1, summary=4 * B, status=B)
     dev_t = {k: o[k][:n] for k, n in sizes.items()}
     dev_t['bonds'] = dev_t['bonds'].reshape(cap, 2)
@@ -71,14 +74,16 @@ def sdf_gpu(dev, t, elements=ELEMENTS, largest=False, capacity=None):
     g = Guarded(dev)
     text, tptr, status = g.new(cap, torch.uint8), g.new(B + 1, torch.int64), g.new(B)
     L = hip.lib()
-    scratch = g.new(int(L.kpd_sdf_scratch_bytes(N, B)), torch.uint8)
+    nb = int(L.kpd_sdf_scratch_bytes(N, B))
+    scratch, p_scr = guarded(nb, torch.uint8, dev, CANARY)
     sym = hip._packed_symbols(elements, dev, 3)
     hip.check(L.kpd_sdf_emit(t['pos'].data_ptr(), t['ptr'].data_ptr(), N, B, t['elem'].data_ptr(), len(elements), sym.data_ptr(),
                              t['frag'].data_ptr(), t['bonds'].data_ptr(), t['order'].data_ptr(), t['bond_ptr'].data_ptr(), t['cap'],
                              t['status'].data_ptr(), int(largest), text.data_ptr(), cap, tptr.data_ptr(), status.data_ptr(),
-                             scratch.data_ptr(), torch.cuda.current_stream().cuda_stream))
+                             p_scr, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     g.check()
+    assert intact(scratch, nb, CANARY), f'kpd_sdf_emit wrote outside its {nb} bytes of scratch'
     p = tptr[:B + 1].cpu().tolist()
     raw = bytes(text[:cap].cpu().numpy())
     st = status[:B].cpu().tolist()
@@ -212,8 +217,23 @@ def test_one_ligand_and_more_ligands_than_one_wave_of_workgroups(cuda):
     want, wst = R.sdf_batch(pos, ptr, ELEMENTS, ref)
     assert st == wst and blocks == want
     # no ligands at all
-    got, _ = perceive_gpu(cuda, np.zeros((0, 3)), np.zeros((0, 10)), [0])
+    got, t = perceive_gpu(cuda, np.zeros((0, 3)), np.zeros((0, 10)), [0])
     assert got['bond_ptr'].tolist() == [0]
+    assert sdf_gpu(cuda, t) == ([], [], [0])
+
+
+def test_scratch_stays_inside_the_size_asked_for(cuda):
+    """perceive_gpu / sdf_gpu put guard bands on both sides of exactly kpd_*_scratch_bytes and assert them untouched: a batch
+    whose every scratch buffer is used to its last element (3 n bond rows are reserved, the ligand counts end the region)."""
+    rng = np.random.default_rng(5)
+    pos, feat, ptr = concat([cloud(rng, n) for n in (17, 1, 64, 30)])
+    ref = R.perceive_batch(pos, feat, ptr, Z, ALLOWED)
+    got, t = perceive_gpu(cuda, pos, feat, ptr)
+    assert_equal(got, ref, 'guarded scratch')
+    for largest in (False, True):
+        blocks, st, _ = sdf_gpu(cuda, t, largest=largest)
+        want, wst = R.sdf_batch(pos, ptr, ELEMENTS, ref, largest_only=largest)
+        assert st == wst and blocks == want
 
 
 def test_bond_capacity_too_small_for_the_middle_ligand_only(cuda):

@@ -11,10 +11,10 @@ from keypoint_diffusion_amd import pocket as P
 
 from . import util
 from .test_pocket_config import load_cases, restate_points, restate_select
+from .util import GUARD, guarded, intact
 
 pytestmark = pytest.mark.gpu
 EMPTY, CAPACITY, BAD_RES, BAD_SEGMENT = 1, 2, 4, 8
-GUARD = 64
 
 
 @pytest.fixture(scope='module')
@@ -261,13 +261,78 @@ def test_small_large_and_degenerate_inputs(cuda):
     assert sel['status'] == [EMPTY]
 
 
-def guarded(n, dtype, dev, value):
-    buf = torch.full((n + 2 * GUARD,), value, dtype=dtype, device=dev)
-    return buf, buf.data_ptr() + GUARD * buf.element_size()
+# The offsets of both entry points come from the library's one scan kernel (csrc/scan_core.h): a single workgroup that takes
+# SCAN_T counts per chunk and carries the running sum from chunk to chunk.
+SCAN_T = 1024          # SCAN_THREADS of csrc/scan_core.h; test_scan_t_is_the_kernels_block_size holds the two together
 
 
-def intact(buf, n, value):
-    return bool((buf[:GUARD] == value).all()) and bool((buf[GUARD + n:] == value).all())
+def run_small(parts, dev):
+    """Both entry points on a list of (pos, res, lig) with run_one's parameters; everything on the host."""
+    cat = lambda k, dt: torch.cat([p[k] for p in parts]).to(dt).to(dev)
+    rc, lc = [p[0].shape[0] for p in parts], [p[2].shape[0] for p in parts]
+    pos, res, lig, rp, lp = cat(0, torch.float32), cat(1, torch.int32), cat(2, torch.float32), ptr32(rc, dev), ptr32(lc, dev)
+    ones = torch.ones(sum(rc), dtype=torch.bool, device=dev)
+    sel = hip.pocket_select(pos, rp, res, ones, ones, lig, lp, max(rc), 6.0, 4.0)
+    ip = hip.interface_points(pos, rp, sel['pocket_mask'], lig, lp, 5.0, 2.0)
+    return dict(rows=sel['rows'].long().cpu(), pocket_res=sel['pocket_res'].long().cpu(), pocket_ptr=sel['pocket_ptr'], status=sel['status'],
+                points=ip['points'].cpu(), ip_ptr=ip['ip_ptr'], n_cand=ip['n_cand'], ip_status=ip['status'], n_rec=sum(rc))
+
+
+@pytest.fixture(scope='module')
+def many_small(cuda):
+    """2 SCAN_T + 1 small complexes, a few without receptor atoms or with the ligand far away (zero counts mid-scan), and what
+    slices of at most 64 of them give, per complex with rows counted from the complex's first atom."""
+    g = torch.Generator().manual_seed(77)
+    n = 2 * SCAN_T + 1
+    nr, nl = torch.randint(8, 21, (n,), generator=g).tolist(), torch.randint(3, 7, (n,), generator=g).tolist()
+    parts = []
+    for i in range(n):
+        pos, res, lig = small_complex(0 if i % 97 == 40 else nr[i], nl[i], seed=1000 + i)
+        parts.append((pos, res, lig + 1000.0 if i % 101 == 5 else lig))
+    per = []
+    for lo in range(0, n, 64):
+        r = run_small(parts[lo:lo + 64], cuda)
+        off = 0
+        for k, p in enumerate(parts[lo:lo + 64]):
+            p0, p1, q0, q1 = r['pocket_ptr'][k], r['pocket_ptr'][k + 1], r['ip_ptr'][k], r['ip_ptr'][k + 1]
+            per.append(dict(rows=r['rows'][p0:p1] - off, pocket_res=r['pocket_res'][p0:p1], points=r['points'][q0:q1], n_cand=r['n_cand'][k],
+                            status=r['status'][k], ip_status=r['ip_status'][k]))
+            off += p[0].shape[0]
+    return parts, per
+
+
+@pytest.mark.parametrize('B', [1, SCAN_T - 1, SCAN_T, SCAN_T + 1, 2 * SCAN_T + 1])
+def test_offsets_across_the_chunks_of_the_scan(many_small, cuda, B):
+    parts, per = many_small
+    got = run_small(parts[:B], cuda)
+    first = [0] + list(np.cumsum([p[0].shape[0] for p in parts[:B]]))
+    want = per[:B]
+    assert got['pocket_ptr'] == [0] + list(np.cumsum([w['rows'].numel() for w in want]))          # offsets shifted on the host
+    assert got['ip_ptr'] == [0] + list(np.cumsum([w['points'].shape[0] for w in want]))
+    assert torch.equal(got['rows'], torch.cat([w['rows'] + first[k] for k, w in enumerate(want)]))
+    assert torch.equal(got['pocket_res'], torch.cat([w['pocket_res'] for w in want]))
+    assert torch.equal(got['points'], torch.cat([w['points'] for w in want]))
+    for k in ('n_cand', 'status', 'ip_status'):
+        assert got[k] == [w[k] for w in want], k
+    if B > 1:                                                   # the batch has complexes with nothing selected, and ones with something
+        assert 0 < sum(st == EMPTY for st in got['status']) < B and got['pocket_ptr'][-1] > 0 and got['ip_ptr'][-1] > 0
+
+
+def test_scan_t_is_the_kernels_block_size():
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(hip.__file__), 'csrc', 'scan_core.h')).read()
+    assert int(re.search(r'constexpr int SCAN_THREADS = (\d+);', src).group(1)) == SCAN_T
+    assert 2 * SCAN_T < 1040 + 1000 + 30 < 3 * SCAN_T       # the source-CSR batch of test_recenc_train_gpu.py: three chunks, the last partial
+
+
+def test_no_complexes_at_all(cuda):
+    none = run_small([small_complex(0, 0, seed=1)], cuda)       # one complex without atoms: offsets [0, 0]
+    assert none['pocket_ptr'] == [0, 0] and none['ip_ptr'] == [0, 0]
+    z3, zi, zb, p0 = torch.zeros(0, 3, device=cuda), torch.zeros(0, dtype=torch.int32, device=cuda), torch.zeros(0, dtype=torch.bool, device=cuda), ptr32([], cuda)
+    sel = hip.pocket_select(z3, p0, zi, zb, zb, z3, p0, 0, 6.0, 4.0)
+    ip = hip.interface_points(z3, p0, zb, z3, p0, 5.0, 2.0)
+    assert sel['pocket_ptr'] == [0] and sel['status'] == [] and ip['ip_ptr'] == [0] and ip['n_cand'] == [] and ip['status'] == []
 
 
 def test_capacities_one_too_small(cases, cuda):

@@ -29,7 +29,10 @@ def _weights(n_kp, S, seed, V=16):
                                        (dict(RECENC_CFGS['recenc_norm10'], vector_size=8), [33, 21]),
                                        (dict(RECENC_CFGS['recenc_mean'], vector_size=5), [33, 21]),
                                        # a pocket above 256 atoms: the attention kernels stride a graph's atoms 256 at a time
-                                       (RECENC_CFGS['recenc_norm10'], [300, 21])])
+                                       (RECENC_CFGS['recenc_norm10'], [300, 21]),
+                                       # 2070 receptor atoms: the source-CSR scan (csrc/scan_core.h, 1024 entries per chunk) carries over
+                                       # two chunk boundaries and ends in a partial chunk
+                                       (RECENC_CFGS['recenc_norm10'], [1040, 1000, 30])])
 def test_encoder_gradients_match_oracle_autograd(cuda, cfg, n_rec):
     cfg = dict(cfg, dropout=0.0)
     kw = dict(cfg, graph_cutoffs=CUT)

@@ -121,3 +121,16 @@ def run_threaded_world(world: int, fn, timeout: float = 600.0):
     if errors:
         raise errors[0][1]
     return results
+
+
+GUARD = 64
+
+
+def guarded(n, dtype, dev, value):
+    """A buffer of n elements between two bands of GUARD elements, all set to `value`: (the whole buffer, the address of element 0)."""
+    buf = torch.full((n + 2 * GUARD,), value, dtype=dtype, device=dev)
+    return buf, buf.data_ptr() + GUARD * buf.element_size()
+
+
+def intact(buf, n, value):
+    return bool((buf[:GUARD] == value).all()) and bool((buf[GUARD + n:] == value).all())
