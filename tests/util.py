@@ -70,16 +70,63 @@ def elementwise_excess(a: torch.Tensor, b: torch.Tensor, rtol: float = 1e-4, ato
     return float(((a - b).abs() / (atol + rtol * b.abs())).max())
 
 
-def assert_parity(got: torch.Tensor, ref: torch.Tensor, counts=None, tol: float = 1e-4, what: str = '', atol_rel: float = 1e-6):
+def assert_parity(got: torch.Tensor, ref: torch.Tensor, counts=None, tol: float = 1e-4, what: str = '', atol_rel: float = 1e-6,
+                  max_excess: float = 1.0):
     """The three parity measures of the denoiser tests: whole-tensor relative error (BASELINE.json's '1e-4 rel fp32'),
-    the same per complex, and an elementwise allclose(rtol = tol, atol = atol_rel * max |ref|)."""
+    the same per complex, and an elementwise allclose(rtol = tol, atol = atol_rel * max |ref|).  `max_excess` above 1 loosens the
+    elementwise measure alone, for a case whose caller has measured that fp32 itself needs it."""
     e = rel_err(got, ref)
     assert e < tol, f'{what}: rel err {e:.3e} >= {tol}'
     if counts is not None:
         pc = per_complex_rel_err(got, ref, counts)
         assert pc < tol, f'{what}: per-complex rel err {pc:.3e} >= {tol}'
     ex = elementwise_excess(got, ref, rtol=tol, atol_rel=atol_rel)
-    assert ex <= 1.0, f'{what}: allclose(rtol={tol}, atol={atol_rel} max|ref|) violated by a factor {ex:.2f}'
+    assert ex <= max_excess, f'{what}: allclose(rtol={tol}, atol={atol_rel} max|ref|) violated by a factor {ex:.2f}'
+
+
+def assert_param_grads(model, ref_grads: dict, tol: float, min_checked: int = 10, tol_of: dict = None):
+    """Every parameter gradient of `model` against `ref_grads` (name -> float64 gradient or None, from autograd through an oracle):
+    max |g - ref| <= tol * max |ref| per tensor (`tol_of`: name -> another bound for single tensors).  A parameter the oracle never
+    applies (gradient None or all zero) must have none here either; a lone bias is judged on the scale of its weight's gradient (a
+    cancelling sum over all edges)."""
+    worst, checked = [], 0
+    for n, p in model.named_parameters():
+        r = ref_grads[n]
+        if r is None or float(r.abs().max()) < 1e-10:                # fc_dst: built, never applied (:190-191); a saturated tanh head
+            assert p.grad is None or float(p.grad.abs().max()) <= 1e-9, n
+            continue
+        assert p.grad is not None, n
+        scale = r.abs().max().item()
+        if r.numel() == 1 and n.endswith('.bias'):                    # lone attention bias: a cancelling sum over all edges
+            scale = max(scale, ref_grads[n[:-4] + 'weight'].abs().max().item())
+        worst.append(((p.grad.cpu().double() - r).abs().max().item() / scale / (tol_of or {}).get(n, tol), n))
+        checked += 1
+    worst.sort(reverse=True)
+    assert checked > min_checked and worst[0][0] < 1.0, [(e * (tol_of or {}).get(n, tol), n) for e, n in worst[:8]]
+
+
+def _pair_dist(x, y, n_x, n_y):
+    """float64 distance matrices [n_y[b], n_x[b]] of every complex."""
+    x, y, ox, oy = x.detach().double(), y.detach().double(), 0, 0
+    for nx, ny in zip([int(c) for c in n_x], [int(c) for c in n_y]):
+        yield torch.cdist(y[oy:oy + ny], x[ox:ox + nx])
+        ox, oy = ox + nx, oy + ny
+
+
+def knn_rel_gap(x, y, k, n_x, n_y) -> float:
+    """How far a kNN edge list (k nearest x of every y, nearest first) is from changing: the smallest (d_j+1 - d_j) / d_j+1 over
+    consecutive entries of each query's k + 1 smallest distances -- membership (k-th against (k+1)-th) and order alike."""
+    gap = float('inf')
+    for d in _pair_dist(x, y, n_x, n_y):
+        d = torch.sort(d, dim=1).values[:, :k + 1]
+        if d.shape[1] > 1:
+            gap = min(gap, float(((d[:, 1:] - d[:, :-1]) / d[:, 1:].clamp(min=1e-30)).min()))
+    return gap
+
+
+def radius_rel_gap(x, y, r, n_x, n_y) -> float:
+    """How far a radius edge list (x within r of y) is from changing: the smallest |d - r| / r over all pairs of a complex."""
+    return min(float(((d - r).abs() / r).min()) for d in _pair_dist(x, y, n_x, n_y))
 
 
 def run_threaded_world(world: int, fn, timeout: float = 600.0):
