@@ -883,6 +883,83 @@ kpd_status kpd_relax(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, 
                      const int32_t *pocket_ptr, int32_t n_pocket, int32_t P, int32_t max_pocket, const int32_t *pocket_of,
                      const kpd_relax_params *params, float *pos_out, double *report, int32_t *status, void *stream);
 
+/* Scores of sampled ligands in their rigid pockets (csrc/vina.hip).  Stands where upstream hands pocket_minimized_ligands.sdf to
+ * gnina (analysis/docking/gen_docking_cmds.py), which docks or minimises under the AutoDock Vina scoring function.  This is the
+ * Vina FUNCTIONAL FORM: five pair terms over ligand x pocket heavy atoms, the sum divided by 1 + w_rot N_rot, with its analytic
+ * gradient.  The typing cannot be Vina's own (Vina reads hydrogens and AutoDock atom types from PDBQT; ligands and pockets here
+ * carry heavy atoms and element classes only), so THIS COMMENT IS THE DEFINITION.  THE SCORES ARE NOT gnina's OR Vina's NUMBERS:
+ * they rank samples scored by this function against each other.  Out of scope: no torsional or rigid-body minimisation under
+ * this function (gnina's --minimize; the gradient delivered here is what it would be built on), no search and no docking, no
+ * intramolecular term, no hydrogens, no aromaticity.
+ *
+ * Ligand and pocket are in one frame, as for kpd_relax.  All arithmetic is fp64 on values read from the fp32 inputs.
+ * Distances: d2(i,j) by the recipe of kpd_mol_perceive and kpd_pocket_select (differences of the fp32 coordinates in fp64, each
+ *   product and sum rounded once, (dx^2 + dy^2) + dz^2, no fused multiply-add).  A pair takes part iff d2 < r_c * r_c; then
+ *   r = sqrt(d2) and the surface distance is d = (r - R_i) - R_j, in that order, R the fp64 values of the fp32 radii.
+ * Types: three flags per atom, H = 1 (hydrophobic), D = 2 (hydrogen-bond donor), A = 4 (acceptor), from the atomic number Z, the
+ *   heavy degree deg and the neighbours.  A neighbour with Z = 1 is ignored throughout (it neither counts in deg nor matters below).
+ *   Ligand: neighbours and orders are those of kpd_mol_perceive (bond_ij, bond_order).  Pocket: a pair i < j of one pocket is a
+ *   neighbour pair iff it passes step 1 of the bond rule above (d2 > 0.16 and the order-1 test with m = 45, radii table above);
+ *   its order comes from step 3; there is no degree pruning and no valence repair; an atomic number outside the table has no
+ *   neighbours.
+ *     Z = 6 (C):                   H iff no neighbour has Z outside {1, 6}, else 0
+ *     Z = 9, 17, 35, 53:           H
+ *     Z = 7 (N):                   D iff deg <= 2 and not (deg == 1 and that bond has order 3); A iff not D and deg <= 2; else 0
+ *     Z = 8 (O):                   A always; also D iff deg == 0, or deg == 1 and that bond has order 1
+ *     Z = 12, 20, 25 .. 30 (metals): D
+ *     anything else:               0
+ *   An atom with Z = 1, or whose radius is not > 0, takes no part in any term; its reported type is -1.
+ *   Limits: an aromatic or imine N of degree 2 counts as a donor (no aromaticity, no hydrogens), so a histidine's two ring N
+ *   are both donors; the O rule leans on the length classes (C=O 1.23 A is a double, C-O 1.36 .. 1.43 A a single).  The caller
+ *   may override any atom's flags (lig_type_in, and whatever it writes into pocket_type; bits above 4 are ignored).
+ * Rotors: N_rot = the number of ligand bonds of order 1 with both ends of heavy degree >= 2 that are in no ring (a bond is in a
+ *   ring iff its ends stay connected when it is removed).  Limits: an amide C-N counts; rotors that would move only hydrogens
+ *   (hydroxyl, amine) do not count, where Vina counts them half.
+ * Pair terms, for u = d / 0.5 and v = (d - 3) / 2:
+ *     gauss1 = exp(-(u u)), gauss2 = exp(-(v v)), repulsion = d < 0 ? d d : 0,
+ *     hydrophobic, only when both atoms carry H: 1 for d < 0.5, 1.5 - d for d < 1.5, else 0,
+ *     hbond, only when one atom carries D and the other A (either way round, once per pair): 1 for d < -0.7, d / -0.7 for d < 0,
+ *     else 0.
+ *   inter = sum over the five terms of w_term * (sum over the pairs of term); score = inter / (1 + w_rot N_rot).
+ *   kpd_vina_defaults: w_gauss1 -0.035579, w_gauss2 -0.005156, w_repulsion 0.840245, w_hydrophobic -0.035069, w_hbond -0.587439,
+ *   w_rot 0.05846, r_c 8.  RECALLED, NOT CHECKED AGAINST TROTT & OLSON 2010 OR VINA'S SOURCE: nothing may rely on these being
+ *   Vina's values.  The radii come from the caller (lig_radius [F] per ligand class, pocket_radius [n_pocket]).
+ *   grad[i] = (1 / (1 + w_rot N_rot)) sum_j (sum over the terms of w_term dterm/dd) (x_i - x_j) / r; a pair with r < 1e-6
+ *   contributes energy and no force.  atom_score[i] = the un-normalised weighted pair sum of ligand atom i.
+ *   Every sum is reduced in a fixed order that depends on the ligand and its pocket only.
+ *
+ * kpd_vina_pocket_types: pocket_x [n_pocket,3], pocket_z [n_pocket] (atomic numbers), pocket_ptr [P+1]; all device pointers.
+ *   Out (device): pocket_type [n_pocket] (flags, or -1; -1 also for the atoms outside every well-formed segment), status [P]:
+ *   bit 0 = malformed segment (not 0 <= pocket_ptr[q] <= pocket_ptr[q+1] <= n_pocket; none of its atoms is typed), bit 1 = a
+ *   non-finite coordinate (that atom has no neighbours and type -1).  One launch (and a memset) whatever P is; one thread per
+ *   atom, the atoms of its pocket tiled through LDS: quadratic per pocket, which is right for pockets of hundreds of atoms.
+ *   Done once per pocket set and reused for raw and relaxed poses.
+ *
+ * kpd_vina_score: pos, lig_ptr, elem, z, bond_ij, bond_ptr, mol_status, pocket_x, pocket_ptr, pocket_of, max_atoms and
+ *   max_pocket as for kpd_relax; bond_order [cap_bonds] as kpd_mol_perceive wrote it; lig_radius [F]; lig_type_in NULL, or
+ *   [n_atoms] whose entries >= 0 replace the perceived flags; pocket_radius, pocket_type [n_pocket]; params: NULL for
+ *   kpd_vina_defaults.  Out (device): report [B,8] fp64 = {score, inter, weighted gauss1, gauss2, repulsion, hydrophobic, hbond,
+ *   N_rot}; grad [n_atoms,3] fp64 or NULL; atom_score [n_atoms] fp64 or NULL; lig_type [n_atoms] or NULL; status [B]:
+ *   bit 0 = no molecule (the conditions of kpd_relax, or a bond order outside 1 .. 3), bit 1 = a non-finite coordinate or radius
+ *   in the ligand or its pocket, a pocket_of outside [-1, P) or a malformed pocket segment, bit 2 (informational) = some atom of
+ *   the ligand or of its pocket took no part (type -1, or a radius that is not > 0).  With bit 0 or 1 the ligand's report, grad
+ *   and atom_score rows are zeros and its types are -1 (rows of a malformed ligand segment are not written); nothing is read or
+ *   written out of bounds.  pocket_of = -1: all terms are 0 and N_rot is still reported.  Inputs are never written.
+ *   One workgroup per ligand, one launch whatever B is; no scratch, no host synchronisation, no atomics on floats; a ligand's
+ *   results are bitwise independent of the rest of the batch, of max_atoms / max_pocket, and of the repeat. */
+typedef struct kpd_vina_params {
+    double w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond, w_rot, r_c;
+} kpd_vina_params;
+void kpd_vina_defaults(kpd_vina_params *params);
+kpd_status kpd_vina_pocket_types(const float *pocket_x, const int32_t *pocket_z, const int32_t *pocket_ptr, int32_t n_pocket, int32_t P,
+                                 int32_t *pocket_type, int32_t *status, void *stream);
+kpd_status kpd_vina_score(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, int32_t max_atoms, const int32_t *elem,
+                          int32_t F, const int32_t *z, const float *lig_radius, const int32_t *bond_ij, const int32_t *bond_order,
+                          const int32_t *bond_ptr, int32_t cap_bonds, const int32_t *mol_status, const int32_t *lig_type_in,
+                          const float *pocket_x, const float *pocket_radius, const int32_t *pocket_type, const int32_t *pocket_ptr,
+                          int32_t n_pocket, int32_t P, int32_t max_pocket, const int32_t *pocket_of, const kpd_vina_params *params,
+                          double *report, double *grad, double *atom_score, int32_t *lig_type, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

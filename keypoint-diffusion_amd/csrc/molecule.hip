@@ -18,20 +18,6 @@ namespace kpd {
 
 enum : int { SDF_NONFINITE = 1, SDF_WIDE = 2, SDF_NO_MOLECULE = 4, SDF_CAPACITY = 8 };
 
-// fp64 sum of squares of the exact differences; every product and sum is rounded on its own (no fused multiply-add)
-__device__ __forceinline__ double mol_d2(const float *p, int i, int j) {
-    const double dx = (double)p[i * 3] - (double)p[j * 3], dy = (double)p[i * 3 + 1] - (double)p[j * 3 + 1],
-                 dz = (double)p[i * 3 + 2] - (double)p[j * 3 + 2];
-    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-}
-
-// d2 <= ((r_k(i) + r_k(j) + margin) pm)^2; false if either radius is 0
-__device__ __forceinline__ bool within(double d2, unsigned ri, unsigned rj, int margin) {
-    if (!ri || !rj) return false;
-    const int T = (int)ri + (int)rj + margin;
-    return d2 <= (double)(T * T) * 1e-4;
-}
-
 __device__ __forceinline__ int wave_exclusive(int v, int lane, int &total) {
     int s = v;
 #pragma unroll

@@ -1,6 +1,6 @@
 // What the molecule kernels share (molecule.hip: perception and SDF text; molset.hip: keys, fingerprints, diversity): the size
 // limits of one ligand, the element table, the status bits of kpd_mol_perceive and the segment check.
-// relax.hip reads the same table for its rest lengths.
+// relax.hip reads the same table for its rest lengths; vina.hip types pocket atoms by the same distance recipe and step-1 / step-3 tests.
 #pragma once
 #include "common.h"
 
@@ -33,6 +33,22 @@ __device__ __forceinline__ unsigned element_row(int z) {
     default: return 0u;
     }
 #undef KPD_EL
+}
+
+// fp64 sum of squares of the exact differences; every product and sum is rounded on its own (no fused multiply-add)
+__device__ __forceinline__ double sum_sq(double dx, double dy, double dz) {
+    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+}
+__device__ __forceinline__ double mol_d2(const float *p, int i, int j) {
+    return sum_sq((double)p[i * 3] - (double)p[j * 3], (double)p[i * 3 + 1] - (double)p[j * 3 + 1],
+                  (double)p[i * 3 + 2] - (double)p[j * 3 + 2]);
+}
+
+// d2 <= ((r_k(i) + r_k(j) + margin) pm)^2; false if either radius is 0
+__device__ __forceinline__ bool within(double d2, unsigned ri, unsigned rj, int margin) {
+    if (!ri || !rj) return false;
+    const int T = (int)ri + (int)rj + margin;
+    return d2 <= (double)(T * T) * 1e-4;
 }
 
 __device__ __forceinline__ bool mol_segment(const int *__restrict__ ptr, int b, int n, int &a0, int &a1) {

@@ -1,0 +1,527 @@
+// Scores of sampled ligands in their rigid pockets on the device: the AutoDock Vina FUNCTIONAL FORM (five pair terms over ligand x
+// pocket heavy atoms, divided by 1 + w_rot N_rot), where upstream hands pocket_minimized_ligands.sdf to gnina
+// (analysis/docking: gen_docking_cmds.py).  Vina's own typing reads hydrogens and AutoDock atom types from PDBQT; ligands and
+// pockets here carry heavy atoms and element classes, so include/kpd.h DEFINES the typing (three flags per atom from the element,
+// the heavy degree and the neighbours' elements and length-class bond orders) and the rotor count.  NOT gnina's numbers: the
+// scores rank samples scored here against each other.  No search, no minimisation under this function, no intramolecular term.
+// k_vina_pocket_types: one thread per pocket atom, the atoms of its pocket tiled through LDS 256 at a time (quadratic per pocket,
+// which is right for pockets of hundreds of atoms); done once per pocket set.
+// k_vina_score: one workgroup (4 waves) per ligand and ONE launch: the ligand's bond graph as a bit matrix in LDS, typing, the
+// rotor count (one thread per bond walks the graph without it), then the pair sums: an atom's five terms and its gradient are
+// summed by one wavefront whose lanes stride the pocket atoms (the first of them staged in LDS, the rest read from global memory
+// with the same bits) and meet in a butterfly.  Nothing is shared between ligands, no atomics on floats, no host synchronisation:
+// a ligand's result is bitwise independent of the batch, of what was staged, and of the repeat.
+#include <algorithm>
+
+#include "common.h"
+#include "molecule_core.h"
+
+namespace kpd {
+
+constexpr int VN_T = 256;                 // threads of a workgroup
+constexpr int VN_DEG = 6;                 // neighbours of one atom (the largest valence cap of the bond rule)
+constexpr int VN_LDS = 64 * 1024 - 512;   // dynamic LDS of a workgroup: what needs no opt-in, less the static bytes of the votes
+constexpr int VN_POCKET_ROW = 20;         // staged pocket atom: 3 floats, radius, type
+
+enum : int { VN_NO_MOLECULE = 1, VN_BAD_INPUT = 2, VN_ATOM_OUT = 4 };
+enum : int { VN_H = 1, VN_D = 2, VN_A = 4 };
+enum : unsigned { VN_HETERO = 1u };       // neighbour flags: bit 0 = a neighbour that is neither C nor H, bit k = a bond of order k
+
+struct VinaP {
+    double w[5], w_rot, rc2;
+};
+
+// byte offsets of the dynamic LDS of a workgroup for ligands of at most nm atoms and `stage` staged pocket atoms
+struct VinaLayout {
+    size_t part, red, x0, rad, zat, typ, cnt, flg, adj, px, prad, ptyp, bytes;
+    int W;
+};
+
+__host__ __device__ inline VinaLayout vina_layout(int nm, int stage) {
+    VinaLayout L;
+    L.W = (nm + 31) / 32;
+    size_t o = 0;
+    auto take = [&o](size_t bytes) {
+        const size_t at = o;
+        o += (bytes + 15) & ~(size_t)15;
+        return at;
+    };
+    L.part = take((size_t)nm * 5 * 8);
+    L.red = take(8 * 8);
+    L.x0 = take((size_t)nm * 3 * 4);
+    L.rad = take((size_t)nm * 4);
+    L.zat = take((size_t)nm * 4);
+    L.typ = take((size_t)nm * 4);
+    L.cnt = take((size_t)nm * 4);
+    L.flg = take((size_t)nm * 4);
+    L.adj = take((size_t)nm * L.W * 4);
+    L.px = take((size_t)stage * 3 * 4);
+    L.prad = take((size_t)stage * 4);
+    L.ptyp = take((size_t)stage * 4);
+    L.bytes = o;
+    return L;
+}
+
+__device__ __forceinline__ double vina_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__device__ __forceinline__ bool vina_finite(float v) { return fabsf(v) < __builtin_inff(); }
+
+// the flags of include/kpd.h from the atomic number, the heavy degree and the neighbour flags
+__device__ __forceinline__ int vina_flags(int z, int deg, unsigned nf) {
+    switch (z) {
+    case 6: return (nf & VN_HETERO) ? 0 : VN_H;
+    case 9:
+    case 17:
+    case 35:
+    case 53: return VN_H;
+    case 7:
+        if (deg > 2) return 0;
+        return (deg == 1 && (nf & (1u << 3))) ? VN_A : VN_D;
+    case 8: return VN_A | ((deg == 0 || (deg == 1 && (nf & (1u << 1)))) ? VN_D : 0);
+    case 12:
+    case 20:
+    case 25:
+    case 26:
+    case 27:
+    case 28:
+    case 29:
+    case 30: return VN_D;
+    default: return 0;
+    }
+}
+
+// ---- pocket typing: block (q, t) types the atoms [256 t, 256 t + 256) of pocket q ------------------------------------------
+__global__ void __launch_bounds__(VN_T)
+k_vina_pocket_types(const float *__restrict__ pocket_x, const int *__restrict__ pocket_z, const int *__restrict__ pocket_ptr, int n_pocket,
+                    int tiles, int *__restrict__ pocket_type, int *__restrict__ status) {
+    __shared__ float sx[VN_T * 3];
+    __shared__ unsigned srow[VN_T];      // element_row, radii zeroed for an atom that has no neighbours
+    __shared__ int sz[VN_T];
+    const int q = blockIdx.x / tiles, t = blockIdx.x % tiles, tid = threadIdx.x;
+    const int q0 = pocket_ptr[q], q1 = pocket_ptr[q + 1];
+    if (q0 < 0 || q1 < q0 || q1 > n_pocket) {        // malformed: no atom is touched
+        if (t == 0 && tid == 0) status[q] = 1;
+        return;
+    }
+    const int np = q1 - q0;
+    if (t && t * VN_T >= np) return;
+    const int i = t * VN_T + tid;
+    float xi = 0.f, yi = 0.f, zi = 0.f;
+    unsigned ri = 0;
+    int Zi = 0;
+    bool fin_i = false;
+    if (i < np) {
+        const float *r = pocket_x + (size_t)(q0 + i) * 3;
+        xi = r[0];
+        yi = r[1];
+        zi = r[2];
+        Zi = pocket_z[q0 + i];
+        fin_i = vina_finite(xi) && vina_finite(yi) && vina_finite(zi);
+        ri = fin_i ? element_row(Zi) : 0u;
+    }
+    int deg = 0, bad = 0;
+    unsigned nf = 0;
+    for (int j0 = 0; j0 < np; j0 += VN_T) {
+        __syncthreads();
+        const int jl = j0 + tid;
+        if (jl < np) {
+            const float *r = pocket_x + (size_t)(q0 + jl) * 3;
+            const float x = r[0], y = r[1], z = r[2];
+            const int Z = pocket_z[q0 + jl];
+            const bool fin = vina_finite(x) && vina_finite(y) && vina_finite(z);
+            if (!fin) bad = 1;
+            sx[3 * tid] = x;
+            sx[3 * tid + 1] = y;
+            sx[3 * tid + 2] = z;
+            srow[tid] = fin ? element_row(Z) : 0u;
+            sz[tid] = Z;
+        }
+        __syncthreads();
+        if (!(ri & 0xffu)) continue;                 // block-uniform barriers stay above; this atom has no neighbours
+        const int cnt = min(VN_T, np - j0);
+        for (int j = 0; j < cnt; ++j) {
+            if (j0 + j == i) continue;
+            const unsigned rj = srow[j];
+            const double d2 = sum_sq((double)xi - (double)sx[3 * j], (double)yi - (double)sx[3 * j + 1], (double)zi - (double)sx[3 * j + 2]);
+            if (!(d2 > 0.16 && within(d2, ri & 0xffu, rj & 0xffu, 45))) continue;
+            const int Zj = sz[j];
+            if (Zj == 1) continue;                   // hydrogens are no neighbours for the typing
+            ++deg;
+            if (Zj != 6) nf |= VN_HETERO;
+            const int order = within(d2, (ri >> 16) & 0xffu, (rj >> 16) & 0xffu, 3) ? 3 : within(d2, (ri >> 8) & 0xffu, (rj >> 8) & 0xffu, 5) ? 2 : 1;
+            nf |= 1u << order;
+        }
+    }
+    if (i < np) pocket_type[q0 + i] = (!fin_i || Zi == 1) ? -1 : vina_flags(Zi, deg, nf);
+    const int any_bad = __syncthreads_or(bad);
+    if (t == 0 && tid == 0) status[q] = any_bad ? 2 : 0;      // the vote is a predicate, not the OR of the values
+}
+
+// Is bond (i, j) in a ring: does j stay reachable from i without it?  visited / frontier are bit sets in registers.
+__device__ bool vina_in_ring(const unsigned *adj, int W, int i, int j) {
+    unsigned vis[MOL_W], fr[MOL_W];
+#pragma unroll
+    for (int w = 0; w < MOL_W; ++w) vis[w] = fr[w] = (w == (i >> 5)) ? 1u << (i & 31) : 0u;
+    const int jw = j >> 5;
+    const unsigned jb = 1u << (j & 31);
+    for (;;) {
+        int a = -1;
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w)
+            if (a < 0 && fr[w]) {
+                a = 32 * w + __ffs(fr[w]) - 1;
+                fr[w] &= fr[w] - 1;
+            }
+        if (a < 0) return false;
+        const unsigned *row = adj + a * W;
+        bool found = false;
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w) {
+            if (w >= W) continue;
+            unsigned r = row[w];
+            if (a == i && w == jw) r &= ~jb;         // the bond itself
+            const unsigned nw = r & ~vis[w];
+            vis[w] |= nw;
+            fr[w] |= nw;
+            if (w == jw && (vis[w] & jb)) found = true;
+        }
+        if (found) return true;
+    }
+}
+
+// the five terms of one pair at surface distance d (added to t) and dd = sum over the terms of w_term * dterm/dd
+__device__ __forceinline__ double vina_pair(double d, int ti, int tj, const VinaP &P, double (&t)[5]) {
+    const double u = d / 0.5, v = (d - 3.0) / 2.0;
+    const double g1 = exp(-(u * u)), g2 = exp(-(v * v));
+    t[0] += g1;
+    t[1] += g2;
+    double dd = P.w[0] * (-4.0 * u * g1) + P.w[1] * (-v * g2);
+    if (d < 0.0) {
+        t[2] += d * d;
+        dd += P.w[2] * (2.0 * d);
+    }
+    if (ti & tj & VN_H) {
+        if (d < 0.5) {
+            t[3] += 1.0;
+        } else if (d < 1.5) {
+            t[3] += 1.5 - d;
+            dd -= P.w[3];
+        }
+    }
+    if (((ti & VN_D) && (tj & VN_A)) || ((ti & VN_A) && (tj & VN_D))) {
+        if (d < -0.7) {
+            t[4] += 1.0;
+        } else if (d < 0.0) {
+            t[4] += d / -0.7;
+            dd += P.w[4] / -0.7;
+        }
+    }
+    return dd;
+}
+
+__global__ void __launch_bounds__(VN_T)
+k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_atoms, int nm, const int *__restrict__ elem, int F,
+             const int *__restrict__ zs, const float *__restrict__ lig_radius, const int *__restrict__ bond_ij,
+             const int *__restrict__ bond_order, const int *__restrict__ bond_ptr, int cap_bonds, const int *__restrict__ mol_status,
+             const int *__restrict__ lig_type_in, const float *__restrict__ pocket_x, const float *__restrict__ pocket_radius,
+             const int *__restrict__ pocket_type, const int *__restrict__ pocket_ptr, int n_pocket, int n_pockets, int stage_cap,
+             const int *__restrict__ pocket_of, VinaP P, double *__restrict__ report, double *__restrict__ grad,
+             double *__restrict__ atom_score, int *__restrict__ lig_type, int *__restrict__ status) {
+    extern __shared__ double lds_d[];
+    char *lds = reinterpret_cast<char *>(lds_d);
+    const VinaLayout L = vina_layout(nm, stage_cap);
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, W = L.W;
+    double *part = reinterpret_cast<double *>(lds + L.part), *red = reinterpret_cast<double *>(lds + L.red);
+    float *x0 = reinterpret_cast<float *>(lds + L.x0), *rad = reinterpret_cast<float *>(lds + L.rad);
+    int *zat = reinterpret_cast<int *>(lds + L.zat), *typ = reinterpret_cast<int *>(lds + L.typ);
+    unsigned *cnt = reinterpret_cast<unsigned *>(lds + L.cnt), *flg = reinterpret_cast<unsigned *>(lds + L.flg);
+    unsigned *adj = reinterpret_cast<unsigned *>(lds + L.adj);
+    float *px = reinterpret_cast<float *>(lds + L.px), *prad = reinterpret_cast<float *>(lds + L.prad);
+    int *ptyp = reinterpret_cast<int *>(lds + L.ptyp);
+
+    // ---- is there a molecule (bit 0)?  Every `st` below is block-uniform.
+    int a0, a1, st = 0;
+    const bool seg = mol_segment(lig_ptr, b, n_atoms, a0, a1);
+    const int n = a1 - a0;
+    int p0 = 0, p1 = 0;
+    if (!seg || n <= 0 || n > MOL_MAX || n > nm || (mol_status[b] & (MOL_EMPTY | MOL_CAPACITY | MOL_BAD_SEGMENT))) st = VN_NO_MOLECULE;
+    if (!st) {
+        p0 = bond_ptr[b];
+        p1 = bond_ptr[b + 1];
+        if (p0 < 0 || p1 < p0 || p1 > cap_bonds || p1 - p0 > 3 * MOL_MAX) st = VN_NO_MOLECULE;
+    }
+    // ---- its pocket (bit 1)
+    int np = 0, q0 = 0;
+    if (!st) {
+        const int po = pocket_of[b];
+        if (po < -1 || po >= n_pockets) {
+            st = VN_BAD_INPUT;
+        } else if (po >= 0) {
+            q0 = pocket_ptr[po];
+            const int q1 = pocket_ptr[po + 1];
+            if (q0 < 0 || q1 < q0 || q1 > n_pocket) st = VN_BAD_INPUT;
+            else np = q1 - q0;
+        }
+    }
+    const int stage = min(np, stage_cap);
+    int atom_out = 0;
+    if (!st) {
+        int bad = 0;
+        for (int a = tid; a < n; a += VN_T) {
+            cnt[a] = 0;
+            flg[a] = 0;
+            zat[a] = 0;
+            rad[a] = 0.f;
+            for (int w = 0; w < W; ++w) adj[a * W + w] = 0;
+            const size_t ga = (size_t)(a0 + a);
+            const int e = elem[ga];
+            if (e < 0 || e >= F) {
+                bad |= VN_NO_MOLECULE;
+                continue;
+            }
+            const float rv = lig_radius[e];
+            if (!vina_finite(rv)) bad |= VN_BAD_INPUT;
+            rad[a] = rv;
+            zat[a] = zs[e];
+            for (int k = 0; k < 3; ++k) {
+                const float v = pos[ga * 3 + k];
+                if (!vina_finite(v)) bad |= VN_BAD_INPUT;
+                x0[3 * a + k] = v;
+            }
+        }
+        for (int j = tid; j < np; j += VN_T) {       // every pocket atom is checked, the first `stage` are kept
+            const float *r = pocket_x + (size_t)(q0 + j) * 3;
+            const float rv = pocket_radius[q0 + j];
+            const int tj = pocket_type[q0 + j];
+            if (!(vina_finite(r[0]) && vina_finite(r[1]) && vina_finite(r[2]) && vina_finite(rv))) bad |= VN_BAD_INPUT;
+            if (tj < 0 || !(rv > 0.0f)) atom_out = 1;
+            if (j < stage) {
+                px[3 * j] = r[0];
+                px[3 * j + 1] = r[1];
+                px[3 * j + 2] = r[2];
+                prad[j] = rv;
+                ptyp[j] = tj;
+            }
+        }
+        const int no_mol = __syncthreads_or(bad & VN_NO_MOLECULE), bad_in = __syncthreads_or(bad & VN_BAD_INPUT);     // votes, not sums
+        st = no_mol ? VN_NO_MOLECULE : bad_in ? VN_BAD_INPUT : 0;
+    }
+    if (!st) {                                       // the bond graph: bit matrix, degrees, neighbour flags (integer atomics: no order)
+        int bad = 0;
+        for (int k = p0 + tid; k < p1; k += VN_T) {
+            const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0, o = bond_order[k];
+            if (i < 0 || i >= n || j < 0 || j >= n || i == j || o < 1 || o > 3) {
+                bad = 1;
+                continue;
+            }
+            const int zi = zat[i], zj = zat[j];
+            if (!(element_row(zi) & 0xffu) || !(element_row(zj) & 0xffu)) {      // an element the bond rule never bonds
+                bad = 1;
+                continue;
+            }
+            const unsigned was = atomicOr(&adj[i * W + (j >> 5)], 1u << (j & 31));
+            atomicOr(&adj[j * W + (i >> 5)], 1u << (i & 31));
+            if (was & (1u << (j & 31))) bad = 1;     // a bond twice
+            const unsigned ci = atomicAdd(&cnt[i], 1u + (zj != 1 ? 16u : 0u)), cj = atomicAdd(&cnt[j], 1u + (zi != 1 ? 16u : 0u));
+            if ((ci & 15u) >= (unsigned)VN_DEG || (cj & 15u) >= (unsigned)VN_DEG) bad = 1;      // a seventh neighbour
+            if (zj != 1) atomicOr(&flg[i], (zj != 6 ? VN_HETERO : 0u) | (1u << o));
+            if (zi != 1) atomicOr(&flg[j], (zi != 6 ? VN_HETERO : 0u) | (1u << o));
+        }
+        st = __syncthreads_or(bad) ? VN_NO_MOLECULE : 0;
+    }
+    if (st) {                                        // left out: zero rows, types -1
+        if (tid < 8) report[(size_t)b * 8 + tid] = 0.0;
+        if (tid == 0) status[b] = st;
+        if (seg)
+            for (int a = a0 + tid; a < a1; a += VN_T) {
+                if (grad) grad[(size_t)a * 3] = grad[(size_t)a * 3 + 1] = grad[(size_t)a * 3 + 2] = 0.0;
+                if (atom_score) atom_score[a] = 0.0;
+                if (lig_type) lig_type[a] = -1;
+            }
+        return;
+    }
+    // ---- types
+    for (int a = tid; a < n; a += VN_T) {
+        const int z = zat[a];
+        int f = vina_flags(z, (int)((cnt[a] >> 4) & 15u), flg[a]);
+        if (lig_type_in) {
+            const int over = lig_type_in[a0 + a];
+            if (over >= 0) f = over & 7;
+        }
+        const int t = (z == 1 || !(rad[a] > 0.0f)) ? -1 : f;
+        if (t < 0) atom_out = 1;
+        typ[a] = t;
+        if (lig_type) lig_type[a0 + a] = t;
+    }
+    // ---- rotors: single bonds between atoms of heavy degree >= 2 that are in no ring
+    int rot = 0;
+    for (int k = p0 + tid; k < p1; k += VN_T) {
+        if (bond_order[k] != 1) continue;
+        const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0;
+        if (((cnt[i] >> 4) & 15u) < 2u || ((cnt[j] >> 4) & 15u) < 2u) continue;
+        if (!vina_in_ring(adj, W, i, j)) ++rot;
+    }
+    rot = wave_sum(rot);
+    int *redi = reinterpret_cast<int *>(red);
+    if (lane == 0) redi[wv] = rot;
+    if (__syncthreads_or(atom_out)) st |= VN_ATOM_OUT;   // also orders typ and redi before their readers
+    const int n_rot = (redi[0] + redi[1]) + (redi[2] + redi[3]);
+    const double inv_norm = 1.0 / (1.0 + P.w_rot * (double)n_rot);
+
+    // ---- pair sums: wave w takes the atoms w, w + 4, ...
+    const float *gpx = pocket_x + (size_t)q0 * 3, *gpr = pocket_radius + q0;
+    const int *gpt = pocket_type + q0;
+    for (int i = wv; i < n; i += 4) {
+        const int ti = typ[i];
+        double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, gx = 0.0, gy = 0.0, gz = 0.0;
+        if (ti >= 0) {                               // wave-uniform
+            const double xi = (double)x0[3 * i], yi = (double)x0[3 * i + 1], zi = (double)x0[3 * i + 2], Ri = (double)rad[i];
+            for (int j = lane; j < np; j += 64) {
+                float qx, qy, qz, rj;
+                int tj;
+                if (j < stage) {
+                    qx = px[3 * j];
+                    qy = px[3 * j + 1];
+                    qz = px[3 * j + 2];
+                    rj = prad[j];
+                    tj = ptyp[j];
+                } else {
+                    const float *r = gpx + (size_t)j * 3;
+                    qx = r[0];
+                    qy = r[1];
+                    qz = r[2];
+                    rj = gpr[j];
+                    tj = gpt[j];
+                }
+                if (tj < 0 || !(rj > 0.0f)) continue;
+                const double dx = xi - (double)qx, dy = yi - (double)qy, dz = zi - (double)qz;
+                const double d2 = sum_sq(dx, dy, dz);
+                if (!(d2 < P.rc2)) continue;
+                const double r = __dsqrt_rn(d2), d = (r - Ri) - (double)rj;
+                const double dd = vina_pair(d, ti, tj & 7, P, t);
+                if (r >= 1e-6) {
+                    const double k = dd / r;
+                    gx += k * dx;
+                    gy += k * dy;
+                    gz += k * dz;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) t[k] = vina_wave_sum(t[k]);
+        gx = vina_wave_sum(gx);
+        gy = vina_wave_sum(gy);
+        gz = vina_wave_sum(gz);
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) part[5 * i + k] = t[k];
+            if (grad) {
+                double *g = grad + (size_t)(a0 + i) * 3;
+                g[0] = gx * inv_norm;
+                g[1] = gy * inv_norm;
+                g[2] = gz * inv_norm;
+            }
+            if (atom_score) atom_score[a0 + i] = (((P.w[0] * t[0] + P.w[1] * t[1]) + P.w[2] * t[2]) + P.w[3] * t[3]) + P.w[4] * t[4];
+        }
+    }
+    __syncthreads();
+    if (wv == 0) {
+        double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int i = lane; i < n; i += 64) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) s[k] += part[5 * i + k];
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) s[k] = vina_wave_sum(s[k]);
+        if (lane == 0) {
+            double *r = report + (size_t)b * 8;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) s[k] *= P.w[k];
+            const double inter = (((s[0] + s[1]) + s[2]) + s[3]) + s[4];
+            r[0] = inter * inv_norm;
+            r[1] = inter;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) r[2 + k] = s[k];
+            r[7] = (double)n_rot;
+            status[b] = st;
+        }
+    }
+}
+
+}  // namespace kpd
+
+using namespace kpd;
+
+extern "C" kpd_status kpd_vina_pocket_types(const float *pocket_x, const int32_t *pocket_z, const int32_t *pocket_ptr, int32_t n_pocket,
+                                            int32_t P, int32_t *pocket_type, int32_t *status, void *stream) {
+    KPD_REQUIRE(n_pocket >= 0 && P >= 0, KPD_ERR_INVALID, "n_pocket=%d P=%d", n_pocket, P);
+    KPD_REQUIRE(!P || (pocket_ptr && status), KPD_ERR_INVALID, "null argument");
+    KPD_REQUIRE(!n_pocket || (pocket_x && pocket_z && pocket_type), KPD_ERR_INVALID, "null pocket buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // atoms outside every well-formed segment read -1
+    if (n_pocket) KPD_HIP(hipMemsetAsync(pocket_type, 0xff, (size_t)n_pocket * 4, st));
+    if (!P) return KPD_OK;
+    const int tiles = std::max(1, cdiv(n_pocket, VN_T));
+    KPD_REQUIRE((int64_t)P * tiles <= 0x7fffffffLL, KPD_ERR_INVALID, "P=%d pockets x %d tiles exceed the grid", P, tiles);
+    hipLaunchKernelGGL(k_vina_pocket_types, dim3((unsigned)(P * tiles)), dim3(VN_T), 0, st, pocket_x, pocket_z, pocket_ptr, n_pocket, tiles,
+                       pocket_type, status);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+extern "C" kpd_status kpd_vina_score(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, int32_t max_atoms,
+                                     const int32_t *elem, int32_t F, const int32_t *z, const float *lig_radius, const int32_t *bond_ij,
+                                     const int32_t *bond_order, const int32_t *bond_ptr, int32_t cap_bonds, const int32_t *mol_status,
+                                     const int32_t *lig_type_in, const float *pocket_x, const float *pocket_radius,
+                                     const int32_t *pocket_type, const int32_t *pocket_ptr, int32_t n_pocket, int32_t P,
+                                     int32_t max_pocket, const int32_t *pocket_of, const kpd_vina_params *params, double *report,
+                                     double *grad, double *atom_score, int32_t *lig_type, int32_t *status, void *stream) {
+    KPD_REQUIRE(n_atoms >= 0 && B >= 0 && F >= 1 && cap_bonds >= 0 && n_pocket >= 0 && P >= 0 && max_pocket >= 0, KPD_ERR_INVALID,
+                "n_atoms=%d B=%d F=%d cap_bonds=%d n_pocket=%d P=%d max_pocket=%d", n_atoms, B, F, cap_bonds, n_pocket, P, max_pocket);
+    KPD_REQUIRE(max_atoms >= 1 && max_atoms <= MOL_MAX, KPD_ERR_INVALID, "max_atoms=%d (1 .. %d)", max_atoms, MOL_MAX);
+    KPD_REQUIRE(lig_ptr && z && lig_radius && bond_ptr, KPD_ERR_INVALID, "null argument");
+    KPD_REQUIRE(!n_atoms || (pos && elem), KPD_ERR_INVALID, "null argument");
+    KPD_REQUIRE(!B || (mol_status && pocket_of && report && status), KPD_ERR_INVALID, "null argument");
+    KPD_REQUIRE(!cap_bonds || (bond_ij && bond_order), KPD_ERR_INVALID, "null bond buffer");
+    KPD_REQUIRE(!P || pocket_ptr, KPD_ERR_INVALID, "null pocket_ptr");
+    KPD_REQUIRE(!n_pocket || (pocket_x && pocket_radius && pocket_type), KPD_ERR_INVALID, "null pocket buffer");
+    kpd_vina_params d;
+    kpd_vina_defaults(&d);
+    if (params) d = *params;
+    const double ws[5] = {d.w_gauss1, d.w_gauss2, d.w_repulsion, d.w_hydrophobic, d.w_hbond};
+    bool ok = d.r_c > 0.0 && d.r_c < 1e6 && d.w_rot >= 0.0 && d.w_rot < 1e12;
+    for (double w : ws) ok = ok && w > -1e12 && w < 1e12;
+    KPD_REQUIRE(ok, KPD_ERR_INVALID, "weights %g %g %g %g %g (finite) w_rot=%g (>= 0) r_c=%g (> 0)", ws[0], ws[1], ws[2], ws[3], ws[4],
+                d.w_rot, d.r_c);
+    if (!B) return KPD_OK;
+    VinaP vp;
+    for (int k = 0; k < 5; ++k) vp.w[k] = ws[k];
+    vp.w_rot = d.w_rot;
+    vp.rc2 = d.r_c * d.r_c;
+    // as much of the largest pocket as fits beside a max_atoms ligand
+    const size_t fixed = vina_layout(max_atoms, 0).bytes;
+    KPD_REQUIRE(fixed + 64 <= (size_t)VN_LDS, KPD_ERR_INVALID, "no LDS for %d atoms", max_atoms);
+    const int stage = (int)std::min<size_t>((size_t)max_pocket, ((size_t)VN_LDS - 64 - fixed) / VN_POCKET_ROW);
+    const VinaLayout L = vina_layout(max_atoms, stage);
+    KPD_REQUIRE(L.bytes <= (size_t)VN_LDS, KPD_ERR_INVALID, "LDS layout of %zu bytes", L.bytes);
+    hipLaunchKernelGGL(k_vina_score, dim3(B), dim3(VN_T), L.bytes, static_cast<hipStream_t>(stream), pos, lig_ptr, n_atoms, max_atoms, elem,
+                       F, z, lig_radius, bond_ij, bond_order, bond_ptr, cap_bonds, mol_status, lig_type_in, pocket_x, pocket_radius,
+                       pocket_type, pocket_ptr, n_pocket, P, stage, pocket_of, vp, report, grad, atom_score, lig_type, status);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+extern "C" void kpd_vina_defaults(kpd_vina_params *p) {
+    if (!p) return;
+    p->w_gauss1 = -0.035579;
+    p->w_gauss2 = -0.005156;
+    p->w_repulsion = 0.840245;
+    p->w_hydrophobic = -0.035069;
+    p->w_hbond = -0.587439;
+    p->w_rot = 0.05846;
+    p->r_c = 8.0;
+}

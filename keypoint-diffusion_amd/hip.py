@@ -89,6 +89,10 @@ class KpdRelaxParams(C.Structure):
                 ('gtol', C.c_double), ('max_step', C.c_double), ('max_iters', C.c_int32)]
 
 
+class KpdVinaParams(C.Structure):
+    _fields_ = [(name, C.c_double) for name in ('w_gauss1', 'w_gauss2', 'w_repulsion', 'w_hydrophobic', 'w_hbond', 'w_rot', 'r_c')]
+
+
 class KpdError(RuntimeError):
     pass
 
@@ -198,6 +202,12 @@ def lib():
     L.kpd_relax_defaults.restype = None
     L.kpd_relax.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
                             [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p, C.POINTER(KpdRelaxParams)] + [C.c_void_p] * 4)
+    L.kpd_vina_defaults.argtypes = [C.POINTER(KpdVinaParams)]
+    L.kpd_vina_defaults.restype = None
+    L.kpd_vina_pocket_types.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 3
+    L.kpd_vina_score.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 +
+                                 [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.POINTER(KpdVinaParams)] +
+                                 [C.c_void_p] * 6)
     _lib = L
     return L
 
@@ -230,6 +240,7 @@ EXPORTS = [
     'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
     'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
     'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_relax_defaults', 'kpd_relax',
+    'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score',
 ]
 
 
@@ -1168,6 +1179,91 @@ def relax(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_vdw: torch.Tensor, mo
                           M if max_pocket is None else int(max_pocket), _ptr(pocket_of), C.byref(p), _ptr(pos_out), _ptr(report),
                           _ptr(status), _stream()))
     return pos_out, report, status
+
+
+VINA_NO_MOLECULE, VINA_BAD_INPUT, VINA_ATOM_OUT = 1, 2, 4       # status bits of kpd_vina_score
+VINA_POCKET_BAD_SEGMENT, VINA_POCKET_NONFINITE = 1, 2           # status bits of kpd_vina_pocket_types
+VINA_H, VINA_D, VINA_A = 1, 2, 4                                # type flags: hydrophobic, hydrogen-bond donor, acceptor
+VINA_REPORT = ('score', 'inter', 'gauss1', 'gauss2', 'repulsion', 'hydrophobic', 'hbond', 'n_rot')
+
+
+def vina_params(**params) -> KpdVinaParams:
+    """The parameters of kpd_vina_score: the library's defaults (kpd_vina_defaults: Vina's published weights as recalled, not
+    checked against the paper or Vina's source) with the given fields replaced."""
+    p = KpdVinaParams()
+    lib().kpd_vina_defaults(C.byref(p))
+    names = [f[0] for f in KpdVinaParams._fields_]
+    for k, v in params.items():
+        if k not in names:
+            raise KpdError(f'vina: unknown parameter {k!r} (known: {sorted(names)})')
+        setattr(p, k, float(v))
+    if not (all(abs(getattr(p, k)) < 1e12 for k in names) and 0 < p.r_c < 1e6 and p.w_rot >= 0):
+        raise KpdError('vina: ' + ', '.join(f'{k} {getattr(p, k)}' for k in names) + ': the weights must be finite, w_rot >= 0, r_c > 0')
+    return p
+
+
+def vina_pocket_types(pocket_x: torch.Tensor, pocket_z: torch.Tensor, pocket_ptr: torch.Tensor):
+    """The H / D / A flags of every pocket atom on the GPU (kpd_vina_pocket_types; include/kpd.h states the rule, this library's
+    own).  pocket_x [M,3] fp32, pocket_z [M] int32 atomic numbers, pocket_ptr [P+1] int32; all GPU tensors.  Returns
+    (pocket_type [M] int32, -1 for an atom that takes no part; status [P] int32: bit 0 malformed segment, bit 1 a non-finite
+    coordinate).  Quadratic per pocket; done once per pocket set.  No host synchronisation."""
+    pocket_x = _dev_f32(pocket_x, 'pocket_x')
+    P = _offsets(pocket_ptr, 'vina_pocket_types: pocket_ptr', 'P')
+    M = pocket_x.shape[0]
+    pocket_z = _per_entry(pocket_z, 'vina_pocket_types: pocket_z', M, 'pocket atom')
+    if pocket_x.shape != (M, 3):
+        raise KpdError(f'vina_pocket_types: pocket_x {tuple(pocket_x.shape)} must be [M,3]')
+    types = torch.empty(M, dtype=torch.int32, device=pocket_x.device)
+    status = torch.empty(P, dtype=torch.int32, device=pocket_x.device)
+    check(lib().kpd_vina_pocket_types(_ptr(pocket_x), _ptr(pocket_z), _ptr(pocket_ptr), M, P, _ptr(types), _ptr(status), _stream()))
+    return types, status
+
+
+def vina_score(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch.Tensor, mol: dict, pocket_x: torch.Tensor,
+               pocket_radius: torch.Tensor, pocket_type: torch.Tensor, pocket_ptr: torch.Tensor, pocket_of: torch.Tensor,
+               lig_type_in: Optional[torch.Tensor] = None, grad: bool = False, atom_score: bool = False, max_atoms: int = MOL_MAX_ATOMS,
+               max_pocket: Optional[int] = None, **params):
+    """Score a batch of perceived ligands in their rigid pockets on the GPU (kpd_vina_score; include/kpd.h states the function:
+    the Vina functional form with a typing rule of this library's own, NOT gnina's or Vina's numbers).  pos [N,3] fp32, lig_ptr
+    [B+1] int32, z: the atomic number of every feature class, lig_radius [F] fp32, `mol`: what `mol_perceive` returned, pocket_x
+    [M,3], pocket_radius [M] fp32, pocket_type [M] int32 (from `vina_pocket_types` or the caller), pocket_ptr [P+1] and pocket_of
+    [B] int32 (-1: no pocket), lig_type_in: None or [N] int32 whose entries >= 0 replace the perceived flags; all GPU tensors.
+    Returns a dict of device tensors: report [B,8] float64 (columns VINA_REPORT), status [B], lig_type [N] and, on request, grad
+    [N,3] and atom_score [N] float64.  No host synchronisation."""
+    pos = _dev_f32(pos, 'pos')
+    B = _offsets(lig_ptr, 'lig_ptr')
+    _mol_fields('vina_score', mol, ('elem', 'bonds', 'order', 'bond_ptr', 'status'))
+    P = _offsets(pocket_ptr, 'vina_score: pocket_ptr', 'P')
+    pocket_of = _per_entry(pocket_of, 'vina_score: pocket_of', B, 'ligand', contiguous=True)
+    lig_radius, pocket_x, pocket_radius = _dev_f32(lig_radius, 'lig_radius'), _dev_f32(pocket_x, 'pocket_x'), _dev_f32(pocket_radius, 'pocket_radius')
+    N, F, M = pos.shape[0], len(z), pocket_x.shape[0]
+    pocket_type = _per_entry(pocket_type, 'vina_score: pocket_type', M, 'pocket atom')
+    if lig_type_in is not None:
+        lig_type_in = _per_entry(lig_type_in, 'vina_score: lig_type_in', N, 'ligand atom')
+    cap_bonds = mol['order'].numel()
+    if (pos.shape != (N, 3) or F < 1 or lig_radius.shape != (F,) or mol['elem'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or
+            mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B or pocket_x.shape != (M, 3) or pocket_radius.shape != (M,)):
+        raise KpdError(f'vina_score: pos {tuple(pos.shape)}, {B} ligands, {F} classes, lig_radius {tuple(lig_radius.shape)}, pocket_x '
+                       f'{tuple(pocket_x.shape)}, pocket_radius {tuple(pocket_radius.shape)}, {P} pockets do not match each other or '
+                       f'the perceived molecules')
+    max_atoms = int(max_atoms)
+    if not 1 <= max_atoms <= MOL_MAX_ATOMS:
+        raise KpdError(f'vina_score: max_atoms {max_atoms} must be 1 .. {MOL_MAX_ATOMS}')
+    p = vina_params(**params)
+    dev = pos.device
+    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
+    out = dict(report=torch.empty(B, 8, dtype=torch.float64, device=dev), status=torch.empty(B, dtype=torch.int32, device=dev),
+               lig_type=torch.empty(N, dtype=torch.int32, device=dev))
+    if grad:
+        out['grad'] = torch.empty(N, 3, dtype=torch.float64, device=dev)
+    if atom_score:
+        out['atom_score'] = torch.empty(N, dtype=torch.float64, device=dev)
+    check(lib().kpd_vina_score(_ptr(pos), _ptr(lig_ptr), N, B, max_atoms, _ptr(mol['elem']), F, _ptr(zt), _ptr(lig_radius), _ptr(mol['bonds']),
+                               _ptr(mol['order']), _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']), _ptr(lig_type_in), _ptr(pocket_x),
+                               _ptr(pocket_radius), _ptr(pocket_type), _ptr(pocket_ptr), M, P, M if max_pocket is None else int(max_pocket),
+                               _ptr(pocket_of), C.byref(p), _ptr(out['report']), _ptr(out.get('grad')), _ptr(out.get('atom_score')),
+                               _ptr(out['lig_type']), _ptr(out['status']), _stream()))
+    return out
 
 
 def sample_update(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h, coef):

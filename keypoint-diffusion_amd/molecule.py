@@ -16,7 +16,13 @@ inherits the length-class bond orders.
 openbabel's perception rules are not restated: include/kpd.h defines the rule used here, the lookup-table builder of the
 EDM / DiffSBDD lineage (covalent radii for connectivity, length classes for the bond orders, valence caps).  The bond orders
 are length classes, not a Kekule structure; connectivity, fragments and `metrics` do not depend on them.  What needs
-sanitisation or a docking program (`validity`, QED / SA, docking) stays with the caller, who can read the SDF blocks with rdkit.
+sanitisation or a docking program (`validity`, QED / SA, docking and gnina's `--minimize`) stays with the caller, who can read the
+SDF blocks with rdkit.  The scoring half of docking is here: `Molecules.vina_score` / `score_samples` evaluate the AutoDock Vina
+FUNCTIONAL FORM (five pair terms over ligand x pocket heavy atoms, divided by 1 + w_rot N_rot) with its analytic gradient for the
+whole batch in one launch (`kpd_vina_score`, csrc/vina.hip).  The typing is a rule of this library's own, defined in
+include/kpd.h (no hydrogens, no aromaticity), and the weights and radii are recalled constants: the scores rank samples scored
+here against each other and ARE NOT gnina's or Vina's numbers.  No search, no minimisation under this function, no
+intramolecular term.
 
 Where upstream minimises every sample inside its pocket with RDKit's UFF (analysis/pocket_minimization.py), `Molecules.relax` /
 `relax_samples` relax the whole batch in one kernel launch (`kpd_relax`, csrc/relax.hip) with a force field of this library's
@@ -71,6 +77,42 @@ def vdw_table(elements: Sequence[str], vdw: Optional[Dict[str, tuple]] = None) -
             raise hip.KpdError(f'relax: van der Waals parameters of {el!r} must be x > 0 and D >= 0 (got {row!r})')
         rows.append([x, d])
     return rows
+
+
+# surface radii for `Molecules.vina_score`, element -> Angstrom, in the form of Vina's "xs" radii (1.2 for the metals the typing
+# rule knows).  RECALLED, NOT CHECKED AGAINST TROTT & OLSON 2010 OR VINA'S SOURCE: nothing may rely on these being Vina's values;
+# pass `radii=` to override.
+XS_RADII: Dict[str, float] = {
+    'C': 1.9, 'N': 1.8, 'O': 1.7, 'F': 1.5, 'Si': 2.2, 'P': 2.1, 'S': 2.0, 'Cl': 1.8, 'Br': 2.0, 'I': 2.2,
+    'Mg': 1.2, 'Ca': 1.2, 'Mn': 1.2, 'Fe': 1.2, 'Co': 1.2, 'Ni': 1.2, 'Cu': 1.2, 'Zn': 1.2,
+}
+
+
+def xs_radius_table(elements: Sequence[str], radii: Optional[Dict[str, float]] = None) -> List[float]:
+    """The radius of every element symbol, from `radii` first and XS_RADII second; an element in neither raises.  A radius of 0
+    is allowed: such an atom takes no part in the score (kpd_vina_score reports it with type -1 and status bit 2)."""
+    out = []
+    for el in elements:
+        r = (radii or {}).get(el, XS_RADII.get(el))
+        if r is None:
+            raise hip.KpdError(f'vina_score: no radius for element {el!r}; pass radii={{{el!r}: R}}')
+        r = float(r)
+        if not 0 <= r < float('inf'):
+            raise hip.KpdError(f'vina_score: the radius of {el!r} must be finite and >= 0 (got {r!r})')
+        out.append(r)
+    return out
+
+
+def _pocket_of(pocket_of, B: int, n_pockets: int, dev) -> torch.Tensor:
+    """The pocket of every ligand as an int32 tensor on `dev`: all zeros when one pocket is given and `pocket_of` is None."""
+    if pocket_of is None:
+        if n_pockets != 1:
+            raise ValueError(f'pocket_of is needed to tell which of the {n_pockets} pockets every ligand sits in')
+        return torch.zeros(B, dtype=torch.int32, device=dev)
+    host = torch.as_tensor(pocket_of).cpu().flatten()
+    if host.numel() != B or (host.numel() and (int(host.min()) < -1 or int(host.max()) >= n_pockets)):
+        raise ValueError(f'pocket_of must name one of the {n_pockets} pockets (or -1) for each of the {B} ligands')
+    return host.to(torch.int32).to(dev)
 
 
 class Molecules:
@@ -221,15 +263,7 @@ class Molecules:
         for q, (p, els) in enumerate(zip(pocket_pos, pocket_elements)):
             if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] != len(els):
                 raise hip.KpdError(f'relax: pocket {q} has positions {tuple(p.shape)} and {len(els)} element symbols')
-        if pocket_of is None:
-            if len(pocket_pos) != 1:
-                raise ValueError(f'pocket_of is needed to tell which of the {len(pocket_pos)} pockets every ligand sits in')
-            pocket_of = torch.zeros(B, dtype=torch.int32, device=dev)
-        else:
-            host = torch.as_tensor(pocket_of).cpu().flatten()
-            if host.numel() != B or (host.numel() and (int(host.min()) < -1 or int(host.max()) >= len(pocket_pos))):
-                raise ValueError(f'pocket_of must name one of the {len(pocket_pos)} pockets (or -1) for each of the {B} ligands')
-            pocket_of = host.to(torch.int32).to(dev)
+        pocket_of = _pocket_of(pocket_of, B, len(pocket_pos), dev)
         lig_vdw = torch.tensor(vdw_table(self.lig_elements, vdw), dtype=torch.float32, device=dev).reshape(-1, 2)
         rows = [r for els in pocket_elements for r in vdw_table(els, vdw)]
         pocket_vdw = torch.tensor(rows, dtype=torch.float32, device=dev).reshape(-1, 2)
@@ -244,6 +278,57 @@ class Molecules:
         pos, report, status = hip.relax(self.pos, self.lig_ptr, z, lig_vdw, mol, pocket_x, pocket_vdw, pocket_ptr, pocket_of,
                                         max_atoms=max(1, min(n_max, hip.MOL_MAX_ATOMS)), max_pocket=max(sizes, default=0), **params)
         return Relaxed(self, pos, report, status)
+
+
+    def vina_score(self, pocket_pos: List[torch.Tensor], pocket_elements: List[Sequence[str]], pocket_of=None,
+                   radii: Optional[Dict[str, float]] = None, pocket_types=None, lig_types: Optional[torch.Tensor] = None,
+                   grad: bool = False, **params) -> 'VinaScores':
+        """Score every ligand in its rigid pocket on the GPU, all in one launch (`kpd_vina_score`): the Vina functional form that
+        include/kpd.h defines, with a typing rule of this library's own and recalled weights and radii.  NOT gnina's or Vina's
+        numbers: the scores rank samples scored by this function against each other.
+        `pocket_pos`, `pocket_elements`, `pocket_of`: as for `relax`; `radii`: element -> radius, consulted before XS_RADII (an
+        element in neither raises); `pocket_types`: a `VinaScores.pocket_types` to reuse, or the caller's own flags (1 hydrophobic,
+        2 donor, 4 acceptor, -1 takes no part) as one sequence per pocket or one [M] tensor, in place of the perceived ones;
+        `lig_types`: [N] int32 whose entries >= 0 replace the perceived ligand flags; `grad`: also return the gradient and the
+        per-atom scores; `params`: w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond, w_rot, r_c."""
+        if self.pos is None or self.lig_elements is None or self.bonds is None:
+            raise hip.KpdError('these Molecules carry no coordinates: build them with build_molecules')
+        if len(pocket_pos) != len(pocket_elements):
+            raise ValueError('pocket_pos and pocket_elements must have one entry per pocket')
+        if not self.pos.is_cuda or any(not p.is_cuda for p in pocket_pos):
+            raise hip.KpdError('vina_score: ligands and pockets must live on the GPU; scoring has no CPU implementation')
+        B, dev = len(self), self.pos.device
+        for q, (p, els) in enumerate(zip(pocket_pos, pocket_elements)):
+            if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] != len(els):
+                raise hip.KpdError(f'vina_score: pocket {q} has positions {tuple(p.shape)} and {len(els)} element symbols')
+        pocket_of = _pocket_of(pocket_of, B, len(pocket_pos), dev)
+        lig_radius = torch.tensor(xs_radius_table(self.lig_elements, radii), dtype=torch.float32, device=dev)
+        pocket_radius = torch.tensor([r for els in pocket_elements for r in xs_radius_table(els, radii)], dtype=torch.float32, device=dev)
+        sizes = [int(p.shape[0]) for p in pocket_pos]
+        pocket_x = torch.cat([p.reshape(-1, 3).float() for p in pocket_pos]) if sizes else torch.zeros(0, 3, device=dev)
+        pocket_ptr = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0).to(torch.int32).to(dev)
+        if pocket_types is None:
+            pz = torch.tensor([ATOMIC_NUMBERS.get(el, 0) for els in pocket_elements for el in els], dtype=torch.int32, device=dev)
+            pocket_types, _ = hip.vina_pocket_types(pocket_x, pz, pocket_ptr)
+        else:
+            if not isinstance(pocket_types, torch.Tensor):
+                pocket_types = torch.tensor([int(t) for row in pocket_types for t in row], dtype=torch.int32)
+            pocket_types = pocket_types.to(torch.int32).to(dev).flatten()
+            if pocket_types.numel() != sum(sizes):
+                raise hip.KpdError(f'vina_score: pocket_types has {pocket_types.numel()} entries for {sum(sizes)} pocket atoms')
+        if lig_types is not None:
+            lig_types = torch.as_tensor(lig_types).to(torch.int32).to(dev).flatten()
+        z = [ATOMIC_NUMBERS.get(el, 0) for el in self.lig_elements]
+        mol = dict(elem=self.elem, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
+        if B == 0:
+            empty = dict(report=torch.zeros(0, 8, dtype=torch.float64, device=dev), status=torch.zeros(0, dtype=torch.int32, device=dev),
+                         lig_type=torch.zeros(0, dtype=torch.int32, device=dev))
+            return VinaScores(self, empty, pocket_types)
+        n_max = self._max_atoms if self._max_atoms is not None else hip.MOL_MAX_ATOMS
+        out = hip.vina_score(self.pos, self.lig_ptr, z, lig_radius, mol, pocket_x, pocket_radius, pocket_types, pocket_ptr, pocket_of,
+                             lig_type_in=lig_types, grad=grad, atom_score=grad, max_atoms=max(1, min(n_max, hip.MOL_MAX_ATOMS)),
+                             max_pocket=max(sizes, default=0), **params)
+        return VinaScores(self, out, pocket_types)
 
 
 class Relaxed:
@@ -271,6 +356,50 @@ class Relaxed:
         keep = ((st & (hip.RELAX_NO_MOLECULE | hip.RELAX_BAD_INPUT)) == 0).nonzero().flatten().tolist()
         return dict(lig_idx=keep, rmsd=rep[keep, 2].tolist(), energy_before=rep[keep, 0].tolist(), energy_after=rep[keep, 1].tolist(),
                     pocket_energy=rep[keep, 9].tolist())
+
+
+class VinaScores:
+    """What `Molecules.vina_score` returns: `.report` [B,8] float64 (columns hip.VINA_REPORT: score, inter, the five weighted
+    terms, n_rot) and `.status` [B] (bits: 1 no molecule, 2 bad input, 4 some atom took no part), `.score` [B] (NaN where status
+    bit 0 or 1 is set), `.lig_types` [N] and `.pocket_types` [M] (flags 1 hydrophobic, 2 donor, 4 acceptor; -1 takes no part),
+    device tensors; `.grad` / `.atom_score`: lists of per-ligand [n_i,3] / [n_i] float64 tensors, or None when not asked for.
+    NOT gnina's or Vina's numbers: see include/kpd.h."""
+
+    def __init__(self, mols: Molecules, out: Dict[str, torch.Tensor], pocket_types: torch.Tensor):
+        self.report, self.status, self.lig_types, self.pocket_types = out['report'], out['status'], out['lig_type'], pocket_types
+        self._grad, self._atom_score, self._mols = out.get('grad'), out.get('atom_score'), mols
+
+    def _split(self, t):
+        if t is None:
+            return None
+        m = self._mols
+        return list(torch.split(t, m._sizes if m._sizes is not None else (m.lig_ptr[1:] - m.lig_ptr[:-1]).tolist()))
+
+    @property
+    def score(self) -> torch.Tensor:
+        left_out = (self.status & (hip.VINA_NO_MOLECULE | hip.VINA_BAD_INPUT)) != 0
+        return torch.where(left_out, torch.full_like(self.report[:, 0], float('nan')), self.report[:, 0])
+
+    @property
+    def grad(self):
+        return self._split(self._grad)
+
+    @property
+    def atom_score(self):
+        return self._split(self._atom_score)
+
+    def table(self) -> Dict[str, list]:
+        """lig_idx, score, inter, the five weighted terms, n_rot and efficiency = score / heavy atoms taking part, as lists;
+        ligands that were left out (status bit 0 or 1) have no row, as in `Relaxed.table`."""
+        st, rep = self.status.cpu(), self.report.cpu()
+        keep = ((st & (hip.VINA_NO_MOLECULE | hip.VINA_BAD_INPUT)) == 0).nonzero().flatten().tolist()
+        taking = [int((t >= 0).sum()) for t in self._split(self.lig_types.cpu())]
+        out: Dict[str, list] = dict(lig_idx=keep)
+        for k, name in enumerate(hip.VINA_REPORT[:7]):
+            out[name] = rep[keep, k].tolist()
+        out['n_rot'] = [int(v) for v in rep[keep, 7].tolist()]
+        out['efficiency'] = [rep[b, 0].item() / taking[b] if taking[b] else 0.0 for b in keep]
+        return out
 
 
 def _class_tables(lig_elements: Sequence[str], allowed_bonds: Optional[Dict[str, object]]):
@@ -363,3 +492,35 @@ def relax_samples(samples: List[dict], pockets: List[dict], lig_elements: Sequen
         pocket_pos = [p.to(device) for p in pocket_pos]
     mols = build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds)
     return mols.relax(pocket_pos, [list(p['elements']) for p in pockets], pocket_of=pocket_of, vdw=vdw, **params)
+
+
+def score_samples(samples: List[dict], pockets: List[dict], lig_elements: Sequence[str], device=None, relax: bool = False,
+                  allowed_bonds: Optional[Dict[str, object]] = None, radii: Optional[Dict[str, float]] = None,
+                  vdw: Optional[Dict[str, tuple]] = None, pocket_types=None, grad: bool = False, vina: Optional[Dict[str, float]] = None,
+                  **relax_params):
+    """Score every sampled ligand in its own pocket (`Molecules.vina_score`, whose limits apply: NOT gnina's numbers), in the
+    mould of `relax_samples`: `samples` is the list of {'positions', 'features'} dicts `_sample` returns, one per pocket, and
+    `pockets` one {'positions', 'elements'} dict per entry.  Returns the `VinaScores` of the sampled poses; with `relax=True`
+    the ligands are also relaxed in their pockets (`Molecules.relax` with `vdw` and `relax_params`, e.g. max_iters) and the
+    result is (scores of the raw poses, scores of the relaxed poses, the `Relaxed`).  The pocket types are computed once.
+    `vina`: parameters of the score (w_gauss1 .. r_c)."""
+    if len(samples) != len(pockets):
+        raise ValueError('samples and pockets must have one entry per pocket')
+    lig_pos, lig_feat, pocket_of = [], [], []
+    for q, rec in enumerate(samples):
+        lig_pos.extend(rec['positions'])
+        lig_feat.extend(rec['features'])
+        pocket_of.extend([q] * len(rec['positions']))
+    pocket_pos = [torch.as_tensor(p['positions']) for p in pockets]
+    if device is not None:
+        lig_pos, lig_feat = [p.to(device) for p in lig_pos], [f.to(device) for f in lig_feat]
+        pocket_pos = [p.to(device) for p in pocket_pos]
+    pocket_elements = [list(p['elements']) for p in pockets]
+    mols = build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds)
+    raw = mols.vina_score(pocket_pos, pocket_elements, pocket_of=pocket_of, radii=radii, pocket_types=pocket_types, grad=grad, **(vina or {}))
+    if not relax:
+        return raw
+    relaxed = mols.relax(pocket_pos, pocket_elements, pocket_of=pocket_of, vdw=vdw, **relax_params)
+    after = relaxed.molecules.vina_score(pocket_pos, pocket_elements, pocket_of=pocket_of, radii=radii, pocket_types=raw.pocket_types,
+                                         grad=grad, **(vina or {}))
+    return raw, after, relaxed
