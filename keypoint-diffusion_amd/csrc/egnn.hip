@@ -584,10 +584,19 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
     hipStream_t st = static_cast<hipStream_t>(stream);
     const kpd_egnn_config &c = m->cfg;
 
-    KPD_HIP(hipMemcpyAsync(m->x[NT_LIG], bt->lig_x, (size_t)bt->n_lig * 12, hipMemcpyDeviceToDevice, st));
-    KPD_HIP(hipMemcpyAsync(m->x[NT_KP], bt->kp_x, (size_t)bt->n_kp * 12, hipMemcpyDeviceToDevice, st));
-    KPD_TRY(launch_node_graph_index(bt->lig_ptr, bt->B, bt->n_lig, m->bidx[NT_LIG], st));
-    KPD_TRY(launch_node_graph_index(bt->kp_ptr, bt->B, bt->n_kp, m->bidx[NT_KP], st));
+    // One-hot kp_h (below): the flag's reset rides in the ligand launch of k_node_graph_index and the test of every keypoint row in
+    // the keypoint launch behind it.
+    const int n_tab = bt->B * c.rec_nf;
+    const bool kp_tab = m->kp_table && m->gemm_mode == 0 && m->tab_rows > 0 && (long)bt->B * c.rec_nf <= bt->n_kp / 2;
+    m->last_table = kp_tab;
+    KPD_TRY(launch_node_graph_index(bt->lig_ptr, bt->B, bt->n_lig, m->bidx[NT_LIG], st, kp_tab ? m->kp_ok : nullptr));
+    if (kp_tab)
+        KPD_TRY(launch_node_graph_index(bt->kp_ptr, bt->B, bt->n_kp, m->bidx[NT_KP], st, nullptr, bt->kp_h, c.rec_nf, m->rowmap, m->kp_ok));
+    else
+        KPD_TRY(launch_node_graph_index(bt->kp_ptr, bt->B, bt->n_kp, m->bidx[NT_KP], st));
+    // The coordinates are not copied into the engine first: the kernels read the caller's arrays until a node update has written
+    // m->x (layer 0 reads bt->lig_x / bt->kp_x, its node update writes x_in + delta into m->x).
+    const float *x_cur[2] = {bt->lig_x, bt->kp_x};
     KPD_TRY(launch_lig_graph(bt, c.ll_cutoff, c.ll_k, c.kl_cutoff, c.kl_k, &m->lg, m->ll_deg, m->ll_off, m->kl_off, m->kl_pg, st));
     // LigRecEGNN.forward returns only (h_lig, x_lig) (dynamics.py:288-294): in the final layer the lk / kk messages and
     // the keypoint update feed nothing, so that layer runs the ll + kl edge types and the ligand update only (the GVP
@@ -607,16 +616,11 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
     // One-hot kp_h (the fixed receptor encoder's element encoding): the layer-0 keypoint state embed(kp_h[v], t[graph(v)]) and its
     // eight projections take at most rec_nf values per complex.  The same two kernels run on the B * rec_nf class rows, and layer 0's
     // edge kernel gathers keypoint rows from that table -- row for row the bits the per-atom launch gives.  Whether kp_h IS one-hot
-    // is decided on the device at every forward (k_kp_classify -> kp_ok); the per-atom launch stays in the stream behind it and
+    // is decided on the device at every forward (k_node_graph_index above -> kp_ok); the per-atom launch stays in the stream behind it and
     // returns at once when the flag is set.  Enqueued only where it can pay: fp32 mode, a learned embedding, at most half as many
     // class rows as keypoints.
-    const int n_tab = bt->B * c.rec_nf;
-    const bool kp_tab = m->kp_table && m->gemm_mode == 0 && m->tab_rows > 0 && (long)bt->B * c.rec_nf <= bt->n_kp / 2;
-    m->last_table = kp_tab;
     if (kp_tab) {
         KPD_REQUIRE(n_tab <= m->tab_rows, KPD_ERR_CAPACITY, "internal: %d class rows, table of %d", n_tab, m->tab_rows);
-        KPD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->kp_ok), 0x3f800000, 1, st));
-        KPD_TRY(launch_kp_classify(bt->kp_h, bt->n_kp, c.rec_nf, m->bidx[NT_KP], m->rowmap, m->kp_ok, st));
         KPD_TRY(launch_embed(m->tab_in, n_tab, c.rec_nf, m->re_W0, m->re_b0, 2 * c.rec_nf, m->re_W1t, m->re_b1, t_dev, m->tab_bidx,
                              m->hT, 0, st));
     }
@@ -687,7 +691,7 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
         memset(&ea, 0, sizeof(ea));
         const bool last = li == n_layers - 1;
         ea.meta = last ? m->meta + 16 : m->meta;
-        ea.x[0] = m->x[0]; ea.x[1] = m->x[1]; ea.P[0] = m->P[0]; ea.P[1] = m->P[1];
+        ea.x[0] = x_cur[0]; ea.x[1] = x_cur[1]; ea.P[0] = m->P[0]; ea.P[1] = m->P[1];
         ea.use_tanh = c.use_tanh; ea.coords_range = c.coords_range;
         ea.tile_rows = tr;
         ea.gemm_mode = tr == TM ? m->gemm_mode : 0;
@@ -736,6 +740,7 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
                 na.u.n = n[nt]; na.u.h = m->h[nt];
                 if (nt < m->n_upd && !(nt == NT_KP && last && prune)) {
                     fill_update(na.u, nt);
+                    na.u.x_in = x_cur[nt] == m->x[nt] ? nullptr : x_cur[nt];
                     na.do_update = 1;
                 }
                 if (!na.do_update && !na.do_proj) na.u.n = 0;          // nothing to do for this node type
@@ -743,8 +748,14 @@ extern "C" kpd_status kpd_egnn_forward(kpd_egnn *m, const kpd_batch *bt, const f
             lp.tiles0 = cdiv(lp.nt[0].u.n, TN);
             lp.gemm_mode = m->gemm_mode;
             KPD_TRY(launch_node_layer(lp, st));
+            for (int nt = 0; nt < 2; ++nt)
+                if (lp.nt[nt].do_update) x_cur[nt] = m->x[nt];
         }
     }
+    // a node type that no layer updated (no layers at all, keypoints without update_kp_feat or in a single pruned layer): m->x still
+    // has to hold its coordinates for the decoder and the x_lig / x_kp taps
+    if (x_cur[NT_LIG] != m->x[NT_LIG]) KPD_HIP(hipMemcpyAsync(m->x[NT_LIG], bt->lig_x, (size_t)bt->n_lig * 12, hipMemcpyDeviceToDevice, st));
+    if (x_cur[NT_KP] != m->x[NT_KP]) KPD_HIP(hipMemcpyAsync(m->x[NT_KP], bt->kp_x, (size_t)bt->n_kp * 12, hipMemcpyDeviceToDevice, st));
     KPD_TRY(launch_decode(m->h[NT_LIG], m->x[NT_LIG], bt->lig_x, bt->n_lig, c.atom_nf, 2 * c.atom_nf, m->de_W0, m->de_b0,
                           m->de_W1, m->de_b1, eps_h, eps_x, st));
     return KPD_OK;

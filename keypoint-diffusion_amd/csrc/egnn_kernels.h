@@ -12,7 +12,6 @@ constexpr int ET_LL = 0, ET_KL = 1, ET_LK = 2, ET_KK = 3;
 constexpr int NT_LIG = 0, NT_KP = 1;
 
 constexpr int EDGE_LDS_BYTES = TM * SA * 4 + (TM * 2 + TM + 3 * TM + TM + 3 * TM + 4 * HS + 8 + TM) * 4;   // ... misc[8], 64 column-256 values
-constexpr int EDGE_KPT_LDS_BYTES = EDGE_LDS_BYTES + 2 * TM * 4;     // k_egnn_edge_kpt: + the gather offsets of both sides (EdgeSmem::gsrc / gdst)
 // k_egnn_edge_h: two f16 planes of 64 x 280 halves (= the T tile's region), row data, two fp32 head rows, W2 row 256 as 2 x 2 x 272 halves
 constexpr int EDGE_H_LDS_BYTES = 64 * 280 * 2 * 2 + (TM * 2 + TM + 3 * TM + TM + 3 * TM + 2 * HS + 8) * 4 + 2 * 2 * 272 * 2;
 
@@ -120,6 +119,7 @@ struct NodeArgs {
     int n;
     float *h;                       // [n][HS] in/out
     float *x;                       // [n][3] in/out
+    const float *x_in;              // null, or the coordinates to read instead of x (layer 0: the caller's array; x is written only)
     const int *bidx;
     const float *z;                 // [B]
     int n_in;
@@ -159,15 +159,16 @@ constexpr int NODE_H_LDS_BYTES = NODE_H_TILE_FLOATS * 4 + 3 * TN * 4;
 
 
 kpd_status egnn_kernels_init();
-kpd_status launch_node_graph_index(const int *ptr, int B, int n, int *bidx, hipStream_t st);
+// bidx[i] = graph of node i.  Riders (EGNN forward): set_ok receives the bits of 1.0f; with kp_h every node's row of kp_h [n][fin] is
+// tested for one-hot: rowmap[v] = bidx[v] * fin + c for a row that is exactly e_c (one element with the bits of 1.0f, all others
+// +0.0f), any other row stores 0 to *ok (set by an EARLIER launch on the stream)
+kpd_status launch_node_graph_index(const int *ptr, int B, int n, int *bidx, hipStream_t st, int *set_ok = nullptr,
+                                   const float *kp_h = nullptr, int fin = 0, int *rowmap = nullptr, int *ok = nullptr);
 kpd_status launch_egnn_meta(const int *counts, int e_kk, int active_mask, int active_last, const int *lig_ptr, const int *kp_ptr,
                             const int *ll_per_graph, const int *kk_rowptr, int B, const int *kl_off, float message_norm,
                             int update_kp, int *meta, float *z_lig, float *z_kp, hipStream_t st, int tile_rows = TM);
 kpd_status launch_embed(const float *in, int n, int fin, const float *W0, const float *b0, int hid, const float *W1t,
                         const float *b1, const float *t, const int *bidx, float *out, int identity, hipStream_t st);
-// one-hot test of the keypoint features: rowmap[v] = bidx[v] * fin + c for a row that is exactly e_c (one element with the bits of
-// 1.0f, all others +0.0f); any other row stores 0 to *ok (set by the caller beforehand, on the stream)
-kpd_status launch_kp_classify(const float *kp_h, int n, int fin, const int *bidx, int *rowmap, int *ok, hipStream_t st);
 kpd_status launch_decode(const float *h, const float *x, const float *x0, int n, int atom_nf, int hid, const float *W0,
                          const float *b0, const float *W1, const float *b1, float *eps_h, float *eps_x, hipStream_t st);
 kpd_status launch_egnn_edge(const EdgeArgs &a, int tile_cap, hipStream_t st);

@@ -23,25 +23,12 @@
 namespace kpd {
 
 // ---- small helpers ------------------------------------------------------------------------
-__global__ void k_node_graph_index(const int *__restrict__ ptr, int B, int n, int *__restrict__ bidx) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int lo = 0, hi = B;                       // largest b with ptr[b] <= i
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (ptr[mid] <= i) lo = mid; else hi = mid;
-    }
-    bidx[i] = lo;
-}
-
-// Layer 0 of the fixed receptor encoder: kp_h is a one-hot element encoding, so the embedded keypoint rows and their projections take
-// at most fin distinct values per complex.  rowmap[v] = row of node v in the per-class table (graph * fin + class); a row that is not
-// exactly one-hot (compared by bits: one 1.0f, the rest +0.0f, so that the class row e_c is the same input bit for bit) clears *ok and
-// the forward runs the per-atom path (egnn.hip).
-__global__ void k_kp_classify(const float *__restrict__ kp_h, int n, int fin, const int *__restrict__ bidx, int *__restrict__ rowmap,
-                              int *__restrict__ ok) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= n) return;
+// One-hot test of a keypoint row (layer 0 of the fixed receptor encoder: kp_h is a one-hot element encoding, so the embedded keypoint
+// rows and their projections take at most fin distinct values per complex).  rowmap[v] = row of node v in the per-class table
+// (graph * fin + class); a row that is not exactly one-hot (compared by bits: one 1.0f, the rest +0.0f, so that the class row e_c is
+// the same input bit for bit) clears *ok and the forward runs the per-atom path (egnn.hip).
+__device__ __forceinline__ void kp_classify_row(const float *__restrict__ kp_h, int v, int graph, int fin, int *__restrict__ rowmap,
+                                                int *__restrict__ ok) {
     const unsigned *row = reinterpret_cast<const unsigned *>(kp_h) + (size_t)v * fin;
     int ones = 0, other = 0, c = 0;
     for (int k = 0; k < fin; ++k) {
@@ -49,8 +36,25 @@ __global__ void k_kp_classify(const float *__restrict__ kp_h, int n, int fin, co
         if (u == 0x3f800000u) { ++ones; c = k; }
         else if (u != 0u) other = 1;
     }
-    rowmap[v] = bidx[v] * fin + c;                       // always inside the table
+    rowmap[v] = graph * fin + c;                         // always inside the table
     if (ones != 1 || other) *ok = 0;
+}
+
+// bidx[i] = graph of node i.  Two riders of the EGNN forward, which launches this kernel for the ligand atoms and then for the
+// keypoints (stream order): set_ok (ligand launch) receives the bits of 1.0f, and with kp_h (keypoint launch) every row is tested for
+// one-hot and clears the same flag -- neither the flag's reset nor the test is a launch of its own.
+__global__ void k_node_graph_index(const int *__restrict__ ptr, int B, int n, int *__restrict__ bidx, int *__restrict__ set_ok,
+                                   const float *__restrict__ kp_h, int fin, int *__restrict__ rowmap, int *__restrict__ ok) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0 && set_ok) *set_ok = 0x3f800000;
+    if (i >= n) return;
+    int lo = 0, hi = B;                       // largest b with ptr[b] <= i
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (ptr[mid] <= i) lo = mid; else hi = mid;
+    }
+    bidx[i] = lo;
+    if (kp_h) kp_classify_row(kp_h, i, lo, fin, rowmap, ok);
 }
 
 // meta layout: [0..3] E per etype (ll, kl, lk, kk), [4..8] first tile of each etype (+total); the same nine
@@ -199,13 +203,12 @@ constexpr unsigned PROW_B = NSLOT * HS * 4;       // bytes of one node's row of 
 struct EdgeSmem {
     float *A;
     int *src, *dst;     // byte offsets of the endpoints' P rows (node * PROW_B)
-    int *gsrc, *gdst;   // byte offsets the gathers read: src / dst themselves, or (k_egnn_edge_kpt) the rows of the keypoint class table
+    int *gsrc, *gdst;   // byte offsets the LDS-addressed gathers read (edge_gather_issue): src / dst themselves
     float *d, *xd, *att, *mx;
     float *wv;          // [4][HS]: soft-attention row (+bias at ATT_BIAS_AT), coordinate head row, W2[256, :] of edge_mlp / coord_mlp
     int *misc;          // [0] first run continues the previous tile, [2..3] segment-end mask, [4..5] head mask
 };
 
-template <bool KPT = false>
 __device__ __forceinline__ EdgeSmem edge_smem(float *smem) {
     EdgeSmem s;
     s.A = smem;
@@ -217,8 +220,8 @@ __device__ __forceinline__ EdgeSmem edge_smem(float *smem) {
     s.mx = s.att + TM;
     s.wv = s.mx + 3 * TM;
     s.misc = reinterpret_cast<int *>(s.wv + 4 * HS);
-    s.gsrc = KPT ? s.misc + 8 + TM : s.src;      // (EDGE_KPT_LDS_BYTES)
-    s.gdst = KPT ? s.gsrc + TM : s.dst;
+    s.gsrc = s.src;
+    s.gdst = s.dst;
     return s;
 }
 
@@ -281,6 +284,71 @@ __device__ __forceinline__ void edge_gather_issue_early(EdgeGather<NW> &g, const
         const int c = lane & 3;
         g.tps = *reinterpret_cast<const f32x4 *>(ps + (ou + 16u * (64 + c)));
         g.tpd = *reinterpret_cast<const f32x4 *>(pd + (ov + 16u * (64 + c)));
+    }
+}
+
+// Scalar form of the gathers' addressing (k_egnn_edge<4> / k_egnn_edge_kpt).  A wave's RPW rows are consecutive edges at a wave-uniform
+// index, so their endpoints are scalar loads and the P-row byte offsets live in scalar registers from the top of the tile on: every
+// gather of both branches is then scalar base + one lane offset, with no per-row vector add, v_readlane or LDS read of the offset.
+// tu / tv: the per-lane offsets of columns 256.. (row lane >> 2, chunk lane & 3).  Rows past ne read the tile's last edge.
+template <int NW>
+struct EdgeRowOffs {
+    unsigned ou[TM / NW], ov[TM / NW];
+    unsigned tu, tv;
+};
+
+template <int NW>
+__device__ __forceinline__ void edge_row_offsets(EdgeRowOffs<NW> &o, const int *__restrict__ esrc, const int *__restrict__ edst, int e0, int ne,
+                                                 int wave, int lane, const int *__restrict__ maps, const int *__restrict__ mapd) {
+    constexpr int RPW = TM / NW;
+    const int *es = esrc + e0, *ed = edst + e0;
+    const int last = ne - 1;
+    int iu[RPW], iv[RPW];
+#pragma unroll
+    for (int rr = 0; rr < RPW; ++rr) {
+        const int r = min(wave * RPW + rr, last);         // (scalar: wave is wave-uniform by construction)
+        iu[rr] = es[r];
+        iv[rr] = ed[r];
+    }
+    const int rl = min(wave * RPW + ((lane >> 2) & (RPW - 1)), last);
+    int tu = es[rl], tv = ed[rl];
+    // one branch per side around all of its table lookups: a test per row made every lookup wait for its own round trip
+    if (maps) {
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) iu[rr] = maps[iu[rr]];
+        tu = maps[tu];
+    }
+    if (mapd) {
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) iv[rr] = mapd[iv[rr]];
+        tv = mapd[tv];
+    }
+#pragma unroll
+    for (int rr = 0; rr < RPW; ++rr) {
+        o.ou[rr] = (unsigned)iu[rr] * PROW_B;
+        o.ov[rr] = (unsigned)iv[rr] * PROW_B;
+    }
+    o.tu = (unsigned)tu * PROW_B + 16u * (64 + (lane & 3));
+    o.tv = (unsigned)tv * PROW_B + 16u * (64 + (lane & 3));
+}
+
+typedef __attribute__((address_space(1))) const char gchar;
+template <int NW>
+__device__ __forceinline__ void edge_gather_issue_s(EdgeGather<NW> &g, const EdgeRowOffs<NW> &o, const float *__restrict__ Ps,
+                                                    const float *__restrict__ Pd, int lane) {
+    constexpr int RPW = TM / NW;
+    gchar *ps = (gchar *)reinterpret_cast<const char *>(Ps), *pd = (gchar *)reinterpret_cast<const char *>(Pd);
+    const unsigned vo = 16u * lane;
+#pragma unroll
+    for (int rr = 0; rr < RPW; ++rr) {
+        gchar *bs = ps + o.ou[rr], *bd = pd + o.ov[rr];
+        asm volatile("" : "+s"(bs), "+s"(bd));          // (constraints only: the row bases stay in scalar registers)
+        g.ps[rr] = *reinterpret_cast<gf32x4 *>(bs + vo);
+        g.pd[rr] = *reinterpret_cast<gf32x4 *>(bd + vo);
+    }
+    if (lane < 4 * RPW && (lane & 3) < 2) {
+        g.tps = *reinterpret_cast<gf32x4 *>(ps + o.tu);
+        g.tpd = *reinterpret_cast<gf32x4 *>(pd + o.tv);
     }
 }
 
@@ -356,8 +424,8 @@ template <int NW, bool KPT>
 __device__ __forceinline__ void egnn_edge_tile(const EdgeArgs &a) {
     constexpr int TPR = NW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const EdgeSmem s = edge_smem<KPT>(smem);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const EdgeSmem s = edge_smem(smem);
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     // tile decode (XCD-aware: consecutive tiles -- neighbouring edges of one complex, which
     // share P rows -- go to the same XCD / L2)
     const int T = a.meta[8];
@@ -402,8 +470,10 @@ __device__ __forceinline__ void egnn_edge_tile(const EdgeArgs &a) {
     // the feature branch's P rows start travelling before the geometry chain and the first barrier (-1.1 % on the kernel, same-call
     // A/B: 0.859 vs 0.869 ms)
     EdgeGather<NW> ge;
-    if constexpr (KPT) {
-        if (bsel & 1) edge_gather_issue_early<NW>(ge, esrc, edst, e0, ne, Ps, Pd, wave, lane, maps, mapd);
+    [[maybe_unused]] EdgeRowOffs<NW> ro;
+    if constexpr (NW == 4) {
+        edge_row_offsets<NW>(ro, esrc, edst, e0, ne, wave, lane, maps, mapd);
+        if (bsel & 1) edge_gather_issue_s<NW>(ge, ro, Ps, Pd, lane);
     } else {
         if (bsel & 1) edge_gather_issue_early<NW>(ge, esrc, edst, e0, ne, Ps, Pd, wave, lane);
     }
@@ -414,10 +484,6 @@ __device__ __forceinline__ void egnn_edge_tile(const EdgeArgs &a) {
         const int u = esrc[e], v = edst[e];
         s.src[tid] = (int)((unsigned)u * PROW_B);        // byte offsets of the nodes' P rows
         s.dst[tid] = (int)((unsigned)v * PROW_B);
-        if constexpr (KPT) {                             // s.dst stays the node: the segmented sums divide it back into the node index
-            s.gsrc[tid] = (int)((unsigned)(maps ? maps[u] : u) * PROW_B);
-            s.gdst[tid] = (int)((unsigned)(mapd ? mapd[v] : v) * PROW_B);
-        }
         const float *xs = a.x[snt] + (size_t)u * 3, *xd = a.x[dnt] + (size_t)v * 3;
         const float dx = xs[0] - xd[0], dy = xs[1] - xd[1], dz = xs[2] - xd[2];
         const float d = sqrtf(dx * dx + dy * dy + dz * dz);
@@ -453,9 +519,10 @@ __device__ __forceinline__ void egnn_edge_tile(const EdgeArgs &a) {
     if constexpr (NW == 4) gemm_b_prefetch(bpre, (bsel & 1) ? a.wp_e[et] : a.wp_c[et], wave, lane);     // lands during the gather / A-build
     lds_barrier();
 
-    const int first_is_cont = s.misc[0];
-    const unsigned long long endmask =
-        ((unsigned long long)(unsigned)s.misc[3] << 32) | (unsigned long long)(unsigned)s.misc[2];
+    // (wave-uniform by construction: in scalar registers the run tests of the segmented sum below are scalar work)
+    const int first_is_cont = __builtin_amdgcn_readfirstlane(s.misc[0]);
+    const unsigned long long endmask = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(s.misc[3]) << 32) |
+                                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(s.misc[2]);
     f32x16 acc[2][WaveCols<NW>::NT];
     float ex;
     EdgeGather<NW == 4 ? 4 : TM> gc;      // (one row per wave, unused, in the 8-wave build)
@@ -473,7 +540,7 @@ __device__ __forceinline__ void egnn_edge_tile(const EdgeArgs &a) {
     store_T_silu_w<NW, true>(s.A, acc, ex, a.b_e[et], tid, wave, lane);
     if constexpr (NW == 4) {  // the coordinate branch's P rows start travelling now; consumed after the segmented sum below
         if (bsel & 2) {
-            edge_gather_issue<NW>(gc, s, Ps + HS, Pd + HS, wave, lane);
+            edge_gather_issue_s<NW>(gc, ro, Ps + HS, Pd + HS, lane);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -492,29 +559,23 @@ __device__ __forceinline__ void egnn_edge_tile(const EdgeArgs &a) {
     if (tid < 256) {
         float run = 0.0f;
         int piece = 0;
+        const int dall = s.dst[lane];          // row lane's destination offset: a run's end reads its row's with one v_readlane
 #pragma unroll 1
         for (int r0 = 0; r0 < TM; r0 += 16) {
             if (r0 >= ne) break;
             float v[16], w[16];
-            int dvv[16];
-            {
-                typedef int i32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const i32x4 t = *reinterpret_cast<const i32x4 *>(s.dst + r0 + 4 * j);
-                    dvv[4 * j] = t[0]; dvv[4 * j + 1] = t[1]; dvv[4 * j + 2] = t[2]; dvv[4 * j + 3] = t[3];
-                }
-            }
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 w[i] = s.att[r0 + i];
                 v[i] = s.A[(r0 + i) * SA + tid];
             }
+            const unsigned ends16 = (unsigned)(endmask >> r0);       // (scalar)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 run = fmaf(v[i], w[i], run);
-                if ((endmask >> (r0 + i)) & 1ull) {
-                    float *out = (piece == 0 && first_is_cont) ? hcont : hmain + ((unsigned)dvv[i] / (unsigned)(NSLOT * 4));
+                if (__builtin_expect((ends16 >> i) & 1u, 0)) {        // a scalar branch: the run's row base is scalar too
+                    const unsigned doff = (unsigned)__builtin_amdgcn_readlane(dall, r0 + i) / (unsigned)(NSLOT * 4);
+                    float *out = (piece == 0 && first_is_cont) ? hcont : hmain + doff;
                     out[tid] = run;
                     run = 0.0f;
                     ++piece;
@@ -530,7 +591,7 @@ __device__ __forceinline__ void egnn_edge_tile(const EdgeArgs &a) {
     // ---- coordinate messages: msg_x = tanh(coord_mlp(f)) * x_diff * range (dynamics.py:113-120)
     if (bsel & 2) {
     if constexpr (NW == 4) {
-        if (!(bsel & 1)) edge_gather_issue<NW>(gc, s, Ps + HS, Pd + HS, wave, lane);        // (a coordinate-only work item of the tail)
+        if (!(bsel & 1)) edge_gather_issue_s<NW>(gc, ro, Ps + HS, Pd + HS, lane);        // (a coordinate-only work item of the tail)
         edge_gather_finish<NW>(gc, s, a.wr_c[et], wave, lane);
     } else build_edge_A<NW>(s, Ps + HS, Pd + HS, a.wr_c[et], wave, lane);
     lds_barrier();
@@ -1685,7 +1746,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
                     }
                 }
                 float *xv = a.x + (size_t)v * 3;
-                xv[0] += sx / z; xv[1] += sy / z; xv[2] += sz / z;
+                const float *xi = (a.x_in ? a.x_in : a.x) + (size_t)v * 3;      // (layer 0 reads the caller's coordinates)
+                xv[0] = xi[0] + sx / z; xv[1] = xi[1] + sy / z; xv[2] = xi[2] + sz / z;
             }
             s_z[tid] = z;
         } else if (tid >= 512 - 3 * 66) {
@@ -1912,7 +1974,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 6))) voi
                 }
             }
             float *xv = a.x + (size_t)v * 3;
-            xv[0] += sx / z; xv[1] += sy / z; xv[2] += sz / z;
+            const float *xi = (a.x_in ? a.x_in : a.x) + (size_t)v * 3;      // (layer 0 reads the caller's coordinates)
+            xv[0] = xi[0] + sx / z; xv[1] = xi[1] + sy / z; xv[2] = xi[2] + sz / z;
         }
         s_z[tid] = z;
     }
@@ -2046,9 +2109,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 6))) voi
 // kept for the engines' create paths: everything it used to do now happens per (kernel, device) at launch time
 kpd_status egnn_kernels_init() { return KPD_OK; }
 
-kpd_status launch_node_graph_index(const int *ptr, int B, int n, int *bidx, hipStream_t st) {
+kpd_status launch_node_graph_index(const int *ptr, int B, int n, int *bidx, hipStream_t st, int *set_ok, const float *kp_h, int fin,
+                                   int *rowmap, int *ok) {
     if (n == 0) return KPD_OK;
-    hipLaunchKernelGGL(k_node_graph_index, dim3(cdiv(n, 256)), dim3(256), 0, st, ptr, B, n, bidx);
+    KPD_REQUIRE(!kp_h || (fin > 0 && rowmap && ok), KPD_ERR_INVALID, "node graph index: one-hot test without its outputs");
+    hipLaunchKernelGGL(k_node_graph_index, dim3(cdiv(n, 256)), dim3(256), 0, st, ptr, B, n, bidx, set_ok, kp_h, fin, rowmap, ok);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
 }
@@ -2072,13 +2137,6 @@ kpd_status launch_embed(const float *in, int n, int fin, const float *W0, const 
     else
         hipLaunchKernelGGL(k_embed<512>, dim3(cdiv(n, EMB_NODES)), dim3(256), 0, st, in, n, fin, W0, b0, hid, W1t, b1, t, bidx,
                            out, identity);
-    KPD_LAUNCH_CHECK();
-    return KPD_OK;
-}
-
-kpd_status launch_kp_classify(const float *kp_h, int n, int fin, const int *bidx, int *rowmap, int *ok, hipStream_t st) {
-    if (n == 0) return KPD_OK;
-    hipLaunchKernelGGL(k_kp_classify, dim3(cdiv(n, 256)), dim3(256), 0, st, kp_h, n, fin, bidx, rowmap, ok);
     KPD_LAUNCH_CHECK();
     return KPD_OK;
 }
@@ -2115,8 +2173,8 @@ kpd_status launch_egnn_edge(const EdgeArgs &a, int tile_cap, hipStream_t st) {
     b.split_slots = 2 * cu_count() / 8;
     if (a.kp_ok) {
         KPD_REQUIRE(a.PT && a.rowmap, KPD_ERR_INVALID, "edge launch: keypoint class table without its rows or row map");
-        KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_egnn_edge_kpt), EDGE_KPT_LDS_BYTES));
-        hipLaunchKernelGGL(k_egnn_edge_kpt, dim3(8 * (cdiv(tile_cap, 8) + b.split_slots / 2)), dim3(256), EDGE_KPT_LDS_BYTES, st, b);
+        KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_egnn_edge_kpt), EDGE_LDS_BYTES));
+        hipLaunchKernelGGL(k_egnn_edge_kpt, dim3(8 * (cdiv(tile_cap, 8) + b.split_slots / 2)), dim3(256), EDGE_LDS_BYTES, st, b);
         KPD_LAUNCH_CHECK();
         return KPD_OK;
     }

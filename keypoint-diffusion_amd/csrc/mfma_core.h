@@ -614,14 +614,15 @@ __device__ __forceinline__ float silu_pre_x64(float xs) {
 template <int TPR>
 __device__ __forceinline__ float row_dot_chunks(const float *__restrict__ T, const float *__restrict__ w, int chunks, int tid) {
     const int row = tid / TPR, q = tid % TPR;
-    const f32x4 *a = reinterpret_cast<const f32x4 *>(T + row * SA);
-    const f32x4 *wv = reinterpret_cast<const f32x4 *>(w);
+    // one base per lane and operand, the chunk index as an immediate (as a[q + TPR i] every chunk cost an or + shift-add for its address)
+    const f32x4 *a = reinterpret_cast<const f32x4 *>(T + row * SA) + q;
+    const f32x4 *wv = reinterpret_cast<const f32x4 *>(w) + q;
     float s = 0.0f;
 #pragma unroll
     for (int i = 0; i < (66 + TPR - 1) / TPR; ++i) {
         const int c = q + TPR * i;
         if (c < chunks) {
-            const f32x4 av = a[c], wq = wv[c];
+            const f32x4 av = a[TPR * i], wq = wv[TPR * i];
             s = fmaf(av[0], wq[0], s);
             s = fmaf(av[1], wq[1], s);
             s = fmaf(av[2], wq[2], s);
