@@ -91,8 +91,7 @@ k_mol_perceive(const float *__restrict__ pos, const float *__restrict__ feat, co
             cls[k] = c;
             elem[g] = c;
             unsigned row = element_row(zs[c]);
-            const float big = __builtin_inff();
-            const bool finite = fabsf(x) < big && fabsf(y) < big && fabsf(z) < big;        // false for NaN too
+            const bool finite = finite_f(x) && finite_f(y) && finite_f(z);
             if (!row || !finite) st = MOL_BAD_ATOM;
             if (!finite) row &= 0xff000000u;
             el[a] = row;
@@ -388,6 +387,7 @@ k_sdf_size(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n
     if (!flags) {
         p0 = bond_ptr[b];
         p1 = bond_ptr[b + 1];
+        // not mol_bond_range: a ligand without bonds has a block (atoms only) even where its empty range lies beyond cap_bonds
         if (p0 < 0 || p1 < p0 || (p1 > p0 && p1 > cap_bonds) || p1 - p0 > 3 * MOL_MAX) flags = SDF_NO_MOLECULE;
     }
     if (flags) {                                    // block-uniform
@@ -407,7 +407,7 @@ k_sdf_size(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n
         const size_t g = (size_t)(a0 + tid);
         for (int c = 0; c < 3; ++c) {
             const float v = pos[g * 3 + c];
-            if (!(fabsf(v) < __builtin_inff())) flags |= SDF_NONFINITE;
+            if (!finite_f(v)) flags |= SDF_NONFINITE;
             else if (width_f4(v) > 10) flags |= SDF_WIDE;
         }
         f = frag[g];

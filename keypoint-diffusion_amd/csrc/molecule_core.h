@@ -1,7 +1,12 @@
 // What the molecule kernels share (molecule.hip: perception and SDF text; molset.hip: keys, fingerprints, diversity): the size
-// limits of one ligand, the element table, the status bits of kpd_mol_perceive and the segment check.
+// limits of one ligand, the element table, the status bits of kpd_mol_perceive, the segment and bond-range checks.
 // relax.hip reads the same table for its rest lengths; vina.hip types pocket atoms by the same distance recipe and step-1 / step-3 tests.
+// relax.hip and vina.hip also share everything that means "one workgroup takes one perceived ligand and its pocket" (the second
+// half of this file): the device front end with status bits 0 and 1, the two-vote epilogue of the staging loops, the LDS carving,
+// and on the host the argument check and the number of staged pocket rows.  pocket.hip takes the segment check alone.
 #pragma once
+#include <algorithm>
+
 #include "common.h"
 
 namespace kpd {
@@ -9,6 +14,7 @@ namespace kpd {
 constexpr int MOL_MAX = 256;            // atoms of one ligand
 constexpr int MOL_W = MOL_MAX / 32;     // words of one row of a bit matrix
 constexpr int MOL_K = MOL_MAX / 64;     // atoms per lane
+constexpr int MOL_DEG = 6;              // neighbours of one atom: the largest valence cap of the bond rule
 
 enum : int { MOL_EMPTY = 1, MOL_CAPACITY = 2, MOL_BAD_ATOM = 4, MOL_BAD_SEGMENT = 8 };
 
@@ -51,16 +57,95 @@ __device__ __forceinline__ bool within(double d2, unsigned ri, unsigned rj, int 
     return d2 <= (double)(T * T) * 1e-4;
 }
 
+// rows [a0, a1) of entry b, or false if the segment table is malformed (nothing of that entry is then touched)
 __device__ __forceinline__ bool mol_segment(const int *__restrict__ ptr, int b, int n, int &a0, int &a1) {
     a0 = ptr[b];
     a1 = ptr[b + 1];
     return a0 >= 0 && a1 >= a0 && a1 <= n;
 }
 
+// bonds [p0, p1) of ligand b, or false if the range is malformed, ends beyond cap_bonds or holds more bonds than MOL_MAX atoms can have
+__device__ __forceinline__ bool mol_bond_range(const int *__restrict__ bond_ptr, int b, int cap_bonds, int &p0, int &p1) {
+    p0 = bond_ptr[b];
+    p1 = bond_ptr[b + 1];
+    return p0 >= 0 && p1 >= p0 && p1 <= cap_bonds && p1 - p0 <= 3 * MOL_MAX;
+}
+
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
     for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
     return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {      // a butterfly: the same bits on every lane
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }      // false for NaN too
+
+// ---- one workgroup takes one perceived ligand and its pocket (kpd_relax, kpd_vina_score) ---------------------------------
+enum : int { LP_NO_MOLECULE = 1, LP_BAD_INPUT = 2 };     // bits 0 and 1 of both status words
+
+// the ligand's n atoms [a0, a1) (to be used only where seg: lig_ptr was well-formed), its bonds [p0, p1), the np atoms of its pocket from q0
+struct LigandInPocket {
+    int a0, a1, n, p0, p1, q0, np;
+    bool seg;
+};
+
+// Fills s for ligand b; returns 0, LP_NO_MOLECULE (bad or empty segment, more than nm atoms, left out by perception, bad bond
+// range) or LP_BAD_INPUT (pocket_of or its pocket_ptr range out of bounds).  Block-uniform; nothing is read behind a failed check.
+__device__ __forceinline__ int ligand_in_pocket(const int *__restrict__ lig_ptr, int b, int n_atoms, int nm,
+                                                const int *__restrict__ bond_ptr, int cap_bonds, const int *__restrict__ mol_status,
+                                                const int *__restrict__ pocket_of, const int *__restrict__ pocket_ptr, int n_pocket,
+                                                int n_pockets, LigandInPocket &s) {
+    s.seg = mol_segment(lig_ptr, b, n_atoms, s.a0, s.a1);
+    s.n = s.a1 - s.a0;
+    s.p0 = s.p1 = s.q0 = s.np = 0;
+    if (!s.seg || s.n <= 0 || s.n > MOL_MAX || s.n > nm || (mol_status[b] & (MOL_EMPTY | MOL_CAPACITY | MOL_BAD_SEGMENT))) return LP_NO_MOLECULE;
+    if (!mol_bond_range(bond_ptr, b, cap_bonds, s.p0, s.p1)) return LP_NO_MOLECULE;
+    const int po = pocket_of[b];
+    if (po < -1 || po >= n_pockets) return LP_BAD_INPUT;
+    if (po >= 0) {
+        s.q0 = pocket_ptr[po];
+        const int q1 = pocket_ptr[po + 1];
+        if (s.q0 < 0 || q1 < s.q0 || q1 > n_pocket) return LP_BAD_INPUT;
+        s.np = q1 - s.q0;
+    }
+    return 0;
+}
+
+// what the threads of a workgroup found while staging atoms and pocket -> its status: two votes, not a sum (and a barrier)
+__device__ __forceinline__ int lp_votes(int bad) {
+    const int no_mol = __syncthreads_or(bad & LP_NO_MOLECULE), bad_in = __syncthreads_or(bad & LP_BAD_INPUT);
+    return no_mol ? LP_NO_MOLECULE : bad_in ? LP_BAD_INPUT : 0;
+}
+
+// carves `bytes`, rounded up to `align` (a power of two), off an LDS layout that has grown to o; returns where they start
+__host__ __device__ inline size_t lds_take(size_t &o, size_t bytes, size_t align) {
+    const size_t at = o;
+    o += (bytes + align - 1) & ~(align - 1);
+    return at;
+}
+
+// ---- the host side: the arguments kpd_relax and kpd_vina_score share; every *_ok is the caller's "none of these is null"
+static inline kpd_status ligand_pocket_args(int n_atoms, int B, int max_atoms, int F, int cap_bonds, int n_pocket, int P, int max_pocket,
+                                            bool tables_ok, bool atoms_ok, bool ligands_ok, bool bonds_ok, bool pocket_ptr_ok,
+                                            bool pocket_ok) {
+    KPD_REQUIRE(n_atoms >= 0 && B >= 0 && F >= 1 && cap_bonds >= 0 && n_pocket >= 0 && P >= 0 && max_pocket >= 0, KPD_ERR_INVALID,
+                "n_atoms=%d B=%d F=%d cap_bonds=%d n_pocket=%d P=%d max_pocket=%d", n_atoms, B, F, cap_bonds, n_pocket, P, max_pocket);
+    KPD_REQUIRE(max_atoms >= 1 && max_atoms <= MOL_MAX, KPD_ERR_INVALID, "max_atoms=%d (1 .. %d)", max_atoms, MOL_MAX);
+    KPD_REQUIRE(tables_ok && (!n_atoms || atoms_ok) && (!B || ligands_ok), KPD_ERR_INVALID, "null argument");
+    KPD_REQUIRE(!cap_bonds || bonds_ok, KPD_ERR_INVALID, "null bond buffer");
+    KPD_REQUIRE(!P || pocket_ptr_ok, KPD_ERR_INVALID, "null pocket_ptr");
+    KPD_REQUIRE(!n_pocket || pocket_ok, KPD_ERR_INVALID, "null pocket buffer");
+    return KPD_OK;
+}
+
+// as much of the largest pocket as fits beside the `fixed` bytes of a max_atoms ligand, in rows; -1 if that ligand does not fit
+static inline int stage_rows(size_t fixed, size_t lds_budget, size_t row_bytes, int max_pocket) {
+    if (fixed + 64 > lds_budget) return -1;
+    return (int)std::min<size_t>((size_t)max_pocket, (lds_budget - 64 - fixed) / row_bytes);
 }
 
 }  // namespace kpd

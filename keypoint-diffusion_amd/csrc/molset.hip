@@ -15,7 +15,6 @@ namespace kpd {
 typedef unsigned long long u64;
 
 constexpr u64 MS_K1 = 0x9E3779B97F4A7C15ull, MS_K2 = 0xC2B2AE3D27D4EB4Full, MS_K3 = 0x165667B19E3779F9ull;
-constexpr int MS_DEG = 6;               // neighbours of one atom: the largest valence cap of the bond rule
 constexpr int MS_ROW = MOL_W + 1;       // padded adjacency row: in the BFS every lane walks rows of its own
 constexpr int MS_FAR = 65535;           // d(a, b) of an atom that cannot be reached
 constexpr int MS_FP_WORDS = 128;        // nbits <= 4096
@@ -48,7 +47,7 @@ __device__ __forceinline__ int wave_max(int v) {
 __device__ __forceinline__ u64 refine(const u64 *x, const unsigned short *nbr, int deg, int a) {
     u64 s = MS_K1 * x[a];
     for (int k = 0; k < deg; ++k) {
-        const unsigned e = nbr[a * MS_DEG + k];
+        const unsigned e = nbr[a * MOL_DEG + k];
         s += mix(x[e & 0xffu] + (u64)(e >> 8) * MS_K2);
     }
     return mix(s);
@@ -72,7 +71,7 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
     __shared__ int zv[MOL_MAX];                     // Z
     __shared__ int deg[MOL_MAX];
     __shared__ int fsize[MOL_MAX];
-    __shared__ unsigned short nbr[MOL_MAX * MS_DEG];
+    __shared__ unsigned short nbr[MOL_MAX * MOL_DEG];
     __shared__ unsigned inS[MOL_W];
     __shared__ unsigned row[MS_FP_WORDS];
     __shared__ int bad;
@@ -82,11 +81,7 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
     const int n = a1 - a0;
     ok = ok && n > 0 && n <= MOL_MAX && !(mol_status[b] & (MOL_EMPTY | MOL_CAPACITY | MOL_BAD_SEGMENT));
     int p0 = 0, p1 = 0;
-    if (ok) {
-        p0 = bond_ptr[b];
-        p1 = bond_ptr[b + 1];
-        ok = p0 >= 0 && p1 >= p0 && p1 <= cap_bonds && p1 - p0 <= 3 * MOL_MAX;
-    }
+    ok = ok && mol_bond_range(bond_ptr, b, cap_bonds, p0, p1);
     unsigned *out_row = fp + (size_t)b * nwords;
     if (ok) {                                       // wave-uniform, as every `ok` below
 #pragma unroll
@@ -156,12 +151,12 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
                 const unsigned was = atomicOr(&A[i * MS_ROW + (j >> 5)], 1u << (j & 31));
                 atomicOr(&A[j * MS_ROW + (i >> 5)], 1u << (i & 31));
                 const int si = atomicAdd(&deg[i], 1), sj = atomicAdd(&deg[j], 1);
-                if (((was >> (j & 31)) & 1u) || si >= MS_DEG || sj >= MS_DEG) {          // a bond twice, or a seventh neighbour
+                if (((was >> (j & 31)) & 1u) || si >= MOL_DEG || sj >= MOL_DEG) {          // a bond twice, or a seventh neighbour
                     atomicOr(&bad, 1);
                     continue;
                 }
-                nbr[i * MS_DEG + si] = (unsigned short)((unsigned)j | l << 8);
-                nbr[j * MS_DEG + sj] = (unsigned short)((unsigned)i | l << 8);
+                nbr[i * MOL_DEG + si] = (unsigned short)((unsigned)j | l << 8);
+                nbr[j * MOL_DEG + sj] = (unsigned short)((unsigned)i | l << 8);
             }
             __syncthreads();
             ok = !bad && nS > 0;

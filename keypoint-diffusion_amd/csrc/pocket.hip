@@ -7,6 +7,7 @@
 // complexes, there are no float atomics, and results are bitwise independent of batch composition.
 #include "common.h"
 #include "engine.h"
+#include "molecule_core.h"
 #include "scan_core.h"
 
 namespace kpd {
@@ -17,13 +18,6 @@ constexpr int IP_ITEMS = 4;             // (ligand, receptor) pairs per thread a
 constexpr int IP_MAX_POINTS = 4096;     // interface points of one complex held in LDS while thinning
 
 enum : int { PK_EMPTY = 1, PK_CAPACITY = 2, PK_BAD_RES = 4, PK_BAD_SEGMENT = 8 };
-
-// rows [a0, a1) of complex b, or false if the segment table is malformed (nothing of that complex is then touched)
-__device__ __forceinline__ bool segment(const int *__restrict__ ptr, int b, int n, int &a0, int &a1) {
-    a0 = ptr[b];
-    a1 = ptr[b + 1];
-    return a0 >= 0 && a1 >= a0 && a1 <= n;
-}
 
 // ligand of the complex into LDS; returns its size, or -1 if it does not fit
 __device__ __forceinline__ int load_ligand(const float *__restrict__ lig_x, int l0, int l1, float *lig) {
@@ -54,7 +48,7 @@ k_pocket_mark(const float *__restrict__ rec_x, const int *__restrict__ rec_ptr, 
     __shared__ float red[PK_THREADS / 64][6];
     const int b = blockIdx.x, tid = threadIdx.x;
     int a0, a1, l0, l1;
-    const bool ok = segment(rec_ptr, b, n_rec, a0, a1) && segment(lig_ptr, b, n_lig, l0, l1);
+    const bool ok = mol_segment(rec_ptr, b, n_rec, a0, a1) && mol_segment(lig_ptr, b, n_lig, l0, l1);
     if (!ok || l1 - l0 > PK_MAX_LIG) {
         if (tid == 0 && blockIdx.y == 0) atomicOr(status + b, PK_BAD_SEGMENT);
         return;
@@ -137,7 +131,7 @@ k_pocket_count(const int *__restrict__ rec_ptr, int n_rec, const int *__restrict
     __shared__ int part[PK_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
     int a0, a1;
-    if (!segment(rec_ptr, b, n_rec, a0, a1) || (status[b] & PK_BAD_SEGMENT)) {
+    if (!mol_segment(rec_ptr, b, n_rec, a0, a1) || (status[b] & PK_BAD_SEGMENT)) {
         if (tid == 0) cnt[b] = 0;
         return;
     }
@@ -167,7 +161,7 @@ k_pocket_compact(const int *__restrict__ rec_ptr, int n_rec, const int *__restri
     __shared__ int part[PK_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
     int a0, a1;
-    if (!segment(rec_ptr, b, n_rec, a0, a1) || (status[b] & PK_BAD_SEGMENT)) return;
+    if (!mol_segment(rec_ptr, b, n_rec, a0, a1) || (status[b] & PK_BAD_SEGMENT)) return;
     const int p0 = pocket_ptr[b], p1 = pocket_ptr[b + 1];
     if (p1 > cap_rows) {
         if (tid == 0 && p1 > p0) atomicOr(status + b, PK_CAPACITY);
@@ -205,7 +199,7 @@ k_ip_select(const float *__restrict__ rec_x, const int *__restrict__ rec_ptr, in
     __shared__ int wfirst[PK_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     int a0, a1, l0, l1;
-    const bool ok = segment(rec_ptr, b, n_rec, a0, a1) && segment(lig_ptr, b, n_lig, l0, l1);
+    const bool ok = mol_segment(rec_ptr, b, n_rec, a0, a1) && mol_segment(lig_ptr, b, n_lig, l0, l1);
     if (!ok || l1 - l0 > PK_MAX_LIG) {
         if (tid == 0) {
             status[b] = PK_BAD_SEGMENT;

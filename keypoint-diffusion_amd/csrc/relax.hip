@@ -10,8 +10,6 @@
 // its lanes stride the pocket atoms, then the ligand atoms, take one bond or angle each, and meet in a butterfly; every dot product
 // meets in the same fixed tree.  Nothing is shared between ligands, no atomics on floats, no host synchronisation: a ligand's result
 // is bitwise independent of the batch, of what was staged, and of the repeat.
-#include <algorithm>
-
 #include "common.h"
 #include "molecule_core.h"
 
@@ -19,13 +17,12 @@ namespace kpd {
 
 constexpr int RX_T = 256;                // threads of a workgroup
 constexpr int RX_M = 8;                  // stored correction pairs
-constexpr int RX_DEG = 6;                // neighbours of one atom (the largest valence cap of the bond rule)
 constexpr int RX_LDS = 160 * 1024 - 512;  // LDS of one CU, less the few static bytes the compiler adds for the block-wide votes
 constexpr int RX_POCKET_ROW = 28;        // staged pocket atom: 3 floats, 2 doubles
 constexpr double RX_COS100 = -0.1736481776669303, RX_COS150 = -0.8660254037844387, RX_COS114 = -0.4184314830435483;
 constexpr double RX_COS_TET = -0.3333333228927115;        // cos 109.47122 deg
 
-enum : int { RX_NO_MOLECULE = 1, RX_BAD_INPUT = 2, RX_ITER_CAP = 4, RX_LINE_SEARCH = 8 };
+enum : int { RX_ITER_CAP = 4, RX_LINE_SEARCH = 8 };      // status bits 2 and 3; bits 0 and 1 are LP_NO_MOLECULE and LP_BAD_INPUT
 
 struct RelaxP {
     double k_b, k_a, rc2, inv_rc2, s, ce, cf, w_intra, gtol, max_step;
@@ -42,11 +39,7 @@ __host__ __device__ inline RelaxLayout relax_layout(int nm, int stage) {
     RelaxLayout L;
     L.W = (nm + 31) / 32;
     size_t o = 0;
-    auto take = [&o](size_t bytes) {
-        const size_t at = o;
-        o += (bytes + 7) & ~(size_t)7;
-        return at;
-    };
+    auto take = [&o](size_t bytes) { return lds_take(o, bytes, 8); };
     L.vec = take((size_t)(5 + 2 * RX_M) * 3 * nm * 8);       // x, g, p, xt, gt, S[8], Y[8]
     L.sx = take((size_t)nm * 8);
     L.sD = take((size_t)nm * 8);
@@ -61,8 +54,8 @@ __host__ __device__ inline RelaxLayout relax_layout(int nm, int stage) {
     L.excl = take((size_t)nm * L.W * 4);
     L.acls = take((size_t)nm * 4);
     L.deg = take((size_t)nm * 4);
-    L.r0h = take((size_t)nm * RX_DEG * 2);
-    L.nbr = take((size_t)nm * RX_DEG);
+    L.r0h = take((size_t)nm * MOL_DEG * 2);
+    L.nbr = take((size_t)nm * MOL_DEG);
     L.bytes = o;
     return L;
 }
@@ -80,12 +73,6 @@ struct RelaxCtx {
     RelaxP P;
 };
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 __device__ __forceinline__ double wave_max_d(double v) {
 #pragma unroll
     for (int off = 32; off; off >>= 1) v = fmax(v, __shfl_xor(v, off));
@@ -97,7 +84,7 @@ __device__ __forceinline__ double wave_max_d(double v) {
 __device__ __forceinline__ double block_dot(const double *a, const double *b, int N3, double *red, int tid) {
     double v = 0.0;
     for (int k = tid; k < N3; k += RX_T) v += a[k] * b[k];
-    v = wave_sum_d(v);
+    v = wave_sum(v);
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     const double r = ((red[0] + red[1]) + red[2]) + red[3];
@@ -137,13 +124,13 @@ __device__ __forceinline__ void lj_pair(double d2, double xij, double Dij, const
 // slots (a, b), a < b < 6, of pair q = 0 .. 14 of a neighbour list, and back
 __device__ __forceinline__ void pair_slots(int q, int &a, int &b) {
     a = 0;
-    while (q >= RX_DEG - 1 - a) {
-        q -= RX_DEG - 1 - a;
+    while (q >= MOL_DEG - 1 - a) {
+        q -= MOL_DEG - 1 - a;
         ++a;
     }
     b = a + 1 + q;
 }
-__device__ __forceinline__ int pair_index(int a, int b) { return a * (2 * RX_DEG - 1 - a) / 2 + b - a - 1; }
+__device__ __forceinline__ int pair_index(int a, int b) { return a * (2 * MOL_DEG - 1 - a) / 2 + b - a - 1; }
 
 // cosine of the angle a - c - b in the coordinates v (double or the fp32 input); false if an arm is shorter than 1e-6
 template <typename T>
@@ -230,9 +217,9 @@ __device__ void relax_eval(const RelaxCtx &C, const double *xq, double *gq, int 
         }
         const int di = C.deg[i];
         if (lane < di) {                            // one bond per lane
-            const int j = C.nbr[i * RX_DEG + lane];
+            const int j = C.nbr[i * MOL_DEG + lane];
             const double dx = xi - xq[3 * j], dy = yi - xq[3 * j + 1], dz = zi - xq[3 * j + 2];
-            const double d = sqrt(dx * dx + dy * dy + dz * dz), dl = d - 0.005 * (double)C.r0h[i * RX_DEG + lane];
+            const double d = sqrt(dx * dx + dy * dy + dz * dz), dl = d - 0.005 * (double)C.r0h[i * MOL_DEG + lane];
             if (i < j) eb += 0.5 * C.P.k_b * dl * dl;
             if (d >= 1e-6) {
                 const double k = C.P.k_b * dl / d;
@@ -245,28 +232,28 @@ __device__ void relax_eval(const RelaxCtx &C, const double *xq, double *gq, int 
             int a, b;
             pair_slots(lane, a, b);
             if (b < di)
-                ea += angle_term(C, xq, C.nbr[i * RX_DEG + a], i, C.nbr[i * RX_DEG + b], (C.acls[i] >> (2 * lane)) & 3u, true, gx, gy, gz);
+                ea += angle_term(C, xq, C.nbr[i * MOL_DEG + a], i, C.nbr[i * MOL_DEG + b], (C.acls[i] >> (2 * lane)) & 3u, true, gx, gy, gz);
         } else if (lane < 45) {                     // the angles i is an end of: neighbour s of i, its t-th other neighbour
             const int s = (lane - 15) / 5, t = (lane - 15) % 5;
             if (s < di) {
-                const int c = C.nbr[i * RX_DEG + s], dc = C.deg[c];
+                const int c = C.nbr[i * MOL_DEG + s], dc = C.deg[c];
                 int at = 0;
-                while (at < dc && C.nbr[c * RX_DEG + at] != i) ++at;
+                while (at < dc && C.nbr[c * MOL_DEG + at] != i) ++at;
                 const int o = t < at ? t : t + 1;
                 if (at < dc && o < dc) {
                     const unsigned cls = (C.acls[c] >> (2 * pair_index(min(at, o), max(at, o)))) & 3u;
-                    double unused = angle_term(C, xq, i, c, C.nbr[c * RX_DEG + o], cls, false, gx, gy, gz);
+                    double unused = angle_term(C, xq, i, c, C.nbr[c * MOL_DEG + o], cls, false, gx, gy, gz);
                     (void)unused;
                 }
             }
         }
-        gx = wave_sum_d(gx);
-        gy = wave_sum_d(gy);
-        gz = wave_sum_d(gz);
-        eb = wave_sum_d(eb);
-        ea = wave_sum_d(ea);
-        ei = wave_sum_d(ei);
-        ep = wave_sum_d(ep);
+        gx = wave_sum(gx);
+        gy = wave_sum(gy);
+        gz = wave_sum(gz);
+        eb = wave_sum(eb);
+        ea = wave_sum(ea);
+        ei = wave_sum(ei);
+        ep = wave_sum(ep);
         if (lane == 0) {
             gq[3 * i] = gx;
             gq[3 * i + 1] = gy;
@@ -286,7 +273,7 @@ __device__ void relax_eval(const RelaxCtx &C, const double *xq, double *gq, int 
             gm = fmax(gm, sqrt(gq[3 * i] * gq[3 * i] + gq[3 * i + 1] * gq[3 * i + 1] + gq[3 * i + 2] * gq[3 * i + 2]));
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) part[k] = wave_sum_d(part[k]);
+        for (int k = 0; k < 4; ++k) part[k] = wave_sum(part[k]);
         gm = wave_max_d(gm);
         if (lane == 0) {
 #pragma unroll
@@ -297,8 +284,6 @@ __device__ void relax_eval(const RelaxCtx &C, const double *xq, double *gq, int 
     }
     __syncthreads();
 }
-
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }
 
 __global__ void __launch_bounds__(RX_T)
 k_relax(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_atoms, int nm, const int *__restrict__ elem, int F,
@@ -323,30 +308,10 @@ k_relax(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_at
     unsigned short *r0h = reinterpret_cast<unsigned short *>(lds + L.r0h);
     unsigned char *nbr = reinterpret_cast<unsigned char *>(lds + L.nbr);
 
-    // ---- is there a molecule (bit 0)?  Every `st` below is block-uniform.
-    int a0, a1, st = 0;
-    const bool seg = mol_segment(lig_ptr, b, n_atoms, a0, a1);
-    const int n = a1 - a0;
-    int p0 = 0, p1 = 0;
-    if (!seg || n <= 0 || n > MOL_MAX || n > nm || (mol_status[b] & (MOL_EMPTY | MOL_CAPACITY | MOL_BAD_SEGMENT))) st = RX_NO_MOLECULE;
-    if (!st) {
-        p0 = bond_ptr[b];
-        p1 = bond_ptr[b + 1];
-        if (p0 < 0 || p1 < p0 || p1 > cap_bonds || p1 - p0 > 3 * MOL_MAX) st = RX_NO_MOLECULE;
-    }
-    // ---- its pocket (bit 1)
-    int np = 0, q0 = 0;
-    if (!st) {
-        const int po = pocket_of[b];
-        if (po < -1 || po >= n_pockets) {
-            st = RX_BAD_INPUT;
-        } else if (po >= 0) {
-            q0 = pocket_ptr[po];
-            const int q1 = pocket_ptr[po + 1];
-            if (q0 < 0 || q1 < q0 || q1 > n_pocket) st = RX_BAD_INPUT;
-            else np = q1 - q0;
-        }
-    }
+    // ---- is there a molecule (bit 0), and its pocket (bit 1)?  Every `st` below is block-uniform.
+    LigandInPocket lp;
+    int st = ligand_in_pocket(lig_ptr, b, n_atoms, nm, bond_ptr, cap_bonds, mol_status, pocket_of, pocket_ptr, n_pocket, n_pockets, lp);
+    const int a0 = lp.a0, n = lp.n, p0 = lp.p0, p1 = lp.p1, q0 = lp.q0, np = lp.np;
     if (!st) {
         int bad = 0;
         for (int a = tid; a < n; a += RX_T) {
@@ -355,16 +320,16 @@ k_relax(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_at
             const size_t ga = (size_t)(a0 + a);
             const int e = elem[ga];
             if (e < 0 || e >= F) {
-                bad |= RX_NO_MOLECULE;
+                bad |= LP_NO_MOLECULE;
                 continue;
             }
             const float vx = lig_vdw[2 * e], vD = lig_vdw[2 * e + 1];
-            if (!(finite_f(vx) && finite_f(vD) && vx > 0.0f && vD >= 0.0f)) bad |= RX_BAD_INPUT;
+            if (!(finite_f(vx) && finite_f(vD) && vx > 0.0f && vD >= 0.0f)) bad |= LP_BAD_INPUT;
             sx[a] = sqrt((double)vx);
             sD[a] = sqrt((double)vD);
             for (int k = 0; k < 3; ++k) {
                 const float v = pos[ga * 3 + k];
-                if (!finite_f(v)) bad |= RX_BAD_INPUT;
+                if (!finite_f(v)) bad |= LP_BAD_INPUT;
                 x0[3 * a + k] = v;
                 x[3 * a + k] = (double)v;
             }
@@ -373,7 +338,7 @@ k_relax(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_at
         for (int j = tid; j < np; j += RX_T) {       // every pocket atom is checked, the first `stage` are kept
             const float *r = pocket_x + (size_t)(q0 + j) * 3, *v = pocket_vdw + (size_t)(q0 + j) * 2;
             if (!(finite_f(r[0]) && finite_f(r[1]) && finite_f(r[2]) && finite_f(v[0]) && finite_f(v[1]) && v[0] > 0.0f && v[1] >= 0.0f))
-                bad |= RX_BAD_INPUT;
+                bad |= LP_BAD_INPUT;
             if (j < stage) {
                 px[3 * j] = r[0];
                 px[3 * j + 1] = r[1];
@@ -382,8 +347,7 @@ k_relax(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_at
                 psD[j] = sqrt((double)v[1]);
             }
         }
-        const int no_mol = __syncthreads_or(bad & RX_NO_MOLECULE), bad_in = __syncthreads_or(bad & RX_BAD_INPUT);     // votes, not sums
-        st = no_mol ? RX_NO_MOLECULE : bad_in ? RX_BAD_INPUT : 0;
+        st = lp_votes(bad);
     }
     if (!st) {                                       // neighbour lists from the bond list
         int bad = 0;
@@ -394,20 +358,20 @@ k_relax(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_at
                 continue;
             }
             const int si = atomicAdd(&deg[i], 1), sj = atomicAdd(&deg[j], 1);
-            if (si >= RX_DEG || sj >= RX_DEG) {      // a seventh neighbour
+            if (si >= MOL_DEG || sj >= MOL_DEG) {      // a seventh neighbour
                 bad = 1;
                 continue;
             }
-            nbr[i * RX_DEG + si] = (unsigned char)j;
-            nbr[j * RX_DEG + sj] = (unsigned char)i;
+            nbr[i * MOL_DEG + si] = (unsigned char)j;
+            nbr[j * MOL_DEG + sj] = (unsigned char)i;
         }
-        st = __syncthreads_or(bad) ? RX_NO_MOLECULE : 0;
+        st = __syncthreads_or(bad) ? LP_NO_MOLECULE : 0;
     }
     if (!st) {                                       // sorted lists (the atomics above have no order), rest lengths
         int bad = 0;
         for (int i = tid; i < n; i += RX_T) {
             const int di = deg[i];
-            unsigned char *l = nbr + i * RX_DEG;
+            unsigned char *l = nbr + i * MOL_DEG;
             for (int a = 1; a < di; ++a)
                 for (int c = a; c > 0 && l[c - 1] > l[c]; --c) {
                     const unsigned char t = l[c];
@@ -441,10 +405,10 @@ k_relax(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_at
                         bd = off;
                     }
                 }
-                r0h[i * RX_DEG + a] = (unsigned short)best;
+                r0h[i * MOL_DEG + a] = (unsigned short)best;
             }
         }
-        st = __syncthreads_or(bad) ? RX_NO_MOLECULE : 0;
+        st = __syncthreads_or(bad) ? LP_NO_MOLECULE : 0;
     }
     if (st) {                                        // left out: pos_out keeps the input rows the host copied
         if (tid < 12) report[(size_t)b * 12 + tid] = 0.0;
@@ -481,16 +445,16 @@ k_relax(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_at
         const int di = deg[i];
         unsigned cls = 0;
         for (int a = 0; a < di; ++a) {
-            const int j = nbr[i * RX_DEG + a];
+            const int j = nbr[i * MOL_DEG + a];
             row[j >> 5] |= 1u << (j & 31);
             for (int c = 0; c < deg[j]; ++c) {
-                const int k = nbr[j * RX_DEG + c];
+                const int k = nbr[j * MOL_DEG + c];
                 row[k >> 5] |= 1u << (k & 31);
             }
             for (int c = a + 1; c < di; ++c) {
                 double u[3], w[3], uu, ww, inv, cs = 0.0;
                 unsigned code = 0;                   // keep the sampled angle (also when it cannot be measured)
-                if (angle_cos(x0, j, i, (int)nbr[i * RX_DEG + c], u, w, uu, ww, inv, cs) && !(cs > RX_COS100))
+                if (angle_cos(x0, j, i, (int)nbr[i * MOL_DEG + c], u, w, uu, ww, inv, cs) && !(cs > RX_COS100))
                     code = di >= 4 ? 1u : cs <= RX_COS150 ? 3u : cs <= RX_COS114 ? 2u : 1u;
                 cls |= code << (2 * pair_index(a, c));
             }
@@ -613,7 +577,7 @@ k_relax(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_at
         const double d = (double)v - (double)x0[k];
         sq += d * d;
     }
-    sq = wave_sum_d(sq);
+    sq = wave_sum(sq);
     if ((tid & 63) == 0) red[tid >> 6] = sq;
     __syncthreads();
     if (tid == 0) {
@@ -644,15 +608,9 @@ extern "C" kpd_status kpd_relax(const float *pos, const int32_t *lig_ptr, int32_
                                 const float *pocket_vdw, const int32_t *pocket_ptr, int32_t n_pocket, int32_t P, int32_t max_pocket,
                                 const int32_t *pocket_of, const kpd_relax_params *params, float *pos_out, double *report,
                                 int32_t *status, void *stream) {
-    KPD_REQUIRE(n_atoms >= 0 && B >= 0 && F >= 1 && cap_bonds >= 0 && n_pocket >= 0 && P >= 0 && max_pocket >= 0, KPD_ERR_INVALID,
-                "n_atoms=%d B=%d F=%d cap_bonds=%d n_pocket=%d P=%d max_pocket=%d", n_atoms, B, F, cap_bonds, n_pocket, P, max_pocket);
-    KPD_REQUIRE(max_atoms >= 1 && max_atoms <= MOL_MAX, KPD_ERR_INVALID, "max_atoms=%d (1 .. %d)", max_atoms, MOL_MAX);
-    KPD_REQUIRE(lig_ptr && z && lig_vdw && bond_ptr, KPD_ERR_INVALID, "null argument");
-    KPD_REQUIRE(!n_atoms || (pos && elem && pos_out), KPD_ERR_INVALID, "null argument");
-    KPD_REQUIRE(!B || (mol_status && pocket_of && report && status), KPD_ERR_INVALID, "null argument");
-    KPD_REQUIRE(!cap_bonds || bond_ij, KPD_ERR_INVALID, "null bond buffer");
-    KPD_REQUIRE(!P || pocket_ptr, KPD_ERR_INVALID, "null pocket_ptr");
-    KPD_REQUIRE(!n_pocket || (pocket_x && pocket_vdw), KPD_ERR_INVALID, "null pocket buffer");
+    KPD_TRY(ligand_pocket_args(n_atoms, B, max_atoms, F, cap_bonds, n_pocket, P, max_pocket, lig_ptr && z && lig_vdw && bond_ptr,
+                               pos && elem && pos_out, mol_status && pocket_of && report && status, bond_ij, pocket_ptr,
+                               pocket_x && pocket_vdw));
     kpd_relax_params d;
     kpd_relax_defaults(&d);
     if (params) d = *params;
@@ -677,9 +635,8 @@ extern "C" kpd_status kpd_relax(const float *pos, const int32_t *lig_ptr, int32_
     rp.max_step = d.max_step;
     rp.max_iters = d.max_iters;
     // as much of the largest pocket as fits beside the state of a max_atoms ligand
-    const size_t fixed = relax_layout(max_atoms, 0).bytes;
-    KPD_REQUIRE(fixed + 64 <= (size_t)RX_LDS, KPD_ERR_INVALID, "no LDS for %d atoms", max_atoms);
-    const int stage = (int)std::min<size_t>((size_t)max_pocket, ((size_t)RX_LDS - 64 - fixed) / RX_POCKET_ROW);
+    const int stage = stage_rows(relax_layout(max_atoms, 0).bytes, RX_LDS, RX_POCKET_ROW, max_pocket);
+    KPD_REQUIRE(stage >= 0, KPD_ERR_INVALID, "no LDS for %d atoms", max_atoms);
     const RelaxLayout L = relax_layout(max_atoms, stage);
     KPD_REQUIRE(L.bytes <= (size_t)RX_LDS, KPD_ERR_INVALID, "LDS layout of %zu bytes", L.bytes);
     KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_relax), (int)L.bytes));

@@ -11,19 +11,16 @@
 // summed by one wavefront whose lanes stride the pocket atoms (the first of them staged in LDS, the rest read from global memory
 // with the same bits) and meet in a butterfly.  Nothing is shared between ligands, no atomics on floats, no host synchronisation:
 // a ligand's result is bitwise independent of the batch, of what was staged, and of the repeat.
-#include <algorithm>
-
 #include "common.h"
 #include "molecule_core.h"
 
 namespace kpd {
 
 constexpr int VN_T = 256;                 // threads of a workgroup
-constexpr int VN_DEG = 6;                 // neighbours of one atom (the largest valence cap of the bond rule)
 constexpr int VN_LDS = 64 * 1024 - 512;   // dynamic LDS of a workgroup: what needs no opt-in, less the static bytes of the votes
 constexpr int VN_POCKET_ROW = 20;         // staged pocket atom: 3 floats, radius, type
 
-enum : int { VN_NO_MOLECULE = 1, VN_BAD_INPUT = 2, VN_ATOM_OUT = 4 };
+enum : int { VN_ATOM_OUT = 4 };           // status bit 2; bits 0 and 1 are LP_NO_MOLECULE and LP_BAD_INPUT
 enum : int { VN_H = 1, VN_D = 2, VN_A = 4 };
 enum : unsigned { VN_HETERO = 1u };       // neighbour flags: bit 0 = a neighbour that is neither C nor H, bit k = a bond of order k
 
@@ -41,11 +38,7 @@ __host__ __device__ inline VinaLayout vina_layout(int nm, int stage) {
     VinaLayout L;
     L.W = (nm + 31) / 32;
     size_t o = 0;
-    auto take = [&o](size_t bytes) {
-        const size_t at = o;
-        o += (bytes + 15) & ~(size_t)15;
-        return at;
-    };
+    auto take = [&o](size_t bytes) { return lds_take(o, bytes, 16); };
     L.part = take((size_t)nm * 5 * 8);
     L.red = take(8 * 8);
     L.x0 = take((size_t)nm * 3 * 4);
@@ -61,14 +54,6 @@ __host__ __device__ inline VinaLayout vina_layout(int nm, int stage) {
     L.bytes = o;
     return L;
 }
-
-__device__ __forceinline__ double vina_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ bool vina_finite(float v) { return fabsf(v) < __builtin_inff(); }
 
 // the flags of include/kpd.h from the atomic number, the heavy degree and the neighbour flags
 __device__ __forceinline__ int vina_flags(int z, int deg, unsigned nf) {
@@ -120,7 +105,7 @@ k_vina_pocket_types(const float *__restrict__ pocket_x, const int *__restrict__ 
         yi = r[1];
         zi = r[2];
         Zi = pocket_z[q0 + i];
-        fin_i = vina_finite(xi) && vina_finite(yi) && vina_finite(zi);
+        fin_i = finite_f(xi) && finite_f(yi) && finite_f(zi);
         ri = fin_i ? element_row(Zi) : 0u;
     }
     int deg = 0, bad = 0;
@@ -132,7 +117,7 @@ k_vina_pocket_types(const float *__restrict__ pocket_x, const int *__restrict__ 
             const float *r = pocket_x + (size_t)(q0 + jl) * 3;
             const float x = r[0], y = r[1], z = r[2];
             const int Z = pocket_z[q0 + jl];
-            const bool fin = vina_finite(x) && vina_finite(y) && vina_finite(z);
+            const bool fin = finite_f(x) && finite_f(y) && finite_f(z);
             if (!fin) bad = 1;
             sx[3 * tid] = x;
             sx[3 * tid + 1] = y;
@@ -243,30 +228,10 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
     float *px = reinterpret_cast<float *>(lds + L.px), *prad = reinterpret_cast<float *>(lds + L.prad);
     int *ptyp = reinterpret_cast<int *>(lds + L.ptyp);
 
-    // ---- is there a molecule (bit 0)?  Every `st` below is block-uniform.
-    int a0, a1, st = 0;
-    const bool seg = mol_segment(lig_ptr, b, n_atoms, a0, a1);
-    const int n = a1 - a0;
-    int p0 = 0, p1 = 0;
-    if (!seg || n <= 0 || n > MOL_MAX || n > nm || (mol_status[b] & (MOL_EMPTY | MOL_CAPACITY | MOL_BAD_SEGMENT))) st = VN_NO_MOLECULE;
-    if (!st) {
-        p0 = bond_ptr[b];
-        p1 = bond_ptr[b + 1];
-        if (p0 < 0 || p1 < p0 || p1 > cap_bonds || p1 - p0 > 3 * MOL_MAX) st = VN_NO_MOLECULE;
-    }
-    // ---- its pocket (bit 1)
-    int np = 0, q0 = 0;
-    if (!st) {
-        const int po = pocket_of[b];
-        if (po < -1 || po >= n_pockets) {
-            st = VN_BAD_INPUT;
-        } else if (po >= 0) {
-            q0 = pocket_ptr[po];
-            const int q1 = pocket_ptr[po + 1];
-            if (q0 < 0 || q1 < q0 || q1 > n_pocket) st = VN_BAD_INPUT;
-            else np = q1 - q0;
-        }
-    }
+    // ---- is there a molecule (bit 0), and its pocket (bit 1)?  Every `st` below is block-uniform.
+    LigandInPocket lp;
+    int st = ligand_in_pocket(lig_ptr, b, n_atoms, nm, bond_ptr, cap_bonds, mol_status, pocket_of, pocket_ptr, n_pocket, n_pockets, lp);
+    const int a0 = lp.a0, a1 = lp.a1, n = lp.n, p0 = lp.p0, p1 = lp.p1, q0 = lp.q0, np = lp.np;
     const int stage = min(np, stage_cap);
     int atom_out = 0;
     if (!st) {
@@ -280,16 +245,16 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
             const size_t ga = (size_t)(a0 + a);
             const int e = elem[ga];
             if (e < 0 || e >= F) {
-                bad |= VN_NO_MOLECULE;
+                bad |= LP_NO_MOLECULE;
                 continue;
             }
             const float rv = lig_radius[e];
-            if (!vina_finite(rv)) bad |= VN_BAD_INPUT;
+            if (!finite_f(rv)) bad |= LP_BAD_INPUT;
             rad[a] = rv;
             zat[a] = zs[e];
             for (int k = 0; k < 3; ++k) {
                 const float v = pos[ga * 3 + k];
-                if (!vina_finite(v)) bad |= VN_BAD_INPUT;
+                if (!finite_f(v)) bad |= LP_BAD_INPUT;
                 x0[3 * a + k] = v;
             }
         }
@@ -297,7 +262,7 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
             const float *r = pocket_x + (size_t)(q0 + j) * 3;
             const float rv = pocket_radius[q0 + j];
             const int tj = pocket_type[q0 + j];
-            if (!(vina_finite(r[0]) && vina_finite(r[1]) && vina_finite(r[2]) && vina_finite(rv))) bad |= VN_BAD_INPUT;
+            if (!(finite_f(r[0]) && finite_f(r[1]) && finite_f(r[2]) && finite_f(rv))) bad |= LP_BAD_INPUT;
             if (tj < 0 || !(rv > 0.0f)) atom_out = 1;
             if (j < stage) {
                 px[3 * j] = r[0];
@@ -307,8 +272,7 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
                 ptyp[j] = tj;
             }
         }
-        const int no_mol = __syncthreads_or(bad & VN_NO_MOLECULE), bad_in = __syncthreads_or(bad & VN_BAD_INPUT);     // votes, not sums
-        st = no_mol ? VN_NO_MOLECULE : bad_in ? VN_BAD_INPUT : 0;
+        st = lp_votes(bad);
     }
     if (!st) {                                       // the bond graph: bit matrix, degrees, neighbour flags (integer atomics: no order)
         int bad = 0;
@@ -327,16 +291,16 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
             atomicOr(&adj[j * W + (i >> 5)], 1u << (i & 31));
             if (was & (1u << (j & 31))) bad = 1;     // a bond twice
             const unsigned ci = atomicAdd(&cnt[i], 1u + (zj != 1 ? 16u : 0u)), cj = atomicAdd(&cnt[j], 1u + (zi != 1 ? 16u : 0u));
-            if ((ci & 15u) >= (unsigned)VN_DEG || (cj & 15u) >= (unsigned)VN_DEG) bad = 1;      // a seventh neighbour
+            if ((ci & 15u) >= (unsigned)MOL_DEG || (cj & 15u) >= (unsigned)MOL_DEG) bad = 1;      // a seventh neighbour
             if (zj != 1) atomicOr(&flg[i], (zj != 6 ? VN_HETERO : 0u) | (1u << o));
             if (zi != 1) atomicOr(&flg[j], (zi != 6 ? VN_HETERO : 0u) | (1u << o));
         }
-        st = __syncthreads_or(bad) ? VN_NO_MOLECULE : 0;
+        st = __syncthreads_or(bad) ? LP_NO_MOLECULE : 0;
     }
     if (st) {                                        // left out: zero rows, types -1
         if (tid < 8) report[(size_t)b * 8 + tid] = 0.0;
         if (tid == 0) status[b] = st;
-        if (seg)
+        if (lp.seg)
             for (int a = a0 + tid; a < a1; a += VN_T) {
                 if (grad) grad[(size_t)a * 3] = grad[(size_t)a * 3 + 1] = grad[(size_t)a * 3 + 2] = 0.0;
                 if (atom_score) atom_score[a] = 0.0;
@@ -412,10 +376,10 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
             }
         }
 #pragma unroll
-        for (int k = 0; k < 5; ++k) t[k] = vina_wave_sum(t[k]);
-        gx = vina_wave_sum(gx);
-        gy = vina_wave_sum(gy);
-        gz = vina_wave_sum(gz);
+        for (int k = 0; k < 5; ++k) t[k] = wave_sum(t[k]);
+        gx = wave_sum(gx);
+        gy = wave_sum(gy);
+        gz = wave_sum(gz);
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) part[5 * i + k] = t[k];
@@ -436,7 +400,7 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
             for (int k = 0; k < 5; ++k) s[k] += part[5 * i + k];
         }
 #pragma unroll
-        for (int k = 0; k < 5; ++k) s[k] = vina_wave_sum(s[k]);
+        for (int k = 0; k < 5; ++k) s[k] = wave_sum(s[k]);
         if (lane == 0) {
             double *r = report + (size_t)b * 8;
 #pragma unroll
@@ -480,15 +444,9 @@ extern "C" kpd_status kpd_vina_score(const float *pos, const int32_t *lig_ptr, i
                                      const int32_t *pocket_type, const int32_t *pocket_ptr, int32_t n_pocket, int32_t P,
                                      int32_t max_pocket, const int32_t *pocket_of, const kpd_vina_params *params, double *report,
                                      double *grad, double *atom_score, int32_t *lig_type, int32_t *status, void *stream) {
-    KPD_REQUIRE(n_atoms >= 0 && B >= 0 && F >= 1 && cap_bonds >= 0 && n_pocket >= 0 && P >= 0 && max_pocket >= 0, KPD_ERR_INVALID,
-                "n_atoms=%d B=%d F=%d cap_bonds=%d n_pocket=%d P=%d max_pocket=%d", n_atoms, B, F, cap_bonds, n_pocket, P, max_pocket);
-    KPD_REQUIRE(max_atoms >= 1 && max_atoms <= MOL_MAX, KPD_ERR_INVALID, "max_atoms=%d (1 .. %d)", max_atoms, MOL_MAX);
-    KPD_REQUIRE(lig_ptr && z && lig_radius && bond_ptr, KPD_ERR_INVALID, "null argument");
-    KPD_REQUIRE(!n_atoms || (pos && elem), KPD_ERR_INVALID, "null argument");
-    KPD_REQUIRE(!B || (mol_status && pocket_of && report && status), KPD_ERR_INVALID, "null argument");
-    KPD_REQUIRE(!cap_bonds || (bond_ij && bond_order), KPD_ERR_INVALID, "null bond buffer");
-    KPD_REQUIRE(!P || pocket_ptr, KPD_ERR_INVALID, "null pocket_ptr");
-    KPD_REQUIRE(!n_pocket || (pocket_x && pocket_radius && pocket_type), KPD_ERR_INVALID, "null pocket buffer");
+    KPD_TRY(ligand_pocket_args(n_atoms, B, max_atoms, F, cap_bonds, n_pocket, P, max_pocket, lig_ptr && z && lig_radius && bond_ptr,
+                               pos && elem, mol_status && pocket_of && report && status, bond_ij && bond_order, pocket_ptr,
+                               pocket_x && pocket_radius && pocket_type));
     kpd_vina_params d;
     kpd_vina_defaults(&d);
     if (params) d = *params;
@@ -503,9 +461,8 @@ extern "C" kpd_status kpd_vina_score(const float *pos, const int32_t *lig_ptr, i
     vp.w_rot = d.w_rot;
     vp.rc2 = d.r_c * d.r_c;
     // as much of the largest pocket as fits beside a max_atoms ligand
-    const size_t fixed = vina_layout(max_atoms, 0).bytes;
-    KPD_REQUIRE(fixed + 64 <= (size_t)VN_LDS, KPD_ERR_INVALID, "no LDS for %d atoms", max_atoms);
-    const int stage = (int)std::min<size_t>((size_t)max_pocket, ((size_t)VN_LDS - 64 - fixed) / VN_POCKET_ROW);
+    const int stage = stage_rows(vina_layout(max_atoms, 0).bytes, VN_LDS, VN_POCKET_ROW, max_pocket);
+    KPD_REQUIRE(stage >= 0, KPD_ERR_INVALID, "no LDS for %d atoms", max_atoms);
     const VinaLayout L = vina_layout(max_atoms, stage);
     KPD_REQUIRE(L.bytes <= (size_t)VN_LDS, KPD_ERR_INVALID, "LDS layout of %zu bytes", L.bytes);
     hipLaunchKernelGGL(k_vina_score, dim3(B), dim3(VN_T), L.bytes, static_cast<hipStream_t>(stream), pos, lig_ptr, n_atoms, max_atoms, elem,

@@ -1128,15 +1128,43 @@ RELAX_REPORT = ('E_before', 'E_after', 'rmsd', 'gmax_after', 'iterations', 'eval
                 'E_pocket_before', 'gmax_before')
 
 
-def relax_params(**params) -> KpdRelaxParams:
-    """The parameters of kpd_relax: the library's defaults (kpd_relax_defaults) with the given fields replaced."""
-    p = KpdRelaxParams()
-    lib().kpd_relax_defaults(C.byref(p))
-    names = {f[0] for f in KpdRelaxParams._fields_}
+def _struct_params(where: str, Struct, defaults_fn, params: dict, ints=()):
+    """A `Struct` with the library's defaults (`defaults_fn`) and the fields named in `params` replaced (`ints`: the integer
+    ones); an unknown name raises.  Returns the struct and its field names."""
+    p = Struct()
+    defaults_fn(C.byref(p))
+    names = [f[0] for f in Struct._fields_]
     for k, v in params.items():
         if k not in names:
-            raise KpdError(f'relax: unknown parameter {k!r} (known: {sorted(names)})')
-        setattr(p, k, int(v) if k == 'max_iters' else float(v))
+            raise KpdError(f'{where}: unknown parameter {k!r} (known: {sorted(names)})')
+        setattr(p, k, int(v) if k in ints else float(v))
+    return p, names
+
+
+def _ligand_pocket_args(where: str, pos, lig_ptr, z, mol: dict, fields, pocket_x, pocket_ptr, pocket_of, max_atoms, max_pocket):
+    """What `relax` and `vina_score` share: perceived ligands (the `fields` of `mol`) and their pockets as the library takes them.
+    Returns pos, pocket_x and pocket_of normalised, B, N, F, M, P, zt (z on the device), max_atoms and max_pocket (M if None)."""
+    pos = _dev_f32(pos, 'pos')
+    B = _offsets(lig_ptr, 'lig_ptr')
+    _mol_fields(where, mol, fields)
+    P = _offsets(pocket_ptr, f'{where}: pocket_ptr', 'P')
+    pocket_of = _per_entry(pocket_of, f'{where}: pocket_of', B, 'ligand', contiguous=True)
+    pocket_x = _dev_f32(pocket_x, 'pocket_x')
+    N, F, M = pos.shape[0], len(z), pocket_x.shape[0]
+    if (pos.shape != (N, 3) or F < 1 or mol['elem'].numel() != N or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B or
+            pocket_x.shape != (M, 3)):
+        raise KpdError(f'{where}: pos {tuple(pos.shape)}, {B} ligands, {F} classes, pocket_x {tuple(pocket_x.shape)}, {P} pockets do not '
+                       f'match each other or the perceived molecules')
+    max_atoms = int(max_atoms)
+    if not 1 <= max_atoms <= MOL_MAX_ATOMS:
+        raise KpdError(f'{where}: max_atoms {max_atoms} must be 1 .. {MOL_MAX_ATOMS}')
+    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=pos.device)
+    return pos, pocket_x, pocket_of, B, N, F, M, P, zt, max_atoms, M if max_pocket is None else int(max_pocket)
+
+
+def relax_params(**params) -> KpdRelaxParams:
+    """The parameters of kpd_relax: the library's defaults (kpd_relax_defaults) with the given fields replaced."""
+    p, _ = _struct_params('relax', KpdRelaxParams, lib().kpd_relax_defaults, params, ints=('max_iters',))
     if not (p.k_b >= 0 and p.k_a >= 0 and p.r_c > 0 and 0 < p.s < 1 and p.w_intra >= 0 and p.gtol >= 0 and p.max_step > 0 and
             p.max_iters >= 0):
         raise KpdError(f'relax: k_b {p.k_b}, k_a {p.k_a}, w_intra {p.w_intra}, gtol {p.gtol} must be >= 0, r_c {p.r_c} and max_step '
@@ -1152,32 +1180,20 @@ def relax(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_vdw: torch.Tensor, mo
     pocket_ptr [P+1] and pocket_of [B] int32 (-1: no pocket); all GPU tensors.  max_atoms / max_pocket: host-known upper bounds
     that size the kernel's LDS (a larger ligand is left out, a larger pocket is merely read from global memory).  Returns
     (pos_out [N,3] fp32, report [B,12] float64 with the columns RELAX_REPORT, status [B] int32).  No host synchronisation."""
-    pos = _dev_f32(pos, 'pos')
-    B = _offsets(lig_ptr, 'lig_ptr')
-    _mol_fields('relax', mol, ('elem', 'bonds', 'bond_ptr', 'status'))
-    P = _offsets(pocket_ptr, 'relax: pocket_ptr', 'P')
-    pocket_of = _per_entry(pocket_of, 'relax: pocket_of', B, 'ligand', contiguous=True)
-    lig_vdw, pocket_x, pocket_vdw = _dev_f32(lig_vdw, 'lig_vdw'), _dev_f32(pocket_x, 'pocket_x'), _dev_f32(pocket_vdw, 'pocket_vdw')
-    N, F, M = pos.shape[0], len(z), pocket_x.shape[0]
+    pos, pocket_x, pocket_of, B, N, F, M, P, zt, max_atoms, max_pocket = _ligand_pocket_args(
+        'relax', pos, lig_ptr, z, mol, ('elem', 'bonds', 'bond_ptr', 'status'), pocket_x, pocket_ptr, pocket_of, max_atoms, max_pocket)
+    lig_vdw, pocket_vdw = _dev_f32(lig_vdw, 'lig_vdw'), _dev_f32(pocket_vdw, 'pocket_vdw')
     cap_bonds = mol['bonds'].numel() // 2
-    if (pos.shape != (N, 3) or F < 1 or lig_vdw.shape != (F, 2) or mol['elem'].numel() != N or mol['bond_ptr'].numel() != B + 1 or
-            mol['status'].numel() != B or pocket_x.shape != (M, 3) or pocket_vdw.shape != (M, 2)):
-        raise KpdError(f'relax: pos {tuple(pos.shape)}, {B} ligands, {F} classes, lig_vdw {tuple(lig_vdw.shape)}, pocket_x '
-                       f'{tuple(pocket_x.shape)}, pocket_vdw {tuple(pocket_vdw.shape)}, {P} pockets, pocket_of {tuple(pocket_of.shape)} '
-                       f'do not match each other or the perceived molecules')
-    max_atoms = int(max_atoms)
-    if not 1 <= max_atoms <= MOL_MAX_ATOMS:
-        raise KpdError(f'relax: max_atoms {max_atoms} must be 1 .. {MOL_MAX_ATOMS}')
+    if lig_vdw.shape != (F, 2) or pocket_vdw.shape != (M, 2):
+        raise KpdError(f'relax: lig_vdw {tuple(lig_vdw.shape)} must be [{F},2] and pocket_vdw {tuple(pocket_vdw.shape)} [{M},2]')
     p = relax_params(**params)
     dev = pos.device
-    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
     pos_out = torch.empty_like(pos)
     report = torch.empty(B, 12, dtype=torch.float64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
     check(lib().kpd_relax(_ptr(pos), _ptr(lig_ptr), N, B, max_atoms, _ptr(mol['elem']), F, _ptr(zt), _ptr(lig_vdw), _ptr(mol['bonds']),
                           _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']), _ptr(pocket_x), _ptr(pocket_vdw), _ptr(pocket_ptr), M, P,
-                          M if max_pocket is None else int(max_pocket), _ptr(pocket_of), C.byref(p), _ptr(pos_out), _ptr(report),
-                          _ptr(status), _stream()))
+                          max_pocket, _ptr(pocket_of), C.byref(p), _ptr(pos_out), _ptr(report), _ptr(status), _stream()))
     return pos_out, report, status
 
 
@@ -1190,13 +1206,7 @@ VINA_REPORT = ('score', 'inter', 'gauss1', 'gauss2', 'repulsion', 'hydrophobic',
 def vina_params(**params) -> KpdVinaParams:
     """The parameters of kpd_vina_score: the library's defaults (kpd_vina_defaults: Vina's published weights as recalled, not
     checked against the paper or Vina's source) with the given fields replaced."""
-    p = KpdVinaParams()
-    lib().kpd_vina_defaults(C.byref(p))
-    names = [f[0] for f in KpdVinaParams._fields_]
-    for k, v in params.items():
-        if k not in names:
-            raise KpdError(f'vina: unknown parameter {k!r} (known: {sorted(names)})')
-        setattr(p, k, float(v))
+    p, names = _struct_params('vina', KpdVinaParams, lib().kpd_vina_defaults, params)
     if not (all(abs(getattr(p, k)) < 1e12 for k in names) and 0 < p.r_c < 1e6 and p.w_rot >= 0):
         raise KpdError('vina: ' + ', '.join(f'{k} {getattr(p, k)}' for k in names) + ': the weights must be finite, w_rot >= 0, r_c > 0')
     return p
@@ -1230,28 +1240,19 @@ def vina_score(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch.Te
     [B] int32 (-1: no pocket), lig_type_in: None or [N] int32 whose entries >= 0 replace the perceived flags; all GPU tensors.
     Returns a dict of device tensors: report [B,8] float64 (columns VINA_REPORT), status [B], lig_type [N] and, on request, grad
     [N,3] and atom_score [N] float64.  No host synchronisation."""
-    pos = _dev_f32(pos, 'pos')
-    B = _offsets(lig_ptr, 'lig_ptr')
-    _mol_fields('vina_score', mol, ('elem', 'bonds', 'order', 'bond_ptr', 'status'))
-    P = _offsets(pocket_ptr, 'vina_score: pocket_ptr', 'P')
-    pocket_of = _per_entry(pocket_of, 'vina_score: pocket_of', B, 'ligand', contiguous=True)
-    lig_radius, pocket_x, pocket_radius = _dev_f32(lig_radius, 'lig_radius'), _dev_f32(pocket_x, 'pocket_x'), _dev_f32(pocket_radius, 'pocket_radius')
-    N, F, M = pos.shape[0], len(z), pocket_x.shape[0]
+    pos, pocket_x, pocket_of, B, N, F, M, P, zt, max_atoms, max_pocket = _ligand_pocket_args(
+        'vina_score', pos, lig_ptr, z, mol, ('elem', 'bonds', 'order', 'bond_ptr', 'status'), pocket_x, pocket_ptr, pocket_of, max_atoms,
+        max_pocket)
+    lig_radius, pocket_radius = _dev_f32(lig_radius, 'lig_radius'), _dev_f32(pocket_radius, 'pocket_radius')
     pocket_type = _per_entry(pocket_type, 'vina_score: pocket_type', M, 'pocket atom')
     if lig_type_in is not None:
         lig_type_in = _per_entry(lig_type_in, 'vina_score: lig_type_in', N, 'ligand atom')
     cap_bonds = mol['order'].numel()
-    if (pos.shape != (N, 3) or F < 1 or lig_radius.shape != (F,) or mol['elem'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or
-            mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B or pocket_x.shape != (M, 3) or pocket_radius.shape != (M,)):
-        raise KpdError(f'vina_score: pos {tuple(pos.shape)}, {B} ligands, {F} classes, lig_radius {tuple(lig_radius.shape)}, pocket_x '
-                       f'{tuple(pocket_x.shape)}, pocket_radius {tuple(pocket_radius.shape)}, {P} pockets do not match each other or '
-                       f'the perceived molecules')
-    max_atoms = int(max_atoms)
-    if not 1 <= max_atoms <= MOL_MAX_ATOMS:
-        raise KpdError(f'vina_score: max_atoms {max_atoms} must be 1 .. {MOL_MAX_ATOMS}')
+    if lig_radius.shape != (F,) or pocket_radius.shape != (M,) or mol['bonds'].numel() != 2 * cap_bonds:
+        raise KpdError(f'vina_score: lig_radius {tuple(lig_radius.shape)} must be [{F}], pocket_radius {tuple(pocket_radius.shape)} [{M}] '
+                       f'and bonds hold two atoms for each of the {cap_bonds} orders')
     p = vina_params(**params)
     dev = pos.device
-    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
     out = dict(report=torch.empty(B, 8, dtype=torch.float64, device=dev), status=torch.empty(B, dtype=torch.int32, device=dev),
                lig_type=torch.empty(N, dtype=torch.int32, device=dev))
     if grad:
@@ -1260,9 +1261,9 @@ def vina_score(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch.Te
         out['atom_score'] = torch.empty(N, dtype=torch.float64, device=dev)
     check(lib().kpd_vina_score(_ptr(pos), _ptr(lig_ptr), N, B, max_atoms, _ptr(mol['elem']), F, _ptr(zt), _ptr(lig_radius), _ptr(mol['bonds']),
                                _ptr(mol['order']), _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']), _ptr(lig_type_in), _ptr(pocket_x),
-                               _ptr(pocket_radius), _ptr(pocket_type), _ptr(pocket_ptr), M, P, M if max_pocket is None else int(max_pocket),
-                               _ptr(pocket_of), C.byref(p), _ptr(out['report']), _ptr(out.get('grad')), _ptr(out.get('atom_score')),
-                               _ptr(out['lig_type']), _ptr(out['status']), _stream()))
+                               _ptr(pocket_radius), _ptr(pocket_type), _ptr(pocket_ptr), M, P, max_pocket, _ptr(pocket_of), C.byref(p),
+                               _ptr(out['report']), _ptr(out.get('grad')), _ptr(out.get('atom_score')), _ptr(out['lig_type']),
+                               _ptr(out['status']), _stream()))
     return out
 
 

@@ -242,6 +242,27 @@ class Molecules:
             out['diversity_std'] = float(per_group.std(unbiased=False)) if per_group.numel() else 0.0
         return out
 
+    def _in_pockets(self, where: str, what: str, pocket_pos, pocket_elements, pocket_of):
+        """What `relax` and `vina_score` share: the guards, then the pockets as one device batch.  Returns pocket_x [M,3],
+        pocket_ptr [P+1], pocket_of [B], the pockets' sizes, the atomic number of every ligand class and the max_atoms bound."""
+        if self.pos is None or self.lig_elements is None or self.bonds is None:
+            raise hip.KpdError('these Molecules carry no coordinates: build them with build_molecules')
+        if len(pocket_pos) != len(pocket_elements):
+            raise ValueError('pocket_pos and pocket_elements must have one entry per pocket')
+        if not self.pos.is_cuda or any(not p.is_cuda for p in pocket_pos):
+            raise hip.KpdError(f'{where}: ligands and pockets must live on the GPU; {what} has no CPU implementation')
+        dev = self.pos.device
+        for q, (p, els) in enumerate(zip(pocket_pos, pocket_elements)):
+            if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] != len(els):
+                raise hip.KpdError(f'{where}: pocket {q} has positions {tuple(p.shape)} and {len(els)} element symbols')
+        pocket_of = _pocket_of(pocket_of, len(self), len(pocket_pos), dev)
+        sizes = [int(p.shape[0]) for p in pocket_pos]
+        pocket_x = torch.cat([p.reshape(-1, 3).float() for p in pocket_pos]) if sizes else torch.zeros(0, 3, device=dev)
+        pocket_ptr = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0).to(torch.int32).to(dev)
+        n_max = self._max_atoms if self._max_atoms is not None else hip.MOL_MAX_ATOMS
+        return (pocket_x, pocket_ptr, pocket_of, sizes, [ATOMIC_NUMBERS.get(el, 0) for el in self.lig_elements],
+                max(1, min(n_max, hip.MOL_MAX_ATOMS)))
+
 
     def relax(self, pocket_pos: List[torch.Tensor], pocket_elements: List[Sequence[str]], pocket_of=None,
               vdw: Optional[Dict[str, tuple]] = None, **params) -> 'Relaxed':
@@ -253,30 +274,16 @@ class Molecules:
         pocket; `pocket_of`: the pocket of every ligand (-1: none), all zeros by default when one pocket is given; `vdw`:
         element -> (x, D), consulted before VDW_PARAMS (an element in neither raises); `params`: k_b, k_a, r_c, s, w_intra,
         gtol, max_step, max_iters."""
-        if self.pos is None or self.lig_elements is None or self.bonds is None:
-            raise hip.KpdError('these Molecules carry no coordinates: build them with build_molecules')
-        if len(pocket_pos) != len(pocket_elements):
-            raise ValueError('pocket_pos and pocket_elements must have one entry per pocket')
-        if not self.pos.is_cuda or any(not p.is_cuda for p in pocket_pos):
-            raise hip.KpdError('relax: ligands and pockets must live on the GPU; relaxation has no CPU implementation')
-        B, dev = len(self), self.pos.device
-        for q, (p, els) in enumerate(zip(pocket_pos, pocket_elements)):
-            if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] != len(els):
-                raise hip.KpdError(f'relax: pocket {q} has positions {tuple(p.shape)} and {len(els)} element symbols')
-        pocket_of = _pocket_of(pocket_of, B, len(pocket_pos), dev)
+        pocket_x, pocket_ptr, pocket_of, sizes, z, max_atoms = self._in_pockets('relax', 'relaxation', pocket_pos, pocket_elements, pocket_of)
+        dev = self.pos.device
         lig_vdw = torch.tensor(vdw_table(self.lig_elements, vdw), dtype=torch.float32, device=dev).reshape(-1, 2)
         rows = [r for els in pocket_elements for r in vdw_table(els, vdw)]
         pocket_vdw = torch.tensor(rows, dtype=torch.float32, device=dev).reshape(-1, 2)
-        sizes = [int(p.shape[0]) for p in pocket_pos]
-        pocket_x = torch.cat([p.reshape(-1, 3).float() for p in pocket_pos]) if sizes else torch.zeros(0, 3, device=dev)
-        pocket_ptr = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0).to(torch.int32).to(dev)
-        z = [ATOMIC_NUMBERS.get(el, 0) for el in self.lig_elements]
         mol = dict(elem=self.elem, bonds=self.bonds, bond_ptr=self.bond_ptr, status=self.status)
-        if B == 0:
+        if len(self) == 0:
             return Relaxed(self, self.pos, torch.zeros(0, 12, dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev))
-        n_max = self._max_atoms if self._max_atoms is not None else hip.MOL_MAX_ATOMS
         pos, report, status = hip.relax(self.pos, self.lig_ptr, z, lig_vdw, mol, pocket_x, pocket_vdw, pocket_ptr, pocket_of,
-                                        max_atoms=max(1, min(n_max, hip.MOL_MAX_ATOMS)), max_pocket=max(sizes, default=0), **params)
+                                        max_atoms=max_atoms, max_pocket=max(sizes, default=0), **params)
         return Relaxed(self, pos, report, status)
 
 
@@ -291,22 +298,10 @@ class Molecules:
         2 donor, 4 acceptor, -1 takes no part) as one sequence per pocket or one [M] tensor, in place of the perceived ones;
         `lig_types`: [N] int32 whose entries >= 0 replace the perceived ligand flags; `grad`: also return the gradient and the
         per-atom scores; `params`: w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond, w_rot, r_c."""
-        if self.pos is None or self.lig_elements is None or self.bonds is None:
-            raise hip.KpdError('these Molecules carry no coordinates: build them with build_molecules')
-        if len(pocket_pos) != len(pocket_elements):
-            raise ValueError('pocket_pos and pocket_elements must have one entry per pocket')
-        if not self.pos.is_cuda or any(not p.is_cuda for p in pocket_pos):
-            raise hip.KpdError('vina_score: ligands and pockets must live on the GPU; scoring has no CPU implementation')
-        B, dev = len(self), self.pos.device
-        for q, (p, els) in enumerate(zip(pocket_pos, pocket_elements)):
-            if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] != len(els):
-                raise hip.KpdError(f'vina_score: pocket {q} has positions {tuple(p.shape)} and {len(els)} element symbols')
-        pocket_of = _pocket_of(pocket_of, B, len(pocket_pos), dev)
+        pocket_x, pocket_ptr, pocket_of, sizes, z, max_atoms = self._in_pockets('vina_score', 'scoring', pocket_pos, pocket_elements, pocket_of)
+        dev = self.pos.device
         lig_radius = torch.tensor(xs_radius_table(self.lig_elements, radii), dtype=torch.float32, device=dev)
         pocket_radius = torch.tensor([r for els in pocket_elements for r in xs_radius_table(els, radii)], dtype=torch.float32, device=dev)
-        sizes = [int(p.shape[0]) for p in pocket_pos]
-        pocket_x = torch.cat([p.reshape(-1, 3).float() for p in pocket_pos]) if sizes else torch.zeros(0, 3, device=dev)
-        pocket_ptr = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0).to(torch.int32).to(dev)
         if pocket_types is None:
             pz = torch.tensor([ATOMIC_NUMBERS.get(el, 0) for els in pocket_elements for el in els], dtype=torch.int32, device=dev)
             pocket_types, _ = hip.vina_pocket_types(pocket_x, pz, pocket_ptr)
@@ -318,16 +313,14 @@ class Molecules:
                 raise hip.KpdError(f'vina_score: pocket_types has {pocket_types.numel()} entries for {sum(sizes)} pocket atoms')
         if lig_types is not None:
             lig_types = torch.as_tensor(lig_types).to(torch.int32).to(dev).flatten()
-        z = [ATOMIC_NUMBERS.get(el, 0) for el in self.lig_elements]
         mol = dict(elem=self.elem, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
-        if B == 0:
+        if len(self) == 0:
             empty = dict(report=torch.zeros(0, 8, dtype=torch.float64, device=dev), status=torch.zeros(0, dtype=torch.int32, device=dev),
                          lig_type=torch.zeros(0, dtype=torch.int32, device=dev))
             return VinaScores(self, empty, pocket_types)
-        n_max = self._max_atoms if self._max_atoms is not None else hip.MOL_MAX_ATOMS
         out = hip.vina_score(self.pos, self.lig_ptr, z, lig_radius, mol, pocket_x, pocket_radius, pocket_types, pocket_ptr, pocket_of,
-                             lig_type_in=lig_types, grad=grad, atom_score=grad, max_atoms=max(1, min(n_max, hip.MOL_MAX_ATOMS)),
-                             max_pocket=max(sizes, default=0), **params)
+                             lig_type_in=lig_types, grad=grad, atom_score=grad, max_atoms=max_atoms, max_pocket=max(sizes, default=0),
+                             **params)
         return VinaScores(self, out, pocket_types)
 
 
