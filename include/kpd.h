@@ -888,9 +888,9 @@ kpd_status kpd_relax(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, 
  * Vina FUNCTIONAL FORM: five pair terms over ligand x pocket heavy atoms, the sum divided by 1 + w_rot N_rot, with its analytic
  * gradient.  The typing cannot be Vina's own (Vina reads hydrogens and AutoDock atom types from PDBQT; ligands and pockets here
  * carry heavy atoms and element classes only), so THIS COMMENT IS THE DEFINITION.  THE SCORES ARE NOT gnina's OR Vina's NUMBERS:
- * they rank samples scored by this function against each other.  Out of scope: no torsional or rigid-body minimisation under
- * this function (gnina's --minimize; the gradient delivered here is what it would be built on), no search and no docking, no
- * intramolecular term, no hydrogens, no aromaticity.
+ * they rank samples scored by this function against each other.  Out of scope: no search and no docking, no intramolecular
+ * term in the score, no hydrogens, no aromaticity.  The torsional and rigid-body minimisation under this function (gnina's
+ * --minimize) is kpd_vina_minimize below, built on the gradient delivered here.
  *
  * Ligand and pocket are in one frame, as for kpd_relax.  All arithmetic is fp64 on values read from the fp32 inputs.
  * Distances: d2(i,j) by the recipe of kpd_mol_perceive and kpd_pocket_select (differences of the fp32 coordinates in fp64, each
@@ -959,6 +959,85 @@ kpd_status kpd_vina_score(const float *pos, const int32_t *lig_ptr, int32_t n_at
                           const float *pocket_x, const float *pocket_radius, const int32_t *pocket_type, const int32_t *pocket_ptr,
                           int32_t n_pocket, int32_t P, int32_t max_pocket, const int32_t *pocket_of, const kpd_vina_params *params,
                           double *report, double *grad, double *atom_score, int32_t *lig_type, int32_t *status, void *stream);
+
+/* Local minimisation of sampled ligands under that score, over rigid-body and torsional degrees of freedom (csrc/vina_min.hip).
+ * Stands where upstream runs gen_docking_cmds.py --minimize: gnina --minimize on pocket_minimized_ligands.sdf, written out as
+ * gen_ligands_gnina_minimized.sdf.  gnina's minimiser, its torsion tree (which reads hydrogens) and its numbers cannot be restated
+ * here, so THIS COMMENT IS THE DEFINITION.  THE POSES AND SCORES ARE NOT gnina's OR Vina's: typing, rotor rule, pair terms, weights
+ * and the recalled constants are those of kpd_vina_score, and what is reported is the score at the nearest local minimum of THIS
+ * function.  No search, no docking, a rigid pocket, no hydrogens.
+ *
+ * All arithmetic is fp64 on values read from the fp32 inputs.  The distance recipe, the types, the rotor rule, the pair terms,
+ * the weights, r_c and the r < 1e-6 rule are those of kpd_vina_score, word for word.
+ * Active rotors: the bonds the N_rot rule counts (order 1, both ends of heavy degree >= 2, in no ring), in bond_ij order; the
+ *   first max_rotors of them are active, the rest are frozen (status bit 4, informational).  max_rotors = 0: rigid bodies only.
+ *   T = the number of active rotors.
+ * Rigid pieces: the connected components of the bond graph without the active rotor bonds.
+ * Bodies: each fragment (the labels of `frag`, as kpd_mol_perceive wrote them: connected components ranked by their lowest atom)
+ *   is one body with 6 coordinates, translation t_f and rotation vector w_f.  A ligand with more than 8 fragments is left out
+ *   (status bit 5).  F = the number of fragments; D = 6 F + T <= 112.
+ * Orientation of rotor k = (i, j), i < j as in bond_ij: walk the graph from j without the bond.  If the walk reaches the lowest
+ *   atom of the fragment, the moved set M_k is the fragment minus the reached set and b_k = i; else M_k is the reached set and
+ *   b_k = j.  a_k is the other end.  depth(k) = the number of active rotors k' with b_k in M_k'.
+ * The chart.  The state is the Cartesian x (rigid by construction); a step delta in R^D acts as move(x, delta) in two stages:
+ *   1. torsions: for atom i, the active rotors with i in M_k from the deepest to the shallowest (no ties on a path); each turns
+ *      the atom about the line through the PRE-STEP x_a, x_b by delta_theta_k: with u_k = (x_b - x_a) / |x_b - x_a| (0 if that
+ *      length is below 1e-6) and r = x - x_b, x' = x_b + (r cos + (u x r) sin) + u (u.r)(1 - cos) (Rodrigues).  Deeper turns
+ *      never move a shallower axis, so this is the exact tree kinematics.
+ *   2. bodies: x'' = (c_f + R(delta_w_f)(x' - c_f)) + delta_t_f, c_f the mean of the fragment's pre-step atoms summed in index
+ *      order, R the Rodrigues rotation about delta_w_f / |delta_w_f| by |delta_w_f|, the identity for |delta_w_f| < 1e-12.
+ *   Gradient at delta = 0 from the Cartesian gradient g:  dE/dt_f = sum_{i in f} g_i;  dE/dw_f = sum_{i in f} (x_i - c_f) x g_i;
+ *   dE/dtheta_k = u_k . sum_{i in M_k} (x_i - x_b) x g_i.  Order in the vector: (t, w) per fragment in label order, then the
+ *   rotors in active order.  First-order velocity of atom i under p:  v_i = p_t + p_w x (x_i - c_f) + sum_{k: i in M_k}
+ *   p_theta_k u_k x (x_i - x_b).
+ * Objective: E = inter + w_intra intra, un-normalised.  inter is kpd_vina_score's weighted five-term sum.  intra is the same pair
+ *   function (same weights, radii, types, cutoff) over the ligand pairs i < j of which both atoms take part, that lie in
+ *   different rigid pieces, and whose shortest bond path has four or more bonds or that are not connected.
+ *   score = inter / (1 + w_rot N_rot); N_rot counts all rotors, the frozen ones included.
+ * Minimiser: L-BFGS on delta with the rules of kpd_relax: 8 stored pairs, gamma = s.y / y.y of the newest pair, a pair with
+ *   s.y <= 1e-10 y.y or y.y <= 1e-20 g'.g' is not stored; one iteration, while gnorm > gtol and fewer than max_iters were run:
+ *   p = -H g; if not g.p < 0, drop the pairs and take p = -g.  First trial alpha = min(1, max_step / max_i |v_i|); accept if E'
+ *   is finite and E' <= E + 1e-4 alpha g.p, else halve alpha, at most 20 times.  If no step is accepted and pairs are stored,
+ *   drop them (the iteration is spent); if none are stored, stop with status bit 3.  A pair is s = alpha p and y = g'_delta -
+ *   g_delta, each gradient taken in the chart of its own point.  gnorm = max_d |g_delta,d|.
+ *   After at least one iteration x is rounded to fp32 and evaluated once more there (that evaluation is counted); should E have
+ *   risen above E_before, the ligand keeps its input rows and the numbers of the first evaluation.  Hence E_after <= E_before.
+ *   Every sum is reduced in a fixed order that depends on the ligand and its pocket only.
+ *
+ * kpd_vina_minimize: the inputs of kpd_vina_score, and frag [n_atoms] as kpd_mol_perceive wrote it; max_rotors (0 .. 64) is a
+ *   host-known bound like max_atoms; params: NULL for kpd_vina_min_defaults (kpd_vina_defaults, w_intra 1, gtol 1e-3, max_step
+ *   0.2, max_iters 200).  Out (device): pos_out [n_atoms,3] fp32 (may be pos itself); report [B,16] fp64 = {score_before,
+ *   score_after, E_before, E_after, inter_before, inter_after, intra_before, intra_after, rmsd (plain, as kpd_relax),
+ *   gnorm_before, gnorm_after, iterations, evaluations, N_rot, T, F}; status [B]: bits 0, 1, 2 as for kpd_vina_score (bit 0 also
+ *   for a bond whose ends are not i < j, a frag entry outside [0, n), a bond between two labels, or a label below the largest
+ *   that no atom carries), bit 3 = the
+ *   line search could not lower E further (informational), bit 4 = rotors were frozen (informational), bit 5 = more than 8
+ *   fragments, bit 6 = gnorm_after > gtol without bit 3 (max_iters came first; informational).  With bit 0, 1 or 5 the ligand's
+ *   rows of pos_out are its input rows and its report is zeros; nothing is read or written out of bounds.
+ *   One workgroup per ligand, one launch (and one copy pos -> pos_out) whatever B is; no scratch, no host synchronisation, no
+ *   atomics on floats; a ligand's result is bitwise independent of the rest of the batch, of max_atoms / max_pocket, of
+ *   max_rotors once it is at least the ligand's rotor count, and of the repeat. */
+enum {
+    KPD_VINA_MIN_NO_MOLECULE = 1,
+    KPD_VINA_MIN_BAD_INPUT = 2,
+    KPD_VINA_MIN_ATOM_OUT = 4,
+    KPD_VINA_MIN_LINE_SEARCH = 8,
+    KPD_VINA_MIN_FROZEN_ROTORS = 16,
+    KPD_VINA_MIN_FRAGMENTS = 32,
+    KPD_VINA_MIN_ITER_CAP = 64
+};
+typedef struct kpd_vina_min_params {
+    double w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond, w_rot, r_c, w_intra, gtol, max_step;
+    int32_t max_iters;
+} kpd_vina_min_params;
+void kpd_vina_min_defaults(kpd_vina_min_params *params);
+kpd_status kpd_vina_minimize(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, int32_t max_atoms,
+                             const int32_t *elem, int32_t F, const int32_t *z, const float *lig_radius, const int32_t *frag,
+                             const int32_t *bond_ij, const int32_t *bond_order, const int32_t *bond_ptr, int32_t cap_bonds,
+                             const int32_t *mol_status, const int32_t *lig_type_in, const float *pocket_x, const float *pocket_radius,
+                             const int32_t *pocket_type, const int32_t *pocket_ptr, int32_t n_pocket, int32_t P, int32_t max_pocket,
+                             const int32_t *pocket_of, int32_t max_rotors, const kpd_vina_min_params *params, float *pos_out,
+                             double *report, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,1029 @@
+// Local minimisation of sampled ligands under the Vina-form score of vina.hip, over rigid-body and torsional degrees of freedom:
+// the step upstream runs as `gnina --minimize` (analysis/docking/gen_docking_cmds.py --minimize).  include/kpd.h DEFINES the torsion
+// tree, the chart, the intramolecular term and the minimiser; typing, rotor rule, pair terms and constants are those of
+// kpd_vina_score.  NOT gnina's or Vina's numbers.
+// k_vina_minimize: one workgroup (4 waves) per ligand and ONE launch for the whole minimisation of every ligand.  Once per ligand:
+// the bond graph as a bit matrix in LDS, typing, the rotor list in bond order, the moved set of every active rotor as a bit set
+// (one thread per rotor walks the graph without its bond), piece labels by label propagation, the mask of intramolecular pairs.
+// One evaluation: an atom's pocket and intramolecular terms and its Cartesian gradient are summed by one wavefront (lanes stride the
+// pocket atoms, then the ligand's own, and meet in a butterfly); the projection on the pose coordinates takes one wavefront per
+// body or rotor over its atom set.  The pose vectors have at most 112 entries, so the two-loop recursion and every dot product of
+// the L-BFGS run on one wavefront, two entries per lane.  Nothing is shared between ligands, no atomics on floats, no host
+// synchronisation: a ligand's result is bitwise independent of the batch, of what was staged, of the bounds, and of the repeat.
+// The helpers that vina.hip also has (flags, pair terms) are restated here so that vina.hip's kernels keep their code objects.
+#include "common.h"
+#include "molecule_core.h"
+
+namespace kpd {
+
+constexpr int VM_T = 256;                 // threads of a workgroup
+constexpr int VM_M = 8;                   // stored correction pairs
+constexpr int VM_LDS = 160 * 1024 - 512;  // LDS of one CU, less the few static bytes the compiler adds for the block-wide votes
+constexpr int VM_POCKET_ROW = 20;         // staged pocket atom: 3 floats, radius, type
+constexpr int VM_FRAGS = 8;               // bodies of one ligand
+constexpr int VM_ROTORS = 64;             // active rotors of one ligand
+
+enum : int { VM_ATOM_OUT = 4, VM_LINE_SEARCH = 8, VM_FROZEN = 16, VM_FRAGMENTS = 32, VM_ITER_CAP = 64 };      // status bits 2 .. 6
+enum : int { VM_H = 1, VM_D = 2, VM_A = 4 };
+enum : unsigned { VM_HETERO = 1u };       // neighbour flags: bit 0 = a neighbour that is neither C nor H, bit k = a bond of order k
+// slots of `scal`
+enum : int { VS_INTER = 0, VS_INTRA, VS_E, VS_GNORM, VS_GP, VS_SY, VS_YY, VS_GG, VS_RESET, VS_COUNT = 16 };
+
+struct VinaMinP {
+    double w[5], w_rot, rc2, w_intra, gtol, max_step;
+    int max_iters;
+};
+
+// byte offsets of the dynamic LDS of a workgroup for ligands of at most nm atoms, mr active rotors and `stage` staged pocket atoms
+struct VinaMinLayout {
+    size_t x, xt, g, part, vec, rho, scal, red, cen, axu, trig, body, x0, rad, zat, typ, cnt, flg, frg, piece, adj, adjp, imask, mset, fset,
+        ra, rb, depth, ord, flow, fcnt, rflag, px, prad, ptyp, bytes;
+    int W, DS;
+};
+
+__host__ __device__ inline VinaMinLayout vina_min_layout(int nm, int mr, int stage) {
+    VinaMinLayout L;
+    L.W = (nm + 31) / 32;
+    L.DS = 6 * VM_FRAGS + mr;             // stride of the pose vectors
+    size_t o = 0;
+    auto take = [&o](size_t bytes) { return lds_take(o, bytes, 16); };
+    L.x = take((size_t)nm * 3 * 8);
+    L.xt = take((size_t)nm * 3 * 8);
+    L.g = take((size_t)nm * 3 * 8);
+    L.part = take((size_t)nm * 10 * 8);
+    L.vec = take((size_t)(3 + 2 * VM_M) * L.DS * 8);          // g_delta, its trial, p, S[8], Y[8]
+    L.rho = take(VM_M * 8);
+    L.scal = take(VS_COUNT * 8);
+    L.red = take(8 * 8);
+    L.cen = take(VM_FRAGS * 3 * 8);
+    L.axu = take((size_t)(mr + 1) * 3 * 8);
+    L.trig = take((size_t)(mr + 1) * 2 * 8);
+    L.body = take(VM_FRAGS * 8 * 8);
+    L.x0 = take((size_t)nm * 3 * 4);
+    L.rad = take((size_t)nm * 4);
+    L.zat = take((size_t)nm * 4);
+    L.typ = take((size_t)nm * 4);
+    L.cnt = take((size_t)nm * 4);
+    L.flg = take((size_t)nm * 4);
+    L.frg = take((size_t)nm * 4);
+    L.piece = take((size_t)nm * 4);
+    L.adj = take((size_t)nm * L.W * 4);
+    L.adjp = take((size_t)nm * L.W * 4);
+    L.imask = take((size_t)nm * L.W * 4);
+    L.mset = take((size_t)(mr + 1) * L.W * 4);
+    L.fset = take((size_t)VM_FRAGS * L.W * 4);
+    L.ra = take((size_t)(mr + 1) * 4);
+    L.rb = take((size_t)(mr + 1) * 4);
+    L.depth = take((size_t)(mr + 1) * 4);
+    L.ord = take((size_t)(mr + 1) * 4);
+    L.flow = take(VM_FRAGS * 4);
+    L.fcnt = take(VM_FRAGS * 4);
+    L.rflag = take((size_t)nm * 3);
+    L.px = take((size_t)stage * 3 * 4);
+    L.prad = take((size_t)stage * 4);
+    L.ptyp = take((size_t)stage * 4);
+    L.bytes = o;
+    return L;
+}
+
+struct VinaMinCtx {
+    int n, np, stage, W, F, T, D;
+    const float *rad, *px, *prad, *gpx, *gpr;
+    const int *typ, *ptyp, *gpt, *frg, *ra, *rb, *ord, *fcnt;
+    const unsigned *imask, *mset;
+    double *part, *scal, *red, *cen, *axu, *trig, *body;
+    VinaMinP P;
+};
+
+// the flags of include/kpd.h from the atomic number, the heavy degree and the neighbour flags (as in vina.hip)
+__device__ __forceinline__ int vm_flags(int z, int deg, unsigned nf) {
+    switch (z) {
+    case 6: return (nf & VM_HETERO) ? 0 : VM_H;
+    case 9:
+    case 17:
+    case 35:
+    case 53: return VM_H;
+    case 7:
+        if (deg > 2) return 0;
+        return (deg == 1 && (nf & (1u << 3))) ? VM_A : VM_D;
+    case 8: return VM_A | ((deg == 0 || (deg == 1 && (nf & (1u << 1)))) ? VM_D : 0);
+    case 12:
+    case 20:
+    case 25:
+    case 26:
+    case 27:
+    case 28:
+    case 29:
+    case 30: return VM_D;
+    default: return 0;
+    }
+}
+
+// the five terms of one pair at surface distance d (added to t) and dd = sum over the terms of w_term * dterm/dd (as in vina.hip)
+__device__ __forceinline__ double vm_pair(double d, int ti, int tj, const VinaMinP &P, double (&t)[5]) {
+    const double u = d / 0.5, v = (d - 3.0) / 2.0;
+    const double g1 = exp(-(u * u)), g2 = exp(-(v * v));
+    t[0] += g1;
+    t[1] += g2;
+    double dd = P.w[0] * (-4.0 * u * g1) + P.w[1] * (-v * g2);
+    if (d < 0.0) {
+        t[2] += d * d;
+        dd += P.w[2] * (2.0 * d);
+    }
+    if (ti & tj & VM_H) {
+        if (d < 0.5) {
+            t[3] += 1.0;
+        } else if (d < 1.5) {
+            t[3] += 1.5 - d;
+            dd -= P.w[3];
+        }
+    }
+    if (((ti & VM_D) && (tj & VM_A)) || ((ti & VM_A) && (tj & VM_D))) {
+        if (d < -0.7) {
+            t[4] += 1.0;
+        } else if (d < 0.0) {
+            t[4] += d / -0.7;
+            dd += P.w[4] / -0.7;
+        }
+    }
+    return dd;
+}
+
+__device__ __forceinline__ bool vm_bit(const unsigned *row, int j) { return (row[j >> 5] >> (j & 31)) & 1u; }
+
+__device__ __forceinline__ double vm_wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
+
+// The atoms reached from `from` when its bond to `other` is removed, as a bit set in registers (the walk of vina.hip, run to its end).
+__device__ void vm_reach(const unsigned *adj, int W, int from, int other, unsigned (&vis)[MOL_W]) {
+    unsigned fr[MOL_W];
+#pragma unroll
+    for (int w = 0; w < MOL_W; ++w) vis[w] = fr[w] = (w == (from >> 5)) ? 1u << (from & 31) : 0u;
+    const int ow = other >> 5;
+    const unsigned ob = 1u << (other & 31);
+    for (;;) {
+        int a = -1;
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w)
+            if (a < 0 && fr[w]) {
+                a = 32 * w + __ffs(fr[w]) - 1;
+                fr[w] &= fr[w] - 1;
+            }
+        if (a < 0) return;
+        const unsigned *row = adj + a * W;
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w) {
+            if (w >= W) continue;
+            unsigned r = row[w];
+            if (a == from && w == ow) r &= ~ob;      // the bond itself
+            const unsigned nw = r & ~vis[w];
+            vis[w] |= nw;
+            fr[w] |= nw;
+        }
+    }
+}
+
+// r turned about the unit axis u by the angle whose cosine and sine are c, s (Rodrigues)
+__device__ __forceinline__ void vm_rot(double &rx, double &ry, double &rz, double ux, double uy, double uz, double c, double s) {
+    const double cx = uy * rz - uz * ry, cy = uz * rx - ux * rz, cz = ux * ry - uy * rx;
+    const double k = ((ux * rx + uy * ry) + uz * rz) * (1.0 - c);
+    rx = (rx * c + cx * s) + ux * k;
+    ry = (ry * c + cy * s) + uy * k;
+    rz = (rz * c + cz * s) + uz * k;
+}
+
+// Energy and Cartesian gradient at xq.  Wave w takes the atoms w, w + 4, ...; afterwards scal = {inter, intra, E, ...}.
+__device__ void vm_eval(const VinaMinCtx &C, const double *xq, double *gq, int tid) {
+    const int lane = tid & 63, wv = tid >> 6;
+    for (int i = wv; i < C.n; i += 4) {
+        const int ti = C.typ[i];
+        double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, u[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, gx = 0.0, gy = 0.0, gz = 0.0;
+        if (ti >= 0) {                               // wave-uniform
+            const double xi = xq[3 * i], yi = xq[3 * i + 1], zi = xq[3 * i + 2], Ri = (double)C.rad[i];
+            for (int j = lane; j < C.np; j += 64) {  // the pocket: the pair loop of k_vina_score
+                float qx, qy, qz, rj;
+                int tj;
+                if (j < C.stage) {
+                    qx = C.px[3 * j];
+                    qy = C.px[3 * j + 1];
+                    qz = C.px[3 * j + 2];
+                    rj = C.prad[j];
+                    tj = C.ptyp[j];
+                } else {
+                    const float *r = C.gpx + (size_t)j * 3;
+                    qx = r[0];
+                    qy = r[1];
+                    qz = r[2];
+                    rj = C.gpr[j];
+                    tj = C.gpt[j];
+                }
+                if (tj < 0 || !(rj > 0.0f)) continue;
+                const double dx = xi - (double)qx, dy = yi - (double)qy, dz = zi - (double)qz;
+                const double d2 = sum_sq(dx, dy, dz);
+                if (!(d2 < C.P.rc2)) continue;
+                const double r = __dsqrt_rn(d2), d = (r - Ri) - (double)rj;
+                const double dd = vm_pair(d, ti, tj & 7, C.P, t);
+                if (r >= 1e-6) {
+                    const double k = dd / r;
+                    gx += k * dx;
+                    gy += k * dy;
+                    gz += k * dz;
+                }
+            }
+            const unsigned *row = C.imask + i * C.W;
+            for (int j = lane; j < C.n; j += 64) {   // the ligand's own atoms: every pair is seen from both of its atoms
+                if (!vm_bit(row, j)) continue;
+                const double dx = xi - xq[3 * j], dy = yi - xq[3 * j + 1], dz = zi - xq[3 * j + 2];
+                const double d2 = sum_sq(dx, dy, dz);
+                if (!(d2 < C.P.rc2)) continue;
+                const double r = __dsqrt_rn(d2), d = (r - Ri) - (double)C.rad[j];
+                const double dd = vm_pair(d, ti, C.typ[j] & 7, C.P, u);
+                if (r >= 1e-6) {
+                    const double k = C.P.w_intra * dd / r;
+                    gx += k * dx;
+                    gy += k * dy;
+                    gz += k * dz;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            t[k] = wave_sum(t[k]);
+            u[k] = wave_sum(u[k]);
+        }
+        gx = wave_sum(gx);
+        gy = wave_sum(gy);
+        gz = wave_sum(gz);
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                C.part[10 * i + k] = t[k];
+                C.part[10 * i + 5 + k] = u[k];
+            }
+            gq[3 * i] = gx;
+            gq[3 * i + 1] = gy;
+            gq[3 * i + 2] = gz;
+        }
+    }
+    __syncthreads();
+    if (wv == 0) {
+        double s[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int i = lane; i < C.n; i += 64) {
+#pragma unroll
+            for (int k = 0; k < 10; ++k) s[k] += C.part[10 * i + k];
+        }
+#pragma unroll
+        for (int k = 0; k < 10; ++k) s[k] = wave_sum(s[k]);
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 10; ++k) s[k] *= C.P.w[k % 5];
+            const double inter = (((s[0] + s[1]) + s[2]) + s[3]) + s[4];
+            const double intra = 0.5 * ((((s[5] + s[6]) + s[7]) + s[8]) + s[9]);
+            C.scal[VS_INTER] = inter;
+            C.scal[VS_INTRA] = intra;
+            C.scal[VS_E] = inter + C.P.w_intra * intra;
+        }
+    }
+    __syncthreads();
+}
+
+// The gradient at delta = 0 in the chart at xq, from the Cartesian gradient gq: the centres and axes of xq are left in cen / axu,
+// the largest |entry| in scal[VS_GNORM].
+__device__ void vm_project(const VinaMinCtx &C, const double *xq, const double *gq, double *gd, int tid) {
+    const int lane = tid & 63, wv = tid >> 6;
+    if (tid < 3 * C.F) {                             // a centre's component: its fragment's atoms in index order
+        const int f = tid / 3, c = tid % 3;
+        double s = 0.0;
+        for (int i = 0; i < C.n; ++i)
+            if (C.frg[i] == f) s += xq[3 * i + c];
+        C.cen[tid] = s / (double)C.fcnt[f];
+    }
+    __syncthreads();
+    for (int q = wv; q < C.F + C.T; q += 4) {        // wave-uniform
+        if (q < C.F) {
+            const double cx = C.cen[3 * q], cy = C.cen[3 * q + 1], cz = C.cen[3 * q + 2];
+            double tx = 0.0, ty = 0.0, tz = 0.0, ox = 0.0, oy = 0.0, oz = 0.0;
+            for (int i = lane; i < C.n; i += 64) {
+                if (C.frg[i] != q) continue;
+                const double gx = gq[3 * i], gy = gq[3 * i + 1], gz = gq[3 * i + 2];
+                const double rx = xq[3 * i] - cx, ry = xq[3 * i + 1] - cy, rz = xq[3 * i + 2] - cz;
+                tx += gx;
+                ty += gy;
+                tz += gz;
+                ox += ry * gz - rz * gy;
+                oy += rz * gx - rx * gz;
+                oz += rx * gy - ry * gx;
+            }
+            tx = wave_sum(tx);
+            ty = wave_sum(ty);
+            tz = wave_sum(tz);
+            ox = wave_sum(ox);
+            oy = wave_sum(oy);
+            oz = wave_sum(oz);
+            if (lane == 0) {
+                double *o = gd + 6 * q;
+                o[0] = tx;
+                o[1] = ty;
+                o[2] = tz;
+                o[3] = ox;
+                o[4] = oy;
+                o[5] = oz;
+            }
+        } else {
+            const int k = q - C.F, a = C.ra[k], b = C.rb[k];
+            const double bx = xq[3 * b], by = xq[3 * b + 1], bz = xq[3 * b + 2];
+            const double ax = bx - xq[3 * a], ay = by - xq[3 * a + 1], az = bz - xq[3 * a + 2];
+            const double len = sqrt((ax * ax + ay * ay) + az * az);
+            const bool ok = len >= 1e-6;             // an axis that cannot be measured turns nothing
+            const double ux = ok ? ax / len : 0.0, uy = ok ? ay / len : 0.0, uz = ok ? az / len : 0.0;
+            const unsigned *M = C.mset + k * C.W;
+            double sx = 0.0, sy = 0.0, sz = 0.0;
+            for (int i = lane; i < C.n; i += 64) {
+                if (!vm_bit(M, i)) continue;
+                const double gx = gq[3 * i], gy = gq[3 * i + 1], gz = gq[3 * i + 2];
+                const double rx = xq[3 * i] - bx, ry = xq[3 * i + 1] - by, rz = xq[3 * i + 2] - bz;
+                sx += ry * gz - rz * gy;
+                sy += rz * gx - rx * gz;
+                sz += rx * gy - ry * gx;
+            }
+            sx = wave_sum(sx);
+            sy = wave_sum(sy);
+            sz = wave_sum(sz);
+            if (lane == 0) {
+                C.axu[3 * k] = ux;
+                C.axu[3 * k + 1] = uy;
+                C.axu[3 * k + 2] = uz;
+                gd[6 * C.F + k] = (ux * sx + uy * sy) + uz * sz;
+            }
+        }
+    }
+    __syncthreads();
+    if (wv == 0) {
+        double m = 0.0;
+        for (int d = lane; d < C.D; d += 64) m = fmax(m, fabs(gd[d]));
+        m = vm_wave_max(m);
+        if (lane == 0) C.scal[VS_GNORM] = m;
+    }
+    __syncthreads();
+}
+
+// a . b over the D entries of two pose vectors on one wavefront: lane l takes the entries l and l + 64
+__device__ __forceinline__ double vm_dot(const double *a, const double *b, int D, int lane) {
+    double v = 0.0;
+    if (lane < D) v = a[lane] * b[lane];
+    if (lane + 64 < D) v += a[lane + 64] * b[lane + 64];
+    return wave_sum(v);
+}
+
+// The direction p = -H g_delta by the two-loop recursion over the m newest pairs, on wave 0 alone; scal[VS_GP] = g.p; should that
+// not be negative, p = -g and scal[VS_RESET] = 1 (the pairs are to be dropped).
+__device__ void vm_direction(const double *gd, const double *S, const double *Y, const double *rho, int DS, int D, int m, int head,
+                             double gamma, double *p, double *scal, int lane) {
+    const int d0 = lane, d1 = lane + 64;
+    const bool in0 = d0 < D, in1 = d1 < D;
+    const double g0 = in0 ? gd[d0] : 0.0, g1 = in1 ? gd[d1] : 0.0;
+    double q0 = g0, q1 = g1, al[VM_M];
+#pragma unroll
+    for (int k = 0; k < VM_M; ++k) {                 // newest first
+        al[k] = 0.0;
+        if (k < m) {
+            const int slot = (head + VM_M - 1 - k) & (VM_M - 1);
+            const double s0 = in0 ? S[slot * DS + d0] : 0.0, s1 = in1 ? S[slot * DS + d1] : 0.0;
+            const double y0 = in0 ? Y[slot * DS + d0] : 0.0, y1 = in1 ? Y[slot * DS + d1] : 0.0;
+            al[k] = rho[slot] * wave_sum(s0 * q0 + s1 * q1);
+            q0 -= al[k] * y0;
+            q1 -= al[k] * y1;
+        }
+    }
+    if (m) {
+        q0 *= gamma;
+        q1 *= gamma;
+    }
+#pragma unroll
+    for (int k = VM_M - 1; k >= 0; --k) {            // oldest first
+        if (k < m) {
+            const int slot = (head + VM_M - 1 - k) & (VM_M - 1);
+            const double s0 = in0 ? S[slot * DS + d0] : 0.0, s1 = in1 ? S[slot * DS + d1] : 0.0;
+            const double y0 = in0 ? Y[slot * DS + d0] : 0.0, y1 = in1 ? Y[slot * DS + d1] : 0.0;
+            const double be = rho[slot] * wave_sum(y0 * q0 + y1 * q1);
+            q0 += (al[k] - be) * s0;
+            q1 += (al[k] - be) * s1;
+        }
+    }
+    q0 = -q0;
+    q1 = -q1;
+    double gp = wave_sum(g0 * q0 + g1 * q1), reset = 0.0;
+    if (!(gp < 0.0)) {                               // no descent direction: forget the pairs
+        reset = 1.0;
+        q0 = -g0;
+        q1 = -g1;
+        gp = -wave_sum(g0 * g0 + g1 * g1);
+    }
+    if (in0) p[d0] = q0;
+    if (in1) p[d1] = q1;
+    if (lane == 0) {
+        scal[VS_GP] = gp;
+        scal[VS_RESET] = reset;
+    }
+}
+
+// the largest first-order speed of an atom under the pose velocity p (a maximum has no order); cen and axu are those of x
+__device__ double vm_vmax(const VinaMinCtx &C, const double *x, const double *p, int tid) {
+    double m = 0.0;
+    for (int i = tid; i < C.n; i += VM_T) {
+        const int f = C.frg[i];
+        const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
+        const double *pf = p + 6 * f;
+        const double rx = xi - C.cen[3 * f], ry = yi - C.cen[3 * f + 1], rz = zi - C.cen[3 * f + 2];
+        double vx = pf[0] + (pf[4] * rz - pf[5] * ry), vy = pf[1] + (pf[5] * rx - pf[3] * rz), vz = pf[2] + (pf[3] * ry - pf[4] * rx);
+        for (int k = 0; k < C.T; ++k) {
+            if (!vm_bit(C.mset + k * C.W, i)) continue;
+            const int b = C.rb[k];
+            const double pk = p[6 * C.F + k], ux = C.axu[3 * k], uy = C.axu[3 * k + 1], uz = C.axu[3 * k + 2];
+            const double sx = xi - x[3 * b], sy = yi - x[3 * b + 1], sz = zi - x[3 * b + 2];
+            vx += pk * (uy * sz - uz * sy);
+            vy += pk * (uz * sx - ux * sz);
+            vz += pk * (ux * sy - uy * sx);
+        }
+        m = fmax(m, sqrt((vx * vx + vy * vy) + vz * vz));
+    }
+    m = vm_wave_max(m);
+    if ((tid & 63) == 0) C.red[tid >> 6] = m;
+    __syncthreads();
+    const double r = fmax(fmax(C.red[0], C.red[1]), fmax(C.red[2], C.red[3]));
+    __syncthreads();
+    return r;
+}
+
+// xt = move(x, alpha p): torsions from the deepest to the shallowest about the axes of x, then the bodies about the centres of x
+__device__ void vm_move(const VinaMinCtx &C, const double *x, const double *p, double alpha, double *xt, int tid) {
+    if (tid < C.T) {
+        double s, c;
+        sincos(alpha * p[6 * C.F + tid], &s, &c);
+        C.trig[2 * tid] = c;
+        C.trig[2 * tid + 1] = s;
+    } else if (tid >= 64 && tid < 64 + C.F) {
+        const int f = tid - 64;
+        const double *pf = p + 6 * f;
+        const double ox = alpha * pf[3], oy = alpha * pf[4], oz = alpha * pf[5];
+        const double th = sqrt((ox * ox + oy * oy) + oz * oz);
+        double *o = C.body + 8 * f;
+        double s = 0.0, c = 1.0;
+        const bool turn = th >= 1e-12;
+        if (turn) sincos(th, &s, &c);
+        o[0] = turn ? ox / th : 0.0;
+        o[1] = turn ? oy / th : 0.0;
+        o[2] = turn ? oz / th : 0.0;
+        o[3] = c;
+        o[4] = s;
+        o[5] = alpha * pf[0];
+        o[6] = alpha * pf[1];
+        o[7] = alpha * pf[2];
+    }
+    __syncthreads();
+    for (int i = tid; i < C.n; i += VM_T) {
+        double px = x[3 * i], py = x[3 * i + 1], pz = x[3 * i + 2];
+        for (int kk = 0; kk < C.T; ++kk) {
+            const int k = C.ord[kk];
+            if (!vm_bit(C.mset + k * C.W, i)) continue;
+            const int b = C.rb[k];
+            const double bx = x[3 * b], by = x[3 * b + 1], bz = x[3 * b + 2];
+            double rx = px - bx, ry = py - by, rz = pz - bz;
+            vm_rot(rx, ry, rz, C.axu[3 * k], C.axu[3 * k + 1], C.axu[3 * k + 2], C.trig[2 * k], C.trig[2 * k + 1]);
+            px = bx + rx;
+            py = by + ry;
+            pz = bz + rz;
+        }
+        const int f = C.frg[i];
+        const double *o = C.body + 8 * f;
+        const double cx = C.cen[3 * f], cy = C.cen[3 * f + 1], cz = C.cen[3 * f + 2];
+        double rx = px - cx, ry = py - cy, rz = pz - cz;
+        vm_rot(rx, ry, rz, o[0], o[1], o[2], o[3], o[4]);
+        xt[3 * i] = (cx + rx) + o[5];
+        xt[3 * i + 1] = (cy + ry) + o[6];
+        xt[3 * i + 2] = (cz + rz) + o[7];
+    }
+    __syncthreads();
+}
+
+// Three waves per SIMD: the compiler's own choice is 173 VGPRs, one short of that; bounded to 168 it spills four of them (20 B of
+// scratch per lane) and the third workgroup on a compute unit more than pays for it (profiles/vina_min.md).
+__global__ void __launch_bounds__(VM_T) __attribute__((amdgpu_waves_per_eu(3, 3)))
+k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, int nm, const int *__restrict__ elem, int F,
+                const int *__restrict__ zs, const float *__restrict__ lig_radius, const int *__restrict__ frag,
+                const int *__restrict__ bond_ij, const int *__restrict__ bond_order, const int *__restrict__ bond_ptr, int cap_bonds,
+                const int *__restrict__ mol_status, const int *__restrict__ lig_type_in, const float *__restrict__ pocket_x,
+                const float *__restrict__ pocket_radius, const int *__restrict__ pocket_type, const int *__restrict__ pocket_ptr,
+                int n_pocket, int n_pockets, int stage_cap, const int *__restrict__ pocket_of, int max_rotors, VinaMinP P,
+                float *pos_out, double *__restrict__ report, int *__restrict__ status) {      // pos_out may be pos: no __restrict__ on the two
+    extern __shared__ double lds_d[];
+    char *lds = reinterpret_cast<char *>(lds_d);
+    const VinaMinLayout L = vina_min_layout(nm, max_rotors, stage_cap);
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, W = L.W, DS = L.DS;
+    double *x = reinterpret_cast<double *>(lds + L.x), *xt = reinterpret_cast<double *>(lds + L.xt);
+    double *g = reinterpret_cast<double *>(lds + L.g);
+    double *gd = reinterpret_cast<double *>(lds + L.vec), *gdt = gd + DS, *p = gdt + DS, *S = p + DS, *Y = S + VM_M * DS;
+    double *rho = reinterpret_cast<double *>(lds + L.rho), *scal = reinterpret_cast<double *>(lds + L.scal);
+    double *red = reinterpret_cast<double *>(lds + L.red);
+    float *x0 = reinterpret_cast<float *>(lds + L.x0), *rad = reinterpret_cast<float *>(lds + L.rad);
+    int *zat = reinterpret_cast<int *>(lds + L.zat), *typ = reinterpret_cast<int *>(lds + L.typ);
+    unsigned *cnt = reinterpret_cast<unsigned *>(lds + L.cnt), *flg = reinterpret_cast<unsigned *>(lds + L.flg);
+    int *frg = reinterpret_cast<int *>(lds + L.frg), *piece = reinterpret_cast<int *>(lds + L.piece);
+    unsigned *adj = reinterpret_cast<unsigned *>(lds + L.adj), *adjp = reinterpret_cast<unsigned *>(lds + L.adjp);
+    unsigned *imask = reinterpret_cast<unsigned *>(lds + L.imask), *mset = reinterpret_cast<unsigned *>(lds + L.mset);
+    unsigned *fset = reinterpret_cast<unsigned *>(lds + L.fset);
+    int *ra = reinterpret_cast<int *>(lds + L.ra), *rb = reinterpret_cast<int *>(lds + L.rb);
+    int *depth = reinterpret_cast<int *>(lds + L.depth), *ord = reinterpret_cast<int *>(lds + L.ord);
+    int *flow = reinterpret_cast<int *>(lds + L.flow), *fcnt = reinterpret_cast<int *>(lds + L.fcnt);
+    unsigned char *rflag = reinterpret_cast<unsigned char *>(lds + L.rflag);
+    float *px = reinterpret_cast<float *>(lds + L.px), *prad = reinterpret_cast<float *>(lds + L.prad);
+    int *ptyp = reinterpret_cast<int *>(lds + L.ptyp);
+
+    // ---- is there a molecule (bit 0), and its pocket (bit 1)?  Every `st` below is block-uniform.
+    LigandInPocket lp;
+    int st = ligand_in_pocket(lig_ptr, b, n_atoms, nm, bond_ptr, cap_bonds, mol_status, pocket_of, pocket_ptr, n_pocket, n_pockets, lp);
+    const int a0 = lp.a0, n = lp.n, p0 = lp.p0, p1 = lp.p1, q0 = lp.q0, np = lp.np;
+    const int stage = min(np, stage_cap);
+    int atom_out = 0;
+    if (!st) {
+        if (tid < VM_FRAGS) {
+            flow[tid] = MOL_MAX;
+            fcnt[tid] = 0;
+        }
+        for (int k = tid; k < VM_FRAGS * W; k += VM_T) fset[k] = 0;
+        int bad = 0;
+        for (int a = tid; a < n; a += VM_T) {
+            cnt[a] = 0;
+            flg[a] = 0;
+            zat[a] = 0;
+            rad[a] = 0.f;
+            frg[a] = 0;
+            for (int w = 0; w < W; ++w) adj[a * W + w] = 0;
+            const size_t ga = (size_t)(a0 + a);
+            const int e = elem[ga], fl = frag[ga];
+            if (e < 0 || e >= F || fl < 0 || fl >= n) {
+                bad |= LP_NO_MOLECULE;
+                continue;
+            }
+            frg[a] = fl;
+            const float rv = lig_radius[e];
+            if (!finite_f(rv)) bad |= LP_BAD_INPUT;
+            rad[a] = rv;
+            zat[a] = zs[e];
+            for (int k = 0; k < 3; ++k) {
+                const float v = pos[ga * 3 + k];
+                if (!finite_f(v)) bad |= LP_BAD_INPUT;
+                x0[3 * a + k] = v;
+                x[3 * a + k] = (double)v;
+            }
+        }
+        for (int j = tid; j < np; j += VM_T) {       // every pocket atom is checked, the first `stage` are kept
+            const float *r = pocket_x + (size_t)(q0 + j) * 3;
+            const float rv = pocket_radius[q0 + j];
+            const int tj = pocket_type[q0 + j];
+            if (!(finite_f(r[0]) && finite_f(r[1]) && finite_f(r[2]) && finite_f(rv))) bad |= LP_BAD_INPUT;
+            if (tj < 0 || !(rv > 0.0f)) atom_out = 1;
+            if (j < stage) {
+                px[3 * j] = r[0];
+                px[3 * j + 1] = r[1];
+                px[3 * j + 2] = r[2];
+                prad[j] = rv;
+                ptyp[j] = tj;
+            }
+        }
+        st = lp_votes(bad);
+    }
+    int n_frag = 0;
+    if (!st) {                                       // the bond graph (integer atomics: no order), the fragments
+        int bad = 0, top = 0;
+        for (int k = p0 + tid; k < p1; k += VM_T) {
+            const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0, o = bond_order[k];
+            if (i < 0 || j >= n || i >= j || o < 1 || o > 3) {      // bond_ij holds i < j: a bond listed both ways round cannot hide from `was`
+                bad = 1;
+                continue;
+            }
+            const int zi = zat[i], zj = zat[j];
+            if (!(element_row(zi) & 0xffu) || !(element_row(zj) & 0xffu) || frg[i] != frg[j]) {      // never bonded; two fragments
+                bad = 1;
+                continue;
+            }
+            const unsigned was = atomicOr(&adj[i * W + (j >> 5)], 1u << (j & 31));
+            atomicOr(&adj[j * W + (i >> 5)], 1u << (i & 31));
+            if (was & (1u << (j & 31))) bad = 1;     // a bond twice
+            const unsigned ci = atomicAdd(&cnt[i], 1u + (zj != 1 ? 16u : 0u)), cj = atomicAdd(&cnt[j], 1u + (zi != 1 ? 16u : 0u));
+            if ((ci & 15u) >= (unsigned)MOL_DEG || (cj & 15u) >= (unsigned)MOL_DEG) bad = 1;      // a seventh neighbour
+            if (zj != 1) atomicOr(&flg[i], (zj != 6 ? VM_HETERO : 0u) | (1u << o));
+            if (zi != 1) atomicOr(&flg[j], (zi != 6 ? VM_HETERO : 0u) | (1u << o));
+        }
+        for (int a = tid; a < n; a += VM_T) {
+            const int fl = frg[a];
+            top = max(top, fl);
+            if (fl < VM_FRAGS) {
+                atomicMin(&flow[fl], a);
+                atomicAdd(&fcnt[fl], 1);
+                atomicOr(&fset[fl * W + (a >> 5)], 1u << (a & 31));
+            }
+        }
+        st = __syncthreads_or(bad) ? LP_NO_MOLECULE : 0;
+        const int many = __syncthreads_or(top >= VM_FRAGS);
+        if (!st && many) st = VM_FRAGMENTS;
+        if (!st) {                                   // labels 0 .. n_frag - 1, every one of them used
+            int hole = 0;
+            for (int f = 0; f < VM_FRAGS; ++f) {
+                if (fcnt[f]) {
+                    if (f != n_frag) hole = 1;
+                    ++n_frag;
+                }
+            }
+            if (hole) st = LP_NO_MOLECULE;
+        }
+    }
+    if (st) {                                        // left out: pos_out keeps the input rows the host copied
+        if (tid < 16) report[(size_t)b * 16 + tid] = 0.0;
+        if (tid == 0) status[b] = st;
+        return;
+    }
+    // ---- types
+    for (int a = tid; a < n; a += VM_T) {
+        const int z = zat[a];
+        int f = vm_flags(z, (int)((cnt[a] >> 4) & 15u), flg[a]);
+        if (lig_type_in) {
+            const int over = lig_type_in[a0 + a];
+            if (over >= 0) f = over & 7;
+        }
+        const int t = (z == 1 || !(rad[a] > 0.0f)) ? -1 : f;
+        if (t < 0) atom_out = 1;
+        typ[a] = t;
+    }
+    // ---- rotors in bond order: single bonds between atoms of heavy degree >= 2 that are in no ring
+    const int nb = min(p1 - p0, 3 * nm);             // a graph that passed the checks has at most 3 n bonds
+    for (int k = tid; k < nb; k += VM_T) {
+        int is = 0;
+        if (bond_order[p0 + k] == 1) {
+            const int i = bond_ij[(size_t)(p0 + k) * 2] - a0, j = bond_ij[(size_t)(p0 + k) * 2 + 1] - a0;
+            if (((cnt[i] >> 4) & 15u) >= 2u && ((cnt[j] >> 4) & 15u) >= 2u) {
+                unsigned vis[MOL_W];
+                vm_reach(adj, W, j, i, vis);
+                unsigned hit = 0;
+#pragma unroll
+                for (int w = 0; w < MOL_W; ++w)
+                    if (w == (i >> 5)) hit = vis[w] & (1u << (i & 31));
+                is = hit ? 0 : 1;
+            }
+        }
+        rflag[k] = (unsigned char)is;
+    }
+    if (__syncthreads_or(atom_out)) st |= VM_ATOM_OUT;   // also orders typ and rflag before their readers
+    int *redi = reinterpret_cast<int *>(red);
+    if (wv == 0) {                                   // the first max_rotors of them are active
+        int base = 0;
+        for (int c = 0; c < nb; c += 64) {
+            const int k = c + lane;
+            const int is = k < nb ? rflag[k] : 0;
+            const unsigned long long m = __ballot(is);
+            const int rank = base + __popcll(m & ((1ull << lane) - 1ull));
+            if (is && rank < max_rotors) {
+                ra[rank] = bond_ij[(size_t)(p0 + k) * 2] - a0;
+                rb[rank] = bond_ij[(size_t)(p0 + k) * 2 + 1] - a0;
+            }
+            base += __popcll(m);
+        }
+        if (lane == 0) redi[0] = base;
+    }
+    __syncthreads();
+    const int n_rot = redi[0], T = min(n_rot, max_rotors), D = 6 * n_frag + T;
+    if (n_rot > T) st |= VM_FROZEN;
+    const double inv_norm = 1.0 / (1.0 + P.w_rot * (double)n_rot);
+    // ---- the moved set of every active rotor (i, j): the side of j, or the rest of the fragment when that side holds its lowest atom
+    for (int a = tid; a < n; a += VM_T)
+        for (int w = 0; w < W; ++w) adjp[a * W + w] = adj[a * W + w];
+    if (tid < T) {
+        const int i = ra[tid], j = rb[tid], low = flow[frg[j]];
+        unsigned vis[MOL_W];
+        vm_reach(adj, W, j, i, vis);
+        unsigned hit = 0;
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w)
+            if (w == (low >> 5)) hit = vis[w] & (1u << (low & 31));
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w) {
+            if (w >= W) continue;
+            mset[tid * W + w] = hit ? fset[frg[j] * W + w] & ~vis[w] : vis[w];
+        }
+        if (hit) {                                   // b is the end that moves, a the other one
+            ra[tid] = j;
+            rb[tid] = i;
+        }
+    }
+    __syncthreads();
+    if (tid < T) {                                   // pieces: the graph without the active rotor bonds
+        const int i = ra[tid], j = rb[tid];
+        atomicAnd(&adjp[i * W + (j >> 5)], ~(1u << (j & 31)));
+        atomicAnd(&adjp[j * W + (i >> 5)], ~(1u << (i & 31)));
+        int d = 0;
+        for (int k = 0; k < T; ++k) d += vm_bit(mset + k * W, rb[tid]) ? 1 : 0;
+        depth[tid] = d;
+    }
+    for (int a = tid; a < n; a += VM_T) piece[a] = a;
+    __syncthreads();
+    if (tid == 0) {                                  // rotors from the deepest to the shallowest, by index within one depth
+        for (int k = 0; k < T; ++k) {
+            int c = k;
+            while (c > 0 && depth[ord[c - 1]] < depth[k]) {
+                ord[c] = ord[c - 1];
+                --c;
+            }
+            ord[c] = k;
+        }
+    }
+    // Label propagation: the fixed point is the lowest atom of every piece.  A sweep reads labels that other threads are lowering in
+    // the same sweep (aligned 32-bit words, no barrier between): a label only ever decreases and always names an atom of the same
+    // piece, so a stale read merely delays the descent, and the loop ends on a sweep in which nobody wrote, which has no race.  The
+    // result does not depend on the interleaving.
+    for (;;) {
+        int changed = 0;
+        for (int a = tid; a < n; a += VM_T) {
+            int l = piece[a];
+            const int before = l;
+            for (int w = 0; w < W; ++w) {
+                unsigned bits = adjp[a * W + w];
+                while (bits) {
+                    l = min(l, piece[32 * w + __ffs(bits) - 1]);
+                    bits &= bits - 1;
+                }
+            }
+            l = min(l, piece[l]);
+            if (l != before) {
+                piece[a] = l;
+                changed = 1;
+            }
+        }
+        if (!__syncthreads_or(changed)) break;
+    }
+    // ---- intramolecular pairs: both atoms take part, different pieces, four or more bonds apart or not connected
+    for (int a = tid; a < n; a += VM_T) {
+        unsigned e1[MOL_W], e2[MOL_W], e3[MOL_W];
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w) {
+            e1[w] = w < W ? adj[a * W + w] : 0u;
+            if (w == (a >> 5)) e1[w] |= 1u << (a & 31);
+            e2[w] = e1[w];
+        }
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w) {
+            unsigned bits = e1[w];
+            while (bits) {
+                const int j = 32 * w + __ffs(bits) - 1;
+                bits &= bits - 1;
+#pragma unroll
+                for (int v = 0; v < MOL_W; ++v)
+                    if (v < W) e2[v] |= adj[j * W + v];
+            }
+        }
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w) e3[w] = e2[w];
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w) {
+            unsigned bits = e2[w];
+            while (bits) {
+                const int j = 32 * w + __ffs(bits) - 1;
+                bits &= bits - 1;
+#pragma unroll
+                for (int v = 0; v < MOL_W; ++v)
+                    if (v < W) e3[v] |= adj[j * W + v];
+            }
+        }
+        const int pa = piece[a];
+        const bool on = typ[a] >= 0;
+#pragma unroll
+        for (int w = 0; w < MOL_W; ++w) {
+            if (w >= W) continue;
+            unsigned m = 0;
+            for (int j = 32 * w; j < min(n, 32 * w + 32); ++j)
+                if (on && typ[j] >= 0 && piece[j] != pa) m |= 1u << (j & 31);
+            imask[a * W + w] = m & ~e3[w];
+        }
+    }
+    __syncthreads();
+
+    VinaMinCtx C;
+    C.n = n;
+    C.np = np;
+    C.stage = stage;
+    C.W = W;
+    C.F = n_frag;
+    C.T = T;
+    C.D = D;
+    C.rad = rad;
+    C.px = px;
+    C.prad = prad;
+    C.gpx = pocket_x + (size_t)q0 * 3;
+    C.gpr = pocket_radius + q0;
+    C.typ = typ;
+    C.ptyp = ptyp;
+    C.gpt = pocket_type + q0;
+    C.frg = frg;
+    C.ra = ra;
+    C.rb = rb;
+    C.ord = ord;
+    C.fcnt = fcnt;
+    C.imask = imask;
+    C.mset = mset;
+    C.part = reinterpret_cast<double *>(lds + L.part);
+    C.scal = scal;
+    C.red = red;
+    C.cen = reinterpret_cast<double *>(lds + L.cen);
+    C.axu = reinterpret_cast<double *>(lds + L.axu);
+    C.trig = reinterpret_cast<double *>(lds + L.trig);
+    C.body = reinterpret_cast<double *>(lds + L.body);
+    C.P = P;
+
+    const int N3 = 3 * n;
+    vm_eval(C, x, g, tid);
+    double inter = scal[VS_INTER], intra = scal[VS_INTRA], E = scal[VS_E];
+    vm_project(C, x, g, gd, tid);
+    double gnorm = scal[VS_GNORM];
+    const double E_before = E, inter_before = inter, intra_before = intra, gnorm_before = gnorm;
+    int m = 0, head = 0, iters = 0, evals = 1;
+    double gamma = 1.0;
+    for (int it = 0; it < P.max_iters; ++it) {
+        if (gnorm <= P.gtol) break;
+        ++iters;
+        if (wv == 0) vm_direction(gd, S, Y, rho, DS, D, m, head, gamma, p, scal, lane);
+        __syncthreads();
+        if (scal[VS_RESET] != 0.0) m = 0;
+        const double gp = scal[VS_GP];
+        const double vmax = vm_vmax(C, x, p, tid);
+        double alpha = fmin(1.0, P.max_step / vmax);
+        bool accepted = false;
+        for (int ls = 0; ls <= 20; ++ls) {
+            vm_move(C, x, p, alpha, xt, tid);
+            vm_eval(C, xt, g, tid);
+            ++evals;
+            const double Et = scal[VS_E];
+            if (fabs(Et) < __builtin_inf() && Et <= E + 1e-4 * alpha * gp) {
+                accepted = true;
+                break;
+            }
+            alpha *= 0.5;
+        }
+        if (!accepted) {
+            if (m) {                                 // try again along -g
+                m = 0;
+                continue;
+            }
+            st |= VM_LINE_SEARCH;
+            break;
+        }
+        E = scal[VS_E];
+        inter = scal[VS_INTER];
+        intra = scal[VS_INTRA];
+        vm_project(C, xt, g, gdt, tid);              // the new point's own chart
+        gnorm = scal[VS_GNORM];
+        for (int d = tid; d < D; d += VM_T) {
+            S[head * DS + d] = alpha * p[d];
+            Y[head * DS + d] = gdt[d] - gd[d];
+        }
+        __syncthreads();
+        if (wv == 0) {
+            const double sy = vm_dot(S + head * DS, Y + head * DS, D, lane), yy = vm_dot(Y + head * DS, Y + head * DS, D, lane),
+                         gg = vm_dot(gdt, gdt, D, lane);
+            if (lane == 0) {
+                scal[VS_SY] = sy;
+                scal[VS_YY] = yy;
+                scal[VS_GG] = gg;
+            }
+        }
+        __syncthreads();
+        const double sy = scal[VS_SY], yy = scal[VS_YY], gg = scal[VS_GG];
+        if (sy > 1e-10 * yy && yy > 1e-20 * gg) {       // the second test: where the energy is linear, y is rounding noise
+            if (tid == 0) rho[head] = 1.0 / sy;
+            gamma = sy / yy;
+            head = (head + 1) & (VM_M - 1);
+            m = min(m + 1, VM_M);
+        }
+        double *sw = x;
+        x = xt;
+        xt = sw;
+        sw = gd;
+        gd = gdt;
+        gdt = sw;
+        __syncthreads();                             // rho is read, and scal written again, only behind this
+    }
+    // The report describes the rows written: where the ligand moved, the score is evaluated once more at the fp32-rounded
+    // positions.  Should that rounding alone turn the (then tiny) gain into a rise, the ligand keeps its input rows.
+    bool keep = false;
+    if (iters) {
+        for (int k = tid; k < N3; k += VM_T) xt[k] = (double)(float)x[k];
+        __syncthreads();
+        vm_eval(C, xt, g, tid);
+        ++evals;
+        keep = scal[VS_E] <= E_before;
+        E = keep ? scal[VS_E] : E_before;
+        inter = keep ? scal[VS_INTER] : inter_before;
+        intra = keep ? scal[VS_INTRA] : intra_before;
+        vm_project(C, xt, g, gdt, tid);
+        gnorm = keep ? scal[VS_GNORM] : gnorm_before;
+    }
+    if (gnorm > P.gtol && !(st & VM_LINE_SEARCH)) st |= VM_ITER_CAP;
+
+    double sq = 0.0;
+    for (int k = tid; k < N3; k += VM_T) {
+        const float v = keep ? (float)xt[k] : x0[k];
+        pos_out[(size_t)a0 * 3 + k] = v;
+        const double d = (double)v - (double)x0[k];
+        sq += d * d;
+    }
+    sq = wave_sum(sq);
+    if (lane == 0) red[wv] = sq;
+    __syncthreads();
+    if (tid == 0) {
+        double *r = report + (size_t)b * 16;
+        r[0] = inter_before * inv_norm;
+        r[1] = inter * inv_norm;
+        r[2] = E_before;
+        r[3] = E;
+        r[4] = inter_before;
+        r[5] = inter;
+        r[6] = intra_before;
+        r[7] = intra;
+        r[8] = sqrt((((red[0] + red[1]) + red[2]) + red[3]) / (double)n);
+        r[9] = gnorm_before;
+        r[10] = gnorm;
+        r[11] = (double)iters;
+        r[12] = (double)evals;
+        r[13] = (double)n_rot;
+        r[14] = (double)T;
+        r[15] = (double)n_frag;
+        status[b] = st;
+    }
+}
+
+}  // namespace kpd
+
+using namespace kpd;
+
+extern "C" kpd_status kpd_vina_minimize(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, int32_t max_atoms,
+                                        const int32_t *elem, int32_t F, const int32_t *z, const float *lig_radius, const int32_t *frag,
+                                        const int32_t *bond_ij, const int32_t *bond_order, const int32_t *bond_ptr, int32_t cap_bonds,
+                                        const int32_t *mol_status, const int32_t *lig_type_in, const float *pocket_x,
+                                        const float *pocket_radius, const int32_t *pocket_type, const int32_t *pocket_ptr,
+                                        int32_t n_pocket, int32_t P, int32_t max_pocket, const int32_t *pocket_of, int32_t max_rotors,
+                                        const kpd_vina_min_params *params, float *pos_out, double *report, int32_t *status,
+                                        void *stream) {
+    KPD_TRY(ligand_pocket_args(n_atoms, B, max_atoms, F, cap_bonds, n_pocket, P, max_pocket, lig_ptr && z && lig_radius && bond_ptr,
+                               pos && elem && frag && pos_out, mol_status && pocket_of && report && status, bond_ij && bond_order,
+                               pocket_ptr, pocket_x && pocket_radius && pocket_type));
+    KPD_REQUIRE(max_rotors >= 0 && max_rotors <= VM_ROTORS, KPD_ERR_INVALID, "max_rotors=%d (0 .. %d)", max_rotors, VM_ROTORS);
+    kpd_vina_min_params d;
+    kpd_vina_min_defaults(&d);
+    if (params) d = *params;
+    const double ws[5] = {d.w_gauss1, d.w_gauss2, d.w_repulsion, d.w_hydrophobic, d.w_hbond};
+    bool ok = d.r_c > 0.0 && d.r_c < 1e6 && d.w_rot >= 0.0 && d.w_rot < 1e12 && d.w_intra >= 0.0 && d.w_intra < 1e12 && d.gtol >= 0.0 &&
+              d.max_step > 0.0 && d.max_iters >= 0;
+    for (double w : ws) ok = ok && w > -1e12 && w < 1e12;
+    KPD_REQUIRE(ok, KPD_ERR_INVALID, "weights %g %g %g %g %g (finite) w_rot=%g w_intra=%g gtol=%g (>= 0) r_c=%g max_step=%g (> 0) max_iters=%d",
+                ws[0], ws[1], ws[2], ws[3], ws[4], d.w_rot, d.w_intra, d.gtol, d.r_c, d.max_step, d.max_iters);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n_atoms && pos_out != pos) KPD_HIP(hipMemcpyAsync(pos_out, pos, (size_t)n_atoms * 12, hipMemcpyDeviceToDevice, st));
+    if (!B) return KPD_OK;
+    VinaMinP vp;
+    for (int k = 0; k < 5; ++k) vp.w[k] = ws[k];
+    vp.w_rot = d.w_rot;
+    vp.rc2 = d.r_c * d.r_c;
+    vp.w_intra = d.w_intra;
+    vp.gtol = d.gtol;
+    vp.max_step = d.max_step;
+    vp.max_iters = d.max_iters;
+    // as much of the largest pocket as fits beside the state of a max_atoms ligand
+    const int stage = stage_rows(vina_min_layout(max_atoms, max_rotors, 0).bytes, VM_LDS, VM_POCKET_ROW, max_pocket);
+    KPD_REQUIRE(stage >= 0, KPD_ERR_INVALID, "no LDS for %d atoms", max_atoms);
+    const VinaMinLayout L = vina_min_layout(max_atoms, max_rotors, stage);
+    KPD_REQUIRE(L.bytes <= (size_t)VM_LDS, KPD_ERR_INVALID, "LDS layout of %zu bytes", L.bytes);
+    KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_vina_minimize), (int)L.bytes));
+    hipLaunchKernelGGL(k_vina_minimize, dim3(B), dim3(VM_T), L.bytes, st, pos, lig_ptr, n_atoms, max_atoms, elem, F, z, lig_radius, frag,
+                       bond_ij, bond_order, bond_ptr, cap_bonds, mol_status, lig_type_in, pocket_x, pocket_radius, pocket_type, pocket_ptr,
+                       n_pocket, P, stage, pocket_of, max_rotors, vp, pos_out, report, status);
+    KPD_LAUNCH_CHECK();
+    return KPD_OK;
+}
+
+extern "C" void kpd_vina_min_defaults(kpd_vina_min_params *p) {
+    if (!p) return;
+    kpd_vina_params v;
+    kpd_vina_defaults(&v);
+    p->w_gauss1 = v.w_gauss1;
+    p->w_gauss2 = v.w_gauss2;
+    p->w_repulsion = v.w_repulsion;
+    p->w_hydrophobic = v.w_hydrophobic;
+    p->w_hbond = v.w_hbond;
+    p->w_rot = v.w_rot;
+    p->r_c = v.r_c;
+    p->w_intra = 1.0;
+    p->gtol = 1e-3;
+    p->max_step = 0.2;
+    p->max_iters = 200;
+}

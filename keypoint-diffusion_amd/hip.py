@@ -93,6 +93,11 @@ class KpdVinaParams(C.Structure):
     _fields_ = [(name, C.c_double) for name in ('w_gauss1', 'w_gauss2', 'w_repulsion', 'w_hydrophobic', 'w_hbond', 'w_rot', 'r_c')]
 
 
+class KpdVinaMinParams(C.Structure):
+    _fields_ = ([(name, C.c_double) for name in ('w_gauss1', 'w_gauss2', 'w_repulsion', 'w_hydrophobic', 'w_hbond', 'w_rot', 'r_c', 'w_intra',
+                                                  'gtol', 'max_step')] + [('max_iters', C.c_int32)])
+
+
 class KpdError(RuntimeError):
     pass
 
@@ -208,6 +213,11 @@ def lib():
     L.kpd_vina_score.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 +
                                  [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.POINTER(KpdVinaParams)] +
                                  [C.c_void_p] * 6)
+    L.kpd_vina_min_defaults.argtypes = [C.POINTER(KpdVinaMinParams)]
+    L.kpd_vina_min_defaults.restype = None
+    L.kpd_vina_minimize.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 +
+                                    [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.POINTER(KpdVinaMinParams)] +
+                                    [C.c_void_p] * 4)
     _lib = L
     return L
 
@@ -240,7 +250,7 @@ EXPORTS = [
     'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
     'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
     'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_relax_defaults', 'kpd_relax',
-    'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score',
+    'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score', 'kpd_vina_min_defaults', 'kpd_vina_minimize',
 ]
 
 
@@ -1265,6 +1275,62 @@ def vina_score(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch.Te
                                _ptr(out['report']), _ptr(out.get('grad')), _ptr(out.get('atom_score')), _ptr(out['lig_type']),
                                _ptr(out['status']), _stream()))
     return out
+
+
+# status bits of kpd_vina_minimize (bits 0 .. 2 as for kpd_vina_score)
+VINA_MIN_NO_MOLECULE, VINA_MIN_BAD_INPUT, VINA_MIN_ATOM_OUT, VINA_MIN_LINE_SEARCH = 1, 2, 4, 8
+VINA_MIN_FROZEN_ROTORS, VINA_MIN_FRAGMENTS, VINA_MIN_ITER_CAP = 16, 32, 64
+VINA_MIN_REPORT = ('score_before', 'score_after', 'E_before', 'E_after', 'inter_before', 'inter_after', 'intra_before', 'intra_after',
+                   'rmsd', 'gnorm_before', 'gnorm_after', 'iterations', 'evaluations', 'n_rot', 'n_active', 'n_frag')
+VINA_MIN_MAX_ROTORS = 64
+
+
+def vina_min_params(**params) -> KpdVinaMinParams:
+    """The parameters of kpd_vina_minimize: the library's defaults (kpd_vina_min_defaults: those of kpd_vina_score, w_intra 1,
+    gtol 1e-3, max_step 0.2, max_iters 200) with the given fields replaced."""
+    p, names = _struct_params('vina_minimize', KpdVinaMinParams, lib().kpd_vina_min_defaults, params, ints=('max_iters',))
+    if not (all(abs(getattr(p, k)) < 1e12 for k in names) and 0 < p.r_c < 1e6 and p.w_rot >= 0 and p.w_intra >= 0 and p.gtol >= 0 and
+            p.max_step > 0 and p.max_iters >= 0):
+        raise KpdError('vina_minimize: ' + ', '.join(f'{k} {getattr(p, k)}' for k in names) +
+                       ': the weights must be finite, w_rot, w_intra, gtol and max_iters >= 0, r_c and max_step > 0')
+    return p
+
+
+def vina_minimize(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch.Tensor, mol: dict, pocket_x: torch.Tensor,
+                  pocket_radius: torch.Tensor, pocket_type: torch.Tensor, pocket_ptr: torch.Tensor, pocket_of: torch.Tensor,
+                  lig_type_in: Optional[torch.Tensor] = None, max_atoms: int = MOL_MAX_ATOMS, max_pocket: Optional[int] = None,
+                  max_rotors: int = VINA_MIN_MAX_ROTORS, **params):
+    """Minimise a batch of perceived ligands in their rigid pockets under the score of `vina_score`, over rigid-body and torsional
+    degrees of freedom, on the GPU in one launch (kpd_vina_minimize; include/kpd.h states the torsion tree, the chart, the
+    intramolecular term and the minimiser: this library's own, NOT gnina's or Vina's numbers).  The arguments are those of
+    `vina_score`, with `mol` also holding 'frag'; max_rotors (0 .. 64): the rotors beyond it are frozen, 0 = rigid bodies only.
+    Returns (pos_out [N,3] fp32, report [B,16] float64 with the columns VINA_MIN_REPORT, status [B] int32).  No host
+    synchronisation."""
+    pos, pocket_x, pocket_of, B, N, F, M, P, zt, max_atoms, max_pocket = _ligand_pocket_args(
+        'vina_minimize', pos, lig_ptr, z, mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'), pocket_x, pocket_ptr, pocket_of,
+        max_atoms, max_pocket)
+    lig_radius, pocket_radius = _dev_f32(lig_radius, 'lig_radius'), _dev_f32(pocket_radius, 'pocket_radius')
+    pocket_type = _per_entry(pocket_type, 'vina_minimize: pocket_type', M, 'pocket atom')
+    if lig_type_in is not None:
+        lig_type_in = _per_entry(lig_type_in, 'vina_minimize: lig_type_in', N, 'ligand atom')
+    cap_bonds = mol['order'].numel()
+    max_rotors = int(max_rotors)
+    if (lig_radius.shape != (F,) or pocket_radius.shape != (M,) or mol['bonds'].numel() != 2 * cap_bonds or mol['frag'].numel() != N or
+            not 0 <= max_rotors <= VINA_MIN_MAX_ROTORS):
+        raise KpdError(f'vina_minimize: lig_radius {tuple(lig_radius.shape)} must be [{F}], pocket_radius {tuple(pocket_radius.shape)} '
+                       f'[{M}], frag hold {N} labels, bonds two atoms for each of the {cap_bonds} orders, and max_rotors {max_rotors} '
+                       f'be 0 .. {VINA_MIN_MAX_ROTORS}')
+    p = vina_min_params(**params)
+    dev = pos.device
+    pos_out = torch.empty_like(pos)
+    report = torch.empty(B, 16, dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib().kpd_vina_minimize(_ptr(pos), _ptr(lig_ptr), N, B, max_atoms, _ptr(mol['elem']), F, _ptr(zt), _ptr(lig_radius),
+                                  _ptr(mol['frag']), _ptr(mol['bonds']), _ptr(mol['order']), _ptr(mol['bond_ptr']), cap_bonds,
+                                  _ptr(mol['status']), _ptr(lig_type_in), _ptr(pocket_x), _ptr(pocket_radius), _ptr(pocket_type),
+                                  _ptr(pocket_ptr), M, P, max_pocket, _ptr(pocket_of), max_rotors, C.byref(p), _ptr(pos_out),
+                                  _ptr(report), _ptr(status), _stream()))
+    return pos_out, report, status
 
 
 def sample_update(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h, coef):

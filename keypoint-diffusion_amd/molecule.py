@@ -286,6 +286,26 @@ class Molecules:
                                         max_atoms=max_atoms, max_pocket=max(sizes, default=0), **params)
         return Relaxed(self, pos, report, status)
 
+    def _vina_inputs(self, where: str, what: str, pocket_pos, pocket_elements, pocket_of, radii, pocket_types, lig_types):
+        """What `vina_score` and `vina_minimize` share beyond `_in_pockets`: the radius tables, the pocket types (perceived once, or
+        the caller's, normalised to one [M] int32 device tensor) and the ligand type overrides.  Returns the tuple of `_in_pockets`
+        followed by the device, lig_radius [F], pocket_radius [M], pocket_types [M] and lig_types ([N] or None)."""
+        pocket_x, pocket_ptr, pocket_of, sizes, z, max_atoms = self._in_pockets(where, what, pocket_pos, pocket_elements, pocket_of)
+        dev = self.pos.device
+        lig_radius = torch.tensor(xs_radius_table(self.lig_elements, radii), dtype=torch.float32, device=dev)
+        pocket_radius = torch.tensor([r for els in pocket_elements for r in xs_radius_table(els, radii)], dtype=torch.float32, device=dev)
+        if pocket_types is None:
+            pz = torch.tensor([ATOMIC_NUMBERS.get(el, 0) for els in pocket_elements for el in els], dtype=torch.int32, device=dev)
+            pocket_types, _ = hip.vina_pocket_types(pocket_x, pz, pocket_ptr)
+        else:
+            if not isinstance(pocket_types, torch.Tensor):
+                pocket_types = torch.tensor([int(t) for row in pocket_types for t in row], dtype=torch.int32)
+            pocket_types = pocket_types.to(torch.int32).to(dev).flatten()
+            if pocket_types.numel() != sum(sizes):
+                raise hip.KpdError(f'{where}: pocket_types has {pocket_types.numel()} entries for {sum(sizes)} pocket atoms')
+        if lig_types is not None:
+            lig_types = torch.as_tensor(lig_types).to(torch.int32).to(dev).flatten()
+        return pocket_x, pocket_ptr, pocket_of, sizes, z, max_atoms, dev, lig_radius, pocket_radius, pocket_types, lig_types
 
     def vina_score(self, pocket_pos: List[torch.Tensor], pocket_elements: List[Sequence[str]], pocket_of=None,
                    radii: Optional[Dict[str, float]] = None, pocket_types=None, lig_types: Optional[torch.Tensor] = None,
@@ -298,21 +318,8 @@ class Molecules:
         2 donor, 4 acceptor, -1 takes no part) as one sequence per pocket or one [M] tensor, in place of the perceived ones;
         `lig_types`: [N] int32 whose entries >= 0 replace the perceived ligand flags; `grad`: also return the gradient and the
         per-atom scores; `params`: w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond, w_rot, r_c."""
-        pocket_x, pocket_ptr, pocket_of, sizes, z, max_atoms = self._in_pockets('vina_score', 'scoring', pocket_pos, pocket_elements, pocket_of)
-        dev = self.pos.device
-        lig_radius = torch.tensor(xs_radius_table(self.lig_elements, radii), dtype=torch.float32, device=dev)
-        pocket_radius = torch.tensor([r for els in pocket_elements for r in xs_radius_table(els, radii)], dtype=torch.float32, device=dev)
-        if pocket_types is None:
-            pz = torch.tensor([ATOMIC_NUMBERS.get(el, 0) for els in pocket_elements for el in els], dtype=torch.int32, device=dev)
-            pocket_types, _ = hip.vina_pocket_types(pocket_x, pz, pocket_ptr)
-        else:
-            if not isinstance(pocket_types, torch.Tensor):
-                pocket_types = torch.tensor([int(t) for row in pocket_types for t in row], dtype=torch.int32)
-            pocket_types = pocket_types.to(torch.int32).to(dev).flatten()
-            if pocket_types.numel() != sum(sizes):
-                raise hip.KpdError(f'vina_score: pocket_types has {pocket_types.numel()} entries for {sum(sizes)} pocket atoms')
-        if lig_types is not None:
-            lig_types = torch.as_tensor(lig_types).to(torch.int32).to(dev).flatten()
+        (pocket_x, pocket_ptr, pocket_of, sizes, z, max_atoms, dev, lig_radius, pocket_radius, pocket_types,
+         lig_types) = self._vina_inputs('vina_score', 'scoring', pocket_pos, pocket_elements, pocket_of, radii, pocket_types, lig_types)
         mol = dict(elem=self.elem, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
         if len(self) == 0:
             empty = dict(report=torch.zeros(0, 8, dtype=torch.float64, device=dev), status=torch.zeros(0, dtype=torch.int32, device=dev),
@@ -322,6 +329,55 @@ class Molecules:
                              lig_type_in=lig_types, grad=grad, atom_score=grad, max_atoms=max_atoms, max_pocket=max(sizes, default=0),
                              **params)
         return VinaScores(self, out, pocket_types)
+
+    def vina_minimize(self, pocket_pos: List[torch.Tensor], pocket_elements: List[Sequence[str]], pocket_of=None,
+                      radii: Optional[Dict[str, float]] = None, pocket_types=None, lig_types: Optional[torch.Tensor] = None,
+                      max_rotors: Optional[int] = None, **params) -> 'VinaMinimized':
+        """Minimise every ligand in its rigid pocket under the score of `vina_score`, over rigid-body and torsional degrees of
+        freedom, all in one launch (`kpd_vina_minimize`): what upstream does with `gnina --minimize` (gen_docking_cmds.py
+        --minimize), with the torsion tree, the intramolecular term and the L-BFGS include/kpd.h defines.  NOT gnina's or Vina's
+        numbers: the typing, the weights and the radii are those of `vina_score`.
+        `pocket_pos`, `pocket_elements`, `pocket_of`, `radii`, `pocket_types`, `lig_types`: as for `vina_score`; `max_rotors`
+        (0 .. 64, 64 by default): the rotors beyond it are frozen, 0 minimises rigid bodies only; `params`: the parameters of
+        `vina_score` and w_intra, gtol, max_step, max_iters."""
+        (pocket_x, pocket_ptr, pocket_of, sizes, z, max_atoms, dev, lig_radius, pocket_radius, pocket_types,
+         lig_types) = self._vina_inputs('vina_minimize', 'minimisation', pocket_pos, pocket_elements, pocket_of, radii, pocket_types, lig_types)
+        mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
+        if len(self) == 0:
+            return VinaMinimized(self, self.pos, torch.zeros(0, 16, dtype=torch.float64, device=dev),
+                                 torch.zeros(0, dtype=torch.int32, device=dev), pocket_types)
+        pos, report, status = hip.vina_minimize(self.pos, self.lig_ptr, z, lig_radius, mol, pocket_x, pocket_radius, pocket_types, pocket_ptr,
+                                                pocket_of, lig_type_in=lig_types, max_atoms=max_atoms, max_pocket=max(sizes, default=0),
+                                                max_rotors=hip.VINA_MIN_MAX_ROTORS if max_rotors is None else max_rotors, **params)
+        return VinaMinimized(self, pos, report, status, pocket_types)
+
+
+class VinaMinimized:
+    """What `Molecules.vina_minimize` returns: `.molecules` (a `Molecules` with the same bond graph at the minimised pose, so its
+    `.sdf()` blocks are the counterpart of upstream's gen_ligands_gnina_minimized.sdf and `.vina_score(...)` gives the five terms
+    there), `.pos` (a list of per-ligand [n_i,3] tensors), `.report` [B,16] float64 (columns hip.VINA_MIN_REPORT), `.status` [B]
+    (bits: 1 no molecule, 2 bad input, 4 some atom took no part, 8 line search exhausted, 16 rotors frozen, 32 more than 8
+    fragments, 64 max_iters reached before gtol; with 1, 2 or 32 the ligand is unchanged) and `.pocket_types` [M], device tensors.
+    NOT gnina's or Vina's numbers: see include/kpd.h."""
+
+    def __init__(self, mols: Molecules, pos: torch.Tensor, report: torch.Tensor, status: torch.Tensor, pocket_types: torch.Tensor):
+        self.molecules = Molecules(mols.lig_ptr, mols.summary, mols.status, mols.elem, mols.valence, mols.frag, mols.bonds, mols.order,
+                                   mols.bond_ptr, pos, mols.lig_elements, mols._max_atoms)
+        self.report, self.status, self.pocket_types, self._sizes = report, status, pocket_types, mols._sizes
+
+    @property
+    def pos(self) -> List[torch.Tensor]:
+        sizes = self._sizes if self._sizes is not None else (self.molecules.lig_ptr[1:] - self.molecules.lig_ptr[:-1]).tolist()
+        return list(torch.split(self.molecules.pos, sizes))
+
+    def table(self) -> Dict[str, list]:
+        """lig_idx, score_before, score_after, rmsd, n_rot, iterations, as lists; ligands that were left out (status bit 0, 1 or 5)
+        have no row, as in `Relaxed.table`."""
+        st, rep = self.status.cpu(), self.report.cpu()
+        out_bits = hip.VINA_MIN_NO_MOLECULE | hip.VINA_MIN_BAD_INPUT | hip.VINA_MIN_FRAGMENTS
+        keep = ((st & out_bits) == 0).nonzero().flatten().tolist()
+        return dict(lig_idx=keep, score_before=rep[keep, 0].tolist(), score_after=rep[keep, 1].tolist(), rmsd=rep[keep, 8].tolist(),
+                    n_rot=[int(v) for v in rep[keep, 13].tolist()], iterations=[int(v) for v in rep[keep, 11].tolist()])
 
 
 class Relaxed:
@@ -517,3 +573,36 @@ def score_samples(samples: List[dict], pockets: List[dict], lig_elements: Sequen
     after = relaxed.molecules.vina_score(pocket_pos, pocket_elements, pocket_of=pocket_of, radii=radii, pocket_types=raw.pocket_types,
                                          grad=grad, **(vina or {}))
     return raw, after, relaxed
+
+
+def minimize_samples(samples: List[dict], pockets: List[dict], lig_elements: Sequence[str], device=None, relax: bool = False,
+                     allowed_bonds: Optional[Dict[str, object]] = None, radii: Optional[Dict[str, float]] = None,
+                     vdw: Optional[Dict[str, tuple]] = None, pocket_types=None, max_rotors: Optional[int] = None,
+                     relax_params: Optional[Dict[str, float]] = None, **params):
+    """Minimise every sampled ligand in its own pocket under the Vina-form score (`Molecules.vina_minimize`, whose limits apply:
+    NOT gnina's numbers), in the mould of `relax_samples`: the counterpart of upstream's gen_docking_cmds.py --minimize.
+    `samples` is the list of {'positions', 'features'} dicts `_sample` returns, one per pocket, and `pockets` one {'positions',
+    'elements'} dict per entry.  Returns the `VinaMinimized`; with `relax=True` the ligands are first relaxed in their pockets
+    (`Molecules.relax` with `vdw` and `relax_params`, e.g. dict(max_iters=...)), which is upstream's order, and the result is
+    (the `Relaxed`, the `VinaMinimized` of the relaxed poses).  The pocket types are computed once.  `params`: the parameters of
+    `Molecules.vina_minimize` (w_gauss1 .. r_c, w_intra, gtol, max_step, max_iters)."""
+    if len(samples) != len(pockets):
+        raise ValueError('samples and pockets must have one entry per pocket')
+    lig_pos, lig_feat, pocket_of = [], [], []
+    for q, rec in enumerate(samples):
+        lig_pos.extend(rec['positions'])
+        lig_feat.extend(rec['features'])
+        pocket_of.extend([q] * len(rec['positions']))
+    pocket_pos = [torch.as_tensor(p['positions']) for p in pockets]
+    if device is not None:
+        lig_pos, lig_feat = [p.to(device) for p in lig_pos], [f.to(device) for f in lig_feat]
+        pocket_pos = [p.to(device) for p in pocket_pos]
+    pocket_elements = [list(p['elements']) for p in pockets]
+    mols = build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds)
+    relaxed = None
+    if relax:
+        relaxed = mols.relax(pocket_pos, pocket_elements, pocket_of=pocket_of, vdw=vdw, **(relax_params or {}))
+        mols = relaxed.molecules
+    out = mols.vina_minimize(pocket_pos, pocket_elements, pocket_of=pocket_of, radii=radii, pocket_types=pocket_types, max_rotors=max_rotors,
+                             **params)
+    return (relaxed, out) if relax else out
