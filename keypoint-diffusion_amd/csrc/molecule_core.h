@@ -4,6 +4,8 @@
 // relax.hip and vina.hip also share everything that means "one workgroup takes one perceived ligand and its pocket" (the second
 // half of this file): the device front end with status bits 0 and 1, the two-vote epilogue of the staging loops, the LDS carving,
 // and on the host the argument check and the number of staged pocket rows.  pocket.hip takes the segment check alone.
+// vina_min.hip takes the same front end; what vina.hip and vina_min.hip share beyond it (typing, pair terms, staging, bond graph,
+// graph walk) is in vina_core.h.  The wave butterflies (wave_sum, the fp64 wave_max) serve relax.hip and both of them.
 #pragma once
 #include <algorithm>
 
@@ -81,10 +83,15 @@ __device__ __forceinline__ double wave_sum(double v) {      // a butterfly: the 
     for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
     return v;
 }
+__device__ __forceinline__ double wave_max(double v) {      // a maximum has no order
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
 
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }      // false for NaN too
 
-// ---- one workgroup takes one perceived ligand and its pocket (kpd_relax, kpd_vina_score) ---------------------------------
+// ---- one workgroup takes one perceived ligand and its pocket (kpd_relax, kpd_vina_score, kpd_vina_minimize) ---------------------------------
 enum : int { LP_NO_MOLECULE = 1, LP_BAD_INPUT = 2 };     // bits 0 and 1 of both status words
 
 // the ligand's n atoms [a0, a1) (to be used only where seg: lig_ptr was well-formed), its bonds [p0, p1), the np atoms of its pocket from q0

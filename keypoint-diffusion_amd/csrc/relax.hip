@@ -73,12 +73,6 @@ struct RelaxCtx {
     RelaxP P;
 };
 
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
-}
-
 // a . b over N3 elements: thread t takes t, t + 256, ...; butterfly inside each wave; the four waves in order.  Same value on every
 // thread.
 __device__ __forceinline__ double block_dot(const double *a, const double *b, int N3, double *red, int tid) {
@@ -96,7 +90,7 @@ __device__ __forceinline__ double block_dot(const double *a, const double *b, in
 __device__ __forceinline__ double block_max_norm(const double *v, int n, double *red, int tid) {
     double m = 0.0;
     for (int i = tid; i < n; i += RX_T) m = fmax(m, sqrt(v[3 * i] * v[3 * i] + v[3 * i + 1] * v[3 * i + 1] + v[3 * i + 2] * v[3 * i + 2]));
-    m = wave_max_d(m);
+    m = wave_max(m);
     if ((tid & 63) == 0) red[tid >> 6] = m;
     __syncthreads();
     const double r = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
@@ -274,7 +268,7 @@ __device__ void relax_eval(const RelaxCtx &C, const double *xq, double *gq, int 
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) part[k] = wave_sum(part[k]);
-        gm = wave_max_d(gm);
+        gm = wave_max(gm);
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) C.scal[k] = part[k];

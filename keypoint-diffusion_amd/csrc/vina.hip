@@ -13,20 +13,11 @@
 // a ligand's result is bitwise independent of the batch, of what was staged, and of the repeat.
 #include "common.h"
 #include "molecule_core.h"
+#include "vina_core.h"
 
 namespace kpd {
 
-constexpr int VN_T = 256;                 // threads of a workgroup
 constexpr int VN_LDS = 64 * 1024 - 512;   // dynamic LDS of a workgroup: what needs no opt-in, less the static bytes of the votes
-constexpr int VN_POCKET_ROW = 20;         // staged pocket atom: 3 floats, radius, type
-
-enum : int { VN_ATOM_OUT = 4 };           // status bit 2; bits 0 and 1 are LP_NO_MOLECULE and LP_BAD_INPUT
-enum : int { VN_H = 1, VN_D = 2, VN_A = 4 };
-enum : unsigned { VN_HETERO = 1u };       // neighbour flags: bit 0 = a neighbour that is neither C nor H, bit k = a bond of order k
-
-struct VinaP {
-    double w[5], w_rot, rc2;
-};
 
 // byte offsets of the dynamic LDS of a workgroup for ligands of at most nm atoms and `stage` staged pocket atoms
 struct VinaLayout {
@@ -53,30 +44,6 @@ __host__ __device__ inline VinaLayout vina_layout(int nm, int stage) {
     L.ptyp = take((size_t)stage * 4);
     L.bytes = o;
     return L;
-}
-
-// the flags of include/kpd.h from the atomic number, the heavy degree and the neighbour flags
-__device__ __forceinline__ int vina_flags(int z, int deg, unsigned nf) {
-    switch (z) {
-    case 6: return (nf & VN_HETERO) ? 0 : VN_H;
-    case 9:
-    case 17:
-    case 35:
-    case 53: return VN_H;
-    case 7:
-        if (deg > 2) return 0;
-        return (deg == 1 && (nf & (1u << 3))) ? VN_A : VN_D;
-    case 8: return VN_A | ((deg == 0 || (deg == 1 && (nf & (1u << 1)))) ? VN_D : 0);
-    case 12:
-    case 20:
-    case 25:
-    case 26:
-    case 27:
-    case 28:
-    case 29:
-    case 30: return VN_D;
-    default: return 0;
-    }
 }
 
 // ---- pocket typing: block (q, t) types the atoms [256 t, 256 t + 256) of pocket q ------------------------------------------
@@ -146,68 +113,6 @@ k_vina_pocket_types(const float *__restrict__ pocket_x, const int *__restrict__ 
     if (t == 0 && tid == 0) status[q] = any_bad ? 2 : 0;      // the vote is a predicate, not the OR of the values
 }
 
-// Is bond (i, j) in a ring: does j stay reachable from i without it?  visited / frontier are bit sets in registers.
-__device__ bool vina_in_ring(const unsigned *adj, int W, int i, int j) {
-    unsigned vis[MOL_W], fr[MOL_W];
-#pragma unroll
-    for (int w = 0; w < MOL_W; ++w) vis[w] = fr[w] = (w == (i >> 5)) ? 1u << (i & 31) : 0u;
-    const int jw = j >> 5;
-    const unsigned jb = 1u << (j & 31);
-    for (;;) {
-        int a = -1;
-#pragma unroll
-        for (int w = 0; w < MOL_W; ++w)
-            if (a < 0 && fr[w]) {
-                a = 32 * w + __ffs(fr[w]) - 1;
-                fr[w] &= fr[w] - 1;
-            }
-        if (a < 0) return false;
-        const unsigned *row = adj + a * W;
-        bool found = false;
-#pragma unroll
-        for (int w = 0; w < MOL_W; ++w) {
-            if (w >= W) continue;
-            unsigned r = row[w];
-            if (a == i && w == jw) r &= ~jb;         // the bond itself
-            const unsigned nw = r & ~vis[w];
-            vis[w] |= nw;
-            fr[w] |= nw;
-            if (w == jw && (vis[w] & jb)) found = true;
-        }
-        if (found) return true;
-    }
-}
-
-// the five terms of one pair at surface distance d (added to t) and dd = sum over the terms of w_term * dterm/dd
-__device__ __forceinline__ double vina_pair(double d, int ti, int tj, const VinaP &P, double (&t)[5]) {
-    const double u = d / 0.5, v = (d - 3.0) / 2.0;
-    const double g1 = exp(-(u * u)), g2 = exp(-(v * v));
-    t[0] += g1;
-    t[1] += g2;
-    double dd = P.w[0] * (-4.0 * u * g1) + P.w[1] * (-v * g2);
-    if (d < 0.0) {
-        t[2] += d * d;
-        dd += P.w[2] * (2.0 * d);
-    }
-    if (ti & tj & VN_H) {
-        if (d < 0.5) {
-            t[3] += 1.0;
-        } else if (d < 1.5) {
-            t[3] += 1.5 - d;
-            dd -= P.w[3];
-        }
-    }
-    if (((ti & VN_D) && (tj & VN_A)) || ((ti & VN_A) && (tj & VN_D))) {
-        if (d < -0.7) {
-            t[4] += 1.0;
-        } else if (d < 0.0) {
-            t[4] += d / -0.7;
-            dd += P.w[4] / -0.7;
-        }
-    }
-    return dd;
-}
-
 __global__ void __launch_bounds__(VN_T)
 k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n_atoms, int nm, const int *__restrict__ elem, int F,
              const int *__restrict__ zs, const float *__restrict__ lig_radius, const int *__restrict__ bond_ij,
@@ -236,7 +141,7 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
     int atom_out = 0;
     if (!st) {
         int bad = 0;
-        for (int a = tid; a < n; a += VN_T) {
+        for (int a = tid; a < n; a += VN_T) {        // k_vina_minimize stages its atoms the same way
             cnt[a] = 0;
             flg[a] = 0;
             zat[a] = 0;
@@ -258,43 +163,11 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
                 x0[3 * a + k] = v;
             }
         }
-        for (int j = tid; j < np; j += VN_T) {       // every pocket atom is checked, the first `stage` are kept
-            const float *r = pocket_x + (size_t)(q0 + j) * 3;
-            const float rv = pocket_radius[q0 + j];
-            const int tj = pocket_type[q0 + j];
-            if (!(finite_f(r[0]) && finite_f(r[1]) && finite_f(r[2]) && finite_f(rv))) bad |= LP_BAD_INPUT;
-            if (tj < 0 || !(rv > 0.0f)) atom_out = 1;
-            if (j < stage) {
-                px[3 * j] = r[0];
-                px[3 * j + 1] = r[1];
-                px[3 * j + 2] = r[2];
-                prad[j] = rv;
-                ptyp[j] = tj;
-            }
-        }
+        vina_stage_pocket(pocket_x, pocket_radius, pocket_type, q0, np, stage, tid, px, prad, ptyp, bad, atom_out);
         st = lp_votes(bad);
     }
-    if (!st) {                                       // the bond graph: bit matrix, degrees, neighbour flags (integer atomics: no order)
-        int bad = 0;
-        for (int k = p0 + tid; k < p1; k += VN_T) {
-            const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0, o = bond_order[k];
-            if (i < 0 || i >= n || j < 0 || j >= n || i == j || o < 1 || o > 3) {
-                bad = 1;
-                continue;
-            }
-            const int zi = zat[i], zj = zat[j];
-            if (!(element_row(zi) & 0xffu) || !(element_row(zj) & 0xffu)) {      // an element the bond rule never bonds
-                bad = 1;
-                continue;
-            }
-            const unsigned was = atomicOr(&adj[i * W + (j >> 5)], 1u << (j & 31));
-            atomicOr(&adj[j * W + (i >> 5)], 1u << (i & 31));
-            if (was & (1u << (j & 31))) bad = 1;     // a bond twice
-            const unsigned ci = atomicAdd(&cnt[i], 1u + (zj != 1 ? 16u : 0u)), cj = atomicAdd(&cnt[j], 1u + (zi != 1 ? 16u : 0u));
-            if ((ci & 15u) >= (unsigned)MOL_DEG || (cj & 15u) >= (unsigned)MOL_DEG) bad = 1;      // a seventh neighbour
-            if (zj != 1) atomicOr(&flg[i], (zj != 6 ? VN_HETERO : 0u) | (1u << o));
-            if (zi != 1) atomicOr(&flg[j], (zi != 6 ? VN_HETERO : 0u) | (1u << o));
-        }
+    if (!st) {                                       // the bond graph: a bond may be listed as (j, i), there are no fragment labels
+        const int bad = vina_bond_graph<false, false>(bond_ij, bond_order, p0, p1, a0, n, W, tid, zat, nullptr, adj, cnt, flg);
         st = __syncthreads_or(bad) ? LP_NO_MOLECULE : 0;
     }
     if (st) {                                        // left out: zero rows, types -1
@@ -309,25 +182,15 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
         return;
     }
     // ---- types
-    for (int a = tid; a < n; a += VN_T) {
-        const int z = zat[a];
-        int f = vina_flags(z, (int)((cnt[a] >> 4) & 15u), flg[a]);
-        if (lig_type_in) {
-            const int over = lig_type_in[a0 + a];
-            if (over >= 0) f = over & 7;
-        }
-        const int t = (z == 1 || !(rad[a] > 0.0f)) ? -1 : f;
-        if (t < 0) atom_out = 1;
-        typ[a] = t;
-        if (lig_type) lig_type[a0 + a] = t;
-    }
+    vina_type_atoms(n, a0, tid, zat, cnt, flg, rad, lig_type_in, typ, lig_type, atom_out);
     // ---- rotors: single bonds between atoms of heavy degree >= 2 that are in no ring
     int rot = 0;
     for (int k = p0 + tid; k < p1; k += VN_T) {
         if (bond_order[k] != 1) continue;
         const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0;
         if (((cnt[i] >> 4) & 15u) < 2u || ((cnt[j] >> 4) & 15u) < 2u) continue;
-        if (!vina_in_ring(adj, W, i, j)) ++rot;
+        unsigned vis[MOL_W];
+        if (!vina_walk<true>(adj, W, i, j, vis)) ++rot;      // in no ring: j is not reached from i without the bond
     }
     rot = wave_sum(rot);
     int *redi = reinterpret_cast<int *>(red);
@@ -344,36 +207,7 @@ k_vina_score(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
         double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, gx = 0.0, gy = 0.0, gz = 0.0;
         if (ti >= 0) {                               // wave-uniform
             const double xi = (double)x0[3 * i], yi = (double)x0[3 * i + 1], zi = (double)x0[3 * i + 2], Ri = (double)rad[i];
-            for (int j = lane; j < np; j += 64) {
-                float qx, qy, qz, rj;
-                int tj;
-                if (j < stage) {
-                    qx = px[3 * j];
-                    qy = px[3 * j + 1];
-                    qz = px[3 * j + 2];
-                    rj = prad[j];
-                    tj = ptyp[j];
-                } else {
-                    const float *r = gpx + (size_t)j * 3;
-                    qx = r[0];
-                    qy = r[1];
-                    qz = r[2];
-                    rj = gpr[j];
-                    tj = gpt[j];
-                }
-                if (tj < 0 || !(rj > 0.0f)) continue;
-                const double dx = xi - (double)qx, dy = yi - (double)qy, dz = zi - (double)qz;
-                const double d2 = sum_sq(dx, dy, dz);
-                if (!(d2 < P.rc2)) continue;
-                const double r = __dsqrt_rn(d2), d = (r - Ri) - (double)rj;
-                const double dd = vina_pair(d, ti, tj & 7, P, t);
-                if (r >= 1e-6) {
-                    const double k = dd / r;
-                    gx += k * dx;
-                    gy += k * dy;
-                    gz += k * dz;
-                }
-            }
+            vina_pocket_sums(xi, yi, zi, Ri, ti, lane, np, stage, px, prad, ptyp, gpx, gpr, gpt, P, t, gx, gy, gz);
         }
 #pragma unroll
         for (int k = 0; k < 5; ++k) t[k] = wave_sum(t[k]);
@@ -450,16 +284,9 @@ extern "C" kpd_status kpd_vina_score(const float *pos, const int32_t *lig_ptr, i
     kpd_vina_params d;
     kpd_vina_defaults(&d);
     if (params) d = *params;
-    const double ws[5] = {d.w_gauss1, d.w_gauss2, d.w_repulsion, d.w_hydrophobic, d.w_hbond};
-    bool ok = d.r_c > 0.0 && d.r_c < 1e6 && d.w_rot >= 0.0 && d.w_rot < 1e12;
-    for (double w : ws) ok = ok && w > -1e12 && w < 1e12;
-    KPD_REQUIRE(ok, KPD_ERR_INVALID, "weights %g %g %g %g %g (finite) w_rot=%g (>= 0) r_c=%g (> 0)", ws[0], ws[1], ws[2], ws[3], ws[4],
-                d.w_rot, d.r_c);
-    if (!B) return KPD_OK;
     VinaP vp;
-    for (int k = 0; k < 5; ++k) vp.w[k] = ws[k];
-    vp.w_rot = d.w_rot;
-    vp.rc2 = d.r_c * d.r_c;
+    KPD_TRY(vina_fill_params(d, vp));
+    if (!B) return KPD_OK;
     // as much of the largest pocket as fits beside a max_atoms ligand
     const int stage = stage_rows(vina_layout(max_atoms, 0).bytes, VN_LDS, VN_POCKET_ROW, max_pocket);
     KPD_REQUIRE(stage >= 0, KPD_ERR_INVALID, "no LDS for %d atoms", max_atoms);

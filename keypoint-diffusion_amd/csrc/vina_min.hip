@@ -10,27 +10,23 @@
 // body or rotor over its atom set.  The pose vectors have at most 112 entries, so the two-loop recursion and every dot product of
 // the L-BFGS run on one wavefront, two entries per lane.  Nothing is shared between ligands, no atomics on floats, no host
 // synchronisation: a ligand's result is bitwise independent of the batch, of what was staged, of the bounds, and of the repeat.
-// The helpers that vina.hip also has (flags, pair terms) are restated here so that vina.hip's kernels keep their code objects.
 #include "common.h"
 #include "molecule_core.h"
+#include "vina_core.h"
 
 namespace kpd {
 
-constexpr int VM_T = 256;                 // threads of a workgroup
 constexpr int VM_M = 8;                   // stored correction pairs
 constexpr int VM_LDS = 160 * 1024 - 512;  // LDS of one CU, less the few static bytes the compiler adds for the block-wide votes
-constexpr int VM_POCKET_ROW = 20;         // staged pocket atom: 3 floats, radius, type
 constexpr int VM_FRAGS = 8;               // bodies of one ligand
 constexpr int VM_ROTORS = 64;             // active rotors of one ligand
 
-enum : int { VM_ATOM_OUT = 4, VM_LINE_SEARCH = 8, VM_FROZEN = 16, VM_FRAGMENTS = 32, VM_ITER_CAP = 64 };      // status bits 2 .. 6
-enum : int { VM_H = 1, VM_D = 2, VM_A = 4 };
-enum : unsigned { VM_HETERO = 1u };       // neighbour flags: bit 0 = a neighbour that is neither C nor H, bit k = a bond of order k
+enum : int { VM_LINE_SEARCH = 8, VM_FROZEN = 16, VM_FRAGMENTS = 32, VM_ITER_CAP = 64 };      // status bits 3 .. 6, above VN_ATOM_OUT
 // slots of `scal`
 enum : int { VS_INTER = 0, VS_INTRA, VS_E, VS_GNORM, VS_GP, VS_SY, VS_YY, VS_GG, VS_RESET, VS_COUNT = 16 };
 
-struct VinaMinP {
-    double w[5], w_rot, rc2, w_intra, gtol, max_step;
+struct VinaMinP : VinaP {
+    double w_intra, gtol, max_step;
     int max_iters;
 };
 
@@ -95,96 +91,7 @@ struct VinaMinCtx {
     VinaMinP P;
 };
 
-// the flags of include/kpd.h from the atomic number, the heavy degree and the neighbour flags (as in vina.hip)
-__device__ __forceinline__ int vm_flags(int z, int deg, unsigned nf) {
-    switch (z) {
-    case 6: return (nf & VM_HETERO) ? 0 : VM_H;
-    case 9:
-    case 17:
-    case 35:
-    case 53: return VM_H;
-    case 7:
-        if (deg > 2) return 0;
-        return (deg == 1 && (nf & (1u << 3))) ? VM_A : VM_D;
-    case 8: return VM_A | ((deg == 0 || (deg == 1 && (nf & (1u << 1)))) ? VM_D : 0);
-    case 12:
-    case 20:
-    case 25:
-    case 26:
-    case 27:
-    case 28:
-    case 29:
-    case 30: return VM_D;
-    default: return 0;
-    }
-}
-
-// the five terms of one pair at surface distance d (added to t) and dd = sum over the terms of w_term * dterm/dd (as in vina.hip)
-__device__ __forceinline__ double vm_pair(double d, int ti, int tj, const VinaMinP &P, double (&t)[5]) {
-    const double u = d / 0.5, v = (d - 3.0) / 2.0;
-    const double g1 = exp(-(u * u)), g2 = exp(-(v * v));
-    t[0] += g1;
-    t[1] += g2;
-    double dd = P.w[0] * (-4.0 * u * g1) + P.w[1] * (-v * g2);
-    if (d < 0.0) {
-        t[2] += d * d;
-        dd += P.w[2] * (2.0 * d);
-    }
-    if (ti & tj & VM_H) {
-        if (d < 0.5) {
-            t[3] += 1.0;
-        } else if (d < 1.5) {
-            t[3] += 1.5 - d;
-            dd -= P.w[3];
-        }
-    }
-    if (((ti & VM_D) && (tj & VM_A)) || ((ti & VM_A) && (tj & VM_D))) {
-        if (d < -0.7) {
-            t[4] += 1.0;
-        } else if (d < 0.0) {
-            t[4] += d / -0.7;
-            dd += P.w[4] / -0.7;
-        }
-    }
-    return dd;
-}
-
 __device__ __forceinline__ bool vm_bit(const unsigned *row, int j) { return (row[j >> 5] >> (j & 31)) & 1u; }
-
-__device__ __forceinline__ double vm_wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
-}
-
-// The atoms reached from `from` when its bond to `other` is removed, as a bit set in registers (the walk of vina.hip, run to its end).
-__device__ void vm_reach(const unsigned *adj, int W, int from, int other, unsigned (&vis)[MOL_W]) {
-    unsigned fr[MOL_W];
-#pragma unroll
-    for (int w = 0; w < MOL_W; ++w) vis[w] = fr[w] = (w == (from >> 5)) ? 1u << (from & 31) : 0u;
-    const int ow = other >> 5;
-    const unsigned ob = 1u << (other & 31);
-    for (;;) {
-        int a = -1;
-#pragma unroll
-        for (int w = 0; w < MOL_W; ++w)
-            if (a < 0 && fr[w]) {
-                a = 32 * w + __ffs(fr[w]) - 1;
-                fr[w] &= fr[w] - 1;
-            }
-        if (a < 0) return;
-        const unsigned *row = adj + a * W;
-#pragma unroll
-        for (int w = 0; w < MOL_W; ++w) {
-            if (w >= W) continue;
-            unsigned r = row[w];
-            if (a == from && w == ow) r &= ~ob;      // the bond itself
-            const unsigned nw = r & ~vis[w];
-            vis[w] |= nw;
-            fr[w] |= nw;
-        }
-    }
-}
 
 // r turned about the unit axis u by the angle whose cosine and sine are c, s (Rodrigues)
 __device__ __forceinline__ void vm_rot(double &rx, double &ry, double &rz, double ux, double uy, double uz, double c, double s) {
@@ -203,36 +110,7 @@ __device__ void vm_eval(const VinaMinCtx &C, const double *xq, double *gq, int t
         double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, u[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, gx = 0.0, gy = 0.0, gz = 0.0;
         if (ti >= 0) {                               // wave-uniform
             const double xi = xq[3 * i], yi = xq[3 * i + 1], zi = xq[3 * i + 2], Ri = (double)C.rad[i];
-            for (int j = lane; j < C.np; j += 64) {  // the pocket: the pair loop of k_vina_score
-                float qx, qy, qz, rj;
-                int tj;
-                if (j < C.stage) {
-                    qx = C.px[3 * j];
-                    qy = C.px[3 * j + 1];
-                    qz = C.px[3 * j + 2];
-                    rj = C.prad[j];
-                    tj = C.ptyp[j];
-                } else {
-                    const float *r = C.gpx + (size_t)j * 3;
-                    qx = r[0];
-                    qy = r[1];
-                    qz = r[2];
-                    rj = C.gpr[j];
-                    tj = C.gpt[j];
-                }
-                if (tj < 0 || !(rj > 0.0f)) continue;
-                const double dx = xi - (double)qx, dy = yi - (double)qy, dz = zi - (double)qz;
-                const double d2 = sum_sq(dx, dy, dz);
-                if (!(d2 < C.P.rc2)) continue;
-                const double r = __dsqrt_rn(d2), d = (r - Ri) - (double)rj;
-                const double dd = vm_pair(d, ti, tj & 7, C.P, t);
-                if (r >= 1e-6) {
-                    const double k = dd / r;
-                    gx += k * dx;
-                    gy += k * dy;
-                    gz += k * dz;
-                }
-            }
+            vina_pocket_sums(xi, yi, zi, Ri, ti, lane, C.np, C.stage, C.px, C.prad, C.ptyp, C.gpx, C.gpr, C.gpt, C.P, t, gx, gy, gz);
             const unsigned *row = C.imask + i * C.W;
             for (int j = lane; j < C.n; j += 64) {   // the ligand's own atoms: every pair is seen from both of its atoms
                 if (!vm_bit(row, j)) continue;
@@ -240,7 +118,7 @@ __device__ void vm_eval(const VinaMinCtx &C, const double *xq, double *gq, int t
                 const double d2 = sum_sq(dx, dy, dz);
                 if (!(d2 < C.P.rc2)) continue;
                 const double r = __dsqrt_rn(d2), d = (r - Ri) - (double)C.rad[j];
-                const double dd = vm_pair(d, ti, C.typ[j] & 7, C.P, u);
+                const double dd = vina_pair(d, ti, C.typ[j] & 7, C.P, u);
                 if (r >= 1e-6) {
                     const double k = C.P.w_intra * dd / r;
                     gx += k * dx;
@@ -364,7 +242,7 @@ __device__ void vm_project(const VinaMinCtx &C, const double *xq, const double *
     if (wv == 0) {
         double m = 0.0;
         for (int d = lane; d < C.D; d += 64) m = fmax(m, fabs(gd[d]));
-        m = vm_wave_max(m);
+        m = wave_max(m);
         if (lane == 0) C.scal[VS_GNORM] = m;
     }
     __syncthreads();
@@ -433,7 +311,7 @@ __device__ void vm_direction(const double *gd, const double *S, const double *Y,
 // the largest first-order speed of an atom under the pose velocity p (a maximum has no order); cen and axu are those of x
 __device__ double vm_vmax(const VinaMinCtx &C, const double *x, const double *p, int tid) {
     double m = 0.0;
-    for (int i = tid; i < C.n; i += VM_T) {
+    for (int i = tid; i < C.n; i += VN_T) {
         const int f = C.frg[i];
         const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
         const double *pf = p + 6 * f;
@@ -450,7 +328,7 @@ __device__ double vm_vmax(const VinaMinCtx &C, const double *x, const double *p,
         }
         m = fmax(m, sqrt((vx * vx + vy * vy) + vz * vz));
     }
-    m = vm_wave_max(m);
+    m = wave_max(m);
     if ((tid & 63) == 0) C.red[tid >> 6] = m;
     __syncthreads();
     const double r = fmax(fmax(C.red[0], C.red[1]), fmax(C.red[2], C.red[3]));
@@ -484,7 +362,7 @@ __device__ void vm_move(const VinaMinCtx &C, const double *x, const double *p, d
         o[7] = alpha * pf[2];
     }
     __syncthreads();
-    for (int i = tid; i < C.n; i += VM_T) {
+    for (int i = tid; i < C.n; i += VN_T) {
         double px = x[3 * i], py = x[3 * i + 1], pz = x[3 * i + 2];
         for (int kk = 0; kk < C.T; ++kk) {
             const int k = C.ord[kk];
@@ -511,7 +389,7 @@ __device__ void vm_move(const VinaMinCtx &C, const double *x, const double *p, d
 
 // Three waves per SIMD: the compiler's own choice is 173 VGPRs, one short of that; bounded to 168 it spills four of them (20 B of
 // scratch per lane) and the third workgroup on a compute unit more than pays for it (profiles/vina_min.md).
-__global__ void __launch_bounds__(VM_T) __attribute__((amdgpu_waves_per_eu(3, 3)))
+__global__ void __launch_bounds__(VN_T) __attribute__((amdgpu_waves_per_eu(3, 3)))
 k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, int nm, const int *__restrict__ elem, int F,
                 const int *__restrict__ zs, const float *__restrict__ lig_radius, const int *__restrict__ frag,
                 const int *__restrict__ bond_ij, const int *__restrict__ bond_order, const int *__restrict__ bond_ptr, int cap_bonds,
@@ -553,9 +431,9 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
             flow[tid] = MOL_MAX;
             fcnt[tid] = 0;
         }
-        for (int k = tid; k < VM_FRAGS * W; k += VM_T) fset[k] = 0;
+        for (int k = tid; k < VM_FRAGS * W; k += VN_T) fset[k] = 0;
         int bad = 0;
-        for (int a = tid; a < n; a += VM_T) {
+        for (int a = tid; a < n; a += VN_T) {        // k_vina_score's atom staging, plus the fragment label and the fp64 copy
             cnt[a] = 0;
             flg[a] = 0;
             zat[a] = 0;
@@ -580,45 +458,14 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
                 x[3 * a + k] = (double)v;
             }
         }
-        for (int j = tid; j < np; j += VM_T) {       // every pocket atom is checked, the first `stage` are kept
-            const float *r = pocket_x + (size_t)(q0 + j) * 3;
-            const float rv = pocket_radius[q0 + j];
-            const int tj = pocket_type[q0 + j];
-            if (!(finite_f(r[0]) && finite_f(r[1]) && finite_f(r[2]) && finite_f(rv))) bad |= LP_BAD_INPUT;
-            if (tj < 0 || !(rv > 0.0f)) atom_out = 1;
-            if (j < stage) {
-                px[3 * j] = r[0];
-                px[3 * j + 1] = r[1];
-                px[3 * j + 2] = r[2];
-                prad[j] = rv;
-                ptyp[j] = tj;
-            }
-        }
+        vina_stage_pocket(pocket_x, pocket_radius, pocket_type, q0, np, stage, tid, px, prad, ptyp, bad, atom_out);
         st = lp_votes(bad);
     }
     int n_frag = 0;
-    if (!st) {                                       // the bond graph (integer atomics: no order), the fragments
-        int bad = 0, top = 0;
-        for (int k = p0 + tid; k < p1; k += VM_T) {
-            const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0, o = bond_order[k];
-            if (i < 0 || j >= n || i >= j || o < 1 || o > 3) {      // bond_ij holds i < j: a bond listed both ways round cannot hide from `was`
-                bad = 1;
-                continue;
-            }
-            const int zi = zat[i], zj = zat[j];
-            if (!(element_row(zi) & 0xffu) || !(element_row(zj) & 0xffu) || frg[i] != frg[j]) {      // never bonded; two fragments
-                bad = 1;
-                continue;
-            }
-            const unsigned was = atomicOr(&adj[i * W + (j >> 5)], 1u << (j & 31));
-            atomicOr(&adj[j * W + (i >> 5)], 1u << (i & 31));
-            if (was & (1u << (j & 31))) bad = 1;     // a bond twice
-            const unsigned ci = atomicAdd(&cnt[i], 1u + (zj != 1 ? 16u : 0u)), cj = atomicAdd(&cnt[j], 1u + (zi != 1 ? 16u : 0u));
-            if ((ci & 15u) >= (unsigned)MOL_DEG || (cj & 15u) >= (unsigned)MOL_DEG) bad = 1;      // a seventh neighbour
-            if (zj != 1) atomicOr(&flg[i], (zj != 6 ? VM_HETERO : 0u) | (1u << o));
-            if (zi != 1) atomicOr(&flg[j], (zi != 6 ? VM_HETERO : 0u) | (1u << o));
-        }
-        for (int a = tid; a < n; a += VM_T) {
+    if (!st) {                                       // the bond graph: bond_ij holds i < j inside one fragment; then the fragments
+        const int bad = vina_bond_graph<true, true>(bond_ij, bond_order, p0, p1, a0, n, W, tid, zat, frg, adj, cnt, flg);
+        int top = 0;
+        for (int a = tid; a < n; a += VN_T) {
             const int fl = frg[a];
             top = max(top, fl);
             if (fl < VM_FRAGS) {
@@ -647,26 +494,16 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
         return;
     }
     // ---- types
-    for (int a = tid; a < n; a += VM_T) {
-        const int z = zat[a];
-        int f = vm_flags(z, (int)((cnt[a] >> 4) & 15u), flg[a]);
-        if (lig_type_in) {
-            const int over = lig_type_in[a0 + a];
-            if (over >= 0) f = over & 7;
-        }
-        const int t = (z == 1 || !(rad[a] > 0.0f)) ? -1 : f;
-        if (t < 0) atom_out = 1;
-        typ[a] = t;
-    }
+    vina_type_atoms(n, a0, tid, zat, cnt, flg, rad, lig_type_in, typ, nullptr, atom_out);
     // ---- rotors in bond order: single bonds between atoms of heavy degree >= 2 that are in no ring
     const int nb = min(p1 - p0, 3 * nm);             // a graph that passed the checks has at most 3 n bonds
-    for (int k = tid; k < nb; k += VM_T) {
+    for (int k = tid; k < nb; k += VN_T) {
         int is = 0;
         if (bond_order[p0 + k] == 1) {
             const int i = bond_ij[(size_t)(p0 + k) * 2] - a0, j = bond_ij[(size_t)(p0 + k) * 2 + 1] - a0;
             if (((cnt[i] >> 4) & 15u) >= 2u && ((cnt[j] >> 4) & 15u) >= 2u) {
                 unsigned vis[MOL_W];
-                vm_reach(adj, W, j, i, vis);
+                vina_walk<false>(adj, W, j, i, vis);
                 unsigned hit = 0;
 #pragma unroll
                 for (int w = 0; w < MOL_W; ++w)
@@ -676,7 +513,7 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
         }
         rflag[k] = (unsigned char)is;
     }
-    if (__syncthreads_or(atom_out)) st |= VM_ATOM_OUT;   // also orders typ and rflag before their readers
+    if (__syncthreads_or(atom_out)) st |= VN_ATOM_OUT;   // also orders typ and rflag before their readers
     int *redi = reinterpret_cast<int *>(red);
     if (wv == 0) {                                   // the first max_rotors of them are active
         int base = 0;
@@ -698,12 +535,12 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
     if (n_rot > T) st |= VM_FROZEN;
     const double inv_norm = 1.0 / (1.0 + P.w_rot * (double)n_rot);
     // ---- the moved set of every active rotor (i, j): the side of j, or the rest of the fragment when that side holds its lowest atom
-    for (int a = tid; a < n; a += VM_T)
+    for (int a = tid; a < n; a += VN_T)
         for (int w = 0; w < W; ++w) adjp[a * W + w] = adj[a * W + w];
     if (tid < T) {
         const int i = ra[tid], j = rb[tid], low = flow[frg[j]];
         unsigned vis[MOL_W];
-        vm_reach(adj, W, j, i, vis);
+        vina_walk<false>(adj, W, j, i, vis);
         unsigned hit = 0;
 #pragma unroll
         for (int w = 0; w < MOL_W; ++w)
@@ -727,7 +564,7 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
         for (int k = 0; k < T; ++k) d += vm_bit(mset + k * W, rb[tid]) ? 1 : 0;
         depth[tid] = d;
     }
-    for (int a = tid; a < n; a += VM_T) piece[a] = a;
+    for (int a = tid; a < n; a += VN_T) piece[a] = a;
     __syncthreads();
     if (tid == 0) {                                  // rotors from the deepest to the shallowest, by index within one depth
         for (int k = 0; k < T; ++k) {
@@ -745,7 +582,7 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
     // result does not depend on the interleaving.
     for (;;) {
         int changed = 0;
-        for (int a = tid; a < n; a += VM_T) {
+        for (int a = tid; a < n; a += VN_T) {
             int l = piece[a];
             const int before = l;
             for (int w = 0; w < W; ++w) {
@@ -764,7 +601,7 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
         if (!__syncthreads_or(changed)) break;
     }
     // ---- intramolecular pairs: both atoms take part, different pieces, four or more bonds apart or not connected
-    for (int a = tid; a < n; a += VM_T) {
+    for (int a = tid; a < n; a += VN_T) {
         unsigned e1[MOL_W], e2[MOL_W], e3[MOL_W];
 #pragma unroll
         for (int w = 0; w < MOL_W; ++w) {
@@ -883,7 +720,7 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
         intra = scal[VS_INTRA];
         vm_project(C, xt, g, gdt, tid);              // the new point's own chart
         gnorm = scal[VS_GNORM];
-        for (int d = tid; d < D; d += VM_T) {
+        for (int d = tid; d < D; d += VN_T) {
             S[head * DS + d] = alpha * p[d];
             Y[head * DS + d] = gdt[d] - gd[d];
         }
@@ -917,7 +754,7 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
     // positions.  Should that rounding alone turn the (then tiny) gain into a rise, the ligand keeps its input rows.
     bool keep = false;
     if (iters) {
-        for (int k = tid; k < N3; k += VM_T) xt[k] = (double)(float)x[k];
+        for (int k = tid; k < N3; k += VN_T) xt[k] = (double)(float)x[k];
         __syncthreads();
         vm_eval(C, xt, g, tid);
         ++evals;
@@ -931,7 +768,7 @@ k_vina_minimize(const float *pos, const int *__restrict__ lig_ptr, int n_atoms, 
     if (gnorm > P.gtol && !(st & VM_LINE_SEARCH)) st |= VM_ITER_CAP;
 
     double sq = 0.0;
-    for (int k = tid; k < N3; k += VM_T) {
+    for (int k = tid; k < N3; k += VN_T) {
         const float v = keep ? (float)xt[k] : x0[k];
         pos_out[(size_t)a0 * 3 + k] = v;
         const double d = (double)v - (double)x0[k];
@@ -981,30 +818,24 @@ extern "C" kpd_status kpd_vina_minimize(const float *pos, const int32_t *lig_ptr
     kpd_vina_min_params d;
     kpd_vina_min_defaults(&d);
     if (params) d = *params;
-    const double ws[5] = {d.w_gauss1, d.w_gauss2, d.w_repulsion, d.w_hydrophobic, d.w_hbond};
-    bool ok = d.r_c > 0.0 && d.r_c < 1e6 && d.w_rot >= 0.0 && d.w_rot < 1e12 && d.w_intra >= 0.0 && d.w_intra < 1e12 && d.gtol >= 0.0 &&
-              d.max_step > 0.0 && d.max_iters >= 0;
-    for (double w : ws) ok = ok && w > -1e12 && w < 1e12;
-    KPD_REQUIRE(ok, KPD_ERR_INVALID, "weights %g %g %g %g %g (finite) w_rot=%g w_intra=%g gtol=%g (>= 0) r_c=%g max_step=%g (> 0) max_iters=%d",
-                ws[0], ws[1], ws[2], ws[3], ws[4], d.w_rot, d.w_intra, d.gtol, d.r_c, d.max_step, d.max_iters);
+    VinaMinP vp;
+    KPD_TRY(vina_fill_params({d.w_gauss1, d.w_gauss2, d.w_repulsion, d.w_hydrophobic, d.w_hbond, d.w_rot, d.r_c}, vp));
+    KPD_REQUIRE(d.w_intra >= 0.0 && d.w_intra < 1e12 && d.gtol >= 0.0 && d.max_step > 0.0 && d.max_iters >= 0, KPD_ERR_INVALID,
+                "w_intra=%g gtol=%g (>= 0) max_step=%g (> 0) max_iters=%d", d.w_intra, d.gtol, d.max_step, d.max_iters);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_atoms && pos_out != pos) KPD_HIP(hipMemcpyAsync(pos_out, pos, (size_t)n_atoms * 12, hipMemcpyDeviceToDevice, st));
     if (!B) return KPD_OK;
-    VinaMinP vp;
-    for (int k = 0; k < 5; ++k) vp.w[k] = ws[k];
-    vp.w_rot = d.w_rot;
-    vp.rc2 = d.r_c * d.r_c;
     vp.w_intra = d.w_intra;
     vp.gtol = d.gtol;
     vp.max_step = d.max_step;
     vp.max_iters = d.max_iters;
     // as much of the largest pocket as fits beside the state of a max_atoms ligand
-    const int stage = stage_rows(vina_min_layout(max_atoms, max_rotors, 0).bytes, VM_LDS, VM_POCKET_ROW, max_pocket);
+    const int stage = stage_rows(vina_min_layout(max_atoms, max_rotors, 0).bytes, VM_LDS, VN_POCKET_ROW, max_pocket);
     KPD_REQUIRE(stage >= 0, KPD_ERR_INVALID, "no LDS for %d atoms", max_atoms);
     const VinaMinLayout L = vina_min_layout(max_atoms, max_rotors, stage);
     KPD_REQUIRE(L.bytes <= (size_t)VM_LDS, KPD_ERR_INVALID, "LDS layout of %zu bytes", L.bytes);
     KPD_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_vina_minimize), (int)L.bytes));
-    hipLaunchKernelGGL(k_vina_minimize, dim3(B), dim3(VM_T), L.bytes, st, pos, lig_ptr, n_atoms, max_atoms, elem, F, z, lig_radius, frag,
+    hipLaunchKernelGGL(k_vina_minimize, dim3(B), dim3(VN_T), L.bytes, st, pos, lig_ptr, n_atoms, max_atoms, elem, F, z, lig_radius, frag,
                        bond_ij, bond_order, bond_ptr, cap_bonds, mol_status, lig_type_in, pocket_x, pocket_radius, pocket_type, pocket_ptr,
                        n_pocket, P, stage, pocket_of, max_rotors, vp, pos_out, report, status);
     KPD_LAUNCH_CHECK();
