@@ -888,9 +888,10 @@ kpd_status kpd_relax(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, 
  * Vina FUNCTIONAL FORM: five pair terms over ligand x pocket heavy atoms, the sum divided by 1 + w_rot N_rot, with its analytic
  * gradient.  The typing cannot be Vina's own (Vina reads hydrogens and AutoDock atom types from PDBQT; ligands and pockets here
  * carry heavy atoms and element classes only), so THIS COMMENT IS THE DEFINITION.  THE SCORES ARE NOT gnina's OR Vina's NUMBERS:
- * they rank samples scored by this function against each other.  Out of scope: no search and no docking, no intramolecular
- * term in the score, no hydrogens, no aromaticity.  The torsional and rigid-body minimisation under this function (gnina's
- * --minimize) is kpd_vina_minimize below, built on the gradient delivered here.
+ * they rank samples scored by this function against each other.  Out of scope here: no intramolecular
+ * term in the score, no hydrogens, no aromaticity; this call scores the poses it is given.  The torsional and rigid-body
+ * minimisation under this function (gnina's --minimize) is kpd_vina_minimize below, built on the gradient delivered here, and
+ * the search for poses (gnina's docking) is kpd_vina_dock below it.
  *
  * Ligand and pocket are in one frame, as for kpd_relax.  All arithmetic is fp64 on values read from the fp32 inputs.
  * Distances: d2(i,j) by the recipe of kpd_mol_perceive and kpd_pocket_select (differences of the fp32 coordinates in fp64, each
@@ -965,7 +966,7 @@ kpd_status kpd_vina_score(const float *pos, const int32_t *lig_ptr, int32_t n_at
  * gen_ligands_gnina_minimized.sdf.  gnina's minimiser, its torsion tree (which reads hydrogens) and its numbers cannot be restated
  * here, so THIS COMMENT IS THE DEFINITION.  THE POSES AND SCORES ARE NOT gnina's OR Vina's: typing, rotor rule, pair terms, weights
  * and the recalled constants are those of kpd_vina_score, and what is reported is the score at the nearest local minimum of THIS
- * function.  No search, no docking, a rigid pocket, no hydrogens.
+ * function.  No search in this call (kpd_vina_dock below searches), a rigid pocket, no hydrogens.
  *
  * All arithmetic is fp64 on values read from the fp32 inputs.  The distance recipe, the types, the rotor rule, the pair terms,
  * the weights, r_c and the r < 1e-6 rule are those of kpd_vina_score, word for word.
@@ -1038,6 +1039,92 @@ kpd_status kpd_vina_minimize(const float *pos, const int32_t *lig_ptr, int32_t n
                              const int32_t *pocket_type, const int32_t *pocket_ptr, int32_t n_pocket, int32_t P, int32_t max_pocket,
                              const int32_t *pocket_of, int32_t max_rotors, const kpd_vina_min_params *params, float *pos_out,
                              double *report, int32_t *status, void *stream);
+
+/* Monte-Carlo search of sampled ligands in their pockets under that score (csrc/vina_dock.hip).  Stands where upstream runs
+ * gen_docking_cmds.py without --minimize: full gnina docking inside --autobox_ligand <reference ligand>, written out as
+ * gen_ligands_docked.sdf.  gnina's search, its torsion tree and its numbers cannot be restated here, so THIS COMMENT IS THE
+ * DEFINITION.  THE POSES AND SCORES ARE NOT gnina's OR Vina's: typing, rotor rule, pair terms, weights and the recalled constants
+ * are those of kpd_vina_score, and the search is the one written down here.  A rigid pocket, no hydrogens.
+ *
+ * All arithmetic is fp64.  Everything not restated here is that of kpd_vina_minimize, word for word: types, rotors, pieces,
+ * bodies, the chart move(x, delta), the objective E = inter + w_intra intra, and the minimiser's rules.
+ * Random numbers: Philox4x32-10, key = (low, high) half of seed, counter = (q, s, c, id): block q, step s, chain c, and id =
+ *   lig_id[b] (b itself when lig_id is NULL), so a ligand's result does not depend on its place in the batch.  Word j of a block
+ *   becomes u_j = (w_j + 0.5) 2^-32, in (0, 1).  ball(u1, u2, u3), a vector of the unit ball: z = 2 u1 - 1, phi = 2 pi u2, rho =
+ *   cbrt(u3), v = rho (sqrt(1 - z z) cos phi, sqrt(1 - z z) sin phi, z).  Blocks: q = 0, the mutation of step s; q = 1, word 0:
+ *   the Metropolis draw of step s; of the random start (s = 0): q = 2 + 2 f, the rotation of fragment f; q = 3 + 2 f, its place;
+ *   q = 18 + j, word k - 4 j: the angle of active rotor k in 4 j .. 4 j + 3.
+ * minimise(x, K): the iteration loop of kpd_vina_minimize from x with max_iters = K and fresh L-BFGS memory, in fp64 throughout:
+ *   the closing fp32 step is not taken.  K = 0 is one evaluation.  A line search that is exhausted ends that minimisation only.
+ * The box test: a pose is outside iff the mean of all the ligand's atoms (summed in index order) is below box_lo or above box_hi
+ *   in any coordinate.
+ * Chain c of a ligand:
+ *   Step 0.  Chain 0 starts at the input pose.  A chain c >= 1 starts at move(input, delta): theta_k = pi (2 u - 1) for every
+ *     active rotor; w_f = pi ball(u0, u1, u2) of block 2 + 2 f and t_f = (lo + u (hi - lo)) - c_f, coordinate j from word j of
+ *     block 3 + 2 f, for every fragment f (c_f its centre in the input pose).  The start is minimised with step_iters and becomes
+ *     the chain's current pose, and its best if E is finite; if E is not finite, or if the minimised start of a chain c >= 1 is
+ *     outside the box (counted as a box rejection), the chain ends with nothing found.
+ *   Step s = 1 .. n_steps.  With u0 .. u3 of block 0: e = min(floor(u0 (2 F + T)), 2 F + T - 1) selects one slot group of a delta
+ *     that is zero elsewhere.  e < F: t_e = amplitude ball(u1, u2, u3).  F <= e < 2 F, f = e - F: w_f = (amplitude / r_f) ball(u1,
+ *     u2, u3), r_f = sqrt(sum_{i in f} |x_i - c_f|^2 / n_f) summed in index order, each |.|^2 as (dx^2 + dy^2) + dz^2; delta stays
+ *     0 where r_f < 1e-6.  e >= 2 F, k = e - 2 F: theta_k = pi (2 u1 - 1).  candidate = minimise(move(current, delta), step_iters).
+ *     It is box-rejected, before minimising (then nothing is evaluated) and again after, if it is outside the box.  Otherwise it is
+ *     accepted iff E_cand is finite and (E_cand < E_cur or u_M < exp((E_cur - E_cand) / temperature)), and then becomes the
+ *     current pose.  The chain's best is the lowest-E candidate with a finite E that was not box-rejected, accepted or not; a tie
+ *     stays with the earlier step.
+ *   Refinement.  x = minimise(best, max_iters), then the closing step of kpd_vina_minimize: x is rounded to fp32 and evaluated
+ *     there; the rounded point is kept iff its E does not exceed the best's E and, for a chain c >= 1, it is inside the box, else
+ *     the fp32 rounding of the best itself is kept and evaluated.  What is reported is always the evaluation at the fp32 rows
+ *     written.  So a pose of a chain c >= 1 lies in the box (to the fp32 rounding of its rows); chain 0, which starts at the input
+ *     pose wherever that is, is box-tested in its steps only.
+ * Modes: the chains that found a pose are ranked by (E, chain index) and walked in that order; a pose is kept iff its RMSD to
+ *   every pose kept before is >= min_rmsd, until n_modes are kept.  That RMSD is sqrt(sum_i |x_i - y_i|^2 / n) over all atoms of
+ *   the fp32 rows, in fp64, summed in index order.
+ *
+ * kpd_vina_dock: the inputs of kpd_vina_minimize, and box_lo, box_hi [B,3] fp32 (the search box of every ligand), lig_id [B] or
+ *   NULL, seed, n_chains (1 .. 64), n_steps (>= 0), n_modes (1 .. n_chains); params: NULL for kpd_vina_dock_defaults
+ *   (kpd_vina_min_defaults, temperature 1.2, amplitude 2 A (Vina's, RECALLED, NOT CHECKED), min_rmsd 1 A, step_iters 20; max_iters
+ *   200 is the refinement's).  KPD_ERR_INVALID for counts out of range and for temperature, amplitude or min_rmsd that are not
+ *   > 0.  Out (device): pos_out [n_modes,n_atoms,3] fp32, mode-major, so mode 0 is a drop-in pos; rows of a mode that does not
+ *   exist are the input rows (pos_out and chain_pos must not be pos).  n_found [B].  report [B,n_modes,8] fp64 = {score, E,
+ *   inter, intra, rmsd to the input pose (as kpd_vina_minimize's), rmsd to mode 0, chain, gnorm}, zeros for a mode that does not
+ *   exist.  chain_pos [n_chains,n_atoms,3] fp32 and chain_report [B,n_chains,10] fp64 = {E, inter, intra, step of the best (-1:
+ *   none), accepted steps, box rejections, evaluations, found, gnorm, score} are caller-allocated, the search's only global
+ *   intermediate, and double as diagnostics; the rows of a chain that found nothing are the input rows, its first three and last
+ *   two columns zeros.  status [B]: bits 0, 1, 2, 4, 5 as for kpd_vina_minimize, bit 7 = a box bound that is not finite or lo >
+ *   hi, bit 8 = the input pose is outside the box (informational), bit 9 = fewer than n_modes were found (informational).  With
+ *   bit 0, 1, 5 or 7 the ligand is left out: n_found 0, zero reports, its input rows in every mode and chain.
+ *   k_vina_dock runs one workgroup per (ligand, chain), k_vina_dock_modes one per ligand: two launches, and n_modes + n_chains
+ *   copies pos -> rows, whatever B is; no host synchronisation, no atomics on floats.  A ligand's result is bitwise independent
+ *   of the rest of the batch and of its place in it (given lig_id), of max_atoms / max_pocket, of max_rotors once it is at least
+ *   the ligand's rotor count, and of the repeat; chain c's chain_pos and chain_report do not depend on n_chains.  With n_chains =
+ *   1, n_steps = 0 and step_iters = 0, mode 0 is kpd_vina_minimize's result to the bit. */
+enum {
+    KPD_VINA_DOCK_NO_MOLECULE = 1,
+    KPD_VINA_DOCK_BAD_INPUT = 2,
+    KPD_VINA_DOCK_ATOM_OUT = 4,
+    KPD_VINA_DOCK_FROZEN_ROTORS = 16,
+    KPD_VINA_DOCK_FRAGMENTS = 32,
+    KPD_VINA_DOCK_BAD_BOX = 128,
+    KPD_VINA_DOCK_START_OUTSIDE = 256,
+    KPD_VINA_DOCK_FEW_MODES = 512
+};
+typedef struct kpd_vina_dock_params {
+    double w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond, w_rot, r_c, w_intra, gtol, max_step;
+    int32_t max_iters;
+    double temperature, amplitude, min_rmsd;
+    int32_t step_iters;
+} kpd_vina_dock_params;
+void kpd_vina_dock_defaults(kpd_vina_dock_params *params);
+kpd_status kpd_vina_dock(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, int32_t max_atoms,
+                         const int32_t *elem, int32_t F, const int32_t *z, const float *lig_radius, const int32_t *frag,
+                         const int32_t *bond_ij, const int32_t *bond_order, const int32_t *bond_ptr, int32_t cap_bonds,
+                         const int32_t *mol_status, const int32_t *lig_type_in, const float *pocket_x, const float *pocket_radius,
+                         const int32_t *pocket_type, const int32_t *pocket_ptr, int32_t n_pocket, int32_t P, int32_t max_pocket,
+                         const int32_t *pocket_of, int32_t max_rotors, const float *box_lo, const float *box_hi,
+                         const int32_t *lig_id, uint64_t seed, int32_t n_chains, int32_t n_steps, int32_t n_modes,
+                         const kpd_vina_dock_params *params, float *pos_out, int32_t *n_found, double *report, float *chain_pos,
+                         double *chain_report, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

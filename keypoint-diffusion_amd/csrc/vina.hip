@@ -3,7 +3,7 @@
 // (analysis/docking: gen_docking_cmds.py).  Vina's own typing reads hydrogens and AutoDock atom types from PDBQT; ligands and
 // pockets here carry heavy atoms and element classes, so include/kpd.h DEFINES the typing (three flags per atom from the element,
 // the heavy degree and the neighbours' elements and length-class bond orders) and the rotor count.  NOT gnina's numbers: the
-// scores rank samples scored here against each other.  No search, no minimisation under this function, no intramolecular term.
+// scores rank samples scored here against each other.  No intramolecular term; minimisation and search under this function are vina_min.hip and vina_dock.hip.
 // k_vina_pocket_types: one thread per pocket atom, the atoms of its pocket tiled through LDS 256 at a time (quadratic per pocket,
 // which is right for pockets of hundreds of atoms); done once per pocket set.
 // k_vina_score: one workgroup (4 waves) per ligand and ONE launch: the ligand's bond graph as a bit matrix in LDS, typing, the

@@ -98,6 +98,11 @@ class KpdVinaMinParams(C.Structure):
                                                   'gtol', 'max_step')] + [('max_iters', C.c_int32)])
 
 
+class KpdVinaDockParams(C.Structure):
+    _fields_ = (KpdVinaMinParams._fields_ + [(name, C.c_double) for name in ('temperature', 'amplitude', 'min_rmsd')] +
+                [('step_iters', C.c_int32)])
+
+
 class KpdError(RuntimeError):
     pass
 
@@ -218,6 +223,11 @@ def lib():
     L.kpd_vina_minimize.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 +
                                     [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.POINTER(KpdVinaMinParams)] +
                                     [C.c_void_p] * 4)
+    L.kpd_vina_dock_defaults.argtypes = [C.POINTER(KpdVinaDockParams)]
+    L.kpd_vina_dock_defaults.restype = None
+    L.kpd_vina_dock.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 +
+                                [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
+                                [C.c_uint64] + [C.c_int32] * 3 + [C.POINTER(KpdVinaDockParams)] + [C.c_void_p] * 7)
     _lib = L
     return L
 
@@ -251,6 +261,7 @@ EXPORTS = [
     'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
     'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_relax_defaults', 'kpd_relax',
     'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score', 'kpd_vina_min_defaults', 'kpd_vina_minimize',
+    'kpd_vina_dock_defaults', 'kpd_vina_dock',
 ]
 
 
@@ -1331,6 +1342,76 @@ def vina_minimize(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch
                                   _ptr(pocket_ptr), M, P, max_pocket, _ptr(pocket_of), max_rotors, C.byref(p), _ptr(pos_out),
                                   _ptr(report), _ptr(status), _stream()))
     return pos_out, report, status
+
+
+# status bits of kpd_vina_dock (bits 0, 1, 2, 4, 5 as for kpd_vina_minimize)
+VINA_DOCK_NO_MOLECULE, VINA_DOCK_BAD_INPUT, VINA_DOCK_ATOM_OUT, VINA_DOCK_FROZEN_ROTORS, VINA_DOCK_FRAGMENTS = 1, 2, 4, 16, 32
+VINA_DOCK_BAD_BOX, VINA_DOCK_START_OUTSIDE, VINA_DOCK_FEW_MODES = 128, 256, 512
+VINA_DOCK_LEFT_OUT = VINA_DOCK_NO_MOLECULE | VINA_DOCK_BAD_INPUT | VINA_DOCK_FRAGMENTS | VINA_DOCK_BAD_BOX
+VINA_DOCK_REPORT = ('score', 'E', 'inter', 'intra', 'rmsd_input', 'rmsd_best', 'chain', 'gnorm')
+VINA_DOCK_CHAIN_REPORT = ('E', 'inter', 'intra', 'best_step', 'accepted', 'box_rejected', 'evaluations', 'found', 'gnorm', 'score')
+VINA_DOCK_MAX_CHAINS = 64
+
+
+def vina_dock_params(**params) -> KpdVinaDockParams:
+    """The parameters of kpd_vina_dock: the library's defaults (kpd_vina_dock_defaults: those of kpd_vina_minimize, temperature
+    1.2, amplitude 2, min_rmsd 1, step_iters 20; max_iters is the refinement's) with the given fields replaced."""
+    p, names = _struct_params('vina_dock', KpdVinaDockParams, lib().kpd_vina_dock_defaults, params, ints=('max_iters', 'step_iters'))
+    if not (all(abs(getattr(p, k)) < 1e12 for k in names) and 0 < p.r_c < 1e6 and p.w_rot >= 0 and p.w_intra >= 0 and p.gtol >= 0 and
+            p.max_step > 0 and p.max_iters >= 0 and p.step_iters >= 0 and p.temperature > 0 and p.amplitude > 0 and p.min_rmsd > 0):
+        raise KpdError('vina_dock: ' + ', '.join(f'{k} {getattr(p, k)}' for k in names) + ': the weights must be finite, w_rot, w_intra, '
+                       'gtol, max_iters and step_iters >= 0, r_c, max_step, temperature, amplitude and min_rmsd > 0')
+    return p
+
+
+def vina_dock(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch.Tensor, mol: dict, pocket_x: torch.Tensor,
+              pocket_radius: torch.Tensor, pocket_type: torch.Tensor, pocket_ptr: torch.Tensor, pocket_of: torch.Tensor,
+              box_lo: torch.Tensor, box_hi: torch.Tensor, n_chains: int = 8, n_steps: int = 50, n_modes: Optional[int] = None,
+              seed: int = 0, lig_id: Optional[torch.Tensor] = None, lig_type_in: Optional[torch.Tensor] = None,
+              max_atoms: int = MOL_MAX_ATOMS, max_pocket: Optional[int] = None, max_rotors: int = VINA_MIN_MAX_ROTORS, **params):
+    """Search poses of a batch of perceived ligands in their rigid pockets under the score of `vina_score`: n_chains Monte-Carlo
+    chains per ligand (perturb, minimise, Metropolis) inside the box [box_lo, box_hi] ([B,3] fp32), then ranking and clustering
+    into n_modes poses (`min(9, n_chains)` by default), on the GPU in two launches (kpd_vina_dock; include/kpd.h DEFINES the
+    search: this library's own, NOT gnina's or Vina's docking or numbers).  The other arguments are those of `vina_minimize`;
+    lig_id [B] int32 names every ligand's random stream (its index by default).  Returns a dict of device tensors: pos [n_modes,N,3]
+    fp32 (rows of a mode that does not exist are the input rows), n_found [B], report [B,n_modes,8] float64 (columns
+    VINA_DOCK_REPORT), chain_pos [n_chains,N,3], chain_report [B,n_chains,10] (columns VINA_DOCK_CHAIN_REPORT), status [B].  No host
+    synchronisation."""
+    pos, pocket_x, pocket_of, B, N, F, M, P, zt, max_atoms, max_pocket = _ligand_pocket_args(
+        'vina_dock', pos, lig_ptr, z, mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'), pocket_x, pocket_ptr, pocket_of,
+        max_atoms, max_pocket)
+    lig_radius, pocket_radius = _dev_f32(lig_radius, 'lig_radius'), _dev_f32(pocket_radius, 'pocket_radius')
+    box_lo, box_hi = _dev_f32(box_lo, 'box_lo'), _dev_f32(box_hi, 'box_hi')
+    pocket_type = _per_entry(pocket_type, 'vina_dock: pocket_type', M, 'pocket atom')
+    if lig_type_in is not None:
+        lig_type_in = _per_entry(lig_type_in, 'vina_dock: lig_type_in', N, 'ligand atom')
+    if lig_id is not None:
+        lig_id = _per_entry(lig_id, 'vina_dock: lig_id', B, 'ligand', contiguous=True)
+    cap_bonds = mol['order'].numel()
+    max_rotors, n_chains, n_steps, seed = int(max_rotors), int(n_chains), int(n_steps), int(seed)
+    n_modes = min(9, n_chains) if n_modes is None else int(n_modes)
+    if (lig_radius.shape != (F,) or pocket_radius.shape != (M,) or mol['bonds'].numel() != 2 * cap_bonds or mol['frag'].numel() != N or
+            not 0 <= max_rotors <= VINA_MIN_MAX_ROTORS or box_lo.shape != (B, 3) or box_hi.shape != (B, 3)):
+        raise KpdError(f'vina_dock: lig_radius {tuple(lig_radius.shape)} must be [{F}], pocket_radius {tuple(pocket_radius.shape)} '
+                       f'[{M}], frag hold {N} labels, bonds two atoms for each of the {cap_bonds} orders, max_rotors {max_rotors} '
+                       f'be 0 .. {VINA_MIN_MAX_ROTORS}, box_lo {tuple(box_lo.shape)} and box_hi {tuple(box_hi.shape)} be [{B},3]')
+    if not (1 <= n_chains <= VINA_DOCK_MAX_CHAINS and 1 <= n_modes <= n_chains and n_steps >= 0 and 0 <= seed < 1 << 64):
+        raise KpdError(f'vina_dock: n_chains {n_chains} must be 1 .. {VINA_DOCK_MAX_CHAINS}, n_modes {n_modes} 1 .. n_chains, n_steps '
+                       f'{n_steps} >= 0, seed {seed} in [0, 2^64)')
+    p = vina_dock_params(**params)
+    dev = pos.device
+    out = dict(pos=torch.empty(n_modes, N, 3, dtype=torch.float32, device=dev), n_found=torch.empty(B, dtype=torch.int32, device=dev),
+               report=torch.empty(B, n_modes, len(VINA_DOCK_REPORT), dtype=torch.float64, device=dev),
+               chain_pos=torch.empty(n_chains, N, 3, dtype=torch.float32, device=dev),
+               chain_report=torch.empty(B, n_chains, len(VINA_DOCK_CHAIN_REPORT), dtype=torch.float64, device=dev),
+               status=torch.empty(B, dtype=torch.int32, device=dev))
+    check(lib().kpd_vina_dock(_ptr(pos), _ptr(lig_ptr), N, B, max_atoms, _ptr(mol['elem']), F, _ptr(zt), _ptr(lig_radius),
+                              _ptr(mol['frag']), _ptr(mol['bonds']), _ptr(mol['order']), _ptr(mol['bond_ptr']), cap_bonds,
+                              _ptr(mol['status']), _ptr(lig_type_in), _ptr(pocket_x), _ptr(pocket_radius), _ptr(pocket_type),
+                              _ptr(pocket_ptr), M, P, max_pocket, _ptr(pocket_of), max_rotors, _ptr(box_lo), _ptr(box_hi), _ptr(lig_id),
+                              seed, n_chains, n_steps, n_modes, C.byref(p), _ptr(out['pos']), _ptr(out['n_found']), _ptr(out['report']),
+                              _ptr(out['chain_pos']), _ptr(out['chain_report']), _ptr(out['status']), _stream()))
+    return out
 
 
 def sample_update(pb: PreparedBatch, atom_nf, lig_x, lig_h, kp_x, eps_x, eps_h, noise_x, noise_h, coef):

@@ -21,8 +21,9 @@ SDF blocks with rdkit.  The scoring half of docking is here: `Molecules.vina_sco
 FUNCTIONAL FORM (five pair terms over ligand x pocket heavy atoms, divided by 1 + w_rot N_rot) with its analytic gradient for the
 whole batch in one launch (`kpd_vina_score`, csrc/vina.hip).  The typing is a rule of this library's own, defined in
 include/kpd.h (no hydrogens, no aromaticity), and the weights and radii are recalled constants: the scores rank samples scored
-here against each other and ARE NOT gnina's or Vina's numbers.  No search, no minimisation under this function, no
-intramolecular term.
+here against each other and ARE NOT gnina's or Vina's numbers.  That call scores the poses it is given; `Molecules.vina_minimize`
+/ `minimize_samples` minimise them under the function and `Molecules.vina_dock` / `dock_samples` search for poses under it
+(`kpd_vina_minimize`, `kpd_vina_dock`): this library's own minimiser and search, defined in include/kpd.h, NOT gnina's.
 
 Where upstream minimises every sample inside its pocket with RDKit's UFF (analysis/pocket_minimization.py), `Molecules.relax` /
 `relax_samples` relax the whole batch in one kernel launch (`kpd_relax`, csrc/relax.hip) with a force field of this library's
@@ -351,6 +352,110 @@ class Molecules:
                                                 max_rotors=hip.VINA_MIN_MAX_ROTORS if max_rotors is None else max_rotors, **params)
         return VinaMinimized(self, pos, report, status, pocket_types)
 
+    def _dock_box(self, pocket_of: torch.Tensor, n_pockets: int, box, autobox_ligand, autobox_add: float):
+        """The search box of every ligand, (lo, hi) as [B,3] fp32 device tensors: `box` per ligand or per pocket, else the bounding
+        box of the pocket's `autobox_ligand` widened by `autobox_add`, else (also for a ligand without a pocket) that of the
+        ligand's own input pose."""
+        dev, B = self.pos.device, len(self)
+        sizes = self.lig_ptr[1:] - self.lig_ptr[:-1]
+        idx = torch.repeat_interleave(torch.arange(B, device=dev), sizes.long())[:, None].expand(-1, 3)
+        own_lo = torch.full((B, 3), float('inf'), device=dev).scatter_reduce(0, idx, self.pos, 'amin') - float(autobox_add)
+        own_hi = torch.full((B, 3), float('-inf'), device=dev).scatter_reduce(0, idx, self.pos, 'amax') + float(autobox_add)
+        if box is None and autobox_ligand is None:
+            return own_lo, own_hi
+        if box is not None:
+            lo, hi = (torch.as_tensor(t, dtype=torch.float32).to(dev).reshape(-1, 3) for t in box)
+            if lo.shape != hi.shape or lo.shape[0] not in (B, n_pockets):
+                raise hip.KpdError(f'vina_dock: box must be (lo, hi) of [{B},3] per ligand or [{n_pockets},3] per pocket, got '
+                                   f'{tuple(lo.shape)} and {tuple(hi.shape)}')
+            if lo.shape[0] == B:
+                return lo.contiguous(), hi.contiguous()
+        else:
+            if len(autobox_ligand) != n_pockets:
+                raise hip.KpdError(f'vina_dock: autobox_ligand must hold one [n,3] reference ligand for each of the {n_pockets} pockets')
+            ref = [torch.as_tensor(r, dtype=torch.float32).to(dev).reshape(-1, 3) for r in autobox_ligand]
+            lo = torch.stack([r.amin(dim=0) for r in ref]) - float(autobox_add)
+            hi = torch.stack([r.amax(dim=0) for r in ref]) + float(autobox_add)
+        has, q = (pocket_of >= 0)[:, None], pocket_of.clamp(min=0).long()
+        return torch.where(has, lo[q], own_lo).contiguous(), torch.where(has, hi[q], own_hi).contiguous()
+
+    def vina_dock(self, pocket_pos: List[torch.Tensor], pocket_elements: List[Sequence[str]], pocket_of=None, box=None,
+                  autobox_ligand=None, autobox_add: float = 4.0, n_chains: int = 8, n_steps: int = 50, n_modes: Optional[int] = None,
+                  seed: int = 0, lig_ids=None, radii: Optional[Dict[str, float]] = None, pocket_types=None,
+                  lig_types: Optional[torch.Tensor] = None, max_rotors: Optional[int] = None, **params) -> 'VinaDocked':
+        """Search poses of every ligand in its rigid pocket under the score of `vina_score`: `n_chains` Monte-Carlo chains per
+        ligand (perturb, minimise, Metropolis) inside a box, then ranking and clustering into `n_modes` poses, in two launches
+        (`kpd_vina_dock`): what upstream does with full gnina docking inside `--autobox_ligand` (gen_docking_cmds.py without
+        --minimize), with the search include/kpd.h DEFINES.  NOT gnina's or Vina's docking and NOT their numbers: the typing, the
+        weights and the radii are those of `vina_score`.
+        `pocket_pos`, `pocket_elements`, `pocket_of`, `radii`, `pocket_types`, `lig_types`, `max_rotors`: as for `vina_minimize`;
+        `box`: (lo, hi), each [B,3] per ligand or [P,3] per pocket; `autobox_ligand`: a reference ligand's [n,3] per pocket, whose
+        bounding box widened by `autobox_add` is the box, as gnina's `--autobox_ligand`; with neither, the box is the ligand's own
+        input bounding box widened by `autobox_add`; `n_modes`: `min(9, n_chains)` by default; `seed` and `lig_ids` (the name of
+        every ligand's random stream, its index by default) fix the random numbers; `params`: the parameters of `vina_minimize`
+        (max_iters is the final refinement's) and temperature, amplitude, min_rmsd, step_iters."""
+        (pocket_x, pocket_ptr, pocket_of, sizes, z, max_atoms, dev, lig_radius, pocket_radius, pocket_types,
+         lig_types) = self._vina_inputs('vina_dock', 'docking', pocket_pos, pocket_elements, pocket_of, radii, pocket_types, lig_types)
+        n_chains = int(n_chains)
+        n_modes = min(9, n_chains) if n_modes is None else int(n_modes)
+        mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
+        if len(self) == 0:
+            i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+            f64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
+            empty = dict(pos=torch.zeros(max(n_modes, 1), 0, 3, device=dev), n_found=i32(0), report=f64(0, max(n_modes, 1), 8),
+                         chain_pos=torch.zeros(max(n_chains, 1), 0, 3, device=dev), chain_report=f64(0, max(n_chains, 1), 10), status=i32(0))
+            z3 = torch.zeros(0, 3, device=dev)
+            return VinaDocked(self, empty, pocket_types, (z3, z3))
+        lo, hi = self._dock_box(pocket_of, len(pocket_pos), box, autobox_ligand, autobox_add)
+        if lig_ids is not None:
+            lig_ids = torch.as_tensor(lig_ids).to(torch.int32).to(dev).flatten()
+        out = hip.vina_dock(self.pos, self.lig_ptr, z, lig_radius, mol, pocket_x, pocket_radius, pocket_types, pocket_ptr, pocket_of, lo, hi,
+                            n_chains=n_chains, n_steps=n_steps, n_modes=n_modes, seed=seed, lig_id=lig_ids, lig_type_in=lig_types,
+                            max_atoms=max_atoms, max_pocket=max(sizes, default=0),
+                            max_rotors=hip.VINA_MIN_MAX_ROTORS if max_rotors is None else max_rotors, **params)
+        return VinaDocked(self, out, pocket_types, (lo, hi))
+
+
+class VinaDocked:
+    """What `Molecules.vina_dock` returns: `.molecules` (a `Molecules` with the same bond graph at mode 0, the best pose found),
+    `.mode(k)` (the same at mode k; a ligand with fewer modes keeps its input pose there), `.n_found` [B], `.report`
+    [B,n_modes,8] float64 (columns hip.VINA_DOCK_REPORT), `.chain_report` [B,n_chains,10] (columns hip.VINA_DOCK_CHAIN_REPORT),
+    `.status` [B] (bits: 1 no molecule, 2 bad input, 4 some atom took no part, 16 rotors frozen, 32 more than 8 fragments, 128 a
+    bad box, 256 the input pose is outside the box, 512 fewer than n_modes found; with 1, 2, 32 or 128 the ligand is unchanged),
+    `.box` (lo, hi) [B,3] and `.pocket_types` [M], device tensors.  NOT gnina's or Vina's docking or numbers: see include/kpd.h."""
+
+    def __init__(self, mols: Molecules, out: Dict[str, torch.Tensor], pocket_types: torch.Tensor, box):
+        self._mols, self._pos, self.chain_pos = mols, out['pos'], out['chain_pos']
+        self.n_found, self.report, self.chain_report, self.status = out['n_found'], out['report'], out['chain_report'], out['status']
+        self.pocket_types, self.box = pocket_types, box
+        self.molecules = self.mode(0)
+
+    @property
+    def n_modes(self) -> int:
+        return int(self._pos.shape[0])
+
+    def mode(self, k: int) -> Molecules:
+        """The batch at mode k (0 is the best) as `Molecules`."""
+        if not 0 <= int(k) < self.n_modes:
+            raise IndexError(f'mode {k} of {self.n_modes}')
+        m = self._mols
+        return Molecules(m.lig_ptr, m.summary, m.status, m.elem, m.valence, m.frag, m.bonds, m.order, m.bond_ptr, self._pos[int(k)],
+                         m.lig_elements, m._max_atoms, sizes=m._sizes)
+
+    def sdf(self) -> List[str]:
+        """Per ligand its found modes in rank order as consecutive MOL blocks, the layout of a gnina output file
+        (gen_ligands_docked.sdf); the empty string for a ligand with no mode."""
+        found = self.n_found.tolist()
+        blocks = [self.mode(k).sdf(strict=False) for k in range(max(found, default=0))]
+        return [''.join(blocks[k][b] for k in range(found[b])) for b in range(len(found))]
+
+    def table(self) -> Dict[str, list]:
+        """lig_idx, mode, score, rmsd_input, chain, as lists: one row per found mode, ligands in batch order, modes in rank order."""
+        found, rep = self.n_found.tolist(), self.report.cpu()
+        rows = [(b, k) for b in range(len(found)) for k in range(found[b])]
+        return dict(lig_idx=[b for b, _ in rows], mode=[k for _, k in rows], score=[rep[b, k, 0].item() for b, k in rows],
+                    rmsd_input=[rep[b, k, 4].item() for b, k in rows], chain=[int(rep[b, k, 6].item()) for b, k in rows])
+
 
 class VinaMinimized:
     """What `Molecules.vina_minimize` returns: `.molecules` (a `Molecules` with the same bond graph at the minimised pose, so its
@@ -605,4 +710,37 @@ def minimize_samples(samples: List[dict], pockets: List[dict], lig_elements: Seq
         mols = relaxed.molecules
     out = mols.vina_minimize(pocket_pos, pocket_elements, pocket_of=pocket_of, radii=radii, pocket_types=pocket_types, max_rotors=max_rotors,
                              **params)
+    return (relaxed, out) if relax else out
+
+
+def dock_samples(samples: List[dict], pockets: List[dict], lig_elements: Sequence[str], ref_ligands=None, relax: bool = False, device=None,
+                 allowed_bonds: Optional[Dict[str, object]] = None, radii: Optional[Dict[str, float]] = None,
+                 vdw: Optional[Dict[str, tuple]] = None, pocket_types=None, max_rotors: Optional[int] = None,
+                 relax_params: Optional[Dict[str, float]] = None, **dock):
+    """Dock every sampled ligand in its own pocket under the Vina-form score (`Molecules.vina_dock`, whose limits apply: NOT
+    gnina's docking or numbers), beside `minimize_samples`: the counterpart of upstream's gen_docking_cmds.py without --minimize.
+    `samples` and `pockets` as for `minimize_samples`; `ref_ligands`: one [n,3] reference ligand per pocket, whose bounding box
+    widened by `autobox_add` is the search box (`--autobox_ligand`); without it every ligand searches the box of its own input
+    pose.  Returns the `VinaDocked`; with `relax=True` the ligands are first relaxed in their pockets and the result is (the
+    `Relaxed`, the `VinaDocked` of the relaxed poses).  `dock`: what `Molecules.vina_dock` takes (box, autobox_add, n_chains,
+    n_steps, n_modes, seed, lig_ids and the parameters)."""
+    if len(samples) != len(pockets):
+        raise ValueError('samples and pockets must have one entry per pocket')
+    lig_pos, lig_feat, pocket_of = [], [], []
+    for q, rec in enumerate(samples):
+        lig_pos.extend(rec['positions'])
+        lig_feat.extend(rec['features'])
+        pocket_of.extend([q] * len(rec['positions']))
+    pocket_pos = [torch.as_tensor(p['positions']) for p in pockets]
+    if device is not None:
+        lig_pos, lig_feat = [p.to(device) for p in lig_pos], [f.to(device) for f in lig_feat]
+        pocket_pos = [p.to(device) for p in pocket_pos]
+    pocket_elements = [list(p['elements']) for p in pockets]
+    mols = build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds)
+    relaxed = None
+    if relax:
+        relaxed = mols.relax(pocket_pos, pocket_elements, pocket_of=pocket_of, vdw=vdw, **(relax_params or {}))
+        mols = relaxed.molecules
+    out = mols.vina_dock(pocket_pos, pocket_elements, pocket_of=pocket_of, autobox_ligand=ref_ligands, radii=radii,
+                         pocket_types=pocket_types, max_rotors=max_rotors, **dock)
     return (relaxed, out) if relax else out
