@@ -698,11 +698,13 @@ kpd_status kpd_interface_points(const float *rec_x, const int32_t *rec_ptr, cons
  * through openbabel), check_atom_valency and compute_avg_frag_size (analysis/metrics.py:156-206) and the SDF writing of
  * sample.py.  openbabel's rules cannot be restated here, so THIS COMMENT IS THE DEFINITION: the lookup-table builder of the
  * EDM / DiffSBDD lineage that upstream's molecule_builder.py was adapted from.  Connectivity comes from covalent radii, bond
- * orders from length classes, both under valence caps.  Sanitisation, RDKit's force fields and docking stay with the caller;
+ * orders from length classes, both under valence caps.  Sanitisation (rings, Kekule orders, hydrogen counts, validity) is
+ * kpd_mol_sanitize below; RDKit's force fields stay with the caller;
  * what upstream compares SMILES for (uniqueness, novelty) is kpd_mol_keys below, and the relaxation of the samples inside their
  * pockets (by a force field of this library's own, not UFF) is kpd_relax at the end of this file.
  *
- * Ligands carry heavy atoms only; no hydrogens are added.  Everything below is per ligand (at most 256 atoms).
+ * Ligands carry heavy atoms only; no hydrogens are added here (kpd_mol_sanitize counts them per atom, without positions).
+ * Everything below is per ligand (at most 256 atoms).
  * Element table, by atomic number (radii after Pyykko & Atsumi 2009 in integer picometres, single / double / triple, 0 = no
  * bond of that order; cap = chemical valence cap):
  *     H  1:  32   0   0  1      B  5:  85  78   0  3      C  6:  75  67  60  4      N  7:  71  60  54  3      O  8:  63  57   0  2
@@ -726,8 +728,8 @@ kpd_status kpd_interface_points(const float *rec_x, const int32_t *rec_ptr, cons
  *   6. validity (upstream's check_atom_valency): an atom is invalid if valence == 0, valence > allowed[class], or its element
  *      is unknown.  `allowed` comes from the caller (upstream's allowed_bonds maxima) and is deliberately another table than
  *      `cap`: a sulfone S (valence 6 > 4) counts as invalid, as it would upstream.
- * Limits: the orders are LENGTH CLASSES.  No aromaticity or Kekule perception (an ideal benzene, 1.397 A, gets six single
- *   bonds), no formal charges (nitro groups are demoted to single bonds).  Connectivity, fragments and the counts of step 5 do
+ * Limits: the orders are LENGTH CLASSES.  No aromaticity or Kekule perception in this call (an ideal benzene, 1.397 A, gets six
+ *   single bonds; kpd_mol_sanitize writes Kekule orders next to them), no formal charges (nitro groups are demoted to single bonds).  Connectivity, fragments and the counts of step 5 do
  *   not depend on the orders.
  *
  * kpd_mol_perceive: pos [n_atoms,3], feat [n_atoms,F], lig_ptr [B+1], z [F] (atomic number of every feature class), allowed
@@ -784,8 +786,9 @@ kpd_status kpd_sdf_emit(const float *pos, const int32_t *lig_ptr, int32_t n_atom
  *   sets bit (f_r[a] mod nbits) of the ligand's row: bit k is bit (k & 31) of word (k >> 5).  The seeds are local on purpose:
  *   molecules that share a substructure share its bits.
  * Limits: a key describes the CONSTITUTION only: no stereo (enantiomers and E/Z isomers share a key), no hydrogens, no
- *   charges.  With with_orders it inherits the length-class bond orders of kpd_mol_perceive (no aromaticity: two Kekule-like
- *   geometries of one ring can differ); with_orders = 0 makes it independent of them.  It is a hash: equal keys of
+ *   charges.  With with_orders it inherits the bond orders it is given: the length classes of kpd_mol_perceive know no
+ *   aromaticity (two Kekule-like geometries of one ring can differ), order_k of kpd_mol_sanitize does; with_orders = 0 makes it
+ *   independent of them.  It is a hash: equal keys of
  *   non-isomorphic graphs are possible in principle (none among the 1 136 pairs of equal size, composition and bond count,
  *   27 of them isomorphic, of the 700 seeded random molecule-like graphs of tests/test_molset_config.py: there key equality
  *   and labelled-graph isomorphism coincide).
@@ -812,6 +815,77 @@ kpd_status kpd_mol_keys(const int32_t *lig_ptr, int32_t n_atoms, int32_t B, cons
                         int32_t nbits, int64_t *key, uint32_t *fp, int64_t *atom_inv, int32_t *status, void *stream);
 kpd_status kpd_fp_diversity(const uint32_t *fp, const uint8_t *use, int32_t B, int32_t W, const int32_t *group_ptr, int32_t G,
                             double *div_sum, int64_t *n_pairs, int32_t *status, void *stream);
+
+/* Sanitisation of the perceived molecules (csrc/sanitize.hip): ring bonds, planar rings, a Kekule assignment, aromatic rings,
+ * implicit hydrogens, donor / acceptor flags, validity and the per-molecule descriptors.  Stands where upstream calls
+ * Chem.SanitizeMol on every sample (`validity` of ModelAnalyzer.sample_and_analyze, analysis/metrics.py) and reads molecular
+ * weight, donors, acceptors, rotatable bonds and the Lipinski count off the RDKit molecule (MoleculeProperties).  RDKit's rules
+ * cannot be restated here, so THIS COMMENT IS THE DEFINITION; no agreement with RDKit or openbabel is claimed.  The inputs are
+ * what kpd_mol_perceive left on the device and are never written; a second set of bond orders (order_k) is written next to the
+ * length classes.  Scope S, Z(a), deg(a) and "both ends in S" are those of kpd_mol_keys; n, m = atoms and bonds in S.
+ * Arithmetic: all geometry is fp64 on the differences of the fp32 coordinates; every product and sum is rounded once (no fused
+ *   multiply-add); d2 and the length tests are those of kpd_mol_perceive.  A NaN or Inf coordinate makes every test it enters false.
+ * Steps:
+ *   1. ring bonds and rings: a bond is a ring bond iff its ends stay connected without it (the rule of N_rot below); ring atoms are
+ *      their ends.  n_rings = m - n + (the number of distinct `frag` labels in S).  The simple cycles of 5 and of 6 atoms in S are
+ *      listed, each once (from its smallest atom, the second atom smaller than the last; ordered by start atom, then
+ *      lexicographically -- no output depends on that order).  More than 64 of them: status bit 1 (TOO_MANY_RINGS), steps 2 - 4 are
+ *      skipped (order_k = bond_order, nothing planar or aromatic) and the ligand is not valid.
+ *   2. planar rings: a cycle p_0 .. p_{k-1} is planar iff each of its k cyclic windows a, b, c, d of four consecutive atoms passes:
+ *      u = b - a, v = c - b, w = d - c, n1 = u x v, n2 = v x w (a component is (x y) - (x' y')), dot products ((.) + (.)) + (.),
+ *      q = |n1|^2 |n2|^2; pass iff q >= 1e-12 and n1.n2 >= 0.9396926207859084 * sqrt(q) (cos 20 deg).  Planar ring bonds and atoms
+ *      are those of planar cycles.
+ *   3. Kekule assignment on the candidate graph G.  Atoms of G: planar ring atoms with Z in {6, 7} and cap(Z) - (number of the
+ *      atom's planar ring bonds) - (sum of bond_order over its other bonds) >= 1, cap from the table above.  Edges of G: planar
+ *      ring bonds between two such atoms that pass the order-1 length test with margin -3 pm (C-C <= 1.47 A, C-N <= 1.43 A;
+ *      this keeps the CH2 of cyclopentadiene out).  Per connected component of G with an edge: the matching M that maximises
+ *      first the number of matched carbons, then the number of matched atoms, and among those has the lexicographically smallest
+ *      ascending list of bond_ij row numbers.  This is an optimum: it does not depend on how it is found.  A component of more
+ *      than 24 atoms sets status bit 2 (COMPONENT_TOO_LARGE): nothing in it is matched, every planar ring bond with an end in it
+ *      keeps bond_order, and its carbons count as unsatisfied.  order_k = 2 on matched bonds, 1 on the other planar ring bonds,
+ *      bond_order on every other bond.  A carbon of G with an edge that M leaves unmatched is UNSATISFIED ("cannot kekulise").
+ *   4. aromatic rings: valence_k(a) = sum of order_k over a's bonds in S.  A planar cycle is aromatic iff every atom contributes
+ *      and the contributions sum to 6: 1 for a matched atom; else 2 for O or S with deg 2; else 2 for an unmatched planar ring N
+ *      with deg 2 or 3 and valence_k = deg (a "lone-pair N": pyrrole N-H, N-alkyl); else 0 for a C with a bond of order_k 2, not a
+ *      planar ring bond, to N, O or S; anything else does not contribute.  Aromatic atoms and bonds are those of aromatic cycles.
+ *   5. hydrogens: h = max(0, normal(Z, valence_k) - valence_k); normal = 4 for C and Si, 3 for N, B and As, 2 for O, 1 for H and
+ *      the halogens, for S the smallest of 2, 4, 6 that is >= valence_k (6 beyond), for P of 3, 5 (5 beyond), 0 otherwise.
+ *      No hydrogen positions are produced.
+ *   6. flags: donor = N or O with h >= 1; acceptor = every O, and every N that is no donor, has deg <= 2 and is no lone-pair N;
+ *      over-valent = valence_k > allowed[class] (the table of kpd_mol_perceive's step 6).
+ *   7. valid iff there is a molecule, no atom of S is over-valent or unsatisfied and neither cap bit is set.  An isolated atom
+ *      is valid (its valence 0 is atom_validity's business).
+ *   8. descriptors over S: desc_i = {n_heavy (Z != 1), n_h (sum of h), hbd (donors), hba (acceptors), n_rot (the rotor rule of
+ *      kpd_vina_score below on order_k: order_k 1, both ends of heavy degree >= 2, no ring bond), n_rings, n_arom_rings (aromatic
+ *      cycles), n_arom_atoms, lipinski4, n_cycles (the cycles of step 1)}; mw = sum over the classes c in class order of
+ *      (double)count_c * mass[c], then + (double)n_h * mass_h (each product and sum rounded once; the counts are integers);
+ *      lipinski4 = how many of mw < 500, hbd <= 5, hba <= 10, n_rot <= 10 hold.  Upstream's fifth rule (Crippen logP <= 5) is
+ *      deliberately NOT counted: logP, QED and SA need RDKit's parameter files and stay with the caller.
+ * Limits: no formal charges (a nitro group stays demoted, its O read as hydroxyls; pyridinium or an N-oxide ends up over-valent or
+ *   non-aromatic); no 7-membered aromatic rings; no tautomer canonicalisation (which N of an imidazole carries the H follows
+ *   from the lexicographic choice, so per-atom h and the Kekule pattern may move under renumbering; the aromatic sets, valid and
+ *   every descriptor do not); no stereo.
+ *
+ * kpd_mol_sanitize: pos [n_atoms,3], lig_ptr [B+1], elem / frag [n_atoms], bond_ij [cap_bonds,2], bond_order [cap_bonds], bond_ptr
+ *   [B+1], mol_status [B] as kpd_mol_perceive wrote them, z / allowed [F], mass [F] fp64 and mass_h (the mass of every class and
+ *   of hydrogen, from the caller); all device pointers.  Out (device): order_k [cap_bonds], bond_flags [cap_bonds] (bit 0 ring,
+ *   1 planar ring, 2 aromatic), valence_k / atom_h / atom_flags [n_atoms] (bit 0 ring, 1 aromatic, 2 donor, 3 acceptor, 4
+ *   unsatisfied, 5 over-valent; -1, 0, 0 for atoms outside S or of a ligand without a molecule), desc_i [B,10], desc_f [B,2] =
+ *   {mw, 0 (reserved)}, valid [B], status [B]: bit 0 = no molecule (the conditions of kpd_mol_keys: mol_status bits 0, 1 or 3, an
+ *   empty S, an element or fragment out of range, a bond outside the ligand, twice (whichever way round it is listed), of an order
+ *   outside 1 .. 3, or a seventh neighbour): desc 0, valid 0, its bond rows read bond_order and flags 0 (rows of a malformed bond range, and rows of no ligand,
+ *   read 0); bits 1 and 2 as above.  A bond of S's ligand with an end outside S reads bond_order and flags 0.
+ *   One wave per ligand, one launch (and five memsets) whatever B is; no scratch, no host synchronisation, no float atomics;
+ *   nothing is read or written out of bounds; a ligand's results are bitwise independent of the rest of the batch and of the repeat.
+ *   Two well-formed lig_ptr segments that share atoms (or bond_ptr ranges that share rows) are both processed, each workgroup
+ *   writing the rows it sees: the per-atom and per-bond outputs of the shared rows are then UNSPECIFIED (whichever stores last);
+ *   the per-ligand outputs (desc_i, desc_f, valid, status) are not affected.  kpd_mol_perceive never produces such input. */
+kpd_status kpd_mol_sanitize(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, const int32_t *elem, int32_t F,
+                            const int32_t *z, const int32_t *allowed, const double *mass, double mass_h, const int32_t *frag,
+                            const int32_t *bond_ij, const int32_t *bond_order, const int32_t *bond_ptr, int32_t cap_bonds,
+                            const int32_t *mol_status, int32_t largest_only, int32_t *order_k, int32_t *bond_flags,
+                            int32_t *valence_k, int32_t *atom_h, int32_t *atom_flags, int32_t *desc_i, double *desc_f,
+                            int32_t *valid, int32_t *status, void *stream);
 
 /* Relaxation of sampled ligands inside their rigid pockets (csrc/relax.hip).  Stands where upstream runs
  * analysis/pocket_minimization.py: RDKit's UFF on ligand + receptor with every receptor atom fixed, maxIts = 400, then the plain
@@ -911,7 +985,7 @@ kpd_status kpd_relax(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, 
  *     anything else:               0
  *   An atom with Z = 1, or whose radius is not > 0, takes no part in any term; its reported type is -1.
  *   Limits: an aromatic or imine N of degree 2 counts as a donor (no aromaticity, no hydrogens), so a histidine's two ring N
- *   are both donors; the O rule leans on the length classes (C=O 1.23 A is a double, C-O 1.36 .. 1.43 A a single).  The caller
+ *   are both donors (for the ligand, flags recomputed from the hydrogen counts of kpd_mol_sanitize can be passed as lig_type_in); the O rule leans on the length classes (C=O 1.23 A is a double, C-O 1.36 .. 1.43 A a single).  The caller
  *   may override any atom's flags (lig_type_in, and whatever it writes into pocket_type; bits above 4 are ignored).
  * Rotors: N_rot = the number of ligand bonds of order 1 with both ends of heavy degree >= 2 that are in no ring (a bond is in a
  *   ring iff its ends stay connected when it is removed).  Limits: an amide C-N counts; rotors that would move only hydrogens

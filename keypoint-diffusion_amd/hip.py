@@ -208,6 +208,8 @@ def lib():
     L.kpd_mol_keys.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p] +
                                [C.c_int32] * 4 + [C.c_void_p] * 5)
     L.kpd_fp_diversity.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
+    L.kpd_mol_sanitize.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_double] +
+                                   [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 10)
     L.kpd_relax_defaults.argtypes = [C.POINTER(KpdRelaxParams)]
     L.kpd_relax_defaults.restype = None
     L.kpd_relax.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
@@ -259,7 +261,7 @@ EXPORTS = [
     'kpd_dist_hinge',
     'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
     'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
-    'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_relax_defaults', 'kpd_relax',
+    'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_mol_sanitize', 'kpd_relax_defaults', 'kpd_relax',
     'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score', 'kpd_vina_min_defaults', 'kpd_vina_minimize',
     'kpd_vina_dock_defaults', 'kpd_vina_dock',
 ]
@@ -1122,6 +1124,39 @@ def mol_keys(lig_ptr: torch.Tensor, z, mol: dict, largest_only: bool = True, wit
     check(lib().kpd_mol_keys(_ptr(lig_ptr), N, B, _ptr(mol['elem']), F, _ptr(zt), _ptr(mol['frag']), _ptr(mol['bonds']), _ptr(mol['order']),
                              _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']), int(bool(largest_only)), int(bool(with_orders)), radius,
                              nbits, _ptr(out['key']), _ptr(out['fp']), _ptr(out.get('atom_inv')), _ptr(out['status']), _stream()))
+    return out
+
+SAN_NO_MOLECULE, SAN_TOO_MANY_RINGS, SAN_COMPONENT_TOO_LARGE = 1, 2, 4      # status bits of kpd_mol_sanitize
+SAN_BOND_RING, SAN_BOND_PLANAR, SAN_BOND_AROMATIC = 1, 2, 4                # bond_flags
+SAN_ATOM_RING, SAN_ATOM_AROMATIC, SAN_ATOM_DONOR, SAN_ATOM_ACCEPTOR, SAN_ATOM_UNSATISFIED, SAN_ATOM_OVERVALENT = 1, 2, 4, 8, 16, 32
+SAN_DESC_I = ('n_heavy', 'n_h', 'hbd', 'hba', 'n_rot', 'n_rings', 'n_arom_rings', 'n_arom_atoms', 'lipinski4', 'n_cycles')
+
+
+def mol_sanitize(pos: torch.Tensor, lig_ptr: torch.Tensor, z, allowed, mass, mass_h: float, mol: dict, largest_only: bool = False):
+    """Ring perception, Kekule orders, aromaticity, implicit hydrogens, validity and descriptors of a batch of perceived
+    molecules on the GPU (kpd_mol_sanitize; include/kpd.h states the rule).  `mol`: what `mol_perceive` returned; z / allowed /
+    mass: the atomic number, the largest allowed valence and the mass of every feature class, mass_h: the mass of hydrogen.
+    Returns a dict of device tensors: order_k / bond_flags [cap_bonds], valence_k / atom_h / atom_flags [N], desc_i [B,10]
+    (columns SAN_DESC_I), desc_f [B,2] float64 (mw, reserved), valid [B], status [B].  No host synchronisation."""
+    pos = _dev_f32(pos, 'pos')
+    B = _offsets(lig_ptr, 'lig_ptr')
+    _mol_fields('mol_sanitize', mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'))
+    N, F, cap_bonds = pos.shape[0], len(z), mol['order'].numel()
+    if (pos.shape != (N, 3) or F < 1 or len(allowed) != F or len(mass) != F or mol['elem'].numel() != N or mol['frag'].numel() != N or
+            mol['bonds'].numel() != 2 * cap_bonds or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B):
+        raise KpdError(f'mol_sanitize: pos {tuple(pos.shape)}, {B} ligands, {F} atomic numbers, {len(allowed)} valences, {len(mass)} masses '
+                       f'do not match the perceived molecules')
+    dev = pos.device
+    table = torch.tensor([list(map(int, z)), list(map(int, allowed))], dtype=torch.int32, device=dev)
+    mt = torch.tensor(list(map(float, mass)), dtype=torch.float64, device=dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = dict(order_k=i32(cap_bonds), bond_flags=i32(cap_bonds), valence_k=i32(N), atom_h=i32(N), atom_flags=i32(N), desc_i=i32(B, 10),
+               desc_f=torch.empty(B, 2, dtype=torch.float64, device=dev), valid=i32(B), status=i32(B))
+    check(lib().kpd_mol_sanitize(_ptr(pos), _ptr(lig_ptr), N, B, _ptr(mol['elem']), F, _ptr(table[0]), _ptr(table[1]), _ptr(mt), float(mass_h),
+                                 _ptr(mol['frag']), _ptr(mol['bonds']), _ptr(mol['order']), _ptr(mol['bond_ptr']), cap_bonds,
+                                 _ptr(mol['status']), int(bool(largest_only)),
+                                 *[_ptr(out[k]) for k in ('order_k', 'bond_flags', 'valence_k', 'atom_h', 'atom_flags', 'desc_i', 'desc_f',
+                                                          'valid', 'status')], _stream()))
     return out
 
 

@@ -15,9 +15,11 @@ inherits the length-class bond orders.
 
 openbabel's perception rules are not restated: include/kpd.h defines the rule used here, the lookup-table builder of the
 EDM / DiffSBDD lineage (covalent radii for connectivity, length classes for the bond orders, valence caps).  The bond orders
-are length classes, not a Kekule structure; connectivity, fragments and `metrics` do not depend on them.  What needs
-sanitisation or a docking program (`validity`, QED / SA, docking and gnina's `--minimize`) stays with the caller, who can read the
-SDF blocks with rdkit.  The scoring half of docking is here: `Molecules.vina_score` / `score_samples` evaluate the AutoDock Vina
+are length classes, not a Kekule structure; connectivity, fragments and `metrics` do not depend on them.  `Molecules.sanitize`
+(`kpd_mol_sanitize`, csrc/sanitize.hip) adds what upstream gets from Chem.SanitizeMol and MoleculeProperties: ring and aromaticity
+perception, Kekule bond orders, implicit hydrogen counts, `validity` and molecular weight / donors / acceptors / rotatable bonds /
+Lipinski count, by a rule include/kpd.h defines (NOT RDKit's, and not compared with it).  QED, SA and logP need RDKit's parameter
+files and stay with the caller, who can read the SDF blocks with rdkit.  The scoring half of docking is here: `Molecules.vina_score` / `score_samples` evaluate the AutoDock Vina
 FUNCTIONAL FORM (five pair terms over ligand x pocket heavy atoms, divided by 1 + w_rot N_rot) with its analytic gradient for the
 whole batch in one launch (`kpd_vina_score`, csrc/vina.hip).  The typing is a rule of this library's own, defined in
 include/kpd.h (no hydrogens, no aromaticity), and the weights and radii are recalled constants: the scores rank samples scored
@@ -104,6 +106,30 @@ def xs_radius_table(elements: Sequence[str], radii: Optional[Dict[str, float]] =
     return out
 
 
+# monoisotopic masses for `Molecules.sanitize`, element -> u, to stand where upstream calls Descriptors.ExactMolWt.  RECALLED, NOT
+# CHECKED AGAINST A TABLE OF NUCLIDES: nothing may rely on the last digits; pass `masses=` to override.
+MONOISOTOPIC_MASS: Dict[str, float] = {
+    'H': 1.00782503223, 'B': 11.00930536, 'C': 12.0, 'N': 14.00307400443, 'O': 15.99491461957, 'F': 18.99840316273,
+    'Si': 27.97692653465, 'P': 30.97376199842, 'S': 31.9720711744, 'Cl': 34.968852682, 'As': 74.92159457, 'Se': 79.9165218,
+    'Br': 78.9183376, 'I': 126.9044719,
+}
+
+
+def mass_table(elements: Sequence[str], masses: Optional[Dict[str, float]] = None):
+    """(the mass of every element symbol, the mass of hydrogen), from `masses` first and MONOISOTOPIC_MASS second; an element in
+    neither raises."""
+    out = []
+    for el in list(elements) + ['H']:
+        m = (masses or {}).get(el, MONOISOTOPIC_MASS.get(el))
+        if m is None:
+            raise hip.KpdError(f'sanitize: no mass for element {el!r}; pass masses={{{el!r}: m}}')
+        m = float(m)
+        if not 0 <= m < 1e6:
+            raise hip.KpdError(f'sanitize: the mass of {el!r} must be finite and >= 0 (got {m!r})')
+        out.append(m)
+    return out[:-1], out[-1]
+
+
 def _pocket_of(pocket_of, B: int, n_pockets: int, dev) -> torch.Tensor:
     """The pocket of every ligand as an int32 tensor on `dev`: all zeros when one pocket is given and `pocket_of` is None."""
     if pocket_of is None:
@@ -133,6 +159,8 @@ class Molecules:
         self.elem, self.valence, self.frag, self.bonds, self.order, self.bond_ptr = elem, valence, frag, bonds, order, bond_ptr
         self.pos, self.lig_elements = pos, None if lig_elements is None else list(lig_elements)
         self._sizes = None if sizes is None else list(sizes)           # host-known atoms per ligand, if the builder knew them
+        self.valid: Optional[torch.Tensor] = None                      # [B] bool, on the molecules `sanitize` returns
+        self._allowed: Optional[List[int]] = None                      # the validity table the builder used, if it knew one
         self._max_atoms = max_atoms if max_atoms is not None or not self._sizes else max(self._sizes)
 
     def __len__(self) -> int:
@@ -159,7 +187,8 @@ class Molecules:
         atom_validity = 1 - invalid atoms / atoms (`check_atom_valency`), avg_frag_frac = mean of largest fragment atoms / atoms
         (`compute_avg_frag_size`), connectivity = share of ligands with that ratio >= `connectivity_thresh`, and, when the
         training set's `type_counts` [F] are given, atom_type_kldiv (`LigandTypeDistribution.kl_divergence`, its EPS included,
-        in float64).  Upstream computes `connectivity` over the molecules rdkit could sanitise; here it is over all ligands.
+        in float64).  Upstream computes `connectivity` over the molecules rdkit could sanitise; here it is over all ligands
+        (`sanitize().metrics()` gives upstream's order of operations, `validity` first).
         Ligands that are empty or were left out do not count, as upstream skips a molecule it could not build; with no ligand
         left every number is upstream's 0.0."""
         n = (self.lig_ptr[1:] - self.lig_ptr[:-1]).double()
@@ -209,7 +238,7 @@ class Molecules:
 
     def set_metrics(self, group_ptr: Optional[torch.Tensor] = None, train_keys: Optional[torch.Tensor] = None,
                     connectivity_thresh: float = 0.5, radius: int = 2, nbits: int = 2048, largest_frag: bool = True,
-                    with_orders: bool = True) -> Dict[str, object]:
+                    with_orders: bool = True, valid_only: bool = False) -> Dict[str, object]:
         """Upstream's numbers about the set of samples, from keys and fingerprints instead of SMILES and RDKit fingerprints:
         uniqueness = distinct keys / connected ligands (`compute_uniqueness`, analysis/metrics.py:135-140; "connected": has a
         molecule and largest fragment atoms / atoms >= `connectivity_thresh`, `compute_connectivity` without the sanitisation
@@ -218,9 +247,14 @@ class Molecules:
         offsets: consecutive ligands of a pocket form a group) diversity_per_group [G] (float64 device tensor: the mean
         Tanimoto distance over the pairs of a group's ligands that have a molecule, 0.0 for fewer than two,
         `MoleculeProperties.calculate_diversity`), diversity (its mean) and diversity_std (`np.std`, as upstream prints).
-        An empty set gives upstream's 0.0."""
+        An empty set gives upstream's 0.0.  `valid_only` (only on the `Sanitized.molecules` of `sanitize`): every number is
+        taken over the ligands that sanitised, which is upstream's order of operations."""
         r = self._keys(largest_frag, with_orders, radius, nbits)
         has = (r['status'] & hip.KEY_NO_MOLECULE) == 0
+        if valid_only:
+            if self.valid is None:
+                raise hip.KpdError('set_metrics(valid_only=True) needs the molecules of Molecules.sanitize()')
+            has = has & self.valid
         n = (self.lig_ptr[1:] - self.lig_ptr[:-1]).double()
         connected = has & (self.summary[:, 2].double() / n >= connectivity_thresh)
         keys = r['key'][connected]
@@ -242,6 +276,33 @@ class Molecules:
             out['diversity'] = float(per_group.mean()) if per_group.numel() else 0.0
             out['diversity_std'] = float(per_group.std(unbiased=False)) if per_group.numel() else 0.0
         return out
+
+    def sanitize(self, largest_frag: bool = False, masses: Optional[Dict[str, float]] = None,
+                 allowed_bonds: Optional[Dict[str, object]] = None) -> 'Sanitized':
+        """Sanitise every ligand on the GPU in one launch (`kpd_mol_sanitize`): ring bonds, planar rings, Kekule bond orders,
+        aromatic rings, implicit hydrogen counts, donor / acceptor flags, `valid` and the per-molecule descriptors, by the rule
+        include/kpd.h defines.  Stands where upstream calls Chem.SanitizeMol and MoleculeProperties; NOT RDKit's rule and not
+        compared with it.  `largest_frag`: over the largest fragment only; `masses`: element -> mass, consulted before
+        MONOISOTOPIC_MASS ('H' for the hydrogens); `allowed_bonds` (an intended extension of the plain signature): the over-valence
+        table, in the form `build_molecules` takes; by default the very table these molecules were built with, so that
+        `atom_validity` and `valid` judge by one table."""
+        if self.pos is None or self.lig_elements is None or self.bonds is None:
+            raise hip.KpdError('these Molecules carry no coordinates: build them with build_molecules')
+        if not self.pos.is_cuda:
+            raise hip.KpdError(f'sanitize: ligands must live on the GPU (got {self.pos.device}); sanitisation has no CPU implementation')
+        z, allowed = _class_tables(self.lig_elements, allowed_bonds)
+        if allowed_bonds is None and self._allowed is not None:
+            allowed = self._allowed
+        mass, mass_h = mass_table(self.lig_elements, masses)
+        dev = self.pos.device
+        if len(self) == 0:
+            i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+            out = dict(order_k=i32(0), bond_flags=i32(0), valence_k=i32(0), atom_h=i32(0), atom_flags=i32(0), desc_i=i32(0, 10),
+                       desc_f=torch.zeros(0, 2, dtype=torch.float64, device=dev), valid=i32(0), status=i32(0))
+        else:
+            mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
+            out = hip.mol_sanitize(self.pos, self.lig_ptr, z, allowed, mass, mass_h, mol, largest_only=largest_frag)
+        return Sanitized(self, out, z, largest_frag)
 
     def _in_pockets(self, where: str, what: str, pocket_pos, pocket_elements, pocket_of):
         """What `relax` and `vina_score` share: the guards, then the pockets as one device batch.  Returns pocket_x [M,3],
@@ -416,6 +477,80 @@ class Molecules:
         return VinaDocked(self, out, pocket_types, (lo, hi))
 
 
+class Sanitized:
+    """What `Molecules.sanitize` returns: `.molecules` (a `Molecules` whose `order` is order_k and whose `valence` is valence_k, so
+    `.sdf()`, `.keys()`, `.relax()`, `.vina_score()`, `.vina_minimize()` and `.vina_dock()` work unchanged on the Kekule orders),
+    `.h` [N] (implicit hydrogens), `.aromatic_atoms` [N] and `.aromatic_bonds` [3N] (bool), `.atom_flags` [N] and `.bond_flags`
+    [3N] (bits hip.SAN_ATOM_* / hip.SAN_BOND_*), `.valid` [B] (bool), `.status` [B] (bits: 1 no molecule, 2 more than 64 five-
+    or six-cycles, 4 a candidate component of more than 24 atoms), device tensors.  The rule is include/kpd.h's, NOT RDKit's."""
+
+    def __init__(self, mols: Molecules, out: Dict[str, torch.Tensor], z: Sequence[int], largest_frag: bool):
+        self.molecules = Molecules(mols.lig_ptr, mols.summary, mols.status, mols.elem, out['valence_k'], mols.frag, mols.bonds,
+                                   out['order_k'], mols.bond_ptr, mols.pos, mols.lig_elements, mols._max_atoms, sizes=mols._sizes)
+        self.valid = out['valid'] != 0
+        self.molecules.valid, self.molecules._allowed = self.valid, mols._allowed
+        self.h, self.atom_flags, self.bond_flags, self.status = out['atom_h'], out['atom_flags'], out['bond_flags'], out['status']
+        self.aromatic_atoms = (out['atom_flags'] & hip.SAN_ATOM_AROMATIC) != 0
+        self.aromatic_bonds = (out['bond_flags'] & hip.SAN_BOND_AROMATIC) != 0
+        self.largest_frag, self._desc_i, self._desc_f, self._z = bool(largest_frag), out['desc_i'], out['desc_f'], list(z)
+
+    def descriptors(self) -> Dict[str, torch.Tensor]:
+        """Per ligand, as [B] device tensors: n_heavy, n_h, hbd, hba, n_rot, n_rings, n_arom_rings, n_arom_atoms, lipinski4 (how
+        many of mw < 500, hbd <= 5, hba <= 10, n_rot <= 10 hold: upstream's logP rule is not counted), n_cycles (int32) and mw
+        (float64).  Zeros for a ligand without a molecule."""
+        out = {name: self._desc_i[:, k] for k, name in enumerate(hip.SAN_DESC_I)}
+        out['mw'] = self._desc_f[:, 0]
+        return out
+
+    def table(self) -> Dict[str, list]:
+        """lig_idx, valid and the descriptors as lists; ligands without a molecule (status bit 0) have no row."""
+        st = self.status.cpu()
+        keep = ((st & hip.SAN_NO_MOLECULE) == 0).nonzero().flatten().tolist()
+        out: Dict[str, list] = dict(lig_idx=keep, valid=self.valid.cpu()[keep].tolist())
+        for name, col in self.descriptors().items():
+            out[name] = col.cpu()[keep].tolist()
+        return out
+
+    def vina_types(self) -> torch.Tensor:
+        """[N] int32 for `lig_types=` of `vina_score` / `vina_minimize` / `vina_dock`: the flags of kpd_vina_score recomputed
+        from the hydrogen counts.  N: donor (2) iff h >= 1, else acceptor (4) under the acceptor rule of include/kpd.h, else 0;
+        O: acceptor, and donor iff h >= 1; -1 (keep the rule of kpd_vina_score) for every other element and outside the scope."""
+        m = self.molecules
+        zt = torch.tensor(self._z, dtype=torch.int32, device=m.elem.device)
+        za = torch.where(m.elem >= 0, zt[m.elem.clamp(min=0).long()], torch.zeros_like(m.elem))
+        donor = (self.h >= 1).to(torch.int32) * 2
+        acc = ((self.atom_flags & hip.SAN_ATOM_ACCEPTOR) != 0).to(torch.int32) * 4
+        t = torch.full_like(m.elem, -1)
+        t = torch.where(za == 7, torch.where(donor > 0, donor, acc), t)
+        t = torch.where(za == 8, donor | 4, t)
+        return torch.where(m.valence >= 0, t, torch.full_like(t, -1))
+
+    def metrics(self, type_counts: Optional[torch.Tensor] = None, connectivity_thresh: float = 0.5,
+                group_ptr: Optional[torch.Tensor] = None, train_keys: Optional[torch.Tensor] = None) -> Dict[str, object]:
+        """Upstream's order of operations (ModelAnalyzer.sample_and_analyze): validity = ligands that sanitised / ligands that
+        were built (as in `Molecules.metrics`, empty and left-out ligands do not count); connectivity over the valid ligands;
+        uniqueness, novelty and diversity (`set_metrics(valid_only=True)`) over the valid, connected ones; atom_validity,
+        avg_frag_frac and atom_type_kldiv as `Molecules.metrics` gives them; and the mean and standard deviation (np.std) of
+        mw, hbd, hba, n_rot and lipinski4 over the valid ligands.  `group_ptr` and `train_keys` are those of `set_metrics` (the
+        pockets' groups for diversity, the training keys for novelty), passed through so that one call gives upstream's seven."""
+        m = self.molecules
+        out: Dict[str, object] = m.metrics(type_counts, connectivity_thresh)
+        n = (m.lig_ptr[1:] - m.lig_ptr[:-1]).double()
+        built = (n > 0) & ((m.status & hip.MOL_BAD_SEGMENT) == 0)
+        valid = self.valid & built
+        n_built, n_valid = int(built.sum()), int(valid.sum())
+        out['validity'] = n_valid / n_built if n_built else 0.0
+        frac = m.summary[:, 2].double() / n.clamp(min=1)
+        out['connectivity'] = float((frac[valid] >= connectivity_thresh).double().mean()) if n_valid else 0.0
+        out.update(m.set_metrics(group_ptr, train_keys, connectivity_thresh, largest_frag=True, valid_only=True))
+        desc = self.descriptors()
+        for name in ('mw', 'hbd', 'hba', 'n_rot', 'lipinski4'):
+            col = desc[name][valid].double()
+            out[name + '_mean'] = float(col.mean()) if n_valid else 0.0
+            out[name + '_std'] = float(col.std(unbiased=False)) if n_valid else 0.0
+        return out
+
+
 class VinaDocked:
     """What `Molecules.vina_dock` returns: `.molecules` (a `Molecules` with the same bond graph at mode 0, the best pose found),
     `.mode(k)` (the same at mode k; a ligand with fewer modes keeps its input pose there), `.n_found` [B], `.report`
@@ -588,8 +723,10 @@ def build_molecules(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], l
     if feat.dim() != 2 or feat.shape[1] != len(lig_elements):
         raise hip.KpdError(f'features {tuple(feat.shape)} do not match the {len(lig_elements)} element symbols')
     m = hip.mol_perceive(pos, feat, ptr, z, allowed)
-    return Molecules(ptr, m['summary'], m['status'], m['elem'], m['valence'], m['frag'], m['bonds'], m['order'], m['bond_ptr'],
+    mols = Molecules(ptr, m['summary'], m['status'], m['elem'], m['valence'], m['frag'], m['bonds'], m['order'], m['bond_ptr'],
                      hip._dev_f32(pos, 'pos'), lig_elements, sizes=sizes)
+    mols._allowed = allowed
+    return mols
 
 
 def training_keys(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig_elements: Sequence[str], largest_frag: bool = True,
@@ -605,13 +742,17 @@ def training_keys(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig
 
 def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_counts: Optional[torch.Tensor] = None,
                     allowed_bonds: Optional[Dict[str, object]] = None, connectivity_thresh: float = 0.5, device=None,
-                    train_keys: Optional[torch.Tensor] = None, set_metrics: bool = False) -> Dict[str, float]:
+                    train_keys: Optional[torch.Tensor] = None, set_metrics: bool = False, sanitize: bool = False,
+                    masses: Optional[Dict[str, float]] = None) -> Dict[str, float]:
     """The part of `ModelAnalyzer.sample_and_analyze` (analysis/metrics.py:60-100) that needs no rdkit: `samples` is the list
     of {'positions', 'features'} dicts `_sample` returns, one per pocket; the result is `Molecules.metrics` over all of them
     and, with `set_metrics=True`, `Molecules.set_metrics` as well (uniqueness, novelty against `train_keys` if given, and the
     diversity of every pocket's ligands).
     `_sample` hands its ligands back on the host: name the GPU to work on as `device` and they are copied there (one copy of
-    the concatenated batch would do as well: `build_molecules` takes GPU tensors only and never computes on the host)."""
+    the concatenated batch would do as well: `build_molecules` takes GPU tensors only and never computes on the host).
+    `sanitize=True`: the numbers of `Sanitized.metrics` instead, upstream's seven in upstream's order of operations (`validity`
+    first; connectivity, uniqueness, novelty and diversity over the ligands that sanitised) and the descriptor statistics; the
+    rule is include/kpd.h's (`Molecules.sanitize`), NOT RDKit's.  With the default every key and value is what it was."""
     lig_pos, lig_feat = [], []
     for rec in samples:
         lig_pos.extend(rec['positions'])
@@ -619,6 +760,9 @@ def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_count
     if device is not None:
         lig_pos, lig_feat = [p.to(device) for p in lig_pos], [f.to(device) for f in lig_feat]
     mols = build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds)
+    if sanitize:
+        group_ptr = torch.tensor([0] + [len(rec['positions']) for rec in samples], dtype=torch.int64).cumsum(0).to(torch.int32)
+        return mols.sanitize(masses=masses).metrics(type_counts, connectivity_thresh, group_ptr, train_keys)
     out = mols.metrics(type_counts, connectivity_thresh)
     if set_metrics:
         group_ptr = torch.tensor([0] + [len(rec['positions']) for rec in samples], dtype=torch.int64).cumsum(0).to(torch.int32)
