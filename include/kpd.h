@@ -703,7 +703,7 @@ kpd_status kpd_interface_points(const float *rec_x, const int32_t *rec_ptr, cons
  * what upstream compares SMILES for (uniqueness, novelty) is kpd_mol_keys below, and the relaxation of the samples inside their
  * pockets (by a force field of this library's own, not UFF) is kpd_relax at the end of this file.
  *
- * Ligands carry heavy atoms only; no hydrogens are added here (kpd_mol_sanitize counts them per atom, without positions).
+ * Ligands carry heavy atoms only; no hydrogens are added here (kpd_mol_sanitize counts them per atom, kpd_mol_add_hs places them).
  * Everything below is per ligand (at most 256 atoms).
  * Element table, by atomic number (radii after Pyykko & Atsumi 2009 in integer picometres, single / double / triple, 0 = no
  * bond of that order; cap = chemical valence cap):
@@ -850,7 +850,7 @@ kpd_status kpd_fp_diversity(const uint32_t *fp, const uint8_t *use, int32_t B, i
  *      planar ring bond, to N, O or S; anything else does not contribute.  Aromatic atoms and bonds are those of aromatic cycles.
  *   5. hydrogens: h = max(0, normal(Z, valence_k) - valence_k); normal = 4 for C and Si, 3 for N, B and As, 2 for O, 1 for H and
  *      the halogens, for S the smallest of 2, 4, 6 that is >= valence_k (6 beyond), for P of 3, 5 (5 beyond), 0 otherwise.
- *      No hydrogen positions are produced.
+ *      No hydrogen positions are produced here: kpd_mol_add_hs below turns the counts into atoms.
  *   6. flags: donor = N or O with h >= 1; acceptor = every O, and every N that is no donor, has deg <= 2 and is no lone-pair N;
  *      over-valent = valence_k > allowed[class] (the table of kpd_mol_perceive's step 6).
  *   7. valid iff there is a molecule, no atom of S is over-valent or unsatisfied and neither cap bit is set.  An isolated atom
@@ -886,6 +886,86 @@ kpd_status kpd_mol_sanitize(const float *pos, const int32_t *lig_ptr, int32_t n_
                             const int32_t *mol_status, int32_t largest_only, int32_t *order_k, int32_t *bond_flags,
                             int32_t *valence_k, int32_t *atom_h, int32_t *atom_flags, int32_t *desc_i, double *desc_f,
                             int32_t *valid, int32_t *status, void *stream);
+
+/* Explicit hydrogens on the sanitised molecules (csrc/hydrogens.hip): the hydrogen counts of kpd_mol_sanitize become atoms with
+ * coordinates and bonds.  Stands where upstream calls Chem.AddHs(lig, addCoords=True) before every force-field step
+ * (analysis/pocket_minimization.py, process_molecule(add_hydrogens=True)).  RDKit's coordinates cannot be restated here, so THIS
+ * COMMENT IS THE DEFINITION; the coordinates are not RDKit's and are not compared with them.  The inputs are what kpd_mol_perceive
+ * and kpd_mol_sanitize left on the device and are never written; the output is a second molecule batch in the layout of
+ * kpd_mol_perceive, which every call of this file takes unchanged (its bond orders are order_k).
+ * Scope S, Z(a) (0 for an atomic number outside 0 .. 255) and "both ends in S" are those of kpd_mol_sanitize.  An atom a of S gets
+ *   h = atom_h[a] hydrogens, an atom outside S none.  a's neighbours are its partners over bonds with both ends in S.
+ * Atom order of a ligand: its input atoms in input order, then the hydrogens grouped by parent in ascending order, by site
+ *   t = 0 .. h-1 within a parent (the append convention of AddHs).  Bond rows: the input rows are sorted by (i, j) with i < j, so
+ *   the H bonds of atom i sort right after its rows (i, .): the input row r (local) with first atom i moves to local row
+ *   r + (hydrogens of the atoms < i), and the H bond of site t of atom i is local row
+ *   (input rows whose first atom is <= i) + (hydrogens of the atoms < i) + t.
+ * Arithmetic: fp64 on the fp32 coordinates; every product, sum and difference is rounded once (no fused multiply-add), sqrt and
+ *   / are correctly rounded.  a.b = (ax bx + ay by) + az bz; a x b = (ay bz - az by, az bx - ax bz, ax by - ay bx); a vector over
+ *   a scalar, a sum or difference of vectors, and "x a + y b" = (x a_c) + (y b_c) are taken component by component; -a is exact.
+ *   Constants: T3 = 0.3333333333333333, T1 = 0.9428090415820634, S3 = 0.5773502691896258, T2 = 0.816496580927726,
+ *   H3 = 0.8660254037844386.
+ * Neighbours of a in ascending row order; for neighbour b: v = P_b - P_a, n2 = v.v.  n2 < 1e-12: b is ignored for directions
+ *   (status bit 3).  Else u = v / sqrt(n2).  The k remaining are u_1 .. u_k, b_1 the first of them.
+ * Bond length: L = (double)(r1(Z(a)) + 32) * 0.01 with r1 from the element table above (C-H 1.07, N-H 1.03, O-H 0.95, S-H 1.35 A:
+ *   the rest lengths kpd_relax picks for those bonds).
+ * Class of a, the first that holds (over all of a's neighbours, ignored ones too): LINEAR if a has a bond of order_k 3 or two or
+ *   more of order_k 2; PLANAR if a has a bond of order_k 2, or a is aromatic (atom_flags bit 1), or Z(a) = 7 and a neighbour is
+ *   aromatic or has a bond of order_k >= 2 (amide, aniline, enamine and pyrrole-type N); TET otherwise.
+ * perp(u): e = the coordinate axis with the smallest |u_c| (the first on a tie), q_c = e_c - (u_e u_c), perp = q / sqrt(q.q).
+ * azimuth (k = 1, u = u_1, b = b_1): c = the lowest-row neighbour of b other than a; w = P_c - P_b, q_c = w_c - ((w.u) u_c);
+ *   if c exists and q.q >= 1e-12: p0 = (-q) / sqrt(q.q) (the first hydrogen is anti to c), else p0 = perp(u).  t = u x p0,
+ *   p1 = -0.5 p0 + H3 t, p2 = -0.5 p0 + (-H3) t.
+ * Directions d_0 .. d_{h-1}:
+ *   TET, k = 0, h <= 4: the first h of (S3, S3, S3), (S3, -S3, -S3), (-S3, S3, -S3), (-S3, -S3, S3);
+ *   TET, k = 1, h <= 3: d_i = (-T3) u + T1 p_i;
+ *   TET, k = 2, h <= 2: s = u_1 + u_2, x = u_1 x u_2; if s.s >= 1e-12 and x.x >= 1e-12: w = (-s) / sqrt(s.s), n = x / sqrt(x.x),
+ *     d_0 = S3 w + T2 n, d_1 = S3 w + (-T2) n;
+ *   TET, k = 3, h = 1: s = (u_1 + u_2) + u_3, x = (u_2 - u_1) x (u_3 - u_1); if x.x >= 1e-12: n = x / sqrt(x.x), d = -n if
+ *     n.s > 0 else n (the normal, not the sum, keeps a flat three-neighbour centre from putting its H onto a neighbour);
+ *     else if s.s >= 1e-4: d = (-s) / sqrt(s.s);
+ *   PLANAR, k = 1, h <= 2: d_0 = -0.5 u + H3 p0 (trans to c), d_1 = -0.5 u + (-H3) p0;
+ *   PLANAR, k = 2, h = 1: s = u_1 + u_2; if s.s >= 1e-4: d = (-s) / sqrt(s.s);
+ *   LINEAR, k = 1, h = 1: d = -u;
+ *   the general rule, for every other (class, k, h) and whenever a condition above fails (status bit 3): s = ((0 + u_1) + u_2) ..
+ *     + u_k; for t = 0 .. h-1: if k + t > 0 and s.s >= 1e-4: d_t = (-s) / sqrt(s.s); else if k + t > 0: d_t = perp(the first of
+ *     u_1 .. u_k, d_0 ..); else d_t = (S3, S3, S3); then s = s + d_t.
+ * Position of a hydrogen: each component is (float)(P_a.c + L * d.c).
+ * Limits: no clash avoidance between hydrogens of different atoms; no orientation of hydroxyl or amine hydrogens towards a
+ *   pocket; no formal charges; no tautomer choice beyond atom_h; NOT RDKit's coordinates.
+ *
+ * kpd_mol_add_hs: pos [n_atoms,3], lig_ptr [B+1], elem / frag [n_atoms], bond_ij [cap_bonds_in,2], bond_ptr [B+1], mol_status [B] as
+ *   kpd_mol_perceive wrote them; order_k [cap_bonds_in], valence_k / atom_h / atom_flags [n_atoms] and san_status [B] (its `status`)
+ *   as kpd_mol_sanitize wrote them with the same largest_only; z / allowed [F]; h_class: the class the new atoms get,
+ *   z[h_class] must be 1 (else every ligand has status bit 0); all device pointers.  Out (device): out_ptr [B+1], out_pos
+ *   [cap_atoms,3], out_elem / out_valence / out_frag [cap_atoms], out_bond_ij [cap_bonds,2] (global output rows, i < j, per
+ *   ligand sorted by i, then j), out_order [cap_bonds], out_bond_ptr [B+1], out_summary [B,4] = {n_bonds, n_frags,
+ *   largest_frag_atoms (its hydrogens counted), n_invalid_atoms (step 6 of kpd_mol_perceive on out_valence and allowed, the
+ *   hydrogens included)}, parent [cap_atoms] (for an H the output row of its heavy atom, else the atom's own row), source
+ *   [cap_atoms] (-1 for an H, else the input row), n_h [B] (hydrogens added), status [B].  out_valence = valence_k + h for an
+ *   input atom, 1 for an H; out_order = order_k, 1 for an H bond; out_frag is the parent's.  out_ptr[B] and out_bond_ptr[B] are
+ *   the sizes needed, also when they exceed cap_atoms / cap_bonds (the convention of kpd_sdf_emit's text_ptr); a ligand that
+ *   does not fit either capacity is not written and gets status bit 2.  Rows nothing is written to read 0 (out_pos, out_order)
+ *   or -1.  The number and order of the ligands never change.  A ligand that gets no hydrogens is copied through (its rows,
+ *   its bonds with order_k, no H): bit 0 = no molecule (san_status bit 0, mol_status bits 0, 1 or 3, more than 256 atoms, a
+ *   malformed bond range (then no bonds are copied), an element or fragment out of range, atom_h outside 0 .. 4, an empty S, a
+ *   bond row that is not i < j inside the ligand with order_k 1 .. 3, rows not ascending in (i, j), a seventh neighbour;
+ *   out_summary is {n_bonds, 0, 0, 0}); bit 1 = more than 256 atoms after the addition; bit 4 = a non-finite coordinate.  A
+ *   malformed lig_ptr segment contributes no rows (bit 0).  Bit 3 is informational: some atom used the general rule or ignored a
+ *   coincident neighbour.  scratch: kpd_mol_add_hs_scratch_bytes(n_atoms, B) device bytes.  n_atoms + 256 B must stay below 2^31
+ *   and B at most 2^21 (KPD_ERR_CAPACITY).
+ *   One wave per ligand; a size pass, one exclusive scan (atoms and bonds packed into one 64-bit count) and a write pass: three
+ *   launches and no fills whatever B >= 1 is (the write pass blanks the rows no ligand fills; B = 0: fills only); no host synchronisation, no float atomics; nothing is read or written out of
+ *   bounds; a ligand's results are bitwise independent of the rest of the batch and of the repeat. */
+int64_t kpd_mol_add_hs_scratch_bytes(int32_t n_atoms, int32_t B);
+kpd_status kpd_mol_add_hs(const float *pos, const int32_t *lig_ptr, int32_t n_atoms, int32_t B, const int32_t *elem, int32_t F,
+                          const int32_t *z, const int32_t *allowed, const int32_t *frag, const int32_t *bond_ij,
+                          const int32_t *order_k, const int32_t *bond_ptr, int32_t cap_bonds_in, const int32_t *mol_status,
+                          const int32_t *san_status, const int32_t *valence_k, const int32_t *atom_h, const int32_t *atom_flags,
+                          int32_t largest_only, int32_t h_class, int32_t cap_atoms, int32_t cap_bonds, int32_t *out_ptr,
+                          float *out_pos, int32_t *out_elem, int32_t *out_valence, int32_t *out_frag, int32_t *out_bond_ij,
+                          int32_t *out_order, int32_t *out_bond_ptr, int32_t *out_summary, int32_t *parent, int32_t *source,
+                          int32_t *n_h, int32_t *status, void *scratch, void *stream);
 
 /* Relaxation of sampled ligands inside their rigid pockets (csrc/relax.hip).  Stands where upstream runs
  * analysis/pocket_minimization.py: RDKit's UFF on ligand + receptor with every receptor atom fixed, maxIts = 400, then the plain

@@ -210,6 +210,10 @@ def lib():
     L.kpd_fp_diversity.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
     L.kpd_mol_sanitize.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_double] +
                                    [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 10)
+    L.kpd_mol_add_hs_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.kpd_mol_add_hs_scratch_bytes.restype = C.c_int64
+    L.kpd_mol_add_hs.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] +
+                                 [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 15)
     L.kpd_relax_defaults.argtypes = [C.POINTER(KpdRelaxParams)]
     L.kpd_relax_defaults.restype = None
     L.kpd_relax.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
@@ -261,7 +265,7 @@ EXPORTS = [
     'kpd_dist_hinge',
     'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
     'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
-    'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_mol_sanitize', 'kpd_relax_defaults', 'kpd_relax',
+    'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_mol_sanitize', 'kpd_mol_add_hs_scratch_bytes', 'kpd_mol_add_hs', 'kpd_relax_defaults', 'kpd_relax',
     'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score', 'kpd_vina_min_defaults', 'kpd_vina_minimize',
     'kpd_vina_dock_defaults', 'kpd_vina_dock',
 ]
@@ -1157,6 +1161,47 @@ def mol_sanitize(pos: torch.Tensor, lig_ptr: torch.Tensor, z, allowed, mass, mas
                                  _ptr(mol['status']), int(bool(largest_only)),
                                  *[_ptr(out[k]) for k in ('order_k', 'bond_flags', 'valence_k', 'atom_h', 'atom_flags', 'desc_i', 'desc_f',
                                                           'valid', 'status')], _stream()))
+    return out
+
+
+HS_NO_MOLECULE, HS_TOO_MANY_ATOMS, HS_NO_ROOM, HS_GENERAL, HS_NONFINITE = 1, 2, 4, 8, 16       # status bits of kpd_mol_add_hs
+
+
+def mol_add_hs(pos: torch.Tensor, lig_ptr: torch.Tensor, z, allowed, h_class: int, mol: dict, san: dict, largest_only: bool = False):
+    """Explicit hydrogens with coordinates on a batch of sanitised molecules on the GPU (kpd_mol_add_hs; include/kpd.h states the
+    placement rule).  `mol`: what `mol_perceive` returned, `san`: what `mol_sanitize` returned for it with the same
+    `largest_only`; z / allowed: the atomic number and the largest allowed valence of every class, `h_class`: the class the new
+    atoms get (z[h_class] must be 1).  The outputs are sized from one device sum of atom_h, the only host synchronisation of this function.  Returns a dict of device tensors in the layout of `mol_perceive` -- lig_ptr [B+1],
+    pos [cap_atoms,3], elem / valence / frag [cap_atoms], bonds [cap_bonds,2], order [cap_bonds], bond_ptr [B+1], summary [B,4]
+    -- and parent / source [cap_atoms], n_h [B], status [B] (bits HS_*)."""
+    pos = _dev_f32(pos, 'pos')
+    B = _offsets(lig_ptr, 'lig_ptr')
+    _mol_fields('mol_add_hs', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'))
+    _mol_fields('mol_add_hs', san, ('order_k', 'valence_k', 'atom_h', 'atom_flags', 'status'))
+    N, F, cap_in = pos.shape[0], len(z), san['order_k'].numel()
+    if (pos.shape != (N, 3) or F < 1 or len(allowed) != F or mol['elem'].numel() != N or mol['frag'].numel() != N or
+            mol['bonds'].numel() != 2 * cap_in or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B or
+            san['status'].numel() != B or any(san[k].numel() != N for k in ('valence_k', 'atom_h', 'atom_flags'))):
+        raise KpdError(f'mol_add_hs: pos {tuple(pos.shape)}, {B} ligands, {F} atomic numbers, {len(allowed)} valences do not match the '
+                       f'perceived and sanitised molecules')
+    h_class = int(h_class)
+    if not (0 <= h_class < F and int(z[h_class]) == 1):
+        raise KpdError(f'mol_add_hs: h_class {h_class} must name a class of atomic number 1')
+    dev = pos.device
+    n_h = int(san['atom_h'].clamp(min=0).sum().item()) if N else 0          # an upper bound: ligands copied through add none
+    cap_atoms, cap_bonds = N + n_h, cap_in + n_h
+    table = torch.tensor([list(map(int, z)), list(map(int, allowed))], dtype=torch.int32, device=dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = dict(lig_ptr=i32(B + 1), pos=torch.empty(cap_atoms, 3, dtype=torch.float32, device=dev), elem=i32(cap_atoms),
+               valence=i32(cap_atoms), frag=i32(cap_atoms), bonds=i32(cap_bonds, 2), order=i32(cap_bonds), bond_ptr=i32(B + 1),
+               summary=i32(B, 4), parent=i32(cap_atoms), source=i32(cap_atoms), n_h=i32(B), status=i32(B))
+    scratch = torch.empty(int(lib().kpd_mol_add_hs_scratch_bytes(N, B)), dtype=torch.uint8, device=dev)
+    check(lib().kpd_mol_add_hs(_ptr(pos), _ptr(lig_ptr), N, B, _ptr(mol['elem']), F, _ptr(table[0]), _ptr(table[1]), _ptr(mol['frag']),
+                               _ptr(mol['bonds']), _ptr(san['order_k']), _ptr(mol['bond_ptr']), cap_in, _ptr(mol['status']),
+                               _ptr(san['status']), _ptr(san['valence_k']), _ptr(san['atom_h']), _ptr(san['atom_flags']),
+                               int(bool(largest_only)), h_class, cap_atoms, cap_bonds,
+                               *[_ptr(out[k]) for k in ('lig_ptr', 'pos', 'elem', 'valence', 'frag', 'bonds', 'order', 'bond_ptr', 'summary',
+                                                        'parent', 'source', 'n_h', 'status')], _ptr(scratch), _stream()))
     return out
 
 

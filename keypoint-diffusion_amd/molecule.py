@@ -19,7 +19,9 @@ are length classes, not a Kekule structure; connectivity, fragments and `metrics
 (`kpd_mol_sanitize`, csrc/sanitize.hip) adds what upstream gets from Chem.SanitizeMol and MoleculeProperties: ring and aromaticity
 perception, Kekule bond orders, implicit hydrogen counts, `validity` and molecular weight / donors / acceptors / rotatable bonds /
 Lipinski count, by a rule include/kpd.h defines (NOT RDKit's, and not compared with it).  QED, SA and logP need RDKit's parameter
-files and stay with the caller, who can read the SDF blocks with rdkit.  The scoring half of docking is here: `Molecules.vina_score` / `score_samples` evaluate the AutoDock Vina
+files and stay with the caller, who can read the SDF blocks with rdkit.  `Sanitized.add_hs` (`kpd_mol_add_hs`, csrc/hydrogens.hip)
+turns the hydrogen counts into atoms with coordinates and bonds, where upstream calls Chem.AddHs(lig, addCoords=True): ideal sites by a
+rule include/kpd.h defines, NOT RDKit's coordinates; the result is a `Molecules` every call below takes unchanged.  The scoring half of docking is here: `Molecules.vina_score` / `score_samples` evaluate the AutoDock Vina
 FUNCTIONAL FORM (five pair terms over ligand x pocket heavy atoms, divided by 1 + w_rot N_rot) with its analytic gradient for the
 whole batch in one launch (`kpd_vina_score`, csrc/vina.hip).  The typing is a rule of this library's own, defined in
 include/kpd.h (no hydrogens, no aromaticity), and the weights and radii are recalled constants: the scores rank samples scored
@@ -30,7 +32,8 @@ here against each other and ARE NOT gnina's or Vina's numbers.  That call scores
 Where upstream minimises every sample inside its pocket with RDKit's UFF (analysis/pocket_minimization.py), `Molecules.relax` /
 `relax_samples` relax the whole batch in one kernel launch (`kpd_relax`, csrc/relax.hip) with a force field of this library's
 own, defined in include/kpd.h: harmonic bonds and angles around the ideal values nearest to the sampled geometry, soft-core
-Lennard-Jones inside the ligand and against the pocket, L-BFGS.  It is NOT UFF: heavy atoms only, no torsions or inversions,
+Lennard-Jones inside the ligand and against the pocket, L-BFGS.  It is NOT UFF: heavy atoms only (unless the molecules of
+`Sanitized.add_hs` are passed, `relax_samples(add_hs=True)`), no torsions or inversions,
 no electrostatics, a rigid pocket.  Its energies rank samples relaxed here against each other; they are not comparable with
 RDKit's, and whoever needs UFF itself still runs RDKit on the SDF blocks.
 
@@ -88,12 +91,16 @@ def vdw_table(elements: Sequence[str], vdw: Optional[Dict[str, tuple]] = None) -
 XS_RADII: Dict[str, float] = {
     'C': 1.9, 'N': 1.8, 'O': 1.7, 'F': 1.5, 'Si': 2.2, 'P': 2.1, 'S': 2.0, 'Cl': 1.8, 'Br': 2.0, 'I': 2.2,
     'Mg': 1.2, 'Ca': 1.2, 'Mn': 1.2, 'Fe': 1.2, 'Co': 1.2, 'Ni': 1.2, 'Cu': 1.2, 'Zn': 1.2,
+    'H': 1.0,       # never enters the score: see xs_radius_table
 }
 
 
 def xs_radius_table(elements: Sequence[str], radii: Optional[Dict[str, float]] = None) -> List[float]:
     """The radius of every element symbol, from `radii` first and XS_RADII second; an element in neither raises.  A radius of 0
-    is allowed: such an atom takes no part in the score (kpd_vina_score reports it with type -1 and status bit 2)."""
+    is allowed: such an atom takes no part in the score (kpd_vina_score reports it with type -1 and status bit 2).
+    'H' has an entry so that the class list of hydrogenated molecules (`Sanitized.add_hs`) passes; it holds for ligand and pocket
+    class lists alike (a list naming 'H' used to raise here), and its value never enters a score: kpd_vina_score and
+    kpd_vina_pocket_types give every hydrogen type -1 whatever its radius."""
     out = []
     for el in elements:
         r = (radii or {}).get(el, XS_RADII.get(el))
@@ -161,6 +168,7 @@ class Molecules:
         self._sizes = None if sizes is None else list(sizes)           # host-known atoms per ligand, if the builder knew them
         self.valid: Optional[torch.Tensor] = None                      # [B] bool, on the molecules `sanitize` returns
         self._allowed: Optional[List[int]] = None                      # the validity table the builder used, if it knew one
+        self._allowed_h: Optional[int] = None                          # the entry for 'H' of the caller's table, if it has one
         self._max_atoms = max_atoms if max_atoms is not None or not self._sizes else max(self._sizes)
 
     def __len__(self) -> int:
@@ -302,7 +310,10 @@ class Molecules:
         else:
             mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
             out = hip.mol_sanitize(self.pos, self.lig_ptr, z, allowed, mass, mass_h, mol, largest_only=largest_frag)
-        return Sanitized(self, out, z, largest_frag)
+        san = Sanitized(self, out, z, largest_frag)
+        if allowed_bonds is not None and 'H' in allowed_bonds:
+            san.molecules._allowed_h = _class_tables(['H'], allowed_bonds)[1][0]
+        return san
 
     def _in_pockets(self, where: str, what: str, pocket_pos, pocket_elements, pocket_of):
         """What `relax` and `vina_score` share: the guards, then the pockets as one device batch.  Returns pocket_x [M,3],
@@ -488,11 +499,21 @@ class Sanitized:
         self.molecules = Molecules(mols.lig_ptr, mols.summary, mols.status, mols.elem, out['valence_k'], mols.frag, mols.bonds,
                                    out['order_k'], mols.bond_ptr, mols.pos, mols.lig_elements, mols._max_atoms, sizes=mols._sizes)
         self.valid = out['valid'] != 0
-        self.molecules.valid, self.molecules._allowed = self.valid, mols._allowed
+        self.molecules.valid, self.molecules._allowed, self.molecules._allowed_h = self.valid, mols._allowed, mols._allowed_h
         self.h, self.atom_flags, self.bond_flags, self.status = out['atom_h'], out['atom_flags'], out['bond_flags'], out['status']
         self.aromatic_atoms = (out['atom_flags'] & hip.SAN_ATOM_AROMATIC) != 0
         self.aromatic_bonds = (out['bond_flags'] & hip.SAN_BOND_AROMATIC) != 0
         self.largest_frag, self._desc_i, self._desc_f, self._z = bool(largest_frag), out['desc_i'], out['desc_f'], list(z)
+        self._out = out
+
+    def add_hs(self) -> 'Hydrogenated':
+        """Explicit hydrogens with coordinates for every ligand, on the GPU (`kpd_mol_add_hs`): what upstream gets from
+        Chem.AddHs(lig, addCoords=True).  The counts are `.h`; the placement rule (ideal tetrahedral / trigonal / linear sites at
+        the X-H rest lengths of `relax`, the first hydrogen of a chain end anti to the chain) is include/kpd.h's, NOT RDKit's.
+        The hydrogens take the class 'H' of `lig_elements`, appended if it is absent (its validity entry is the caller's
+        `allowed_bonds['H']` if there is one).  Two host synchronisations: the sum of the counts that sizes the outputs, and the
+        copy of the B + 1 offsets that gives the new atoms per ligand."""
+        return Hydrogenated(self)
 
     def descriptors(self) -> Dict[str, torch.Tensor]:
         """Per ligand, as [B] device tensors: n_heavy, n_h, hbd, hba, n_rot, n_rings, n_arom_rings, n_arom_atoms, lipinski4 (how
@@ -549,6 +570,52 @@ class Sanitized:
             out[name + '_mean'] = float(col.mean()) if n_valid else 0.0
             out[name + '_std'] = float(col.std(unbiased=False)) if n_valid else 0.0
         return out
+
+
+class Hydrogenated:
+    """What `Sanitized.add_hs` returns: `.molecules` (a `Molecules` with the hydrogens appended to every ligand's atoms and bonds,
+    Kekule orders, so `.sdf()`, `.keys()`, `.sanitize()`, `.relax()`, `.vina_score()`, `.vina_minimize()` and `.vina_dock()` work
+    unchanged; its `lig_elements` are the input's plus 'H' if that was absent), `.parent` [N'] (for an H the row of its heavy
+    atom, else the atom's own row), `.source` [N'] (-1 for an H, else the row in `.heavy`), `.is_h` [N'] (bool), `.n_h` [B],
+    `.status` [B] (bits hip.HS_*: 1 no molecule, 2 more than 256 atoms with the hydrogens, 8 some atom placed by the general rule,
+    16 a non-finite coordinate; with 1, 2 or 16 the ligand is copied through without hydrogens), device tensors, and `.heavy`
+    (the `Sanitized.molecules` it came from).  The placement rule is include/kpd.h's, NOT RDKit's."""
+
+    def __init__(self, san: 'Sanitized'):
+        m = san.molecules
+        if m.pos is None or m.lig_elements is None or m.bonds is None:
+            raise hip.KpdError('these Molecules carry no coordinates: build them with build_molecules')
+        if not m.pos.is_cuda:
+            raise hip.KpdError(f'add_hs: ligands must live on the GPU (got {m.pos.device}); hydrogen placement has no CPU implementation')
+        elements = list(m.lig_elements)
+        allowed = list(m._allowed) if m._allowed is not None else _class_tables(elements, None)[1]
+        if 'H' not in elements:
+            elements.append('H')
+            allowed.append(ALLOWED_BONDS['H'] if m._allowed_h is None else m._allowed_h)
+        h_class = elements.index('H')
+        z = [ATOMIC_NUMBERS.get(el, 0) for el in elements]
+        dev = m.pos.device
+        self.heavy = m
+        if len(m) == 0:
+            i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+            out = dict(lig_ptr=i32(1), pos=torch.zeros(0, 3, device=dev), elem=i32(0), valence=i32(0), frag=i32(0), bonds=i32(0, 2),
+                       order=i32(0), bond_ptr=i32(1), summary=i32(0, 4), parent=i32(0), source=i32(0), n_h=i32(0), status=i32(0))
+            sizes: Optional[List[int]] = []
+        else:
+            mol = dict(elem=m.elem, frag=m.frag, bonds=m.bonds, bond_ptr=m.bond_ptr, status=m.status)
+            out = hip.mol_add_hs(m.pos, m.lig_ptr, z, allowed, h_class, mol, san._out, largest_only=san.largest_frag)
+            sizes = (out['lig_ptr'][1:] - out['lig_ptr'][:-1]).cpu().tolist()
+            for k in ('pos', 'elem', 'valence', 'frag', 'parent', 'source'):       # rows sized for ligands that were copied through
+                out[k] = out[k][:sum(sizes)]
+        self.molecules = Molecules(out['lig_ptr'], out['summary'], m.status, out['elem'], out['valence'], out['frag'], out['bonds'],
+                                   out['order'], out['bond_ptr'], out['pos'], elements, sizes=sizes)
+        self.molecules.valid, self.molecules._allowed, self.molecules._allowed_h = san.valid, allowed, m._allowed_h
+        self.parent, self.source, self.n_h, self.status = out['parent'], out['source'], out['n_h'], out['status']
+        self.is_h = (out['source'] < 0) & (out['elem'] >= 0)
+
+    def sdf(self, largest_frag: bool = False, strict: bool = True) -> List[str]:
+        """`.molecules.sdf()`: the blocks with their 'H' atom lines."""
+        return self.molecules.sdf(largest_frag=largest_frag, strict=strict)
 
 
 class VinaDocked:
@@ -726,6 +793,8 @@ def build_molecules(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], l
     mols = Molecules(ptr, m['summary'], m['status'], m['elem'], m['valence'], m['frag'], m['bonds'], m['order'], m['bond_ptr'],
                      hip._dev_f32(pos, 'pos'), lig_elements, sizes=sizes)
     mols._allowed = allowed
+    if allowed_bonds is not None and 'H' in allowed_bonds:
+        mols._allowed_h = _class_tables(['H'], allowed_bonds)[1][0]
     return mols
 
 
@@ -771,12 +840,15 @@ def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_count
 
 
 def relax_samples(samples: List[dict], pockets: List[dict], lig_elements: Sequence[str], device=None,
-                  allowed_bonds: Optional[Dict[str, object]] = None, vdw: Optional[Dict[str, tuple]] = None, **params) -> Relaxed:
+                  allowed_bonds: Optional[Dict[str, object]] = None, vdw: Optional[Dict[str, tuple]] = None, add_hs: bool = False,
+                  **params) -> Relaxed:
     """The counterpart of `analyze_samples` for upstream's analysis/pocket_minimization.py: `samples` is the list of
     {'positions', 'features'} dicts `_sample` returns, one per pocket, and `pockets` one {'positions': [m,3] tensor, 'elements':
     m symbols} dict per entry, in the frame of its ligands.  All ligands are perceived and relaxed inside their own pocket in
     one batch (`Molecules.relax`, whose limits apply: the force field of include/kpd.h, NOT UFF); ligand k of the result is
-    the k-th ligand in the order of `samples`.  `device`: the GPU to copy host tensors to, as for `analyze_samples`."""
+    the k-th ligand in the order of `samples`.  `device`: the GPU to copy host tensors to, as for `analyze_samples`.
+    `add_hs=True` (upstream's `pocket_minimization(add_hs=True)`): the ligands are sanitised and given explicit hydrogens
+    (`Sanitized.add_hs`) before they are relaxed; the result's `.molecules` then carry the hydrogens."""
     if len(samples) != len(pockets):
         raise ValueError('samples and pockets must have one entry per pocket')
     lig_pos, lig_feat, pocket_of = [], [], []
@@ -789,7 +861,26 @@ def relax_samples(samples: List[dict], pockets: List[dict], lig_elements: Sequen
         lig_pos, lig_feat = [p.to(device) for p in lig_pos], [f.to(device) for f in lig_feat]
         pocket_pos = [p.to(device) for p in pocket_pos]
     mols = build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds)
+    if add_hs:
+        mols = mols.sanitize().add_hs().molecules
     return mols.relax(pocket_pos, [list(p['elements']) for p in pockets], pocket_of=pocket_of, vdw=vdw, **params)
+
+
+def hydrogenate_samples(samples: List[dict], lig_elements: Sequence[str], device=None,
+                        allowed_bonds: Optional[Dict[str, object]] = None, largest_frag: bool = False,
+                        masses: Optional[Dict[str, float]] = None) -> Hydrogenated:
+    """Perceive, sanitise and hydrogenate all sampled ligands in one batch, in the mould of `relax_samples`: `samples` is the
+    list of {'positions', 'features'} dicts `_sample` returns, one per pocket; ligand k of the result is the k-th ligand in the
+    order of `samples`.  Stands where upstream calls `process_molecule(add_hydrogens=True)`; the rules are include/kpd.h's
+    (`Molecules.sanitize`, `Sanitized.add_hs`), NOT RDKit's.  `device`: the GPU to copy host tensors to."""
+    lig_pos, lig_feat = [], []
+    for rec in samples:
+        lig_pos.extend(rec['positions'])
+        lig_feat.extend(rec['features'])
+    if device is not None:
+        lig_pos, lig_feat = [p.to(device) for p in lig_pos], [f.to(device) for f in lig_feat]
+    mols = build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds)
+    return mols.sanitize(largest_frag=largest_frag, masses=masses, allowed_bonds=allowed_bonds).add_hs()
 
 
 def score_samples(samples: List[dict], pockets: List[dict], lig_elements: Sequence[str], device=None, relax: bool = False,

@@ -55,16 +55,20 @@ def write_xyz_file(coords: torch.Tensor, atom_types: Sequence[str], filename: Op
 
 
 def sampled_ligands_sdf(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig_elements: Sequence[str],
-                        largest_frag: bool = False) -> List[str]:
+                        largest_frag: bool = False, add_hs: bool = False) -> List[str]:
     """For every sampled ligand its MOL V2000 block, closed by `$$$$` (bonds perceived on the GPU, `molecule.build_molecules`);
-    `largest_frag`: only the largest fragment of every ligand, as upstream's `process_molecule(largest_frag=True)`."""
+    `largest_frag`: only the largest fragment of every ligand, as upstream's `process_molecule(largest_frag=True)`;
+    `add_hs`: sanitised (Kekule bond orders) and with explicit hydrogens, as its `add_hydrogens=True` (`Sanitized.add_hs`)."""
     from .molecule import build_molecules
-    return build_molecules(lig_pos, lig_feat, lig_elements).sdf(largest_frag=largest_frag)
+    mols = build_molecules(lig_pos, lig_feat, lig_elements)
+    if add_hs:
+        mols = mols.sanitize(largest_frag=largest_frag).add_hs().molecules
+    return mols.sdf(largest_frag=largest_frag)
 
 
 def write_sdf_file(filename, lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig_elements: Sequence[str],
-                   largest_frag: bool = False) -> None:
+                   largest_frag: bool = False, add_hs: bool = False) -> None:
     """Write the blocks of `sampled_ligands_sdf`, concatenated, as one SDF file."""
-    blocks = sampled_ligands_sdf(lig_pos, lig_feat, lig_elements, largest_frag=largest_frag)
+    blocks = sampled_ligands_sdf(lig_pos, lig_feat, lig_elements, largest_frag=largest_frag, add_hs=add_hs)
     with open(filename, 'w') as f:
         f.write(''.join(blocks))
