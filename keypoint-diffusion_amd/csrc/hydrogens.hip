@@ -7,9 +7,12 @@
 // kernel runs twice: a size pass that only counts, the shared exclusive scan (atoms and bonds of a ligand packed into one
 // 64-bit count), and the write pass, which also blanks the rows no ligand fills.  Integer LDS atomics only (all commutative), no float atomics, no scratch memory.
 // All geometry is fp64 with every product and sum rounded once: the Makefile compiles this file with -ffp-contract=off.
+// The front end (entry check, atom staging, the scope S, the bond loop with its ordered row contract), the bits of
+// kpd_mol_sanitize's outputs that are read here and the fp64 vectors are those of molgraph_core.h, shared with k_mol_keys and
+// k_mol_sanitize.
 #include "common.h"
 #include "engine.h"
-#include "molecule_core.h"
+#include "molgraph_core.h"
 #include "scan_core.h"
 
 namespace kpd {
@@ -18,28 +21,8 @@ enum : int { HS_NO_MOLECULE = 1, HS_TOO_MANY_ATOMS = 2, HS_NO_ROOM = 4, HS_GENER
 enum : int { HS_LINEAR = 0, HS_PLANAR = 1, HS_TET = 2 };
 // what the class of an atom is read from: its own bonds and the aromatic flag
 enum : unsigned { HI_TRIPLE = 1, HI_TWO_DOUBLES = 2, HI_DOUBLE = 4, HI_AROMATIC = 8 };
-constexpr int SAN_NO_MOLECULE_BIT = 1, SAN_ATOM_AROMATIC_BIT = 2;
 constexpr double HS_THIRD = 0.3333333333333333, HS_TET1 = 0.9428090415820634, HS_S3 = 0.5773502691896258, HS_TET2 = 0.816496580927726,
                  HS_H3 = 0.8660254037844386;
-
-struct V3 {
-    double x, y, z;
-};
-__device__ __forceinline__ double vdot(V3 a, V3 b) { return __dadd_rn(__dadd_rn(__dmul_rn(a.x, b.x), __dmul_rn(a.y, b.y)), __dmul_rn(a.z, b.z)); }
-__device__ __forceinline__ V3 vcross(V3 a, V3 b) {
-    return {__dsub_rn(__dmul_rn(a.y, b.z), __dmul_rn(a.z, b.y)), __dsub_rn(__dmul_rn(a.z, b.x), __dmul_rn(a.x, b.z)),
-            __dsub_rn(__dmul_rn(a.x, b.y), __dmul_rn(a.y, b.x))};
-}
-__device__ __forceinline__ V3 vadd(V3 a, V3 b) { return {__dadd_rn(a.x, b.x), __dadd_rn(a.y, b.y), __dadd_rn(a.z, b.z)}; }
-__device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {__dsub_rn(a.x, b.x), __dsub_rn(a.y, b.y), __dsub_rn(a.z, b.z)}; }
-__device__ __forceinline__ V3 vover(V3 a, double s) { return {__ddiv_rn(a.x, s), __ddiv_rn(a.y, s), __ddiv_rn(a.z, s)}; }
-__device__ __forceinline__ V3 vneg(V3 a) { return {-a.x, -a.y, -a.z}; }
-// x a + y b, component by component: (x a_c) + (y b_c)
-__device__ __forceinline__ V3 vcomb(double x, V3 a, double y, V3 b) {
-    return {__dadd_rn(__dmul_rn(x, a.x), __dmul_rn(y, b.x)), __dadd_rn(__dmul_rn(x, a.y), __dmul_rn(y, b.y)),
-            __dadd_rn(__dmul_rn(x, a.z), __dmul_rn(y, b.z))};
-}
-__device__ __forceinline__ V3 vat(const float *p, int a) { return {(double)p[a * 3], (double)p[a * 3 + 1], (double)p[a * 3 + 2]}; }
 
 __device__ __forceinline__ V3 vperp(V3 u) {
     int e = 0;
@@ -55,18 +38,6 @@ __device__ __forceinline__ V3 vperp(V3 u) {
     const V3 q = {__dsub_rn(e == 0 ? 1.0 : 0.0, __dmul_rn(ue, u.x)), __dsub_rn(e == 1 ? 1.0 : 0.0, __dmul_rn(ue, u.y)),
                   __dsub_rn(e == 2 ? 1.0 : 0.0, __dmul_rn(ue, u.z))};
     return vover(q, __dsqrt_rn(vdot(q, q)));
-}
-
-// exclusive prefix of v over the lanes of the wave; total = the wave's sum
-__device__ __forceinline__ int hs_wave_exclusive(int v, int lane, int &total) {
-    int s = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(s, off);
-        if (lane >= off) s += t;
-    }
-    total = __shfl(s, 63);
-    return s - v;
 }
 
 // where the hydrogens of one atom go: rows of the output batch, or nowhere (a ligand that does not fit is not written)
@@ -253,14 +224,10 @@ k_mol_add_hs(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
     __shared__ unsigned inS[MOL_W];
     __shared__ int bad, stat;
     const int b = blockIdx.x, lane = threadIdx.x;
-    int a0, a1;
-    const bool seg = mol_segment(lig_ptr, b, n_atoms, a0, a1);
-    const int n = seg ? a1 - a0 : 0;
-    int p0 = 0, p1 = 0;
-    const bool range_ok = seg && mol_bond_range(bond_ptr, b, cap_in, p0, p1);
-    const int m = range_ok ? p1 - p0 : 0;
-    bool ok = range_ok && n > 0 && n <= MOL_MAX && !(mol_status[b] & (MOL_EMPTY | MOL_CAPACITY | MOL_BAD_SEGMENT)) &&
-              !(san_status[b] & SAN_NO_MOLECULE_BIT) && zs[h_class] == 1;
+    const MolEntry en = mol_entry(lig_ptr, b, n_atoms, bond_ptr, cap_in, mol_status);
+    const int a0 = en.a0, n = en.seg ? en.n : 0, p0 = en.p0;
+    const int m = en.seg && en.range_ok ? en.p1 - p0 : 0;
+    bool ok = en.ok && !(san_status[b] & SAN_NO_MOLECULE) && zs[h_class] == 1;
     bool finite = true;
     int fr_of[MOL_K] = {-1, -1, -1, -1}, h_raw[MOL_K] = {0, 0, 0, 0};
     if (ok) {                                       // wave-uniform, as every `ok` below
@@ -276,81 +243,31 @@ k_mol_add_hs(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
         }
         if (lane == 0) bad = stat = 0;
         __syncthreads();
-#pragma unroll
-        for (int k = 0; k < MOL_K; ++k) {
-            const int a = lane + 64 * k;
-            if (a < n) {
-                const size_t g = (size_t)(a0 + a);
-                const int e = elem[g], f = frag[g], h = atom_h[g];
-                if (e < 0 || e >= F || f < 0 || f >= n || h < 0 || h > 4) {
-                    atomicOr(&bad, 1);
-                } else {
-                    const int zz = zs[e];
-                    zv[a] = (unsigned char)(zz >= 0 && zz <= 255 ? zz : 0);
-                    fr_of[k] = f;
-                    h_raw[k] = h;
-                    atomicAdd(&fsize[f], 1);
-                    if (atom_flags[g] & SAN_ATOM_AROMATIC_BIT) info[a] = HI_AROMATIC;
-                }
-                const float x = pos[g * 3], y = pos[g * 3 + 1], z = pos[g * 3 + 2];
-                p[a * 3] = x;
-                p[a * 3 + 1] = y;
-                p[a * 3 + 2] = z;
-                if (!(finite_f(x) && finite_f(y) && finite_f(z))) finite = false;
-            }
-        }
+        mol_stage_atoms(elem, F, zs, frag, a0, n, lane, fsize, &bad, fr_of, [&](int k, int a, size_t g, int z) {
+            const int h = atom_h[g];
+            if (h < 0 || h > 4) return false;
+            zv[a] = mol_z_byte(z);
+            h_raw[k] = h;
+            if (atom_flags[g] & AT_AROMATIC) info[a] = HI_AROMATIC;
+            const float x = pos[g * 3], y = pos[g * 3 + 1], w = pos[g * 3 + 2];
+            p[a * 3] = x;
+            p[a * 3 + 1] = y;
+            p[a * 3 + 2] = w;
+            if (!(finite_f(x) && finite_f(y) && finite_f(w))) finite = false;
+            return true;
+        });
         __syncthreads();
         ok = !bad;
         finite = !__any(!finite);
     }
     int nS = 0, n_frags = 0;
     if (ok) {
-        // the scope S of kpd_mol_sanitize: the largest fragment (most atoms, then the lowest rank), or every atom
-        int rank = -1;
-        if (largest_only) {
-            int best = 0;
-#pragma unroll
-            for (int k = 0; k < MOL_K; ++k) {
-                const int f = lane + 64 * k;
-                if (f < n && fsize[f]) best = max(best, fsize[f] * MOL_MAX + (MOL_MAX - 1 - f));
-            }
-#pragma unroll
-            for (int off = 32; off; off >>= 1) best = max(best, __shfl_xor(best, off));
-            rank = MOL_MAX - 1 - best % MOL_MAX;
-        }
-#pragma unroll
-        for (int k = 0; k < MOL_K; ++k) {
-            n_frags += __popcll(__ballot(lane + 64 * k < n && fsize[lane + 64 * k] > 0));
-            const unsigned long long mk = __ballot(fr_of[k] >= 0 && (rank < 0 || fr_of[k] == rank));
-            nS += __popcll(mk);
-            if (lane == 0) {
-                inS[2 * k] = (unsigned)mk;
-                inS[2 * k + 1] = (unsigned)(mk >> 32);
-            }
-        }
-        __syncthreads();
+        const MolScope sc = mol_scope(fsize, fr_of, n, lane, largest_only, inS);
+        nS = sc.nS;
+        n_frags = sc.n_frag;
         // the bond rows: i < j inside the ligand, order_k 1 .. 3, in (i, j) order (so none twice); neighbour entries inside S
-        for (int k = p0 + lane; k < p1; k += 64) {
-            const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0, o = order_k[k];
-            bool good = i >= 0 && i < j && j < n && o >= 1 && o <= 3;
-            if (good && k > p0) {
-                const int pi = bond_ij[(size_t)(k - 1) * 2] - a0, pj = bond_ij[(size_t)(k - 1) * 2 + 1] - a0;
-                good = pi < i || (pi == i && pj < j);
-            }
-            if (!good) {
-                atomicOr(&bad, 1);
-                continue;
-            }
-            atomicAdd(&upto[i], 1);
-            if (!((inS[i >> 5] >> (i & 31)) & (inS[j >> 5] >> (j & 31)) & 1u)) continue;
-            const int si = atomicAdd(&deg[i], 1), sj = atomicAdd(&deg[j], 1);
-            if (si >= MOL_DEG || sj >= MOL_DEG) {   // a seventh neighbour
-                atomicOr(&bad, 1);
-                continue;
-            }
-            nb[i * MOL_DEG + si] = (unsigned)j | (unsigned)o << 8;
-            nb[j * MOL_DEG + sj] = (unsigned)i | (unsigned)o << 8;
-        }
+        mol_bond_graph<true>(bond_ij, order_k, p0, en.p1, a0, n, lane, inS, (unsigned *)nullptr, 0, deg, upto, nb, &bad,
+                             [](int, int o) { return (unsigned)o << 8; });
         __syncthreads();
         ok = !bad && nS > 0;
     }
@@ -381,12 +298,12 @@ k_mol_add_hs(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
                 if (doubles >= 1) inf |= HI_DOUBLE;
                 if (doubles >= 2) inf |= HI_TWO_DOUBLES;
                 info[a] = (unsigned char)inf;
-                if ((inS[a >> 5] >> (a & 31)) & 1u) h = h_raw[k];
+                if (in_scope(inS, a)) h = h_raw[k];
                 hs[a] = (unsigned char)h;
             }
             int tot_h, tot_r;
             const int rows = a < n ? upto[a] : 0;
-            const int eh = hs_wave_exclusive(h, lane, tot_h), er = hs_wave_exclusive(rows, lane, tot_r);
+            const int eh = wave_exclusive(h, lane, tot_h), er = wave_exclusive(rows, lane, tot_r);
             if (a < n) {
                 before[a] = base_h + eh;
                 upto[a] = base_r + er + rows;
@@ -474,8 +391,7 @@ k_mol_add_hs(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
             const int e = elem[a0 + a], v = valence_k[a0 + a] + (grow ? (int)hs[a] : 0);
             invalid += v == 0 || v > allowed[e] || !element_row(zs[e]);
         }
-#pragma unroll
-        for (int off = 32; off; off >>= 1) largest = max(largest, __shfl_xor(largest, off));
+        largest = wave_max(largest);
         invalid = wave_sum(invalid);
         if (grow && (allowed[h_class] < 1 || !element_row(zs[h_class]))) invalid += H;
     }

@@ -11,23 +11,12 @@
 #include "common.h"
 #include "emit_core.h"
 #include "engine.h"
-#include "molecule_core.h"
+#include "molgraph_core.h"
 #include "scan_core.h"
 
 namespace kpd {
 
 enum : int { SDF_NONFINITE = 1, SDF_WIDE = 2, SDF_NO_MOLECULE = 4, SDF_CAPACITY = 8 };
-
-__device__ __forceinline__ int wave_exclusive(int v, int lane, int &total) {
-    int s = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(s, off);
-        if (lane >= off) s += t;
-    }
-    total = __shfl(s, 63);
-    return s - v;
-}
 
 // the bond of the wave's candidates with the highest (order, d2, partner), on every lane
 __device__ __forceinline__ void wave_argmax(int &o, double &d, int &j) {
@@ -419,10 +408,10 @@ k_sdf_size(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int n
     __syncthreads();
     flags = red[0];
     if (largest_only && !flags) {                   // most atoms, then the lowest rank
-        const int key = tid < n && fsize[tid] ? fsize[tid] * MOL_MAX + (MOL_MAX - 1 - tid) : 0;
+        const int key = tid < n && fsize[tid] ? frag_key(fsize[tid], tid) : 0;
         atomicMax(&best, key);
         __syncthreads();
-        const int rank = MOL_MAX - 1 - best % MOL_MAX;
+        const int rank = frag_key_rank(best);
         int nb = 0;
         for (int k = p0 + tid; k < p1; k += 256) {
             const int i = bond_ij[(size_t)k * 2] - a0;

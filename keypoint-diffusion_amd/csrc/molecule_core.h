@@ -6,6 +6,8 @@
 // and on the host the argument check and the number of staged pocket rows.  pocket.hip takes the segment check alone.
 // vina_min.hip takes the same front end; what vina.hip and vina_min.hip share beyond it (typing, pair terms, staging, bond graph,
 // graph walk) is in vina_core.h.  The wave butterflies (wave_sum, the fp64 wave_max) serve relax.hip and both of them.
+// molset.hip, sanitize.hip and hydrogens.hip share "one wave takes one perceived ligand and builds its graph in the scope S"
+// through molgraph_core.h, which stands on this file; the int wave_max, the 64-bit wave_sum and wave_exclusive serve them and molecule.hip.
 #pragma once
 #include <algorithm>
 
@@ -77,6 +79,27 @@ __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
     for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
     return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {      // modulo 2^64
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v = max(v, __shfl_xor(v, off));
+    return v;
+}
+// exclusive prefix of v over the lanes of the wave; total = the wave's sum
+__device__ __forceinline__ int wave_exclusive(int v, int lane, int &total) {
+    int s = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(s, off);
+        if (lane >= off) s += t;
+    }
+    total = __shfl(s, 63);
+    return s - v;
 }
 __device__ __forceinline__ double wave_sum(double v) {      // a butterfly: the same bits on every lane
 #pragma unroll

@@ -7,8 +7,11 @@
 // k_mol_keys: one wave per ligand, as k_mol_perceive.  Adjacency bit rows and neighbour lists in LDS, all-pairs BFS with a
 // lane per source atom and the frontier as a bitset in registers, the invariants double-buffered, lanes stride over the atoms
 // in passes of 64.  k_fp_diversity: one workgroup per group, a thread per pair, fp64 partial sums reduced by a fixed tree.
+// The front end of k_mol_keys (entry check, atom staging, the scope S, the membership test) is that of molgraph_core.h, shared
+// with k_mol_sanitize and k_mol_add_hs; the bond loop is the header's unordered form written out here, the one piece whose call
+// cost time.  The header's fp64 vectors are not used here (no -ffp-contract=off).
 #include "common.h"
-#include "molecule_core.h"
+#include "molgraph_core.h"
 
 namespace kpd {
 
@@ -29,18 +32,6 @@ __device__ __forceinline__ u64 mix(u64 x) {                     // the splitmix6
     x *= 0x94D049BB133111EBull;
     x ^= x >> 31;
     return x;
-}
-
-__device__ __forceinline__ u64 wave_sum64(u64 v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = max(v, __shfl_xor(v, off));
-    return v;
 }
 
 // one refinement step of atom a: mix(K1 x[a] + sum over its bonds of mix(x[b] + l K2)); a neighbour entry is b | l << 8
@@ -76,12 +67,9 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
     __shared__ unsigned row[MS_FP_WORDS];
     __shared__ int bad;
     const int b = blockIdx.x, lane = threadIdx.x;
-    int a0, a1;
-    bool ok = mol_segment(lig_ptr, b, n_atoms, a0, a1);
-    const int n = a1 - a0;
-    ok = ok && n > 0 && n <= MOL_MAX && !(mol_status[b] & (MOL_EMPTY | MOL_CAPACITY | MOL_BAD_SEGMENT));
-    int p0 = 0, p1 = 0;
-    ok = ok && mol_bond_range(bond_ptr, b, cap_bonds, p0, p1);
+    const MolEntry en = mol_entry(lig_ptr, b, n_atoms, bond_ptr, cap_bonds, mol_status);
+    const int a0 = en.a0, n = en.n;
+    bool ok = en.ok;
     unsigned *out_row = fp + (size_t)b * nwords;
     if (ok) {                                       // wave-uniform, as every `ok` below
 #pragma unroll
@@ -94,64 +82,33 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
         for (int w = lane; w < MS_FP_WORDS; w += 64) row[w] = 0;
         if (lane == 0) bad = 0;
         __syncthreads();
-        // atoms: atomic number of the class, sizes of the fragments
+        // atoms: atomic number of the class (the full int), sizes of the fragments
         int fr_of[MOL_K];
-#pragma unroll
-        for (int k = 0; k < MOL_K; ++k) {
-            const int a = lane + 64 * k;
-            fr_of[k] = -1;
-            if (a < n) {
-                const int e = elem[a0 + a], f = frag[a0 + a];
-                if (e < 0 || e >= F || f < 0 || f >= n) {
-                    atomicOr(&bad, 1);
-                } else {
-                    const int z = zs[e];
-                    zv[a] = z;
-                    zk[a] = (u64)(long long)z * MS_K2;
-                    fr_of[k] = f;
-                    atomicAdd(&fsize[f], 1);
-                }
-            }
-        }
+        mol_stage_atoms(elem, F, zs, frag, a0, n, lane, fsize, &bad, fr_of, [&](int, int a, size_t, int z) {
+            zv[a] = z;
+            zk[a] = (u64)(long long)z * MS_K2;
+            return true;
+        });
         __syncthreads();
         ok = !bad;
-        // the scope S: the largest fragment (most atoms, then the lowest rank), or every atom
         int nS = 0;
         if (ok) {
-            int rank = -1;
-            if (largest_only) {
-                int best = 0;
-#pragma unroll
-                for (int k = 0; k < MOL_K; ++k) {
-                    const int f = lane + 64 * k;
-                    if (f < n && fsize[f]) best = max(best, fsize[f] * MOL_MAX + (MOL_MAX - 1 - f));
-                }
-                best = wave_max(best);
-                rank = MOL_MAX - 1 - best % MOL_MAX;
-            }
-#pragma unroll
-            for (int k = 0; k < MOL_K; ++k) {
-                const u64 m = __ballot(fr_of[k] >= 0 && (rank < 0 || fr_of[k] == rank));
-                nS += __popcll(m);
-                if (lane == 0) {
-                    inS[2 * k] = (unsigned)m;
-                    inS[2 * k + 1] = (unsigned)(m >> 32);
-                }
-            }
-            __syncthreads();
-            // bonds with both ends in S: adjacency bits and neighbour lists (the order of a list does not matter)
-            for (int k = p0 + lane; k < p1; k += 64) {
+            nS = mol_scope(fsize, fr_of, n, lane, largest_only, inS).nS;
+            // bonds with both ends in S: adjacency bits and neighbour lists (the order of a list does not matter).  This is
+            // mol_bond_graph<false> of molgraph_core.h written out: calling it here costs 1.7 % (profiles/molgraph_core.md)
+            for (int k = en.p0 + lane; k < en.p1; k += 64) {
                 const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0, o = bond_order[k];
                 if (i < 0 || i >= n || j < 0 || j >= n || i == j || o < 1 || o > 3) {
                     atomicOr(&bad, 1);
                     continue;
                 }
-                if (!((inS[i >> 5] >> (i & 31)) & (inS[j >> 5] >> (j & 31)) & 1u)) continue;
+                if (!both_in_scope(inS, i, j)) continue;
                 const unsigned l = with_orders ? (unsigned)o : 1u;
-                const unsigned was = atomicOr(&A[i * MS_ROW + (j >> 5)], 1u << (j & 31));
-                atomicOr(&A[j * MS_ROW + (i >> 5)], 1u << (i & 31));
+                const int lo = min(i, j), hi = max(i, j);   // the first mark is on one word whichever way round the bond is listed
+                const unsigned was = atomicOr(&A[lo * MS_ROW + (hi >> 5)], 1u << (hi & 31));
+                atomicOr(&A[hi * MS_ROW + (lo >> 5)], 1u << (lo & 31));
                 const int si = atomicAdd(&deg[i], 1), sj = atomicAdd(&deg[j], 1);
-                if (((was >> (j & 31)) & 1u) || si >= MOL_DEG || sj >= MOL_DEG) {          // a bond twice, or a seventh neighbour
+                if (((was >> (hi & 31)) & 1u) || si >= MOL_DEG || sj >= MOL_DEG) {          // a bond twice, or a seventh neighbour
                     atomicOr(&bad, 1);
                     continue;
                 }
@@ -167,7 +124,7 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
 #pragma unroll
             for (int k = 0; k < MOL_K; ++k) {
                 const int a = lane + 64 * k;
-                in[k] = (inS[a >> 5] >> (a & 31)) & 1u;
+                in[k] = in_scope(inS, a);
                 dg[k] = in[k] ? deg[a] : 0;
                 m2 += dg[k];
             }
@@ -200,7 +157,7 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
             // (inv is free: the barrier after the last fingerprint step is behind every lane, and the BFS reads none of it)
             for (int k = 0; k < MOL_K; ++k) {
                 const int a = lane + 64 * k;
-                if (a >= n || !((inS[a >> 5] >> (a & 31)) & 1u)) continue;
+                if (a >= n || !in_scope(inS, a)) continue;
                 unsigned vis[MOL_W], front[MOL_W], next[MOL_W];
 #pragma unroll
                 for (int w = 0; w < MOL_W; ++w) vis[w] = front[w] = (w == (a >> 5)) ? 1u << (a & 31) : 0u;
@@ -265,7 +222,7 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
                 total += mix(inv[cur][a]);
                 if (atom_inv) atom_inv[a0 + a] = (long long)inv[cur][a];
             }
-            total = wave_sum64(total);
+            total = wave_sum(total);
             if (lane == 0) {
                 key[b] = (long long)mix((u64)nS + (u64)m * MS_K3 + MS_K1 * total);
                 status[b] = 0;

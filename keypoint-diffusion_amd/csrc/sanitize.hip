@@ -11,21 +11,21 @@
 // path search packs into two 64-bit registers.  Integer LDS atomics only (all of them commutative), no float atomics, no
 // scratch memory.  All geometry is fp64 with every product and sum rounded once: the Makefile compiles this file with
 // -ffp-contract=off (the __d*_rn functions of the HIP headers are plain operators, which the default setting may fuse).
+// The front end (entry check, atom staging, the scope S, the bond loop with its unordered row contract), the status bits, the six
+// atom flags that are written out and the fp64 vectors are those of molgraph_core.h, shared with k_mol_keys and k_mol_add_hs.
 #include "common.h"
-#include "molecule_core.h"
+#include "molgraph_core.h"
 #include "vina_core.h"
 
 namespace kpd {
 
 typedef unsigned long long u64;
 
-enum : int { SAN_NO_MOLECULE = 1, SAN_TOO_MANY_RINGS = 2, SAN_COMPONENT_TOO_LARGE = 4 };
 enum : int { SAN_MAX_CYCLES = 64, SAN_MAX_COMPONENT = 24 };
 // a neighbour entry: partner | order << 8 | local bond row << 10 | flags
 enum : unsigned { NB_RING = 1u << 20, NB_PLANAR = 1u << 21, NB_GEDGE = 1u << 22, NB_MATCHED = 1u << 23, NB_AROMATIC = 1u << 24 };
-// atom flags: the six that are written out, and the working ones above them
-enum : unsigned { AT_RING = 1, AT_AROMATIC = 2, AT_DONOR = 4, AT_ACCEPTOR = 8, AT_UNSATISFIED = 16, AT_OVERVALENT = 32, AT_OUT = 63,
-                  AT_PLANAR = 1u << 8, AT_ING = 1u << 9, AT_MATCHED = 1u << 10, AT_LONE_PAIR = 1u << 11, AT_TOO_LARGE = 1u << 12 };
+// the working atom flags, above the six of molgraph_core.h that are written out
+enum : unsigned { AT_PLANAR = 1u << 8, AT_ING = 1u << 9, AT_MATCHED = 1u << 10, AT_LONE_PAIR = 1u << 11, AT_TOO_LARGE = 1u << 12 };
 
 __device__ __forceinline__ int normal_valence(int z, int val) {
     switch (z) {
@@ -60,31 +60,20 @@ __device__ __forceinline__ int order_k_of(unsigned e, unsigned fi, unsigned fj) 
     return (int)((e >> 8) & 3u);
 }
 
-__device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
-    return __dadd_rn(__dadd_rn(__dmul_rn(ax, bx), __dmul_rn(ay, by)), __dmul_rn(az, bz));
-}
-
 // step 2: all windows of four consecutive atoms of the cycle (atom t in byte t of `path`) pass the 20 degree test
 __device__ bool cycle_planar(const float *p, u64 path, int len) {
     for (int t = 0; t < len; ++t) {
-        double q[4][3];
+        V3 q[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             int at = t + k;
             if (at >= len) at -= len;
-            const int a = (int)((path >> (8 * at)) & 0xffull);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) q[k][c] = (double)p[a * 3 + c];
+            q[k] = vat(p, (int)((path >> (8 * at)) & 0xffull));
         }
-        const double ux = q[1][0] - q[0][0], uy = q[1][1] - q[0][1], uz = q[1][2] - q[0][2];
-        const double vx = q[2][0] - q[1][0], vy = q[2][1] - q[1][1], vz = q[2][2] - q[1][2];
-        const double wx = q[3][0] - q[2][0], wy = q[3][1] - q[2][1], wz = q[3][2] - q[2][2];
-        const double n1x = __dsub_rn(__dmul_rn(uy, vz), __dmul_rn(uz, vy)), n1y = __dsub_rn(__dmul_rn(uz, vx), __dmul_rn(ux, vz)),
-                     n1z = __dsub_rn(__dmul_rn(ux, vy), __dmul_rn(uy, vx));
-        const double n2x = __dsub_rn(__dmul_rn(vy, wz), __dmul_rn(vz, wy)), n2y = __dsub_rn(__dmul_rn(vz, wx), __dmul_rn(vx, wz)),
-                     n2z = __dsub_rn(__dmul_rn(vx, wy), __dmul_rn(vy, wx));
-        const double qq = __dmul_rn(dot3(n1x, n1y, n1z, n1x, n1y, n1z), dot3(n2x, n2y, n2z, n2x, n2y, n2z));
-        if (!(qq >= 1e-12 && dot3(n1x, n1y, n1z, n2x, n2y, n2z) >= __dmul_rn(0.9396926207859084, __dsqrt_rn(qq)))) return false;
+        const V3 u = vsub(q[1], q[0]), v = vsub(q[2], q[1]), w = vsub(q[3], q[2]);
+        const V3 n1 = vcross(u, v), n2 = vcross(v, w);
+        const double qq = __dmul_rn(vdot(n1, n1), vdot(n2, n2));
+        if (!(qq >= 1e-12 && vdot(n1, n2) >= __dmul_rn(0.9396926207859084, __dsqrt_rn(qq)))) return false;
     }
     return true;
 }
@@ -171,13 +160,9 @@ k_mol_sanitize(const float *__restrict__ pos, const int *__restrict__ lig_ptr, i
     __shared__ unsigned inS[MOL_W];
     __shared__ int bad, ncyc, stat;
     const int b = blockIdx.x, lane = threadIdx.x;
-    int a0, a1;
-    bool ok = mol_segment(lig_ptr, b, n_atoms, a0, a1);
-    const int n = a1 - a0;
-    ok = ok && n > 0 && n <= MOL_MAX && !(mol_status[b] & (MOL_EMPTY | MOL_CAPACITY | MOL_BAD_SEGMENT));
-    int p0 = 0, p1 = 0;
-    const bool range_ok = mol_bond_range(bond_ptr, b, cap_bonds, p0, p1);
-    ok = ok && range_ok;
+    const MolEntry en = mol_entry(lig_ptr, b, n_atoms, bond_ptr, cap_bonds, mol_status);
+    const int a0 = en.a0, n = en.n, p0 = en.p0, p1 = en.p1;
+    bool ok = en.ok;
     int fr_of[MOL_K] = {-1, -1, -1, -1};
     if (ok) {                                       // wave-uniform, as every `ok` below
 #pragma unroll
@@ -191,82 +176,29 @@ k_mol_sanitize(const float *__restrict__ pos, const int *__restrict__ lig_ptr, i
         }
         if (lane == 0) bad = ncyc = stat = 0;
         __syncthreads();
-#pragma unroll
-        for (int k = 0; k < MOL_K; ++k) {
-            const int a = lane + 64 * k;
-            if (a < n) {
-                const size_t g = (size_t)(a0 + a);
-                const int e = elem[g], f = frag[g];
-                if (e < 0 || e >= F || f < 0 || f >= n) {
-                    atomicOr(&bad, 1);
-                } else {
-                    const int zz = zs[e];
-                    zv[a] = (unsigned char)(zz >= 0 && zz <= 255 ? zz : 0);
-                    fr_of[k] = f;
-                    atomicAdd(&fsize[f], 1);
-                }
-                p[a * 3] = pos[g * 3];
-                p[a * 3 + 1] = pos[g * 3 + 1];
-                p[a * 3 + 2] = pos[g * 3 + 2];
-            }
-        }
+        mol_stage_atoms(elem, F, zs, frag, a0, n, lane, fsize, &bad, fr_of, [&](int, int a, size_t g, int z) {
+            zv[a] = mol_z_byte(z);
+            p[a * 3] = pos[g * 3];
+            p[a * 3 + 1] = pos[g * 3 + 1];
+            p[a * 3 + 2] = pos[g * 3 + 2];
+            return true;
+        });
         __syncthreads();
         ok = !bad;
     }
     int nS = 0, n_frag = 1;
     if (ok) {
-        // the scope S of kpd_mol_keys: the largest fragment (most atoms, then the lowest rank), or every atom
-        int rank = -1;
-        if (largest_only) {
-            int best = 0;
-#pragma unroll
-            for (int k = 0; k < MOL_K; ++k) {
-                const int f = lane + 64 * k;
-                if (f < n && fsize[f]) best = max(best, fsize[f] * MOL_MAX + (MOL_MAX - 1 - f));
-            }
-#pragma unroll
-            for (int off = 32; off; off >>= 1) best = max(best, __shfl_xor(best, off));
-            rank = MOL_MAX - 1 - best % MOL_MAX;
-        } else {
-            n_frag = 0;
-#pragma unroll
-            for (int k = 0; k < MOL_K; ++k) n_frag += __popcll(__ballot(lane + 64 * k < n && fsize[lane + 64 * k] > 0));
-        }
-#pragma unroll
-        for (int k = 0; k < MOL_K; ++k) {
-            const u64 m = __ballot(fr_of[k] >= 0 && (rank < 0 || fr_of[k] == rank));
-            nS += __popcll(m);
-            if (lane == 0) {
-                inS[2 * k] = (unsigned)m;
-                inS[2 * k + 1] = (unsigned)(m >> 32);
-            }
-        }
-        __syncthreads();
+        const MolScope sc = mol_scope(fsize, fr_of, n, lane, largest_only, inS);
+        nS = sc.nS;
+        if (!largest_only) n_frag = sc.n_frag;
         // bonds with both ends in S: adjacency bits and neighbour entries
-        for (int k = p0 + lane; k < p1; k += 64) {
-            const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0, o = bond_order[k];
-            if (i < 0 || i >= n || j < 0 || j >= n || i == j || o < 1 || o > 3) {
-                atomicOr(&bad, 1);
-                continue;
-            }
-            if (!((inS[i >> 5] >> (i & 31)) & (inS[j >> 5] >> (j & 31)) & 1u)) continue;
-            const int lo = min(i, j), hi = max(i, j);   // the first mark is on one word whichever way round the bond is listed
-            const unsigned was = atomicOr(&adj[lo * MOL_W + (hi >> 5)], 1u << (hi & 31));
-            atomicOr(&adj[hi * MOL_W + (lo >> 5)], 1u << (lo & 31));
-            const int si = atomicAdd(&deg[i], 1), sj = atomicAdd(&deg[j], 1);
-            if (((was >> (hi & 31)) & 1u) || si >= MOL_DEG || sj >= MOL_DEG) {         // a bond twice, or a seventh neighbour
-                atomicOr(&bad, 1);
-                continue;
-            }
-            const unsigned common = (unsigned)o << 8 | (unsigned)(k - p0) << 10;
-            nb[i * MOL_DEG + si] = (unsigned)j | common;
-            nb[j * MOL_DEG + sj] = (unsigned)i | common;
-        }
+        mol_bond_graph<false>(bond_ij, bond_order, p0, p1, a0, n, lane, inS, adj, MOL_W, deg, (int *)nullptr, nb, &bad,
+                              [](int row, int o) { return (unsigned)o << 8 | (unsigned)row << 10; });
         __syncthreads();
         ok = !bad && nS > 0;
     }
     if (!ok) {                                      // no molecule: the rows keep the orders they came with
-        if (range_ok)
+        if (en.range_ok)
             for (int k = p0 + lane; k < p1; k += 64) order_k[k] = bond_order[k];
         if (lane < 10) desc_i[b * 10 + lane] = 0;
         if (lane < 2) desc_f[b * 2 + lane] = 0.0;
@@ -280,12 +212,12 @@ k_mol_sanitize(const float *__restrict__ pos, const int *__restrict__ lig_ptr, i
 #pragma unroll
     for (int k = 0; k < MOL_K; ++k) {
         const int a = lane + 64 * k;
-        in[k] = (inS[a >> 5] >> (a & 31)) & 1u;
+        in[k] = in_scope(inS, a);
     }
     // ---- step 1: ring bonds (the ends stay connected without the bond), the 5- and 6-cycles by start atom
     for (int k = p0 + lane; k < p1; k += 64) {
         const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0;
-        if (!((inS[i >> 5] >> (i & 31)) & (inS[j >> 5] >> (j & 31)) & 1u)) continue;
+        if (!both_in_scope(inS, i, j)) continue;
         unsigned vis[MOL_W];
         if (!vina_walk<true>(adj, MOL_W, i, j, vis)) continue;
         atomicOr(&nb[i * MOL_DEG + find_slot(nb, deg[i], i, j)], NB_RING);
@@ -295,7 +227,7 @@ k_mol_sanitize(const float *__restrict__ pos, const int *__restrict__ lig_ptr, i
     }
     for (int k = 0; k < MOL_K; ++k) {
         const int s = lane + 64 * k;
-        if (s >= n || !((inS[s >> 5] >> (s & 31)) & 1u)) continue;
+        if (s >= n || !in_scope(inS, s)) continue;
         u64 path = (u64)s;
         unsigned it = 0;                            // the next neighbour slot of the atom at place d in bits 3 d
         int depth = 1;
@@ -571,7 +503,7 @@ k_mol_sanitize(const float *__restrict__ pos, const int *__restrict__ lig_ptr, i
     int n_rot = 0;
     for (int k = p0 + lane; k < p1; k += 64) {
         const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0;
-        if (!((inS[i >> 5] >> (i & 31)) & (inS[j >> 5] >> (j & 31)) & 1u)) {
+        if (!both_in_scope(inS, i, j)) {
             order_k[k] = bond_order[k];
             continue;
         }
