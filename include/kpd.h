@@ -967,6 +967,67 @@ kpd_status kpd_mol_add_hs(const float *pos, const int32_t *lig_ptr, int32_t n_at
                           int32_t *out_order, int32_t *out_bond_ptr, int32_t *out_summary, int32_t *parent, int32_t *source,
                           int32_t *n_h, int32_t *status, void *scratch, void *stream);
 
+/* Canonical SMILES of the sanitised molecules (csrc/smiles.hip): one string per ligand, the form every downstream tool reads.
+ * Stands where upstream calls Chem.MolToSmiles(largest_mol) to compare samples (`uniqueness`, `novelty`, analysis/metrics.py:102-147).
+ * RDKit's canonicalisation cannot be restated here, so THIS COMMENT IS THE DEFINITION.  The strings are valid SMILES of the same
+ * molecule and canonical under THIS rule: NOT RDKit's canonical SMILES and not openbabel's; they cannot be compared as text with
+ * strings from either (nor with upstream's train_smiles.pkl), only with strings of this call.  The inputs are what kpd_mol_perceive
+ * and kpd_mol_sanitize left on the device and are never written.  Integer arithmetic only, modulo 2^64 where it hashes.
+ * Scope S, Z(a), deg(a), "both ends in S" and mix, K1, K2, K3 are those of kpd_mol_keys; n = atoms in S.
+ * Labelled graph: atom a carries (Z(a), h(a) = atom_h[a], ar(a)) and a bond the label L.  aromatic = 1: ar = bit 1 of atom_flags, L = 4 if
+ *   bond_flags has bit 2 (aromatic), else order_k.  aromatic = 0 (the Kekule form): ar = 0 everywhere and L = order_k.
+ * Ranks:  x_0[a] = mix(Z(a) + deg(a) K3 + (2 h(a) + ar(a)) K2 + K1 * sum over b in S, b != a, of mix(Z(b) K2 + d(a,b)))  (inv_0 of
+ *   kpd_mol_keys with the atom's labels added);  step: x'[a] = mix(K1 x[a] + sum over the bonds (a,b) of mix(x[b] + L K2)); n steps.
+ *   Then, while two atoms of S share a value (compared as unsigned 64-bit integers): v = the smallest shared value, a = the atom
+ *   with the LOWEST INDEX among those with x[a] = v; x[a] = mix(x[a] + K3); c = (the number of distinct values before) + 1; then at
+ *   most n times: step, c' = the number of distinct values; stop if c' = c, else c = c'.  rank(a) = the number of atoms of S with a
+ *   smaller value.  The lowest index is the only place where the numbering of the atoms enters: the ranks, and so the string, are
+ *   independent of the numbering whenever the atoms tied at each stage are equivalent under an automorphism of the labelled graph
+ *   (and, as for the key, up to the 64 bits of a hash).  On the 821 inputs of tests/test_smiles_config.py (18 named molecules and
+ *   8 ring templates in both modes, 48 generated ligands, 700 seeded random molecule-like graphs, 21 graphs written by hand), 8
+ *   renumberings each, no string moved.
+ * String: the fragments of S (the `frag` labels, which must be the connected components of S: else no molecule) in ascending rank
+ *   of their start atom, joined by '.'.  The start atom of a fragment: among its atoms of minimal degree the one of lowest rank.
+ *   Depth-first walk from the start atom; at an atom the neighbours are tried in ascending rank; a neighbour not yet visited becomes
+ *   a child and is walked at once.  Every child but the last is written in parentheses.  A bond to a visited atom that is not the
+ *   parent is a ring closure: it OPENS at the end visited first and ENDS at the other.  Behind the atom's token come the closures
+ *   that end here in ascending number (each number is free again from then on), then the closures that open here in ascending rank
+ *   of the partner; each opening takes the lowest free number from 1; 10 .. 99 are written %nn; no free number among 1 .. 99:
+ *   status bit 1 and an empty string.
+ *   Bond symbol (before the child's token, inside its parenthesis; for a closure before the number where it opens, nothing where it
+ *   ends): nothing for L = 1 unless both atoms are aromatic, then '-' (biphenyl); nothing for L = 4; '=' for 2, '#' for 3.
+ *   Atom token: the element symbol is symbols[elem[a]] (up to four bytes, as kpd_xyz_emit reads it), its first letter in lower case
+ *   when ar = 1.  The token is the bare symbol iff Z is in the organic subset B C N O P S F Cl Br I (by atomic number; when ar = 1
+ *   only b c n o p s) and the hydrogens a reader implies equal h: t = the sum of the atom's labels with L = 4 counted 1; ar = 0:
+ *   (the smallest of the normal valences -- B 3, C 4, N 3 5, O 2, P 3 5, S 2 4 6, halogens 1 -- that is >= t) - t, 0 if none is;
+ *   ar = 1: max(0, (the smallest normal valence) - (t + 1)).  Otherwise it is [X], [XH] or [XHn] (n = h, 2 .. 9): [nH], an
+ *   over-valent [N], [Si], the [H] atoms of a hydrogenated batch.
+ * Limits: no charges, no stereo, no isotopes, no atom classes (the limits of kpd_mol_sanitize: a nitro group reads ON(O)..); no
+ *   tautomer canonicalisation (which N of an imidazole carries the H follows kpd_mol_sanitize, and the string follows it); a label
+ *   4 between atoms that are not both aromatic (no output of kpd_mol_sanitize) is written as nothing.
+ *
+ * kpd_mol_smiles: lig_ptr [B+1], elem / frag [n_atoms], bond_ij [cap_bonds,2], bond_ptr [B+1], mol_status [B] as kpd_mol_perceive
+ *   wrote them; order_k / bond_flags [cap_bonds], atom_h / atom_flags [n_atoms] and san_status [B] (its `status`) as
+ *   kpd_mol_sanitize wrote them with the same largest_only, or with largest_only = 0 (its per-atom and per-bond outputs cover
+ *   every fragment, the largest one included; only atoms and bonds of S are read here); z [F]; symbols [F] as for kpd_xyz_emit; aromatic 0 or 1; all device
+ *   pointers.  Out (device): text [capacity], text_ptr [B+1] int64 (ligand b's string = text[text_ptr[b] : text_ptr[b+1]], no
+ *   newline, no terminator; text_ptr[B] is the size needed, also when it exceeds capacity), status [B]: bit 0 = no molecule (san_status
+ *   bit 0, the conditions of kpd_mol_keys -- mol_status bits 0, 1 or 3, more than 256 atoms, an empty S, an element or fragment out
+ *   of range, a bond outside the ligand, twice, of an order_k outside 1 .. 3, a seventh neighbour --, atom_h outside 0 .. 9, or
+ *   `frag` labels that are not the connected components of S), bit 1 = closure numbers exhausted, bit 2 = capacity too small for
+ *   this ligand (nothing is written for it, as kpd_sdf_emit).  With bits 0 or 1 the string is empty.  Nothing is read or written
+ *   out of bounds.  scratch: kpd_smiles_scratch_bytes(n_atoms, B) device bytes (36 per atom: the bound on the text of one atom).
+ *   One wave per ligand builds the bytes in scratch, the library's exclusive scan turns the lengths into text_ptr, a third kernel
+ *   moves the bytes: three launches whatever B >= 1 is (B = 0: the scan alone), no host synchronisation.  A ligand's bytes are
+ *   independent of the rest of the batch, of cap_bonds, of capacity and of the repeat. */
+int64_t kpd_smiles_scratch_bytes(int32_t n_atoms, int32_t B);
+kpd_status kpd_mol_smiles(const int32_t *lig_ptr, int32_t n_atoms, int32_t B, const int32_t *elem, int32_t F, const int32_t *z,
+                          const uint32_t *symbols, const int32_t *frag, const int32_t *bond_ij, const int32_t *order_k,
+                          const int32_t *bond_flags, const int32_t *bond_ptr, int32_t cap_bonds, const int32_t *mol_status,
+                          const int32_t *san_status, const int32_t *atom_h, const int32_t *atom_flags, int32_t largest_only,
+                          int32_t aromatic, uint8_t *text, int64_t capacity, int64_t *text_ptr, int32_t *status, void *scratch,
+                          void *stream);
+
 /* Relaxation of sampled ligands inside their rigid pockets (csrc/relax.hip).  Stands where upstream runs
  * analysis/pocket_minimization.py: RDKit's UFF on ligand + receptor with every receptor atom fixed, maxIts = 400, then the plain
  * (unaligned) CalcRMS and the energies before and after.  RDKit's UFF cannot be restated here -- it needs hydrogens, atom typing,

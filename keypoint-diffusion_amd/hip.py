@@ -214,6 +214,10 @@ def lib():
     L.kpd_mol_add_hs_scratch_bytes.restype = C.c_int64
     L.kpd_mol_add_hs.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] +
                                  [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 15)
+    L.kpd_smiles_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.kpd_smiles_scratch_bytes.restype = C.c_int64
+    L.kpd_mol_smiles.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32] + [C.c_void_p] * 4 +
+                                 [C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4)
     L.kpd_relax_defaults.argtypes = [C.POINTER(KpdRelaxParams)]
     L.kpd_relax_defaults.restype = None
     L.kpd_relax.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
@@ -265,7 +269,8 @@ EXPORTS = [
     'kpd_dist_hinge',
     'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
     'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
-    'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_mol_sanitize', 'kpd_mol_add_hs_scratch_bytes', 'kpd_mol_add_hs', 'kpd_relax_defaults', 'kpd_relax',
+    'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_mol_sanitize', 'kpd_mol_add_hs_scratch_bytes', 'kpd_mol_add_hs',
+    'kpd_smiles_scratch_bytes', 'kpd_mol_smiles', 'kpd_relax_defaults', 'kpd_relax',
     'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score', 'kpd_vina_min_defaults', 'kpd_vina_minimize',
     'kpd_vina_dock_defaults', 'kpd_vina_dock',
 ]
@@ -1203,6 +1208,47 @@ def mol_add_hs(pos: torch.Tensor, lig_ptr: torch.Tensor, z, allowed, h_class: in
                                *[_ptr(out[k]) for k in ('lig_ptr', 'pos', 'elem', 'valence', 'frag', 'bonds', 'order', 'bond_ptr', 'summary',
                                                         'parent', 'source', 'n_h', 'status')], _ptr(scratch), _stream()))
     return out
+
+
+SMI_NO_MOLECULE, SMI_EXHAUSTED, SMI_CAPACITY = 1, 2, 4        # status bits of kpd_mol_smiles
+
+
+def mol_smiles(lig_ptr: torch.Tensor, z, elements, mol: dict, san: dict, largest_only: bool = False, aromatic: bool = True,
+               capacity: Optional[int] = None):
+    """Canonical SMILES of a batch of sanitised molecules on the GPU (kpd_mol_smiles; include/kpd.h states the rule, which is NOT
+    RDKit's).  `mol`: what `mol_perceive` returned, `san`: what `mol_sanitize` returned for it with the same `largest_only` (or over every
+    atom); z / elements: the atomic number and the symbol (at most four characters) of every class; `aromatic=False`: the Kekule form.
+    Returns (text bytes, text_ptr list of B + 1 offsets, status list of B); ligand b's string is text[text_ptr[b]:text_ptr[b + 1]],
+    empty when its status has bit SMI_NO_MOLECULE or SMI_EXHAUSTED.  The buffer is sized at 8 bytes per atom and the call is
+    repeated once with the size the first one reports if that was too small (`capacity`: the first size); the host
+    synchronisations are the copies of the offsets and of the finished text."""
+    B = _offsets(lig_ptr, 'lig_ptr')
+    _mol_fields('mol_smiles', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'))
+    _mol_fields('mol_smiles', san, ('order_k', 'bond_flags', 'atom_h', 'atom_flags', 'status'))
+    N, F, cap_bonds = mol['elem'].numel(), len(z), san['order_k'].numel()
+    if (F < 1 or len(elements) != F or mol['frag'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or
+            san['bond_flags'].numel() != cap_bonds or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B or
+            san['status'].numel() != B or san['atom_h'].numel() != N or san['atom_flags'].numel() != N):
+        raise KpdError(f'mol_smiles: {B} ligands, {F} atomic numbers, {len(elements)} element symbols do not match the perceived and '
+                       f'sanitised molecules')
+    dev = lig_ptr.device
+    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
+    symbols = _packed_symbols(elements, dev)
+    text_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib().kpd_smiles_scratch_bytes(N, B)), dtype=torch.uint8, device=dev)
+    cap = 8 * N + 16 if capacity is None else int(capacity)
+    for attempt in range(2):
+        text = torch.empty(cap, dtype=torch.uint8, device=dev)
+        check(lib().kpd_mol_smiles(_ptr(lig_ptr), N, B, _ptr(mol['elem']), F, _ptr(zt), _ptr(symbols), _ptr(mol['frag']), _ptr(mol['bonds']),
+                                   _ptr(san['order_k']), _ptr(san['bond_flags']), _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']),
+                                   _ptr(san['status']), _ptr(san['atom_h']), _ptr(san['atom_flags']), int(bool(largest_only)),
+                                   int(bool(aromatic)), _ptr(text), cap, _ptr(text_ptr), _ptr(status), _ptr(scratch), _stream()))
+        ptr = text_ptr.cpu().tolist()
+        if ptr[-1] <= cap:
+            break
+        cap = ptr[-1]                               # the size needed: the second call cannot miss
+    return bytes(text[:min(ptr[-1], cap)].cpu().numpy()), ptr, status.cpu().tolist()
 
 
 def fp_diversity(fp: torch.Tensor, use: torch.Tensor, group_ptr: torch.Tensor):

@@ -515,6 +515,39 @@ class Sanitized:
         copy of the B + 1 offsets that gives the new atoms per ligand."""
         return Hydrogenated(self)
 
+    def smiles(self, kekule: bool = False, largest_frag: Optional[bool] = None) -> List[str]:
+        """One SMILES string per ligand, written on the GPU (`kpd_mol_smiles`): the aromatic form (`c1ccccc1`), with `kekule=True`
+        the Kekule form (`C=1C=CC=CC1`).  `largest_frag`: None, the scope these molecules were sanitised with; True, the largest
+        fragment alone (upstream's `Chem.MolToSmiles(largest_mol)`), which molecules sanitised over every atom can give as well,
+        their per-atom results covering every fragment; False needs molecules sanitised over every atom.  Canonical under the
+        rule of include/kpd.h, NOT RDKit's: equal strings mean the same molecule among strings of this library only.  A ligand
+        without a molecule (or with more than 99 ring closures open at once) gives ''; a ligand that is not `valid` still has a
+        string.  No charges, no stereo."""
+        largest = self.largest_frag if largest_frag is None else bool(largest_frag)
+        if self.largest_frag and not largest:
+            raise hip.KpdError('smiles(largest_frag=False) needs molecules sanitised over every atom: sanitize(largest_frag=False)')
+        m = self.molecules
+        if m.lig_elements is None or m.bonds is None:
+            raise hip.KpdError('these Molecules carry no bond graph: build them with build_molecules')
+        if len(m) == 0:
+            return []
+        if not m.lig_ptr.is_cuda:
+            raise hip.KpdError(f'smiles: ligands must live on the GPU (got {m.lig_ptr.device}); there is no CPU implementation')
+        mol = dict(elem=m.elem, frag=m.frag, bonds=m.bonds, bond_ptr=m.bond_ptr, status=m.status)
+        text, ptr, status = hip.mol_smiles(m.lig_ptr, self._z, m.lig_elements, mol, self._out, largest_only=largest, aromatic=not kekule)
+        if any(s & hip.SMI_CAPACITY for s in status):
+            raise hip.KpdError('smiles: text buffer too small (internal sizing error)')
+        return ['' if status[b] else text[ptr[b]:ptr[b + 1]].decode('ascii') for b in range(len(status))]
+
+    def unique(self, kekule: bool = False, largest_frag: Optional[bool] = None) -> List[int]:
+        """The index of the first ligand of every distinct string of `smiles(kekule, largest_frag)`, ascending; ligands without a
+        molecule are left out."""
+        first: Dict[str, int] = {}
+        for b, s in enumerate(self.smiles(kekule, largest_frag)):
+            if s:
+                first.setdefault(s, b)
+        return sorted(first.values())
+
     def descriptors(self) -> Dict[str, torch.Tensor]:
         """Per ligand, as [B] device tensors: n_heavy, n_h, hbd, hba, n_rot, n_rings, n_arom_rings, n_arom_atoms, lipinski4 (how
         many of mw < 500, hbd <= 5, hba <= 10, n_rot <= 10 hold: upstream's logP rule is not counted), n_cycles (int32) and mw
@@ -547,13 +580,19 @@ class Sanitized:
         return torch.where(m.valence >= 0, t, torch.full_like(t, -1))
 
     def metrics(self, type_counts: Optional[torch.Tensor] = None, connectivity_thresh: float = 0.5,
-                group_ptr: Optional[torch.Tensor] = None, train_keys: Optional[torch.Tensor] = None) -> Dict[str, object]:
+                group_ptr: Optional[torch.Tensor] = None, train_keys: Optional[torch.Tensor] = None, by: str = 'key',
+                train_smiles: Optional[Sequence[str]] = None) -> Dict[str, object]:
         """Upstream's order of operations (ModelAnalyzer.sample_and_analyze): validity = ligands that sanitised / ligands that
         were built (as in `Molecules.metrics`, empty and left-out ligands do not count); connectivity over the valid ligands;
         uniqueness, novelty and diversity (`set_metrics(valid_only=True)`) over the valid, connected ones; atom_validity,
         avg_frag_frac and atom_type_kldiv as `Molecules.metrics` gives them; and the mean and standard deviation (np.std) of
         mw, hbd, hba, n_rot and lipinski4 over the valid ligands.  `group_ptr` and `train_keys` are those of `set_metrics` (the
-        pockets' groups for diversity, the training keys for novelty), passed through so that one call gives upstream's seven."""
+        pockets' groups for diversity, the training keys for novelty), passed through so that one call gives upstream's seven.
+        `by='smiles'`: uniqueness (and novelty against `train_smiles`, strings of this library) are counted on the strings of
+        `smiles(largest_frag=True)` instead of on the keys: the same scope, the largest fragment, as every other set metric, but a
+        string does not depend on the Kekule pattern; every other number is the same.  The default is the key."""
+        if by not in ('key', 'smiles'):
+            raise ValueError(f"by must be 'key' or 'smiles' (got {by!r})")
         m = self.molecules
         out: Dict[str, object] = m.metrics(type_counts, connectivity_thresh)
         n = (m.lig_ptr[1:] - m.lig_ptr[:-1]).double()
@@ -564,6 +603,14 @@ class Sanitized:
         frac = m.summary[:, 2].double() / n.clamp(min=1)
         out['connectivity'] = float((frac[valid] >= connectivity_thresh).double().mean()) if n_valid else 0.0
         out.update(m.set_metrics(group_ptr, train_keys, connectivity_thresh, largest_frag=True, valid_only=True))
+        if by == 'smiles':
+            keep = (valid & (frac >= connectivity_thresh)).cpu().tolist()
+            strings = [s for s, k in zip(self.smiles(largest_frag=True), keep) if k and s]
+            distinct = set(strings)
+            out['uniqueness'] = len(distinct) / len(strings) if strings else 0.0
+            if train_smiles is not None:
+                known = set(train_smiles)
+                out['novelty'] = sum(s not in known for s in distinct) / len(distinct) if distinct else 0.0
         desc = self.descriptors()
         for name in ('mw', 'hbd', 'hba', 'n_rot', 'lipinski4'):
             col = desc[name][valid].double()
@@ -812,7 +859,7 @@ def training_keys(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig
 def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_counts: Optional[torch.Tensor] = None,
                     allowed_bonds: Optional[Dict[str, object]] = None, connectivity_thresh: float = 0.5, device=None,
                     train_keys: Optional[torch.Tensor] = None, set_metrics: bool = False, sanitize: bool = False,
-                    masses: Optional[Dict[str, float]] = None) -> Dict[str, float]:
+                    masses: Optional[Dict[str, float]] = None, smiles: bool = False) -> Dict[str, float]:
     """The part of `ModelAnalyzer.sample_and_analyze` (analysis/metrics.py:60-100) that needs no rdkit: `samples` is the list
     of {'positions', 'features'} dicts `_sample` returns, one per pocket; the result is `Molecules.metrics` over all of them
     and, with `set_metrics=True`, `Molecules.set_metrics` as well (uniqueness, novelty against `train_keys` if given, and the
@@ -821,7 +868,11 @@ def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_count
     the concatenated batch would do as well: `build_molecules` takes GPU tensors only and never computes on the host).
     `sanitize=True`: the numbers of `Sanitized.metrics` instead, upstream's seven in upstream's order of operations (`validity`
     first; connectivity, uniqueness, novelty and diversity over the ligands that sanitised) and the descriptor statistics; the
-    rule is include/kpd.h's (`Molecules.sanitize`), NOT RDKit's.  With the default every key and value is what it was."""
+    rule is include/kpd.h's (`Molecules.sanitize`), NOT RDKit's.  With the default every key and value is what it was.
+    `smiles=True` (implies `sanitize=True`): the result also has 'smiles', one list of strings per entry of `samples`: the SMILES
+    of every ligand's largest fragment (upstream's `Chem.MolToSmiles(largest_mol)`; `Sanitized.smiles`, NOT RDKit's canonical
+    form), '' for a ligand without a molecule."""
+    sanitize = sanitize or smiles
     lig_pos, lig_feat = [], []
     for rec in samples:
         lig_pos.extend(rec['positions'])
@@ -831,7 +882,12 @@ def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_count
     mols = build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds)
     if sanitize:
         group_ptr = torch.tensor([0] + [len(rec['positions']) for rec in samples], dtype=torch.int64).cumsum(0).to(torch.int32)
-        return mols.sanitize(masses=masses).metrics(type_counts, connectivity_thresh, group_ptr, train_keys)
+        san = mols.sanitize(masses=masses)
+        out = san.metrics(type_counts, connectivity_thresh, group_ptr, train_keys)
+        if smiles:
+            strings, at = san.smiles(largest_frag=True), group_ptr.tolist()
+            out['smiles'] = [strings[at[q]:at[q + 1]] for q in range(len(samples))]
+        return out
     out = mols.metrics(type_counts, connectivity_thresh)
     if set_metrics:
         group_ptr = torch.tensor([0] + [len(rec['positions']) for rec in samples], dtype=torch.int64).cumsum(0).to(torch.int32)

@@ -72,3 +72,20 @@ def write_sdf_file(filename, lig_pos: List[torch.Tensor], lig_feat: List[torch.T
     blocks = sampled_ligands_sdf(lig_pos, lig_feat, lig_elements, largest_frag=largest_frag, add_hs=add_hs)
     with open(filename, 'w') as f:
         f.write(''.join(blocks))
+
+
+def sampled_ligands_smiles(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig_elements: Sequence[str],
+                           largest_frag: bool = True) -> List[str]:
+    """For every sampled ligand its SMILES string (perceived, sanitised and written on the GPU: `Sanitized.smiles`), canonical
+    under the rule of include/kpd.h, NOT RDKit's; `largest_frag`: of the largest fragment, as upstream takes the SMILES of
+    (`Chem.MolToSmiles(largest_mol)`).  A ligand without a molecule gives the empty string."""
+    from .molecule import build_molecules
+    return build_molecules(lig_pos, lig_feat, lig_elements).sanitize(largest_frag=largest_frag).smiles()
+
+
+def write_smiles_file(filename, lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig_elements: Sequence[str],
+                      largest_frag: bool = True) -> None:
+    """Write the strings of `sampled_ligands_smiles`, one per line; a ligand without a molecule leaves an empty line."""
+    lines = sampled_ligands_smiles(lig_pos, lig_feat, lig_elements, largest_frag=largest_frag)
+    with open(filename, 'w') as f:
+        f.write(''.join(line + '\n' for line in lines))
