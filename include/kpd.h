@@ -1028,6 +1028,73 @@ kpd_status kpd_mol_smiles(const int32_t *lig_ptr, int32_t n_atoms, int32_t B, co
                           int32_t aromatic, uint8_t *text, int64_t capacity, int64_t *text_ptr, int32_t *status, void *scratch,
                           void *stream);
 
+/* Symmetry-corrected RMSD between poses of one molecule (csrc/pose_rmsd.hip): the minimum over the automorphisms of the labelled
+ * bond graph of the unaligned RMSD.  Stands where upstream calls Chem.CalcRMS(mol1, mol2) (analysis/pocket_minimization.py:21),
+ * the number behind its strain table and behind redocking RMSDs: a phenyl ring flipped by 180 degrees, or a carboxylate, CF3 or
+ * tert-butyl turned by one step, is the same pose, and the atom-by-atom number sqrt(sum_i |x_i - y_i|^2 / n) that kpd_relax,
+ * kpd_vina_minimize and kpd_vina_dock report calls it 1 - 2.5 A away.  RDKit's matcher cannot be restated here, so THIS COMMENT IS
+ * THE DEFINITION, down to the order of every choice (tests/pose_rmsd_ref.py restates it bit for bit); no agreement with RDKit's
+ * numbers is claimed.  The inputs are what kpd_mol_perceive (and, for labels, kpd_mol_sanitize) left on the device and are never
+ * written.  mix, K1, K2, K3, Z(a) and the scope of kpd_mol_keys are those stated there.
+ * Scope S: that of kpd_mol_keys (largest_only); with skip_h != 0 the atoms with Z(a) = 1 then leave S as well (the largest
+ *   fragment is chosen with them counted).  n = atoms in S; only bonds with both ends in S count; deg(a), d(a,b) inside S.
+ * Labels: A(a) = Z(a) + 256 atom_label[a] (atom_label = 0 everywhere when the pointer is NULL; allowed 0 .. 2^20 - 1) and
+ *   L(bond) = bond_label[row] (1 everywhere when NULL; allowed 1 .. 15).  Every atom and every bond row of the ligand is range-
+ *   checked, in S or not.  NULL, NULL is elements and connectivity only: Kekule orders as labels would make the two Kekule
+ *   patterns of one benzene ring different graphs.  The labelled graph of kpd_mol_smiles (atom_label = 2 h + ar, bond_label = 4 on
+ *   an aromatic bond, else order_k) does not depend on the pattern either.
+ * Class c(a): inv_n[a] of kpd_mol_keys with Z replaced by A and l by L, deg and d(a,b) inside S, n refinement steps.  c only
+ *   prunes: it cannot change which bijections are automorphisms (an automorphism keeps it), but it decides how many candidates
+ *   are tried, so it is part of the rule.
+ * Automorphism: a bijection pi of S with A(pi(a)) = A(a) that maps every bond (a,b) onto a bond (pi(a), pi(b)) of the same L.
+ * Source order u_0 .. u_{n-1}: repeat: the lowest-index atom of S not yet listed starts a breadth-first traversal, the
+ *   neighbours of an atom in ascending index.  p(u) = the atom from whose list u was enqueued; a start atom has none.
+ * Cost: a search takes a source pose X and a target pose Y (fp32 rows).  d2(u,v) = the fp64 squared distance of X[u] and Y[v]
+ *   in the arithmetic of kpd_mol_perceive: the differences of the fp32 values in fp64, every product and sum rounded once,
+ *   (dx^2 + dy^2) + dz^2.  cost(pi) = ((d2(u_0, pi u_0) + d2(u_1, pi u_1)) + ..) in source order; s_id = cost(identity).
+ * Search: best = s_id, map = identity, nodes = 0.  At depth t, u = u_t, the candidates are the atoms v of S that are no image
+ *   yet, have A(v) = A(u), deg(v) = deg(u) and c(v) = c(u), are neighbours of pi(p(u)) if u has a p(u), and have a bond
+ *   (v, pi(w)) of label L(u,w) for every neighbour w of u listed before u.  They are tried in ascending (d2(u,v), index of v).
+ *   For each: nodes += 1; if nodes > max_nodes the whole search stops with what it has (status bit 1); s = s_t + d2(u,v) (s_0 =
+ *   0); if s >= best this candidate and all later ones of this depth are dropped; else at t = n - 1: best = s and the map is
+ *   recorded (strict improvement only: the first optimum in this order wins); else descend with s_{t+1} = s.
+ *   Rounded addition of non-negative terms is monotone (x <= y implies x + d <= y + d after rounding, and s + d >= s), so a
+ *   dropped candidate cannot lead below best, nor can a later one of its depth: the pruning is exact, and best is the minimum of
+ *   cost(pi) over ALL automorphisms whatever the order of the candidates.  The order decides nodes and which of several optimal
+ *   maps is reported.
+ * Results: rmsd = sqrt(best / n), plain = sqrt(s_id / n) (division and square root correctly rounded); rmsd <= plain always; a
+ *   search that stopped at max_nodes still gives an upper bound of the minimum.
+ * Out of scope: the RMSD after alignment (GetBestRMS), stereo (a mirror image that is a graph automorphism counts), matching
+ *   two different molecules, and kpd_vina_dock's own clustering, which keeps the atom-by-atom number.
+ *
+ * kpd_pose_rmsd: lig_ptr [B+1], elem / frag [n_atoms], bond_ij [cap_bonds,2], bond_ptr [B+1], mol_status [B] as kpd_mol_perceive
+ *   wrote them (the bond orders are not read), z [F]; bond_label [cap_bonds] / atom_label [n_atoms] int32 or NULL; ref_pos
+ *   [n_atoms,3] and pos [K,n_atoms,3] fp32, pose-major, the layout of kpd_vina_dock's pos_out; all device pointers.
+ *   pairs = 0: X = ref_pos, Y = pose k, K >= 1; rmsd, plain [B,K] fp64, nodes [B,K] int64; map [K,n_atoms] int32 or NULL:
+ *     map[k][a] = the global row pi(a) of the recorded map, -1 outside S.
+ *   pairs = 1: X = pose i, Y = pose j for i < j only, K <= 64; outputs [B,K,K]: the UPPER triangle is computed (cost is not
+ *     bitwise symmetric in X and Y: the source order sums other terms), the lower one is its mirror, the diagonal 0; ref_pos and
+ *     map are not used.
+ *   max_nodes >= 1.  KPD_ERR_INVALID for K, pairs or max_nodes out of range.
+ *   status [B]: bit 0 = no molecule (the conditions of kpd_mol_keys without its test of the orders -- mol_status bits 0, 1 or 3,
+ *   more than 256 atoms, an element or fragment out of range, a bond outside the ligand, twice, a seventh neighbour --, a label
+ *   out of range, or an empty S): zeros everywhere and map -1.  bit 1 = some search of this ligand stopped at max_nodes (its
+ *   nodes reads max_nodes + 1), informational.  bit 2 = a non-finite coordinate of an atom of S in a pose used: every search that
+ *   reads it gives zeros, nodes 0 and map -1.
+ *   scratch: kpd_pose_rmsd_scratch_bytes(n_atoms, K, pairs) device bytes (-1 for arguments out of range): the running sums s_t of
+ *   the searches in flight, 8 n_atoms min(64, searches per ligand).
+ *   One wave per ligand, each lane a search of its own, strided over the K poses (or the K (K - 1) / 2 pairs): one launch
+ *   whatever B and K are, and the fills of the outputs; no host synchronisation, no atomics on floats.  Nothing is read or
+ *   written out of bounds.  A ligand's results are bitwise independent of the rest of the batch, of cap_bonds, of K (per pose)
+ *   and of the repeat. */
+enum { KPD_POSE_NO_MOLECULE = 1, KPD_POSE_MAX_NODES = 2, KPD_POSE_NONFINITE = 4 };
+int64_t kpd_pose_rmsd_scratch_bytes(int32_t n_atoms, int32_t K, int32_t pairs);
+kpd_status kpd_pose_rmsd(const int32_t *lig_ptr, int32_t n_atoms, int32_t B, const int32_t *elem, int32_t F, const int32_t *z,
+                         const int32_t *frag, const int32_t *bond_ij, const int32_t *bond_ptr, int32_t cap_bonds,
+                         const int32_t *mol_status, const int32_t *bond_label, const int32_t *atom_label, int32_t largest_only,
+                         int32_t skip_h, const float *ref_pos, const float *pos, int32_t K, int32_t pairs, int64_t max_nodes,
+                         double *rmsd, double *plain, int32_t *map, int64_t *nodes, int32_t *status, void *scratch, void *stream);
+
 /* Relaxation of sampled ligands inside their rigid pockets (csrc/relax.hip).  Stands where upstream runs
  * analysis/pocket_minimization.py: RDKit's UFF on ligand + receptor with every receptor atom fixed, maxIts = 400, then the plain
  * (unaligned) CalcRMS and the energies before and after.  RDKit's UFF cannot be restated here -- it needs hydrogens, atom typing,

@@ -1,5 +1,6 @@
 // "One wave takes one perceived ligand and builds its bond graph in the scope S", stated once for k_mol_keys (molset.hip),
-// k_mol_sanitize (sanitize.hip), k_mol_add_hs (hydrogens.hip) and k_smiles_build (smiles.hip, the unordered row contract): the entry check, the atom staging, the scope, the bond loop
+// k_mol_sanitize (sanitize.hip), k_mol_add_hs (hydrogens.hip), k_smiles_build (smiles.hip, the unordered row contract) and k_pose_rmsd
+// (pose_rmsd.hip: entry check, staging and scope; its bond loop carries labels, not orders): the entry check, the atom staging, the scope, the bond loop
 // with its two row contracts, and the membership test.  include/kpd.h states the rule (kpd_mol_keys: which ligands have no
 // molecule, which atoms count).  The pattern is that of vina_core.h: everything is __device__ __forceinline__, arrays come in as
 // plain pointers (an LDS array stays in its address space after inlining), the __shared__ declarations and the kernels stay in

@@ -218,6 +218,10 @@ def lib():
     L.kpd_smiles_scratch_bytes.restype = C.c_int64
     L.kpd_mol_smiles.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32] + [C.c_void_p] * 4 +
                                  [C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4)
+    L.kpd_pose_rmsd_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.kpd_pose_rmsd_scratch_bytes.restype = C.c_int64
+    L.kpd_pose_rmsd.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3 +
+                                [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 7)
     L.kpd_relax_defaults.argtypes = [C.POINTER(KpdRelaxParams)]
     L.kpd_relax_defaults.restype = None
     L.kpd_relax.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
@@ -270,7 +274,7 @@ EXPORTS = [
     'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
     'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
     'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_mol_sanitize', 'kpd_mol_add_hs_scratch_bytes', 'kpd_mol_add_hs',
-    'kpd_smiles_scratch_bytes', 'kpd_mol_smiles', 'kpd_relax_defaults', 'kpd_relax',
+    'kpd_smiles_scratch_bytes', 'kpd_mol_smiles', 'kpd_pose_rmsd_scratch_bytes', 'kpd_pose_rmsd', 'kpd_relax_defaults', 'kpd_relax',
     'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score', 'kpd_vina_min_defaults', 'kpd_vina_minimize',
     'kpd_vina_dock_defaults', 'kpd_vina_dock',
 ]
@@ -1249,6 +1253,57 @@ def mol_smiles(lig_ptr: torch.Tensor, z, elements, mol: dict, san: dict, largest
             break
         cap = ptr[-1]                               # the size needed: the second call cannot miss
     return bytes(text[:min(ptr[-1], cap)].cpu().numpy()), ptr, status.cpu().tolist()
+
+
+POSE_NO_MOLECULE, POSE_MAX_NODES, POSE_NONFINITE = 1, 2, 4      # status bits of kpd_pose_rmsd
+POSE_MAX_PAIR_POSES = 64
+
+
+def pose_rmsd(lig_ptr: torch.Tensor, z, mol: dict, pos: torch.Tensor, ref_pos: Optional[torch.Tensor] = None, pairs: bool = False,
+              largest_only: bool = False, skip_h: bool = True, max_nodes: int = 65536, bond_label: Optional[torch.Tensor] = None,
+              atom_label: Optional[torch.Tensor] = None, want_map: bool = True):
+    """Symmetry-corrected RMSD between poses of a batch of perceived molecules on the GPU (kpd_pose_rmsd; include/kpd.h states the
+    rule): the minimum over the automorphisms of the bond graph of the unaligned RMSD.  `mol`: what `mol_perceive` returned, z: the
+    atomic number of every feature class; pos [K,N,3]: K poses of the whole batch; `pairs=False`: every pose against `ref_pos`
+    [N,3], `pairs=True` (K <= 64): every pose against every other; bond_label [cap_bonds] (1 .. 15) / atom_label [N] (0 .. 2^20 - 1):
+    int32 labels an automorphism must keep, None: connectivity and elements alone.  Returns a dict of device tensors: rmsd / plain
+    float64 and nodes int64, [B,K] or [B,K,K]; map [K,N] int32 (pairs=False and `want_map`); status [B] (bits POSE_*).  No host
+    synchronisation."""
+    B = _offsets(lig_ptr, 'lig_ptr')
+    _mol_fields('pose_rmsd', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'))
+    if not (isinstance(pos, torch.Tensor) and pos.dim() == 3 and pos.shape[2] == 3):
+        raise KpdError(f'pose_rmsd: pos must be [K,N,3], got {tuple(getattr(pos, "shape", ()))}')
+    pos = _dev_f32(pos, 'pos')
+    K, N, F = pos.shape[0], pos.shape[1], len(z)
+    pairs, max_nodes = bool(pairs), int(max_nodes)
+    if K < 1 or (pairs and K > POSE_MAX_PAIR_POSES) or max_nodes < 1:
+        raise KpdError(f'pose_rmsd: K={K} must be >= 1 (<= {POSE_MAX_PAIR_POSES} with pairs) and max_nodes={max_nodes} >= 1')
+    cap_bonds = mol['bonds'].numel() // 2
+    if (F < 1 or mol['elem'].numel() != N or mol['frag'].numel() != N or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B):
+        raise KpdError(f'pose_rmsd: pos {tuple(pos.shape)}, {B} ligands, {F} atomic numbers do not match the perceived molecules')
+    if not pairs:
+        if ref_pos is None:
+            raise KpdError('pose_rmsd: ref_pos is needed unless pairs=True')
+        ref_pos = _dev_f32(ref_pos, 'ref_pos')
+        if ref_pos.shape != (N, 3):
+            raise KpdError(f'pose_rmsd: ref_pos must be [{N},3], got {tuple(ref_pos.shape)}')
+    if bond_label is not None:
+        bond_label = _per_entry(bond_label, 'bond_label', cap_bonds, 'bond row')
+    if atom_label is not None:
+        atom_label = _per_entry(atom_label, 'atom_label', N, 'atom')
+    dev = pos.device
+    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
+    shape = (B, K, K) if pairs else (B, K)
+    out = dict(rmsd=torch.empty(shape, dtype=torch.float64, device=dev), plain=torch.empty(shape, dtype=torch.float64, device=dev),
+               nodes=torch.empty(shape, dtype=torch.int64, device=dev), status=torch.empty(B, dtype=torch.int32, device=dev))
+    if not pairs and want_map:
+        out['map'] = torch.empty(K, N, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib().kpd_pose_rmsd_scratch_bytes(N, K, int(pairs))), dtype=torch.uint8, device=dev)
+    check(lib().kpd_pose_rmsd(_ptr(lig_ptr), N, B, _ptr(mol['elem']), F, _ptr(zt), _ptr(mol['frag']), _ptr(mol['bonds']), _ptr(mol['bond_ptr']),
+                              cap_bonds, _ptr(mol['status']), _ptr(bond_label), _ptr(atom_label), int(bool(largest_only)), int(bool(skip_h)),
+                              None if pairs else _ptr(ref_pos), _ptr(pos), K, int(pairs), max_nodes, _ptr(out['rmsd']), _ptr(out['plain']),
+                              _ptr(out.get('map')), _ptr(out['nodes']), _ptr(out['status']), _ptr(scratch), _stream()))
+    return out
 
 
 def fp_diversity(fp: torch.Tensor, use: torch.Tensor, group_ptr: torch.Tensor):

@@ -244,6 +244,53 @@ class Molecules:
         neighbourhood radius 0 .. `radius`; all zero for a ligand without a molecule."""
         return self._keys(largest_frag, with_orders, radius, nbits)['fp']
 
+    def _pose_stack(self, pos) -> torch.Tensor:
+        """[N,3], [K,N,3] or a list of per-ligand [n_i,3] / [K,n_i,3] tensors -> [K,N,3]."""
+        if isinstance(pos, (list, tuple)):
+            if len(pos) != len(self):
+                raise hip.KpdError(f'pose_rmsd: {len(pos)} per-ligand tensors for {len(self)} ligands')
+            parts = [p if p.dim() == 3 else p[None] for p in pos]
+            pos = torch.cat(parts, dim=1) if parts else torch.zeros(1, 0, 3, device=self.lig_ptr.device)
+        if not isinstance(pos, torch.Tensor) or pos.dim() not in (2, 3) or pos.shape[-1] != 3:
+            raise hip.KpdError('pose_rmsd: pos must be [N,3], [K,N,3] or a list of per-ligand tensors')
+        return pos if pos.dim() == 3 else pos[None]
+
+    def pose_rmsd(self, pos, ref=None, largest_frag: bool = False, skip_h: bool = True, pairs: bool = False, max_nodes: int = 65536,
+                  bond_label: Optional[torch.Tensor] = None, atom_label: Optional[torch.Tensor] = None) -> 'PoseRMSD':
+        """The symmetry-corrected RMSD of poses of these molecules, on the GPU (`kpd_pose_rmsd`): the minimum over the automorphisms
+        of the bond graph of the unaligned RMSD, what upstream reads off `Chem.CalcRMS` (analysis/pocket_minimization.py), under
+        the rule of include/kpd.h; no agreement with RDKit's numbers is claimed.  A flipped phenyl ring or a carboxylate turned by
+        one step is the same pose: its value is 0 where the plain atom-by-atom number reports 1 - 2.5 A.
+        `pos`: [N,3], [K,N,3] or a list of per-ligand tensors, K poses of the whole batch; `ref`: the pose they are compared with,
+        these molecules' own `pos` by default; `pairs=True` (K <= 64): every pose against every other instead; `largest_frag`:
+        over the largest fragment alone; `skip_h`: hydrogens take no part; `bond_label` [3N] / `atom_label` [N]: int32 labels an
+        automorphism must keep (None: elements and connectivity only, so that the two Kekule patterns of a ring are one graph)."""
+        if self.lig_elements is None or self.bonds is None:
+            raise hip.KpdError('these Molecules carry no bond graph: build them with build_molecules')
+        stack = self._pose_stack(pos)
+        K = int(stack.shape[0])
+        if K < 1 or (pairs and K > hip.POSE_MAX_PAIR_POSES):
+            raise hip.KpdError(f'pose_rmsd: {K} poses; at least 1, and at most {hip.POSE_MAX_PAIR_POSES} with pairs=True')
+        if not stack.is_cuda:
+            raise hip.KpdError(f'pose_rmsd: poses must live on the GPU (got {stack.device}); there is no CPU implementation')
+        if not pairs:
+            ref = self.pos if ref is None else ref
+            if ref is None:
+                raise hip.KpdError('these Molecules carry no coordinates: pass ref')
+            ref = self._pose_stack(ref)[0]
+        dev = stack.device
+        if len(self) == 0:
+            shape = (0, K, K) if pairs else (0, K)
+            f64 = torch.zeros(shape, dtype=torch.float64, device=dev)
+            return PoseRMSD(dict(rmsd=f64, plain=f64.clone(), nodes=torch.zeros(shape, dtype=torch.int64, device=dev),
+                                 status=torch.zeros(0, dtype=torch.int32, device=dev),
+                                 **({} if pairs else dict(map=torch.zeros(K, 0, dtype=torch.int32, device=dev)))), bool(pairs))
+        mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, bond_ptr=self.bond_ptr, status=self.status)
+        z = [ATOMIC_NUMBERS.get(el, 0) for el in self.lig_elements]
+        out = hip.pose_rmsd(self.lig_ptr, z, mol, stack, None if pairs else ref, pairs=pairs, largest_only=largest_frag, skip_h=skip_h,
+                            max_nodes=max_nodes, bond_label=bond_label, atom_label=atom_label)
+        return PoseRMSD(out, bool(pairs))
+
     def set_metrics(self, group_ptr: Optional[torch.Tensor] = None, train_keys: Optional[torch.Tensor] = None,
                     connectivity_thresh: float = 0.5, radius: int = 2, nbits: int = 2048, largest_frag: bool = True,
                     with_orders: bool = True, valid_only: bool = False) -> Dict[str, object]:
@@ -488,6 +535,31 @@ class Molecules:
         return VinaDocked(self, out, pocket_types, (lo, hi))
 
 
+class PoseRMSD:
+    """What `pose_rmsd` returns, device tensors: `.rmsd` and `.plain` (the atom-by-atom number over the same atoms; rmsd <= plain)
+    float64 and `.nodes` int64 (candidates the search tried), [B,K], or [B,K,K] for pairs (symmetric, the diagonal 0); `.map`
+    [K,N] int32 (the row whose place in the pose answers each atom of the reference, -1 for an atom that took no part; None for
+    pairs); `.status` [B] (bits: 1 no molecule -- zeros and map -1 --, 2 some search stopped at max_nodes and gives an upper
+    bound, 4 a non-finite coordinate: the searches that read it give zeros)."""
+
+    def __init__(self, out: Dict[str, torch.Tensor], pairs: bool):
+        self.rmsd, self.plain, self.nodes, self.status = out['rmsd'], out['plain'], out['nodes'], out['status']
+        self.map, self.pairs = out.get('map'), pairs
+
+    def table(self) -> Dict[str, list]:
+        """lig_idx, pose (pairs: pose_i, pose_j with i < j), rmsd, plain, nodes as lists; ligands without a molecule have no row."""
+        keep = ((self.status.cpu() & hip.POSE_NO_MOLECULE) == 0).nonzero().flatten().tolist()
+        K = int(self.rmsd.shape[1])
+        rmsd, plain, nodes = self.rmsd.cpu(), self.plain.cpu(), self.nodes.cpu()
+        if self.pairs:
+            rows = [(b, i, j) for b in keep for i in range(K) for j in range(i + 1, K)]
+            return dict(lig_idx=[r[0] for r in rows], pose_i=[r[1] for r in rows], pose_j=[r[2] for r in rows],
+                        rmsd=[rmsd[r].item() for r in rows], plain=[plain[r].item() for r in rows], nodes=[int(nodes[r]) for r in rows])
+        rows = [(b, k) for b in keep for k in range(K)]
+        return dict(lig_idx=[r[0] for r in rows], pose=[r[1] for r in rows], rmsd=[rmsd[r].item() for r in rows],
+                    plain=[plain[r].item() for r in rows], nodes=[int(nodes[r]) for r in rows])
+
+
 class Sanitized:
     """What `Molecules.sanitize` returns: `.molecules` (a `Molecules` whose `order` is order_k and whose `valence` is valence_k, so
     `.sdf()`, `.keys()`, `.relax()`, `.vina_score()`, `.vina_minimize()` and `.vina_dock()` work unchanged on the Kekule orders),
@@ -538,6 +610,23 @@ class Sanitized:
         if any(s & hip.SMI_CAPACITY for s in status):
             raise hip.KpdError('smiles: text buffer too small (internal sizing error)')
         return ['' if status[b] else text[ptr[b]:ptr[b + 1]].decode('ascii') for b in range(len(status))]
+
+    def pose_rmsd(self, pos, ref=None, largest_frag: Optional[bool] = None, skip_h: bool = True, pairs: bool = False,
+                  max_nodes: int = 65536, bond_label: Optional[torch.Tensor] = None,
+                  atom_label: Optional[torch.Tensor] = None) -> 'PoseRMSD':
+        """`Molecules.pose_rmsd` on the labelled graph of the SMILES rule: by default atom_label = 2 h + aromatic and bond_label = 4
+        on an aromatic bond, else the Kekule order, so an automorphism keeps hydrogen counts and bond orders but does not depend
+        on which Kekule pattern the ring was given.  `largest_frag`: None, the scope these molecules were sanitised with."""
+        largest = self.largest_frag if largest_frag is None else bool(largest_frag)
+        if self.largest_frag and not largest:
+            raise hip.KpdError('pose_rmsd(largest_frag=False) needs molecules sanitised over every atom: sanitize(largest_frag=False)')
+        m = self.molecules
+        if atom_label is None:
+            atom_label = (2 * self.h.clamp(min=0) + self.aromatic_atoms.to(torch.int32)).to(torch.int32)
+        if bond_label is None:      # rows outside the sanitised scope or beyond bond_ptr[B] carry no order: any label in range will do
+            bond_label = torch.where(self.aromatic_bonds, torch.full_like(m.order, 4), m.order.clamp(1, 3)).to(torch.int32)
+        return m.pose_rmsd(pos, ref, largest_frag=largest, skip_h=skip_h, pairs=pairs, max_nodes=max_nodes, bond_label=bond_label,
+                           atom_label=atom_label)
 
     def unique(self, kekule: bool = False, largest_frag: Optional[bool] = None) -> List[int]:
         """The index of the first ligand of every distinct string of `smiles(kekule, largest_frag)`, ascending; ligands without a
@@ -698,6 +787,35 @@ class VinaDocked:
         blocks = [self.mode(k).sdf(strict=False) for k in range(max(found, default=0))]
         return [''.join(blocks[k][b] for k in range(found[b])) for b in range(len(found))]
 
+    def sym_rmsd(self, **kw) -> torch.Tensor:
+        """[B,n_modes] float64: the symmetry-corrected RMSD (`Molecules.pose_rmsd`, whose keywords pass through) of every mode to
+        the input pose, 0 for a mode that does not exist.  `report[:, :, 4]`, the atom-by-atom number, is never smaller."""
+        r = self._mols.pose_rmsd(self._pos, **kw).rmsd
+        exists = torch.arange(self.n_modes, device=r.device)[None, :] < self.n_found[:, None]
+        return torch.where(exists, r, torch.zeros_like(r))
+
+    def mode_rmsd(self, **kw) -> torch.Tensor:
+        """[B,n_modes,n_modes] float64: the symmetry-corrected RMSD between the modes of every ligand (symmetric, the diagonal 0);
+        0 where either mode does not exist."""
+        r = self._mols.pose_rmsd(self._pos, pairs=True, **kw).rmsd
+        exists = torch.arange(self.n_modes, device=r.device)[None, :] < self.n_found[:, None]
+        return torch.where(exists[:, :, None] & exists[:, None, :], r, torch.zeros_like(r))
+
+    def distinct_modes(self, min_rmsd: float = 1.0, **kw) -> List[List[int]]:
+        """Per ligand the modes that stay when the "Modes" rule of include/kpd.h is walked over the found modes in rank order with
+        the symmetry-corrected RMSD: a mode is kept iff its `mode_rmsd` to every mode kept before is >= `min_rmsd`.  The modes
+        `vina_dock` itself returned were told apart by the atom-by-atom number, so a pose with a flipped phenyl ring or a turned
+        carboxylate can be among them twice; this drops the repeat.  A host walk over the [B,n_modes,n_modes] matrix."""
+        r, found = self.mode_rmsd(**kw).cpu(), self.n_found.tolist()
+        out = []
+        for b, n in enumerate(found):
+            kept: List[int] = []
+            for k in range(n):
+                if all(float(r[b, k, j]) >= float(min_rmsd) for j in kept):
+                    kept.append(k)
+            out.append(kept)
+        return out
+
     def table(self) -> Dict[str, list]:
         """lig_idx, mode, score, rmsd_input, chain, as lists: one row per found mode, ligands in batch order, modes in rank order."""
         found, rep = self.n_found.tolist(), self.report.cpu()
@@ -718,6 +836,12 @@ class VinaMinimized:
         self.molecules = Molecules(mols.lig_ptr, mols.summary, mols.status, mols.elem, mols.valence, mols.frag, mols.bonds, mols.order,
                                    mols.bond_ptr, pos, mols.lig_elements, mols._max_atoms)
         self.report, self.status, self.pocket_types, self._sizes = report, status, pocket_types, mols._sizes
+        self._input = mols
+
+    def sym_rmsd(self, **kw) -> torch.Tensor:
+        """[B] float64: the symmetry-corrected RMSD (`Molecules.pose_rmsd`, whose keywords pass through) of the minimised pose to
+        the input pose; `report[:, 8]`, the atom-by-atom number, is never smaller.  0 for a ligand without a molecule."""
+        return self._input.pose_rmsd(self.molecules.pos, **kw).rmsd[:, 0]
 
     @property
     def pos(self) -> List[torch.Tensor]:
@@ -744,6 +868,13 @@ class Relaxed:
         self.molecules = Molecules(mols.lig_ptr, mols.summary, mols.status, mols.elem, mols.valence, mols.frag, mols.bonds, mols.order,
                                    mols.bond_ptr, pos, mols.lig_elements, mols._max_atoms)
         self.report, self.status, self._sizes = report, status, mols._sizes
+        self._input = mols
+
+    def sym_rmsd(self, **kw) -> torch.Tensor:
+        """[B] float64: the symmetry-corrected RMSD (`Molecules.pose_rmsd`, whose keywords pass through) of the relaxed pose to the
+        input pose, upstream's `Chem.CalcRMS` column under the rule of include/kpd.h; `report[:, 2]`, the atom-by-atom number, is
+        never smaller.  0 for a ligand without a molecule."""
+        return self._input.pose_rmsd(self.molecules.pos, **kw).rmsd[:, 0]
 
     @property
     def pos(self) -> List[torch.Tensor]:
