@@ -266,8 +266,8 @@ k_mol_add_hs(const float *__restrict__ pos, const int *__restrict__ lig_ptr, int
         nS = sc.nS;
         n_frags = sc.n_frag;
         // the bond rows: i < j inside the ligand, order_k 1 .. 3, in (i, j) order (so none twice); neighbour entries inside S
-        mol_bond_graph<true>(bond_ij, order_k, p0, en.p1, a0, n, lane, inS, (unsigned *)nullptr, 0, deg, upto, nb, &bad,
-                             [](int, int o) { return (unsigned)o << 8; });
+        mol_bond_graph<true>(bond_ij, p0, en.p1, a0, n, lane, inS, (unsigned *)nullptr, 0, deg, upto, nb, &bad,
+                             [order_k](int k) { return order_k[k]; }, 3, [](int, int o) { return (unsigned)o << 8; });
         __syncthreads();
         ok = !bad && nS > 0;
     }

@@ -7,7 +7,8 @@
 // vina_min.hip takes the same front end; what vina.hip and vina_min.hip share beyond it (typing, pair terms, staging, bond graph,
 // graph walk) is in vina_core.h.  The wave butterflies (wave_sum, the fp64 wave_max) serve relax.hip and both of them.
 // molset.hip, sanitize.hip and hydrogens.hip share "one wave takes one perceived ligand and builds its graph in the scope S"
-// through molgraph_core.h, which stands on this file; the int wave_max, the 64-bit wave_sum and wave_exclusive serve them and molecule.hip.
+// through molgraph_core.h, which stands on this file; the int wave_max, the 64-bit wave_sum and wave_exclusive serve them and molecule.hip,
+// the two wave minima smiles.hip.
 #pragma once
 #include <algorithm>
 
@@ -88,6 +89,15 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {  
 __device__ __forceinline__ int wave_max(int v) {
 #pragma unroll
     for (int off = 32; off; off >>= 1) v = max(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ int wave_min_int(int v) { return -wave_max(-v); }
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        const unsigned long long t = __shfl_xor(v, off);
+        v = t < v ? t : v;
+    }
     return v;
 }
 // exclusive prefix of v over the lanes of the wave; total = the wave's sum

@@ -1,7 +1,7 @@
 // "One wave takes one perceived ligand and builds its bond graph in the scope S", stated once for k_mol_keys (molset.hip),
-// k_mol_sanitize (sanitize.hip), k_mol_add_hs (hydrogens.hip), k_smiles_build (smiles.hip, the unordered row contract) and k_pose_rmsd
-// (pose_rmsd.hip: entry check, staging and scope; its bond loop carries labels, not orders): the entry check, the atom staging, the scope, the bond loop
-// with its two row contracts, and the membership test.  include/kpd.h states the rule (kpd_mol_keys: which ligands have no
+// k_mol_sanitize (sanitize.hip), k_mol_add_hs (hydrogens.hip), k_smiles_build (smiles.hip) and k_pose_rmsd (pose_rmsd.hip; the last
+// two under the unordered row contract, pose_rmsd with its labels for the orders): the entry check, the atom staging, the scope, the bond
+// loop with its two row contracts, and the membership test.  include/kpd.h states the rule (kpd_mol_keys: which ligands have no
 // molecule, which atoms count).  The pattern is that of vina_core.h: everything is __device__ __forceinline__, arrays come in as
 // plain pointers (an LDS array stays in its address space after inlining), the __shared__ declarations and the kernels stay in
 // their files, and what one kernel alone does with an atom or a bond comes in as a callable that is inlined at the call site.
@@ -104,22 +104,24 @@ __device__ __forceinline__ MolScope mol_scope(const int *fsize, const int (&fr_o
 }
 
 // ---- the bond loop ---------------------------------------------------------------------------------------------------------------
-// Bonds [p0, p1), a lane per row: both ends inside the ligand, an order in 1 .. 3; a bond with both ends in S takes a slot in each
-// end's neighbour list, nb[i * MOL_DEG + slot] = (NB)(j | common(local row, order)), and a seventh neighbour is refused.  Whatever
+// Bonds [p0, p1), a lane per row: both ends inside the ligand, label(row) in 1 .. max_label (the order, 1 .. 3; k_pose_rmsd: the
+// caller's label, 1 .. 15, or 1 without any); a bond with both ends in S takes a slot in each end's neighbour list,
+// nb[i * MOL_DEG + slot] = (NB)(j | common(local row, label)), and a seventh neighbour is refused.  Whatever
 // is refused raises *bad.  deg zeroed by the caller, a barrier before and after this.  The two row contracts:
-// ORDERED = false (sanitize; keys has this form written out in molset.hip, where the call cost time: profiles/molgraph_core.md):
+// ORDERED = false (sanitize, smiles, pose_rmsd; keys has this form written out in molset.hip, where the call cost time:
+//   profiles/molgraph_core.md):
 //   i != j, and a bond listed twice is found through the bit matrix adj (`stride` words per row, zeroed by the caller).  The first
 //   mark goes on the (low, high) word whichever way round the bond is listed, so two lanes that meet (i, j) and (j, i) in the same
 //   pass cannot both read "not yet"; upto is not touched.
 // ORDERED = true (add_hs): i < j and the rows strictly ascending in (i, j), so none comes twice and adj is not touched; upto[i]
 //   (zeroed by the caller) counts the rows that start at i, in S or not.
-template <bool ORDERED, class NB, class Common>
-__device__ __forceinline__ void mol_bond_graph(const int *__restrict__ bond_ij, const int *__restrict__ order, int p0, int p1, int a0, int n,
-                                               int lane, const unsigned *inS, unsigned *adj, int stride, int *deg, int *upto, NB *nb,
-                                               int *bad, Common common) {
+template <bool ORDERED, class NB, class Label, class Common>
+__device__ __forceinline__ void mol_bond_graph(const int *__restrict__ bond_ij, int p0, int p1, int a0, int n, int lane, const unsigned *inS,
+                                               unsigned *adj, int stride, int *deg, int *upto, NB *nb, int *bad, Label label, int max_label,
+                                               Common common) {
     for (int k = p0 + lane; k < p1; k += 64) {
-        const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0, o = order[k];
-        bool good = (ORDERED ? i >= 0 && i < j && j < n : i >= 0 && i < n && j >= 0 && j < n && i != j) && o >= 1 && o <= 3;
+        const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0, o = label(k);
+        bool good = (ORDERED ? i >= 0 && i < j && j < n : i >= 0 && i < n && j >= 0 && j < n && i != j) && o >= 1 && o <= max_label;
         if (ORDERED && good && k > p0) {
             const int pi = bond_ij[(size_t)(k - 1) * 2] - a0, pj = bond_ij[(size_t)(k - 1) * 2 + 1] - a0;
             good = pi < i || (pi == i && pj < j);

@@ -9,40 +9,18 @@
 // in passes of 64.  k_fp_diversity: one workgroup per group, a thread per pair, fp64 partial sums reduced by a fixed tree.
 // The front end of k_mol_keys (entry check, atom staging, the scope S, the membership test) is that of molgraph_core.h, shared
 // with k_mol_sanitize and k_mol_add_hs; the bond loop is the header's unordered form written out here, the one piece whose call
-// cost time.  The header's fp64 vectors are not used here (no -ffp-contract=off).
+// cost time.  The invariant (mix, the constants, the seed's BFS, the refinement step and its loop) is that of molrefine_core.h,
+// shared with k_smiles_build and k_pose_rmsd.  The header's fp64 vectors are not used here (no -ffp-contract=off).
 #include "common.h"
 #include "molgraph_core.h"
+#include "molrefine_core.h"
 
 namespace kpd {
 
-typedef unsigned long long u64;
-
-constexpr u64 MS_K1 = 0x9E3779B97F4A7C15ull, MS_K2 = 0xC2B2AE3D27D4EB4Full, MS_K3 = 0x165667B19E3779F9ull;
-constexpr int MS_ROW = MOL_W + 1;       // padded adjacency row: in the BFS every lane walks rows of its own
-constexpr int MS_FAR = 65535;           // d(a, b) of an atom that cannot be reached
 constexpr int MS_FP_WORDS = 128;        // nbits <= 4096
 
 enum : int { KEY_NO_MOLECULE = 1 };
 enum : int { DIV_BAD_SEGMENT = 1 };
-
-__device__ __forceinline__ u64 mix(u64 x) {                     // the splitmix64 finaliser
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
-// one refinement step of atom a: mix(K1 x[a] + sum over its bonds of mix(x[b] + l K2)); a neighbour entry is b | l << 8
-__device__ __forceinline__ u64 refine(const u64 *x, const unsigned short *nbr, int deg, int a) {
-    u64 s = MS_K1 * x[a];
-    for (int k = 0; k < deg; ++k) {
-        const unsigned e = nbr[a * MOL_DEG + k];
-        s += mix(x[e & 0xffu] + (u64)(e >> 8) * MS_K2);
-    }
-    return mix(s);
-}
 
 __device__ __forceinline__ void set_fp_bit(unsigned *row, u64 h, int nwords) {
     const unsigned bit = (unsigned)h & (unsigned)(nwords * 32 - 1);
@@ -56,7 +34,7 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
            const int *__restrict__ bond_ptr, int cap_bonds, const int *__restrict__ mol_status, int largest_only, int with_orders,
            int radius, int nwords, long long *__restrict__ key, unsigned *__restrict__ fp, long long *__restrict__ atom_inv,
            int *__restrict__ status) {
-    __shared__ unsigned A[MOL_MAX * MS_ROW];        // bonded, both ends in S
+    __shared__ unsigned A[MOL_MAX * MR_ROW];        // bonded, both ends in S
     __shared__ u64 inv[2][MOL_MAX];
     __shared__ u64 zk[MOL_MAX];                     // Z K2
     __shared__ int zv[MOL_MAX];                     // Z
@@ -77,7 +55,7 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
             const int a = lane + 64 * k;
             deg[a] = 0;
             fsize[a] = 0;
-            for (int w = 0; w < MS_ROW; ++w) A[a * MS_ROW + w] = 0;
+            for (int w = 0; w < MR_ROW; ++w) A[a * MR_ROW + w] = 0;
         }
         for (int w = lane; w < MS_FP_WORDS; w += 64) row[w] = 0;
         if (lane == 0) bad = 0;
@@ -86,7 +64,7 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
         int fr_of[MOL_K];
         mol_stage_atoms(elem, F, zs, frag, a0, n, lane, fsize, &bad, fr_of, [&](int, int a, size_t, int z) {
             zv[a] = z;
-            zk[a] = (u64)(long long)z * MS_K2;
+            zk[a] = (u64)(long long)z * MR_K2;
             return true;
         });
         __syncthreads();
@@ -105,8 +83,8 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
                 if (!both_in_scope(inS, i, j)) continue;
                 const unsigned l = with_orders ? (unsigned)o : 1u;
                 const int lo = min(i, j), hi = max(i, j);   // the first mark is on one word whichever way round the bond is listed
-                const unsigned was = atomicOr(&A[lo * MS_ROW + (hi >> 5)], 1u << (hi & 31));
-                atomicOr(&A[hi * MS_ROW + (lo >> 5)], 1u << (lo & 31));
+                const unsigned was = atomicOr(&A[lo * MR_ROW + (hi >> 5)], 1u << (hi & 31));
+                atomicOr(&A[hi * MR_ROW + (lo >> 5)], 1u << (lo & 31));
                 const int si = atomicAdd(&deg[i], 1), sj = atomicAdd(&deg[j], 1);
                 if (((was >> (hi & 31)) & 1u) || si >= MOL_DEG || sj >= MOL_DEG) {          // a bond twice, or a seventh neighbour
                     atomicOr(&bad, 1);
@@ -135,7 +113,7 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
             for (int k = 0; k < MOL_K; ++k) {
                 const int a = lane + 64 * k;
                 if (!in[k]) continue;
-                const u64 f0 = mix((u64)(long long)zv[a] + (u64)dg[k] * MS_K3);
+                const u64 f0 = mr_mix((u64)(long long)zv[a] + (u64)dg[k] * MR_K3);
                 inv[0][a] = f0;
                 set_fp_bit(row, f0, nwords);
             }
@@ -145,7 +123,7 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
                 for (int k = 0; k < MOL_K; ++k) {
                     const int a = lane + 64 * k;
                     if (!in[k]) continue;
-                    const u64 f = refine(inv[cur], nbr, dg[k], a);
+                    const u64 f = mr_refine(inv[cur], nbr, dg[k], a);
                     inv[cur ^ 1][a] = f;
                     set_fp_bit(row, f, nwords);
                 }
@@ -153,78 +131,26 @@ k_mol_keys(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict__
                 cur ^= 1;
             }
             for (int w = lane; w < nwords; w += 64) out_row[w] = row[w];
-            // key seeds: every other atom of S by element and distance, a BFS per source atom over bitset frontiers
-            // (inv is free: the barrier after the last fingerprint step is behind every lane, and the BFS reads none of it)
+            // key seeds: every other atom of S by element and distance (mr_seed_sum), then |S| steps: a difference has reached every
+            // atom it can reach (inv is free: the barrier after the last fingerprint step is behind every lane, and the BFS reads none of it)
+#pragma unroll
             for (int k = 0; k < MOL_K; ++k) {
                 const int a = lane + 64 * k;
-                if (a >= n || !in_scope(inS, a)) continue;
-                unsigned vis[MOL_W], front[MOL_W], next[MOL_W];
-#pragma unroll
-                for (int w = 0; w < MOL_W; ++w) vis[w] = front[w] = (w == (a >> 5)) ? 1u << (a & 31) : 0u;
-                u64 sum = 0;
-                for (int d = 1;; ++d) {
-#pragma unroll
-                    for (int w = 0; w < MOL_W; ++w) next[w] = 0;
-#pragma unroll
-                    for (int w = 0; w < MOL_W; ++w) {
-                        unsigned bits = front[w];
-                        while (bits) {
-                            const int j = 32 * w + __ffs(bits) - 1;
-                            bits &= bits - 1;
-#pragma unroll
-                            for (int v = 0; v < MOL_W; ++v) next[v] |= A[j * MS_ROW + v];
-                        }
-                    }
-                    unsigned any = 0;
-#pragma unroll
-                    for (int w = 0; w < MOL_W; ++w) {
-                        next[w] &= ~vis[w];
-                        any |= next[w];
-                    }
-                    if (!any) break;
-#pragma unroll
-                    for (int w = 0; w < MOL_W; ++w) {
-                        unsigned bits = next[w];
-                        while (bits) {
-                            sum += mix(zk[32 * w + __ffs(bits) - 1] + (u64)d);
-                            bits &= bits - 1;
-                        }
-                        vis[w] |= next[w];
-                        front[w] = next[w];
-                    }
-                }
-#pragma unroll
-                for (int w = 0; w < MOL_W; ++w) {
-                    unsigned bits = inS[w] & ~vis[w];
-                    while (bits) {
-                        sum += mix(zk[32 * w + __ffs(bits) - 1] + (u64)MS_FAR);
-                        bits &= bits - 1;
-                    }
-                }
-                inv[0][a] = mix((u64)(long long)zv[a] + (u64)deg[a] * MS_K3 + MS_K1 * sum);
+                if (in[k]) inv[0][a] = mr_mix((u64)(long long)zv[a] + (u64)dg[k] * MR_K3 + MR_K1 * mr_seed_sum(A, zk, inS, a));
             }
             __syncthreads();
-            cur = 0;
-            for (int r = 1; r <= nS; ++r) {         // |S| steps: a difference has reached every atom it can reach
-#pragma unroll
-                for (int k = 0; k < MOL_K; ++k) {
-                    const int a = lane + 64 * k;
-                    if (in[k]) inv[cur ^ 1][a] = refine(inv[cur], nbr, dg[k], a);
-                }
-                __syncthreads();
-                cur ^= 1;
-            }
+            cur = mr_refine_steps(&inv[0][0], nbr, in, dg, lane, 0, nS);
             u64 total = 0;
 #pragma unroll
             for (int k = 0; k < MOL_K; ++k) {
                 const int a = lane + 64 * k;
                 if (!in[k]) continue;
-                total += mix(inv[cur][a]);
+                total += mr_mix(inv[cur][a]);
                 if (atom_inv) atom_inv[a0 + a] = (long long)inv[cur][a];
             }
             total = wave_sum(total);
             if (lane == 0) {
-                key[b] = (long long)mix((u64)nS + (u64)m * MS_K3 + MS_K1 * total);
+                key[b] = (long long)mr_mix((u64)nS + (u64)m * MR_K3 + MR_K1 * total);
                 status[b] = 0;
             }
             return;

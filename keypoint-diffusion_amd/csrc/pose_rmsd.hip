@@ -2,9 +2,10 @@
 // graph of the unaligned RMSD, what upstream reads off Chem.CalcRMS(mol1, mol2) (analysis/pocket_minimization.py:21).  RDKit's
 // substructure matcher cannot be restated: include/kpd.h defines the search down to the order of every candidate, and
 // tests/pose_rmsd_ref.py restates it.  No agreement with RDKit's numbers is claimed.
-// k_pose_rmsd: one wave per ligand.  The front end (entry check, atom staging, the scope S) is that of molgraph_core.h; the bond
-// loop is its unordered form with the caller's labels (1 .. 15, or none) in place of the orders 1 .. 3, so it is written out
-// here.  Seeds, refinement (molrefine_core.h), the classes and the sort of the neighbour lists run across the lanes; the source
+// k_pose_rmsd: one wave per ligand.  The front end (entry check, atom staging, the scope S, the unordered bond loop with the
+// caller's labels, 1 .. 15 or none, in place of the orders 1 .. 3) is that of molgraph_core.h.  The seed sum, the refinement step, the
+// classes (a rank without tie-break) and the sort of the neighbour lists are those of molrefine_core.h and run across the lanes;
+// only the loop of |S| steps around the refinement step is written out here, the one piece whose call cost time.  The source
 // order is one breadth-first walk on lane 0.  Then every lane takes searches of its own, strided over the K poses (or the
 // K (K - 1) / 2 pairs): the graph, the classes and the source order are shared in LDS, the images of a lane's search and its
 // 256-bit "taken" mask lie in LDS over the dead arrays of the refinement, its running sums s_t in the scratch buffer (see
@@ -36,7 +37,7 @@ k_pose_rmsd(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict_
             int *__restrict__ status, double *__restrict__ stack) {
     // buf, first life: x [2][MOL_MAX] and zk [MOL_MAX] (64-bit), the bit matrix A [MOL_MAX * MR_ROW]; second life, behind the
     // barrier after the source order: img [MOL_MAX][64] bytes (the image of u_t in the search of a lane) and taken [MOL_W][64]
-    __shared__ mr_u64 buf[MOL_MAX * 8 + MOL_W * 32];
+    __shared__ u64 buf[MOL_MAX * 8 + MOL_W * 32];
     __shared__ long long av[MOL_MAX];               // A(a) = Z + 256 atom_label
     __shared__ int deg[MOL_MAX];
     __shared__ int fsize[MOL_MAX];
@@ -47,11 +48,11 @@ k_pose_rmsd(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict_
     __shared__ unsigned char ord[MOL_MAX];          // u_t
     __shared__ unsigned inS[MOL_W];
     __shared__ int bad;
-    mr_u64 *const x = buf, *const zk = buf + 2 * MOL_MAX;
+    u64 *const x = buf, *const zk = buf + 2 * MOL_MAX;
     unsigned *const A = reinterpret_cast<unsigned *>(buf + 3 * MOL_MAX);
     unsigned char *const img = reinterpret_cast<unsigned char *>(buf);
     unsigned *const taken = reinterpret_cast<unsigned *>(buf + MOL_MAX * 8);
-    static_assert(3 * MOL_MAX * 8 + MOL_MAX * MR_ROW * 4 <= sizeof(mr_u64) * (MOL_MAX * 8 + MOL_W * 32), "the first life fits in buf");
+    static_assert(3 * MOL_MAX * 8 + MOL_MAX * MR_ROW * 4 <= sizeof(u64) * (MOL_MAX * 8 + MOL_W * 32), "the first life fits in buf");
 
     const int b = blockIdx.x, lane = threadIdx.x;
     const MolEntry en = mol_entry(lig_ptr, b, n_atoms, bond_ptr, cap_bonds, mol_status);
@@ -75,7 +76,7 @@ k_pose_rmsd(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict_
             const int l = atom_label ? atom_label[g] : 0;
             if (l < 0 || l > PR_MAX_ATOM_LABEL) return false;
             av[a] = (long long)z + 256ll * l;
-            zk[a] = (mr_u64)av[a] * MR_K2;
+            zk[a] = (u64)av[a] * MR_K2;
             is_h[k] = z == 1;
             return true;
         });
@@ -97,25 +98,10 @@ k_pose_rmsd(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict_
                 }
                 __syncthreads();
             }
-            // bonds with both ends in S: mol_bond_graph<false> of molgraph_core.h with L in 1 .. 15 (1 without bond_label) for the order
-            for (int k = en.p0 + lane; k < en.p1; k += 64) {
-                const int i = bond_ij[(size_t)k * 2] - a0, j = bond_ij[(size_t)k * 2 + 1] - a0, l = bond_label ? bond_label[k] : 1;
-                if (i < 0 || i >= n || j < 0 || j >= n || i == j || l < 1 || l > PR_MAX_BOND_LABEL) {
-                    atomicOr(&bad, 1);
-                    continue;
-                }
-                if (!both_in_scope(inS, i, j)) continue;
-                const int lo = min(i, j), hi = max(i, j);   // the first mark is on one word whichever way round the bond is listed
-                const unsigned was = atomicOr(&A[lo * MR_ROW + (hi >> 5)], 1u << (hi & 31));
-                atomicOr(&A[hi * MR_ROW + (lo >> 5)], 1u << (lo & 31));
-                const int si = atomicAdd(&deg[i], 1), sj = atomicAdd(&deg[j], 1);
-                if (((was >> (hi & 31)) & 1u) || si >= MOL_DEG || sj >= MOL_DEG) {          // a bond twice, or a seventh neighbour
-                    atomicOr(&bad, 1);
-                    continue;
-                }
-                nb[i * MOL_DEG + si] = (unsigned short)((unsigned)j | (unsigned)l << 8);
-                nb[j * MOL_DEG + sj] = (unsigned short)((unsigned)i | (unsigned)l << 8);
-            }
+            // bonds with both ends in S: the unordered row contract with L in 1 .. 15 (1 without bond_label) for the order
+            mol_bond_graph<false>(bond_ij, en.p0, en.p1, a0, n, lane, inS, A, MR_ROW, deg, (int *)nullptr, nb, &bad,
+                                  [bond_label](int k) { return bond_label ? bond_label[k] : 1; }, PR_MAX_BOND_LABEL,
+                                  [](int, int l) { return (unsigned)l << 8; });
             __syncthreads();
             ok = !bad && nS > 0;
         }
@@ -132,11 +118,13 @@ k_pose_rmsd(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict_
         const int a = lane + 64 * k;
         in[k] = in_scope(inS, a);
         dg[k] = in[k] ? deg[a] : 0;
-        if (in[k]) x[a] = mr_mix((mr_u64)av[a] + (mr_u64)dg[k] * MR_K3 + MR_K1 * mr_seed_sum(A, zk, inS, a));
+        if (in[k]) x[a] = mr_mix((u64)av[a] + (u64)dg[k] * MR_K3 + MR_K1 * mr_seed_sum(A, zk, inS, a));
     }
     __syncthreads();
+    // |S| steps: a difference has reached every atom it can reach.  This is mr_refine_steps of molrefine_core.h written out: calling
+    // it here put the kernel outside its time bound (profiles/molrefine_core.md)
     int cur = 0;
-    for (int r = 1; r <= nS; ++r) {                 // |S| steps: a difference has reached every atom it can reach
+    for (int r = 1; r <= nS; ++r) {
 #pragma unroll
         for (int k = 0; k < MOL_K; ++k) {
             const int a = lane + 64 * k;
@@ -146,30 +134,13 @@ k_pose_rmsd(const int *__restrict__ lig_ptr, int n_atoms, const int *__restrict_
         cur ^= 1;
     }
     {
-        mr_u64 xa[MOL_K];
         int less[MOL_K];
-#pragma unroll
-        for (int k = 0; k < MOL_K; ++k) {
-            xa[k] = in[k] ? x[cur * MOL_MAX + lane + 64 * k] : 0;
-            less[k] = 0;
-        }
-        for (int c = 0; c < n; ++c) {
-            if (!in_scope(inS, c)) continue;        // wave-uniform
-            const mr_u64 xc = x[cur * MOL_MAX + c];
-#pragma unroll
-            for (int k = 0; k < MOL_K; ++k) less[k] += xc < xa[k];
-        }
+        mr_rank<false>(x + cur * MOL_MAX, inS, in, n, lane, less);
 #pragma unroll
         for (int k = 0; k < MOL_K; ++k) {
             if (!in[k]) continue;
             cls[lane + 64 * k] = (unsigned short)less[k];
-            unsigned short *row = nb + (lane + 64 * k) * MOL_DEG;      // neighbours in ascending index
-            for (int s = 1; s < dg[k]; ++s) {
-                const unsigned short e = row[s];
-                int t = s;
-                for (; t > 0 && (row[t - 1] & 0xffu) > (e & 0xffu); --t) row[t] = row[t - 1];
-                row[t] = e;
-            }
+            mr_sort_row(nb + (lane + 64 * k) * MOL_DEG, dg[k], [](unsigned e) { return e & 0xffu; });        // neighbours in ascending index
         }
     }
     __syncthreads();

@@ -192,8 +192,8 @@ k_mol_sanitize(const float *__restrict__ pos, const int *__restrict__ lig_ptr, i
         nS = sc.nS;
         if (!largest_only) n_frag = sc.n_frag;
         // bonds with both ends in S: adjacency bits and neighbour entries
-        mol_bond_graph<false>(bond_ij, bond_order, p0, p1, a0, n, lane, inS, adj, MOL_W, deg, (int *)nullptr, nb, &bad,
-                              [](int row, int o) { return (unsigned)o << 8 | (unsigned)row << 10; });
+        mol_bond_graph<false>(bond_ij, p0, p1, a0, n, lane, inS, adj, MOL_W, deg, (int *)nullptr, nb, &bad,
+                              [bond_order](int k) { return bond_order[k]; }, 3, [](int row, int o) { return (unsigned)o << 8 | (unsigned)row << 10; });
         __syncthreads();
         ok = !bad && nS > 0;
     }

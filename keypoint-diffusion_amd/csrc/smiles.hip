@@ -3,60 +3,27 @@
 // RDKit's canonicalisation cannot be restated: include/kpd.h defines the rule down to the order of every choice, and
 // tests/smiles_ref.py restates it.  NOT RDKit's canonical SMILES.
 // k_smiles_build: one wave per ligand, everything in LDS.  The front end (entry check, atom staging, the scope S, the unordered
-// bond loop) is that of molgraph_core.h, shared with k_mol_keys, k_mol_sanitize and k_mol_add_hs.  Seeds (a BFS per source atom
-// over bitset frontiers), refinement, the census of equal values and the tie-breaking loop run across the lanes, as do the sort of
+// bond loop) is that of molgraph_core.h, shared with k_mol_keys, k_mol_sanitize, k_mol_add_hs and k_pose_rmsd.  Seeds,
+// refinement, the census of equal values and the tie-breaking loop run across the lanes, as do the ranks, the sort of
 // the neighbour lists, the start atom of every fragment and the formatting of the tokens; the depth-first walk and the numbering
 // of the ring closures are serial and stay on lane 0, with nothing but the order, the branch marks and the closure numbers on it.
 // The bytes of a ligand go to scratch (at most SM_BYTES per atom, at its first atom's row), its length to the library's one
 // exclusive scan, and k_smiles_copy moves the bytes to their place: three launches whatever B is, nothing is computed twice.
-// The seed and refinement steps are those of k_mol_keys (molset.hip) with the labels of the sanitised graph; they are written out
-// here, molset.hip is not touched.  Integer arithmetic only.
+// The seed and refinement steps are those of k_mol_keys with the labels of the sanitised graph: molrefine_core.h states them once
+// (with the loop of n steps, the rank and the sort of a neighbour row), shared with k_mol_keys and k_pose_rmsd.  Integer arithmetic only.
 #include "common.h"
 #include "engine.h"
 #include "molgraph_core.h"
+#include "molrefine_core.h"
 #include "scan_core.h"
 
 namespace kpd {
 
-typedef unsigned long long u64;
-
-constexpr u64 SM_K1 = 0x9E3779B97F4A7C15ull, SM_K2 = 0xC2B2AE3D27D4EB4Full, SM_K3 = 0x165667B19E3779F9ull;
-constexpr int SM_ROW = MOL_W + 1;       // padded adjacency row: in the BFS every lane walks rows of its own
-constexpr int SM_FAR = 65535;           // d(a, b) of an atom that cannot be reached
 constexpr int SM_BYTES = 36;            // of text per atom of S, at most: '.' or '(', a bond, "[XxxxHn]", six closures "=%nn", ')'
 constexpr int SM_MAX_H = 9, SM_MAX_CLOSURE = 99;
 constexpr unsigned short SM_NONE = 0xffff;
 
 enum : int { SMI_NO_MOLECULE = 1, SMI_EXHAUSTED = 2, SMI_CAPACITY = 4 };
-
-__device__ __forceinline__ u64 sm_mix(u64 x) {                  // the splitmix64 finaliser
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
-// one refinement step of atom a: mix(K1 x[a] + sum over its bonds of mix(x[b] + l K2)); a neighbour entry is b | l << 8
-__device__ __forceinline__ u64 sm_refine(const u64 *x, const unsigned short *nb, int deg, int a) {
-    u64 s = SM_K1 * x[a];
-    for (int k = 0; k < deg; ++k) {
-        const unsigned e = nb[a * MOL_DEG + k];
-        s += sm_mix(x[e & 0xffu] + (u64)(e >> 8) * SM_K2);
-    }
-    return sm_mix(s);
-}
-
-__device__ __forceinline__ u64 wave_min_u64(u64 v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) {
-        const u64 t = __shfl_xor(v, off);
-        v = t < v ? t : v;
-    }
-    return v;
-}
-__device__ __forceinline__ int wave_min_int(int v) { return -wave_max(-v); }
 
 // the smallest normal valence of the organic subset, 0 for every other element; v: the next ones (0 = none)
 __device__ __forceinline__ int sm_valences(int z, int &v1, int &v2) {
@@ -131,8 +98,8 @@ k_smiles_build(const int *__restrict__ lig_ptr, int n_atoms, const int *__restri
                const int *__restrict__ atom_flags, int largest_only, int aromatic, char *__restrict__ bytes, long long *__restrict__ len,
                int *__restrict__ st_out) {
     // A serves the BFS of the seeds and is dead after them: the arrays of the ranking, the walk and the tokens lie over it
-    // (SM_ROW * 4 = 36 bytes per atom, exactly what they take), so the workgroup stays at 22 KB and seven fit a CU
-    __shared__ unsigned A[MOL_MAX * SM_ROW];        // bonded, both ends in S
+    // (MR_ROW * 4 = 36 bytes per atom, exactly what they take), so the workgroup stays at 22 KB and seven fit a CU
+    __shared__ unsigned A[MOL_MAX * MR_ROW];        // bonded, both ends in S
     __shared__ u64 x[2][MOL_MAX];
     __shared__ u64 zk[MOL_MAX];                     // Z K2
     __shared__ int zv[MOL_MAX];                     // Z
@@ -149,7 +116,7 @@ k_smiles_build(const int *__restrict__ lig_ptr, int n_atoms, const int *__restri
     unsigned char *const number = reinterpret_cast<unsigned char *>(off + MOL_MAX);    // the closure number a bond took where it opened
     unsigned char *const by_rank = number + MOL_MAX * MOL_DEG, *const ord = by_rank + MOL_MAX, *const cursor = ord + MOL_MAX,
                         *const paren = cursor + MOL_MAX, *const psym = paren + MOL_MAX, *const nent = psym + MOL_MAX;
-    static_assert(MOL_DEG * 2 + 3 * 2 + 2 + 4 + MOL_DEG + 6 == SM_ROW * 4, "the arrays over A fill it exactly");
+    static_assert(MOL_DEG * 2 + 3 * 2 + 2 + 4 + MOL_DEG + 6 == MR_ROW * 4, "the arrays over A fill it exactly");
     __shared__ unsigned inS[MOL_W];
     __shared__ int bad, walk_flags;
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -165,7 +132,7 @@ k_smiles_build(const int *__restrict__ lig_ptr, int n_atoms, const int *__restri
             const int a = lane + 64 * k;
             deg[a] = 0;
             fsize[a] = 0;
-            for (int w = 0; w < SM_ROW; ++w) A[a * SM_ROW + w] = 0;
+            for (int w = 0; w < MR_ROW; ++w) A[a * MR_ROW + w] = 0;
         }
         if (lane == 0) bad = walk_flags = 0;
         __syncthreads();
@@ -173,7 +140,7 @@ k_smiles_build(const int *__restrict__ lig_ptr, int n_atoms, const int *__restri
             const int h = atom_h[g];
             if (h < 0 || h > SM_MAX_H) return false;
             zv[a] = z;
-            zk[a] = (u64)(long long)z * SM_K2;
+            zk[a] = (u64)(long long)z * MR_K2;
             hl[a] = (unsigned char)(h << 1 | (aromatic && (atom_flags[g] & AT_AROMATIC) ? 1 : 0));
             frl[a] = (unsigned char)frag[g];        // 0 .. n - 1: checked by the caller of this
             return true;
@@ -183,9 +150,9 @@ k_smiles_build(const int *__restrict__ lig_ptr, int n_atoms, const int *__restri
     }
     if (ok) {
         nS = mol_scope(fsize, fr_of, n, lane, largest_only, inS).nS;
-        mol_bond_graph<false>(bond_ij, order_k, en.p0, en.p1, a0, n, lane, inS, A, SM_ROW, deg, (int *)nullptr, nb, &bad, [&](int r, int o) {
-            return (unsigned)(aromatic && (bond_flags[en.p0 + r] & 4) ? 4 : o) << 8;
-        });
+        mol_bond_graph<false>(bond_ij, en.p0, en.p1, a0, n, lane, inS, A, MR_ROW, deg, (int *)nullptr, nb, &bad,
+                              [order_k](int k) { return order_k[k]; }, 3,
+                              [&](int r, int o) { return (unsigned)(aromatic && (bond_flags[en.p0 + r] & 4) ? 4 : o) << 8; });
         __syncthreads();
         ok = !bad && nS > 0;
     }
@@ -206,54 +173,11 @@ k_smiles_build(const int *__restrict__ lig_ptr, int n_atoms, const int *__restri
         ok = !bad;
     }
     if (ok) {
-        // seeds: every other atom of S by element and distance, a BFS per source atom over bitset frontiers (as k_mol_keys)
+        // seeds: every other atom of S by element and distance (mr_seed_sum, as k_mol_keys), with the hydrogens and the aromatic flag
         for (int k = 0; k < MOL_K; ++k) {
             const int a = lane + 64 * k;
             if (a >= n || !in_scope(inS, a)) continue;
-            unsigned seen[MOL_W], front[MOL_W], next[MOL_W];
-#pragma unroll
-            for (int w = 0; w < MOL_W; ++w) seen[w] = front[w] = (w == (a >> 5)) ? 1u << (a & 31) : 0u;
-            u64 sum = 0;
-            for (int d = 1;; ++d) {
-#pragma unroll
-                for (int w = 0; w < MOL_W; ++w) next[w] = 0;
-#pragma unroll
-                for (int w = 0; w < MOL_W; ++w) {
-                    unsigned bits = front[w];
-                    while (bits) {
-                        const int j = 32 * w + __ffs(bits) - 1;
-                        bits &= bits - 1;
-#pragma unroll
-                        for (int v = 0; v < MOL_W; ++v) next[v] |= A[j * SM_ROW + v];
-                    }
-                }
-                unsigned any = 0;
-#pragma unroll
-                for (int w = 0; w < MOL_W; ++w) {
-                    next[w] &= ~seen[w];
-                    any |= next[w];
-                }
-                if (!any) break;
-#pragma unroll
-                for (int w = 0; w < MOL_W; ++w) {
-                    unsigned bits = next[w];
-                    while (bits) {
-                        sum += sm_mix(zk[32 * w + __ffs(bits) - 1] + (u64)d);
-                        bits &= bits - 1;
-                    }
-                    seen[w] |= next[w];
-                    front[w] = next[w];
-                }
-            }
-#pragma unroll
-            for (int w = 0; w < MOL_W; ++w) {
-                unsigned bits = inS[w] & ~seen[w];
-                while (bits) {
-                    sum += sm_mix(zk[32 * w + __ffs(bits) - 1] + (u64)SM_FAR);
-                    bits &= bits - 1;
-                }
-            }
-            x[0][a] = sm_mix((u64)(long long)zv[a] + (u64)deg[a] * SM_K3 + (u64)hl[a] * SM_K2 + SM_K1 * sum);
+            x[0][a] = mr_mix((u64)(long long)zv[a] + (u64)deg[a] * MR_K3 + (u64)hl[a] * MR_K2 + MR_K1 * mr_seed_sum(A, zk, inS, a));
         }
         __syncthreads();
 #pragma unroll
@@ -263,16 +187,7 @@ k_smiles_build(const int *__restrict__ lig_ptr, int n_atoms, const int *__restri
             closes[a] = 0;
             cursor[a] = paren[a] = psym[a] = nent[a] = 0;
         }
-        int cur = 0;
-        for (int r = 1; r <= nS; ++r) {             // |S| steps: a difference has reached every atom it can reach
-#pragma unroll
-            for (int k = 0; k < MOL_K; ++k) {
-                const int a = lane + 64 * k;
-                if (in[k]) x[cur ^ 1][a] = sm_refine(x[cur], nb, dg[k], a);
-            }
-            __syncthreads();
-            cur ^= 1;
-        }
+        int cur = mr_refine_steps(&x[0][0], nb, in, dg, lane, 0, nS);       // |S| steps: a difference has reached every atom it can reach
         // ties: perturb the lowest-numbered atom of the smallest shared value, refine until no new value appears
         int n_distinct;
         u64 shared;
@@ -283,17 +198,11 @@ k_smiles_build(const int *__restrict__ lig_ptr, int n_atoms, const int *__restri
             for (int k = MOL_K - 1; k >= 0; --k)
                 if (in[k] && x[cur][lane + 64 * k] == shared) first = lane + 64 * k;
             first = wave_min_int(first);
-            if (first < MOL_MAX && lane == (first & 63)) x[cur][first] = sm_mix(x[cur][first] + SM_K3);
+            if (first < MOL_MAX && lane == (first & 63)) x[cur][first] = mr_mix(x[cur][first] + MR_K3);
             __syncthreads();
             int count = n_distinct + 1;
             for (int r = 0; r < nS; ++r) {
-#pragma unroll
-                for (int k = 0; k < MOL_K; ++k) {
-                    const int a = lane + 64 * k;
-                    if (in[k]) x[cur ^ 1][a] = sm_refine(x[cur], nb, dg[k], a);
-                }
-                __syncthreads();
-                cur ^= 1;
+                cur = mr_refine_steps(&x[0][0], nb, in, dg, lane, cur, 1);
                 sm_census(x[cur], inS, in, n, lane, n_distinct, shared);
                 if (n_distinct == count) break;
                 count = n_distinct;
@@ -301,19 +210,8 @@ k_smiles_build(const int *__restrict__ lig_ptr, int n_atoms, const int *__restri
         }
         // ranks (equal values, which 64 bits make unheard of, in atom order: the ranks are a permutation whatever happens)
         {
-            u64 xa[MOL_K];
             int less[MOL_K];
-#pragma unroll
-            for (int k = 0; k < MOL_K; ++k) {
-                xa[k] = in[k] ? x[cur][lane + 64 * k] : 0;
-                less[k] = 0;
-            }
-            for (int c = 0; c < n; ++c) {
-                if (!in_scope(inS, c)) continue;
-                const u64 xc = x[cur][c];
-#pragma unroll
-                for (int k = 0; k < MOL_K; ++k) less[k] += xc < xa[k] || (xc == xa[k] && c < lane + 64 * k);
-            }
+            mr_rank<true>(x[cur], inS, in, n, lane, less);
 #pragma unroll
             for (int k = 0; k < MOL_K; ++k) {
                 if (!in[k]) continue;
@@ -326,16 +224,8 @@ k_smiles_build(const int *__restrict__ lig_ptr, int n_atoms, const int *__restri
         __syncthreads();
         // neighbour lists in ascending rank of the partner
 #pragma unroll
-        for (int k = 0; k < MOL_K; ++k) {
-            if (!in[k]) continue;
-            unsigned short *row = nb + (lane + 64 * k) * MOL_DEG;
-            for (int s = 1; s < dg[k]; ++s) {
-                const unsigned short e = row[s];
-                int t = s;
-                for (; t > 0 && rank[row[t - 1] & 0xffu] > rank[e & 0xffu]; --t) row[t] = row[t - 1];
-                row[t] = e;
-            }
-        }
+        for (int k = 0; k < MOL_K; ++k)
+            if (in[k]) mr_sort_row(nb + (lane + 64 * k) * MOL_DEG, dg[k], [&](unsigned e) { return rank[e & 0xffu]; });
         __syncthreads();
         // the serial part: the walk (order, parents, branch marks), then the closure numbers in written order
         if (lane == 0) {

@@ -4,14 +4,20 @@ ligands (bit 0 of their status words), touch nothing of them, and agree on which
 layout of kpd_mol_perceive: all-carbon chains of 5 .. 12 atoms and of 63, 64, 65, 256 (the edges of the lane passes) and 257 atoms,
 the two ethanols and a chloride of molecule_cases, and a hub with six spokes.  kpd_mol_add_hs is fed what kpd_mol_sanitize wrote
 for the same edited batch.  The expected vectors are written out; sanitize_ref and hydrogens_ref must give them too (molset_ref
-reads the graph without validating it, so it has no say on an edit).  Every raw call runs with canaries."""
+reads the graph without validating it, so it has no say on an edit).  Every raw call runs with canaries.
+kpd_mol_smiles and kpd_pose_rmsd take the same front end, bond loop included (pose_rmsd with its labels 1 .. 15 for the orders), and
+get the same batch and edits in a test of their own below."""
 import numpy as np
 import pytest
 
 from . import hydrogens_cases as HC
 from . import hydrogens_ref as HR
+from . import pose_rmsd_ref as PR
 from . import sanitize_cases as SC
 from . import sanitize_ref as SR
+from . import smiles_ref as SMR
+from . import test_pose_rmsd_gpu as TR
+from . import test_smiles_gpu as TS
 from .molecule_cases import ELEMENTS, TWO_ETHANOLS_CL
 from .test_hydrogens_gpu import add_hs_gpu
 from .test_molset_gpu import keys_gpu, to_device
@@ -116,3 +122,59 @@ def test_the_three_agree_on_the_scope_at_a_tie(cuda, largest):
     for b in range(B):                              # and on every other ligand of the batch
         r = slice(int(ptr[b]), int(ptr[b + 1]))
         assert np.array_equal(keys['atom_inv'][r] != 0, san['valence_k'][r] >= 0), b
+
+
+# ---- the two other users of the front end: kpd_mol_smiles and kpd_pose_rmsd ------------------------------------------------------------
+SYMBOLS_H = ELEMENTS + ['H']                        # the names of the classes of HC.Z_H
+_RESTATED = {}
+
+
+def remembered(fn):
+    """fn with its results kept by the text of its arguments.  An edit touches one or two ligands: the restatement of every other
+    ligand of the batch (the 256-atom chain is a quarter of a second in Python) is computed once, not in each of the eleven cases."""
+    def call(*args):
+        key = fn.__name__ + repr(args)
+        if key not in _RESTATED:
+            _RESTATED[key] = fn(*args)
+        return _RESTATED[key]
+    return call
+
+
+@pytest.mark.parametrize('largest', [False, True])
+def test_smiles_and_pose_rmsd_leave_out_the_same_ligands(cuda, largest, monkeypatch):
+    """kpd_mol_smiles gets the edited perception arrays with the sanitiser's outputs of the clean batch (an edit of `order` goes to
+    order_k), so only its own front end can refuse a ligand; kpd_pose_rmsd gets the edited `order` as bond_label, K = 1, skip_h off
+    and the clean positions as reference and pose.  Bit 0 of both status vectors is the written-out vector of the three calls above;
+    a bond label of 4 is in kpd_pose_rmsd's range, so there ligand 11 stays in."""
+    monkeypatch.setattr(SMR, 'smiles_ligand', remembered(SMR.smiles_ligand))
+    monkeypatch.setattr(PR, 'ligand_graph', remembered(PR.ligand_graph))
+    pos, ptr0, mol0 = base_batch()
+    N = len(pos)
+    san0 = sanitize_gpu(cuda, pos, ptr0, mol0, largest, z=HC.Z_H, allowed=HC.ALLOWED_H, mass=HC.MASS_H_TABLE)
+    assert (san0['status'] & 1).tolist() == [int(b == TOO_LARGE) for b in range(B)]
+    for name, edits, want in cases(ptr0, mol0):
+        want_rmsd = [int(b in (2, TOO_LARGE)) for b in range(B)] if name == 'an order of 0 and of 4' else want
+        edits = dict(edits, order_k=edits['order']) if 'order' in edits else edits
+        ptr, mol = edited(ptr0, dict(mol0, order_k=san0['order_k']), edits)
+        san = dict(san0, order_k=mol.pop('order_k'))
+        # the restatements first: they must give the written-out vectors
+        smi_ref = SMR.smiles_batch(ptr, mol, san, HC.Z_H, SYMBOLS_H, largest)
+        rms_ref = PR.pose_rmsd_batch(ptr, mol, HC.Z_H, pos[None], pos, largest_only=largest, skip_h=False, bond_label=mol['order'])
+        assert [st & 1 for st in smi_ref[2]] == want and (rms_ref['status'] & 1).tolist() == want_rmsd, name
+        texts, at, st, _ = smi = TS.smiles_gpu(cuda, ptr, mol, san, largest, elements=SYMBOLS_H, z=HC.Z_H)
+        rms = TR.rmsd_gpu(cuda, ptr, mol, pos[None], pos, largest=largest, skip_h=False, bond_label=mol['order'], z=HC.Z_H)
+        assert [x & 1 for x in st] == want and (rms['status'] & 1).tolist() == want_rmsd, (name, st, rms['status'])
+        TS.assert_same(smi, smi_ref, name)          # a ligand that stays in: its bytes, and every output of kpd_pose_rmsd
+        TR.assert_same(rms, rms_ref, name)
+        for b in range(B):
+            rows = slice(int(ptr0[b]), int(ptr0[b + 1]))            # the rows the ligand has in the clean batch
+            if want[b]:
+                assert at[b + 1] == at[b] and texts[b] == b'', (name, b)
+            else:
+                assert texts[b] and texts[b] == smi_ref[0][b], (name, b)
+            if want_rmsd[b]:
+                assert rms['rmsd'][b, 0] == 0 and rms['plain'][b, 0] == 0 and rms['nodes'][b, 0] == 0, (name, b)
+                assert (rms['map'][0, rows] == -1).all(), (name, b)
+            else:
+                assert rms['nodes'][b, 0] >= 1 and (rms['map'][0, rows] >= 0).any(), (name, b)       # -1 only outside S
+        assert rms['map'].shape == (1, N)

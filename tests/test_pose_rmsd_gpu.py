@@ -47,12 +47,12 @@ def stack(cases, K, seed=0):
 
 
 def rmsd_gpu(dev, ptr, mol, pos, ref=None, pairs=False, largest=False, skip_h=True, max_nodes=R.DEFAULT_MAX_NODES, bond_label=None,
-             atom_label=None, want_map=True):
+             atom_label=None, want_map=True, z=PC.Z_ALL):
     """kpd_pose_rmsd through the C ABI; returns numpy arrays in the shapes of pose_rmsd_ref.pose_rmsd_batch."""
     i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch.int32).to(dev)
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
     K, N, B, cap = pos.shape[0], pos.shape[1], len(ptr) - 1, len(mol['bonds'])
-    ins = [i32(ptr), i32(mol['elem']), i32(np.asarray(PC.Z_ALL)), i32(mol['frag']), i32(np.asarray(mol['bonds']).reshape(-1)), i32(mol['bond_ptr']),
+    ins = [i32(ptr), i32(mol['elem']), i32(np.asarray(z)), i32(mol['frag']), i32(np.asarray(mol['bonds']).reshape(-1)), i32(mol['bond_ptr']),
            i32(mol['status']), f32(pos)]
     opt = [None if x is None else (f32(x) if k == 2 else i32(x)) for k, x in enumerate((bond_label, atom_label, ref))]
     before = [x.clone() for x in ins] + [None if x is None else x.clone() for x in opt]
@@ -66,7 +66,7 @@ def rmsd_gpu(dev, ptr, mol, pos, ref=None, pairs=False, largest=False, skip_h=Tr
     scratch, p_scr = guarded(nb, torch.uint8, dev, CANARY)
     p = [x.data_ptr() for x in ins]
     q = [None if x is None else x.data_ptr() for x in opt]
-    hip.check(L.kpd_pose_rmsd(p[0], N, B, p[1], len(PC.Z_ALL), p[2], p[3], p[4], p[5], cap, p[6], q[0], q[1], int(largest), int(skip_h), q[2],
+    hip.check(L.kpd_pose_rmsd(p[0], N, B, p[1], len(z), p[2], p[3], p[4], p[5], cap, p[6], q[0], q[1], int(largest), int(skip_h), q[2],
                               p[7], K, int(pairs), int(max_nodes), rmsd.data_ptr(), plain.data_ptr(), None if amap is None else amap.data_ptr(),
                               nodes.data_ptr(), status.data_ptr(), p_scr, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
