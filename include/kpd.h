@@ -1095,6 +1095,99 @@ kpd_status kpd_pose_rmsd(const int32_t *lig_ptr, int32_t n_atoms, int32_t B, con
                          int32_t skip_h, const float *ref_pos, const float *pos, int32_t K, int32_t pairs, int64_t max_nodes,
                          double *rmsd, double *plain, int32_t *map, int64_t *nodes, int32_t *status, void *scratch, void *stream);
 
+/* Plausibility checks of poses (csrc/pose_check.hip): whether a pose is physically plausible, which no energy, score or RMSD of the
+ * calls around it says.  The list follows PoseBusters (Buttenschoen, Morris & Deane 2024): bond lengths and angles in range, no
+ * internal clash, flat aromatic rings and double bonds, no clash with the protein, little volume overlap with it.  PoseBusters
+ * runs on RDKit and cannot be restated here, so THIS COMMENT IS THE DEFINITION, down to the order of every operation
+ * (tests/pose_check_ref.py restates it bit for bit).  THESE ARE NOT PoseBusters' NUMBERS: the reference lengths and angles are
+ * this library's own (the radii table above and the centre classes of kpd_mol_add_hs), not RDKit's distance-geometry bounds;
+ * there is no energy-ratio check; there is no stereo.  The default thresholds are PoseBusters' published ones AS RECALLED, NOT
+ * CHECKED AGAINST THE PAPER OR ITS SOURCE: nothing may rely on them being its values.  All of them are fields of the params.
+ * The graph is what kpd_mol_perceive and kpd_mol_sanitize left on the device; the poses need not be the pose it was perceived
+ * from (relaxed, minimised and docked poses are the main customers).  Inputs are never written.
+ * Scope S, Z(a) (0 for an atomic number outside 0 .. 255), deg(a) and "both ends in S" are those of kpd_mol_sanitize; the
+ *   neighbours of an atom are its partners over bonds with both ends in S, in ascending index.
+ * Arithmetic: fp64 on the fp32 values; every product, sum, difference and quotient is rounded once (no fused multiply-add), sqrt
+ *   and / are correctly rounded; only + - x / sqrt (and floor, for lattice indices) are used.  d2(a,b) = (dx^2 + dy^2) + dz^2 on
+ *   the differences of the fp32 coordinates, d = sqrt(d2); a.b, a x b, a / s and sums of vectors as for kpd_mol_add_hs.  R_a =
+ *   lig_radius[elem[a]], R_j = pocket_radius[j] as fp64.  Every per-pose result is a minimum, a maximum or an integer count: no
+ *   order of summation exists.  "Takes part": an atom of S (a pocket atom) whose radius is > 0; checks 3, 5 and 6 see no other.
+ * r0 of a bond (a,b): from the radii table, in half picometres: L1 = 2 (r1(a) + r1(b)); L2, L3 the same sums of the double and
+ *   triple radii where both are non-zero; L15 = (L1 + L2) / 2.  L = L15 (L1 without an L2) if the bond is aromatic (bond_flags bit
+ *   2); else L3 (L1 without) for order_k 3; else L2 (L1 without) for order_k 2; else L1.  r0 = (double)L * 0.005.  A bond with
+ *   r1 = 0 at either end has no r0 and is examined by neither check 1 nor check 2.
+ * Check 1, bond lengths (fail bit 0): every bond of S with an r0: v = d / r0; fails iff v < bond_lo or v > bond_hi.
+ * Check 2, 1-3 distances (bit 1): every centre j of S and every pair i < k of its neighbours that are not bonded to each other and
+ *   whose bonds to j have an r0: x = r0(i,j), y = r0(j,k), d0sq = ((x x) + (y y)) - (((2 x) y) c), v = d(i,k) / sqrt(d0sq); fails
+ *   iff v < angle_lo or v > angle_hi.  c = cos t0 from deg(j) and the class kpd_mol_add_hs gives j (LINEAR / PLANAR / TET, the
+ *   conjugated-N clause included): deg >= 4: -T3; deg 3: -0.5 if PLANAR or LINEAR, else -T3; deg 2: -1 if LINEAR, -0.5 if PLANAR,
+ *   else -T3.  T3 = 0.3333333333333333.
+ * Check 3, internal clash (bit 2): every pair a < b of atoms that take part whose shortest path in S has four or more bonds, or
+ *   that are not connected: v = d / (R_a + R_b); fails iff v < clash_min.
+ * Check 4, flatness, three sub-checks.  A squared norm below 1e-12 is DEGENERATE.
+ *   aromatic rings (bit 3): every simple cycle of 5 or of 6 atoms in the graph of the aromatic bonds of S, each once: listed from
+ *     its lowest atom p_0 towards the lower of that atom's two ring neighbours, p_0 .. p_{m-1}.  c = (((P_0 + P_1) + ..) + P_{m-1})
+ *     / m; v_k = P_k - c; N = ((0 + v_0 x v_1) + v_1 x v_2) + .. + v_{m-1} x v_0; degenerate N.N: the ring fails and has no value;
+ *     else u = N / sqrt(N.N), value = max_k |v_k . u|; fails iff value > ring_max.
+ *   planar centres (bit 4): every atom a of S with deg 3 that has a bond of order_k 2 or is aromatic (atom_flags bit 1); the
+ *     conjugated-N clause does NOT count here.  Neighbours q_0 < q_1 < q_2: N = (Q_1 - Q_0) x (Q_2 - Q_0); degenerate: fails, no
+ *     value; else value = |(P_a - Q_0) . (N / sqrt(N.N))|; fails iff value > centre_max.
+ *   double-bond twist (bit 5): every bond (a,b), a < b, of order_k 2 that is no ring bond (bond_flags bit 0), every neighbour c of
+ *     a other than b and every neighbour d of b other than a: n1 = (P_a - P_c) x (P_b - P_a), n2 = (P_b - P_a) x (P_d - P_b); a
+ *     degenerate n1.n1 or n2.n2: skipped and counted; else value = ((n1.n2) (n1.n2)) / ((n1.n1) (n2.n2)), the squared cosine of
+ *     the torsion; fails iff value < twist_min.
+ * Check 5, pocket clash (bit 6): every ligand atom a x every atom j of its pocket, both taking part: v = d / (R_a + R_j); fails
+ *   iff v < pocket_min.
+ * Check 6, volume overlap (bit 7): the lattice of the points (h ix, h iy, h iz) over ALL integers (each coordinate one rounded
+ *   product; the lattice is fixed in space, not per ligand).  A point is in the ligand iff d2(point, P_a) <= R_a R_a for some
+ *   ligand atom a that takes part; it is counted once and belongs to the lowest such a.  A ligand point is in the pocket iff
+ *   d2(point, Q_j) <= (s R_j) (s R_j) for some atom j of the pocket that takes part, s = pocket_scale.  n_lig_points, n_overlap_points;
+ *   value = (double)n_overlap_points / (double)n_lig_points, 0 without points; fails iff value > overlap_max.
+ *   pocket_of = -1: checks 5 and 6 examine nothing (no points are counted) and pass.
+ * kpd_pose_check_defaults: bond_lo 0.75, bond_hi 1.25, angle_lo 0.75, angle_hi 1.25, clash_min 0.7, ring_max 0.25, centre_max
+ *   0.25, twist_min 0.75, pocket_min 0.75, pocket_scale 0.8, overlap_max 0.075, h 0.5 (RECALLED, see above).  Every field must be
+ *   in 0 .. 1e6, h in 0.1 .. 4 and pocket_scale at most 4 (KPD_ERR_INVALID).
+ *
+ * kpd_pose_check: lig_ptr, elem, z, frag, bond_ij, order_k, bond_flags, bond_ptr, mol_status, san_status, atom_h, atom_flags and
+ *   largest_only as for kpd_mol_smiles; pos [K,n_atoms,3] fp32, pose-major, K >= 1; lig_radius [F], pocket_radius [n_pocket]
+ *   (van der Waals radii from the caller); pocket_x, pocket_ptr, pocket_of, max_atoms and max_pocket as for kpd_vina_score
+ *   (n_pocket at most 2^22); params: NULL for the defaults; all device pointers but params.
+ *   Out (device), per (ligand, pose), row b K + k: fail [B,K] (the bits above); report [B,K,10] fp64 = {bond min, bond max, angle
+ *   min, angle max, internal clash min, ring max, centre max, twist min, pocket clash min, overlap value}, 0 where nothing was
+ *   examined (or nothing had a value); counts [B,K,17] int32 = {bonds examined, failing, angles, failing, internal pairs, failing,
+ *   rings, failing, centres, failing, torsions, failing, torsions skipped, pocket pairs, failing, n_lig_points, n_overlap_points};
+ *   atom_fail [K,n_atoms]: per atom the bits of the checks it took part in failing (both ends of a bond or pair, the three atoms
+ *   of an angle, the atoms of a ring, the centre, the four atoms of a torsion, the ligand atom of a pocket pair; bit 7 on the
+ *   owners of overlapping points when check 6 fails); status [B,K]:
+ *   bit 0 = no molecule (san_status bit 0, mol_status bits 0, 1 or 3, more than max_atoms atoms, an empty S, an element or
+ *   fragment out of range, a bond outside the ligand, twice, of an order_k outside 1 .. 3, a seventh neighbour, atom_h outside
+ *   0 .. 9, or a bond of S that joins two `frag` labels); bit 1 = bad input: a coordinate of the pose or of its pocket that is not
+ *   finite or not below 2^20 in magnitude (the lattice indices must fit), a radius of an atom of the ligand or of its pocket that
+ *   is not finite or above 8, a pocket_of outside [-1, P) or a malformed pocket segment; bit 2 (informational) = some atom of S or
+ *   of the pocket took no part.  Of bits 0 and 1 one is reported, the first that is met in this order: the ligand's segment, size,
+ *   mol_status and bond range (bit 0); pocket_of and the pocket segment (bit 1); san_status and the graph (bit 0); coordinates and
+ *   radii (bit 1).  With bit 0 or 1 the pose's rows are zeros and fail is 0 (rows of a malformed ligand segment are
+ *   zeros as well); nothing is read or written out of bounds.
+ *   One wave per (ligand, pose): one launch and five fills whatever B and K are; no scratch, no host synchronisation, no float
+ *   atomics.  Of a pocket the first atoms are staged in LDS (as many as max_pocket asks for, at most 2048) and the rest is read
+ *   from global memory with the same result to the bit; the pocket atoms that can reach the ligand's lattice points are culled by
+ *   a box test per pose and a sphere test per ligand atom, whose margins cannot change a count.  A pose's results are bitwise independent of the rest of the batch, of the
+ *   ligand's place in it, of K, of max_atoms / max_pocket, of cap_bonds and of the repeat. */
+enum { KPD_CHECK_NO_MOLECULE = 1, KPD_CHECK_BAD_INPUT = 2, KPD_CHECK_ATOM_OUT = 4 };
+enum { KPD_CHECK_REPORT = 10, KPD_CHECK_COUNTS = 17 };
+typedef struct kpd_pose_check_params {
+    double bond_lo, bond_hi, angle_lo, angle_hi, clash_min, ring_max, centre_max, twist_min, pocket_min, pocket_scale, overlap_max, h;
+} kpd_pose_check_params;
+void kpd_pose_check_defaults(kpd_pose_check_params *params);
+kpd_status kpd_pose_check(const int32_t *lig_ptr, int32_t n_atoms, int32_t B, int32_t max_atoms, const int32_t *elem, int32_t F,
+                          const int32_t *z, const int32_t *frag, const int32_t *bond_ij, const int32_t *order_k,
+                          const int32_t *bond_flags, const int32_t *bond_ptr, int32_t cap_bonds, const int32_t *mol_status,
+                          const int32_t *san_status, const int32_t *atom_h, const int32_t *atom_flags, int32_t largest_only,
+                          const float *pos, int32_t K, const float *lig_radius, const float *pocket_x, const float *pocket_radius,
+                          const int32_t *pocket_ptr, int32_t n_pocket, int32_t P, int32_t max_pocket, const int32_t *pocket_of,
+                          const kpd_pose_check_params *params, int32_t *fail, double *report, int32_t *counts, int32_t *atom_fail,
+                          int32_t *status, void *stream);
+
 /* Relaxation of sampled ligands inside their rigid pockets (csrc/relax.hip).  Stands where upstream runs
  * analysis/pocket_minimization.py: RDKit's UFF on ligand + receptor with every receptor atom fixed, maxIts = 400, then the plain
  * (unaligned) CalcRMS and the energies before and after.  RDKit's UFF cannot be restated here -- it needs hydrogens, atom typing,

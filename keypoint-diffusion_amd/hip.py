@@ -93,6 +93,11 @@ class KpdVinaParams(C.Structure):
     _fields_ = [(name, C.c_double) for name in ('w_gauss1', 'w_gauss2', 'w_repulsion', 'w_hydrophobic', 'w_hbond', 'w_rot', 'r_c')]
 
 
+class KpdPoseCheckParams(C.Structure):
+    _fields_ = [(name, C.c_double) for name in ('bond_lo', 'bond_hi', 'angle_lo', 'angle_hi', 'clash_min', 'ring_max', 'centre_max',
+                                                 'twist_min', 'pocket_min', 'pocket_scale', 'overlap_max', 'h')]
+
+
 class KpdVinaMinParams(C.Structure):
     _fields_ = ([(name, C.c_double) for name in ('w_gauss1', 'w_gauss2', 'w_repulsion', 'w_hydrophobic', 'w_hbond', 'w_rot', 'r_c', 'w_intra',
                                                   'gtol', 'max_step')] + [('max_iters', C.c_int32)])
@@ -222,6 +227,11 @@ def lib():
     L.kpd_pose_rmsd_scratch_bytes.restype = C.c_int64
     L.kpd_pose_rmsd.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3 +
                                 [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 7)
+    L.kpd_pose_check_defaults.argtypes = [C.POINTER(KpdPoseCheckParams)]
+    L.kpd_pose_check_defaults.restype = None
+    L.kpd_pose_check.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] +
+                                 [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 3 +
+                                 [C.c_void_p, C.POINTER(KpdPoseCheckParams)] + [C.c_void_p] * 6)
     L.kpd_relax_defaults.argtypes = [C.POINTER(KpdRelaxParams)]
     L.kpd_relax_defaults.restype = None
     L.kpd_relax.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
@@ -274,7 +284,8 @@ EXPORTS = [
     'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
     'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
     'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_mol_sanitize', 'kpd_mol_add_hs_scratch_bytes', 'kpd_mol_add_hs',
-    'kpd_smiles_scratch_bytes', 'kpd_mol_smiles', 'kpd_pose_rmsd_scratch_bytes', 'kpd_pose_rmsd', 'kpd_relax_defaults', 'kpd_relax',
+    'kpd_smiles_scratch_bytes', 'kpd_mol_smiles', 'kpd_pose_rmsd_scratch_bytes', 'kpd_pose_rmsd', 'kpd_pose_check_defaults',
+    'kpd_pose_check', 'kpd_relax_defaults', 'kpd_relax',
     'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score', 'kpd_vina_min_defaults', 'kpd_vina_minimize',
     'kpd_vina_dock_defaults', 'kpd_vina_dock',
 ]
@@ -1303,6 +1314,82 @@ def pose_rmsd(lig_ptr: torch.Tensor, z, mol: dict, pos: torch.Tensor, ref_pos: O
                               cap_bonds, _ptr(mol['status']), _ptr(bond_label), _ptr(atom_label), int(bool(largest_only)), int(bool(skip_h)),
                               None if pairs else _ptr(ref_pos), _ptr(pos), K, int(pairs), max_nodes, _ptr(out['rmsd']), _ptr(out['plain']),
                               _ptr(out.get('map')), _ptr(out['nodes']), _ptr(out['status']), _ptr(scratch), _stream()))
+    return out
+
+
+CHECK_NO_MOLECULE, CHECK_BAD_INPUT, CHECK_ATOM_OUT = 1, 2, 4     # status bits of kpd_pose_check
+CHECK_FAIL = ('bond', 'angle', 'clash', 'ring', 'centre', 'twist', 'pocket', 'overlap')       # bit k of `fail` and `atom_fail`
+CHECK_REPORT = ('bond_min', 'bond_max', 'angle_min', 'angle_max', 'clash_min', 'ring_max', 'centre_max', 'twist_min', 'pocket_min', 'overlap')
+CHECK_COUNTS = ('bonds', 'bonds_fail', 'angles', 'angles_fail', 'pairs', 'pairs_fail', 'rings', 'rings_fail', 'centres', 'centres_fail',
+                'torsions', 'torsions_fail', 'torsions_skipped', 'pocket_pairs', 'pocket_pairs_fail', 'n_lig_points', 'n_overlap_points')
+CHECK_MAX_RADIUS = 8.0
+
+
+def pose_check_params(**params) -> KpdPoseCheckParams:
+    """The thresholds of kpd_pose_check: the library's defaults (kpd_pose_check_defaults: PoseBusters' published thresholds as
+    recalled, not checked against the paper) with the given fields replaced."""
+    p, names = _struct_params('pose_check', KpdPoseCheckParams, lib().kpd_pose_check_defaults, params)
+    if not (all(0 <= getattr(p, k) <= 1e6 for k in names) and 0.1 <= p.h <= 4 and p.pocket_scale <= 4 and p.bond_lo <= p.bond_hi and
+            p.angle_lo <= p.angle_hi):
+        raise KpdError('pose_check: ' + ', '.join(f'{k} {getattr(p, k)}' for k in names) + ': every threshold must be in 0 .. 1e6, '
+                       'h in 0.1 .. 4, pocket_scale at most 4, and the lower bounds not above the upper ones')
+    return p
+
+
+def pose_check(lig_ptr: torch.Tensor, z, mol: dict, san: dict, pos: torch.Tensor, lig_radius: torch.Tensor,
+               pocket_x: Optional[torch.Tensor] = None, pocket_radius: Optional[torch.Tensor] = None, pocket_ptr: Optional[torch.Tensor] = None,
+               pocket_of: Optional[torch.Tensor] = None, largest_only: bool = False, max_atoms: int = MOL_MAX_ATOMS,
+               max_pocket: Optional[int] = None, **params):
+    """Plausibility checks of K poses of a batch of sanitised molecules on the GPU (kpd_pose_check; include/kpd.h states every
+    check: bond lengths, 1-3 distances, internal clash, flat aromatic rings, planar centres and double bonds, pocket clash and
+    volume overlap; NOT PoseBusters' numbers).  `mol`: what `mol_perceive` returned, `san`: what `mol_sanitize` returned for it;
+    z: the atomic number of every class; pos [K,N,3] (or [N,3]) fp32; lig_radius [F] fp32 van der Waals radii (not > 0: the class
+    takes no part in the clash and overlap checks); pocket_x [M,3], pocket_radius [M] fp32, pocket_ptr [P+1] and pocket_of [B]
+    int32 (-1: no pocket), all four None for no pockets at all; all GPU tensors.  `params`: the thresholds of `pose_check_params`.
+    Returns a dict of device tensors: fail [B,K] int32 (bit k: CHECK_FAIL[k]), report [B,K,10] float64 (CHECK_REPORT), counts
+    [B,K,17] int32 (CHECK_COUNTS), atom_fail [K,N] int32, status [B,K] int32 (bits CHECK_*).  No host synchronisation."""
+    B = _offsets(lig_ptr, 'lig_ptr')
+    _mol_fields('pose_check', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'))
+    _mol_fields('pose_check', san, ('order_k', 'bond_flags', 'atom_h', 'atom_flags', 'status'))
+    if not (isinstance(pos, torch.Tensor) and pos.dim() in (2, 3) and pos.shape[-1] == 3):
+        raise KpdError(f'pose_check: pos must be [K,N,3] or [N,3], got {tuple(getattr(pos, "shape", ()))}')
+    pos = _dev_f32(pos if pos.dim() == 3 else pos[None], 'pos')
+    K, N, F = pos.shape[0], pos.shape[1], len(z)
+    cap_bonds = san['order_k'].numel()
+    if (K < 1 or F < 1 or mol['elem'].numel() != N or mol['frag'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or
+            san['bond_flags'].numel() != cap_bonds or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B or
+            san['status'].numel() != B or san['atom_h'].numel() != N or san['atom_flags'].numel() != N):
+        raise KpdError(f'pose_check: pos {tuple(pos.shape)} (K >= 1), {B} ligands, {F} atomic numbers do not match the perceived and '
+                       f'sanitised molecules')
+    dev = pos.device
+    lig_radius = _dev_f32(lig_radius, 'lig_radius')
+    if lig_radius.shape != (F,):
+        raise KpdError(f'pose_check: lig_radius {tuple(lig_radius.shape)} must be [{F}]')
+    if pocket_x is None:
+        if not (pocket_radius is None and pocket_ptr is None and pocket_of is None):
+            raise KpdError('pose_check: pocket_radius, pocket_ptr and pocket_of need pocket_x')
+        pocket_x, pocket_radius = torch.zeros(0, 3, device=dev), torch.zeros(0, device=dev)
+        pocket_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
+        pocket_of = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    pocket_x, pocket_radius = _dev_f32(pocket_x, 'pocket_x'), _dev_f32(pocket_radius, 'pocket_radius')
+    P = _offsets(pocket_ptr, 'pose_check: pocket_ptr', 'P')
+    pocket_of = _per_entry(pocket_of, 'pose_check: pocket_of', B, 'ligand', contiguous=True)
+    M = pocket_x.shape[0]
+    max_atoms = int(max_atoms)
+    if pocket_x.shape != (M, 3) or pocket_radius.shape != (M,) or not 1 <= max_atoms <= MOL_MAX_ATOMS:
+        raise KpdError(f'pose_check: pocket_x {tuple(pocket_x.shape)} must be [M,3], pocket_radius {tuple(pocket_radius.shape)} [M], '
+                       f'max_atoms {max_atoms} in 1 .. {MOL_MAX_ATOMS}')
+    p = pose_check_params(**params)
+    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
+    out = dict(fail=torch.empty(B, K, dtype=torch.int32, device=dev), report=torch.empty(B, K, len(CHECK_REPORT), dtype=torch.float64, device=dev),
+               counts=torch.empty(B, K, len(CHECK_COUNTS), dtype=torch.int32, device=dev),
+               atom_fail=torch.empty(K, N, dtype=torch.int32, device=dev), status=torch.empty(B, K, dtype=torch.int32, device=dev))
+    check(lib().kpd_pose_check(_ptr(lig_ptr), N, B, max_atoms, _ptr(mol['elem']), F, _ptr(zt), _ptr(mol['frag']), _ptr(mol['bonds']),
+                               _ptr(san['order_k']), _ptr(san['bond_flags']), _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']),
+                               _ptr(san['status']), _ptr(san['atom_h']), _ptr(san['atom_flags']), int(bool(largest_only)), _ptr(pos), K,
+                               _ptr(lig_radius), _ptr(pocket_x), _ptr(pocket_radius), _ptr(pocket_ptr), M, P,
+                               M if max_pocket is None else int(max_pocket), _ptr(pocket_of), C.byref(p), _ptr(out['fail']),
+                               _ptr(out['report']), _ptr(out['counts']), _ptr(out['atom_fail']), _ptr(out['status']), _stream()))
     return out
 
 

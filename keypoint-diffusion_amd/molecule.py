@@ -113,6 +113,30 @@ def xs_radius_table(elements: Sequence[str], radii: Optional[Dict[str, float]] =
     return out
 
 
+# van der Waals radii for `Sanitized.pose_check`, element -> Angstrom, in the form of Bondi 1964 (with later values where Bondi has
+# none).  RECALLED, NOT CHECKED AGAINST THE PAPER: nothing may rely on these being Bondi's values; pass `radii=` to override.
+VDW_RADII: Dict[str, float] = {
+    'H': 1.2, 'B': 1.92, 'C': 1.7, 'N': 1.55, 'O': 1.52, 'F': 1.47, 'Na': 2.27, 'Mg': 1.73, 'Si': 2.1, 'P': 1.8, 'S': 1.8, 'Cl': 1.75,
+    'K': 2.75, 'Ca': 2.31, 'Mn': 2.05, 'Fe': 2.04, 'Co': 2.0, 'Ni': 1.63, 'Cu': 1.4, 'Zn': 1.39, 'As': 1.85, 'Se': 1.9, 'Br': 1.85, 'I': 1.98,
+}
+
+
+def vdw_radius_table(elements: Sequence[str], radii: Optional[Dict[str, float]] = None, with_h: bool = False) -> List[float]:
+    """The van der Waals radius of every element symbol, from `radii` first and VDW_RADII second; an element in neither raises.
+    'H' gets 0 unless `with_h` (or `radii` names it): a radius of 0 keeps an atom out of the clash and overlap checks of
+    kpd_pose_check.  At most hip.CHECK_MAX_RADIUS."""
+    out = []
+    for el in elements:
+        r = (radii or {}).get(el, 0.0 if el == 'H' and not with_h else VDW_RADII.get(el))
+        if r is None:
+            raise hip.KpdError(f'pose_check: no van der Waals radius for element {el!r}; pass radii={{{el!r}: R}}')
+        r = float(r)
+        if not 0 <= r <= hip.CHECK_MAX_RADIUS:
+            raise hip.KpdError(f'pose_check: the radius of {el!r} must be in 0 .. {hip.CHECK_MAX_RADIUS} (got {r!r})')
+        out.append(r)
+    return out
+
+
 # monoisotopic masses for `Molecules.sanitize`, element -> u, to stand where upstream calls Descriptors.ExactMolWt.  RECALLED, NOT
 # CHECKED AGAINST A TABLE OF NUCLIDES: nothing may rely on the last digits; pass `masses=` to override.
 MONOISOTOPIC_MASS: Dict[str, float] = {
@@ -560,6 +584,34 @@ class PoseRMSD:
                     plain=[plain[r].item() for r in rows], nodes=[int(nodes[r]) for r in rows])
 
 
+class PoseChecks:
+    """What `pose_check` returns, device tensors per (ligand, pose): `.passed` [B,K] bool (no check fails, the pose could be
+    checked, and the molecule is `Sanitized.valid`), `.fail` [B,K] int32 (bit k: hip.CHECK_FAIL[k]), `.report` [B,K,10] float64 (the
+    extreme value behind every check, columns hip.CHECK_REPORT), `.counts` [B,K,17] int32 (items examined and failing, columns
+    hip.CHECK_COUNTS), `.atom_fail` [K,N] int32 (per atom the checks it took part in failing), `.status` [B,K] (bits: 1 no molecule,
+    2 bad input, 4 some atom took no part in the clash and overlap checks).  The rule is include/kpd.h's, NOT PoseBusters'."""
+
+    def __init__(self, out: Dict[str, torch.Tensor], valid: torch.Tensor):
+        self.fail, self.report, self.counts, self.atom_fail, self.status = (out[k] for k in ('fail', 'report', 'counts', 'atom_fail', 'status'))
+        checked = (self.status & (hip.CHECK_NO_MOLECULE | hip.CHECK_BAD_INPUT)) == 0
+        self.passed = (self.fail == 0) & checked & valid.to(torch.bool)[:, None]
+
+    def table(self) -> Dict[str, list]:
+        """lig_idx, pose, passed, one bool column per check (True: it passes), then every report and count column, as lists;
+        poses that could not be checked (status bit 0 or 1) have no row."""
+        st, fail, rep, cnt, ok = self.status.cpu(), self.fail.cpu(), self.report.cpu(), self.counts.cpu(), self.passed.cpu()
+        rows = [(b, k) for b in range(st.shape[0]) for k in range(st.shape[1])
+                if not int(st[b, k]) & (hip.CHECK_NO_MOLECULE | hip.CHECK_BAD_INPUT)]
+        out: Dict[str, list] = dict(lig_idx=[b for b, _ in rows], pose=[k for _, k in rows], passed=[bool(ok[r]) for r in rows])
+        for bit, name in enumerate(hip.CHECK_FAIL):
+            out[name + '_ok'] = [not (int(fail[r]) >> bit) & 1 for r in rows]
+        for c, name in enumerate(hip.CHECK_REPORT):
+            out[name] = [rep[r][c].item() for r in rows]
+        for c, name in enumerate(hip.CHECK_COUNTS):
+            out[name] = [int(cnt[r][c]) for r in rows]
+        return out
+
+
 class Sanitized:
     """What `Molecules.sanitize` returns: `.molecules` (a `Molecules` whose `order` is order_k and whose `valence` is valence_k, so
     `.sdf()`, `.keys()`, `.relax()`, `.vina_score()`, `.vina_minimize()` and `.vina_dock()` work unchanged on the Kekule orders),
@@ -627,6 +679,56 @@ class Sanitized:
             bond_label = torch.where(self.aromatic_bonds, torch.full_like(m.order, 4), m.order.clamp(1, 3)).to(torch.int32)
         return m.pose_rmsd(pos, ref, largest_frag=largest, skip_h=skip_h, pairs=pairs, max_nodes=max_nodes, bond_label=bond_label,
                            atom_label=atom_label)
+
+    def pose_check(self, pos=None, pocket_pos: Optional[List[torch.Tensor]] = None, pocket_elements: Optional[List[Sequence[str]]] = None,
+                   pocket_of=None, radii: Optional[Dict[str, float]] = None, with_h: bool = False, largest_frag: Optional[bool] = None,
+                   **thresholds) -> 'PoseChecks':
+        """Whether poses of these molecules are physically plausible, on the GPU in one launch (`kpd_pose_check`): bond lengths and
+        1-3 distances in range, no internal clash, flat aromatic rings, planar centres and double bonds and, with pockets, no clash
+        with the pocket and little volume overlap with it.  The list follows PoseBusters; the rule is include/kpd.h's and these are
+        NOT PoseBusters' numbers (reference lengths and angles of this library's own, no energy check, no stereo).
+        `pos`: [N,3], [K,N,3] or a list of per-ligand tensors, these molecules' own pose by default; relaxed, minimised and docked
+        poses are the main customers.  `pocket_pos`, `pocket_elements`, `pocket_of`: as for `Molecules.relax`; without them the two
+        pocket checks examine nothing.  `radii`: element -> van der Waals radius, consulted before VDW_RADII (an element in neither
+        raises); `with_h`: hydrogens take part in the clash and overlap checks; `largest_frag`: None, the scope these molecules
+        were sanitised with; `thresholds`: the fields of `hip.pose_check_params`."""
+        largest = self.largest_frag if largest_frag is None else bool(largest_frag)
+        if self.largest_frag and not largest:
+            raise hip.KpdError('pose_check(largest_frag=False) needs molecules sanitised over every atom: sanitize(largest_frag=False)')
+        m = self.molecules
+        if m.lig_elements is None or m.bonds is None:
+            raise hip.KpdError('these Molecules carry no bond graph: build them with build_molecules')
+        pos = m.pos if pos is None else pos
+        if pos is None:
+            raise hip.KpdError('these Molecules carry no coordinates: pass pos')
+        stack = m._pose_stack(pos)
+        if not stack.is_cuda or not m.lig_ptr.is_cuda:
+            raise hip.KpdError(f'pose_check: poses must live on the GPU (got {stack.device}); there is no CPU implementation')
+        if (pocket_pos is None) != (pocket_elements is None):
+            raise ValueError('pocket_pos and pocket_elements come together')
+        dev = stack.device
+        lig_radius = torch.tensor(vdw_radius_table(m.lig_elements, radii, with_h), dtype=torch.float32, device=dev)
+        pocket = {}
+        if pocket_pos is not None:
+            if m.pos is None:
+                m = Molecules(m.lig_ptr, m.summary, m.status, m.elem, m.valence, m.frag, m.bonds, m.order, m.bond_ptr, stack[0],
+                              m.lig_elements, m._max_atoms, sizes=m._sizes)
+            pocket_x, pocket_ptr, pocket_of, sizes, _, _ = m._in_pockets('pose_check', 'checking', pocket_pos, pocket_elements, pocket_of)
+            rows = [r for els in pocket_elements for r in vdw_radius_table(els, radii, with_h)]
+            pocket = dict(pocket_x=pocket_x, pocket_radius=torch.tensor(rows, dtype=torch.float32, device=dev), pocket_ptr=pocket_ptr,
+                          pocket_of=pocket_of, max_pocket=max(sizes, default=0))
+        hip.pose_check_params(**thresholds)         # refuse bad thresholds before anything is launched
+        K = int(stack.shape[0])
+        if len(m) == 0:
+            i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+            empty = dict(fail=i32(0, K), report=torch.zeros(0, K, len(hip.CHECK_REPORT), dtype=torch.float64, device=dev),
+                         counts=i32(0, K, len(hip.CHECK_COUNTS)), atom_fail=i32(K, 0), status=i32(0, K))
+            return PoseChecks(empty, self.valid)
+        n_max = m._max_atoms if m._max_atoms is not None else hip.MOL_MAX_ATOMS
+        mol = dict(elem=m.elem, frag=m.frag, bonds=m.bonds, bond_ptr=m.bond_ptr, status=m.status)
+        out = hip.pose_check(m.lig_ptr, self._z, mol, self._out, stack, lig_radius, largest_only=largest,
+                             max_atoms=max(1, min(n_max, hip.MOL_MAX_ATOMS)), **pocket, **thresholds)
+        return PoseChecks(out, self.valid)
 
     def unique(self, kekule: bool = False, largest_frag: Optional[bool] = None) -> List[int]:
         """The index of the first ligand of every distinct string of `smiles(kekule, largest_frag)`, ascending; ligands without a
@@ -794,6 +896,11 @@ class VinaDocked:
         exists = torch.arange(self.n_modes, device=r.device)[None, :] < self.n_found[:, None]
         return torch.where(exists, r, torch.zeros_like(r))
 
+    def pose_check(self, san: 'Sanitized', *args, **kw) -> 'PoseChecks':
+        """`Sanitized.pose_check` of every mode in one call ([B,n_modes] results; a mode that was not found is the input pose).
+        `san`: the `Sanitized` whose `.molecules` were docked; the other arguments (pockets, radii, thresholds) pass through."""
+        return _check_poses_of(san, self._mols, self._pos, args, kw)
+
     def mode_rmsd(self, **kw) -> torch.Tensor:
         """[B,n_modes,n_modes] float64: the symmetry-corrected RMSD between the modes of every ligand (symmetric, the diagonal 0);
         0 where either mode does not exist."""
@@ -843,6 +950,11 @@ class VinaMinimized:
         the input pose; `report[:, 8]`, the atom-by-atom number, is never smaller.  0 for a ligand without a molecule."""
         return self._input.pose_rmsd(self.molecules.pos, **kw).rmsd[:, 0]
 
+    def pose_check(self, san: 'Sanitized', *args, **kw) -> 'PoseChecks':
+        """`Sanitized.pose_check` of the minimised pose.  `san`: the `Sanitized` whose `.molecules` were minimised; the other
+        arguments (pockets, radii, thresholds) pass through."""
+        return _check_poses_of(san, self._input, self.molecules.pos, args, kw)
+
     @property
     def pos(self) -> List[torch.Tensor]:
         sizes = self._sizes if self._sizes is not None else (self.molecules.lig_ptr[1:] - self.molecules.lig_ptr[:-1]).tolist()
@@ -875,6 +987,11 @@ class Relaxed:
         input pose, upstream's `Chem.CalcRMS` column under the rule of include/kpd.h; `report[:, 2]`, the atom-by-atom number, is
         never smaller.  0 for a ligand without a molecule."""
         return self._input.pose_rmsd(self.molecules.pos, **kw).rmsd[:, 0]
+
+    def pose_check(self, san: 'Sanitized', *args, **kw) -> 'PoseChecks':
+        """`Sanitized.pose_check` of the relaxed pose.  `san`: the `Sanitized` whose `.molecules` were relaxed; the other
+        arguments (pockets, radii, thresholds) pass through."""
+        return _check_poses_of(san, self._input, self.molecules.pos, args, kw)
 
     @property
     def pos(self) -> List[torch.Tensor]:
@@ -936,6 +1053,13 @@ class VinaScores:
         return out
 
 
+def _check_poses_of(san: 'Sanitized', mols: Molecules, pos: torch.Tensor, args, kw) -> 'PoseChecks':
+    """What the `pose_check` of `Relaxed`, `VinaMinimized` and `VinaDocked` share: the poses belong to the molecules `san` holds."""
+    if not isinstance(san, Sanitized) or san.molecules.lig_ptr is not mols.lig_ptr or san.molecules.bonds is not mols.bonds:
+        raise hip.KpdError('pose_check: pass the Sanitized whose .molecules these poses were computed from')
+    return san.pose_check(pos, *args, **kw)
+
+
 def _class_tables(lig_elements: Sequence[str], allowed_bonds: Optional[Dict[str, object]]):
     allowed_bonds = ALLOWED_BONDS if allowed_bonds is None else allowed_bonds
     z, allowed = [], []
@@ -990,7 +1114,7 @@ def training_keys(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig
 def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_counts: Optional[torch.Tensor] = None,
                     allowed_bonds: Optional[Dict[str, object]] = None, connectivity_thresh: float = 0.5, device=None,
                     train_keys: Optional[torch.Tensor] = None, set_metrics: bool = False, sanitize: bool = False,
-                    masses: Optional[Dict[str, float]] = None, smiles: bool = False) -> Dict[str, float]:
+                    masses: Optional[Dict[str, float]] = None, smiles: bool = False, pose_check: bool = False) -> Dict[str, float]:
     """The part of `ModelAnalyzer.sample_and_analyze` (analysis/metrics.py:60-100) that needs no rdkit: `samples` is the list
     of {'positions', 'features'} dicts `_sample` returns, one per pocket; the result is `Molecules.metrics` over all of them
     and, with `set_metrics=True`, `Molecules.set_metrics` as well (uniqueness, novelty against `train_keys` if given, and the
@@ -1002,8 +1126,10 @@ def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_count
     rule is include/kpd.h's (`Molecules.sanitize`), NOT RDKit's.  With the default every key and value is what it was.
     `smiles=True` (implies `sanitize=True`): the result also has 'smiles', one list of strings per entry of `samples`: the SMILES
     of every ligand's largest fragment (upstream's `Chem.MolToSmiles(largest_mol)`; `Sanitized.smiles`, NOT RDKit's canonical
-    form), '' for a ligand without a molecule."""
-    sanitize = sanitize or smiles
+    form), '' for a ligand without a molecule.
+    `pose_check=True` (implies `sanitize=True`): the result also has 'plausible', the fraction of the sanitised, connected ligands
+    (those uniqueness is counted over) whose sampled pose passes `Sanitized.pose_check` without a pocket: NOT PoseBusters' number."""
+    sanitize = sanitize or smiles or pose_check
     lig_pos, lig_feat = [], []
     for rec in samples:
         lig_pos.extend(rec['positions'])
@@ -1018,12 +1144,27 @@ def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_count
         if smiles:
             strings, at = san.smiles(largest_frag=True), group_ptr.tolist()
             out['smiles'] = [strings[at[q]:at[q + 1]] for q in range(len(samples))]
+        if pose_check:
+            m = san.molecules
+            n = (m.lig_ptr[1:] - m.lig_ptr[:-1]).double()
+            keep = san.valid & (n > 0) & ((m.status & hip.MOL_BAD_SEGMENT) == 0) & (m.summary[:, 2].double() / n.clamp(min=1) >= connectivity_thresh)
+            n_keep = int(keep.sum())
+            out['plausible'] = float(san.pose_check().passed[:, 0][keep].double().mean()) if n_keep else 0.0
         return out
     out = mols.metrics(type_counts, connectivity_thresh)
     if set_metrics:
         group_ptr = torch.tensor([0] + [len(rec['positions']) for rec in samples], dtype=torch.int64).cumsum(0).to(torch.int32)
         out.update(mols.set_metrics(group_ptr, train_keys, connectivity_thresh))
     return out
+
+
+def check_samples(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig_elements: Sequence[str],
+                  pocket_pos: Optional[List[torch.Tensor]] = None, pocket_elements: Optional[List[Sequence[str]]] = None, pocket_of=None,
+                  allowed_bonds: Optional[Dict[str, object]] = None, radii: Optional[Dict[str, float]] = None, **thresholds) -> PoseChecks:
+    """Perceive, sanitise and check sampled ligands in one go: `build_molecules(...).sanitize().pose_check(...)` on the lists every
+    sampling entry point returns.  The limits of `Sanitized.pose_check` apply: NOT PoseBusters' numbers."""
+    return build_molecules(lig_pos, lig_feat, lig_elements, allowed_bonds).sanitize().pose_check(
+        None, pocket_pos, pocket_elements, pocket_of, radii=radii, **thresholds)
 
 
 def relax_samples(samples: List[dict], pockets: List[dict], lig_elements: Sequence[str], device=None,
