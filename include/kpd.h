@@ -646,7 +646,7 @@ kpd_status kpd_xyz_emit(const float *pos, const float *feat, const int32_t *lig_
  * (csrc/pocket.hip).  Replaces get_pocket_atoms (data_processing/pdbbind_processing.py:85-149, called by
  * process_crossdocked.py:112-119) and the residue-wise selection of process_bindingmoad.py:124-161 / byop.py:119-157:
  * ligand bounding box + padding (:92-97, :114-117), atoms closer than pocket_cutoff to a ligand atom (:124-128), expansion to
- * whole residues (torch.isin, :131-134), compaction (:137-138).  PDB / SDF parsing stays with the caller.
+ * whole residues (torch.isin, :131-134), compaction (:137-138).  The arrays come from files through kpd_pdb_parse / kpd_sdf_parse (end of this file).
  *   rec_x [n_rec,3], rec_ptr [B+1] (complex b = rows [rec_ptr[b], rec_ptr[b+1]), at most max_rec each), res_idx [n_rec]
  *   (per complex in [0, atoms of that complex), as prody's getResindices; need not be contiguous or sorted), probe [n_rec]
  *   bytes (atoms that count for the distance test), emit [n_rec] bytes (atoms that may appear in the pocket), lig_x [n_lig,3],
@@ -1500,6 +1500,121 @@ kpd_status kpd_vina_dock(const float *pos, const int32_t *lig_ptr, int32_t n_ato
                          const int32_t *lig_id, uint64_t seed, int32_t n_chains, int32_t n_steps, int32_t n_modes,
                          const kpd_vina_dock_params *params, float *pos_out, int32_t *n_found, double *report, float *chain_pos,
                          double *chain_report, int32_t *status, void *stream);
+
+/* Structure files (csrc/structure_io.hip): PDB text -> the arrays kpd_pocket_select takes, for a batch of files.  Replaces the
+ * parsing upstream leaves to prody / BioPython (byop.py:101-117, process_crossdocked.py:96-111, process_bindingmoad.py:124-135):
+ * per-file Python work that this library does on the device.  None of those packages is restated here, so THIS COMMENT IS THE
+ * DEFINITION; where it departs from them is listed at the end.  SDF / MOL input: kpd_sdf_parse below.
+ *
+ * Input: text [n_bytes] bytes and file_ptr [B+1] int64, both device: file b is text[file_ptr[b] : file_ptr[b+1]].  `text` needs no
+ *   alignment.  file_ptr must ascend within [0, n_bytes]; a file whose own segment does not (file_ptr[b] < 0, file_ptr[b+1] <
+ *   file_ptr[b] or > n_bytes) gets status bit 4 and no atoms, and what the other files of such a table read as is unspecified
+ *   (still nothing is read or written out of bounds).  n_bytes + B < 2^31 - 1 (KPD_ERR_CAPACITY).
+ * Lines: a line starts at file_ptr[b] of a non-empty file and behind every '\n' inside a file; it ends in front of the next line
+ *   start or at the end of its file, so a file boundary ends a line even without '\n'.  The line's content is its bytes without
+ *   that '\n' and then without one '\r' at the end; of the content only the first 80 bytes (columns 1 .. 80) are read, and
+ *   columns beyond the content read as blanks (0x20).  Tabs and bytes >= 0x80 are ordinary bytes: they are no blanks, digits or
+ *   letters, so they make a number they fall in unparsable.
+ * Real field (columns a .. b): blanks, one optional '+' or '-', digits with at most one '.', blanks; at least one digit ('1.' and
+ *   '.5' are real, '.', '+', '' are not); nothing else: no exponent, no 'nan' / 'inf', no blank inside.  With m the integer its
+ *   digits spell and k the number of digits behind the '.', the value is fp32(fp64(m) / fp64(10^k)), negated after the division
+ *   for '-': one IEEE fp64 division and one rounding to fp32, exact operands, hence numpy.float32(float(field)); '-0.000' is -0.0.
+ *   More than 15 digits (leading zeros not counted) or k > 15: unparsable.
+ * Integer field: blanks, optional sign, 1 .. 9 digits, blanks.  Anything else (hybrid-36, 'A000', '****') is unparsable.
+ * Records: a line whose columns 1-6 are 'ATOM  ' or 'HETATM' and lie inside the content is a record; one whose columns 1-6 are
+ *   'ENDMDL' ends the first model.  Kept are the records in front of the first ENDMDL line of their file, in file order: they are
+ *   the atoms, atom_ptr[b] .. atom_ptr[b+1] of file b.  Columns (wwPDB format 3.3, 1-based): name 13-16, altLoc 17, resName 18-20,
+ *   chainID 22, resSeq 23-26 (integer), iCode 27, x / y / z 31-38 / 39-46 / 47-54 (real), occupancy 55-60, tempFactor 61-66 (real),
+ *   element 77-78.  The serial (7-11) and everything else is not read ('*****' is fine).
+ * Out per atom (capacity cap_atoms rows; atom_ptr [B+1], atom_ptr[B] = the size needed, also when it exceeds cap_atoms; the atoms
+ *   of a file that does not fit are not written), all device:
+ *   pos [.,3]      x, y, z; all three NaN for a bad record (below)
+ *   occ_b [.,2]    occupancy, tempFactor; NaN where the field is blank, beyond the line or unparsable (no error)
+ *   sym            element symbol, up to two bytes NUL-padded little-endian as kpd_xyz_emit's `symbols`, 0 for none.  From the
+ *                  non-blank bytes of columns 77-78 in order, a letter in first place in upper and in second place in lower case,
+ *                  other bytes as they are.  If both columns are blank, from columns 13-14 = (a, b) by the first rule that applies
+ *                  (flag bit 6 says so): a is blank or a digit: b.  a is a letter and resName is a standard amino acid: a
+ *                  ('HD11', 'HH11' are hydrogens).  a and b are letters and a b, in that case form, is one of
+ *                    Li Be Ne Na Mg Al Si Cl Ar Ca Sc Ti Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Zr Mo Ru Rh Pd Ag Cd In Sn
+ *                    Sb Te Xe Cs Ba Pt Au Pb
+ *                  : that symbol.  Otherwise a.  A heuristic, as BioPython's is.
+ *   elem           index of sym in the caller's symbols [F] (first match), or F: upstream's "other" column
+ *   name, resname  columns 13-16 / 18-20 as they are, packed little-endian (column 13 / 18 in the low byte)
+ *   res_class      index of resname in the caller's resnames [R] (packed the same way), or R: upstream's aa_to_idx for ca_only
+ *   resseq         the integer of columns 23-26, 0 when unparsable
+ *   tags           chainID | iCode << 8 | altLoc << 16
+ *   line_off       int64: offset of the record's first byte in text (slice the lines of selected atoms back out as pocket.pdb)
+ *   res_idx        a kept record starts a residue if it is the first of its file or if its columns 18-20 and 22-27 (resName,
+ *                  chainID, resSeq, iCode; compared as bytes) differ from those of the kept record before it.  res_idx = the
+ *                  number of starts up to and including the record, minus 1, per file.  The run-length reading of a PDB file
+ *                  (BioPython's); equal to prody's getResindices when the atoms of every residue are contiguous.
+ *                  kpd_pocket_select uses only equality of these labels.
+ *   flags          bit 0 HETATM, bit 1 hydrogen (sym is H or D), bit 2 water (resName one of HOH DOD WAT H2O OH2 TIP SOL), bit 3
+ *                  altLoc neither blank nor 'A', bit 4 standard amino acid (resName one of ALA ARG ASN ASP CYS GLN GLU GLY HIS ILE
+ *                  LEU LYS MET PHE PRO SER THR TRP TYR VAL), bit 5 C-alpha (name ' CA ' and bit 4), bit 6 element guessed from
+ *                  the name, bit 7 bad record: content shorter than 54 columns, or x, y, z or resSeq unparsable.
+ *   No filtering happens here: the flags become the probe / emit masks of kpd_pocket_select.
+ * Out per file: n_res [B] (residue starts), status [B]: bit 0 = no atom, bit 1 = cap_atoms too small for this file, bit 2 = a bad
+ *   record, bit 3 = records behind the first ENDMDL were ignored, bit 4 = malformed segment, bit 5 = cap_lines too small (no file
+ *   is parsed then).  n_lines [1] = lines of the whole buffer, the cap_lines needed.
+ * scratch: kpd_pdb_scratch_bytes(n_bytes, B, cap_lines) device bytes; it holds the table of line starts.  Six launches whatever B
+ *   is; no host synchronisation; no float atomics; bitwise independent of batch composition.  The line scan reads the buffer in
+ *   tiles of KPD_STRUCT_TILE bytes with aligned 16-byte loads (the partial 16 bytes at either end byte by byte).
+ * Nothing is read or written out of bounds for any bytes of text whatsoever.
+ * Known deviations: no hybrid-36, no exponents (Python's float takes them); altloc choice is the caller's (flag bit 3 is prody's
+ *   default, not BioPython's highest occupancy); water is the list above, not prody's selection grammar; CONECT, TER, MODEL,
+ *   ANISOU and SEQRES are not read; mmCIF, PDBQT and gzip are not supported. */
+#define KPD_STRUCT_TILE 4096
+int64_t kpd_pdb_scratch_bytes(int64_t n_bytes, int32_t B, int32_t cap_lines);
+kpd_status kpd_pdb_parse(const uint8_t *text, int64_t n_bytes, const int64_t *file_ptr, int32_t B, const uint32_t *symbols, int32_t F,
+                         const uint32_t *resnames, int32_t R, int32_t cap_lines, int32_t cap_atoms, float *pos, float *occ_b,
+                         uint32_t *sym, int32_t *elem, uint32_t *name, uint32_t *resname, int32_t *res_class, int32_t *resseq,
+                         uint32_t *tags, int64_t *line_off, int32_t *res_idx, int32_t *flags, int32_t *atom_ptr, int32_t *n_res,
+                         int32_t *status, int32_t *n_lines, void *scratch, void *stream);
+
+/* kpd_sdf_parse: SDF / MOL V2000 text -> molecules in exactly the layout kpd_mol_perceive writes, so that every consumer of that
+ * layout (kpd_sdf_emit, kpd_mol_keys, kpd_mol_sanitize, kpd_pose_rmsd, kpd_vina_score, kpd_relax, ...) takes a file's ligand
+ * unchanged, with the bonds the file states instead of perceived ones.  Replaces parse_ligand (data_processing/
+ * pdbbind_processing.py:45-83: rdkit's SDMolSupplier(sanitize=False) and RemoveAllHs).  THIS COMMENT IS THE DEFINITION.
+ * text, file_ptr, lines, real and integer fields: as for kpd_pdb_parse.
+ * Records: a line whose first four bytes are '$$$$' closes a record; the lines of a file behind its last '$$$$' line (all of them
+ *   if it has none: one bare MOL block) are one more record unless every one of them is without content.  mol_ptr [B+1]: file b
+ *   holds the records mol_ptr[b] .. mol_ptr[b+1]; mol_ptr[B] = M, the records of the call, is the cap_mols needed.  The records of
+ *   a file whose records do not all fit cap_mols are not parsed (file_status bit 1).
+ * A record, by line: title, program, comment, counts, n_a atom lines, n_b bond lines, property lines up to 'M  END'; what follows
+ *   (data items) is not read.  Counts line: n_a = integer of columns 1-3, n_b = integer of columns 4-6, columns 35-39 'V2000'.
+ *   Atom line: x / y / z = reals of columns 1-10 / 11-20 / 21-30; symbol = the non-blank bytes of columns 32-34 up to the first
+ *   blank behind them, the first in upper and the others in lower case, packed as kpd_xyz_emit's `symbols`; columns 35-36 (mass
+ *   difference) and 37-39 (charge): an integer other than 0 sets status bit 5.  Bond line: i, j, type = integers of columns 1-3,
+ *   4-6, 7-9 (1-based atoms of the block).  Type 1 / 2 / 3 is the order; type 4 is written as order 1 and sets status bit 4
+ *   ("aromatic bond type: call kpd_mol_sanitize").  A property line 'M  CHG' or 'M  ISO' sets status bit 5 ("charges / isotopes
+ *   present, ignored": the library carries none).
+ * remove_h != 0: atoms whose symbol is H or D are dropped with their bonds and the others renumbered in order (RemoveAllHs, :66-67).
+ * Out per record (all device; capacity cap_mols records, cap_atoms atoms, cap_bonds bonds):
+ *   lig_ptr [cap_mols+1] (record m's atoms are rows lig_ptr[m] .. lig_ptr[m+1]; lig_ptr[M] = atoms needed; entries behind M repeat
+ *   it), pos [.,3], sym, elem (index of sym in symbols [F], or F for "other": such an atom sets status bit 2, is invalid in step 6,
+ *   and upstream raises Unparsable for its ligand), valence (sum of its bonds' orders), frag; bond_ij [cap_bonds,2] (global rows,
+ *   i < j, per record sorted by i then j whatever the file's order), bond_order, bond_ptr [cap_mols+1]; summary [cap_mols,4] and
+ *   frag by steps 5-6 of kpd_mol_perceive with the caller's z and allowed [F] (an atom whose class is F or whose z the element
+ *   table does not know is invalid); title_off [cap_mols,2] int64 = begin and end of the title line's content in text;
+ *   status [cap_mols]: bits 0-3 are kpd_mol_perceive's (0 = no atom, 1 = cap_atoms or cap_bonds too small for this record: nothing
+ *   but lig_ptr / bond_ptr is written for it, 2 = an "other" or unknown element, 3 = record left out), 4 and 5 as above, and why it
+ *   was left out: 6 = 'V3000' in columns 35-39, 7 = unparsable (count, version, coordinate, blank symbol, bond index or type; a bond
+ *   to atom 0 or beyond n_a; types 5-8), 8 = truncated (fewer lines than 4 + n_a + n_b, or no 'M  END' behind them), 9 = a self
+ *   bond, a repeated bond, or after hydrogen removal more than 256 atoms, more than 3 n bonds or an atom with more than 6 bonds.
+ *   A record that is left out has no atoms and no bonds (lig_ptr[m+1] = lig_ptr[m]) and summary 0.
+ * Out per file: mol_ptr, file_status [B]: bit 1 = cap_mols too small, bit 4 = malformed segment, bit 5 = cap_lines too small.
+ *   n_lines [1] as for kpd_pdb_parse.  scratch: kpd_sdf_parse_scratch_bytes(n_bytes, B, cap_lines, cap_mols).
+ * One wave per record.  Ten launches and one memset whatever B is; no host synchronisation; no float atomics; bitwise independent
+ *   of batch composition.  Nothing is read or written out of bounds for any bytes of text whatsoever.
+ * Not read: V3000 blocks, formal charges, isotopes, stereo flags, atom lists, SGroups; MOL2 and PDBQT are not supported. */
+int64_t kpd_sdf_parse_scratch_bytes(int64_t n_bytes, int32_t B, int32_t cap_lines, int32_t cap_mols);
+kpd_status kpd_sdf_parse(const uint8_t *text, int64_t n_bytes, const int64_t *file_ptr, int32_t B, const uint32_t *symbols, int32_t F,
+                         const int32_t *z, const int32_t *allowed, int32_t remove_h, int32_t cap_lines, int32_t cap_mols,
+                         int32_t cap_atoms, int32_t cap_bonds, int32_t *mol_ptr, int32_t *file_status, int32_t *lig_ptr, float *pos,
+                         uint32_t *sym, int32_t *elem, int32_t *valence, int32_t *frag, int32_t *bond_ij, int32_t *bond_order,
+                         int32_t *bond_ptr, int32_t *summary, int64_t *title_off, int32_t *status, int32_t *n_lines, void *scratch,
+                         void *stream);
 
 #ifdef __cplusplus
 }

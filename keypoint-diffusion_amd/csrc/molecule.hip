@@ -196,112 +196,10 @@ k_mol_perceive(const float *__restrict__ pos, const float *__restrict__ feat, co
         }
         __syncthreads();
     }
-    // step 5: fragments by label propagation (the fixed point is the lowest atom of every component)
-#pragma unroll
-    for (int k = 0; k < MOL_K; ++k) {
-        label[lane + 64 * k] = lane + 64 * k;
-        fsize[lane + 64 * k] = 0;
-    }
-    __syncthreads();
-    for (;;) {
-        bool changed = false;
-#pragma unroll
-        for (int k = 0; k < MOL_K; ++k) {
-            const int i = lane + 64 * k;
-            if (i >= n) continue;
-            int l = label[i];
-            const int before = l;
-            for (int w = 0; w < MOL_W; ++w) {
-                unsigned bits = A1[i * MOL_W + w];
-                while (bits) {
-                    l = min(l, label[32 * w + __ffs(bits) - 1]);
-                    bits &= bits - 1;
-                }
-            }
-            l = min(l, label[l]);                   // pointer jump
-            if (l != before) {
-                label[i] = l;
-                changed = true;
-            }
-        }
-        __syncthreads();
-        if (!__any(changed)) break;                 // wave-uniform
-    }
-    unsigned long long roots[MOL_K];
-#pragma unroll
-    for (int k = 0; k < MOL_K; ++k) {
-        const int i = lane + 64 * k;
-        roots[k] = __ballot(i < n && label[i] == i);
-        if (i < n) atomicAdd(&fsize[label[i]], 1);
-    }
-    __syncthreads();
-    int n_frags = 0;
-#pragma unroll
-    for (int k = 0; k < MOL_K; ++k) n_frags += __popcll(roots[k]);
-    // largest fragment: most atoms, then the lowest rank (= the lowest root)
-    int lo = 0, lj = -1;
-    double unused = 0.0;
-#pragma unroll
-    for (int k = 0; k < MOL_K; ++k) {
-        const int i = lane + 64 * k;
-        if (i < n && label[i] == i && fsize[i] > lo) {
-            lo = fsize[i];
-            lj = MOL_MAX - i;
-        }
-    }
-    wave_argmax(lo, unused, lj);
-    // per-atom outputs, step 6
-    int invalid = 0, mine[MOL_K], total = 0;
-#pragma unroll
-    for (int k = 0; k < MOL_K; ++k) {
-        const int i = lane + 64 * k;
-        mine[k] = 0;
-        if (i < n) {
-            int val = 0;
-            for (int w = 0; w < MOL_W; ++w) {
-                val += __popc(A1[i * MOL_W + w]) + __popc(A2[i * MOL_W + w]) + __popc(A3[i * MOL_W + w]);
-                unsigned up = A1[i * MOL_W + w];
-                if (32 * w + 31 <= i) up = 0;
-                else if (32 * w <= i) up &= ~((2u << (i & 31)) - 1u);
-                mine[k] += __popc(up);
-            }
-            const int root = label[i];
-            int rank = 0;
-#pragma unroll
-            for (int q = 0; q < MOL_K; ++q) {
-                const int below = root - 64 * q;    // roots of chunk q below `root`
-                if (below >= 64) rank += __popcll(roots[q]);
-                else if (below > 0) rank += __popcll(roots[q] & ((1ull << below) - 1ull));
-            }
-            valence[a0 + i] = val;
-            frag[a0 + i] = rank;
-            invalid += (val == 0 || val > allowed[cls[k]]) ? 1 : 0;     // an unknown element is never bonded: valence 0
-        }
-    }
-    invalid = wave_sum(invalid);
-    // bonds in (i, j) order into the ligand's part of the scratch list
-    int base = 0;
-#pragma unroll
-    for (int k = 0; k < MOL_K; ++k) {
-        int chunk;
-        int at = base + wave_exclusive(mine[k], lane, chunk);
-        base += chunk;
-        const int i = lane + 64 * k;
-        if (i >= n) continue;
-        for (int w = i >> 5; w < MOL_W; ++w) {
-            unsigned bits = A1[i * MOL_W + w];
-            if (32 * w <= i) bits &= (i & 31) == 31 ? 0u : ~((2u << (i & 31)) - 1u);
-            while (bits) {
-                const int t = __ffs(bits) - 1, j = 32 * w + t;
-                bits &= bits - 1;
-                const size_t r = (size_t)3 * a0 + at++;
-                tmp_ij[r * 2] = a0 + i;
-                tmp_ij[r * 2 + 1] = a0 + j;
-                tmp_order[r] = 1 + (int)((A2[i * MOL_W + w] >> t) & 1u) + (int)((A3[i * MOL_W + w] >> t) & 1u);
-            }
-        }
-    }
-    total = base;
+    // steps 5 and 6, the per-atom outputs, and the bonds in (i, j) order into the ligand's part of the scratch list
+    int n_frags, lo, invalid, total;
+    mol_fragments_out(A1, A2, A3, label, fsize, n, lane, a0, [&](int k, int val) { return val == 0 || val > allowed[cls[k]]; }, valence, frag,
+                      tmp_ij + (size_t)6 * a0, tmp_order + (size_t)3 * a0, n_frags, lo, invalid, total);
     st = __any(st != 0) ? MOL_BAD_ATOM : 0;
     if (lane == 0) {
         n_bonds[b] = total;

@@ -124,6 +124,122 @@ __device__ __forceinline__ double wave_max(double v) {      // a maximum has no 
 
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }      // false for NaN too
 
+// ---- steps 5 and 6 of kpd_mol_perceive, for a wave that holds a ligand's bond graph as bit matrices (k_mol_perceive; k_sdf_records
+// of structure_io.hip, whose bonds come from a file) ----------------------------------------------------------------------------------
+// A1 / A2 / A3 [n x MOL_W words]: bonded / order >= 2 / order >= 3, symmetric; label, fsize [MOL_MAX]: LDS scratch.
+// Writes valence and frag of the atoms a0 .. a0 + n - 1 and, unless ij_dst is null, the bonds in (i, j) order (global rows) to
+// ij_dst / order_dst.  invalid_atom(k, valence) is step 6 for the lane's k-th atom.  Out, on every lane: fragments, atoms of the
+// largest one, invalid atoms, bonds.
+template <class Invalid>
+__device__ __forceinline__ void mol_fragments_out(const unsigned *A1, const unsigned *A2, const unsigned *A3, int *label, int *fsize, int n,
+                                                  int lane, int a0, Invalid invalid_atom, int *__restrict__ valence, int *__restrict__ frag,
+                                                  int *__restrict__ ij_dst, int *__restrict__ order_dst, int &n_frags, int &largest,
+                                                  int &invalid, int &total) {
+    // step 5: fragments by label propagation (the fixed point is the lowest atom of every component)
+#pragma unroll
+    for (int k = 0; k < MOL_K; ++k) {
+        label[lane + 64 * k] = lane + 64 * k;
+        fsize[lane + 64 * k] = 0;
+    }
+    __syncthreads();
+    for (;;) {
+        bool changed = false;
+#pragma unroll
+        for (int k = 0; k < MOL_K; ++k) {
+            const int i = lane + 64 * k;
+            if (i >= n) continue;
+            int l = label[i];
+            const int before = l;
+            for (int w = 0; w < MOL_W; ++w) {
+                unsigned bits = A1[i * MOL_W + w];
+                while (bits) {
+                    l = min(l, label[32 * w + __ffs(bits) - 1]);
+                    bits &= bits - 1;
+                }
+            }
+            l = min(l, label[l]);                   // pointer jump
+            if (l != before) {
+                label[i] = l;
+                changed = true;
+            }
+        }
+        __syncthreads();
+        if (!__any(changed)) break;                 // wave-uniform
+    }
+    unsigned long long roots[MOL_K];
+#pragma unroll
+    for (int k = 0; k < MOL_K; ++k) {
+        const int i = lane + 64 * k;
+        roots[k] = __ballot(i < n && label[i] == i);
+        if (i < n) atomicAdd(&fsize[label[i]], 1);
+    }
+    __syncthreads();
+    n_frags = 0;
+#pragma unroll
+    for (int k = 0; k < MOL_K; ++k) n_frags += __popcll(roots[k]);
+    // largest fragment: most atoms, then the lowest rank (= the lowest root)
+    int best = 0;
+#pragma unroll
+    for (int k = 0; k < MOL_K; ++k) {
+        const int i = lane + 64 * k;
+        if (i < n && label[i] == i) best = max(best, fsize[i] * (MOL_MAX + 1) + (MOL_MAX - i));
+    }
+    largest = wave_max(best) / (MOL_MAX + 1);
+    // per-atom outputs, step 6
+    int mine[MOL_K];
+    invalid = 0;
+#pragma unroll
+    for (int k = 0; k < MOL_K; ++k) {
+        const int i = lane + 64 * k;
+        mine[k] = 0;
+        if (i < n) {
+            int val = 0;
+            for (int w = 0; w < MOL_W; ++w) {
+                val += __popc(A1[i * MOL_W + w]) + __popc(A2[i * MOL_W + w]) + __popc(A3[i * MOL_W + w]);
+                unsigned up = A1[i * MOL_W + w];
+                if (32 * w + 31 <= i) up = 0;
+                else if (32 * w <= i) up &= ~((2u << (i & 31)) - 1u);
+                mine[k] += __popc(up);
+            }
+            const int root = label[i];
+            int rank = 0;
+#pragma unroll
+            for (int q = 0; q < MOL_K; ++q) {
+                const int below = root - 64 * q;    // roots of chunk q below `root`
+                if (below >= 64) rank += __popcll(roots[q]);
+                else if (below > 0) rank += __popcll(roots[q] & ((1ull << below) - 1ull));
+            }
+            valence[a0 + i] = val;
+            frag[a0 + i] = rank;
+            invalid += invalid_atom(k, val) ? 1 : 0;
+        }
+    }
+    invalid = wave_sum(invalid);
+    // bonds in (i, j) order
+    int base = 0;
+#pragma unroll
+    for (int k = 0; k < MOL_K; ++k) {
+        int chunk;
+        int at = base + wave_exclusive(mine[k], lane, chunk);
+        base += chunk;
+        const int i = lane + 64 * k;
+        if (i >= n || !ij_dst) continue;
+        for (int w = i >> 5; w < MOL_W; ++w) {
+            unsigned bits = A1[i * MOL_W + w];
+            if (32 * w <= i) bits &= (i & 31) == 31 ? 0u : ~((2u << (i & 31)) - 1u);
+            while (bits) {
+                const int t = __ffs(bits) - 1, j = 32 * w + t;
+                bits &= bits - 1;
+                const size_t r = (size_t)at++;
+                ij_dst[r * 2] = a0 + i;
+                ij_dst[r * 2 + 1] = a0 + j;
+                order_dst[r] = 1 + (int)((A2[i * MOL_W + w] >> t) & 1u) + (int)((A3[i * MOL_W + w] >> t) & 1u);
+            }
+        }
+    }
+    total = base;
+}
+
 // ---- one workgroup takes one perceived ligand and its pocket (kpd_relax, kpd_vina_score, kpd_vina_minimize) ---------------------------------
 enum : int { LP_NO_MOLECULE = 1, LP_BAD_INPUT = 2 };     // bits 0 and 1 of both status words
 

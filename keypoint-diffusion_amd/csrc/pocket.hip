@@ -1,7 +1,7 @@
 // Pocket extraction on the device: from whole receptors + ligands to pocket atoms and interface points, for a batch.
 // Replaces, for the array-level part, get_pocket_atoms (data_processing/pdbbind_processing.py:85-149), get_interface_points
-// (:295-325) and the residue-wise selection of process_bindingmoad.py:124-204 / byop.py:119-197.  File parsing stays with
-// the caller.  Every decision (d < cutoff, d < dist_thr, d >= excl_thr) is taken on squared distances computed in fp64 from
+// (:295-325) and the residue-wise selection of process_bindingmoad.py:124-204 / byop.py:119-197.  File parsing is
+// structure_io.hip.  Every decision (d < cutoff, d < dist_thr, d >= excl_thr) is taken on squared distances computed in fp64 from
 // direct differences of the fp32 coordinates: exact differences, no matmul form, so no wobble at the thresholds.
 // Small latency-bound kernels: a complex is one workgroup (or one row of tiles in k_pocket_mark); nothing is shared between
 // complexes, there are no float atomics, and results are bitwise independent of batch composition.

@@ -252,6 +252,14 @@ def lib():
     L.kpd_vina_dock.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 +
                                 [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
                                 [C.c_uint64] + [C.c_int32] * 3 + [C.POINTER(KpdVinaDockParams)] + [C.c_void_p] * 7)
+    L.kpd_pdb_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    L.kpd_pdb_scratch_bytes.restype = C.c_int64
+    L.kpd_pdb_parse.argtypes = ([C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                 C.c_int32] + [C.c_void_p] * 18)
+    L.kpd_sdf_parse_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    L.kpd_sdf_parse_scratch_bytes.restype = C.c_int64
+    L.kpd_sdf_parse.argtypes = ([C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 +
+                                [C.c_void_p] * 17)
     _lib = L
     return L
 
@@ -288,6 +296,7 @@ EXPORTS = [
     'kpd_pose_check', 'kpd_relax_defaults', 'kpd_relax',
     'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score', 'kpd_vina_min_defaults', 'kpd_vina_minimize',
     'kpd_vina_dock_defaults', 'kpd_vina_dock',
+    'kpd_pdb_scratch_bytes', 'kpd_pdb_parse', 'kpd_sdf_parse_scratch_bytes', 'kpd_sdf_parse',
 ]
 
 
@@ -1835,3 +1844,124 @@ def clash_score(lig_x: torch.Tensor, lig_ptr: torch.Tensor, wall_x: torch.Tensor
     out = torch.empty(B, 3, device=lig_x.device, dtype=torch.float32)
     check(lib().kpd_clash_score(B, _ptr(lig_ptr), _ptr(lig_x), _ptr(wall_ptr), _ptr(wall_x), float(threshold), _ptr(out), _stream()))
     return out
+
+
+STRUCT_TILE = 4096            # KPD_STRUCT_TILE of include/kpd.h: bytes of text per workgroup of the line scan (the tests sit on its edges)
+PDB_HETATM, PDB_HYDROGEN, PDB_WATER, PDB_ALTLOC, PDB_STD_AA, PDB_CALPHA, PDB_GUESSED, PDB_BAD = 1, 2, 4, 8, 16, 32, 64, 128   # flags
+PDB_EMPTY, PDB_CAPACITY, PDB_BAD_RECORD, PDB_MODELS, PDB_BAD_SEGMENT, PDB_LINES = 1, 2, 4, 8, 16, 32                            # status
+_PDB_FIELDS = (('pos', torch.float32, 3), ('occ_b', torch.float32, 2), ('sym', torch.int32, 0), ('elem', torch.int32, 0),
+               ('name', torch.int32, 0), ('resname', torch.int32, 0), ('res_class', torch.int32, 0), ('resseq', torch.int32, 0),
+               ('tags', torch.int32, 0), ('line_off', torch.int64, 0), ('res_idx', torch.int32, 0), ('flags', torch.int32, 0))
+
+
+def _text_args(where: str, text, file_ptr):
+    if not (isinstance(text, torch.Tensor) and text.is_cuda and text.dtype == torch.uint8 and text.dim() == 1):
+        raise KpdError(f'{where}: text must be a 1-D uint8 GPU tensor (got {getattr(text, "device", type(text))}); there is no CPU parser')
+    if not (isinstance(file_ptr, torch.Tensor) and file_ptr.is_cuda and file_ptr.dtype == torch.int64 and file_ptr.dim() == 1 and
+            file_ptr.numel() >= 1 and file_ptr.is_contiguous()):
+        raise KpdError(f'{where}: file_ptr must be a contiguous int64 GPU tensor of B + 1 offsets')
+    if not text.is_contiguous():
+        raise KpdError(f'{where}: text must be contiguous (a slice text[k:] is; a strided view is not)')
+    return int(text.numel()), int(file_ptr.numel()) - 1
+
+
+def pdb_parse(text: torch.Tensor, file_ptr: torch.Tensor, elements, resnames=(), cap_lines: Optional[int] = None,
+              cap_atoms: Optional[int] = None):
+    """ATOM / HETATM records of a batch of PDB files on the GPU (kpd_pdb_parse; include/kpd.h states every column and rounding).
+    text [n_bytes] uint8 and file_ptr [B+1] int64 GPU tensors (file b = text[file_ptr[b]:file_ptr[b+1]]; no alignment needed),
+    elements: F symbols in Title case ('C', 'Cl'), resnames: R residue names of exactly three characters.  Without capacities
+    the call sizes its tables from the text's length and repeats itself while the sizes a call reports are larger (unusual text only); with
+    them it is one call, and what does not fit is reported, not written.  Returns a dict: the per-atom device tensors pos, occ_b,
+    sym, elem, name, resname, res_class, resseq, tags, line_off, res_idx, flags (cut to the atoms written), and the host lists
+    atom_ptr (B + 1; the last is the size needed), n_res, status (B each) and n_lines.  One host read per call."""
+    n_bytes, B = _text_args('pdb_parse', text, file_ptr)
+    dev = text.device
+    symbols = _packed_symbols(elements, dev, longest=2)
+    for r in resnames:
+        if len(r.encode('ascii')) != 3:
+            raise KpdError(f'residue name {r!r} must be exactly three ASCII characters (columns 18-20 as they are)')
+    rn = _packed_symbols(resnames, dev, longest=3) if len(resnames) else torch.zeros(0, dtype=torch.int32, device=dev)
+    cl = n_bytes // 32 + B + 16 if cap_lines is None else int(cap_lines)
+    ca = n_bytes // 60 + B + 16 if cap_atoms is None else int(cap_atoms)
+    while True:
+        out = {name: torch.empty((ca, w) if w else (ca,), dtype=dt, device=dev) for name, dt, w in _PDB_FIELDS}
+        meta = torch.empty(3 * B + 2, dtype=torch.int32, device=dev)     # atom_ptr [B + 1], n_res [B], status [B], n_lines [1]
+        nb = int(lib().kpd_pdb_scratch_bytes(n_bytes, B, cl))
+        if nb < 0:
+            raise KpdError(f'pdb_parse: {n_bytes} bytes in {B} files: at most 2^31 - 2 together per call')
+        scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+        base = meta.data_ptr()
+        check(lib().kpd_pdb_parse(_ptr(text), n_bytes, _ptr(file_ptr), B, _ptr(symbols), len(elements), _ptr(rn), len(resnames), cl, ca,
+                                  *[_ptr(out[name]) for name, _, _ in _PDB_FIELDS], base, base + 4 * (B + 1), base + 4 * (2 * B + 1),
+                                  base + 4 * (3 * B + 1), _ptr(scratch), _stream()))
+        host = meta.cpu().tolist()
+        atom_ptr, n_lines = host[:B + 1], host[-1]
+        if (cap_lines is None and n_lines > cl) or (cap_atoms is None and atom_ptr[-1] > ca):
+            cl = max(cl, n_lines) if cap_lines is None else cl          # with too few lines no atom was counted: the atoms may take a third call
+            ca = max(ca, atom_ptr[-1]) if cap_atoms is None else ca
+            continue
+        break
+    n = min(atom_ptr[-1], ca)
+    res = {name: t[:n] for name, t in out.items()}
+    res.update(atom_ptr=atom_ptr, n_res=host[B + 1:2 * B + 1], status=host[2 * B + 1:3 * B + 1], n_lines=n_lines)
+    return res
+
+
+# status bits of kpd_sdf_parse beside MOL_*: why a record reads as it does, or was left out (MOL_BAD_SEGMENT)
+SDF_AROMATIC, SDF_CHARGES, SDF_V3000, SDF_UNPARSABLE, SDF_TRUNCATED, SDF_LIMITS = 16, 32, 64, 128, 256, 512
+
+
+def sdf_parse(text: torch.Tensor, file_ptr: torch.Tensor, elements, z, allowed, remove_h: bool = True, cap_lines: Optional[int] = None,
+              cap_mols: Optional[int] = None, cap_atoms: Optional[int] = None, cap_bonds: Optional[int] = None):
+    """MOL V2000 records of a batch of SDF files on the GPU, in the layout `mol_perceive` returns (kpd_sdf_parse; include/kpd.h
+    states the format and every reason a record is left out).  text / file_ptr as for `pdb_parse`; elements, z, allowed: the F
+    symbols, atomic numbers and largest valences of the ligand classes.  Capacities as for `pdb_parse`: sized from the text, and
+    repeated while a call reports larger sizes.  Returns a dict: device tensors lig_ptr [M+1], pos, sym, elem, valence, frag, bonds
+    [cap_bonds,2], order, bond_ptr [M+1], summary [M,4], status [M], title_off [M,2], and host lists mol_ptr (B + 1), file_status
+    (B), sizes (atoms per record), n_bonds and n_lines.  One host read per call."""
+    n_bytes, B = _text_args('sdf_parse', text, file_ptr)
+    F = len(elements)
+    if F < 1 or len(z) != F or len(allowed) != F:
+        raise KpdError(f'sdf_parse: {F} element symbols, {len(z)} atomic numbers, {len(allowed)} valences')
+    dev = text.device
+    symbols = _packed_symbols(elements, dev, longest=3)
+    zt, at = torch.tensor(list(z), dtype=torch.int32, device=dev), torch.tensor(list(allowed), dtype=torch.int32, device=dev)
+    given = dict(lines=cap_lines, mols=cap_mols, atoms=cap_atoms, bonds=cap_bonds)
+    cap = dict(lines=n_bytes // 24 + B + 16, mols=n_bytes // 1024 + B + 16, atoms=n_bytes // 60 + 16, bonds=n_bytes // 13 // 4 + 16)
+    cap.update({k: int(v) for k, v in given.items() if v is not None})
+    while True:
+        cm, ca, cb = cap['mols'], cap['atoms'], cap['bonds']
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        out = dict(pos=torch.empty(ca, 3, dtype=torch.float32, device=dev), sym=i32(ca), elem=i32(ca), valence=i32(ca), frag=i32(ca),
+                   bonds=i32(cb, 2), order=i32(cb), summary=i32(cm, 4), status=i32(cm), title_off=torch.empty(cm, 2, dtype=torch.int64, device=dev))
+        meta = torch.empty(2 * B + 2 + 2 * (cm + 1), dtype=torch.int32, device=dev)    # mol_ptr [B+1], file_status [B], n_lines, lig_ptr, bond_ptr [cm+1]
+        nb = int(lib().kpd_sdf_parse_scratch_bytes(n_bytes, B, cap['lines'], cm))
+        if nb < 0:
+            raise KpdError(f'sdf_parse: {n_bytes} bytes in {B} files: at most 2^31 - 2 together per call')
+        scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+        base = meta.data_ptr()
+        p_fs, p_nl = base + 4 * (B + 1), base + 4 * (2 * B + 1)
+        p_lig = base + 4 * (2 * B + 2)
+        p_bp = p_lig + 4 * (cm + 1)
+        check(lib().kpd_sdf_parse(_ptr(text), n_bytes, _ptr(file_ptr), B, _ptr(symbols), F, _ptr(zt), _ptr(at), 1 if remove_h else 0, cap['lines'],
+                                  cm, ca, cb, base, p_fs, p_lig, _ptr(out['pos']), _ptr(out['sym']), _ptr(out['elem']), _ptr(out['valence']),
+                                  _ptr(out['frag']), _ptr(out['bonds']), _ptr(out['order']), p_bp, _ptr(out['summary']), _ptr(out['title_off']),
+                                  _ptr(out['status']), p_nl, _ptr(scratch), _stream()))
+        host = meta.cpu().tolist()
+        mol_ptr, file_status, n_lines = host[:B + 1], host[B + 1:2 * B + 1], host[2 * B + 1]
+        lig_ptr, bond_ptr = host[2 * B + 2:2 * B + 3 + cm], host[2 * B + 3 + cm:]
+        need = dict(lines=n_lines, mols=mol_ptr[-1], atoms=lig_ptr[-1], bonds=bond_ptr[-1])
+        short = [k for k in cap if need[k] > cap[k] and given[k] is None]
+        if short:                                           # lines, then records, then atoms and bonds: each is counted once the one before fits
+            for k in short:
+                cap[k] = need[k]
+            continue
+        break
+    M = min(mol_ptr[-1], cm)
+    n_at, n_bo = min(lig_ptr[M], ca), bond_ptr[M]
+    off = 2 * B + 2
+    res = dict(lig_ptr=meta[off:off + M + 1], bond_ptr=meta[off + cm + 1:off + cm + 2 + M], pos=out['pos'][:n_at], sym=out['sym'][:n_at],
+               elem=out['elem'][:n_at], valence=out['valence'][:n_at], frag=out['frag'][:n_at], bonds=out['bonds'], order=out['order'],
+               summary=out['summary'][:M], status=out['status'][:M], title_off=out['title_off'][:M], mol_ptr=mol_ptr, file_status=file_status,
+               sizes=[lig_ptr[m + 1] - lig_ptr[m] for m in range(M)], n_bonds=n_bo, n_atoms=lig_ptr[M], n_lines=n_lines)
+    return res

@@ -198,6 +198,13 @@ class Molecules:
     def __len__(self) -> int:
         return int(self.lig_ptr.numel()) - 1
 
+    @classmethod
+    def from_sdf(cls, files, lig_elements: Sequence[str], remove_hydrogen: bool = True, allowed_bonds: Optional[Dict[str, object]] = None,
+                 device='cuda') -> 'Molecules':
+        """The molecules of SDF / MOL V2000 files, with the bonds the files state: `structure.read_sdf`."""
+        from . import structure
+        return structure.read_sdf(files, lig_elements, remove_hydrogen=remove_hydrogen, allowed_bonds=allowed_bonds, device=device)
+
     def sdf(self, largest_frag: bool = False, strict: bool = True) -> List[str]:
         """One MOL V2000 block (closed by `$$$$`) per ligand, written on the GPU; `largest_frag`: only the largest fragment,
         renumbered (upstream's `process_molecule(largest_frag=True)`).  A ligand that has no block (left out, a non-finite
@@ -1107,6 +1114,16 @@ def training_keys(lig_pos: List[torch.Tensor], lig_feat: List[torch.Tensor], lig
     `build_molecules`).  The ligands are perceived by the same rule as the samples, so novelty compares like with like; pass
     the `largest_frag` / `with_orders` the samples' keys will be computed with.  Ligands without a molecule are left out."""
     mols = build_molecules(lig_pos, lig_feat, lig_elements)
+    r = mols._keys(largest_frag, with_orders)
+    return torch.unique(r['key'][(r['status'] & hip.KEY_NO_MOLECULE) == 0])
+
+
+def training_keys_from_sdf(files, lig_elements: Sequence[str], largest_frag: bool = True, with_orders: bool = True,
+                           remove_hydrogen: bool = True, device='cuda') -> torch.Tensor:
+    """`training_keys` of ligands read from SDF files, with the bonds the files state (not perceived ones): a sorted int64 tensor
+    without repeats.  Records without a molecule are left out.  Keys of file bonds compare with keys of samples only as far as
+    the perceived bonds of the samples agree with what a file would state; with_orders=False compares connectivity alone."""
+    mols = Molecules.from_sdf(files, lig_elements, remove_hydrogen=remove_hydrogen, device=device)
     r = mols._keys(largest_frag, with_orders)
     return torch.unique(r['key'][(r['status'] & hip.KEY_NO_MOLECULE) == 0])
 

@@ -1,8 +1,9 @@
 """Pocket extraction on the device: whole receptors + ligands -> pocket atoms and interface points.
 
-The array-level part of upstream's dataset construction.  File parsing (PDB / mmCIF / SDF, element fixing, the
-standard-amino-acid test) stays with the caller; everything after "coordinates, element features and residue index
-per atom" runs here, batched, in `kpd_pocket_select` and `kpd_interface_points` (csrc/pocket.hip):
+The array-level part of upstream's dataset construction.  File parsing (PDB / SDF, element fixing, the
+standard-amino-acid test) is `structure.read_pdb` / `read_sdf` / `load_complexes` (csrc/structure_io.hip); everything after
+"coordinates, element features and residue index per atom" runs here, batched, in `kpd_pocket_select` and
+`kpd_interface_points` (csrc/pocket.hip):
 
 * `get_pocket_atoms`       data_processing/pdbbind_processing.py:85-149 (the CrossDocked form: box, cutoff, whole residues)
 * `get_interface_points`   data_processing/pdbbind_processing.py:295-325
