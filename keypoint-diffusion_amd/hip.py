@@ -112,6 +112,112 @@ class KpdError(RuntimeError):
     pass
 
 
+# The prototype of every function include/kpd.h declares: name -> (result type, argument types).  This table is the only place a
+# prototype is written: `lib()` sets restype / argtypes from it, EXPORTS is its keys, and tests/test_abi.py compares it with the
+# header's text parameter by parameter (count, order and kind) and the Structure classes above field by field.
+_P, _I32, _I64, _U64, _F32, _F64, _STR, _STATUS, _ref = (C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_char_p,
+                                                         C.c_int, C.POINTER)
+_LIGANDS_IN_POCKETS = [_P, _P] + [_I32] * 3 + [_P, _I32]      # pos, lig_ptr, N, B, max_atoms, elem, F: the head of relax and the vina calls
+PROTOTYPES = {
+    'kpd_last_error': (_STR, []),
+    'kpd_version': (C.c_int, []),
+    'kpd_build_flags': (C.c_int, []),
+    'kpd_build_lig_graph': (_STATUS, [_ref(KpdBatch), _F32, _I32, _F32, _I32, _ref(KpdLigGraph), _P]),
+    'kpd_egnn_forward': (_STATUS, [_P, _ref(KpdBatch)] + [_P] * 4),
+    'kpd_egnn_debug_state': (_STATUS, [_P, _STR, _P, _I64, _P]),
+    'kpd_egnn_last_counts': (_STATUS, [_P, _ref(_I32), _P]),
+    'kpd_egnn_profile': (_STATUS, [_P, _I32]),
+    'kpd_egnn_profile_read': (_STATUS, [_P, _ref(_F64), _ref(_I32)]),
+    'kpd_sample_update': (_STATUS, [_I32, _P, _P, _I32] + [_P] * 8 + [_I32, _P]),
+    'kpd_step_coefficients': (_STATUS, [_P, _I32, _P, _P, _I32, _P, _P]),
+    'kpd_complex_noise': (_STATUS, [_I32, _P, _I32, _P, _U64, _I32, _I32, _P, _P]),
+    'kpd_inpaint_coefficients': (_STATUS, [_P, _I32, _P, _P, _I32, _P, _P]),
+    'kpd_sample_update_inpaint': (_STATUS, [_I32, _P, _P, _I32] + [_P] * 14 + [_I32, _P]),
+    'kpd_sample_renoise': (_STATUS, [_I32, _P, _P, _I32] + [_P] * 6 + [_I32, _P]),
+    'kpd_guided_coefficients': (_STATUS, [_P, _I32, _P, _P, _I32, _F32, _F32, _P, _P]),
+    'kpd_sample_update_guided': (_STATUS, [_I32, _P, _P, _I32] + [_P] * 16 + [_F32, _I32, _P]),
+    'kpd_clash_score': (_STATUS, [_I32] + [_P] * 4 + [_F32, _P, _P]),
+    'kpd_gvp_forward': (_STATUS, [_P, _ref(KpdBatch)] + [_P] * 4),
+    'kpd_gvp_debug_state': (_STATUS, [_P, _STR, _P, _I64, _P]),
+    'kpd_gvp_profile': (_STATUS, [_P, _I32]),
+    'kpd_gvp_profile_read': (_STATUS, [_P, _ref(_F64), _ref(_I32)]),
+    'kpd_gvp_last_counts': (_STATUS, [_P, _ref(_I32), _P]),
+    'kpd_recenc_forward': (_STATUS, [_P, _ref(KpdRecBatch), _ref(KpdRecOut), _P]),
+    'kpd_recegnn_forward': (_STATUS, [_P, _ref(KpdRecBatch), _P, _ref(KpdRecOut)] + [_P] * 3),
+    'kpd_xyz_scratch_bytes': (_I64, [_I32, _I32]),
+    'kpd_xyz_emit': (_STATUS, [_P] * 3 + [_I32] * 3 + [_P] * 3 + [_I64] + [_P] * 4),
+    'kpd_rec_graph_scratch_bytes': (_I64, [_I32, _I32]),
+    'kpd_build_rec_graph': (_STATUS, [_P, _P] + [_I32] * 3 + [_F32, _I32, _P, _I32] + [_P] * 8),
+    'kpd_egnn_trainer_forward': (_STATUS, [_P, _ref(KpdBatch)] + [_P] * 4),
+    'kpd_egnn_trainer_backward': (_STATUS, [_P] * 8),
+    'kpd_egnn_trainer_profile': (_STATUS, [_P, _I32]),
+    'kpd_egnn_trainer_profile_read': (_STATUS, [_P, _ref(_F64), _ref(_I32), _ref(_F64)]),
+    'kpd_gvp_trainer_last_counts': (_STATUS, [_P, _ref(_I32)]),
+    'kpd_gvp_trainer_message_path': (_STATUS, [_P, _ref(_I32)]),
+    'kpd_wgrad_batch': (_STATUS, [_I32, _I32, _ref(KpdWgradItem), _P, _I64, _P]),
+    'kpd_adam_step': (_STATUS, [_P, _I32, _I64, _I32] + [_F64] * 5 + [_I64, _F64, _P]),
+    'kpd_gvp_trainer_forward': (_STATUS, [_P, _ref(KpdBatch)] + [_P] * 4),
+    'kpd_gvp_trainer_backward': (_STATUS, [_P] * 9),
+    'kpd_gvp_trainer_set_dropout': (_STATUS, [_P, _F32, _U64]),
+    'kpd_dropout_mask': (_STATUS, [_U64] + [_I32] * 4 + [_I64, _F32, _P, _P]),
+    'kpd_recenc_trainer_set_dropout': (_STATUS, [_P, _F32, _U64]),
+    'kpd_recenc_trainer_forward': (_STATUS, [_P, _ref(KpdRecBatch), _ref(KpdRecOut), _P]),
+    'kpd_recenc_trainer_backward': (_STATUS, [_P] * 5),
+    'kpd_recegnn_trainer_forward': (_STATUS, [_P, _ref(KpdRecBatch), _P, _ref(KpdRecOut)] + [_P] * 3),
+    'kpd_recegnn_trainer_backward': (_STATUS, [_P] * 4),
+    'kpd_ot_emd_uniform': (_STATUS, [_I32] + [_P] * 5 + [_I32]),
+    'kpd_sgemm': (_STATUS, [_I32] * 5 + [_F32, _P, _I32, _P, _I32, _F32, _P, _I32, _P, _P, _I64, _P]),
+    'kpd_dist_hinge': (_STATUS, [_P, _P, _I32, _P, _P, _I32, _I32, _F32] + [_P] * 5),
+    'kpd_pocket_scratch_bytes': (_I64, [_I32, _I32]),
+    'kpd_pocket_select': (_STATUS, [_P] * 5 + [_I32, _I32, _P, _P, _I32, _I32, _F32, _F32, _I32] + [_P] * 8),
+    'kpd_interface_points_scratch_bytes': (_I64, [_I32] * 3),
+    'kpd_interface_points': (_STATUS, [_P] * 3 + [_I32, _P, _P, _I32, _I32, _F32, _F32, _I32, _I32] + [_P] * 6),
+    'kpd_mol_scratch_bytes': (_I64, [_I32, _I32]),
+    'kpd_mol_perceive': (_STATUS, [_P] * 3 + [_I32] * 3 + [_P, _P, _I32] + [_P] * 10),
+    'kpd_sdf_scratch_bytes': (_I64, [_I32, _I32]),
+    'kpd_sdf_emit': (_STATUS, [_P, _P, _I32, _I32, _P, _I32] + [_P] * 5 + [_I32, _P, _I32, _P, _I64] + [_P] * 4),
+    'kpd_mol_keys': (_STATUS, [_P, _I32, _I32, _P, _I32] + [_P] * 5 + [_I32, _P] + [_I32] * 4 + [_P] * 5),
+    'kpd_fp_diversity': (_STATUS, [_P, _P, _I32, _I32, _P, _I32] + [_P] * 4),
+    'kpd_mol_sanitize': (_STATUS, [_P, _P, _I32, _I32, _P, _I32] + [_P] * 3 + [_F64] + [_P] * 4 + [_I32, _P, _I32] + [_P] * 10),
+    'kpd_mol_add_hs_scratch_bytes': (_I64, [_I32, _I32]),
+    'kpd_mol_add_hs': (_STATUS, [_P, _P, _I32, _I32, _P, _I32] + [_P] * 6 + [_I32] + [_P] * 5 + [_I32] * 4 + [_P] * 15),
+    'kpd_smiles_scratch_bytes': (_I64, [_I32, _I32]),
+    'kpd_mol_smiles': (_STATUS, [_P, _I32, _I32, _P, _I32] + [_P] * 7 + [_I32] + [_P] * 4 + [_I32, _I32, _P, _I64] + [_P] * 4),
+    'kpd_pose_rmsd_scratch_bytes': (_I64, [_I32] * 3),
+    'kpd_pose_rmsd': (_STATUS, [_P, _I32, _I32, _P, _I32] + [_P] * 4 + [_I32] + [_P] * 3 + [_I32, _I32, _P, _P, _I32, _I32, _I64] +
+                      [_P] * 7),
+    'kpd_pose_check_defaults': (None, [_ref(KpdPoseCheckParams)]),
+    'kpd_pose_check': (_STATUS, [_P] + [_I32] * 3 + [_P, _I32] + [_P] * 6 + [_I32] + [_P] * 4 + [_I32, _P, _I32] + [_P] * 4 + [_I32] * 3 +
+                       [_P, _ref(KpdPoseCheckParams)] + [_P] * 6),
+    'kpd_relax_defaults': (None, [_ref(KpdRelaxParams)]),
+    'kpd_relax': (_STATUS, _LIGANDS_IN_POCKETS + [_P] * 4 + [_I32] + [_P] * 4 + [_I32] * 3 + [_P, _ref(KpdRelaxParams)] + [_P] * 4),
+    'kpd_vina_defaults': (None, [_ref(KpdVinaParams)]),
+    'kpd_vina_pocket_types': (_STATUS, [_P] * 3 + [_I32, _I32] + [_P] * 3),
+    'kpd_vina_score': (_STATUS, _LIGANDS_IN_POCKETS + [_P] * 5 + [_I32] + [_P] * 6 + [_I32] * 3 + [_P, _ref(KpdVinaParams)] + [_P] * 6),
+    'kpd_vina_min_defaults': (None, [_ref(KpdVinaMinParams)]),
+    'kpd_vina_minimize': (_STATUS, _LIGANDS_IN_POCKETS + [_P] * 6 + [_I32] + [_P] * 6 + [_I32] * 3 + [_P, _I32, _ref(KpdVinaMinParams)] +
+                          [_P] * 4),
+    'kpd_vina_dock_defaults': (None, [_ref(KpdVinaDockParams)]),
+    'kpd_vina_dock': (_STATUS, _LIGANDS_IN_POCKETS + [_P] * 6 + [_I32] + [_P] * 6 + [_I32] * 3 + [_P, _I32] + [_P] * 3 + [_U64] +
+                      [_I32] * 3 + [_ref(KpdVinaDockParams)] + [_P] * 7),
+    'kpd_pdb_scratch_bytes': (_I64, [_I64, _I32, _I32]),
+    'kpd_pdb_parse': (_STATUS, [_P, _I64, _P, _I32, _P, _I32, _P] + [_I32] * 3 + [_P] * 18),
+    'kpd_sdf_parse_scratch_bytes': (_I64, [_I64] + [_I32] * 3),
+    'kpd_sdf_parse': (_STATUS, [_P, _I64, _P, _I32, _P, _I32, _P, _P] + [_I32] * 5 + [_P] * 17),
+}
+# the handle functions every family has: identical up to the config struct and the number of sizes `reserve` takes
+for _family, _cfg, _n_sizes in (('egnn', KpdEgnnConfig, 6), ('gvp', KpdGvpConfig, 6), ('recenc', KpdRecencConfig, 4),
+                                ('recegnn', KpdRecegnnConfig, 4)):
+    for _prefix in (f'kpd_{_family}_', f'kpd_{_family}_trainer_'):
+        PROTOTYPES[_prefix + 'create'] = (_STATUS, [_ref(_cfg), _ref(_P)])
+        PROTOTYPES[_prefix + 'destroy'] = (None, [_P])
+        PROTOTYPES[_prefix + 'reserve'] = (_STATUS, [_P] + [_I32] * _n_sizes)
+    PROTOTYPES[f'kpd_{_family}_load_weight'] = (_STATUS, [_P, _STR, _P, _ref(_I64), _I32, _P])
+    PROTOTYPES[f'kpd_{_family}_commit'] = (_STATUS, [_P])
+    PROTOTYPES[f'kpd_{_family}_trainer_bind'] = (_STATUS, [_P, _STR, _P, _P, _ref(_I64), _I32])
+EXPORTS = list(PROTOTYPES)
+
+
 def lib():
     """Load (once) and return the HIP library; raise loudly when it is missing."""
     global _lib
@@ -121,183 +227,13 @@ def lib():
         raise KpdError(f'{LIB_PATH} not found: the HIP extension must be built first '
                        f'(python -c "import __graft_entry__ as g; g.build()"). There is no CPU fallback.')
     L = C.CDLL(LIB_PATH)
-    L.kpd_last_error.restype = C.c_char_p
-    L.kpd_version.restype = C.c_int
-    L.kpd_build_flags.restype = C.c_int
-    for name in EXPORTS:
-        getattr(L, name)          # AttributeError if a declared symbol is not exported
-    # the handle functions every family has: identical up to the config struct and the number of sizes `reserve` takes
-    for family, cfg, n_sizes in (('egnn', KpdEgnnConfig, 6), ('gvp', KpdGvpConfig, 6), ('recenc', KpdRecencConfig, 4),
-                                 ('recegnn', KpdRecegnnConfig, 4)):
-        for prefix in (family, family + '_trainer'):
-            fn = lambda name: getattr(L, f'kpd_{prefix}_{name}')
-            fn('create').argtypes = [C.POINTER(cfg), C.POINTER(C.c_void_p)]
-            fn('destroy').argtypes = [C.c_void_p]
-            fn('destroy').restype = None
-            fn('reserve').argtypes = [C.c_void_p] + [C.c_int32] * n_sizes
-        fn = lambda name: getattr(L, f'kpd_{family}_{name}')
-        fn('load_weight').argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_void_p]
-        fn('commit').argtypes = [C.c_void_p]
-        fn('trainer_bind').argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
-    L.kpd_egnn_forward.argtypes = [C.c_void_p, C.POINTER(KpdBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.kpd_egnn_debug_state.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.kpd_egnn_last_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
-    L.kpd_egnn_profile.argtypes = [C.c_void_p, C.c_int32]
-    L.kpd_egnn_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-    L.kpd_gvp_forward.argtypes = [C.c_void_p, C.POINTER(KpdBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.kpd_gvp_debug_state.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.kpd_gvp_last_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
-    L.kpd_gvp_profile.argtypes = [C.c_void_p, C.c_int32]
-    L.kpd_gvp_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-    L.kpd_recenc_forward.argtypes = [C.c_void_p, C.POINTER(KpdRecBatch), C.POINTER(KpdRecOut), C.c_void_p]
-    L.kpd_recegnn_forward.argtypes = [C.c_void_p, C.POINTER(KpdRecBatch), C.c_void_p, C.POINTER(KpdRecOut), C.c_void_p, C.c_void_p,
-                                      C.c_void_p]
-    L.kpd_build_lig_graph.argtypes = [C.POINTER(KpdBatch), C.c_float, C.c_int32, C.c_float, C.c_int32, C.POINTER(KpdLigGraph),
-                                      C.c_void_p]
-    L.kpd_sample_update.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_void_p]
-    L.kpd_complex_noise.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p,
-                                    C.c_void_p]
-    L.kpd_step_coefficients.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    L.kpd_inpaint_coefficients.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    L.kpd_sample_update_inpaint.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 14 + [C.c_int32, C.c_void_p]
-    L.kpd_sample_renoise.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
-    L.kpd_guided_coefficients.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p,
-                                          C.c_void_p]
-    L.kpd_sample_update_guided.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 16 +
-                                           [C.c_float, C.c_int32, C.c_void_p])
-    L.kpd_clash_score.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_void_p]
-    L.kpd_egnn_trainer_forward.argtypes = [C.c_void_p, C.POINTER(KpdBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.kpd_egnn_trainer_backward.argtypes = [C.c_void_p] + [C.c_void_p] * 7
-    L.kpd_egnn_trainer_profile.argtypes = [C.c_void_p, C.c_int32]
-    L.kpd_egnn_trainer_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-    L.kpd_gvp_trainer_forward.argtypes = [C.c_void_p, C.POINTER(KpdBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.kpd_gvp_trainer_backward.argtypes = [C.c_void_p] + [C.c_void_p] * 8
-    L.kpd_gvp_trainer_set_dropout.argtypes = [C.c_void_p, C.c_float, C.c_uint64]
-    L.kpd_gvp_trainer_message_path.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-    L.kpd_wgrad_batch.argtypes = [C.c_int32, C.c_int32, C.POINTER(KpdWgradItem), C.c_void_p, C.c_int64, C.c_void_p]
-    L.kpd_adam_step.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
-                                C.c_double, C.c_void_p]
-    L.kpd_dropout_mask.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
-    L.kpd_recenc_trainer_set_dropout.argtypes = [C.c_void_p, C.c_float, C.c_uint64]
-    L.kpd_recenc_trainer_forward.argtypes = [C.c_void_p, C.POINTER(KpdRecBatch), C.POINTER(KpdRecOut), C.c_void_p]
-    L.kpd_recenc_trainer_backward.argtypes = [C.c_void_p] + [C.c_void_p] * 4
-    L.kpd_recegnn_trainer_forward.argtypes = [C.c_void_p, C.POINTER(KpdRecBatch), C.c_void_p, C.POINTER(KpdRecOut), C.c_void_p, C.c_void_p,
-                                              C.c_void_p]
-    L.kpd_recegnn_trainer_backward.argtypes = [C.c_void_p] + [C.c_void_p] * 3
-    L.kpd_ot_emd_uniform.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-    L.kpd_sgemm.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                            C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.kpd_rec_graph_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.kpd_rec_graph_scratch_bytes.restype = C.c_int64
-    L.kpd_build_rec_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
-                                      C.c_int32] + [C.c_void_p] * 8
-    L.kpd_xyz_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.kpd_xyz_scratch_bytes.restype = C.c_int64
-    L.kpd_xyz_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.kpd_dist_hinge.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 5
-    L.kpd_pocket_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.kpd_pocket_scratch_bytes.restype = C.c_int64
-    L.kpd_pocket_select.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
-                                    C.c_float, C.c_int32] + [C.c_void_p] * 8
-    L.kpd_interface_points_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    L.kpd_interface_points_scratch_bytes.restype = C.c_int64
-    L.kpd_interface_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                       C.c_float, C.c_float, C.c_int32, C.c_int32] + [C.c_void_p] * 6
-    for name in ('kpd_mol_scratch_bytes', 'kpd_sdf_scratch_bytes'):
-        getattr(L, name).argtypes = [C.c_int32, C.c_int32]
-        getattr(L, name).restype = C.c_int64
-    L.kpd_mol_perceive.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 10
-    L.kpd_sdf_emit.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 +
-                               [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4)
-    L.kpd_mol_keys.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p] +
-                               [C.c_int32] * 4 + [C.c_void_p] * 5)
-    L.kpd_fp_diversity.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
-    L.kpd_mol_sanitize.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_double] +
-                                   [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 10)
-    L.kpd_mol_add_hs_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.kpd_mol_add_hs_scratch_bytes.restype = C.c_int64
-    L.kpd_mol_add_hs.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] +
-                                 [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 15)
-    L.kpd_smiles_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.kpd_smiles_scratch_bytes.restype = C.c_int64
-    L.kpd_mol_smiles.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32] + [C.c_void_p] * 4 +
-                                 [C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4)
-    L.kpd_pose_rmsd_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    L.kpd_pose_rmsd_scratch_bytes.restype = C.c_int64
-    L.kpd_pose_rmsd.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3 +
-                                [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 7)
-    L.kpd_pose_check_defaults.argtypes = [C.POINTER(KpdPoseCheckParams)]
-    L.kpd_pose_check_defaults.restype = None
-    L.kpd_pose_check.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] +
-                                 [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 3 +
-                                 [C.c_void_p, C.POINTER(KpdPoseCheckParams)] + [C.c_void_p] * 6)
-    L.kpd_relax_defaults.argtypes = [C.POINTER(KpdRelaxParams)]
-    L.kpd_relax_defaults.restype = None
-    L.kpd_relax.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
-                            [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p, C.POINTER(KpdRelaxParams)] + [C.c_void_p] * 4)
-    L.kpd_vina_defaults.argtypes = [C.POINTER(KpdVinaParams)]
-    L.kpd_vina_defaults.restype = None
-    L.kpd_vina_pocket_types.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 3
-    L.kpd_vina_score.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 +
-                                 [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.POINTER(KpdVinaParams)] +
-                                 [C.c_void_p] * 6)
-    L.kpd_vina_min_defaults.argtypes = [C.POINTER(KpdVinaMinParams)]
-    L.kpd_vina_min_defaults.restype = None
-    L.kpd_vina_minimize.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 +
-                                    [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.POINTER(KpdVinaMinParams)] +
-                                    [C.c_void_p] * 4)
-    L.kpd_vina_dock_defaults.argtypes = [C.POINTER(KpdVinaDockParams)]
-    L.kpd_vina_dock_defaults.restype = None
-    L.kpd_vina_dock.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 +
-                                [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 3 +
-                                [C.c_uint64] + [C.c_int32] * 3 + [C.POINTER(KpdVinaDockParams)] + [C.c_void_p] * 7)
-    L.kpd_pdb_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-    L.kpd_pdb_scratch_bytes.restype = C.c_int64
-    L.kpd_pdb_parse.argtypes = ([C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                 C.c_int32] + [C.c_void_p] * 18)
-    L.kpd_sdf_parse_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
-    L.kpd_sdf_parse_scratch_bytes.restype = C.c_int64
-    L.kpd_sdf_parse.argtypes = ([C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 +
-                                [C.c_void_p] * 17)
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)     # AttributeError if a declared symbol is not exported
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
 
-# every symbol include/kpd.h declares (checked by tests/test_abi.py against the header text)
-EXPORTS = [
-    'kpd_last_error', 'kpd_version', 'kpd_build_flags', 'kpd_build_lig_graph',
-    'kpd_egnn_create', 'kpd_egnn_destroy', 'kpd_egnn_load_weight', 'kpd_egnn_commit', 'kpd_egnn_reserve',
-    'kpd_egnn_forward', 'kpd_egnn_debug_state', 'kpd_egnn_last_counts', 'kpd_egnn_profile',
-    'kpd_egnn_profile_read', 'kpd_sample_update', 'kpd_step_coefficients', 'kpd_complex_noise',
-    'kpd_inpaint_coefficients', 'kpd_sample_update_inpaint', 'kpd_sample_renoise',
-    'kpd_guided_coefficients', 'kpd_sample_update_guided', 'kpd_clash_score',
-    'kpd_gvp_create', 'kpd_gvp_destroy', 'kpd_gvp_load_weight', 'kpd_gvp_commit', 'kpd_gvp_reserve',
-    'kpd_gvp_forward', 'kpd_gvp_debug_state', 'kpd_gvp_profile', 'kpd_gvp_profile_read', 'kpd_gvp_last_counts',
-    'kpd_recenc_create', 'kpd_recenc_destroy', 'kpd_recenc_load_weight', 'kpd_recenc_commit', 'kpd_recenc_reserve',
-    'kpd_recenc_forward',
-    'kpd_recegnn_create', 'kpd_recegnn_destroy', 'kpd_recegnn_load_weight', 'kpd_recegnn_commit', 'kpd_recegnn_reserve',
-    'kpd_recegnn_forward',
-    'kpd_xyz_scratch_bytes', 'kpd_xyz_emit', 'kpd_rec_graph_scratch_bytes', 'kpd_build_rec_graph',
-    'kpd_egnn_trainer_create', 'kpd_egnn_trainer_destroy', 'kpd_egnn_trainer_bind', 'kpd_egnn_trainer_reserve',
-    'kpd_egnn_trainer_forward', 'kpd_egnn_trainer_backward', 'kpd_egnn_trainer_profile', 'kpd_egnn_trainer_profile_read', 'kpd_gvp_trainer_last_counts',
-    'kpd_gvp_trainer_message_path', 'kpd_wgrad_batch', 'kpd_adam_step',
-    'kpd_gvp_trainer_create', 'kpd_gvp_trainer_destroy', 'kpd_gvp_trainer_bind', 'kpd_gvp_trainer_reserve',
-    'kpd_gvp_trainer_forward', 'kpd_gvp_trainer_backward', 'kpd_gvp_trainer_set_dropout', 'kpd_dropout_mask',
-    'kpd_recenc_trainer_create', 'kpd_recenc_trainer_destroy', 'kpd_recenc_trainer_bind', 'kpd_recenc_trainer_set_dropout',
-    'kpd_recenc_trainer_reserve', 'kpd_recenc_trainer_forward', 'kpd_recenc_trainer_backward',
-    'kpd_recegnn_trainer_create', 'kpd_recegnn_trainer_destroy', 'kpd_recegnn_trainer_bind', 'kpd_recegnn_trainer_reserve',
-    'kpd_recegnn_trainer_forward', 'kpd_recegnn_trainer_backward', 'kpd_ot_emd_uniform', 'kpd_sgemm',
-    'kpd_dist_hinge',
-    'kpd_pocket_scratch_bytes', 'kpd_pocket_select', 'kpd_interface_points_scratch_bytes', 'kpd_interface_points',
-    'kpd_mol_scratch_bytes', 'kpd_mol_perceive', 'kpd_sdf_scratch_bytes', 'kpd_sdf_emit',
-    'kpd_mol_keys', 'kpd_fp_diversity', 'kpd_mol_sanitize', 'kpd_mol_add_hs_scratch_bytes', 'kpd_mol_add_hs',
-    'kpd_smiles_scratch_bytes', 'kpd_mol_smiles', 'kpd_pose_rmsd_scratch_bytes', 'kpd_pose_rmsd', 'kpd_pose_check_defaults',
-    'kpd_pose_check', 'kpd_relax_defaults', 'kpd_relax',
-    'kpd_vina_defaults', 'kpd_vina_pocket_types', 'kpd_vina_score', 'kpd_vina_min_defaults', 'kpd_vina_minimize',
-    'kpd_vina_dock_defaults', 'kpd_vina_dock',
-    'kpd_pdb_scratch_bytes', 'kpd_pdb_parse', 'kpd_sdf_parse_scratch_bytes', 'kpd_sdf_parse',
-]
 
 
 def check(status: int):
@@ -335,12 +271,38 @@ def _per_entry(t, name: str, n: int, what: str, contiguous: bool = False) -> tor
     return t.contiguous()
 
 
-def _mol_fields(where: str, mol: dict, names) -> None:
-    """The named entries of what `mol_perceive` returned must be contiguous int32 GPU tensors."""
-    for name in names:
-        t = mol.get(name)
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
-            raise KpdError(f'{where}: {name} must be a contiguous int32 GPU tensor')
+# How many elements every entry of what `mol_perceive` (MOL_LENGTHS) and `mol_sanitize` (SAN_LENGTHS) return has, for N atoms, B
+# ligands and a bond list of cap_bonds rows.  The library cannot see a tensor's length: `_mol_args` is the only guard.
+MOL_LENGTHS = dict(elem='N', valence='N', frag='N', bonds='2 * cap_bonds', order='cap_bonds', bond_ptr='B + 1', status='B')
+SAN_LENGTHS = dict(order_k='cap_bonds', bond_flags='cap_bonds', valence_k='N', atom_h='N', atom_flags='N', status='B')
+
+
+def _numel(t) -> int:
+    """Elements of a tensor, 0 for anything else (which `_mol_args` then refuses by name)."""
+    return t.numel() if isinstance(t, torch.Tensor) else 0
+
+
+def _mol_args(where: str, mol: dict, fields, B: int, N: int, san: Optional[dict] = None, san_fields=()) -> int:
+    """The entries `fields` of `mol` (what `mol_perceive` returned) and `san_fields` of `san` (what `mol_sanitize` returned) must be
+    contiguous int32 GPU tensors of the lengths MOL_LENGTHS / SAN_LENGTHS state.  Returns cap_bonds, the rows of mol['bonds']."""
+    n_bonds = _numel(mol.get('bonds'))
+    if n_bonds % 2:
+        raise KpdError(f'{where}: bonds has {n_bonds} elements, an odd number: it must hold two atoms per row')
+    size = {'N': N, 'B': B, 'B + 1': B + 1, 'cap_bonds': n_bonds // 2, '2 * cap_bonds': n_bonds}
+    for what, src, names, lengths in (('perceived', mol, fields, MOL_LENGTHS), ('sanitised', san, san_fields, SAN_LENGTHS)):
+        for name in names:
+            t = src.get(name)
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+                raise KpdError(f'{where}: {name} must be a contiguous int32 GPU tensor')
+            if t.numel() != size[lengths[name]]:
+                raise KpdError(f'{where}: {name} of the {what} molecules has {t.numel()} elements, not {lengths[name]} = '
+                               f'{size[lengths[name]]} (N = {N} atoms, B = {B} ligands, cap_bonds = {n_bonds // 2} bond rows)')
+    return n_bonds // 2
+
+
+def _class_table(device, *rows) -> torch.Tensor:
+    """The integer per-class tables of a call (atomic numbers, largest valences), one row each, as an int32 device tensor [len(rows), F]."""
+    return torch.tensor([list(map(int, row)) for row in rows], dtype=torch.int32, device=device)
 
 
 class PreparedBatch:
@@ -1091,7 +1053,7 @@ def mol_perceive(pos: torch.Tensor, feat: torch.Tensor, lig_ptr: torch.Tensor, z
         raise KpdError(f'mol_perceive: pos {tuple(pos.shape)}, feat {tuple(feat.shape)}, {len(z)} atomic numbers, {len(allowed)} valences')
     dev = pos.device
     cap = 3 * N if cap_bonds is None else int(cap_bonds)
-    table = torch.tensor([list(map(int, z)), list(map(int, allowed))], dtype=torch.int32, device=dev)
+    table = _class_table(dev, z, allowed)
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
     out = dict(elem=i32(N), valence=i32(N), frag=i32(N), bonds=i32(cap, 2), order=i32(cap), bond_ptr=i32(B + 1), summary=i32(B, 4),
                status=i32(B))
@@ -1110,11 +1072,9 @@ def sdf_emit(pos: torch.Tensor, lig_ptr: torch.Tensor, elements, mol: dict, larg
     pos = _dev_f32(pos, 'pos')
     B = _offsets(lig_ptr, 'lig_ptr')
     N, F = pos.shape[0], len(elements)
-    _mol_fields('sdf_emit', mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'))
-    cap_bonds = mol['order'].numel()
-    if (pos.shape != (N, 3) or F < 1 or mol['elem'].numel() != N or mol['frag'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or
-            mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B):
-        raise KpdError(f'sdf_emit: pos {tuple(pos.shape)}, {B} ligands, {F} element symbols do not match the perceived molecules')
+    cap_bonds = _mol_args('sdf_emit', mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'), B, N)
+    if pos.shape != (N, 3) or F < 1:
+        raise KpdError(f'sdf_emit: pos {tuple(pos.shape)} must be [N,3] and there must be element symbols (got {F})')
     dev = pos.device
     symbols = _packed_symbols(elements, dev, 3)
     cap = 70 * N + 13 * cap_bonds + 77 * B if capacity is None else int(capacity)      # fixed-width lines: the exact upper bound
@@ -1140,16 +1100,14 @@ def mol_keys(lig_ptr: torch.Tensor, z, mol: dict, largest_only: bool = True, wit
     device tensors: key [B] int64 (the uint64 bit pattern), fp [B, nbits/32] int32 (the uint32 bit pattern), status [B] (bit 0:
     no molecule, key 0 and an all-zero row) and, on request, atom_inv [N] int64.  No host synchronisation."""
     B = _offsets(lig_ptr, 'lig_ptr')
-    _mol_fields('mol_keys', mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'))
-    N, F, cap_bonds = mol['elem'].numel(), len(z), mol['order'].numel()
-    if (F < 1 or mol['frag'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or mol['bond_ptr'].numel() != B + 1 or
-            mol['status'].numel() != B):
-        raise KpdError(f'mol_keys: {B} ligands, {F} atomic numbers do not match the perceived molecules')
+    N, F = _numel(mol.get('elem')), len(z)
+    cap_bonds = _mol_args('mol_keys', mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'), B, N)
     nbits, radius = int(nbits), int(radius)
-    if not (0 <= radius <= 4 and 64 <= nbits <= 4096 and nbits & (nbits - 1) == 0):
-        raise KpdError(f'mol_keys: radius {radius} must be 0 .. 4 and nbits {nbits} a power of two in 64 .. 4096')
+    if not (F >= 1 and 0 <= radius <= 4 and 64 <= nbits <= 4096 and nbits & (nbits - 1) == 0):
+        raise KpdError(f'mol_keys: {F} atomic numbers must be at least one, radius {radius} 0 .. 4 and nbits {nbits} a power of two in '
+                       f'64 .. 4096')
     dev = lig_ptr.device
-    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
+    zt = _class_table(dev, z)
     out = dict(key=torch.empty(B, dtype=torch.int64, device=dev), fp=torch.empty(B, nbits // 32, dtype=torch.int32, device=dev),
                status=torch.empty(B, dtype=torch.int32, device=dev))
     if atom_inv:
@@ -1173,14 +1131,13 @@ def mol_sanitize(pos: torch.Tensor, lig_ptr: torch.Tensor, z, allowed, mass, mas
     (columns SAN_DESC_I), desc_f [B,2] float64 (mw, reserved), valid [B], status [B].  No host synchronisation."""
     pos = _dev_f32(pos, 'pos')
     B = _offsets(lig_ptr, 'lig_ptr')
-    _mol_fields('mol_sanitize', mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'))
-    N, F, cap_bonds = pos.shape[0], len(z), mol['order'].numel()
-    if (pos.shape != (N, 3) or F < 1 or len(allowed) != F or len(mass) != F or mol['elem'].numel() != N or mol['frag'].numel() != N or
-            mol['bonds'].numel() != 2 * cap_bonds or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B):
-        raise KpdError(f'mol_sanitize: pos {tuple(pos.shape)}, {B} ligands, {F} atomic numbers, {len(allowed)} valences, {len(mass)} masses '
-                       f'do not match the perceived molecules')
+    N, F = pos.shape[0], len(z)
+    cap_bonds = _mol_args('mol_sanitize', mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'), B, N)
+    if pos.shape != (N, 3) or F < 1 or len(allowed) != F or len(mass) != F:
+        raise KpdError(f'mol_sanitize: pos {tuple(pos.shape)} must be [N,3], and {F} atomic numbers, {len(allowed)} valences, {len(mass)} '
+                       f'masses one per class')
     dev = pos.device
-    table = torch.tensor([list(map(int, z)), list(map(int, allowed))], dtype=torch.int32, device=dev)
+    table = _class_table(dev, z, allowed)
     mt = torch.tensor(list(map(float, mass)), dtype=torch.float64, device=dev)
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
     out = dict(order_k=i32(cap_bonds), bond_flags=i32(cap_bonds), valence_k=i32(N), atom_h=i32(N), atom_flags=i32(N), desc_i=i32(B, 10),
@@ -1205,21 +1162,18 @@ def mol_add_hs(pos: torch.Tensor, lig_ptr: torch.Tensor, z, allowed, h_class: in
     -- and parent / source [cap_atoms], n_h [B], status [B] (bits HS_*)."""
     pos = _dev_f32(pos, 'pos')
     B = _offsets(lig_ptr, 'lig_ptr')
-    _mol_fields('mol_add_hs', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'))
-    _mol_fields('mol_add_hs', san, ('order_k', 'valence_k', 'atom_h', 'atom_flags', 'status'))
-    N, F, cap_in = pos.shape[0], len(z), san['order_k'].numel()
-    if (pos.shape != (N, 3) or F < 1 or len(allowed) != F or mol['elem'].numel() != N or mol['frag'].numel() != N or
-            mol['bonds'].numel() != 2 * cap_in or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B or
-            san['status'].numel() != B or any(san[k].numel() != N for k in ('valence_k', 'atom_h', 'atom_flags'))):
-        raise KpdError(f'mol_add_hs: pos {tuple(pos.shape)}, {B} ligands, {F} atomic numbers, {len(allowed)} valences do not match the '
-                       f'perceived and sanitised molecules')
+    N, F = pos.shape[0], len(z)
+    cap_in = _mol_args('mol_add_hs', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'), B, N,
+                       san, ('order_k', 'valence_k', 'atom_h', 'atom_flags', 'status'))
+    if pos.shape != (N, 3) or F < 1 or len(allowed) != F:
+        raise KpdError(f'mol_add_hs: pos {tuple(pos.shape)} must be [N,3], and {F} atomic numbers, {len(allowed)} valences one per class')
     h_class = int(h_class)
     if not (0 <= h_class < F and int(z[h_class]) == 1):
         raise KpdError(f'mol_add_hs: h_class {h_class} must name a class of atomic number 1')
     dev = pos.device
     n_h = int(san['atom_h'].clamp(min=0).sum().item()) if N else 0          # an upper bound: ligands copied through add none
     cap_atoms, cap_bonds = N + n_h, cap_in + n_h
-    table = torch.tensor([list(map(int, z)), list(map(int, allowed))], dtype=torch.int32, device=dev)
+    table = _class_table(dev, z, allowed)
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
     out = dict(lig_ptr=i32(B + 1), pos=torch.empty(cap_atoms, 3, dtype=torch.float32, device=dev), elem=i32(cap_atoms),
                valence=i32(cap_atoms), frag=i32(cap_atoms), bonds=i32(cap_bonds, 2), order=i32(cap_bonds), bond_ptr=i32(B + 1),
@@ -1247,16 +1201,13 @@ def mol_smiles(lig_ptr: torch.Tensor, z, elements, mol: dict, san: dict, largest
     repeated once with the size the first one reports if that was too small (`capacity`: the first size); the host
     synchronisations are the copies of the offsets and of the finished text."""
     B = _offsets(lig_ptr, 'lig_ptr')
-    _mol_fields('mol_smiles', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'))
-    _mol_fields('mol_smiles', san, ('order_k', 'bond_flags', 'atom_h', 'atom_flags', 'status'))
-    N, F, cap_bonds = mol['elem'].numel(), len(z), san['order_k'].numel()
-    if (F < 1 or len(elements) != F or mol['frag'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or
-            san['bond_flags'].numel() != cap_bonds or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B or
-            san['status'].numel() != B or san['atom_h'].numel() != N or san['atom_flags'].numel() != N):
-        raise KpdError(f'mol_smiles: {B} ligands, {F} atomic numbers, {len(elements)} element symbols do not match the perceived and '
-                       f'sanitised molecules')
+    N, F = _numel(mol.get('elem')), len(z)
+    cap_bonds = _mol_args('mol_smiles', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'), B, N,
+                          san, ('order_k', 'bond_flags', 'atom_h', 'atom_flags', 'status'))
+    if F < 1 or len(elements) != F:
+        raise KpdError(f'mol_smiles: {F} atomic numbers and {len(elements)} element symbols must be one per class')
     dev = lig_ptr.device
-    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
+    zt = _class_table(dev, z)
     symbols = _packed_symbols(elements, dev)
     text_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
@@ -1290,17 +1241,15 @@ def pose_rmsd(lig_ptr: torch.Tensor, z, mol: dict, pos: torch.Tensor, ref_pos: O
     float64 and nodes int64, [B,K] or [B,K,K]; map [K,N] int32 (pairs=False and `want_map`); status [B] (bits POSE_*).  No host
     synchronisation."""
     B = _offsets(lig_ptr, 'lig_ptr')
-    _mol_fields('pose_rmsd', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'))
     if not (isinstance(pos, torch.Tensor) and pos.dim() == 3 and pos.shape[2] == 3):
         raise KpdError(f'pose_rmsd: pos must be [K,N,3], got {tuple(getattr(pos, "shape", ()))}')
     pos = _dev_f32(pos, 'pos')
     K, N, F = pos.shape[0], pos.shape[1], len(z)
     pairs, max_nodes = bool(pairs), int(max_nodes)
-    if K < 1 or (pairs and K > POSE_MAX_PAIR_POSES) or max_nodes < 1:
-        raise KpdError(f'pose_rmsd: K={K} must be >= 1 (<= {POSE_MAX_PAIR_POSES} with pairs) and max_nodes={max_nodes} >= 1')
-    cap_bonds = mol['bonds'].numel() // 2
-    if (F < 1 or mol['elem'].numel() != N or mol['frag'].numel() != N or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B):
-        raise KpdError(f'pose_rmsd: pos {tuple(pos.shape)}, {B} ligands, {F} atomic numbers do not match the perceived molecules')
+    if K < 1 or F < 1 or (pairs and K > POSE_MAX_PAIR_POSES) or max_nodes < 1:
+        raise KpdError(f'pose_rmsd: K={K} must be >= 1 (<= {POSE_MAX_PAIR_POSES} with pairs), max_nodes={max_nodes} >= 1, and there must '
+                       f'be atomic numbers (got {F})')
+    cap_bonds = _mol_args('pose_rmsd', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'), B, N)
     if not pairs:
         if ref_pos is None:
             raise KpdError('pose_rmsd: ref_pos is needed unless pairs=True')
@@ -1312,7 +1261,7 @@ def pose_rmsd(lig_ptr: torch.Tensor, z, mol: dict, pos: torch.Tensor, ref_pos: O
     if atom_label is not None:
         atom_label = _per_entry(atom_label, 'atom_label', N, 'atom')
     dev = pos.device
-    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
+    zt = _class_table(dev, z)
     shape = (B, K, K) if pairs else (B, K)
     out = dict(rmsd=torch.empty(shape, dtype=torch.float64, device=dev), plain=torch.empty(shape, dtype=torch.float64, device=dev),
                nodes=torch.empty(shape, dtype=torch.int64, device=dev), status=torch.empty(B, dtype=torch.int32, device=dev))
@@ -1357,39 +1306,21 @@ def pose_check(lig_ptr: torch.Tensor, z, mol: dict, san: dict, pos: torch.Tensor
     int32 (-1: no pocket), all four None for no pockets at all; all GPU tensors.  `params`: the thresholds of `pose_check_params`.
     Returns a dict of device tensors: fail [B,K] int32 (bit k: CHECK_FAIL[k]), report [B,K,10] float64 (CHECK_REPORT), counts
     [B,K,17] int32 (CHECK_COUNTS), atom_fail [K,N] int32, status [B,K] int32 (bits CHECK_*).  No host synchronisation."""
-    B = _offsets(lig_ptr, 'lig_ptr')
-    _mol_fields('pose_check', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'))
-    _mol_fields('pose_check', san, ('order_k', 'bond_flags', 'atom_h', 'atom_flags', 'status'))
-    if not (isinstance(pos, torch.Tensor) and pos.dim() in (2, 3) and pos.shape[-1] == 3):
-        raise KpdError(f'pose_check: pos must be [K,N,3] or [N,3], got {tuple(getattr(pos, "shape", ()))}')
-    pos = _dev_f32(pos if pos.dim() == 3 else pos[None], 'pos')
-    K, N, F = pos.shape[0], pos.shape[1], len(z)
-    cap_bonds = san['order_k'].numel()
-    if (K < 1 or F < 1 or mol['elem'].numel() != N or mol['frag'].numel() != N or mol['bonds'].numel() != 2 * cap_bonds or
-            san['bond_flags'].numel() != cap_bonds or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B or
-            san['status'].numel() != B or san['atom_h'].numel() != N or san['atom_flags'].numel() != N):
-        raise KpdError(f'pose_check: pos {tuple(pos.shape)} (K >= 1), {B} ligands, {F} atomic numbers do not match the perceived and '
-                       f'sanitised molecules')
-    dev = pos.device
-    lig_radius = _dev_f32(lig_radius, 'lig_radius')
-    if lig_radius.shape != (F,):
-        raise KpdError(f'pose_check: lig_radius {tuple(lig_radius.shape)} must be [{F}]')
     if pocket_x is None:
         if not (pocket_radius is None and pocket_ptr is None and pocket_of is None):
             raise KpdError('pose_check: pocket_radius, pocket_ptr and pocket_of need pocket_x')
+        B, dev = _offsets(lig_ptr, 'lig_ptr'), lig_ptr.device
         pocket_x, pocket_radius = torch.zeros(0, 3, device=dev), torch.zeros(0, device=dev)
         pocket_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
         pocket_of = torch.full((B,), -1, dtype=torch.int32, device=dev)
-    pocket_x, pocket_radius = _dev_f32(pocket_x, 'pocket_x'), _dev_f32(pocket_radius, 'pocket_radius')
-    P = _offsets(pocket_ptr, 'pose_check: pocket_ptr', 'P')
-    pocket_of = _per_entry(pocket_of, 'pose_check: pocket_of', B, 'ligand', contiguous=True)
-    M = pocket_x.shape[0]
-    max_atoms = int(max_atoms)
-    if pocket_x.shape != (M, 3) or pocket_radius.shape != (M,) or not 1 <= max_atoms <= MOL_MAX_ATOMS:
-        raise KpdError(f'pose_check: pocket_x {tuple(pocket_x.shape)} must be [M,3], pocket_radius {tuple(pocket_radius.shape)} [M], '
-                       f'max_atoms {max_atoms} in 1 .. {MOL_MAX_ATOMS}')
+    pos, pocket_x, pocket_of, B, N, F, M, P, cap_bonds, zt, max_atoms, max_pocket = _ligand_pocket_args(
+        'pose_check', pos, lig_ptr, z, mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'), pocket_x, pocket_ptr, pocket_of, max_atoms,
+        max_pocket, san, ('order_k', 'bond_flags', 'atom_h', 'atom_flags', 'status'), stack=True)
+    K, dev = pos.shape[0], pos.device
+    lig_radius, pocket_radius = _dev_f32(lig_radius, 'lig_radius'), _dev_f32(pocket_radius, 'pocket_radius')
+    if lig_radius.shape != (F,) or pocket_radius.shape != (M,):
+        raise KpdError(f'pose_check: lig_radius {tuple(lig_radius.shape)} must be [{F}] and pocket_radius {tuple(pocket_radius.shape)} [{M}]')
     p = pose_check_params(**params)
-    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=dev)
     out = dict(fail=torch.empty(B, K, dtype=torch.int32, device=dev), report=torch.empty(B, K, len(CHECK_REPORT), dtype=torch.float64, device=dev),
                counts=torch.empty(B, K, len(CHECK_COUNTS), dtype=torch.int32, device=dev),
                atom_fail=torch.empty(K, N, dtype=torch.int32, device=dev), status=torch.empty(B, K, dtype=torch.int32, device=dev))
@@ -1397,7 +1328,7 @@ def pose_check(lig_ptr: torch.Tensor, z, mol: dict, san: dict, pos: torch.Tensor
                                _ptr(san['order_k']), _ptr(san['bond_flags']), _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']),
                                _ptr(san['status']), _ptr(san['atom_h']), _ptr(san['atom_flags']), int(bool(largest_only)), _ptr(pos), K,
                                _ptr(lig_radius), _ptr(pocket_x), _ptr(pocket_radius), _ptr(pocket_ptr), M, P,
-                               M if max_pocket is None else int(max_pocket), _ptr(pocket_of), C.byref(p), _ptr(out['fail']),
+                               max_pocket, _ptr(pocket_of), C.byref(p), _ptr(out['fail']),
                                _ptr(out['report']), _ptr(out['counts']), _ptr(out['atom_fail']), _ptr(out['status']), _stream()))
     return out
 
@@ -1439,25 +1370,27 @@ def _struct_params(where: str, Struct, defaults_fn, params: dict, ints=()):
     return p, names
 
 
-def _ligand_pocket_args(where: str, pos, lig_ptr, z, mol: dict, fields, pocket_x, pocket_ptr, pocket_of, max_atoms, max_pocket):
-    """What `relax` and `vina_score` share: perceived ligands (the `fields` of `mol`) and their pockets as the library takes them.
-    Returns pos, pocket_x and pocket_of normalised, B, N, F, M, P, zt (z on the device), max_atoms and max_pocket (M if None)."""
-    pos = _dev_f32(pos, 'pos')
+def _ligand_pocket_args(where: str, pos, lig_ptr, z, mol: dict, fields, pocket_x, pocket_ptr, pocket_of, max_atoms, max_pocket,
+                        san: Optional[dict] = None, san_fields=(), stack: bool = False):
+    """What `relax`, the vina calls and `pose_check` share: perceived ligands (the `fields` of `mol`, the `san_fields` of `san`: see
+    `_mol_args`) and their pockets as the library takes them; M = 0 atoms in P = 0 pockets with every pocket_of -1 is no pocket at
+    all.  `stack`: pos is K poses [K,N,3], or one as [N,3], and is returned as [K,N,3]; else it must be [N,3].  Returns pos,
+    pocket_x and pocket_of normalised, B, N, F, M, P, cap_bonds, zt (z on the device), max_atoms and max_pocket (M if None)."""
+    if not (isinstance(pos, torch.Tensor) and pos.dim() in ((2, 3) if stack else (2,)) and pos.shape[-1] == 3):
+        raise KpdError(f'{where}: pos must be {"[K,N,3] or " if stack else ""}[N,3], got {tuple(getattr(pos, "shape", ()))}')
+    pos = _dev_f32(pos[None] if stack and pos.dim() == 2 else pos, 'pos')
     B = _offsets(lig_ptr, 'lig_ptr')
-    _mol_fields(where, mol, fields)
+    N, F = pos.shape[-2], len(z)
+    cap_bonds = _mol_args(where, mol, fields, B, N, san, san_fields)
     P = _offsets(pocket_ptr, f'{where}: pocket_ptr', 'P')
     pocket_of = _per_entry(pocket_of, f'{where}: pocket_of', B, 'ligand', contiguous=True)
     pocket_x = _dev_f32(pocket_x, 'pocket_x')
-    N, F, M = pos.shape[0], len(z), pocket_x.shape[0]
-    if (pos.shape != (N, 3) or F < 1 or mol['elem'].numel() != N or mol['bond_ptr'].numel() != B + 1 or mol['status'].numel() != B or
-            pocket_x.shape != (M, 3)):
-        raise KpdError(f'{where}: pos {tuple(pos.shape)}, {B} ligands, {F} classes, pocket_x {tuple(pocket_x.shape)}, {P} pockets do not '
-                       f'match each other or the perceived molecules')
-    max_atoms = int(max_atoms)
-    if not 1 <= max_atoms <= MOL_MAX_ATOMS:
-        raise KpdError(f'{where}: max_atoms {max_atoms} must be 1 .. {MOL_MAX_ATOMS}')
-    zt = torch.tensor(list(map(int, z)), dtype=torch.int32, device=pos.device)
-    return pos, pocket_x, pocket_of, B, N, F, M, P, zt, max_atoms, M if max_pocket is None else int(max_pocket)
+    M, max_atoms = pocket_x.shape[0], int(max_atoms)
+    if (stack and pos.shape[0] < 1) or F < 1 or pocket_x.shape != (M, 3) or not 1 <= max_atoms <= MOL_MAX_ATOMS:
+        raise KpdError(f'{where}: pos {tuple(pos.shape)} must hold at least one pose, z at least one class (got {F}), pocket_x '
+                       f'{tuple(pocket_x.shape)} be [M,3] and max_atoms {max_atoms} be 1 .. {MOL_MAX_ATOMS}')
+    return (pos, pocket_x, pocket_of, B, N, F, M, P, cap_bonds, _class_table(pos.device, z), max_atoms,
+            M if max_pocket is None else int(max_pocket))
 
 
 def relax_params(**params) -> KpdRelaxParams:
@@ -1478,10 +1411,9 @@ def relax(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_vdw: torch.Tensor, mo
     pocket_ptr [P+1] and pocket_of [B] int32 (-1: no pocket); all GPU tensors.  max_atoms / max_pocket: host-known upper bounds
     that size the kernel's LDS (a larger ligand is left out, a larger pocket is merely read from global memory).  Returns
     (pos_out [N,3] fp32, report [B,12] float64 with the columns RELAX_REPORT, status [B] int32).  No host synchronisation."""
-    pos, pocket_x, pocket_of, B, N, F, M, P, zt, max_atoms, max_pocket = _ligand_pocket_args(
+    pos, pocket_x, pocket_of, B, N, F, M, P, cap_bonds, zt, max_atoms, max_pocket = _ligand_pocket_args(
         'relax', pos, lig_ptr, z, mol, ('elem', 'bonds', 'bond_ptr', 'status'), pocket_x, pocket_ptr, pocket_of, max_atoms, max_pocket)
     lig_vdw, pocket_vdw = _dev_f32(lig_vdw, 'lig_vdw'), _dev_f32(pocket_vdw, 'pocket_vdw')
-    cap_bonds = mol['bonds'].numel() // 2
     if lig_vdw.shape != (F, 2) or pocket_vdw.shape != (M, 2):
         raise KpdError(f'relax: lig_vdw {tuple(lig_vdw.shape)} must be [{F},2] and pocket_vdw {tuple(pocket_vdw.shape)} [{M},2]')
     p = relax_params(**params)
@@ -1538,17 +1470,15 @@ def vina_score(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch.Te
     [B] int32 (-1: no pocket), lig_type_in: None or [N] int32 whose entries >= 0 replace the perceived flags; all GPU tensors.
     Returns a dict of device tensors: report [B,8] float64 (columns VINA_REPORT), status [B], lig_type [N] and, on request, grad
     [N,3] and atom_score [N] float64.  No host synchronisation."""
-    pos, pocket_x, pocket_of, B, N, F, M, P, zt, max_atoms, max_pocket = _ligand_pocket_args(
+    pos, pocket_x, pocket_of, B, N, F, M, P, cap_bonds, zt, max_atoms, max_pocket = _ligand_pocket_args(
         'vina_score', pos, lig_ptr, z, mol, ('elem', 'bonds', 'order', 'bond_ptr', 'status'), pocket_x, pocket_ptr, pocket_of, max_atoms,
         max_pocket)
     lig_radius, pocket_radius = _dev_f32(lig_radius, 'lig_radius'), _dev_f32(pocket_radius, 'pocket_radius')
     pocket_type = _per_entry(pocket_type, 'vina_score: pocket_type', M, 'pocket atom')
     if lig_type_in is not None:
         lig_type_in = _per_entry(lig_type_in, 'vina_score: lig_type_in', N, 'ligand atom')
-    cap_bonds = mol['order'].numel()
-    if lig_radius.shape != (F,) or pocket_radius.shape != (M,) or mol['bonds'].numel() != 2 * cap_bonds:
-        raise KpdError(f'vina_score: lig_radius {tuple(lig_radius.shape)} must be [{F}], pocket_radius {tuple(pocket_radius.shape)} [{M}] '
-                       f'and bonds hold two atoms for each of the {cap_bonds} orders')
+    if lig_radius.shape != (F,) or pocket_radius.shape != (M,):
+        raise KpdError(f'vina_score: lig_radius {tuple(lig_radius.shape)} must be [{F}] and pocket_radius {tuple(pocket_radius.shape)} [{M}]')
     p = vina_params(**params)
     dev = pos.device
     out = dict(report=torch.empty(B, 8, dtype=torch.float64, device=dev), status=torch.empty(B, dtype=torch.int32, device=dev),
@@ -1594,20 +1524,17 @@ def vina_minimize(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch
     `vina_score`, with `mol` also holding 'frag'; max_rotors (0 .. 64): the rotors beyond it are frozen, 0 = rigid bodies only.
     Returns (pos_out [N,3] fp32, report [B,16] float64 with the columns VINA_MIN_REPORT, status [B] int32).  No host
     synchronisation."""
-    pos, pocket_x, pocket_of, B, N, F, M, P, zt, max_atoms, max_pocket = _ligand_pocket_args(
+    pos, pocket_x, pocket_of, B, N, F, M, P, cap_bonds, zt, max_atoms, max_pocket = _ligand_pocket_args(
         'vina_minimize', pos, lig_ptr, z, mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'), pocket_x, pocket_ptr, pocket_of,
         max_atoms, max_pocket)
     lig_radius, pocket_radius = _dev_f32(lig_radius, 'lig_radius'), _dev_f32(pocket_radius, 'pocket_radius')
     pocket_type = _per_entry(pocket_type, 'vina_minimize: pocket_type', M, 'pocket atom')
     if lig_type_in is not None:
         lig_type_in = _per_entry(lig_type_in, 'vina_minimize: lig_type_in', N, 'ligand atom')
-    cap_bonds = mol['order'].numel()
     max_rotors = int(max_rotors)
-    if (lig_radius.shape != (F,) or pocket_radius.shape != (M,) or mol['bonds'].numel() != 2 * cap_bonds or mol['frag'].numel() != N or
-            not 0 <= max_rotors <= VINA_MIN_MAX_ROTORS):
+    if lig_radius.shape != (F,) or pocket_radius.shape != (M,) or not 0 <= max_rotors <= VINA_MIN_MAX_ROTORS:
         raise KpdError(f'vina_minimize: lig_radius {tuple(lig_radius.shape)} must be [{F}], pocket_radius {tuple(pocket_radius.shape)} '
-                       f'[{M}], frag hold {N} labels, bonds two atoms for each of the {cap_bonds} orders, and max_rotors {max_rotors} '
-                       f'be 0 .. {VINA_MIN_MAX_ROTORS}')
+                       f'[{M}] and max_rotors {max_rotors} be 0 .. {VINA_MIN_MAX_ROTORS}')
     p = vina_min_params(**params)
     dev = pos.device
     pos_out = torch.empty_like(pos)
@@ -1654,7 +1581,7 @@ def vina_dock(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch.Ten
     fp32 (rows of a mode that does not exist are the input rows), n_found [B], report [B,n_modes,8] float64 (columns
     VINA_DOCK_REPORT), chain_pos [n_chains,N,3], chain_report [B,n_chains,10] (columns VINA_DOCK_CHAIN_REPORT), status [B].  No host
     synchronisation."""
-    pos, pocket_x, pocket_of, B, N, F, M, P, zt, max_atoms, max_pocket = _ligand_pocket_args(
+    pos, pocket_x, pocket_of, B, N, F, M, P, cap_bonds, zt, max_atoms, max_pocket = _ligand_pocket_args(
         'vina_dock', pos, lig_ptr, z, mol, ('elem', 'frag', 'bonds', 'order', 'bond_ptr', 'status'), pocket_x, pocket_ptr, pocket_of,
         max_atoms, max_pocket)
     lig_radius, pocket_radius = _dev_f32(lig_radius, 'lig_radius'), _dev_f32(pocket_radius, 'pocket_radius')
@@ -1664,14 +1591,13 @@ def vina_dock(pos: torch.Tensor, lig_ptr: torch.Tensor, z, lig_radius: torch.Ten
         lig_type_in = _per_entry(lig_type_in, 'vina_dock: lig_type_in', N, 'ligand atom')
     if lig_id is not None:
         lig_id = _per_entry(lig_id, 'vina_dock: lig_id', B, 'ligand', contiguous=True)
-    cap_bonds = mol['order'].numel()
     max_rotors, n_chains, n_steps, seed = int(max_rotors), int(n_chains), int(n_steps), int(seed)
     n_modes = min(9, n_chains) if n_modes is None else int(n_modes)
-    if (lig_radius.shape != (F,) or pocket_radius.shape != (M,) or mol['bonds'].numel() != 2 * cap_bonds or mol['frag'].numel() != N or
-            not 0 <= max_rotors <= VINA_MIN_MAX_ROTORS or box_lo.shape != (B, 3) or box_hi.shape != (B, 3)):
+    if (lig_radius.shape != (F,) or pocket_radius.shape != (M,) or not 0 <= max_rotors <= VINA_MIN_MAX_ROTORS or
+            box_lo.shape != (B, 3) or box_hi.shape != (B, 3)):
         raise KpdError(f'vina_dock: lig_radius {tuple(lig_radius.shape)} must be [{F}], pocket_radius {tuple(pocket_radius.shape)} '
-                       f'[{M}], frag hold {N} labels, bonds two atoms for each of the {cap_bonds} orders, max_rotors {max_rotors} '
-                       f'be 0 .. {VINA_MIN_MAX_ROTORS}, box_lo {tuple(box_lo.shape)} and box_hi {tuple(box_hi.shape)} be [{B},3]')
+                       f'[{M}], max_rotors {max_rotors} be 0 .. {VINA_MIN_MAX_ROTORS}, box_lo {tuple(box_lo.shape)} and box_hi '
+                       f'{tuple(box_hi.shape)} be [{B},3]')
     if not (1 <= n_chains <= VINA_DOCK_MAX_CHAINS and 1 <= n_modes <= n_chains and n_steps >= 0 and 0 <= seed < 1 << 64):
         raise KpdError(f'vina_dock: n_chains {n_chains} must be 1 .. {VINA_DOCK_MAX_CHAINS}, n_modes {n_modes} 1 .. n_chains, n_steps '
                        f'{n_steps} >= 0, seed {seed} in [0, 2^64)')

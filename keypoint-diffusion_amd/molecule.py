@@ -173,6 +173,11 @@ def _pocket_of(pocket_of, B: int, n_pockets: int, dev) -> torch.Tensor:
     return host.to(torch.int32).to(dev)
 
 
+def _zeros(dev, **spec) -> Dict[str, torch.Tensor]:
+    """What a call on no ligands returns: name -> zeros of (dtype, *shape) on `dev`."""
+    return {name: torch.zeros(shape, dtype=dtype, device=dev) for name, (dtype, *shape) in spec.items()}
+
+
 class Molecules:
     """The perceived molecules of a batch of ligands, as device tensors:
     elem [N] (element class of every atom), valence [N], frag [N] (rank of the atom's fragment inside its ligand), bonds [3N,2]
@@ -198,6 +203,12 @@ class Molecules:
     def __len__(self) -> int:
         return int(self.lig_ptr.numel()) - 1
 
+    def _mol(self) -> Dict[str, torch.Tensor]:
+        """These molecules as the `mol` the `hip` wrappers take: the entries of `hip.MOL_LENGTHS`.  A wrapper checks and reads the
+        entries it names, so the same dict serves all of them."""
+        return dict(elem=self.elem, valence=self.valence, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr,
+                    status=self.status)
+
     @classmethod
     def from_sdf(cls, files, lig_elements: Sequence[str], remove_hydrogen: bool = True, allowed_bonds: Optional[Dict[str, object]] = None,
                  device='cuda') -> 'Molecules':
@@ -213,8 +224,7 @@ class Molecules:
             raise hip.KpdError('these Molecules carry no coordinates: build them with build_molecules')
         if len(self) == 0:
             return []
-        mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
-        text, ptr, status = hip.sdf_emit(self.pos, self.lig_ptr, self.lig_elements, mol, largest_only=largest_frag)
+        text, ptr, status = hip.sdf_emit(self.pos, self.lig_ptr, self.lig_elements, self._mol(), largest_only=largest_frag)
         bad = [(b, s) for b, s in enumerate(status) if s]
         if bad and strict:
             raise hip.KpdError(f'sdf: no block for ligand {bad[0][0]} (status {bad[0][1]}: 1 non-finite coordinate, 2 coordinate wider '
@@ -256,12 +266,9 @@ class Molecules:
         if self.lig_elements is None or self.bonds is None:
             raise hip.KpdError('these Molecules carry no bond graph: build them with build_molecules')
         if len(self) == 0:
-            dev = self.lig_ptr.device
-            return dict(key=torch.zeros(0, dtype=torch.int64, device=dev), fp=torch.zeros(0, int(nbits) // 32, dtype=torch.int32, device=dev),
-                        status=torch.zeros(0, dtype=torch.int32, device=dev))
-        mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
+            return _zeros(self.lig_ptr.device, key=(torch.int64, 0), fp=(torch.int32, 0, int(nbits) // 32), status=(torch.int32, 0))
         z = [ATOMIC_NUMBERS.get(el, 0) for el in self.lig_elements]
-        return hip.mol_keys(self.lig_ptr, z, mol, largest_only=largest_frag, with_orders=with_orders, radius=radius, nbits=nbits)
+        return hip.mol_keys(self.lig_ptr, z, self._mol(), largest_only=largest_frag, with_orders=with_orders, radius=radius, nbits=nbits)
 
     def keys(self, largest_frag: bool = True, with_orders: bool = True) -> torch.Tensor:
         """One int64 per ligand that is equal for isomorphic bond graphs and different otherwise (the key of include/kpd.h,
@@ -312,13 +319,10 @@ class Molecules:
         dev = stack.device
         if len(self) == 0:
             shape = (0, K, K) if pairs else (0, K)
-            f64 = torch.zeros(shape, dtype=torch.float64, device=dev)
-            return PoseRMSD(dict(rmsd=f64, plain=f64.clone(), nodes=torch.zeros(shape, dtype=torch.int64, device=dev),
-                                 status=torch.zeros(0, dtype=torch.int32, device=dev),
-                                 **({} if pairs else dict(map=torch.zeros(K, 0, dtype=torch.int32, device=dev)))), bool(pairs))
-        mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, bond_ptr=self.bond_ptr, status=self.status)
+            return PoseRMSD(_zeros(dev, rmsd=(torch.float64, *shape), plain=(torch.float64, *shape), nodes=(torch.int64, *shape),
+                                   status=(torch.int32, 0), **({} if pairs else dict(map=(torch.int32, K, 0)))), bool(pairs))
         z = [ATOMIC_NUMBERS.get(el, 0) for el in self.lig_elements]
-        out = hip.pose_rmsd(self.lig_ptr, z, mol, stack, None if pairs else ref, pairs=pairs, largest_only=largest_frag, skip_h=skip_h,
+        out = hip.pose_rmsd(self.lig_ptr, z, self._mol(), stack, None if pairs else ref, pairs=pairs, largest_only=largest_frag, skip_h=skip_h,
                             max_nodes=max_nodes, bond_label=bond_label, atom_label=atom_label)
         return PoseRMSD(out, bool(pairs))
 
@@ -382,12 +386,11 @@ class Molecules:
         mass, mass_h = mass_table(self.lig_elements, masses)
         dev = self.pos.device
         if len(self) == 0:
-            i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
-            out = dict(order_k=i32(0), bond_flags=i32(0), valence_k=i32(0), atom_h=i32(0), atom_flags=i32(0), desc_i=i32(0, 10),
-                       desc_f=torch.zeros(0, 2, dtype=torch.float64, device=dev), valid=i32(0), status=i32(0))
+            i32 = (torch.int32, 0)
+            out = _zeros(dev, order_k=i32, bond_flags=i32, valence_k=i32, atom_h=i32, atom_flags=i32, desc_i=(torch.int32, 0, 10),
+                         desc_f=(torch.float64, 0, 2), valid=i32, status=i32)
         else:
-            mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
-            out = hip.mol_sanitize(self.pos, self.lig_ptr, z, allowed, mass, mass_h, mol, largest_only=largest_frag)
+            out = hip.mol_sanitize(self.pos, self.lig_ptr, z, allowed, mass, mass_h, self._mol(), largest_only=largest_frag)
         san = Sanitized(self, out, z, largest_frag)
         if allowed_bonds is not None and 'H' in allowed_bonds:
             san.molecules._allowed_h = _class_tables(['H'], allowed_bonds)[1][0]
@@ -430,10 +433,9 @@ class Molecules:
         lig_vdw = torch.tensor(vdw_table(self.lig_elements, vdw), dtype=torch.float32, device=dev).reshape(-1, 2)
         rows = [r for els in pocket_elements for r in vdw_table(els, vdw)]
         pocket_vdw = torch.tensor(rows, dtype=torch.float32, device=dev).reshape(-1, 2)
-        mol = dict(elem=self.elem, bonds=self.bonds, bond_ptr=self.bond_ptr, status=self.status)
         if len(self) == 0:
-            return Relaxed(self, self.pos, torch.zeros(0, 12, dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev))
-        pos, report, status = hip.relax(self.pos, self.lig_ptr, z, lig_vdw, mol, pocket_x, pocket_vdw, pocket_ptr, pocket_of,
+            return Relaxed(self, self.pos, **_zeros(dev, report=(torch.float64, 0, 12), status=(torch.int32, 0)))
+        pos, report, status = hip.relax(self.pos, self.lig_ptr, z, lig_vdw, self._mol(), pocket_x, pocket_vdw, pocket_ptr, pocket_of,
                                         max_atoms=max_atoms, max_pocket=max(sizes, default=0), **params)
         return Relaxed(self, pos, report, status)
 
@@ -471,12 +473,10 @@ class Molecules:
         per-atom scores; `params`: w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond, w_rot, r_c."""
         (pocket_x, pocket_ptr, pocket_of, sizes, z, max_atoms, dev, lig_radius, pocket_radius, pocket_types,
          lig_types) = self._vina_inputs('vina_score', 'scoring', pocket_pos, pocket_elements, pocket_of, radii, pocket_types, lig_types)
-        mol = dict(elem=self.elem, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
         if len(self) == 0:
-            empty = dict(report=torch.zeros(0, 8, dtype=torch.float64, device=dev), status=torch.zeros(0, dtype=torch.int32, device=dev),
-                         lig_type=torch.zeros(0, dtype=torch.int32, device=dev))
+            empty = _zeros(dev, report=(torch.float64, 0, 8), status=(torch.int32, 0), lig_type=(torch.int32, 0))
             return VinaScores(self, empty, pocket_types)
-        out = hip.vina_score(self.pos, self.lig_ptr, z, lig_radius, mol, pocket_x, pocket_radius, pocket_types, pocket_ptr, pocket_of,
+        out = hip.vina_score(self.pos, self.lig_ptr, z, lig_radius, self._mol(), pocket_x, pocket_radius, pocket_types, pocket_ptr, pocket_of,
                              lig_type_in=lig_types, grad=grad, atom_score=grad, max_atoms=max_atoms, max_pocket=max(sizes, default=0),
                              **params)
         return VinaScores(self, out, pocket_types)
@@ -493,11 +493,9 @@ class Molecules:
         `vina_score` and w_intra, gtol, max_step, max_iters."""
         (pocket_x, pocket_ptr, pocket_of, sizes, z, max_atoms, dev, lig_radius, pocket_radius, pocket_types,
          lig_types) = self._vina_inputs('vina_minimize', 'minimisation', pocket_pos, pocket_elements, pocket_of, radii, pocket_types, lig_types)
-        mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
         if len(self) == 0:
-            return VinaMinimized(self, self.pos, torch.zeros(0, 16, dtype=torch.float64, device=dev),
-                                 torch.zeros(0, dtype=torch.int32, device=dev), pocket_types)
-        pos, report, status = hip.vina_minimize(self.pos, self.lig_ptr, z, lig_radius, mol, pocket_x, pocket_radius, pocket_types, pocket_ptr,
+            return VinaMinimized(self, self.pos, pocket_types=pocket_types, **_zeros(dev, report=(torch.float64, 0, 16), status=(torch.int32, 0)))
+        pos, report, status = hip.vina_minimize(self.pos, self.lig_ptr, z, lig_radius, self._mol(), pocket_x, pocket_radius, pocket_types, pocket_ptr,
                                                 pocket_of, lig_type_in=lig_types, max_atoms=max_atoms, max_pocket=max(sizes, default=0),
                                                 max_rotors=hip.VINA_MIN_MAX_ROTORS if max_rotors is None else max_rotors, **params)
         return VinaMinimized(self, pos, report, status, pocket_types)
@@ -548,18 +546,16 @@ class Molecules:
          lig_types) = self._vina_inputs('vina_dock', 'docking', pocket_pos, pocket_elements, pocket_of, radii, pocket_types, lig_types)
         n_chains = int(n_chains)
         n_modes = min(9, n_chains) if n_modes is None else int(n_modes)
-        mol = dict(elem=self.elem, frag=self.frag, bonds=self.bonds, order=self.order, bond_ptr=self.bond_ptr, status=self.status)
         if len(self) == 0:
-            i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
-            f64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
-            empty = dict(pos=torch.zeros(max(n_modes, 1), 0, 3, device=dev), n_found=i32(0), report=f64(0, max(n_modes, 1), 8),
-                         chain_pos=torch.zeros(max(n_chains, 1), 0, 3, device=dev), chain_report=f64(0, max(n_chains, 1), 10), status=i32(0))
+            m, c, f32, f64 = max(n_modes, 1), max(n_chains, 1), torch.float32, torch.float64
+            empty = _zeros(dev, pos=(f32, m, 0, 3), n_found=(torch.int32, 0), report=(f64, 0, m, 8), chain_pos=(f32, c, 0, 3),
+                           chain_report=(f64, 0, c, 10), status=(torch.int32, 0))
             z3 = torch.zeros(0, 3, device=dev)
             return VinaDocked(self, empty, pocket_types, (z3, z3))
         lo, hi = self._dock_box(pocket_of, len(pocket_pos), box, autobox_ligand, autobox_add)
         if lig_ids is not None:
             lig_ids = torch.as_tensor(lig_ids).to(torch.int32).to(dev).flatten()
-        out = hip.vina_dock(self.pos, self.lig_ptr, z, lig_radius, mol, pocket_x, pocket_radius, pocket_types, pocket_ptr, pocket_of, lo, hi,
+        out = hip.vina_dock(self.pos, self.lig_ptr, z, lig_radius, self._mol(), pocket_x, pocket_radius, pocket_types, pocket_ptr, pocket_of, lo, hi,
                             n_chains=n_chains, n_steps=n_steps, n_modes=n_modes, seed=seed, lig_id=lig_ids, lig_type_in=lig_types,
                             max_atoms=max_atoms, max_pocket=max(sizes, default=0),
                             max_rotors=hip.VINA_MIN_MAX_ROTORS if max_rotors is None else max_rotors, **params)
@@ -664,8 +660,7 @@ class Sanitized:
             return []
         if not m.lig_ptr.is_cuda:
             raise hip.KpdError(f'smiles: ligands must live on the GPU (got {m.lig_ptr.device}); there is no CPU implementation')
-        mol = dict(elem=m.elem, frag=m.frag, bonds=m.bonds, bond_ptr=m.bond_ptr, status=m.status)
-        text, ptr, status = hip.mol_smiles(m.lig_ptr, self._z, m.lig_elements, mol, self._out, largest_only=largest, aromatic=not kekule)
+        text, ptr, status = hip.mol_smiles(m.lig_ptr, self._z, m.lig_elements, m._mol(), self._out, largest_only=largest, aromatic=not kekule)
         if any(s & hip.SMI_CAPACITY for s in status):
             raise hip.KpdError('smiles: text buffer too small (internal sizing error)')
         return ['' if status[b] else text[ptr[b]:ptr[b + 1]].decode('ascii') for b in range(len(status))]
@@ -727,13 +722,12 @@ class Sanitized:
         hip.pose_check_params(**thresholds)         # refuse bad thresholds before anything is launched
         K = int(stack.shape[0])
         if len(m) == 0:
-            i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
-            empty = dict(fail=i32(0, K), report=torch.zeros(0, K, len(hip.CHECK_REPORT), dtype=torch.float64, device=dev),
-                         counts=i32(0, K, len(hip.CHECK_COUNTS)), atom_fail=i32(K, 0), status=i32(0, K))
+            i32 = torch.int32
+            empty = _zeros(dev, fail=(i32, 0, K), report=(torch.float64, 0, K, len(hip.CHECK_REPORT)), counts=(i32, 0, K, len(hip.CHECK_COUNTS)),
+                           atom_fail=(i32, K, 0), status=(i32, 0, K))
             return PoseChecks(empty, self.valid)
         n_max = m._max_atoms if m._max_atoms is not None else hip.MOL_MAX_ATOMS
-        mol = dict(elem=m.elem, frag=m.frag, bonds=m.bonds, bond_ptr=m.bond_ptr, status=m.status)
-        out = hip.pose_check(m.lig_ptr, self._z, mol, self._out, stack, lig_radius, largest_only=largest,
+        out = hip.pose_check(m.lig_ptr, self._z, m._mol(), self._out, stack, lig_radius, largest_only=largest,
                              max_atoms=max(1, min(n_max, hip.MOL_MAX_ATOMS)), **pocket, **thresholds)
         return PoseChecks(out, self.valid)
 
@@ -842,13 +836,12 @@ class Hydrogenated:
         dev = m.pos.device
         self.heavy = m
         if len(m) == 0:
-            i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
-            out = dict(lig_ptr=i32(1), pos=torch.zeros(0, 3, device=dev), elem=i32(0), valence=i32(0), frag=i32(0), bonds=i32(0, 2),
-                       order=i32(0), bond_ptr=i32(1), summary=i32(0, 4), parent=i32(0), source=i32(0), n_h=i32(0), status=i32(0))
+            i32 = (torch.int32, 0)
+            out = _zeros(dev, lig_ptr=(torch.int32, 1), pos=(torch.float32, 0, 3), elem=i32, valence=i32, frag=i32, bonds=(torch.int32, 0, 2),
+                         order=i32, bond_ptr=(torch.int32, 1), summary=(torch.int32, 0, 4), parent=i32, source=i32, n_h=i32, status=i32)
             sizes: Optional[List[int]] = []
         else:
-            mol = dict(elem=m.elem, frag=m.frag, bonds=m.bonds, bond_ptr=m.bond_ptr, status=m.status)
-            out = hip.mol_add_hs(m.pos, m.lig_ptr, z, allowed, h_class, mol, san._out, largest_only=san.largest_frag)
+            out = hip.mol_add_hs(m.pos, m.lig_ptr, z, allowed, h_class, m._mol(), san._out, largest_only=san.largest_frag)
             sizes = (out['lig_ptr'][1:] - out['lig_ptr'][:-1]).cpu().tolist()
             for k in ('pos', 'elem', 'valence', 'frag', 'parent', 'source'):       # rows sized for ligands that were copied through
                 out[k] = out[k][:sum(sizes)]
