@@ -267,9 +267,11 @@ struct ChunkRing2 {
 // A node's S scalars live on its four lanes (x[nt][r] = s[node][16 nt + 4 (lane >> 4) + r]), so a layer norm is in-lane sums plus
 // two cross-lane adds.
 template <int NTS>
-__device__ __forceinline__ void lanes_ln_stats(const v4f (&x)[NTS], float inv_n, float pad, float &mean, float &rstd) {
-    // inv_n = 1 / n_hidden_scalars; `pad` trailing registers hold 0 (narrower models on these kernels): their (0 - mean)^2 is taken out
-    // of the variance and their weight / bias are 0.  pad = 0 is bit-identical to the fixed-width form.
+__device__ __forceinline__ void lanes_ln_stats(const v4f (&x)[NTS], int q, float inv_n, float pad, float &mean, float &rstd) {
+    // inv_n = 1 / n_hidden_scalars; `pad` trailing columns hold 0 (narrower models on these kernels) and their weight / bias are 0: the
+    // variance runs over the model's own columns 16 nt + 4 q + r < 16 NTS - pad.  (Summing all registers and taking pad * mean^2 out
+    // afterwards cancels: at n_hidden_scalars = 1 the true variance is 0 and what was left was rounding of either sign, a NaN under the
+    // root once it passed -1e-5.)  pad = 0 is bit-identical to the fixed-width form.
     float sum = 0.0f;
 #pragma unroll
     for (int nt = 0; nt < NTS; ++nt) sum += (x[nt][0] + x[nt][1]) + (x[nt][2] + x[nt][3]);
@@ -277,16 +279,27 @@ __device__ __forceinline__ void lanes_ln_stats(const v4f (&x)[NTS], float inv_n,
     sum += __shfl_xor(sum, 32);
     mean = sum * inv_n;
     float var = 0.0f;
+    if (pad == 0.0f) {
 #pragma unroll
-    for (int nt = 0; nt < NTS; ++nt)
+        for (int nt = 0; nt < NTS; ++nt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float d = x[nt][r] - mean;
-            var = fmaf(d, d, var);
-        }
+            for (int r = 0; r < 4; ++r) {
+                const float d = x[nt][r] - mean;
+                var = fmaf(d, d, var);
+            }
+    } else {
+        const int n = 16 * NTS - (int)pad;
+#pragma unroll
+        for (int nt = 0; nt < NTS; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float d = 16 * nt + 4 * q + r < n ? x[nt][r] - mean : 0.0f;
+                var = fmaf(d, d, var);
+            }
+    }
     var += __shfl_xor(var, 16);
     var += __shfl_xor(var, 32);
-    rstd = 1.0f / sqrtf((var - pad * mean * mean) * inv_n + 1e-5f);
+    rstd = 1.0f / sqrtf(var * inv_n + 1e-5f);
 }
 
 // one 16-column tile of the normalised row (columns 16 nt + 4 q ..): what lanes_layernorm leaves in x[nt]
@@ -299,7 +312,7 @@ template <int NTS>
 __device__ __forceinline__ void lanes_layernorm(v4f (&x)[NTS], const float *__restrict__ lw, const float *__restrict__ lb, int q, float inv_n,
                                                 float pad) {
     float mean, rstd;
-    lanes_ln_stats<NTS>(x, inv_n, pad, mean, rstd);
+    lanes_ln_stats<NTS>(x, q, inv_n, pad, mean, rstd);
 #pragma unroll
     for (int nt = 0; nt < NTS; ++nt) x[nt] = lanes_ln_tile(x[nt], lw, lb, nt, q, mean, rstd);
 }

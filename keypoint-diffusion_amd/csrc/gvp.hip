@@ -76,7 +76,8 @@ extern "C" kpd_status kpd_gvp_create(const kpd_gvp_config *cfg, kpd_gvp **out) {
                 "update_kp=0 with more than one convolution cannot run in the reference (gvp.py:501, 536)");
     KPD_REQUIRE(cfg->n_message_gvps >= 1 && cfg->n_message_gvps <= GVP_MAX_CHAIN && cfg->n_update_gvps >= 1 &&
                     cfg->n_update_gvps <= GVP_MAX_CHAIN && cfg->n_noise_gvps >= 1 && cfg->n_noise_gvps <= GVP_MAX_CHAIN,
-                KPD_ERR_INVALID, "GVP chain lengths must be within 1..%d", GVP_MAX_CHAIN);
+                KPD_ERR_INVALID, "GVP chain lengths n_message_gvps=%d / n_update_gvps=%d / n_noise_gvps=%d must be within 1..%d",
+                cfg->n_message_gvps, cfg->n_update_gvps, cfg->n_noise_gvps, GVP_MAX_CHAIN);
     // n_lig_scalars 65 .. 255 (the encoder input n_lig_scalars + 1 fits its 256 columns) run exact fp32 only
     KPD_REQUIRE(cfg->n_lig_scalars >= 1 && cfg->n_lig_scalars <= 255 && cfg->n_kp_scalars >= 1 && cfg->n_kp_scalars <= 256,
                 KPD_ERR_INVALID, "n_lig_scalars=%d / n_kp_scalars=%d outside 1 .. 255 / 1 .. 256", cfg->n_lig_scalars, cfg->n_kp_scalars);

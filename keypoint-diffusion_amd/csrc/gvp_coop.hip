@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256, 2) void k_gvp_node_coop(GvpNodePair p) {
     v4f res[TPW], acc[TPW];
     {
         float mean, rstd;
-        lanes_ln_stats<NTS>(x, a.ln_inv_n, a.ln_pad, mean, rstd);
+        lanes_ln_stats<NTS>(x, q, a.ln_inv_n, a.ln_pad, mean, rstd);
 #pragma unroll
         for (int nt = 0; nt < NTS; ++nt) x[nt] = lanes_ln_tile(x[nt], a.ln1_w, a.ln1_b, nt, q, mean, rstd);
 #pragma unroll

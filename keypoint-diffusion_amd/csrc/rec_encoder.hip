@@ -452,7 +452,8 @@ extern "C" kpd_status kpd_recenc_create(const kpd_recenc_config *cfg, kpd_recenc
     KPD_REQUIRE(cfg->n_keypoints >= 1 && cfg->n_keypoints * cfg->out_scalar_size <= KPE_MAX, KPD_ERR_INVALID, "n_keypoints=%d",
                 cfg->n_keypoints);
     KPD_REQUIRE(cfg->n_message_gvps >= 1 && cfg->n_message_gvps <= GVP_MAX_CHAIN && cfg->n_update_gvps >= 1 &&
-                    cfg->n_update_gvps <= GVP_MAX_CHAIN, KPD_ERR_INVALID, "GVP chain lengths must be within 1..%d", GVP_MAX_CHAIN);
+                    cfg->n_update_gvps <= GVP_MAX_CHAIN, KPD_ERR_INVALID, "GVP chain lengths n_message_gvps=%d / n_update_gvps=%d must be within 1..%d",
+                cfg->n_message_gvps, cfg->n_update_gvps, GVP_MAX_CHAIN);
     KPD_REQUIRE(cfg->n_rr_convs >= 0 && cfg->n_rr_convs <= 16 && cfg->n_rk_convs >= 1 && cfg->n_rk_convs <= 16, KPD_ERR_INVALID,
                 "conv counts");
     KPD_REQUIRE(cfg->message_norm_mode >= 0 && cfg->message_norm_mode <= 2, KPD_ERR_INVALID, "message_norm_mode");

@@ -1,4 +1,6 @@
 """Shared helpers for the test-suite: batch construction and product <-> oracle conversion."""
+import contextlib
+
 import torch
 
 from keypoint_diffusion_amd import graph as G
@@ -29,6 +31,36 @@ def to_obatch(g: G.HeteroBatch) -> OBatch:
         s, d = g.edges(etype=et)
         ob.edges[et] = (cpu(s), cpu(d))
     return ob
+
+
+def to_obatch64(g: G.HeteroBatch) -> OBatch:
+    """`to_obatch` with positions, scalars and vectors in float64: the input of a float64 oracle run."""
+    ob = to_obatch(g)
+    for d in (ob.x, ob.h, ob.v):
+        for nt in d:
+            d[nt] = d[nt].double()
+    return ob
+
+
+@contextlib.contextmanager
+def float64_oracle():
+    """The oracle makes its own constants (zero vectors, the rbf centres) in torch's default dtype: float64 while it runs in float64,
+    so that nothing in a high-precision reference is rounded to fp32 on the way."""
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        yield
+    finally:
+        torch.set_default_dtype(old)
+
+
+def tile_spans(dst: torch.Tensor, n_dst: int, tile: int = 64) -> torch.Tensor:
+    """[n_dst] how many `tile`-edge tiles the run of in-edges of each destination touches when the edges of one type are stored
+    destination-major (0 for a destination without in-edge): a run [lo, hi) touches tiles lo / tile .. (hi - 1) / tile."""
+    deg = torch.bincount(dst, minlength=n_dst)
+    hi = torch.cumsum(deg, 0)
+    lo = hi - deg
+    return torch.where(deg > 0, (hi - 1) // tile - lo // tile + 1, torch.zeros_like(deg))
 
 
 def fixed_encode(g: G.HeteroBatch, n_vec=None) -> G.HeteroBatch:
@@ -91,8 +123,10 @@ def assert_param_grads(model, ref_grads: dict, tol: float, min_checked: int = 10
     cancelling sum over all edges)."""
     worst, checked = [], 0
     for n, p in model.named_parameters():
+        if p.numel() == 0:                                            # GVPDropout's dummy_param: nothing to compare
+            continue
         r = ref_grads[n]
-        if r is None or float(r.abs().max()) < 1e-10:                # fc_dst: built, never applied (:190-191); a saturated tanh head
+        if r is None or float(r.abs().max()) < 1e-10:               # fc_dst: built, never applied (:190-191); a saturated tanh head
             assert p.grad is None or float(p.grad.abs().max()) <= 1e-9, n
             continue
         assert p.grad is not None, n
