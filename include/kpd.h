@@ -1095,6 +1095,94 @@ kpd_status kpd_pose_rmsd(const int32_t *lig_ptr, int32_t n_atoms, int32_t B, con
                          int32_t skip_h, const float *ref_pos, const float *pos, int32_t K, int32_t pairs, int64_t max_nodes,
                          double *rmsd, double *plain, int32_t *map, int64_t *nodes, int32_t *status, void *scratch, void *stream);
 
+/* Substructure search on the sanitised molecules (csrc/substruct.hip): which ligands contain a query graph, at which atoms, and
+ * (for typing tables) which row of a first-match-wins list an atom falls under.  Stands where upstream's users call
+ * mol.HasSubstructMatch / GetSubstructMatches with a SMARTS pattern one molecule at a time, and under what rests on that: functional
+ * group counts, structural alerts, Crippen-style atom typing.  RDKit's matcher cannot be restated here, so THIS COMMENT IS THE
+ * DEFINITION, down to the order of every choice (tests/match_ref.py restates it); it is NOT RDKit's matcher and is not compared with
+ * it.  The labels are those kpd_mol_sanitize wrote: its aromaticity applies, not RDKit's; there are no charges, no stereo and no
+ * ring sizes.  No query text reaches the device: a query is compiled on the host (smarts.py, a SMARTS subset) into the int32 table
+ * below, and that table is the interface.  The library ships no Crippen, QED or PAINS table.  Inputs are never written.
+ * Scope S, Z(a), "both ends in S" and the conditions of "no molecule" are those of kpd_mol_keys / kpd_mol_sanitize (below, at the
+ *   status).  The neighbours of an atom are its partners over bonds with both ends in S, in ascending index; deg(a) their number.
+ * Labels of an atom a of S: z = Z(a) if it is in 0 .. 127, else 0; aromatic = atom_flags bit 1; ring = atom_flags bit 0;
+ *   D = the neighbours with Z != 1; H = atom_h[a] + the neighbours with Z = 1; X = deg(a) + atom_h[a]; v = valence_k[a] +
+ *   atom_h[a]; x = the bonds of a (in S) with bond_flags bit 0.  D, H, X, v and x are clamped at 15 (KPD_Q_TOP): 15 means 15 or more.
+ * Labels of a bond: kind = 3 (aromatic) if bond_flags bit 2 is set, whatever order_k says, else order_k - 1 (0, 1, 2); ring =
+ *   bond_flags bit 0; its bit number in a bond mask is kind + 4 ring.
+ * The table, int32 words:
+ *   [0] = KPD_Q_MAGIC, [1] = P, the rows (1 .. KPD_Q_PATTERNS), [2] = the length of the table in words, [3] = 0;
+ *   [4 + p], p < P: the word at which row p starts; the rows follow each other without gaps in ascending p, the last ends the table.
+ *   A row: {na (atoms, 1 .. KPD_Q_ATOMS), nc (closure bonds; na - 1 + nc <= KPD_Q_BONDS), nalt (alternatives, 1 .. 128), 0},
+ *     then na atom records {parent p(t) (-1 for t = 0, else 0 .. t - 1), the mask of the bond to the parent (0 for t = 0), the
+ *       first alternative of the atom, their number (1 .. KPD_Q_ALT)}: the atoms are in depth-first order;
+ *     then nc closure records {s, t, mask, 0} with s < t < na: the bonds of the query that are no parent bond;
+ *     then nalt alternatives of 16 words {Z[4], cls, D, H, X, v, x, need[2], forbid[2], 0, 0}: Z is a set of 128 bits (bit z of
+ *       word z >> 5); cls bit 0 / 1 = an aliphatic / aromatic atom is allowed, bit 2 / 3 = an atom outside / inside a ring is
+ *       allowed; D .. x are sets of 16 bits, bit k for the label k; need and forbid name LOWER rows of the table, -1 = none.
+ *   An alternative holds at atom a iff a's z is in Z, its aromatic and ring labels are allowed by cls, each of D .. x has the bit
+ *   of a's label, the anchor bit (below) of a is set for every row it needs and for no row it forbids.  The predicate of a query
+ *   atom holds iff one of its alternatives does.  (A SMARTS "$(...)" is a `need` of the row compiled from its inside, "!$(...)"
+ *   a `forbid`; negation of everything else is in the sets.)
+ * Embedding of row q in a ligand: an injective map f of q's atoms into S such that the predicate of every t holds at f(t) and every
+ *   bond (s, t) of the query (parent bonds and closures) lands on a bond (f(s), f(t)) whose bit is in its mask.  Non-induced: bonds
+ *   between images that the query does not mention are allowed.
+ * Search, per (ligand, row, anchor a in S): nothing to do unless the predicate of atom 0 holds at a; then f(0) = a, nodes = 0.  At
+ *   depth t = 1 .. na - 1 the candidates are the neighbours v of f(p(t)), in ascending index, that are no image yet, whose bond to
+ *   f(p(t)) is in the parent mask, at which the predicate of t holds, and that have, for every closure (s, t), a bond to f(s) in
+ *   its mask.  For each candidate: nodes += 1; if nodes > max_nodes this search stops with what it has found (status bit 1);
+ *   else f(t) = v, and at t = na - 1 this is an embedding, otherwise the search descends; when the candidates of a depth are
+ *   used up it returns to the depth above, and ends when those of depth 1 are.  A query of one atom has its one embedding at
+ *   every anchor whose predicate holds, and no nodes.
+ *   Mode KPD_MATCH_ANCHORS: a search stops at its first embedding.  Mode KPD_MATCH_ALL: it enumerates all of them.
+ *   Anchor bit (a, p): some embedding of row p with f(0) = a was found.  The rows are processed in ascending order; the bits of a
+ *   row are complete before a higher row reads them.
+ * Typing: type_group [P] (-1 or anything outside 0 .. G-1: the row takes no part; else its group g) and value [P] fp64.  For a
+ *   group g and an atom of S: type = the lowest row of g whose anchor bit the atom has, -1 if none.  type_sum[b][g] = the sum of
+ *   value[type] over the typed atoms of S in ascending atom index, from 0.0, one rounded fp64 addition at a time; untyped[b][g] =
+ *   the atoms of S without a type.
+ *
+ * kpd_mol_match: lig_ptr [B+1], elem / frag [n_atoms], bond_ij [cap_bonds,2], bond_ptr [B+1], mol_status [B] as kpd_mol_perceive
+ *   wrote them; order_k / bond_flags [cap_bonds], valence_k / atom_h / atom_flags [n_atoms] and san_status [B] (its `status`) as
+ *   kpd_mol_sanitize wrote them with the same largest_only, or with largest_only = 0; z [F]; type_group, value as above or NULL
+ *   with G = 0; all device pointers.  The table comes twice: table_host, the table_words words in HOST memory, which are checked
+ *   before anything is launched, and table, the same words in device memory, which the kernel reads (the caller keeps the two
+ *   equal).  KPD_ERR_INVALID, and no launch, for a malformed table: a bad head, counts beyond the limits, a row whose length is
+ *   not what its counts need, a parent that is not lower, a closure that is not s < t < na, alternatives out of range, a
+ *   mask with bits it cannot have, a reference to a row that is not lower; also for a mode other than 0 / 1 and max_nodes < 1.
+ *   Out (device), W = ceil(P / 32): anchor [n_atoms, W] uint32 (bit p & 31 of word p >> 5 of row a = the anchor bit (a, p));
+ *   hits [B, P] = the anchors of row p in ligand b; first_map [B, P, KPD_Q_ATOMS] int32 or NULL: the first embedding found
+ *   from the lowest anchor that has one, as global atom rows, -1 beyond the row's atoms and without a hit; with KPD_MATCH_ALL
+ *   also n_embed [B, P] int64, the embeddings (as maps: a benzene ring holds c1ccccc1 twelve times), and cover [n_atoms, W]
+ *   uint32: bit p of atom a = a is the image of some query atom in some embedding of row p (both may be NULL otherwise).  Where a
+ *   search stopped at max_nodes, hits, anchor, n_embed and cover are LOWER BOUNDS, and what rows that reference such a row
+ *   report follows the bits that were found.  With G > 0: atom_type [G, n_atoms] int32, type_sum [B, G] fp64, untyped [B, G].
+ *   status [B]: bit 0 = no molecule (san_status bit 0, mol_status bits 0, 1 or 3, more than 256 atoms, an empty S, an element or
+ *   fragment out of range, a bond outside the ligand, twice, of an order_k outside 1 .. 3, a seventh neighbour, or, on an atom
+ *   of S, atom_h outside 0 .. 9 or a negative valence_k): zeros everywhere, first_map -1, atom_type -1; atoms of no ligand and
+ *   atoms outside S read the same.  bit 1 = some search of this ligand stopped at max_nodes, informational.
+ *   One wave per ligand, lane l runs the searches of the anchors l, l + 64, ..; the rows in ascending order, one barrier between
+ *   rows: one launch whatever B and P are, and the fills of the outputs (three to eight); no scratch, no host synchronisation,
+ *   no float atomics.  Nothing is read or written out of bounds.  A ligand's results are bitwise independent of the rest of the
+ *   batch, of cap_bonds and of the repeat; what row p reports is independent of the rows it does not reference (through any
+ *   chain), type_sum included. */
+#define KPD_Q_ATOMS 16
+#define KPD_Q_BONDS 24
+#define KPD_Q_ALT 8
+#define KPD_Q_PATTERNS 512
+#define KPD_Q_TOP 15
+#define KPD_Q_MAGIC 0x4b505101
+enum { KPD_MATCH_ANCHORS = 0, KPD_MATCH_ALL = 1 };
+enum { KPD_MATCH_NO_MOLECULE = 1, KPD_MATCH_MAX_NODES = 2 };
+kpd_status kpd_mol_match(const int32_t *lig_ptr, int32_t n_atoms, int32_t B, const int32_t *elem, int32_t F, const int32_t *z,
+                         const int32_t *frag, const int32_t *bond_ij, const int32_t *order_k, const int32_t *bond_flags,
+                         const int32_t *bond_ptr, int32_t cap_bonds, const int32_t *mol_status, const int32_t *san_status,
+                         const int32_t *valence_k, const int32_t *atom_h, const int32_t *atom_flags, int32_t largest_only,
+                         const int32_t *table_host, const int32_t *table, int32_t table_words, int32_t mode, int64_t max_nodes,
+                         const int32_t *type_group, const double *value, int32_t G, uint32_t *anchor, int32_t *hits,
+                         int32_t *first_map, int64_t *n_embed, uint32_t *cover, int32_t *atom_type, double *type_sum,
+                         int32_t *untyped, int32_t *status, void *stream);
+
 /* Plausibility checks of poses (csrc/pose_check.hip): whether a pose is physically plausible, which no energy, score or RMSD of the
  * calls around it says.  The list follows PoseBusters (Buttenschoen, Morris & Deane 2024): bond lengths and angles in range, no
  * internal clash, flat aromatic rings and double bonds, no clash with the protein, little volume overlap with it.  PoseBusters

@@ -186,6 +186,8 @@ PROTOTYPES = {
     'kpd_pose_rmsd_scratch_bytes': (_I64, [_I32] * 3),
     'kpd_pose_rmsd': (_STATUS, [_P, _I32, _I32, _P, _I32] + [_P] * 4 + [_I32] + [_P] * 3 + [_I32, _I32, _P, _P, _I32, _I32, _I64] +
                       [_P] * 7),
+    'kpd_mol_match': (_STATUS, [_P, _I32, _I32, _P, _I32] + [_P] * 6 + [_I32] + [_P] * 5 + [_I32, _P, _P, _I32, _I32, _I64, _P, _P, _I32] +
+                      [_P] * 10),
     'kpd_pose_check_defaults': (None, [_ref(KpdPoseCheckParams)]),
     'kpd_pose_check': (_STATUS, [_P] + [_I32] * 3 + [_P, _I32] + [_P] * 6 + [_I32] + [_P] * 4 + [_I32, _P, _I32] + [_P] * 4 + [_I32] * 3 +
                        [_P, _ref(KpdPoseCheckParams)] + [_P] * 6),
@@ -1272,6 +1274,62 @@ def pose_rmsd(lig_ptr: torch.Tensor, z, mol: dict, pos: torch.Tensor, ref_pos: O
                               cap_bonds, _ptr(mol['status']), _ptr(bond_label), _ptr(atom_label), int(bool(largest_only)), int(bool(skip_h)),
                               None if pairs else _ptr(ref_pos), _ptr(pos), K, int(pairs), max_nodes, _ptr(out['rmsd']), _ptr(out['plain']),
                               _ptr(out.get('map')), _ptr(out['nodes']), _ptr(out['status']), _ptr(scratch), _stream()))
+    return out
+
+
+MATCH_NO_MOLECULE, MATCH_MAX_NODES = 1, 2                       # status bits of kpd_mol_match
+MATCH_ANCHORS, MATCH_ALL = 0, 1                                 # its modes
+MATCH_Q_ATOMS = 16                                              # KPD_Q_ATOMS: the columns of first_map
+
+
+def mol_match(lig_ptr: torch.Tensor, z, mol: dict, san: dict, patterns, mode: int = MATCH_ANCHORS, max_nodes: int = 65536,
+              want_map: bool = True, type_group=None, value=None, largest_only: bool = False):
+    """Substructure search on a batch of sanitised molecules on the GPU (kpd_mol_match; include/kpd.h states the rule, which is NOT
+    RDKit's matcher).  `mol`: what `mol_perceive` returned, `san`: what `mol_sanitize` returned for it with the same `largest_only` (or
+    over every atom); z: the atomic number of every class; `patterns`: a `smarts.Patterns` (its table is checked on the host and
+    read on the GPU; its rows lifted out of "$(...)" are rows of the outputs like any other).  mode MATCH_ANCHORS: every search
+    stops at its first embedding; MATCH_ALL: all embeddings are counted (n_embed, cover).  type_group [P] (-1: no part in a typing,
+    else the group) and value [P]: a first-match-wins typing table, host sequences or tensors.  Returns a dict of device tensors:
+    anchor [N,W] (int32 words holding the uint32 bits, W = ceil(P / 32)), hits [B,P], status [B] (bits MATCH_*); first_map [B,P,16]
+    with `want_map`; n_embed [B,P] int64 and cover [N,W] with MATCH_ALL; atom_type [G,N], type_sum [B,G] float64 and untyped [B,G]
+    with a typing table.  No host synchronisation once the table is on the device (a typing table given as host data is copied)."""
+    B = _offsets(lig_ptr, 'lig_ptr')
+    N, F = _numel(mol.get('elem')), len(z)
+    cap_bonds = _mol_args('mol_match', mol, ('elem', 'frag', 'bonds', 'bond_ptr', 'status'), B, N,
+                          san, ('order_k', 'bond_flags', 'valence_k', 'atom_h', 'atom_flags', 'status'))
+    mode, max_nodes = int(mode), int(max_nodes)
+    if F < 1 or mode not in (MATCH_ANCHORS, MATCH_ALL) or max_nodes < 1:
+        raise KpdError(f'mol_match: mode={mode} must be MATCH_ANCHORS or MATCH_ALL, max_nodes={max_nodes} >= 1, and there must be atomic '
+                       f'numbers (got {F})')
+    dev = lig_ptr.device
+    host = patterns.host
+    table = patterns.to(dev).table
+    P = patterns.n_rows
+    W = (P + 31) // 32
+    G, tg, val = 0, None, None
+    if type_group is not None:
+        tg_host = torch.as_tensor(type_group).to('cpu', torch.int32).contiguous()
+        if value is None or tg_host.numel() != P or _numel(torch.as_tensor(value)) != P:
+            raise KpdError(f'mol_match: type_group and value must have one entry per row of the table ({P})')
+        G = max(int(tg_host.max()) + 1, 0)
+        tg, val = tg_host.to(dev), torch.as_tensor(value).to(dev, torch.float64).contiguous()
+    zt = _class_table(dev, z)
+    out = dict(anchor=torch.empty(N, W, dtype=torch.int32, device=dev), hits=torch.empty(B, P, dtype=torch.int32, device=dev),
+               status=torch.empty(B, dtype=torch.int32, device=dev))
+    if want_map:
+        out['first_map'] = torch.empty(B, P, MATCH_Q_ATOMS, dtype=torch.int32, device=dev)
+    if mode == MATCH_ALL:
+        out['n_embed'] = torch.empty(B, P, dtype=torch.int64, device=dev)
+        out['cover'] = torch.empty(N, W, dtype=torch.int32, device=dev)
+    if G:
+        out.update(atom_type=torch.empty(G, N, dtype=torch.int32, device=dev), type_sum=torch.empty(B, G, dtype=torch.float64, device=dev),
+                   untyped=torch.empty(B, G, dtype=torch.int32, device=dev))
+    check(lib().kpd_mol_match(_ptr(lig_ptr), N, B, _ptr(mol['elem']), F, _ptr(zt), _ptr(mol['frag']), _ptr(mol['bonds']), _ptr(san['order_k']),
+                              _ptr(san['bond_flags']), _ptr(mol['bond_ptr']), cap_bonds, _ptr(mol['status']), _ptr(san['status']),
+                              _ptr(san['valence_k']), _ptr(san['atom_h']), _ptr(san['atom_flags']), int(bool(largest_only)), _ptr(host),
+                              _ptr(table), host.numel(), mode, max_nodes, _ptr(tg), _ptr(val), G, _ptr(out['anchor']), _ptr(out['hits']),
+                              _ptr(out.get('first_map')), _ptr(out.get('n_embed')), _ptr(out.get('cover')), _ptr(out.get('atom_type')),
+                              _ptr(out.get('type_sum')), _ptr(out.get('untyped')), _ptr(out['status']), _stream()))
     return out
 
 

@@ -43,7 +43,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import hip
+from . import hip, smarts
 
 # atomic numbers of the element symbols a dataset may name (lig_elements / rec_elements of the configs, upstream's allowed_bonds)
 ATOMIC_NUMBERS: Dict[str, int] = {
@@ -615,6 +615,46 @@ class PoseChecks:
         return out
 
 
+class Matches:
+    """What `Sanitized.match` returns, for the user's patterns only (the rows lifted out of "$(...)" are not reported), device
+    tensors: `.hits` [B,n] int32 (atoms that are the image of the pattern's first atom in some embedding), `.has` [B,n] bool,
+    `.first_map` [B,n,16] int32 (the first embedding from the lowest such atom, as atom rows of the batch; -1 beyond the pattern's
+    atoms and without a hit), `.n_embed` [B,n] int64 (embeddings as maps, a benzene ring holds c1ccccc1 twelve times; None unless
+    `all_embeddings`), `.status` [B] (bits: 1 no molecule, 2 some search stopped at max_nodes: the counts are then lower bounds).
+    The rule is include/kpd.h's, NOT RDKit's matcher."""
+
+    def __init__(self, patterns: 'smarts.Patterns', out: Dict[str, torch.Tensor]):
+        self.patterns, self.names, self._out = patterns, patterns.names, out
+        rows = patterns.row_index(out['hits'].device)
+        self.hits, self.status = out['hits'][:, rows], out['status']
+        self.has = self.hits > 0
+        self.first_map = out['first_map'][:, rows] if 'first_map' in out else None
+        self.n_embed = out['n_embed'][:, rows] if 'n_embed' in out else None
+
+    def _bit(self, words: torch.Tensor, p: int) -> torch.Tensor:
+        r = self.patterns.rows[p]
+        return ((words[:, r >> 5] >> (r & 31)) & 1) != 0
+
+    def anchor_atoms(self, p: int) -> torch.Tensor:
+        """[N] bool: the atom is the image of the first atom of pattern p in some embedding."""
+        return self._bit(self._out['anchor'], p)
+
+    def cover_atoms(self, p: int) -> torch.Tensor:
+        """[N] bool: the atom is the image of any atom of pattern p in any embedding (needs `all_embeddings=True`)."""
+        if 'cover' not in self._out:
+            raise hip.KpdError('cover_atoms needs match(..., all_embeddings=True)')
+        return self._bit(self._out['cover'], p)
+
+    def table(self) -> Dict[str, list]:
+        """lig_idx, then one column of hit counts per pattern name; ligands without a molecule have no row."""
+        keep = ((self.status.cpu() & hip.MATCH_NO_MOLECULE) == 0).nonzero().flatten().tolist()
+        hits = self.hits.cpu()
+        out: Dict[str, list] = dict(lig_idx=keep)
+        for k, name in enumerate(self.names):
+            out[name] = hits[keep, k].tolist()
+        return out
+
+
 class Sanitized:
     """What `Molecules.sanitize` returns: `.molecules` (a `Molecules` whose `order` is order_k and whose `valence` is valence_k, so
     `.sdf()`, `.keys()`, `.relax()`, `.vina_score()`, `.vina_minimize()` and `.vina_dock()` work unchanged on the Kekule orders),
@@ -739,6 +779,53 @@ class Sanitized:
             if s:
                 first.setdefault(s, b)
         return sorted(first.values())
+
+    def _patterns(self, patterns) -> 'smarts.Patterns':
+        if isinstance(patterns, smarts.Patterns):
+            return patterns
+        return smarts.compile(patterns)
+
+    def _match(self, pats, mode: int, max_nodes: int, want_map: bool = True, type_group=None, value=None) -> Dict[str, torch.Tensor]:
+        m = self.molecules
+        if m.bonds is None:
+            raise hip.KpdError('these Molecules carry no bond graph: build them with build_molecules')
+        if not m.lig_ptr.is_cuda:
+            raise hip.KpdError(f'match: ligands must live on the GPU (got {m.lig_ptr.device}); there is no CPU implementation')
+        return hip.mol_match(m.lig_ptr, self._z, m._mol(), self._out, pats, mode=mode, max_nodes=max_nodes, want_map=want_map,
+                             type_group=type_group, value=value, largest_only=self.largest_frag)
+
+    def match(self, patterns, all_embeddings: bool = False, max_nodes: int = 65536) -> 'Matches':
+        """Substructure search on the GPU (`kpd_mol_match`): `patterns` is a `smarts.Patterns`, a SMARTS string or a list of them
+        (strings are compiled on the spot; `smarts` states the supported subset).  The queries are matched on THIS library's
+        sanitised labels: its aromaticity, no charges, no stereo, no ring sizes.  The rule is include/kpd.h's; it is NOT RDKit's
+        matcher and is not compared with it.  `all_embeddings`: count every embedding (`.n_embed`, `.cover_atoms`) instead of
+        stopping each search at its first.  The scope is the one these molecules were sanitised with.  The first use of a `Patterns` on
+        a device copies its table and row numbers there; after that a call makes no host synchronisation."""
+        pats = self._patterns(patterns)
+        out = self._match(pats, hip.MATCH_ALL if all_embeddings else hip.MATCH_ANCHORS, max_nodes)
+        return Matches(pats, out)
+
+    def has_substructure(self, pattern: str) -> torch.Tensor:
+        """[B] bool: the ligand contains the SMARTS query (`match`, whose limits apply: NOT RDKit's matcher)."""
+        pats = self._patterns(pattern)
+        if pats.n != 1:
+            raise ValueError('has_substructure takes one pattern; use match() for several')
+        return self._match(pats, hip.MATCH_ANCHORS, 65536, want_map=False)['hits'][:, pats.rows[0]] > 0
+
+    def atom_types(self, patterns, values=None):
+        """First-match-wins atom typing by a caller-supplied table (the form of a Crippen table; the library ships none): the
+        type of an atom is the first pattern of `patterns` it is the first atom of, -1 if none.  `values`: one number per
+        pattern (default 0).  Returns (atom_type [N] int32 as the index of the user's pattern, -1 untyped or out of scope;
+        type_sum [B] float64, the values of a ligand's typed atoms added in ascending atom index; untyped [B] int32)."""
+        pats = self._patterns(patterns)
+        values = [0.0] * pats.n if values is None else [float(v) for v in values]
+        if len(values) != pats.n:
+            raise ValueError(f'atom_types: {len(values)} values for {pats.n} patterns')
+        group, value = [-1] * pats.n_rows, [0.0] * pats.n_rows
+        for k, r in enumerate(pats.rows):
+            group[r], value[r] = 0, values[k]
+        out = self._match(pats, hip.MATCH_ANCHORS, 65536, want_map=False, type_group=group, value=value)
+        return pats.user_index(out['atom_type'].device)[out['atom_type'][0].long()], out['type_sum'][:, 0], out['untyped'][:, 0]
 
     def descriptors(self) -> Dict[str, torch.Tensor]:
         """Per ligand, as [B] device tensors: n_heavy, n_h, hbd, hba, n_rot, n_rings, n_arom_rings, n_arom_atoms, lipinski4 (how
@@ -1124,7 +1211,7 @@ def training_keys_from_sdf(files, lig_elements: Sequence[str], largest_frag: boo
 def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_counts: Optional[torch.Tensor] = None,
                     allowed_bonds: Optional[Dict[str, object]] = None, connectivity_thresh: float = 0.5, device=None,
                     train_keys: Optional[torch.Tensor] = None, set_metrics: bool = False, sanitize: bool = False,
-                    masses: Optional[Dict[str, float]] = None, smiles: bool = False, pose_check: bool = False) -> Dict[str, float]:
+                    masses: Optional[Dict[str, float]] = None, smiles: bool = False, pose_check: bool = False, groups=False) -> Dict[str, float]:
     """The part of `ModelAnalyzer.sample_and_analyze` (analysis/metrics.py:60-100) that needs no rdkit: `samples` is the list
     of {'positions', 'features'} dicts `_sample` returns, one per pocket; the result is `Molecules.metrics` over all of them
     and, with `set_metrics=True`, `Molecules.set_metrics` as well (uniqueness, novelty against `train_keys` if given, and the
@@ -1138,8 +1225,12 @@ def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_count
     of every ligand's largest fragment (upstream's `Chem.MolToSmiles(largest_mol)`; `Sanitized.smiles`, NOT RDKit's canonical
     form), '' for a ligand without a molecule.
     `pose_check=True` (implies `sanitize=True`): the result also has 'plausible', the fraction of the sanitised, connected ligands
-    (those uniqueness is counted over) whose sampled pose passes `Sanitized.pose_check` without a pocket: NOT PoseBusters' number."""
-    sanitize = sanitize or smiles or pose_check
+    (those uniqueness is counted over) whose sampled pose passes `Sanitized.pose_check` without a pocket: NOT PoseBusters' number.
+    `groups=True` or a `smarts.Patterns` (implies `sanitize=True`): the result also has 'group_frequency', name -> the fraction of the
+    ligands that sanitised (`validity`'s numerator) that contain the query, for `smarts.FUNCTIONAL_GROUPS` or the given patterns
+    (`Sanitized.match`: NOT RDKit's matcher).  Every other key and value is what it is without."""
+    want_groups = groups is not False and groups is not None
+    sanitize = sanitize or smiles or pose_check or want_groups
     lig_pos, lig_feat = [], []
     for rec in samples:
         lig_pos.extend(rec['positions'])
@@ -1160,6 +1251,13 @@ def analyze_samples(samples: List[dict], lig_elements: Sequence[str], type_count
             keep = san.valid & (n > 0) & ((m.status & hip.MOL_BAD_SEGMENT) == 0) & (m.summary[:, 2].double() / n.clamp(min=1) >= connectivity_thresh)
             n_keep = int(keep.sum())
             out['plausible'] = float(san.pose_check().passed[:, 0][keep].double().mean()) if n_keep else 0.0
+        if want_groups:
+            pats = groups if isinstance(groups, smarts.Patterns) else smarts.compile(smarts.FUNCTIONAL_GROUPS)
+            m = san.molecules
+            ok = san.valid & ((m.lig_ptr[1:] - m.lig_ptr[:-1]) > 0) & ((m.status & hip.MOL_BAD_SEGMENT) == 0)
+            n_ok = int(ok.sum())
+            has = san.match(pats).has[ok].double().sum(0).cpu().tolist() if n_ok else [0.0] * pats.n
+            out['group_frequency'] = {name: has[k] / n_ok if n_ok else 0.0 for k, name in enumerate(pats.names)}
         return out
     out = mols.metrics(type_counts, connectivity_thresh)
     if set_metrics:
