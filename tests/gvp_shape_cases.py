@@ -7,7 +7,9 @@ before they compare, so a changed generator fails loudly instead of quietly test
 
 The reference everywhere is oracle/gvp.py / oracle/rec_encoder.py run in float64 (weights, positions, features, v_0, t and the
 oracle's own constants), so it is a high-precision one and not a second fp32 rounding of the same sums; gradients are torch autograd
-through it.  References are computed once (lru_cache) and never written to afterwards."""
+through it.  References are computed once (lru_cache) and never written to afterwards.
+
+The denoiser batches (the edge lists of oracle.egnn.lig_edges, the same for both denoisers) also serve egnn_shape_cases.py."""
 import functools
 import math
 
@@ -239,8 +241,38 @@ def prop_b300(st):
     assert den_batch(B300).batch_size == 300 > 256 and st['ll']['E'] == 600 and st['kl']['E'] == 300 * 6 * 2
 
 
+# ---- 4. node counts on and one past the row blocks of the EGNN denoiser's node-side kernels (egnn_shape_cases.py): 32 rows of the node
+# update, 64 of the projection launch, 8 / 16 / 4 of the trainer's LayerNorm backward, k_dx_gather and k_segsum264.  (n_kp, n_lig)
+NODES = {
+    _batch('n_kp64_lig32', hand=((64, 32, 3),), seed=622): (64, 32),
+    _batch('n_kp65_lig33', hand=((65, 33, 3),), seed=1229): (65, 33),
+    _batch('n_kp32_lig64', hand=((32, 64, 3),), seed=639): (32, 64),
+    _batch('n_kp33_lig65', hand=((33, 65, 3),), seed=630): (33, 65),
+}
+# one-atom ligands only: no ll edge in any complex while every keypoint keeps its one kl edge
+ONE_ATOM = _batch('one_atom_ligs', [26, 19, 30], [1, 1, 1], seed=31)
+
+
+def prop_nodes(bname, st):
+    g = den_batch(bname)
+    assert (g.num_nodes('kp'), g.num_nodes('lig')) == NODES[bname] and g.batch_size == 1
+    assert st['kk']['E'] == 3 * NODES[bname][0] and st['kl']['E'] == st['lk']['E'] == 5 * NODES[bname][0] and st['ll']['E'] > 0
+
+
+def node_coverage():
+    """The total keypoint and ligand node counts of the node-count batches."""
+    return {nk for nk, _ in NODES.values()}, {nl for _, nl in NODES.values()}
+
+
+def prop_one_atom(st):
+    g = den_batch(ONE_ATOM)
+    assert g.batch_num_nodes('lig').tolist() == [1, 1, 1] and st['ll']['E'] == 0
+    assert st['kl']['E'] == st['lk']['E'] == g.num_nodes('kp') == 75 and st['kl']['deg'].tolist() == [26, 19, 30]
+
+
 PROPS = {DENSE_RAD: prop_dense_rad, LIG230: prop_lig230, KP600: prop_kp600, EMPTY_KK: prop_empty_kk, ISOLATED: prop_isolated,
-         B1: prop_b1, B300: prop_b300, **{b: functools.partial(prop_tile, b) for b in TILE}}
+         B1: prop_b1, B300: prop_b300, ONE_ATOM: prop_one_atom, **{b: functools.partial(prop_tile, b) for b in TILE},
+         **{b: functools.partial(prop_nodes, b) for b in NODES}}
 
 
 @functools.lru_cache(maxsize=None)
